@@ -14,7 +14,15 @@ dL/dimage = rand(H, W, 3; seed 1); at N > 1 followed by the excha
 RCCL (data parallel by camera view).  The scene is the synthetic config-3 scene of SURVEY.md 8d (seed 0),
 inputs resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the line: `value` (Mpix/s), `ms_per_step` (one timed step), the
+workload and its counts, and `pipeline_roofline` (computed from `ms_per_step`, no run of its own).
+  --dump-outputs DIR  after the timed steps, the arrays the timed path returned in its last step as DIR/<name>.npy (float32):
+                the image of every view and the six parameter gradients (a fixed, seeded sample of rows / pixels where the
+                whole would exceed 64 MB, the sampled indices beside them as float64).  Same arguments, same inputs.
+  --full        everything below as well: the per-stage calibration pass and the dominant call bracketed inside the timed
+                region, the CPU baseline, and the extras measured after the timed region.
+
+Extra objects on the line with --full:
   roofline      the dominant kernel's algorithmic HBM bytes per launch / its average duration (HIP events recorded on the
                 launch stream inside the timed region) against the 8 TB/s HBM peak; `traffic` from profiles/ PMC data.
   cpu_baseline  the CPU oracle (oracle/torch_port.py, the reference's PyTorch CPU path restated) timed on this box's
@@ -22,6 +30,8 @@ Extra objects on the line:
   sustained     >= 1 s of back-to-back steps after the timed region: ms/step mean, min and max over 10 windows.
   three_call_sequence  the same step through the reference's own three calls (build_sigma_from_params, evaluate_sh, render).
   waiting_path  the same step through the call that waits for every frame's pair count (the reference-style call).
+  stages, valu  the per-stage breakdown of the calibration pass; the dominant raster kernel's VALU figures from profiles/.
+  host_queue_ms the host's time to queue one step.
   N = 1 extras  (outside the timed region; --no-extras skips them) forward_only (the reference's FPS protocol,
                 scripts/render_trained.py:319-381: frame by frame, and software-pipelined render_frames), train_step
                 (render + L1/SSIM loss + backward + clip + Adam, scripts/train.py:446-569), config4 (3 M Gaussians, a training iteration
@@ -281,6 +291,50 @@ def host_queue_ms(render_pass, ops, fence, steps=100):
     return (t1 - t0) / steps * 1e3
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all, half for the images, half for the gradients
+_DUMP_HALF = DUMP_BYTES // 2 - (1 << 12)          # (less room for the .npy headers)
+
+
+def _sample_rows(n, row_bytes, budget, seed):
+    """Sorted indices of a fixed, seeded sample of n rows that fits in `budget` bytes (with its float64 index), or None when
+    all n rows fit."""
+    if n * row_bytes <= budget:
+        return None
+    k = budget // (row_bytes + 8)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(path, images, grads):
+    """What the timed path returned in its last step: images = one (H, W, 3) tensor per view, grads = {name: gradient or None}.
+    Written as <path>/<name>.npy in float32; an array too large for its half of DUMP_BYTES is replaced by a seeded sample of its
+    rows (pixels of the images, Gaussians of the gradients), with the sampled indices as image_pixels.npy / grad_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    if images:
+        H, W, _ = images[0].shape
+        pix = _sample_rows(H * W, 12 * len(images), _DUMP_HALF, seed=0)
+        for k, img in enumerate(images):
+            a = img.detach().float().cpu().numpy()
+            if pix is not None:
+                a = a.reshape(H * W, 3)[pix]
+            out["image" if len(images) == 1 else f"image_view{k}"] = a
+        if pix is not None:
+            out["image_pixels"] = pix.astype(np.float64)
+    grads = {k: g for k, g in grads.items() if g is not None}
+    if grads:
+        n = next(iter(grads.values())).shape[0]
+        row_bytes = sum(4 * g[0].numel() for g in grads.values())
+        rows = _sample_rows(n, row_bytes, _DUMP_HALF, seed=1)
+        for k, g in grads.items():
+            a = g.detach().float().cpu().numpy()
+            out["grad_" + k] = a if rows is None else a[rows]
+        if rows is not None:
+            out["grad_rows"] = rows.astype(np.float64)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(out)
+
+
 def timed(fn, steps, fence):
     fence()
     t0 = time.perf_counter()
@@ -297,8 +351,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", type=int, default=3, help="synthetic scene of SURVEY.md §8d (default 3: 1M @ 1080p)")
     ap.add_argument("--forward-only", action="store_true", help="time forward-only inference instead of fwd+bwd")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip forward_only / train_step / config5 / sustained")
+    ap.add_argument("--full", action="store_true", help="also the calibration pass, roofline / stages / valu, the CPU baseline, "
+                    "host_queue_ms and the extras (sustained, waiting_path, forward_only, train_step, config4/5/6, the N > 1 exchange split)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the image(s) and gradients of the last timed step to "
+                    "DIR/<name>.npy (float32, at most 64 MB: seeded samples of larger arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip forward_only / train_step / config5 / sustained")
     ap.add_argument("--cpu-rows", type=int, default=256)
     ap.add_argument("--cpu-budget", type=int, default=150, help="seconds allowed for the CPU baseline leg")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
@@ -315,6 +373,8 @@ def main():
     ap.add_argument("--wait-counts", action="store_true", help="every forward pass waits for its pair count (exact buffers) instead of "
                     "sizing them from earlier frames (ops.deferred_checks)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args, sys.argv[1:]))
@@ -325,9 +385,9 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     if args.launch_check:
         raise SystemExit(launch_check(args, rank, world))
-    # CPU baseline first (rank 0, N = 1 only), before anything touches the GPU, under a time budget
+    # --full: CPU baseline first (rank 0, N = 1 only), before anything touches the GPU, under a time budget
     cb = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         try:
             with _Budget(args.cpu_budget):
                 cb = cpu_baseline(args.config, sample_rows=args.cpu_rows)
@@ -372,6 +432,13 @@ def main():
     cam_args = (H, W, cam["fx"], cam["fy"], cam["cx"], cam["cy"])
 
     info = {}
+    # --dump-outputs: the images of the pass are kept (detached) in the last timed step only -- every other step runs as without it
+    capture, images = [False], []
+
+    def keep(img):
+        if capture[0]:
+            images.append(img.detach())
+        return img
 
     def checked(fn):
         # the way training.Trainer.step renders: no wait for the frame's pair count (buffers sized from earlier frames, SH colour
@@ -381,15 +448,16 @@ def main():
         return fn() if args.wait_counts else ops.run_deferred(fn)
 
     def render_pass():
+        images.clear()
         if need_grad:
             for p in params.values():
                 p.grad = None
             for c in c2ws:                                   # (gradients of the rank's views accumulate in .grad)
-                gs.render_gaussians(*[params[k] for k in NAMES], c, *cam_args).backward(gimg)
+                keep(gs.render_gaussians(*[params[k] for k in NAMES], c, *cam_args)).backward(gimg)
         else:
             with torch.no_grad():
                 for c in c2ws:
-                    gs.render_gaussians(*[params[k] for k in NAMES], c, *cam_args)
+                    keep(gs.render_gaussians(*[params[k] for k in NAMES], c, *cam_args))
 
     def local_step():
         checked(render_pass)
@@ -400,11 +468,12 @@ def main():
             return local_step()
         if mode == "factored":
             def factored_pass():
+                images.clear()
                 for p in params.values():
                     p.grad = None
                 with dp.FactoredExchange(params, world_views=world * vpr) as ex:
                     for c in c2ws:                           # view k's logit gradients are gathered while view k + 1 renders
-                        gs.render_gaussians(*[params[k] for k in NAMES], c, *cam_args).backward(gimg)
+                        keep(gs.render_gaussians(*[params[k] for k in NAMES], c, *cam_args)).backward(gimg)
                 return ex
             # (a repeat would re-issue this rank's collectives: it cannot happen in the timed region -- every rank renders the same view
             # in every step, and the warm-up steps left it the capacity of that view; training.Trainer.step, where views change, agrees
@@ -437,104 +506,106 @@ def main():
         step()
     stats = gs.render_stats()
     p_binned = ops.binned_pairs()            # (list, Gaussian) pairs really binned on this scene (the extras render other scenes later)
-    # Untimed calibration pass with an event pair around EVERY library call: per-stage breakdown, and which call dominates.
-    # (Each event pair costs ~10 us of stream time, so the timed region below only brackets the dominant call.)
-    cal = ops.StageTimer()
-    ops.set_stage_timer(cal)
-    fence()
-    for _ in range(3):
-        step()
-    fence()
-    ops.set_stage_timer(None)
-    cal_stage = cal.totals_ms()
-    dom = max(cal_stage, key=lambda k: cal_stage[k][1])
-    # the dominant call is bracketed in every 8th step of the timed region (an event pair costs ~10 us of stream time and, with the
-    # composite entries, one more library call: the steps in between run exactly as the product does)
-    timer = ops.StageTimer(only=[dom], every=8)
-    ops.set_stage_timer(timer)
+    timer = None
+    if args.full:
+        # Untimed calibration pass with an event pair around EVERY library call: per-stage breakdown, and which call dominates.
+        # (Each event pair costs ~10 us of stream time, so the timed region below only brackets the dominant call.)
+        cal = ops.StageTimer()
+        ops.set_stage_timer(cal)
+        fence()
+        for _ in range(3):
+            step()
+        fence()
+        ops.set_stage_timer(None)
+        cal_stage = cal.totals_ms()
+        dom = max(cal_stage, key=lambda k: cal_stage[k][1])
+        # the dominant call is bracketed in every 8th step of the timed region (an event pair costs ~10 us of stream time and, with the
+        # composite entries, one more library call: the steps in between run exactly as the product does)
+        timer = ops.StageTimer(only=[dom], every=8)
+        ops.set_stage_timer(timer)
     fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        capture[0] = args.dump_outputs is not None and i == args.steps - 1
         step()
     fence()
     elapsed = time.perf_counter() - t0
+    capture[0] = False
     ops.set_stage_timer(None)
     elapsed = max_over_ranks(elapsed)
     ms = elapsed / args.steps * 1e3
+    if args.dump_outputs is not None and rank == 0:      # (at N > 1 the gradients are the exchanged ones, the same on every rank)
+        dump_outputs(args.dump_outputs, list(images), {k: params[k].grad for k in NAMES} if need_grad else {})
+    images.clear()
 
     extras = {}
-    if not args.no_extras:
-        # sustained: >= 1 s of back-to-back steps, ten windows
-        per = max(2, int(math.ceil(100.0 / ms)))
-        wins = [max_over_ranks(timed(step, per, fence)) for _ in range(10)]
-        extras["sustained"] = {"seconds": sum(wins) * per / 1e3, "steps": 10 * per, "ms_per_step": sum(wins) / 10, "min_ms": min(wins),
-                               "max_ms": max(wins), "windows": 10}
-    if not args.wait_counts:
-        extras["host_queue_ms"] = min(host_queue_ms(render_pass, ops, fence) for _ in range(3))
-        extras["host_calls_per_step"] = {"forward": "gsplat_forward_deferred (1 call, 1 arena)", "backward": "gsplat_backward (1 call)"} \
-            if ops._composite else {"forward": "gsplat_project + gsplat_bin + gsplat_rasterize_forward", "backward": "gsplat_rasterize_backward + gsplat_project_backward"}
-    if not args.no_extras and not args.wait_counts and world == 1:
-        # the same step through the call that WAITS for every frame's pair count in the middle of the forward pass (exact buffers,
-        # exceptions raised by the call itself: what a caller that only switched the import gets)
-        def waiting_step():
-            render_pass()
-        for _ in range(3):
-            waiting_step()
-        wms = timed(waiting_step, max(20, args.steps // 4), fence)
-        extras["waiting_path"] = {"what": "render_gaussians() outside deferred_checks(): the host waits for the frame's counters",
-                                  "ms_per_step": wms, "mpix_per_s": H * W / (wms * 1e-3) / 1e6}
-    if world > 1 and need_grad:
-        # the same step without the exchange, and the collectives alone, on buffers of the step's sizes
-        compute_ms = max_over_ranks(timed(local_step, args.steps, fence))
-        small = torch.zeros(11 * N + 64 * 4, dtype=torch.float32, device=dev)        # pos 3 + opacity 1 + scale 3 + quat 4 floats
-        full = torch.zeros(59 * N + 64 * 6, dtype=torch.float32, device=dev) if args.exchange == "allreduce" else None
-        logit = torch.zeros(N, 3, dtype=torch.float32, device=dev)
-        gathered = torch.empty(world * N, 3, dtype=torch.float32, device=dev)
+    if args.full:
+        if not args.no_extras:
+            # sustained: >= 1 s of back-to-back steps, ten windows
+            per = max(2, int(math.ceil(100.0 / ms)))
+            wins = [max_over_ranks(timed(step, per, fence)) for _ in range(10)]
+            extras["sustained"] = {"seconds": sum(wins) * per / 1e3, "steps": 10 * per, "ms_per_step": sum(wins) / 10, "min_ms": min(wins),
+                                   "max_ms": max(wins), "windows": 10}
+        if not args.wait_counts:
+            extras["host_queue_ms"] = min(host_queue_ms(render_pass, ops, fence) for _ in range(3))
+            extras["host_calls_per_step"] = {"forward": "gsplat_forward_deferred (1 call, 1 arena)", "backward": "gsplat_backward (1 call)"} \
+                if ops._composite else {"forward": "gsplat_project + gsplat_bin + gsplat_rasterize_forward", "backward": "gsplat_rasterize_backward + gsplat_project_backward"}
+        if not args.no_extras and not args.wait_counts and world == 1:
+            # the same step through the call that WAITS for every frame's pair count in the middle of the forward pass (exact buffers,
+            # exceptions raised by the call itself: what a caller that only switched the import gets)
+            def waiting_step():
+                render_pass()
+            for _ in range(3):
+                waiting_step()
+            wms = timed(waiting_step, max(20, args.steps // 4), fence)
+            extras["waiting_path"] = {"what": "render_gaussians() outside deferred_checks(): the host waits for the frame's counters",
+                                      "ms_per_step": wms, "mpix_per_s": H * W / (wms * 1e-3) / 1e6}
+        if world > 1 and need_grad:
+            # the same step without the exchange, and the collectives alone, on buffers of the step's sizes
+            compute_ms = max_over_ranks(timed(local_step, args.steps, fence))
+            small = torch.zeros(11 * N + 64 * 4, dtype=torch.float32, device=dev)        # pos 3 + opacity 1 + scale 3 + quat 4 floats
+            full = torch.zeros(59 * N + 64 * 6, dtype=torch.float32, device=dev) if args.exchange == "allreduce" else None
+            logit = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+            gathered = torch.empty(world * N, 3, dtype=torch.float32, device=dev)
 
-        def collectives():
-            if args.exchange == "factored":
-                ws = [dist.all_gather_into_tensor(gathered, logit, async_op=True) for _ in range(vpr)]
-                ws.append(dist.all_reduce(small, async_op=True))
-                for w_ in ws:
-                    w_.wait()
-            else:
-                dist.all_reduce(full)
-        alone_ms = None
-        if args.backend == "nccl":
-            for _ in range(2):
-                collectives()
-            alone_ms = max_over_ranks(timed(collectives, args.steps, fence))
-        # the other form of the exchange, same step (both are built; the first run on real links decides which is the default)
-        alt = "allreduce" if args.exchange == "factored" else "factored"
-        alt_ms = alt_err = None
-        try:
-            for _ in range(2):
-                step(alt)
-            alt_ms = max_over_ranks(timed(lambda: step(alt), args.steps, fence))
-        except Exception as e:                           # never take the headline line down
-            alt_err = f"{type(e).__name__}: {e}"
-        extras["exchange"] = {
-            "mode": args.exchange, "nranks": dist.get_world_size(), "backend": dist.get_backend(),
-            "other_mode": {"mode": alt, "what": info.get(alt), "step_ms": alt_ms, "error": alt_err},
-            "step_ms": ms, "compute_ms": compute_ms, "exchange_ms": ms - compute_ms, "exchange_alone_ms": alone_ms,
-            "allreduce_bytes_per_step": (44 if args.exchange == "factored" else 236) * N,
-            "allgather_bytes_per_rank_per_step": 12 * N * vpr if args.exchange == "factored" else 0,
-            "allgather_bytes_received_per_step": 12 * N * world * vpr if args.exchange == "factored" else 0,
-            "note": "exchange_ms = step - compute: the part of the exchange the step does not hide; the SH rebuild "
-                    "(gsplat_sh_accumulate) counts as exchange"}
-    if world == 1 and rank == 0 and not args.no_extras and args.config == 3 and need_grad:
-        extras.update(single_gpu_extras(gs, ops, params, cam, cam_args, dev, fence))
+            def collectives():
+                if args.exchange == "factored":
+                    ws = [dist.all_gather_into_tensor(gathered, logit, async_op=True) for _ in range(vpr)]
+                    ws.append(dist.all_reduce(small, async_op=True))
+                    for w_ in ws:
+                        w_.wait()
+                else:
+                    dist.all_reduce(full)
+            alone_ms = None
+            if args.backend == "nccl":
+                for _ in range(2):
+                    collectives()
+                alone_ms = max_over_ranks(timed(collectives, args.steps, fence))
+            # the other form of the exchange, same step (both are built; the first run on real links decides which is the default)
+            alt = "allreduce" if args.exchange == "factored" else "factored"
+            alt_ms = alt_err = None
+            try:
+                for _ in range(2):
+                    step(alt)
+                alt_ms = max_over_ranks(timed(lambda: step(alt), args.steps, fence))
+            except Exception as e:                           # never take the headline line down
+                alt_err = f"{type(e).__name__}: {e}"
+            extras["exchange"] = {
+                "mode": args.exchange, "nranks": dist.get_world_size(), "backend": dist.get_backend(),
+                "other_mode": {"mode": alt, "what": info.get(alt), "step_ms": alt_ms, "error": alt_err},
+                "step_ms": ms, "compute_ms": compute_ms, "exchange_ms": ms - compute_ms, "exchange_alone_ms": alone_ms,
+                "allreduce_bytes_per_step": (44 if args.exchange == "factored" else 236) * N,
+                "allgather_bytes_per_rank_per_step": 12 * N * vpr if args.exchange == "factored" else 0,
+                "allgather_bytes_received_per_step": 12 * N * world * vpr if args.exchange == "factored" else 0,
+                "note": "exchange_ms = step - compute: the part of the exchange the step does not hide; the SH rebuild "
+                        "(gsplat_sh_accumulate) counts as exchange"}
+        if world == 1 and rank == 0 and not args.no_extras and args.config == 3 and need_grad:
+            extras.update(single_gpu_extras(gs, ops, params, cam, cam_args, dev, fence))
 
     if rank == 0:
         _, V, P = stats
         HW = H * W
         value = world * vpr * HW * args.steps / elapsed / 1e6
-        stage = dict(cal_stage)
-        stage.update(timer.totals_ms())              # the dominant call: measured live inside the timed region
-        per_stage = {k: {"launches": n, "avg_ms": t / n, "alg_bytes": algorithmic_bytes(k, N, V, P, HW),
-                         "gbs": algorithmic_bytes(k, N, V, P, HW) / (t / n * 1e-3) / 1e9,
-                         "timed_region": k == dom} for k, (n, t) in stage.items()}
-        ach = per_stage[dom]["gbs"]
         fwd_b = 16 * N + 268 * V + 52 * P + 12 * HW
         bwd_b = 236 * N + 272 * V + 80 * P + 20 * HW
         alg_total = (fwd_b + (bwd_b if need_grad else 0)) * vpr
@@ -554,16 +625,23 @@ def main():
                        "counts": "waited for in every forward pass" if args.wait_counts else
                                  "not waited for: buffers from earlier frames, checks once per step (ops.deferred_checks, as Trainer.step)"},
             "fps": world * vpr * args.steps / elapsed, "views_per_rank": vpr,
-            "roofline": {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                         "traffic": pmc_traffic(KERNEL_OF_STAGE[dom], args.config), "kernel": KERNEL_OF_STAGE[dom],
-                         "avg_launch_ms": per_stage[dom]["avg_ms"], "alg_bytes_per_launch": per_stage[dom]["alg_bytes"],
-                         "note": "the raster kernels are VALU-bound, not HBM-bound (DESIGN.md section 6): the HBM fraction of this "
-                                 "kernel is small by construction; pipeline_roofline prices the whole step"},
-            "valu": valu_figures(KERNEL_OF_STAGE[dom], args.config),
             "pipeline_roofline": {"alg_bytes_per_step": alg_total, "achieved": alg_total / (ms * 1e-3) / 1e9,
                                   "frac": alg_total / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "unit": "GB/s"},
-            "stages": per_stage,
         }
+        if args.full:
+            stage = dict(cal_stage)
+            stage.update(timer.totals_ms())              # the dominant call: measured live inside the timed region
+            per_stage = {k: {"launches": n, "avg_ms": t / n, "alg_bytes": algorithmic_bytes(k, N, V, P, HW),
+                             "gbs": algorithmic_bytes(k, N, V, P, HW) / (t / n * 1e-3) / 1e9,
+                             "timed_region": k == dom} for k, (n, t) in stage.items()}
+            ach = per_stage[dom]["gbs"]
+            out["roofline"] = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                               "traffic": pmc_traffic(KERNEL_OF_STAGE[dom], args.config), "kernel": KERNEL_OF_STAGE[dom],
+                               "avg_launch_ms": per_stage[dom]["avg_ms"], "alg_bytes_per_launch": per_stage[dom]["alg_bytes"],
+                               "note": "the raster kernels are VALU-bound, not HBM-bound (DESIGN.md section 6): the HBM fraction of this "
+                                       "kernel is small by construction; pipeline_roofline prices the whole step"}
+            out["valu"] = valu_figures(KERNEL_OF_STAGE[dom], args.config)
+            out["stages"] = per_stage
         out.update(extras)
         if cb is not None:
             out["cpu_baseline"] = cb

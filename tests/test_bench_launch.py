@@ -38,9 +38,9 @@ def test_more_gpus_than_visible_is_refused():
 @pytest.mark.gpu
 def test_two_rank_rehearsal_on_one_gpu_reports_the_exchange():
     """Both ranks on cuda:0, collectives over gloo: the whole N > 1 path of bench.py through the self-launch, with the exchange
-    block on the line."""
+    block on the line (--full: the exchange split is measured after the timed region)."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--backend", "gloo", "--single-device", "--steps", "3", "--warmup", "1",
-                        "--config", "2", "--no-extras"], env=_env(), capture_output=True, text=True, timeout=900)
+                        "--config", "2", "--no-extras", "--full"], env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["exchange"]["nranks"] == 2

@@ -6,5 +6,6 @@ bash tools/profile_all.sh ${tag} all
 bash tools/sq_counters.sh ${tag}
 bash tools/profile_all.sh ${tag}_config5 all --config 5 --steps 4 --warmup 2
 bash tools/profile_all.sh ${tag}_config6 stats --config 6 --steps 10 --warmup 3
-python bench.py --steps 200 --warmup 10 > gpurun_out/${tag}_bench_default.json 2> gpurun_out/${tag}_bench_default.err
+out=${OUT_DIR:-out}; mkdir -p "$out"
+python bench.py --full --steps 200 --warmup 10 > "$out/${tag}_bench_default.json" 2> "$out/${tag}_bench_default.err"
 ls gpurun_out | grep ${tag}
