@@ -11,10 +11,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSPLAT_MI355X_LIB") or os.path.join(_HERE, "csrc", "libgsplat_mi355x.so")
 
 GSPLAT_OK = 0
+GSPLAT_ERR_BAD_ARG = 1
 GSPLAT_SCENE_OK = 0
 GSPLAT_SCENE_ALL_CULLED = 10
 GSPLAT_SCENE_ALL_OFFSCREEN = 11
-ABI_VERSION = 8
+ABI_VERSION = 9
 GSPLAT_PROJECT_COLOUR_FUSED = 1
 GSPLAT_PROJECT_COUNTS_MAPPED = 2
 GSPLAT_PROJECT_SAVE_SH_JACOBIAN = 4

@@ -2722,6 +2722,12 @@ int gsplat_rasterize_backward(int64_t n, int64_t n_binned, const gsplat_view* v,
     return GSPLAT_OK;
 }
 
+// the flag bits the backward entries define; a call with any other bit is refused before it does anything (a library that ignored
+// a flag it does not know would, for GSPLAT_BACKWARD_ACCUMULATE, overwrite where the caller adds)
+static constexpr int32_t PROJECT_BACKWARD_FLAGS = GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_ACCUMULATE;
+static constexpr int32_t BACKWARD_FLAGS = PROJECT_BACKWARD_FLAGS | GSPLAT_BACKWARD_PHASE_RASTER | GSPLAT_BACKWARD_PHASE_PROJECT |
+                                          GSPLAT_BACKWARD_GRAD2D_DIRTY;
+
 static int project_backward_impl(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state,
                                  const float* grad2d, const gsplat_gaussian_grads* out, int32_t flags, void* stream_, const AdamRest* ar) {
     bool fused = false;
@@ -2764,6 +2770,7 @@ static int project_backward_impl(const gsplat_gaussians* g, const float* c2w, co
 
 int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state,
                             const float* grad2d, const gsplat_gaussian_grads* out, int32_t flags, void* stream_) {
+    if (flags & ~PROJECT_BACKWARD_FLAGS) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
     return project_backward_impl(g, c2w, v, project_state, grad2d, out, flags, stream_, nullptr);
 }
 
@@ -2844,6 +2851,7 @@ static int backward_impl(const gsplat_gaussians* g, const float* c2w, const gspl
 int gsplat_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, void* frame, int64_t frame_bytes,
                     int64_t pair_capacity, const float* grad_image, const gsplat_gaussian_grads* out, float* grad_logit,
                     void* det_scratch, int64_t det_scratch_bytes, int32_t flags, void* stream_) {
+    if (flags & ~BACKWARD_FLAGS) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
     return backward_impl(g, c2w, v, frame, frame_bytes, pair_capacity, grad_image, out, grad_logit, det_scratch, det_scratch_bytes, flags,
                          stream_, nullptr);
 }
@@ -2852,6 +2860,7 @@ int gsplat_backward_adam_rest(const gsplat_gaussians* g, const float* c2w, const
                               int64_t pair_capacity, const float* grad_image, const gsplat_gaussian_grads* out, void* det_scratch,
                               int64_t det_scratch_bytes, int32_t flags, const gsplat_adam_group* f_rest, float beta1, float beta2, float eps,
                               void* stream_) {
+    if (flags & ~BACKWARD_FLAGS) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
     if (!g || !f_rest) return fail(GSPLAT_ERR_BAD_ARG, "gaussians / f_rest update is NULL");
     if (flags & (GSPLAT_BACKWARD_PHASE_RASTER | GSPLAT_BACKWARD_PHASE_PROJECT)) return fail(GSPLAT_ERR_BAD_ARG, "the in-place step runs the whole backward pass");
     if (f_rest->n != g->n * 45 || f_rest->step < 1 || !f_rest->param || !f_rest->exp_avg || !f_rest->exp_avg_sq || f_rest->grad_scale ||

@@ -245,13 +245,11 @@ class FactoredExchange:
 
     def __enter__(self):
         from . import ops
-        ops.set_sh_gradient_sink(self)
-        return self
+        self._route = ops.gradient_route(self)
+        return self._route.__enter__()
 
     def __exit__(self, *exc):
-        from . import ops
-        ops.set_sh_gradient_sink(None)
-        return False
+        return self._route.__exit__(*exc)
 
     def pad_views(self, expected):
         """A rank whose pass stopped early (an exception in one of its renders) has issued fewer per-view collectives than its

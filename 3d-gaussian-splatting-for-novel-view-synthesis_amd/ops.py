@@ -14,13 +14,13 @@ PyTorch is plumbing here (device memory, streams, autograd bookkeeping); all ari
 There is no CPU path: CPU tensors, or a missing library, raise.
 """
 import contextlib
+import contextvars
 import ctypes as C
 import weakref
 
-import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, dp
 
 OFFSCREEN_MSG = "All projected points are off-screen"      # reference render.py:236
 
@@ -352,7 +352,7 @@ class _Frame:
     (project_state | bin_state | accum | grad2d, carved by the library); one that went through the separate calls keeps them
     as separate buffers."""
     __slots__ = ("view", "n", "n_pairs", "proj_state", "bin_state", "accum", "fused", "inputs", "c2w", "empty", "grad2d", "sh_jacobian",
-                 "arena", "gaussians", "dirty", "src_ptrs")
+                 "arena", "gaussians", "dirty", "src_ptrs", "route")
 
 
 class _Pending:
@@ -376,7 +376,7 @@ def _new_frame(fused, view, n, pos32, opa32, c2w32, ins, c, d):
     fr = _Frame()
     fr.view, fr.n, fr.fused, fr.c2w, fr.empty, fr.sh_jacobian = view, n, fused, c2w32, False, False
     fr.inputs = dict(pos=pos32, opacity_raw=opa32, **ins)
-    fr.arena = fr.gaussians = fr.proj_state = fr.bin_state = fr.accum = fr.grad2d = None
+    fr.arena = fr.gaussians = fr.proj_state = fr.bin_state = fr.accum = fr.grad2d = fr.route = None
     fr.dirty = False
     # the caller's own SH tensors (before any dtype / layout conversion): what dp.FactoredExchange.owns() compares
     fr.src_ptrs = (c.data_ptr(), d.data_ptr()) if fused else None
@@ -395,6 +395,7 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
     fr = _new_frame(fused, view, n, pos32, opa32, c2w32, ins, c, d)
     if n == 0:      # nothing survives by construction: the reference returns the zero image (render.py:109-112)
         fr.empty = True
+        fr.route = _route_of(fr, False) if need_grad else None
         return None, (torch.zeros((view.H, view.W, 3), dtype=torch.float32, device=dev), fr, _abi.Counts(0, 0, 0, 0, 0, 0))
     g = _make_gaussians(n, pos32, opa32, **ins)
     ckey = capacity_key(dev, view, n)
@@ -412,7 +413,9 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
     pinned, slot = _ws.next_pinned(dev, key, chk)
     ready = _ws.get_event(dev, fresh=deferred, key=key)
     wants_stages = _timer is not None and _timer.wants(_FORWARD_STAGES)
-    if deferred and _composite and not wants_stages:
+    composite = deferred and _composite and not wants_stages
+    fr.route = _route_of(fr, composite) if need_grad else None
+    if composite:
         # ---- the whole forward pass in one call, on one arena
         H, W = view.H, view.W
         flags = (_abi.GSPLAT_FRAME_BACKWARD if need_grad else 0) | (0 if _sh_jacobian else _abi.GSPLAT_FRAME_NO_SH_JACOBIAN)
@@ -523,10 +526,6 @@ def _flat_like(ins):
     return {k: (piece if piece.numel() == v.numel() else piece[:v.numel()]).view(v.shape) for (k, v), piece in zip(ins.items(), parts)}
 
 
-# Data-parallel exchange of the SH gradients in factored form (dp.FactoredExchange): while a sink is installed
-# the render backward of the fused entry hands the 3 colour-logit gradients per Gaussian to the sink instead of
-# computing the 48 SH-coefficient gradients, and returns no gradient for f_dc / f_rest.
-_sh_sink = None
 _deterministic = False
 
 
@@ -539,17 +538,13 @@ def set_deterministic(flag=True):
     return old
 
 
-_rest_update = None
-_grad_acc = None
-
-
 class GradAccumulation:
     """with ops.accumulate_grads(params) as acc: ... several render(...).backward() ...; acc.assign()
 
     The gradients of the views of ONE iteration are summed by the projection backward itself (GSPLAT_BACKWARD_ACCUMULATE) in one flat
     buffer: the first view writes, the others add -- instead of autograd's AccumulateGrad pass per view (read two, write one: 0.4 ms
     per view at 3 M Gaussians).  `params`: dict name -> the leaf tensors the renders are called with (fp32, contiguous, .grad None).
-    A render of other tensors, a frame that waited for its counters or a data-parallel sink keep the ordinary backward.  assign()
+    A render of other tensors, a frame that waited for its counters or a timed pass keep the ordinary backward.  assign()
     sets param.grad (views of the buffer) -- summing in what the ordinary backward may have produced for some views."""
 
     NAMES = ("pos", "opacity_raw", "scale_raw", "q_raw", "f_dc", "f_rest")
@@ -589,101 +584,89 @@ class GradAccumulation:
             p.grad = g if p.grad is None else p.grad.add_(g)
 
 
-@contextlib.contextmanager
 def accumulate_grads(params):
-    global _grad_acc
-    acc = GradAccumulation(params)
-    _grad_acc = acc
+    return gradient_route(GradAccumulation(params))
+
+
+# The route of a frame's gradients: at most one consumer takes them in place of autograd's .grad, for the frames rendered inside
+# its gradient_route() block -- dp.FactoredExchange (data parallel: 3 colour-logit gradients per Gaussian instead of 48 SH ones,
+# DESIGN.md §7), optim._RestUpdate (the Adam step of f_rest inside the backward) or GradAccumulation (the views of an iteration
+# summed by the backward).  The slot is read once, in the caller's thread, when a frame is rendered (fr.route): the backward pass,
+# on autograd's thread, reads fr.route only.
+_route = contextvars.ContextVar("gsplat_gradient_route", default=None)
+
+
+@contextlib.contextmanager
+def gradient_route(consumer):
+    if _route.get() is not None:
+        raise RuntimeError("a gradient route is already active: routes do not nest")
+    token = _route.set(consumer)
     try:
-        yield acc
+        yield consumer
     finally:
-        _grad_acc = None
+        _route.reset(token)
 
 
-def set_rest_update(hook):
-    """hook (optim.GaussianAdam.fused_rest_update) or None: while one is installed, the backward pass of a deferred frame rendered
-    from the hook's own f_rest tensor applies the Adam step of f_rest inside the projection backward (gsplat_backward_adam_rest) and
-    returns no gradient for it."""
-    global _rest_update
-    _rest_update = hook
+def _route_of(fr, composite):
+    """The active route's consumer if it takes the gradients of this frame (composite: queued by gsplat_forward_deferred), else None."""
+    r = _route.get()
+    if r is None or not fr.fused:
+        return None
+    if isinstance(r, dp.FactoredExchange):
+        return r if r.owns(fr.inputs, fr.src_ptrs) else None
+    if not (composite and fr.sh_jacobian):
+        return None
+    if isinstance(r, GradAccumulation):
+        return r if r.matches(fr.inputs) else None
+    return r if r.matches(fr.inputs["f_rest"], fr.src_ptrs[1]) else None          # optim._RestUpdate
 
 
-def set_sh_gradient_sink(sink):
-    """sink: object with .add(grad_logit[N,3], eye[3] device tensor), or None to restore the ordinary backward."""
-    global _sh_sink
-    _sh_sink = sink
+def _backward_call(fr, gi, gg, flags, st, det=None, glogit=None, rest=None):
+    """gsplat_backward on the frame's arena, or gsplat_backward_adam_rest with rest = (AdamGroup, beta1, beta2, eps)."""
+    lib = _abi.lib()
+    args = (fr.gaussians, fr.c2w.data_ptr(), fr.view, fr.arena.data_ptr(), fr.arena.numel(), fr.n_pairs, gi.data_ptr(), gg)
+    scratch = (det.data_ptr(), det.numel()) if det is not None else (None, 0)
+    if rest is None:
+        _abi.check(lib.gsplat_backward(*args, _p(glogit), *scratch, flags, st), "gsplat_backward")
+    else:
+        group, b1, b2, eps = rest
+        _abi.check(lib.gsplat_backward_adam_rest(*args, *scratch, flags, C.byref(group), b1, b2, eps, st), "gsplat_backward_adam_rest")
+
+
+_SH = ("f_dc", "f_rest")
+_GRAD_FIELDS = tuple(name for name, _ in _abi.GaussianGrads._fields_)
 
 
 def _backward_impl(fr, grad_image):
-    """Returns a dict name -> fp32 gradient tensor for every input of the forward call."""
+    """Returns a dict name -> fp32 gradient tensor of the inputs of the forward call (a missing name: fr.route took that gradient)."""
     lib = _abi.lib()
-    ins = fr.inputs
+    ins, route = fr.inputs, fr.route
     dev = ins["pos"].device
-    # the sink only takes over for the parameter tensors it was built for: a render of other tensors (an evaluation
-    # model, a test) while a sink is installed keeps its ordinary SH gradients
-    factored = fr.fused and _sh_sink is not None and getattr(_sh_sink, "owns", lambda _ins, _ptrs=None: True)(ins, fr.src_ptrs)
+    factored = isinstance(route, dp.FactoredExchange)
     if fr.empty or fr.n == 0:
         if factored:
-            _sh_sink.add(torch.zeros((fr.n, 3), dtype=torch.float32, device=dev), fr.c2w[:3, 3])
-            return {k: (None if k in ("f_dc", "f_rest") else torch.zeros_like(v)) for k, v in ins.items()}
-        return {k: torch.zeros_like(v) for k, v in ins.items()}
+            route.add(torch.zeros((fr.n, 3), dtype=torch.float32, device=dev), fr.c2w[:3, 3])
+        return {k: torch.zeros_like(v) for k, v in ins.items() if not (factored and k in _SH)}
     gi = _f32(grad_image, (fr.view.H, fr.view.W, 3), "grad_image")
     if torch.cuda.current_device() != dev.index:
         torch.cuda.set_device(dev)
     stream = torch.cuda.current_stream(dev)
     st = C.c_void_p(stream.cuda_stream)
-    det = None
-    if _deterministic:
-        det = _ws.get_scratch(dev, lib.gsplat_rasterize_backward_scratch_bytes(fr.n, fr.n_pairs), (dev.type, dev.index, stream.cuda_stream))
-    wants_stages = _timer is not None and _timer.wants(_BACKWARD_STAGES)
-    upd = _rest_update
-    fold_rest = (upd is not None and fr.arena is not None and not factored and not wants_stages and fr.fused and fr.sh_jacobian
-                 and not upd.applied and fr.src_ptrs is not None and upd.matches(ins["f_rest"], fr.src_ptrs[1]))
-    acc = _grad_acc
-    sum_views = (acc is not None and fr.arena is not None and not factored and not wants_stages and not fold_rest and fr.fused
-                 and fr.sh_jacobian and not fr.dirty and acc.matches(ins))
-    if sum_views:
-        # the views of an iteration summed in the accumulation's own buffer by the projection backward: autograd gets no gradient
-        bufs, add = acc.begin(stream)
-        gg = _abi.GaussianGrads(_p(bufs["pos"]), _p(bufs["opacity_raw"]), None, None, _p(bufs["scale_raw"]), _p(bufs["q_raw"]),
-                                _p(bufs["f_dc"]), _p(bufs["f_rest"]))
-        fr.dirty = True
-        flags = _abi.GSPLAT_BACKWARD_SH_JACOBIAN | (_abi.GSPLAT_BACKWARD_ACCUMULATE if add else 0)
-        _abi.check(lib.gsplat_backward(fr.gaussians, fr.c2w.data_ptr(), fr.view, fr.arena.data_ptr(), fr.arena.numel(), fr.n_pairs, gi.data_ptr(), gg,
-                                       None, det.data_ptr() if det is not None else None, det.numel() if det is not None else 0, flags, st),
-                   "gsplat_backward")
-        acc.done(stream)
-        composite_calls["backward"] += 1
-        return {k: None for k in ins}
-    out = _flat_like({k: v for k, v in ins.items() if not ((factored and k in ("f_dc", "f_rest")) or (fold_rest and k == "f_rest"))})
-    gg = _abi.GaussianGrads(_p(out["pos"]), _p(out["opacity_raw"]), _p(None if factored else out.get("color")), _p(out.get("sigma")),
-                            _p(out.get("scale_raw")), _p(out.get("q_raw")), _p(out.get("f_dc")), _p(out.get("f_rest")))
-    jac = _abi.GSPLAT_BACKWARD_SH_JACOBIAN if fr.sh_jacobian else 0
-    if fr.arena is not None:
-        # ---- the frame was queued by gsplat_forward_deferred: one call for the whole backward pass (two with a sink in between)
-        dirty = _abi.GSPLAT_BACKWARD_GRAD2D_DIRTY if fr.dirty else 0
-        fr.dirty = True                        # a second backward through the same graph must not reuse a dirty buffer
-        args = (fr.gaussians, fr.c2w.data_ptr(), fr.view, fr.arena.data_ptr(), fr.arena.numel(), fr.n_pairs, gi.data_ptr(), gg)
-        dargs = (det.data_ptr() if det is not None else None, det.numel() if det is not None else 0)
-        if fold_rest:
-            # the Adam step of f_rest inside the projection backward: its 192 bytes of gradient per Gaussian are never written
-            group, b1, b2, eps = upd.begin()
-            _abi.check(lib.gsplat_backward_adam_rest(*args, *dargs, jac | dirty, C.byref(group), b1, b2, eps, st), "gsplat_backward_adam_rest")
-            composite_calls["backward"] += 1
-            out["f_rest"] = None
-            return out
-        if factored or wants_stages:
-            glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=dev) if factored else None
-            with _stage("raster_backward"):
-                _abi.check(lib.gsplat_backward(*args, _p(glogit), *dargs, jac | dirty | _abi.GSPLAT_BACKWARD_PHASE_RASTER, st), "gsplat_backward")
-            if factored:       # logit gradients first: the sink may start exchanging them while the projection backward runs
-                _sh_sink.add(glogit, fr.c2w[:3, 3])
-            with _stage("project_backward"):
-                _abi.check(lib.gsplat_backward(*args, None, None, 0, jac | _abi.GSPLAT_BACKWARD_PHASE_PROJECT, st), "gsplat_backward")
-        else:
-            _abi.check(lib.gsplat_backward(*args, None, *dargs, jac | dirty, st), "gsplat_backward")
-        composite_calls["backward"] += 1
+    det = (_ws.get_scratch(dev, lib.gsplat_rasterize_backward_scratch_bytes(fr.n, fr.n_pairs), (dev.type, dev.index, stream.cuda_stream))
+           if _deterministic else None)
+    staged = _timer is not None and _timer.wants(_BACKWARD_STAGES)
+    # only known now, each sending the frame down the ordinary backward: a timed pass (phase by phase), a second pass through the
+    # frame (views' sum), a step of f_rest already applied (folded step)
+    summing = isinstance(route, GradAccumulation)
+    summed = summing and not (staged or fr.dirty)
+    folded = route is not None and not (factored or summing or staged or route.applied)          # optim._RestUpdate
+    if summed:
+        dst, add = route.begin(stream)
     else:
+        dst = _flat_like({k: v for k, v in ins.items() if not (factored and k in _SH or folded and k == "f_rest")})
+    gg = _abi.GaussianGrads(*map(_p, map(dst.get, _GRAD_FIELDS)))
+    jac = _abi.GSPLAT_BACKWARD_SH_JACOBIAN if fr.sh_jacobian else 0
+    if fr.arena is None:                       # ---- the frame went through the separate calls
         zeroed = fr.grad2d is not None
         grad2d = fr.grad2d if zeroed else torch.empty((fr.n, 16), dtype=torch.float32, device=dev)
         fr.grad2d = None                       # a second backward through the same graph must not reuse a dirty buffer
@@ -692,17 +675,38 @@ def _backward_impl(fr, grad_image):
                                                      _p(fr.accum), _p(gi), _p(grad2d), int(zeroed), _p(det),
                                                      det.numel() if det is not None else 0, st), "gsplat_rasterize_backward")
         if factored:
-            # logit gradients first: the sink may start exchanging them while the projection backward runs
+            # logit gradients first: the exchange may start on them while the projection backward runs
             glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=dev)
             _abi.check(lib.gsplat_logit_grad(fr.n, C.byref(fr.view), _p(fr.proj_state), _p(grad2d), _p(glogit), st), "gsplat_logit_grad")
-            _sh_sink.add(glogit, fr.c2w[:3, 3])
+            route.add(glogit, fr.c2w[:3, 3])
         g = _make_gaussians(fr.n, **ins)
         with _stage("project_backward"):
             _abi.check(lib.gsplat_project_backward(C.byref(g), _p(fr.c2w), C.byref(fr.view), _p(fr.proj_state), _p(grad2d),
                                                    C.byref(gg), jac, st), "gsplat_project_backward")
-    if factored:
-        out["f_dc"] = out["f_rest"] = None
-    return out
+        return dst
+    # ---- the frame was queued by gsplat_forward_deferred: one call for the whole backward pass (two, phase by phase)
+    flags = jac | (_abi.GSPLAT_BACKWARD_GRAD2D_DIRTY if fr.dirty else 0)
+    fr.dirty = True                            # a second backward through the same graph must not reuse a dirty buffer
+    if summed:
+        # the views of an iteration summed in the accumulation's own buffer by the projection backward: autograd gets no gradient
+        _backward_call(fr, gi, gg, flags | (_abi.GSPLAT_BACKWARD_ACCUMULATE if add else 0), st, det)
+        route.done(stream)
+    elif folded:
+        # the Adam step of f_rest inside the projection backward: its 192 bytes of gradient per Gaussian are never written
+        _backward_call(fr, gi, gg, flags, st, det, rest=route.begin())
+        route.commit()
+    elif factored or staged:
+        glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=dev) if factored else None
+        with _stage("raster_backward"):
+            _backward_call(fr, gi, gg, flags | _abi.GSPLAT_BACKWARD_PHASE_RASTER, st, det, glogit)
+        if factored:                           # logit gradients first: the exchange may start on them while the projection backward runs
+            route.add(glogit, fr.c2w[:3, 3])
+        with _stage("project_backward"):
+            _backward_call(fr, gi, gg, jac | _abi.GSPLAT_BACKWARD_PHASE_PROJECT, st)
+    else:
+        _backward_call(fr, gi, gg, flags, st, det)
+    composite_calls["backward"] += 1
+    return {} if summed else dst
 
 
 _BACKWARD_STAGES = frozenset(("raster_backward", "project_backward"))
@@ -749,16 +753,10 @@ class _RenderFn(torch.autograd.Function):
         names = ("pos", "opacity_raw") + (("scale_raw", "q_raw", "f_dc", "f_rest") if fr.fused else ("color", "sigma", None, None))
         outs = []
         for i, nm in enumerate(names):
-            if nm is None or not ctx.needs_input_grad[3 + i]:
-                outs.append(None)
-                continue
-            t = g[nm]
-            if t is None:                     # f_dc / f_rest while a factored-exchange sink is installed
-                outs.append(None)
-                continue
-            if nm == "opacity_raw":
+            t = g.get(nm) if ctx.needs_input_grad[3 + i] else None        # (None also where the frame's route took the gradient)
+            if t is not None and nm == "opacity_raw":
                 t = t.reshape(ctx.opa_shape)
-            outs.append(t if ctx.dtypes[i] == torch.float32 else t.to(ctx.dtypes[i]))
+            outs.append(t if t is None or ctx.dtypes[i] == torch.float32 else t.to(ctx.dtypes[i]))
         return (None, None, None, *outs)
 
 

@@ -5,7 +5,6 @@ learning-rate schedule (:446-457), `clip_grad_norm_(model.pos, max_norm=1.0)` (:
 `GaussianAdam` takes torch-style param groups; `step()` runs ONE fused HIP kernel for all of them (csrc/gsplat_optim.hip); the
 clip coefficient is computed and applied on the device, so a training step has no host synchronisation here.
 """
-import contextlib
 import ctypes as C
 
 import torch
@@ -49,12 +48,15 @@ class _RestUpdate:
                 and f_rest32.data_ptr() == p.data_ptr() and p.data_ptr() % 16 == 0)
 
     def begin(self):
+        """(AdamGroup, beta1, beta2, eps) of the optimiser's next step of the parameter; commit() counts it once the call is queued."""
         st = self.opt._state(self.param)
-        st['step'] += 1
-        self.applied = True
         group = _abi.AdamGroup(self.param.numel(), _p(self.param).value, None, _p(st['exp_avg']).value, _p(st['exp_avg_sq']).value,
-                               float(self.lr), int(st['step']), None)
+                               float(self.lr), int(st['step']) + 1, None)
         return group, float(self.opt.betas[0]), float(self.opt.betas[1]), float(self.opt.eps)
+
+    def commit(self):
+        self.opt._state(self.param)['step'] += 1
+        self.applied = True
 
     def rollback(self):
         """The frame turned out to have outgrown its buffers (or to be off screen): the kernel stepped nothing, so nothing counts."""
@@ -94,19 +96,13 @@ class GaussianAdam:
                                   'exp_avg_sq': torch.zeros_like(p, memory_format=torch.contiguous_format)}
         return st
 
-    @contextlib.contextmanager
     def fused_rest_update(self, param):
         """For an iteration of ONE view rendered inside ops.deferred_checks(): the backward pass applies this optimiser's step of
         `param` (the model's f_rest: 81 % of all parameters) as the gradient is formed, param.grad stays None and step() skips it.
-        Yields the hook: call hook.rollback() when the frame's checks fail afterwards (ops.PairCapacityExceeded, off-screen) -- the
-        kernel itself stepped nothing in that case."""
+        A context (ops.gradient_route) that yields the hook: call hook.rollback() when the frame's checks fail afterwards
+        (ops.PairCapacityExceeded, off-screen) -- the kernel itself stepped nothing in that case."""
         lr = next(g['lr'] for g in self.param_groups if any(p is param for p in g['params']))
-        hook = _RestUpdate(self, param, lr)
-        ops.set_rest_update(hook)
-        try:
-            yield hook
-        finally:
-            ops.set_rest_update(None)
+        return ops.gradient_route(_RestUpdate(self, param, lr))
 
     @torch.no_grad()
     def clip_grad_norm_(self, param, max_norm=1.0):

@@ -126,25 +126,27 @@ class Trainer:
         for attempt in range(4):
             self.optimizer.zero_grad()
             acc = torch.zeros(3, dtype=torch.float32, device=dev)
-            # data parallel: SH gradients travel in factored form (dp.FactoredExchange, 2.6x fewer bytes over xGMI at 8 views)
+            # the route of the gradients (ops.gradient_route): data parallel, SH gradients in factored form (dp.FactoredExchange, 2.6x
+            # fewer bytes over xGMI at 8 views); one view, the Adam step of f_rest inside its backward; several, their sum in the backward
             exchange = dp.FactoredExchange(m.get_params(), world_views=1, group=self.group, equal_views=even) if world > 1 else None
-            # no host synchronisation per view: the renders size their buffers from earlier frames, the per-frame checks
-            # (off-screen exception, buffer capacity) are made ONCE, after the last backward is queued
-            pass_error = None
-            fold = c.fold_rest_step and world == 1 and len(views) == 1
-            rest_hook = None
+            fold = exchange is None and len(views) == 1 and c.fold_rest_step
+            sum_in_kernel = exchange is None and len(views) > 1 and c.sum_views_in_kernel
+            route = (exchange if exchange is not None else self.optimizer.fused_rest_update(m.f_rest) if fold
+                     else ops.accumulate_grads(m.get_params()) if sum_in_kernel else None)
+            pass_error = checks = consumer = None
             try:
-                sum_in_kernel = c.sum_views_in_kernel and world == 1 and len(views) > 1      # the views' gradients summed by the projection backward itself
-                with ops.deferred_checks() as checks, (exchange if exchange is not None else contextlib.nullcontext()), \
-                        (ops.accumulate_grads(m.get_params()) if sum_in_kernel else contextlib.nullcontext()) as grad_acc, \
-                        (self.optimizer.fused_rest_update(m.f_rest) if fold else contextlib.nullcontext()) as rest_hook:
+                # no host synchronisation per view: the renders size their buffers from earlier frames, the per-frame checks
+                # (off-screen exception, buffer capacity) are made ONCE, after the last backward is queued
+                with contextlib.ExitStack() as stack:
+                    checks = stack.enter_context(ops.deferred_checks())
+                    consumer = stack.enter_context(route) if route is not None else None
                     side = self._view_streams(dev) if (c.view_streams > 1 and len(views) > 1 and world == 1) else ()     # (one process: the
                     # exchange's collectives of a data-parallel pass stay on the caller's stream)
                     main = torch.cuda.current_stream(dev) if side else None
                     for st in side:
                         st.wait_stream(main)                                           # parameters, zeroed gradients
                     per_view = []
-                    for k, v in enumerate(views):                                      # (the gradient sink is always removed again)
+                    for k, v in enumerate(views):
                         with (torch.cuda.stream(side[k % len(side)]) if side else contextlib.nullcontext()):
                             image_gt = torch.as_tensor(v['image']).to(dev)
                             c2w = torch.as_tensor(v['c2w'], dtype=torch.float32).to(dev)
@@ -155,8 +157,8 @@ class Trainer:
                             per_view.append(vals)
                     for st in side:
                         main.wait_stream(st)
-                    if grad_acc is not None:
-                        grad_acc.assign()
+                    if sum_in_kernel:
+                        consumer.assign()
                     for vals in per_view:                                              # (on the caller's stream, in view order)
                         if side:
                             vals.record_stream(main)
@@ -170,7 +172,8 @@ class Trainer:
             # exchange would leave them waiting for ever.
             status, err = dp.STATUS_OK, None
             try:
-                checks.verify()
+                if checks is not None:
+                    checks.verify()
                 if exchange is not None and exchange.n_added != len(views):
                     raise RuntimeError(f"{exchange.n_added} of this rank's {len(views)} views went through the factored exchange: a render "
                                        "of this model took the ordinary backward (are f_dc / f_rest the model's own tensors?)")
@@ -178,8 +181,8 @@ class Trainer:
                 status = dp.STATUS_REDO           # a view outgrew the buffers: this pass's gradients are invalid (capacity now raised)
             except Exception as e:                # the reference's off-screen Exception (render.py:235-236), or anything else
                 status, err = (dp.STATUS_OFFSCREEN if str(e) == ops.OFFSCREEN_MSG else dp.STATUS_ERROR), e
-            if status != dp.STATUS_OK and rest_hook is not None:
-                rest_hook.rollback()              # (the kernel stepped nothing for a frame that overflowed or is off screen: nothing counts)
+            if status != dp.STATUS_OK and fold:
+                consumer.rollback()               # (the kernel stepped nothing for a frame that overflowed or is off screen: nothing counts)
             if pass_error is not None:            # an exception inside the render loop itself (a frame that waited for its counters, a device error)
                 err = pass_error
                 status = dp.STATUS_OFFSCREEN if str(err) == ops.OFFSCREEN_MSG else dp.STATUS_ERROR
@@ -203,7 +206,7 @@ class Trainer:
         else:
             raise RuntimeError("the pair buffers overflowed four times in a row")
         names = dp.PARAM_NAMES
-        folded = rest_hook is not None and rest_hook.applied      # f_rest was stepped inside the backward pass: no gradient, no second step
+        folded = fold and consumer.applied      # f_rest was stepped inside the backward pass: no gradient, no second step
         for k in names:
             p = getattr(m, k)
             if p.grad is None and not (folded and p is m.f_rest):

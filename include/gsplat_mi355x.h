@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define GSPLAT_ABI_VERSION 8
+#define GSPLAT_ABI_VERSION 9
 
 /* call status */
 #define GSPLAT_OK 0
@@ -192,7 +192,8 @@ int gsplat_rasterize_backward(int64_t n, int64_t pair_capacity, const gsplat_vie
  * spherical_harmonics.py:166); gsplat_sh_accumulate turns logit gradients of any number of views into SH gradients.
  *   flags          GSPLAT_BACKWARD_SH_JACOBIAN: project_state was filled by gsplat_project with
  *                  GSPLAT_PROJECT_SAVE_SH_JACOBIAN for the SAME g and c2w (same results up to fp32 rounding, 144 bytes
- *                  less HBM traffic per visible Gaussian).  Without the flag the SH coefficients are read again.         */
+ *                  less HBM traffic per visible Gaussian).  Without the flag the SH coefficients are read again.
+ *                  Also GSPLAT_BACKWARD_ACCUMULATE (below); any other bit is refused with GSPLAT_ERR_BAD_ARG.             */
 #define GSPLAT_BACKWARD_SH_JACOBIAN 1
 int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v,
                             const void* project_state, const float* grad2d, const gsplat_gaussian_grads* out,
@@ -217,7 +218,8 @@ int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const g
  *                 arena.  flags: GSPLAT_BACKWARD_SH_JACOBIAN as for gsplat_project_backward (set it iff the frame was made
  *                 with GSPLAT_FRAME_BACKWARD from fused inputs without GSPLAT_FRAME_NO_SH_JACOBIAN);
  *                 GSPLAT_BACKWARD_PHASE_RASTER / _PROJECT: only that half (a data-parallel host starts exchanging grad_logit
- *                 between the two); GSPLAT_BACKWARD_GRAD2D_DIRTY: a second backward pass through the same frame.           */
+ *                 between the two); GSPLAT_BACKWARD_GRAD2D_DIRTY: a second backward pass through the same frame;
+ *                 GSPLAT_BACKWARD_ACCUMULATE (below).  Any other bit is refused with GSPLAT_ERR_BAD_ARG.                      */
 #define GSPLAT_FRAME_BACKWARD 1
 #define GSPLAT_FRAME_NO_SH_JACOBIAN 2
 #define GSPLAT_BACKWARD_PHASE_RASTER 2

@@ -99,6 +99,26 @@ def test_bad_arguments_are_rejected_without_touching_the_gpu():
     assert b"state is NULL" in lib.gsplat_last_error()
 
 
+def test_unknown_backward_flags_are_refused_before_anything_else():
+    """A flag bit a backward entry does not define is refused first (with host arguments only: nothing reaches the GPU), so that
+    a library that does not know a flag cannot quietly do something else -- overwrite where the caller adds, say."""
+    lib = abi.lib()
+    v = abi.make_view(64, 64, 50.0, 50.0, 32.0, 32.0)
+    unknown = 1 << 5
+    assert lib.gsplat_backward(None, None, C.byref(v), None, 0, 0, None, None, None, None, 0, unknown, None) == abi.GSPLAT_ERR_BAD_ARG
+    assert b"unknown flag" in lib.gsplat_last_error()
+    group = abi.AdamGroup()
+    assert lib.gsplat_backward_adam_rest(None, None, C.byref(v), None, 0, 0, None, None, None, 0, unknown, C.byref(group), 0.9, 0.999,
+                                         1e-15, None) == abi.GSPLAT_ERR_BAD_ARG
+    assert b"unknown flag" in lib.gsplat_last_error()
+    for flags in (unknown, abi.GSPLAT_BACKWARD_PHASE_RASTER, abi.GSPLAT_BACKWARD_GRAD2D_DIRTY):     # (composite-only bits, too)
+        assert lib.gsplat_project_backward(None, None, C.byref(v), None, None, None, flags, None) == abi.GSPLAT_ERR_BAD_ARG
+        assert b"unknown flag" in lib.gsplat_last_error()
+    # a defined bit with the same NULL arguments gets as far as the argument checks
+    assert lib.gsplat_backward(None, None, C.byref(v), None, 0, 0, None, None, None, None, 0, abi.GSPLAT_BACKWARD_ACCUMULATE, None) == 1
+    assert b"unknown flag" not in lib.gsplat_last_error()
+
+
 def test_no_cpu_fallback(gs):
     z = torch.zeros
     with pytest.raises(RuntimeError, match="no CPU fallback"):

@@ -212,6 +212,21 @@ def test_agree_on_views_rejects_inconsistent_hints():
     assert dp.agree_on_views(3) == (True, 3)                       # single process: nothing to agree on
 
 
+def test_gradient_routes_do_not_nest():
+    """One consumer at a time takes the gradients of a frame (ops.gradient_route): a second route entered inside the first is
+    refused, the first stays the active one, and none is left behind."""
+    ops = importlib.import_module(PKG + ".ops")
+    dp = importlib.import_module(PKG + ".dp")
+    params = {k: torch.zeros(*s) for k, s in SHAPES.items()}
+    with dp.FactoredExchange(params, world_views=1) as ex:
+        assert ops._route.get() is ex
+        with pytest.raises(RuntimeError, match="do not nest"):
+            with ops.accumulate_grads(params):
+                pass
+        assert ops._route.get() is ex
+    assert ops._route.get() is None
+
+
 # ---- Trainer.step: one agreement per pass, whatever happens on a rank (host logic; the renderer is a toy: the HIP op needs a GPU) ----
 def _toy_trainer_worker(rank, world, port, q, mode):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
@@ -233,20 +248,20 @@ def _toy_trainer_worker(rank, world, port, q, mode):
         def get_num_gaussians(self):
             return n
 
-    class Toy(torch.autograd.Function):          # hands its logit gradients to the installed sink, like the render backward
+    class Toy(torch.autograd.Function):          # hands its logit gradients to the exchange it was rendered under, like the render
         @staticmethod
         def forward(ctx, pos, f_dc, f_rest, opa, scale, quat, c2w, weight):
             ctx.c2w, ctx.weight = c2w, weight
-            ctx.src = (f_dc.data_ptr(), f_rest.data_ptr())
+            route = ops._route.get()                 # (taken in forward, in the caller's thread, as the render does)
+            ctx.route = route if route is not None and route.owns({}, (f_dc.data_ptr(), f_rest.data_ptr())) else None
             return (pos.sum() + opa.sum() + scale.sum() + quat.sum()) * torch.ones(2, 2, 3) * weight
 
         @staticmethod
         def backward(ctx, g):
             s = float(g.sum()) * ctx.weight
-            sink = ops._sh_sink
-            factored = sink is not None and sink.owns({}, ctx.src)
+            factored = ctx.route is not None
             if factored:
-                sink.add(torch.full((n, 3), s), ctx.c2w[:3, 3])
+                ctx.route.add(torch.full((n, 3), s), ctx.c2w[:3, 3])
             sh = (None, None) if factored else (torch.full((n, 3), s), torch.full((n, 45), s))
             return torch.full((n, 3), s), sh[0], sh[1], torch.full((n,), s), torch.full((n, 3), s), torch.full((n, 4), s), None, None
 
@@ -301,7 +316,7 @@ def _toy_trainer_worker(rank, world, port, q, mode):
 
 
 @pytest.mark.parametrize("mode", ["verify_offscreen", "render_raises", "other_error", "redo_once", "fine"])
-def test_trainer_step_agrees_on_the_outcome_of_a_pass(mode):
+def test_trainer_step_agrees_on_the_outcome_of_a_routed_pass(mode):
     """One rank's view has survivors but nothing on screen (found in verify(), or by a frame that waited for its counters after one
     of its views' collectives was already issued), or it fails otherwise: EVERY rank raises within the timeout -- nobody is left
     waiting in a collective.  One rank's pair buffers overflowed: both repeat the pass, and the gradients are those of a clean pass."""
