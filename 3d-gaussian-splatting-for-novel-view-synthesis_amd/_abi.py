@@ -12,10 +12,11 @@ LIB_PATH = os.environ.get("GSPLAT_MI355X_LIB") or os.path.join(_HERE, "csrc", "l
 
 GSPLAT_OK = 0
 GSPLAT_ERR_BAD_ARG = 1
+GSPLAT_ERR_WORKSPACE = 3
 GSPLAT_SCENE_OK = 0
 GSPLAT_SCENE_ALL_CULLED = 10
 GSPLAT_SCENE_ALL_OFFSCREEN = 11
-ABI_VERSION = 9
+ABI_VERSION = 10
 GSPLAT_PROJECT_COLOUR_FUSED = 1
 GSPLAT_PROJECT_COUNTS_MAPPED = 2
 GSPLAT_PROJECT_SAVE_SH_JACOBIAN = 4
@@ -78,6 +79,8 @@ SIGNATURES = {
     "gsplat_rasterize_backward_scratch_bytes": (_I64, [_I64, _I64]),
     "gsplat_rasterize_backward": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP, _VP, C.c_int32, _VP, _I64, _VP]),
     "gsplat_project_backward": (_INT, [_PG, _VP, _PV, _VP, _VP, _PGG, C.c_int32, _VP]),
+    "gsplat_pose_scratch_bytes": (_I64, [_I64]),
+    "gsplat_project_backward_pose": (_INT, [_PG, _VP, _PV, _VP, _VP, _PGG, _VP, _VP, _I64, C.c_int32, _VP]),
     "gsplat_logit_grad": (_INT, [_I64, _PV, _VP, _VP, _VP, _VP]),
     "gsplat_frame_bytes": (_I64, [_I64, _I64, _PV, C.c_int32]),
     "gsplat_forward_deferred": (_INT, [_PG, _VP, _PV, _VP, _I64, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, C.c_int32, _VP]),

@@ -153,9 +153,11 @@ GS_HD RecOut project_core(const GaussIn& in, bool fused, Coef coef, const Camera
 // q = A11 du^2 + 2 A12 du dv + A22 dv^2 and du = px - u:  d u = o (A11 Mx + A12 My), d v = o (A12 Mx + A22 My),
 // d A11 = -0.5 o Mxx, d A12 = -o Mxy, d A22 = -0.5 o Myy.  moments = false: r9[0..5] are those gradients themselves.
 // kj (nullable): the 12 values the forward saved with sh_colour_jac; then `coef` is not read.
-template <class Coef, class Emit>
+// POSE: g_W receives this Gaussian's dL/dW (gs_math.h pose_grad_w; zeros for a Gaussian that is not visible).
+template <bool POSE = false, class Coef, class Emit>
 GS_HD GradOut project_backward_core(const GaussIn& in, bool fused, Coef coef, Emit emit_sh, const Camera& cam, const ViewK& vk,
-                                    bool vis, const float r9[9], bool moments = false, const float* kj = nullptr) {
+                                    bool vis, const float r9[9], bool moments = false, const float* kj = nullptr,
+                                    float* g_W = nullptr) {
     GradOut g;
     for (int k = 0; k < 3; ++k) { g.p[k] = 0.f; g.sr[k] = 0.f; g.col[k] = 0.f; }
     for (int k = 0; k < 4; ++k) g.qr[k] = 0.f;
@@ -176,7 +178,8 @@ GS_HD GradOut project_backward_core(const GaussIn& in, bool fused, Coef coef, Em
             gb = -o.opacity * r9[3];
             gc = -0.5f * o.opacity * r9[4];
         }
-        project_gaussian_backward(m, o, cam, vk, gu, gv, ga, gb, gc, r9[5], g.p, g.S9, g.o_raw);
+        if constexpr (POSE) project_gaussian_backward<true>(m, o, cam, vk, gu, gv, ga, gb, gc, r9[5], g.p, g.S9, g.o_raw, in.p, S, g_W);
+        else project_gaussian_backward(m, o, cam, vk, gu, gv, ga, gb, gc, r9[5], g.p, g.S9, g.o_raw);
         g.col[0] = r9[6]; g.col[1] = r9[7]; g.col[2] = r9[8];
         if (fused) {
             cov_from_params_backward(in.qr, cm, g.S9, g.sr, g.qr);
@@ -195,6 +198,12 @@ GS_HD GradOut project_backward_core(const GaussIn& in, bool fused, Coef coef, Em
     } else if (fused) {
         for (int k = 0; k < 16; ++k)
             for (int ch = 0; ch < 3; ++ch) emit_sh(k, ch, 0.f);
+    }
+    if constexpr (POSE) {
+        if (!vis)
+            for (int k = 0; k < 9; ++k) g_W[k] = 0.f;
+    } else {
+        (void)g_W;
     }
     return g;
 }
@@ -228,12 +237,17 @@ GS_HD int project_one(int64_t i, const gsplat_gaussians& g, bool fused, Coef coe
     return r.vis;
 }
 
+// g_W (nullable): this Gaussian's dL/dW; then `out` may be NULL (pose only: no row is written) and the returned GradOut holds the
+// position gradient the pose sum needs.
 template <class Coef, class Emit>
-GS_HD void project_backward_one(int64_t i, const gsplat_gaussians& g, bool fused, Coef coef, Emit emit_sh, const Camera& cam,
-                                const ViewK& vk, const uint32_t* tiles, const float* grad2d,
-                                const gsplat_gaussian_grads& out) {
-    const GradOut o = project_backward_core(load_gauss_global(i, g, fused), fused, coef, emit_sh, cam, vk, tiles[i] != 0,
-                                            grad2d + i * 16);
+GS_HD GradOut project_backward_one(int64_t i, const gsplat_gaussians& g, bool fused, Coef coef, Emit emit_sh, const Camera& cam,
+                                   const ViewK& vk, const uint32_t* tiles, const float* grad2d,
+                                   const gsplat_gaussian_grads* out_p, float* g_W = nullptr) {
+    const GaussIn in = load_gauss_global(i, g, fused);
+    const GradOut o = g_W ? project_backward_core<true>(in, fused, coef, emit_sh, cam, vk, tiles[i] != 0, grad2d + i * 16, false, nullptr, g_W)
+                          : project_backward_core(in, fused, coef, emit_sh, cam, vk, tiles[i] != 0, grad2d + i * 16);
+    if (!out_p) return o;
+    const gsplat_gaussian_grads& out = *out_p;
     out.pos[i * 3 + 0] = o.p[0]; out.pos[i * 3 + 1] = o.p[1]; out.pos[i * 3 + 2] = o.p[2];
     out.opacity_raw[i] = o.o_raw;
     if (fused) {
@@ -243,6 +257,7 @@ GS_HD void project_backward_one(int64_t i, const gsplat_gaussians& g, bool fused
         for (int k = 0; k < 9; ++k) out.sigma[i * 9 + k] = o.S9[k];
         for (int k = 0; k < 3; ++k) out.color[i * 3 + k] = o.col[k];
     }
+    return o;
 }
 
 // Stand-alone build_sigma_from_params (gaussian.py:71-127) and its backward.

@@ -562,11 +562,31 @@ GS_HD void project_gaussian(const float p[3], const float S[6], float o_raw, con
     }
 }
 
+// Camera pose (B2, pose frames).  The projection sees the pose only through p_c = W (p - e) and C = W S W^T, with W = Rwc =
+// c2w[:3,:3]^T (Camera::w) and e = c2w[:3,3] (Camera::eye).  With g_pc = dL/dp_c and dC = dL/dC (symmetric) one Gaussian gives
+//     dL/dW = g_pc (p - e)^T + 2 dC W S                 (S symmetric: load_cov6 symmetrises an un-fused Sigma)
+// The culls carry no gradient, as for the position.  dL/de = -dL/dp: everything depends on p and e through p - e alone, the SH
+// direction included, so the translation needs no term of its own.
+GS_HD void pose_grad_w(const float g_pc[3], const float dC[9], const float w[9], const float S[6], const float p[3], const float eye[3],
+                       float g_W[9]) {
+    const float pe[3] = {p[0] - eye[0], p[1] - eye[1], p[2] - eye[2]};
+    const float Sf[9] = {S[0], S[1], S[2], S[1], S[3], S[4], S[2], S[4], S[5]};
+    float WS[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) WS[i * 3 + j] = w[i * 3 + 0] * Sf[0 + j] + w[i * 3 + 1] * Sf[3 + j] + w[i * 3 + 2] * Sf[6 + j];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b)
+            g_W[a * 3 + b] = g_pc[a] * pe[b] + 2.f * (dC[a * 3 + 0] * WS[0 + b] + dC[a * 3 + 1] * WS[3 + b] + dC[a * 3 + 2] * WS[6 + b]);
+}
+
 // B2.  Inputs: gradients w.r.t. (u, v, A11, A12, A22, opacity) of a VISIBLE Gaussian (its ProjMid recomputed by
 // project_gaussian).  Outputs: g_p[3] (position), G_S[9] (full symmetric world-covariance gradient), g_o_raw.
+// POSE: also g_W = dL/dW of this Gaussian (pose_grad_w), from its position p and the world covariance S the forward projected.
+// (A template flag, not a null pointer: the code of the variants without it stays exactly what it was.)
+template <bool POSE = false>
 GS_HD void project_gaussian_backward(const ProjMid& m, const Proj& o, const Camera& cam, const ViewK& vk, float g_u, float g_v,
                                      float g_A11, float g_A12, float g_A22, float g_opacity, float g_p[3], float G_S[9],
-                                     float& g_o_raw) {
+                                     float& g_o_raw, const float* p = nullptr, const float* S = nullptr, float* g_W = nullptr) {
     // opacity = clamp(sigmoid, 0, 0.999)
     g_o_raw = (m.sg <= 0.999f) ? g_opacity * m.sg * (1.f - m.sg) : 0.f;
     // min_conis clamp (render.py:310-311): gradient passes where the value is >= the bound
@@ -635,6 +655,12 @@ GS_HD void project_gaussian_backward(const ProjMid& m, const Proj& o, const Came
     g_p[0] = w[0] * dxc + w[3] * dyc + w[6] * dzc;
     g_p[1] = w[1] * dxc + w[4] * dyc + w[7] * dzc;
     g_p[2] = w[2] * dxc + w[5] * dyc + w[8] * dzc;
+    if constexpr (POSE) {
+        const float g_pc[3] = {dxc, dyc, dzc};
+        pose_grad_w(g_pc, dC, w, S, p, cam.eye, g_W);
+    } else {
+        (void)p; (void)S; (void)g_W;
+    }
     (void)o;
 }
 

@@ -405,6 +405,18 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x) {
 __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
     return (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan(x), 63);
 }
+// The same sum of a float: the partial sums meet in a fixed order (the DPP pattern), so the result does not change from run to run.
+__device__ __forceinline__ float wave_sum_f(float x) {
+#define DPP_F32(v, ctrl, rmask) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, rmask, 0xF, false))
+    x += DPP_F32(x, 0x111, 0xF);            // row_shr:1
+    x += DPP_F32(x, 0x112, 0xF);            // row_shr:2
+    x += DPP_F32(x, 0x114, 0xF);            // row_shr:4
+    x += DPP_F32(x, 0x118, 0xF);            // row_shr:8
+    x += DPP_F32(x, 0x142, 0xA);            // row_bcast:15 -> rows 1, 3
+    x += DPP_F32(x, 0x143, 0xC);            // row_bcast:31 -> rows 2, 3
+#undef DPP_F32
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
+}
 __device__ __forceinline__ uint32_t wave_max(uint32_t x) {
     x = max(x, GS_DPP_U32(x, 0u, 0x111, 0xF)); x = max(x, GS_DPP_U32(x, 0u, 0x112, 0xF));
     x = max(x, GS_DPP_U32(x, 0u, 0x114, 0xF)); x = max(x, GS_DPP_U32(x, 0u, 0x118, 0xF));
@@ -2165,13 +2177,18 @@ struct ShEmitLds {
 // place (adam_rows) -- the 192 of the 236 gradient bytes per Gaussian neither leave this kernel nor come back into the optimiser's.
 // ACC (fused inputs, saved Jacobian, not factored): every gradient is ADDED to what `out` holds -- the gradients of the views of one
 // iteration summed by the kernel that forms them, instead of a pass of the host's autograd per view (read two, write one).
-template <bool FUSED, bool JAC = false, bool ADAM = false, bool ACC = false>
+// POSE (not factored): also the camera-pose gradient.  Every lane forms its Gaussian's 12 terms -- dL/dW (gs_math.h pose_grad_w)
+// and dL/dp -- the wave adds them up in a fixed order (wave_sum_f) and stores ONE 64-byte row per block into pose_rows[blockIdx.x]
+// (every block writes its row: nothing to clear); pose_reduce_kernel adds the rows.  out.pos == NULL: no gradient row is stored
+// (pose only).
+template <bool FUSED, bool JAC = false, bool ADAM = false, bool ACC = false, bool POSE = false>
 __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g, const Camera* __restrict__ camp, ViewK vk,
                                                               const uint32_t* __restrict__ tiles, const float* __restrict__ grad2d,
                                                               gsplat_gaussian_grads out, bool factored, const float* __restrict__ kj_in,
-                                                              AdamRest ar) {
+                                                              AdamRest ar, f4* __restrict__ pose_rows = nullptr) {
     static_assert(!ADAM || (FUSED && JAC), "the in-place step needs the direct path");
     static_assert(!ACC || (FUSED && JAC && !ADAM), "accumulation is built for the direct path");
+    static_assert(!POSE || (!ADAM && !ACC), "the pose gradient is built for the plain backward");
     // DIRECT (fused inputs, saved Jacobian): nothing is staged IN (the 44 bytes of geometry are loaded by the lanes), and of the
     // gradients only the 45 f_rest rows go OUT through LDS (the rows of 1 / 3 / 4 floats are stored by the lanes): 11 520 B per
     // wave instead of 15 104 -> 14 waves per CU instead of 10.
@@ -2222,10 +2239,12 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
     GradOut go;
     float gdc[3] = {0.f, 0.f, 0.f};                       // (DIRECT) d L / d f_dc of this lane's Gaussian
     float* const dc_rows = DIRECT ? gdc : s_dc + lane * 3;
+    float gw[9];                                          // (POSE) d L / d W of this lane's Gaussian
     if (vis) {
         if (!DIRECT) in = gauss_from_lds<FUSED>(s, lane);
-        go = project_backward_core(in, FUSED, ShCoefLds{dc_rows, s_rest + lane * 45},
-                                   ShEmitLds{dc_rows, s_rest + lane * 45}, cam, vk, true, r9, true, JAC ? kj : nullptr);
+        go = project_backward_core<POSE>(in, FUSED, ShCoefLds{dc_rows, s_rest + lane * 45},
+                                   ShEmitLds{dc_rows, s_rest + lane * 45}, cam, vk, true, r9, true, JAC ? kj : nullptr,
+                                   POSE ? gw : nullptr);
     } else {
 #pragma unroll
         for (int k = 0; k < 3; ++k) { go.p[k] = 0.f; go.sr[k] = 0.f; go.col[k] = 0.f; }
@@ -2239,6 +2258,25 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
             for (int k = 0; k < 3; ++k) dc_rows[k] = 0.f;
             for (int k = 0; k < 45; ++k) s_rest[lane * 45 + k] = 0.f;
         }
+        if (POSE) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) gw[k] = 0.f;
+        }
+    }
+    if (POSE) {
+        float t[12];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) t[k] = wave_sum_f(gw[k]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) t[9 + k] = wave_sum_f(go.p[k]);
+        if (lane == 0) {
+            f4* row = pose_rows + (int64_t)blockIdx.x * 4;
+            row[0] = f4{t[0], t[1], t[2], t[3]};
+            row[1] = f4{t[4], t[5], t[6], t[7]};
+            row[2] = f4{t[8], t[9], t[10], t[11]};
+            row[3] = f4{0.f, 0.f, 0.f, 0.f};
+        }
+        if (!out.pos) return;                               // pose only (uniform)
     }
     if (DIRECT) {
         if (ACC) {
@@ -2323,6 +2361,38 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
     } else {
         unstage_rows<9>(out.sigma, s.a, row0, g.n, lane);
         unstage_rows<3>(out.color, s.b, row0, g.n, lane);
+    }
+}
+
+// ---- the camera-pose gradient: the rows of project_backward_kernel<..., POSE> added up ------------------------------------------
+// A row (16 floats) = (dL/dW row-major [9], dL/dp [3], 0 [4]) of one block of 64 Gaussians.  Block b of a launch adds rows
+// [b nrows / parts, (b + 1) nrows / parts) -- 16 threads per row, 16 rows at a time, then the 16 partial rows in LDS in a fixed order
+// -- and stores one row into out[b]; with FINAL (one block) it stores dL/dc2w instead: W = c2w[:3,:3]^T -> the transpose,
+// dL/dc2w[:3,3] = -sum dL/dp, the last row of c2w is a constant.  No atomics, no block waits for another: the same rows give the
+// same bits.  Two launches at most: POSE_PARTS blocks, then one.
+constexpr int POSE_PARTS = 256;
+template <bool FINAL>
+__global__ __launch_bounds__(256) void pose_reduce_kernel(const float* __restrict__ rows, int64_t nrows, int parts, float* __restrict__ out) {
+    __shared__ float s_part[16][17];
+    __shared__ float s_sum[16];
+    const int term = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    const int64_t r0 = (int64_t)blockIdx.x * nrows / parts, r1 = (int64_t)(blockIdx.x + 1) * nrows / parts;
+    float acc = 0.f;
+    for (int64_t r = r0 + grp; r < r1; r += 16) acc += rows[r * 16 + term];
+    s_part[grp][term] = acc;
+    __syncthreads();
+    if (threadIdx.x < 16) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t += s_part[k][term];
+        if (FINAL) s_sum[term] = t;
+        else out[(int64_t)blockIdx.x * 16 + term] = t;
+    }
+    if (!FINAL) return;
+    __syncthreads();
+    if (threadIdx.x < 16) {
+        const int r = term >> 2, c = term & 3;          // this thread's entry of dL/dc2w
+        out[term] = r == 3 ? 0.f : (c == 3 ? -s_sum[9 + r] : s_sum[c * 3 + r]);
     }
 }
 
@@ -2772,6 +2842,67 @@ int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const g
                             const float* grad2d, const gsplat_gaussian_grads* out, int32_t flags, void* stream_) {
     if (flags & ~PROJECT_BACKWARD_FLAGS) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
     return project_backward_impl(g, c2w, v, project_state, grad2d, out, flags, stream_, nullptr);
+}
+
+// the camera-pose scratch: one 64-byte row per block of 64 Gaussians, then POSE_PARTS partial rows (host arithmetic only)
+struct PoseScratch { f4* rows; float* part; int64_t nrows, bytes; };
+static PoseScratch carve_pose(void* base, int64_t n) {
+    PoseScratch p;
+    char* b = (char*)base;
+    p.nrows = (n + 63) / 64;
+    int64_t o = 0;
+    p.rows = (f4*)(b + o); o += up((p.nrows > 0 ? p.nrows : 1) * 64);
+    p.part = (float*)(b + o); o += up((int64_t)POSE_PARTS * 64);
+    p.bytes = o;
+    return p;
+}
+
+int64_t gsplat_pose_scratch_bytes(int64_t n) { return n < 0 ? -1 : carve_pose(nullptr, n).bytes; }
+
+int gsplat_project_backward_pose(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state,
+                                 const float* grad2d, const gsplat_gaussian_grads* out, float* grad_c2w, void* pose_scratch,
+                                 int64_t pose_scratch_bytes, int32_t flags, void* stream_) {
+    if (flags & ~GSPLAT_BACKWARD_SH_JACOBIAN) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
+    bool fused = false;
+    int rc = check_gaussians(g, &fused);
+    if (rc) return rc;
+    if ((rc = check_view(v))) return rc;
+    if (!grad_c2w) return fail(GSPLAT_ERR_BAD_ARG, "grad_c2w is NULL");
+    if (!c2w || !project_state || !grad2d) return fail(GSPLAT_ERR_BAD_ARG, "NULL argument");
+    const PoseScratch ps_ = carve_pose(pose_scratch, g->n);
+    if (!pose_scratch || pose_scratch_bytes < ps_.bytes) return fail(GSPLAT_ERR_WORKSPACE, "pose scratch too small (gsplat_pose_scratch_bytes)");
+    if (reinterpret_cast<uintptr_t>(pose_scratch) & 63u) return fail(GSPLAT_ERR_BAD_ARG, "pose scratch must be 64-byte aligned");
+    if (out) {
+        if (!out->pos || !out->opacity_raw) return fail(GSPLAT_ERR_BAD_ARG, "grad pos / opacity_raw is NULL");
+        if (fused && !(out->scale_raw && out->q_raw && out->f_dc && out->f_rest)) return fail(GSPLAT_ERR_BAD_ARG, "fused grads incomplete");
+        if (!fused && !(out->color && out->sigma)) return fail(GSPLAT_ERR_BAD_ARG, "grad color / sigma is NULL");
+    }
+    hipStream_t st = (hipStream_t)stream_;
+    if (g->n == 0) {
+        HIP_TRY(hipMemsetAsync(grad_c2w, 0, 16 * sizeof(float), st));
+        return GSPLAT_OK;
+    }
+    ProjectState ps = carve_project((void*)project_state, g->n, n_lists(v));
+    const ViewK vk = make_viewk(*v);
+    const AdamRest none = {nullptr, nullptr, nullptr, {0.f, 0.f, 0.f, 0.f, 0.f}, nullptr, 0};
+    const gsplat_gaussian_grads o = out ? *out : gsplat_gaussian_grads{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (fused && (flags & GSPLAT_BACKWARD_SH_JACOBIAN))
+        hipLaunchKernelGGL((project_backward_kernel<true, true, false, false, true>), dim3(blocks64(g->n)), dim3(64), 0, st, *g, ps.cam, vk, ps.tiles, grad2d, o, false, ps.kj, none, ps_.rows);
+    else if (fused)
+        hipLaunchKernelGGL((project_backward_kernel<true, false, false, false, true>), dim3(blocks64(g->n)), dim3(64), 0, st, *g, ps.cam, vk, ps.tiles, grad2d, o, false, nullptr, none, ps_.rows);
+    else
+        hipLaunchKernelGGL((project_backward_kernel<false, false, false, false, true>), dim3(blocks64(g->n)), dim3(64), 0, st, *g, ps.cam, vk, ps.tiles, grad2d, o, false, nullptr, none, ps_.rows);
+    LAUNCH_CHECK("project_backward_kernel<pose>");
+    const float* rows = reinterpret_cast<const float*>(ps_.rows);
+    if (ps_.nrows > POSE_PARTS) {
+        hipLaunchKernelGGL(pose_reduce_kernel<false>, dim3(POSE_PARTS), dim3(256), 0, st, rows, ps_.nrows, POSE_PARTS, ps_.part);
+        LAUNCH_CHECK("pose_reduce_kernel");
+        hipLaunchKernelGGL(pose_reduce_kernel<true>, dim3(1), dim3(256), 0, st, ps_.part, (int64_t)POSE_PARTS, 1, grad_c2w);
+    } else {
+        hipLaunchKernelGGL(pose_reduce_kernel<true>, dim3(1), dim3(256), 0, st, rows, ps_.nrows, 1, grad_c2w);
+    }
+    LAUNCH_CHECK("pose_reduce_kernel<final>");
+    return GSPLAT_OK;
 }
 
 // ---- one call per direction (include/gsplat_mi355x.h: "composite entries") ----------------------------------------------

@@ -31,8 +31,42 @@ void hm_project_backward(const gsplat_gaussians* g, const float* c2w, const gspl
     for (int64_t i = 0; i < g->n; ++i) {
         ShCoefGlobal coef{fused ? g->f_dc + i * 3 : nullptr, fused ? g->f_rest + i * 45 : nullptr};
         ShEmitGlobal emit{fused ? out->f_dc + i * 3 : nullptr, fused ? out->f_rest + i * 45 : nullptr};
-        project_backward_one(i, *g, fused, coef, emit, cam, vk, tiles, grad2d, *out);
+        project_backward_one(i, *g, fused, coef, emit, cam, vk, tiles, grad2d, out);
     }
+}
+
+namespace {
+struct ShEmitNullable {     // ShEmitGlobal that drops the values when there is no gradient row (pose only)
+    float* dc;
+    float* rest;
+    void operator()(int k, int ch, float v) const {
+        if (dc) ShEmitGlobal{dc, rest}(k, ch, v);
+    }
+};
+}  // namespace
+
+// hm_project_backward plus the camera-pose gradient: grad_c2w[16] = dL/dc2w (4 x 4 row-major) of the rows' cotangents, the
+// per-Gaussian terms of gs_math.h pose_grad_w summed in double.  out may be NULL (pose only).
+void hm_project_backward_pose(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const uint32_t* tiles,
+                              const float* grad2d, const gsplat_gaussian_grads* out, float* grad_c2w) {
+    Camera cam; build_camera(c2w, cam);
+    const ViewK vk = make_viewk(*v);
+    const bool fused = g->scale_raw != nullptr;
+    double sw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, sp[3] = {0, 0, 0};
+    for (int64_t i = 0; i < g->n; ++i) {
+        ShCoefGlobal coef{fused ? g->f_dc + i * 3 : nullptr, fused ? g->f_rest + i * 45 : nullptr};
+        ShEmitNullable emit{fused && out ? out->f_dc + i * 3 : nullptr, fused && out ? out->f_rest + i * 45 : nullptr};
+        float gw[9];
+        const GradOut o = project_backward_one(i, *g, fused, coef, emit, cam, vk, tiles, grad2d, out, gw);
+        for (int k = 0; k < 9; ++k) sw[k] += gw[k];
+        for (int k = 0; k < 3; ++k) sp[k] += o.p[k];
+    }
+    // W = c2w[:3,:3]^T: dL/dc2w[:3,:3] = (dL/dW)^T; dL/dc2w[:3,3] = -sum dL/dp; the last row is constant
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) grad_c2w[r * 4 + c] = (float)sw[c * 3 + r];
+        grad_c2w[r * 4 + 3] = (float)-sp[r];
+    }
+    for (int c = 0; c < 4; ++c) grad_c2w[12 + c] = 0.f;
 }
 
 // the row spans of a large Gaussian's rectangle (gs_math.h big_row_span), as the binning kernels enumerate them: xa[r], xb[r] for the

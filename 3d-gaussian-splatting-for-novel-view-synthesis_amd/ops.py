@@ -352,7 +352,7 @@ class _Frame:
     (project_state | bin_state | accum | grad2d, carved by the library); one that went through the separate calls keeps them
     as separate buffers."""
     __slots__ = ("view", "n", "n_pairs", "proj_state", "bin_state", "accum", "fused", "inputs", "c2w", "empty", "grad2d", "sh_jacobian",
-                 "arena", "gaussians", "dirty", "src_ptrs", "route")
+                 "arena", "gaussians", "dirty", "src_ptrs", "route", "pose")
 
 
 class _Pending:
@@ -377,7 +377,7 @@ def _new_frame(fused, view, n, pos32, opa32, c2w32, ins, c, d):
     fr.view, fr.n, fr.fused, fr.c2w, fr.empty, fr.sh_jacobian = view, n, fused, c2w32, False, False
     fr.inputs = dict(pos=pos32, opacity_raw=opa32, **ins)
     fr.arena = fr.gaussians = fr.proj_state = fr.bin_state = fr.accum = fr.grad2d = fr.route = None
-    fr.dirty = False
+    fr.dirty = fr.pose = False
     # the caller's own SH tensors (before any dtype / layout conversion): what dp.FactoredExchange.owns() compares
     fr.src_ptrs = (c.data_ptr(), d.data_ptr()) if fused else None
     return fr
@@ -387,12 +387,18 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
     """First half of the forward pass: everything up to (not including) the host's wait for the counters.  Returns
     (pending, None), or (None, result) when nothing is left to do: zero Gaussians, or -- inside a deferred_checks() block once a
     pair capacity is known for this image size -- the whole forward pass was queued by ONE library call
-    (gsplat_forward_deferred) and the result is there."""
+    (gsplat_forward_deferred) and the result is there.  view.pose (set by _RenderFn): the backward pass will also form dL/dc2w
+    (a pose frame: always the separate library calls, never a gradient route)."""
+    pose = getattr(view, "pose", False)
+    if pose and _route.get() is not None:
+        raise RuntimeError("a camera-pose gradient (c2w.requires_grad) is not available inside a gradient_route() block "
+                           "(factored exchange, folded f_rest step, accumulate_grads): render the pose frame outside it")
     lib = _abi.lib()
     dev = pos.device
     n = pos.shape[0]
     pos32, opa32, c2w32, ins = _convert_inputs(fused, n, pos, opacity_raw, c2w, a, b, c, d)
     fr = _new_frame(fused, view, n, pos32, opa32, c2w32, ins, c, d)
+    fr.pose = pose
     if n == 0:      # nothing survives by construction: the reference returns the zero image (render.py:109-112)
         fr.empty = True
         fr.route = _route_of(fr, False) if need_grad else None
@@ -413,7 +419,7 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
     pinned, slot = _ws.next_pinned(dev, key, chk)
     ready = _ws.get_event(dev, fresh=deferred, key=key)
     wants_stages = _timer is not None and _timer.wants(_FORWARD_STAGES)
-    composite = deferred and _composite and not wants_stages
+    composite = deferred and _composite and not wants_stages and not pose
     fr.route = _route_of(fr, composite) if need_grad else None
     if composite:
         # ---- the whole forward pass in one call, on one arena
@@ -637,8 +643,9 @@ _SH = ("f_dc", "f_rest")
 _GRAD_FIELDS = tuple(name for name, _ in _abi.GaussianGrads._fields_)
 
 
-def _backward_impl(fr, grad_image):
-    """Returns a dict name -> fp32 gradient tensor of the inputs of the forward call (a missing name: fr.route took that gradient)."""
+def _backward_impl(fr, grad_image, need_params=True):
+    """Returns a dict name -> fp32 gradient tensor of the inputs of the forward call (a missing name: fr.route took that gradient);
+    a pose frame adds "c2w" (fp32 [4, 4]).  need_params = False (pose frames): only the pose gradient is wanted."""
     lib = _abi.lib()
     ins, route = fr.inputs, fr.route
     dev = ins["pos"].device
@@ -646,7 +653,10 @@ def _backward_impl(fr, grad_image):
     if fr.empty or fr.n == 0:
         if factored:
             route.add(torch.zeros((fr.n, 3), dtype=torch.float32, device=dev), fr.c2w[:3, 3])
-        return {k: torch.zeros_like(v) for k, v in ins.items() if not (factored and k in _SH)}
+        out = {k: torch.zeros_like(v) for k, v in ins.items() if not (factored and k in _SH)}
+        if fr.pose:
+            out["c2w"] = torch.zeros((4, 4), dtype=torch.float32, device=dev)
+        return out
     gi = _f32(grad_image, (fr.view.H, fr.view.W, 3), "grad_image")
     if torch.cuda.current_device() != dev.index:
         torch.cuda.set_device(dev)
@@ -662,6 +672,8 @@ def _backward_impl(fr, grad_image):
     folded = route is not None and not (factored or summing or staged or route.applied)          # optim._RestUpdate
     if summed:
         dst, add = route.begin(stream)
+    elif fr.pose and not need_params:
+        dst = {}
     else:
         dst = _flat_like({k: v for k, v in ins.items() if not (factored and k in _SH or folded and k == "f_rest")})
     gg = _abi.GaussianGrads(*map(_p, map(dst.get, _GRAD_FIELDS)))
@@ -680,6 +692,18 @@ def _backward_impl(fr, grad_image):
             _abi.check(lib.gsplat_logit_grad(fr.n, C.byref(fr.view), _p(fr.proj_state), _p(grad2d), _p(glogit), st), "gsplat_logit_grad")
             route.add(glogit, fr.c2w[:3, 3])
         g = _make_gaussians(fr.n, **ins)
+        if fr.pose:
+            # the same chain rule plus dL/dc2w: per-block rows of the pose terms, added in a fixed order (no gradient rows if
+            # nothing but the pose is wanted)
+            gc2w = torch.empty((4, 4), dtype=torch.float32, device=dev)
+            nbytes = lib.gsplat_pose_scratch_bytes(fr.n)
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            with _stage("project_backward"):
+                _abi.check(lib.gsplat_project_backward_pose(C.byref(g), _p(fr.c2w), C.byref(fr.view), _p(fr.proj_state), _p(grad2d),
+                                                            C.byref(gg) if need_params else None, _p(gc2w), _p(scratch), nbytes, jac,
+                                                            st), "gsplat_project_backward_pose")
+            dst = dict(dst, c2w=gc2w)
+            return dst
         with _stage("project_backward"):
             _abi.check(lib.gsplat_project_backward(C.byref(g), _p(fr.c2w), C.byref(fr.view), _p(fr.proj_state), _p(grad2d),
                                                    C.byref(gg), jac, st), "gsplat_project_backward")
@@ -729,15 +753,17 @@ def sh_accumulate(pos, eyes, grad_logit, scale=1.0):
 
 
 class _RenderFn(torch.autograd.Function):
-    """Autograd node for both entry points; gradients for the tensor inputs only (c2w and scalars get None)."""
+    """Autograd node for both entry points; gradients for the tensor inputs, c2w included (the scalars get None)."""
 
     @staticmethod
     def forward(ctx, fused, view, c2w, pos, opacity_raw, a, b, c, d):
         # needs_input_grad ignores the grad mode (and forward() itself always runs with grad disabled): the caller's grad mode
         # travels in view.grad_mode.  Under torch.no_grad() nothing is saved for a backward that cannot come.
         need = view.grad_mode and any(ctx.needs_input_grad)
+        view.pose = bool(view.grad_mode and ctx.needs_input_grad[2])     # a pose frame: c2w wants a gradient too (Python-side attribute)
         image, fr, counts = _forward_impl(fused, view, c2w, pos, opacity_raw, a, b, c, d, need)
         ctx.frame = fr
+        ctx.c2w_dtype = c2w.dtype
         ctx.dtypes = [t.dtype if isinstance(t, torch.Tensor) else None for t in (pos, opacity_raw, a, b, c, d)]
         ctx.opa_shape = opacity_raw.shape
         global _last_counts, _last_binned
@@ -749,7 +775,7 @@ class _RenderFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_image):
         fr = ctx.frame
-        g = _backward_impl(fr, grad_image)
+        g = _backward_impl(fr, grad_image, any(ctx.needs_input_grad[3:]))
         names = ("pos", "opacity_raw") + (("scale_raw", "q_raw", "f_dc", "f_rest") if fr.fused else ("color", "sigma", None, None))
         outs = []
         for i, nm in enumerate(names):
@@ -757,7 +783,10 @@ class _RenderFn(torch.autograd.Function):
             if t is not None and nm == "opacity_raw":
                 t = t.reshape(ctx.opa_shape)
             outs.append(t if t is None or ctx.dtypes[i] == torch.float32 else t.to(ctx.dtypes[i]))
-        return (None, None, None, *outs)
+        gc2w = g.get("c2w") if ctx.needs_input_grad[2] else None
+        if gc2w is not None and ctx.c2w_dtype != torch.float32:
+            gc2w = gc2w.to(ctx.c2w_dtype)
+        return (None, None, gc2w, *outs)
 
 
 def _view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff):
@@ -776,9 +805,11 @@ def render(pos, color, opacity_raw, sigma, c2w, H, W, fx, fy, cx, cy, near=0.01,
            min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128.):
     """Drop-in for the reference render() (gaussian_splatting/render.py:62-410).
 
-    Returns the image [H, W, 3] in [0, 1], same dtype/device as `pos`, differentiable w.r.t. pos, color, opacity_raw
-    and sigma.  No opacity / frustum / finite survivor -> zero image with zero gradients; survivors but none on
-    screen -> Exception("All projected points are off-screen"), as in the reference.
+    Returns the image [H, W, 3] in [0, 1], same dtype/device as `pos`, differentiable w.r.t. pos, color, opacity_raw,
+    sigma and the camera pose c2w (c2w.requires_grad: dL/dc2w [4, 4] in c2w's dtype, last row 0; such a frame always takes
+    the separate library calls and may not be rendered inside a gradient_route() block).  No opacity / frustum / finite
+    survivor -> zero image with zero gradients; survivors but none on screen -> Exception("All projected points are
+    off-screen"), as in the reference.
     """
     view = _view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff)
     return _RenderFn.apply(False, view, c2w, pos, opacity_raw, color, sigma, None, None)
@@ -787,7 +818,9 @@ def render(pos, color, opacity_raw, sigma, c2w, H, W, fx, fy, cx, cy, near=0.01,
 def render_gaussians(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2w, H, W, fx, fy, cx, cy, near=0.01, far=100.0,
                      pix_guard=32, T=16, min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128.):
     """Fused entry: render(pos, evaluate_sh(f_dc, f_rest, pos, c2w), opacity_raw, build_sigma_from_params(scale_raw,
-    q_raw), c2w, ...) in one pass (the reference's three-call sequence, scripts/train.py:463,502,505-508)."""
+    q_raw), c2w, ...) in one pass (the reference's three-call sequence, scripts/train.py:463,502,505-508).  Differentiable
+    w.r.t. the six parameter tensors and c2w (through the camera transform, the covariance rotation and the SH view
+    direction), as render() is."""
     view = _view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff)
     return _RenderFn.apply(True, view, c2w, pos, opacity_raw, scale_raw, q_raw, f_dc, f_rest)
 
@@ -916,7 +949,7 @@ class _EvaluateShFn(torch.autograd.Function):
             _abi.check(lib.gsplat_evaluate_sh(n, _p(dc), _p(rest), _p(pts), _p(cam), _p(out), _stream_ptr(pts.device)),
                        "gsplat_evaluate_sh")
         ctx.save_for_backward(dc, rest, pts, cam)
-        ctx.dtypes = (f_dc.dtype, f_rest.dtype, points.dtype)
+        ctx.dtypes = (f_dc.dtype, f_rest.dtype, points.dtype, c2w.dtype)
         return out if points.dtype == torch.float32 else out.to(points.dtype)
 
     @staticmethod
@@ -929,12 +962,18 @@ class _EvaluateShFn(torch.autograd.Function):
         with torch.cuda.device(pts.device):
             _abi.check(lib.gsplat_evaluate_sh_backward(n, _p(dc), _p(rest), _p(pts), _p(cam), _p(gc), _p(gdc), _p(grest),
                                                        _p(gpts), _stream_ptr(pts.device)), "gsplat_evaluate_sh_backward")
-        return gdc.to(ctx.dtypes[0]), grest.to(ctx.dtypes[1]), gpts.to(ctx.dtypes[2]), None
+        gc2w = None
+        if ctx.needs_input_grad[3]:
+            # the colour depends on c2w only through the direction p - c2w[:3,3]: dL/dc2w[:3,3] = -sum dL/dp, the rest is 0
+            gc2w = torch.zeros((4, 4), dtype=ctx.dtypes[3], device=pts.device)
+            gc2w[:3, 3] = -gpts.double().sum(0).to(ctx.dtypes[3])
+        return gdc.to(ctx.dtypes[0]), grest.to(ctx.dtypes[1]), gpts.to(ctx.dtypes[2]), gc2w
 
 
 def evaluate_sh(f_dc, f_rest, points, c2w):
     """Drop-in for the reference evaluate_sh (gaussian_splatting/spherical_harmonics.py:70-166): degree-3 real SH,
-    channel-major f_rest, sigmoid output."""
+    channel-major f_rest, sigmoid output.  Differentiable w.r.t. f_dc, f_rest, points and c2w (only its translation column
+    moves the colour: dL/dc2w[:3,3] = -sum dL/dpoints)."""
     return _EvaluateShFn.apply(f_dc, f_rest, points, c2w)
 
 

@@ -16,6 +16,6 @@ check-asan:
 	LD_PRELOAD="$$(gcc -print-file-name=libasan.so) $$(gcc -print-file-name=libubsan.so)" ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 \
 	  UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 OMP_NUM_THREADS=4 \
 	  GSPLAT_HOSTMATH_LIB=$(CURDIR)/$(ASAN_DIR)/libgsmath_host_asan.so GS_ORACLE_LIB=$(CURDIR)/$(ASAN_DIR)/libgs_oracle_asan.so \
-	  python -m pytest tests/test_product_math_cpu.py tests/test_c_oracle_golden.py -x -q -p no:cacheprovider
+	  python -m pytest tests/test_product_math_cpu.py tests/test_pose_grad_cpu.py tests/test_c_oracle_golden.py -x -q -p no:cacheprovider
 
 .PHONY: all check-asan

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define GSPLAT_ABI_VERSION 9
+#define GSPLAT_ABI_VERSION 10
 
 /* call status */
 #define GSPLAT_OK 0
@@ -198,6 +198,19 @@ int gsplat_rasterize_backward(int64_t n, int64_t pair_capacity, const gsplat_vie
 int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v,
                             const void* project_state, const float* grad2d, const gsplat_gaussian_grads* out,
                             int32_t flags, void* stream);
+
+/* gsplat_project_backward plus the gradient w.r.t. the camera pose: grad_c2w[16] (device, row-major 4 x 4) receives dL/dc2w of
+ * the same grad2d (render.py:122,156-159 and spherical_harmonics.py:132 differentiated w.r.t. c2w; its last row is 0).
+ *   out            as for gsplat_project_backward (all gradients of the inputs, not factored), or NULL: the pose gradient only.
+ *   pose_scratch   gsplat_pose_scratch_bytes(n) bytes, 64-byte aligned, caller-owned; nothing needs clearing.
+ *   flags          GSPLAT_BACKWARD_SH_JACOBIAN only; any other bit is refused with GSPLAT_ERR_BAD_ARG.
+ * The per-Gaussian terms are added in a fixed order, without atomics: the same inputs give the same bits.  NULL grad_c2w is
+ * GSPLAT_ERR_BAD_ARG, a scratch below the size GSPLAT_ERR_WORKSPACE.                                                       */
+int64_t gsplat_pose_scratch_bytes(int64_t n);
+int gsplat_project_backward_pose(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v,
+                                 const void* project_state, const float* grad2d, const gsplat_gaussian_grads* out,
+                                 float* grad_c2w, void* pose_scratch, int64_t pose_scratch_bytes, int32_t flags,
+                                 void* stream);
 
 /* ---- composite entries: one call per direction ----------------------------------------------------------------------
  * For a host that does not wait for the counters in the middle of the forward pass (a training loop, a frame sequence:
