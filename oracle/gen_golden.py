@@ -251,6 +251,77 @@ def gen_loss():
     save("loss", **out)
 
 
+LOSS_EDGE_CASES = ("smooth", "flat_bright", "flat_dark", "saturated", "equal_random", "equal_ones", "opposite", "batch3")
+LOSS_EDGE_SSIM_ONLY = ("smooth", "flat_bright", "flat_dark")      # cases about the SSIM term: also with lambdas (0, 1)
+
+
+def _loss_edge_inputs(tag, rng, H, W):
+    """(pred, target) of one loss_edges case, float32 [H, W, 3]."""
+    f32 = np.float32
+    yy, xx = np.meshgrid(np.arange(H) / max(H - 1, 1), np.arange(W) / max(W - 1, 1), indexing="ij")
+    if tag == "smooth":            # what a converged render looks like: low-frequency ramps and sinusoids, pred within 2e-3 of it
+        tgt = np.stack([0.15 + 0.7 * xx, 0.5 + 0.35 * np.sin(2.3 * yy + 1.1 * xx), 0.6 - 0.4 * yy * xx + 0.1 * np.cos(3.0 * xx)], -1)
+        tgt = np.clip(tgt, 0, 1).astype(f32)
+        return np.clip(tgt + rng.normal(0, 2e-3, tgt.shape), 0, 1).astype(f32), tgt
+    if tag in ("flat_bright", "flat_dark"):
+        tgt = np.full((H, W, 3), 0.97 if tag == "flat_bright" else 0.02, dtype=f32)
+        return np.clip(tgt + rng.normal(0, 1e-3, tgt.shape), 0, 1).astype(f32), tgt
+    if tag == "saturated":         # blocks of exactly 0.0 and exactly 1.0 with a soft edge between; the clamp makes many pixels bit-equal
+        edge = [np.clip((xx - 0.5) * W / 6.0 + 0.5, 0, 1), np.clip((0.5 - yy) * H / 6.0 + 0.5, 0, 1),
+                np.clip((xx + yy - 1.0) * (H + W) / 16.0 + 0.5, 0, 1)]
+        tgt = np.stack(edge, -1).astype(f32)
+        return np.clip(tgt + rng.normal(0, 1e-3, tgt.shape), 0, 1).astype(f32), tgt
+    if tag == "equal_random":
+        tgt = rng.uniform(0, 1, (H, W, 3)).astype(f32)
+        return tgt.copy(), tgt
+    if tag == "equal_ones":
+        return np.ones((H, W, 3), f32), np.ones((H, W, 3), f32)
+    if tag == "opposite":
+        return np.zeros((H, W, 3), f32), np.ones((H, W, 3), f32)
+    raise KeyError(tag)
+
+
+def gen_loss_edges():
+    """Fixture of the loss in the regime training converges to (smooth, flat, saturated, equal images), where
+    sigma^2 = E[x^2] - mu^2 cancels: compute_loss (gaussian_splatting/losses.py:158-185) forward + d/dpred in float64 (the
+    expected values) and in float32 (the reference's own error there = the calibration of tests/util.py).
+    Keys per case: pred_, target_ (fp32), vals_, grad_ (fp64), vals32_, grad32_ (the fp32 run; grad32_ stored as fp32); the same with
+    the suffix __ssim for lambdas (0, 1)."""
+    print("loss_edges")
+    import importlib
+    losses = importlib.import_module("gaussian_splatting.losses")
+    rng = np.random.default_rng(412)
+    # every size crosses the 32 x 16 tile borders of the kernel in both directions
+    sizes = {"smooth": (34, 66), "flat_bright": (18, 40), "flat_dark": (18, 40), "saturated": (24, 40), "equal_random": (18, 35),
+             "equal_ones": (18, 35), "opposite": (18, 35), "batch3": (17, 33)}
+    out = {"cases": np.array(LOSS_EDGE_CASES), "ssim_only_cases": np.array(LOSS_EDGE_SSIM_ONLY)}
+    for tag in LOSS_EDGE_CASES:
+        H, W = sizes[tag]
+        if tag == "batch3":
+            pairs = [_loss_edge_inputs(t, rng, H, W) for t in ("smooth", "flat_bright", "saturated")]
+            pred, tgt = np.stack([p for p, _ in pairs]), np.stack([t for _, t in pairs])
+        else:
+            pred, tgt = _loss_edge_inputs(tag, rng, H, W)
+        out.update({f"pred_{tag}": pred, f"target_{tag}": tgt})
+        for lam, sfx in (((0.8, 0.2), ""), ((0.0, 1.0), "__ssim")):
+            if sfx and tag not in LOSS_EDGE_SSIM_ONLY:
+                continue
+            res = {}
+            for dtype, key in ((torch.float64, ""), (torch.float32, "32")):
+                p = _t(pred, dtype, True)
+                total, parts = losses.compute_loss(p, _t(tgt, dtype), *lam)
+                total.backward()
+                res[key] = (np.array([parts["l1"], parts["ssim"], parts["total"]], dtype=np.float64), p.grad.numpy())
+                out[f"vals{key}_{tag}{sfx}"] = res[key][0]
+                out[f"grad{key}_{tag}{sfx}"] = res[key][1]
+            (v64, g64), (v32, g32) = res[""], res["32"]
+            gn = np.linalg.norm(g64)
+            print(f"  {tag}{sfx} {pred.shape}: l1 {v64[0]:.3e} ssim-loss {v64[1]:.3e} total {v64[2]:.3e}; fp32: |d ssim| {abs(v32[1] - v64[1]):.2e} "
+                  f"|d total| {abs(v32[2] - v64[2]):.2e}, grad rel-L2 {np.linalg.norm(g32 - g64) / gn if gn > 1e-12 else float('nan'):.2e} "
+                  f"max|g64| {np.abs(g64).max():.2e} max|g32| {np.abs(g32).max():.2e}")
+    save("loss_edges", **out)
+
+
 def gen_optim():
     """Next-row fixture: the optimiser step at the reference's call sites (scripts/train.py:394-401 Adam groups with
     eps = 1e-15, :446-457 position-LR schedule, :536 clip_grad_norm_(pos, 1.0), :538 optimizer.step()), run with
@@ -465,6 +536,8 @@ if __name__ == "__main__":
         gen_config1()
     if not want or "loss" in want:
         gen_loss()
+    if not want or "loss_edges" in want:
+        gen_loss_edges()
     if not want or "optim" in want:
         gen_optim()
     if not want or "harness" in want:

@@ -99,6 +99,80 @@ def test_bad_arguments_are_rejected_without_touching_the_gpu():
     assert b"state is NULL" in lib.gsplat_last_error()
 
 
+def _host_words(n=16):
+    """A non-NULL address for an argument check to look at; every call below is refused on the host before anything is launched."""
+    buf = (C.c_float * n)()
+    return buf, C.cast(buf, C.c_void_p)
+
+
+def _refused(lib, status, name):
+    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, status)
+    assert name.encode() in lib.gsplat_last_error(), (name, lib.gsplat_last_error())
+
+
+def test_loss_entries_reject_bad_arguments_on_the_host():
+    """gsplat_loss / gsplat_loss_forward / gsplat_loss_backward: a NULL required pointer, H, W or batch <= 0 and batch > 65535 (the
+    grid's z extent) come back as GSPLAT_ERR_BAD_ARG with a message naming the entry."""
+    lib = abi.lib()
+    keep, p = _host_words()
+
+    def loss(pred=p, target=p, batch=1, H=4, W=4, values=p, grad=p, scratch=p):
+        return lib.gsplat_loss(pred, target, batch, H, W, 0.8, 0.2, values, grad, scratch, None)
+
+    def fwd(pred=p, target=p, batch=1, H=4, W=4, values=p, total=p, scratch=p):
+        return lib.gsplat_loss_forward(pred, target, batch, H, W, 0.8, 0.2, 1.0, values, total, scratch, 1, None)
+
+    def bwd(pred=p, target=p, batch=1, H=4, W=4, upstream=p, grad=p, scratch=p):
+        return lib.gsplat_loss_backward(pred, target, batch, H, W, 0.8, 0.2, 1.0, upstream, grad, scratch, None)
+
+    for fn, name, required in ((loss, "gsplat_loss", ("pred", "target", "values", "scratch")),
+                               (fwd, "gsplat_loss_forward", ("pred", "target", "values", "scratch")),
+                               (bwd, "gsplat_loss_backward", ("pred", "target", "grad", "scratch"))):
+        for arg in required:
+            _refused(lib, fn(**{arg: None}), name)
+        for bad in (dict(H=0), dict(H=-3), dict(W=0), dict(W=-1), dict(batch=0), dict(batch=-2), dict(batch=65536), dict(batch=1 << 40)):
+            _refused(lib, fn(**bad), name)
+    del keep
+
+
+def test_optimiser_entries_reject_bad_arguments_on_the_host():
+    lib = abi.lib()
+    keep, p = _host_words()
+    _refused(lib, lib.gsplat_clip_grad_norm(-1, p, 1.0, p, p, None), "gsplat_clip_grad_norm")
+    _refused(lib, lib.gsplat_clip_grad_norm(4, None, 1.0, p, p, None), "gsplat_clip_grad_norm")
+    _refused(lib, lib.gsplat_clip_grad_norm(4, p, 1.0, None, p, None), "gsplat_clip_grad_norm")
+    nine = (abi.AdamGroup * 9)(*[abi.AdamGroup(0, None, None, None, None, 0.01, 1, None) for _ in range(9)])
+    _refused(lib, lib.gsplat_adam_step_multi(9, nine, 0.9, 0.999, 1e-15, None), "gsplat_adam_step_multi")
+    assert lib.gsplat_adam_step_multi(8, nine, 0.9, 0.999, 1e-15, None) == abi.GSPLAT_OK       # eight empty groups: nothing to launch
+    _refused(lib, lib.gsplat_adam_step_multi(-1, nine, 0.9, 0.999, 1e-15, None), "gsplat_adam_step_multi")
+    _refused(lib, lib.gsplat_adam_step_multi(1, None, 0.9, 0.999, 1e-15, None), "gsplat_adam_step_multi")
+    for bad in (abi.AdamGroup(0, None, None, None, None, 0.01, 0, None),             # step < 1 (the bias correction divides by 1 - b^step)
+                abi.AdamGroup(4, p, p, p, p, 0.01, -1, None),
+                abi.AdamGroup(-1, p, p, p, p, 0.01, 1, None),                        # n < 0
+                abi.AdamGroup(4, p, None, p, p, 0.01, 1, None)):                     # a NULL array of a non-empty group
+        two = (abi.AdamGroup * 2)(abi.AdamGroup(0, None, None, None, None, 0.01, 1, None), bad)
+        _refused(lib, lib.gsplat_adam_step_multi(2, two, 0.9, 0.999, 1e-15, None), "gsplat_adam_step_multi")
+        assert b"group 1" in lib.gsplat_last_error()
+    _refused(lib, lib.gsplat_adam_step(-1, p, p, p, p, 0.01, 0.9, 0.999, 1e-15, 1, None, None), "gsplat_adam_step")
+    _refused(lib, lib.gsplat_adam_step(4, p, p, p, p, 0.01, 0.9, 0.999, 1e-15, 0, None, None), "gsplat_adam_step")
+    _refused(lib, lib.gsplat_adam_step(4, p, p, None, p, 0.01, 0.9, 0.999, 1e-15, 1, None, None), "gsplat_adam_step")
+    del keep
+
+
+def test_loss_scratch_bytes_matches_the_layout_in_the_source():
+    """gsplat_loss_scratch_bytes = [two partial sums per 32 x 16 tile and image, rounded up to 256 bytes | with_grad: the nine
+    partial-derivative planes, batch x 9 x H x W floats] (csrc/gsplat_loss.hip); -1 for a size that is none."""
+    lib = abi.lib()
+    for batch, H, W in ((1, 1, 1), (3, 17, 33), (2, 1080, 1920), (1, 16, 32), (65535, 16, 32)):
+        tiles = batch * ((W + 31) // 32) * ((H + 15) // 16)
+        sums = 256 * ((tiles * 2 * 4 + 255) // 256)
+        assert lib.gsplat_loss_scratch_bytes(batch, H, W, 0) == sums
+        assert lib.gsplat_loss_scratch_bytes(batch, H, W, 1) == sums + batch * 9 * H * W * 4
+    for batch, H, W in ((0, 4, 4), (1, 0, 4), (1, 4, 0), (-1, 4, 4), (1, -4, 4)):
+        assert lib.gsplat_loss_scratch_bytes(batch, H, W, 1) == -1
+    assert lib.gsplat_clip_scratch_bytes() == 1024 * 4
+
+
 def test_unknown_backward_flags_are_refused_before_anything_else():
     """A flag bit a backward entry does not define is refused first (with host arguments only: nothing reaches the GPU), so that
     a library that does not know a flag cannot quietly do something else -- overwrite where the caller adds, say."""

@@ -156,3 +156,21 @@ def test_loss_vs_reference():
         t2.backward()
         assert abs(float(t2) - float(d["total2_" + tag])) < 1e-13
         assert np.abs(p2.grad.numpy() - d["grad2_" + tag]).max() < 1e-13
+
+
+def test_loss_edges_vs_reference():
+    """The flat / smooth / saturated / equal regime of tests/golden/loss_edges.npz (sigma^2 = E[x^2] - mu^2 cancels there): the oracle
+    in float64 reproduces the reference's float64 values and gradients to the tolerances of test_loss_vs_reference, so the GPU tests
+    may use it at run time in that regime too."""
+    d = dict(np.load(util.GOLDEN + "/loss_edges.npz"))
+    assert len(d["cases"]) == 8
+    for tag in d["cases"]:
+        for lam, sfx in (((0.8, 0.2), ""), ((0.0, 1.0), "__ssim")):
+            if sfx and tag not in d["ssim_only_cases"]:
+                continue
+            p = torch.tensor(d["pred_" + tag], dtype=F64, requires_grad=True)
+            t = torch.tensor(d["target_" + tag], dtype=F64)
+            total, l1, sl = tp.compute_loss(p, t, *lam)
+            total.backward()
+            assert np.allclose([float(l1), float(sl), float(total)], d[f"vals_{tag}{sfx}"], rtol=1e-12, atol=1e-14), (tag, sfx)
+            assert np.abs(p.grad.numpy() - d[f"grad_{tag}{sfx}"]).max() < 1e-14, (tag, sfx)
