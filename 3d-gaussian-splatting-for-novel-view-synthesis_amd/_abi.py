@@ -16,7 +16,7 @@ GSPLAT_ERR_WORKSPACE = 3
 GSPLAT_SCENE_OK = 0
 GSPLAT_SCENE_ALL_CULLED = 10
 GSPLAT_SCENE_ALL_OFFSCREEN = 11
-ABI_VERSION = 10
+ABI_VERSION = 11
 GSPLAT_PROJECT_COLOUR_FUSED = 1
 GSPLAT_PROJECT_COUNTS_MAPPED = 2
 GSPLAT_PROJECT_SAVE_SH_JACOBIAN = 4
@@ -61,6 +61,16 @@ class Counts(C.Structure):
                 ("max_tiles_per_gaussian", C.c_int32), ("reserved", C.c_int32), ("n_binned", C.c_int64)]
 
 
+class StateLayout(C.Structure):
+    """gsplat_state_layout: byte offsets inside project_state (tests and tools only, no stable contract)."""
+    _fields_ = [("bytes", C.c_int64), ("lists", C.c_int64), ("lists_x", C.c_int32), ("lists_y", C.c_int32)] + [
+        (k, C.c_int64) for k in ("counts", "rec", "rect", "depth", "tiles", "mask", "ranges", "order", "class_bounds", "kj")]
+
+
+class BinLayout(C.Structure):
+    _fields_ = [("bytes", C.c_int64), ("sorted_ids", C.c_int64), ("pair_mask", C.c_int64)]
+
+
 _VP, _I64, _INT = C.c_void_p, C.c_int64, C.c_int
 _PV, _PG, _PGG, _PC = C.POINTER(View), C.POINTER(Gaussians), C.POINTER(GaussianGrads), C.POINTER(Counts)
 
@@ -73,6 +83,8 @@ SIGNATURES = {
     "gsplat_project_scratch_bytes": (_I64, [_I64]),
     "gsplat_bin_state_bytes": (_I64, [_I64, _PV]),
     "gsplat_bin_scratch_bytes": (_I64, [_I64, _PV]),
+    "gsplat_project_state_layout": (_INT, [_I64, _PV, C.POINTER(StateLayout)]),
+    "gsplat_bin_state_layout": (_INT, [_I64, _PV, C.POINTER(BinLayout)]),
     "gsplat_project": (_INT, [_PG, _VP, _PV, _VP, _VP, _I64, _VP, _VP, C.c_int32, _VP]),
     "gsplat_bin": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _I64, _VP]),
     "gsplat_rasterize_forward": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP, _VP, _VP]),

@@ -151,13 +151,14 @@ GS_HD void cov_from_params_backward(const float q_raw[4], const CovMid& m, const
     // q = q_raw / (n + eps)
     const float ne = m.qn + 1e-9f;
     const float dot = dq[0] * q_raw[0] + dq[1] * q_raw[1] + dq[2] * q_raw[2] + dq[3] * q_raw[3];
-    if (m.qn > 1e-4f) {
+    if (m.qn > 1e-2f) {
         // The same gradient without the cancellation.  A rotation of the Gaussian's own axes by d phi changes
         // Sigma = R D R^T by R [[d phi]x, D] R^T, so dL = tau . d phi with the torque (body frame, G' = R^T G R)
         //     tau_x = 2 G'_12 (d_1 - d_2),  tau_y = 2 G'_02 (d_2 - d_0),  tau_z = 2 G'_01 (d_0 - d_1):
         // proportional to the scale differences by construction (exactly zero for equal scales).  A unit quaternion moves by
         // dq = 1/2 q (x) (d phi, 0), whose 4 x 3 matrix M(q) has orthonormal columns: the tangential gradient is 2 M(q) tau.
-        // q is a unit quaternion up to eps / |q_raw| = 1e-9 / n here (n > 1e-4: below fp32 resolution).  What the
+        // q is a unit quaternion up to eps / |q_raw| = 1e-9 / n here, and the torque form is off by ~4 eps / n: n > 1e-2 keeps
+        // that at 4e-7, fp32 rounding (at the earlier n > 1e-4 it was 4e-5 just above the branch).  What the
         // normalisation does to the RADIAL part of dL/dq -- it survives with the factor eps / (n + eps)^2 -- is kept from the
         // chain-rule form, where it is a plain sum.
         const float gp01 = R[0] * GR[1] + R[3] * GR[4] + R[6] * GR[7];
@@ -174,7 +175,7 @@ GS_HD void cov_from_params_backward(const float q_raw[4], const CovMid& m, const
         for (int k = 0; k < 4; ++k) g_q_raw[k] = gt[k] / ne + q_raw[k] * radial;
         return;
     }
-    // tiny |q_raw| (comparable with the reference's eps): R(q) is not a rotation there; the plain chain rule
+    // small |q_raw| (the reference's eps is more than fp32 rounding beside it): R(q) is not a rotation there; the plain chain rule
     const float c = (m.qn > 0.f) ? dot / (m.qn * ne * ne) : 0.f;
     for (int k = 0; k < 4; ++k) g_q_raw[k] = dq[k] / ne - q_raw[k] * c;
 }

@@ -2590,6 +2590,30 @@ int64_t gsplat_bin_scratch_bytes(int64_t pair_capacity, const gsplat_view* v) {
     return carve_bin_scratch(nullptr, pair_capacity, n_bins(n_lists(v))).bytes;
 }
 
+// For tests and tools (see the header): the offsets carve_project / pair_mask_of give, so that nobody mirrors them.
+int gsplat_project_state_layout(int64_t n, const gsplat_view* v, gsplat_state_layout* out) {
+    if (!v || !out) return fail(GSPLAT_ERR_BAD_ARG, "gsplat_project_state_layout: view / out is NULL");
+    if (v->H <= 0 || v->W <= 0 || n < 0) return fail(GSPLAT_ERR_BAD_ARG, "gsplat_project_state_layout: image size must be positive, n >= 0");
+    const int64_t nl = n_lists(v);
+    const ProjectState s = carve_project(nullptr, n > 0 ? n : 1, nl);
+    const auto off = [](const void* p) { return (int64_t)reinterpret_cast<intptr_t>(p); };
+    out->bytes = s.bytes; out->lists = nl;
+    out->lists_x = (v->W + LIST_W - 1) / LIST_W; out->lists_y = (v->H + LIST_H - 1) / LIST_H;
+    out->counts = off(s.counts); out->rec = off(s.rec); out->rect = off(s.rect); out->depth = off(s.depth); out->tiles = off(s.tiles);
+    out->mask = off(s.mask); out->ranges = off(s.ranges); out->order = off(s.order); out->class_bounds = off(s.class_bounds);
+    out->kj = off(s.kj);
+    return GSPLAT_OK;
+}
+
+int gsplat_bin_state_layout(int64_t pair_capacity, const gsplat_view* v, gsplat_bin_layout* out) {
+    if (!v || !out) return fail(GSPLAT_ERR_BAD_ARG, "gsplat_bin_state_layout: view / out is NULL");
+    if (pair_capacity < 0) return fail(GSPLAT_ERR_BAD_ARG, "gsplat_bin_state_layout: pair_capacity must be >= 0");
+    out->bytes = gsplat_bin_state_bytes(pair_capacity, v);
+    out->sorted_ids = 0;
+    out->pair_mask = (int64_t)reinterpret_cast<intptr_t>(pair_mask_of(nullptr, pair_capacity));
+    return GSPLAT_OK;
+}
+
 int gsplat_project(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, void* project_state, void* scratch,
                    int64_t scratch_bytes, gsplat_counts* counts_host, void* counts_event, int32_t flags, void* stream_) {
     bool fused = false;

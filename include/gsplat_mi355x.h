@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define GSPLAT_ABI_VERSION 10
+#define GSPLAT_ABI_VERSION 11
 
 /* call status */
 #define GSPLAT_OK 0
@@ -114,6 +114,31 @@ int64_t gsplat_project_scratch_bytes(int64_t n);     /* persistent counter block
 int64_t gsplat_bin_state_bytes(int64_t pair_capacity, const gsplat_view* v);   /* kept until the backward pass   */
 int64_t gsplat_bin_scratch_bytes(int64_t pair_capacity, const gsplat_view* v); /* free after gsplat_bin          */
 
+/* ---- layout queries: FOR TESTS AND TOOLS ONLY ---------------------------------------------------
+ * Where the arrays a test wants to look at lie inside project_state / bin_state (byte offsets from the start of the buffer).
+ * Pure host functions, nothing is launched.  NOT a stable contract: the carving stays private to the library, the offsets
+ * and the set of arrays may change with any version; a product host never needs them.
+ *   rec           [n][16] floats: u, v, A11, A12 | A22, opacity, ex, ey | r, g, b, depth | the row-span constants
+ *   rect          [n][2] uint32: x0 | y0 << 16, x1 | y1 << 16 -- inclusive rectangle of 16 x 8-pixel lists
+ *   depth [n] float, tiles [n] uint32 (lists the Gaussian is binned to; 0 = culled), mask [n] uint32 (bit k = list k of the
+ *                 rectangle, row-major; all ones for rectangles of more than 32 lists)
+ *   ranges        [lists][2] uint32 start, end in sorted_ids; order [lists] uint32; class_bounds [8] uint32; kj [n][12] floats
+ *   counts        the device copy of gsplat_counts
+ *   sorted_ids    [pair_capacity] uint32; pair_mask [pair_capacity] bytes (written by gsplat_rasterize_forward with `accum`)
+ * Return GSPLAT_OK, or GSPLAT_ERR_BAD_ARG (NULL view / out, non-positive image size, negative n or pair_capacity).          */
+typedef struct gsplat_state_layout {
+    int64_t bytes;                /* = gsplat_project_state_bytes(n, v)                                  */
+    int64_t lists;                /* lists_x * lists_y                                                   */
+    int32_t lists_x, lists_y;
+    int64_t counts, rec, rect, depth, tiles, mask, ranges, order, class_bounds, kj;
+} gsplat_state_layout;
+typedef struct gsplat_bin_layout {
+    int64_t bytes;                /* = gsplat_bin_state_bytes(pair_capacity, v)                          */
+    int64_t sorted_ids, pair_mask;
+} gsplat_bin_layout;
+int gsplat_project_state_layout(int64_t n, const gsplat_view* v, gsplat_state_layout* out);
+int gsplat_bin_state_layout(int64_t pair_capacity, const gsplat_view* v, gsplat_bin_layout* out);
+
 /* ---- forward ----------------------------------------------------------------------------------- */
 /* F1-F8, F10, F13 (+F2, F3 when fused): per-Gaussian projection, culls, EWA covariance, eigen clamp,
  * conic, rectangle and mask of 16 x 8-pixel lists, colour; counts the (list, Gaussian) pairs in total and
@@ -157,7 +182,9 @@ int gsplat_project(const gsplat_gaussians* g, const float* c2w, const gsplat_vie
  *                  from earlier frames.  If the frame has more pairs than that, nothing is written out of bounds, the
  *                  frame's image and gradients are garbage, and the caller finds n_binned > pair_capacity in the
  *                  counters whenever it reads them: it then renders the frame again with larger buffers.
- *                  At most 2^32 - 1 pairs; images up to 8192 coarse bins (64 lists each: 8192 x 8192 pixels).          */
+ *                  At most 2^32 - 1 pairs; images up to 8192 coarse bins (64 lists each: 8192 x 8192 pixels).
+ *                  ONE gsplat_bin per gsplat_project: it adds to per-list counters in project_state that only gsplat_project
+ *                  clears (a frame rendered again with larger buffers is projected again).                             */
 int gsplat_bin(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, void* bin_state,
                void* scratch, int64_t scratch_bytes, void* stream);
 

@@ -77,6 +77,21 @@ def test_size_queries_are_pure_host_functions():
     assert lib.gsplat_bin_state_bytes(p, C.byref(v)) >= p * 5                               # sorted ids + one mask byte per pair
     assert lib.gsplat_bin_scratch_bytes(p, C.byref(v)) >= p * 16
     assert lib.gsplat_project_scratch_bytes(n) >= 256 * 64 + 64          # the persistent counter block: 256 shards + the arrival counter
+    # the layout queries (tests and tools only): the arrays lie inside the buffer, in 256-byte steps, without overlap, and the
+    # sizes are the size queries' -- with no GPU in sight
+    lay = abi.StateLayout()
+    assert lib.gsplat_project_state_layout(n, C.byref(v), C.byref(lay)) == abi.GSPLAT_OK
+    assert lay.bytes == lib.gsplat_project_state_bytes(n, C.byref(v)) and lay.lists == lists and (lay.lists_x, lay.lists_y) == (120, 135)
+    need = dict(counts=32, rec=n * 64, rect=n * 8, depth=n * 4, tiles=n * 4, mask=n * 4, ranges=lists * 8, order=lists * 4,
+                class_bounds=32, kj=n * 48)
+    spans = sorted((getattr(lay, k), getattr(lay, k) + b, k) for k, b in need.items())
+    assert spans[0][0] >= 0 and spans[-1][1] <= lay.bytes and all(o % 256 == 0 for o, _, _ in spans)
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), spans
+    bl = abi.BinLayout()
+    assert lib.gsplat_bin_state_layout(p, C.byref(v), C.byref(bl)) == abi.GSPLAT_OK
+    assert bl.bytes == lib.gsplat_bin_state_bytes(p, C.byref(v)) and bl.sorted_ids == 0
+    assert bl.pair_mask >= p * 4 and bl.pair_mask % 256 == 0 and bl.pair_mask + p <= bl.bytes
+    assert lib.gsplat_bin_state_layout(0, C.byref(v), C.byref(bl)) == abi.GSPLAT_OK and bl.bytes == lib.gsplat_bin_state_bytes(0, C.byref(v))
 
 
 def test_scene_classification_mirrors_reference_conventions():
@@ -97,6 +112,14 @@ def test_bad_arguments_are_rejected_without_touching_the_gpu():
     v8 = abi.make_view(64, 64, 50.0, 50.0, 32.0, 32.0, T=8)
     assert lib.gsplat_bin(0, 0, C.byref(v8), None, None, None, 0, None) == 1
     assert b"state is NULL" in lib.gsplat_last_error()
+    lay, bl = abi.StateLayout(), abi.BinLayout()
+    bad = abi.make_view(0, 64, 50.0, 50.0, 32.0, 32.0)
+    for status in (lib.gsplat_project_state_layout(4, None, C.byref(lay)), lib.gsplat_project_state_layout(4, C.byref(v), None),
+                   lib.gsplat_project_state_layout(-1, C.byref(v), C.byref(lay)), lib.gsplat_project_state_layout(4, C.byref(bad), C.byref(lay))):
+        _refused(lib, status, "gsplat_project_state_layout")
+    for status in (lib.gsplat_bin_state_layout(4, None, C.byref(bl)), lib.gsplat_bin_state_layout(4, C.byref(v), None),
+                   lib.gsplat_bin_state_layout(-1, C.byref(v), C.byref(bl))):
+        _refused(lib, status, "gsplat_bin_state_layout")
 
 
 def _host_words(n=16):
