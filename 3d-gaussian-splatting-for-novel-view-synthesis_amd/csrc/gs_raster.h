@@ -1,0 +1,700 @@
+// gs_raster.h -- K6 / K7 raster kernels and the deterministic-mode kernels.
+#pragma once
+#include "gs_layout.h"
+#include "gs_wave.h"
+
+using namespace gsm;
+namespace {
+
+// ---- K6 / K7: rasterizer -----------------------------------------------------------------------------
+// One wave64 per list (16 x 8 pixels).  The wave is EIGHT groups of 8 lanes: group g owns the 4 x 4-pixel sub-tile
+// (g & 3, g >> 2) of the list; lane j of a group owns pixels (j & 3, j >> 2) and (j & 3, (j >> 2) + 2) of the sub-tile, so a
+// lane's two pixels form a float2 and the arithmetic runs on packed fp32 (v_pk_fma_f32 ...).
+//
+// Why groups: a projected Gaussian covers ~57 pixels on the benchmark scene, a list 128: with the whole wave evaluating
+// every list entry only 13 % of the lane evaluations were inside the ellipse, and both raster kernels are VALU-bound.
+// So the wave walks its depth-sorted list 64 entries at a time; lane l fetches entry l's 64-byte record, stages it in LDS
+// (conic pre-scaled for exp2) and tests the entry's bounding box {|du| <= ex, |dv| <= ey} against the 8 sub-tiles; one
+// ballot per sub-tile compacts the touching entries, in depth order, into that sub-tile's queue (LDS, 2-byte record
+// offsets).  In the inner loop every group pops ITS OWN queue: one iteration composites eight different (sub-tile,
+// Gaussian) pairs, 2.7x fewer pixel evaluations than list-wide evaluation (tools/subtile_stats.py); the loop runs to the
+// longest of the 8 queues (queues padded with a null record: opacity 0 -> alpha 0).  A Gaussian missing from a sub-tile's
+// queue has q > chi, i.e. alpha = 0, on all of its pixels: the composite is unchanged term by term.
+// The next chunk's records are fetched while the current chunk is composited.
+//
+// Launch order: block b takes list order[b] (longest first, from plan_kernel), and the first blocks raise their wave
+// priority so that a dense list is not slowed down by light co-resident waves.
+typedef float v2f __attribute__((ext_vector_type(2)));
+// Exact ellipse / sub-tile test at staging time (subtile_mask_exact), measured on one box: the backward, whose iterations cost
+// 2.5x the forward's, gains (217 -> 207 us); the forward loses (85.6 -> 91.5 us) and keeps the box test.
+// (per-chunk partial sums of the colour and the suffix sums: tried and dropped)
+constexpr int CHUNK = 64;                            // list entries staged per round (one per lane)
+constexpr int QCAP = CHUNK + 8;                      // queue capacity: the inner loops read entries in pairs
+constexpr uint32_t NULL_OFF = CHUNK * 16;            // byte offset of the null record
+constexpr int N_SUB = 8;                             // 4 x 2 sub-tiles of 4 x 4 pixels
+
+// Per-wave statistics for tools/raster_stats.py: only a diagnostics build (-DGSPLAT_DIAGNOSTICS, libgsplat_mi355x_diag.so)
+// can register a buffer; the product library always passes NULL.
+struct WaveStats { uint32_t list_len, chunks, visited, cycles, begin_lo, launch_index; };   // chunks | duration in 100 MHz ticks << 12; begin: 100 MHz ticks; launch_index | XCD << 24
+__device__ __forceinline__ uint32_t xcc_id() {                // (every XCD has its own s_memtime counter)
+    uint32_t v;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
+    return v & 0xFu;
+}
+#ifdef GSPLAT_DIAGNOSTICS
+WaveStats* g_stats_fwd = nullptr;
+WaveStats* g_stats_bwd = nullptr;
+u2* g_ref_rect = nullptr;            // tools/ref_pairs_diff.py: the reference's own tile rectangle (F10) and tile count per Gaussian
+uint32_t* g_ref_tiles = nullptr;
+#define STATS_FWD g_stats_fwd
+#define STATS_BWD g_stats_bwd
+#define REF_RECT g_ref_rect
+#define REF_TILES g_ref_tiles
+#else
+#define STATS_FWD ((WaveStats*)nullptr)
+#define STATS_BWD ((WaveStats*)nullptr)
+#define REF_RECT ((u2*)nullptr)
+#define REF_TILES ((uint32_t*)nullptr)
+#endif
+
+constexpr float QK = -0.72134752044448170368f;      // -0.5 * log2(e)
+
+template <int Q>               // Q = slots per queue (the forward kernel: QCAP; the backward kernel, whose queues are capped: fewer)
+struct RasterLdsT {
+    static constexpr int QSLOTS = Q;
+    f4 r0[CHUNK + 1];          // u, v, k A11, 2 k A12                    [CHUNK] = the null record
+    f4 r1[CHUNK + 1];          // k A22, opacity, r, g
+    f4 r2[CHUNK + 1];          // b, Gaussian id (bits), 0, 0
+    uint16_t q[N_SUB][Q];      // per sub-tile: record offsets (16 * entry) of the entries that touch it, depth order
+};
+using RasterLds = RasterLdsT<QCAP>;
+static_assert(sizeof(uint16_t) * N_SUB * QCAP == 16 * QCAP, "queue block = QCAP 16-byte pieces");
+
+struct Candidate {         // one list entry held by one lane between fetch and staging
+    f4 q0, q1, q2;
+    uint32_t id;
+    uint32_t saved_mask;   // (backward) the sub-tile mask the forward left for this pair
+};
+
+__device__ __forceinline__ Candidate fetch_candidate(int lane, uint32_t base, uint32_t end, const uint32_t* __restrict__ ids,
+                                                     const Rec64* __restrict__ rec, uint32_t id_max,
+                                                     const uint8_t* __restrict__ pair_mask = nullptr) {
+    Candidate c;
+    const uint32_t idx = base + lane;
+    c.id = 0;
+    c.saved_mask = 0u;
+    c.q0 = c.q1 = c.q2 = f4{0.f, 0.f, 0.f, 0.f};
+    if (idx < end) {
+        if (pair_mask) c.saved_mask = pair_mask[idx];
+        c.id = min(ids[idx], id_max);                     // never gather outside the record array
+        const Rec64* __restrict__ r = rec + c.id;        // one 64-byte line
+        c.q0 = r->r0;
+        c.q1 = r->r1;
+        c.q2 = r->r2;
+    }
+    return c;
+}
+
+// Which of the list's 8 sub-tiles can the Gaussian touch?  Bit s = its box [u - ex, u + ex] x [v - ey, v + ey] (the padded
+// half-extents of {q <= chi} from the projection, gs_math.h) meets the pixel centres of sub-tile s.  (ox, oy) = list origin.
+__device__ __forceinline__ uint32_t subtile_mask(const Candidate& c, float ox, float oy) {
+    const float x0 = c.q0.x - c.q1.z - ox, x1 = c.q0.x + c.q1.z - ox;
+    const float y0 = c.q0.y - c.q1.w - oy, y1 = c.q0.y + c.q1.w - oy;
+    uint32_t cm = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cm |= (x1 >= (float)(4 * k) && x0 <= (float)(4 * k + 3)) ? (1u << k) : 0u;
+    uint32_t m = 0u;
+    if (y1 >= 0.f && y0 <= 3.f) m |= cm;
+    if (y1 >= 4.f && y0 <= 7.f) m |= cm << 4;
+    return m;
+}
+
+// Stage one chunk: records into LDS, sub-tile queues built.  n = entries offered (uniform, <= CHUNK).  A queue holds at most
+// MAXQ entries: when a sub-tile would get more, the chunk is cut to the longest prefix of the list that fits (the rest
+// comes back in the next chunk).  Returns {entries taken, length of the longest queue} (uniform); m8 = the lane's sub-tile
+// mask (0 beyond the entries taken), ranks = the lane's position in each of its queues (8 bits per sub-tile).
+struct Staged { int n, maxc; };
+// The same question answered exactly: does {q <= chi} (padded by 1e-3 like the list test of the projection, gs_math.h) reach the
+// pixel centres of sub-tile s?  q is convex: its minimum over the sub-tile's rectangle is 0 if the centre is inside, else it lies
+// on an edge that FACES the centre.  With X = the centre's x clamped to the rectangle (0 in centre-relative coordinates if it
+// is inside the x-range, else the nearer vertical edge) the line x = X is that vertical edge -- or, when there is none, a line
+// through the rectangle, whose points are harmless extra candidates -- and the minimum of q along it is a clamped 1-D quadratic
+// (v_med3); the same with Y.  min(qx, qy) is then the exact minimum in every case, the centre-inside case (X = Y = 0 -> 0)
+// included.  ~135 instructions per entry for the 8 sub-tiles; removes ~14 % of the (sub-tile, Gaussian) pairs the box test lets
+// through.  Non-PD conics: every sub-tile.
+__device__ __forceinline__ uint32_t subtile_mask_exact(const Candidate& c, float ox, float oy, float chi_pad) {
+    const float u = c.q0.x - ox, v = c.q0.y - oy, A = c.q0.z, B = c.q0.w, C = c.q1.x;
+    const float tB_C = -B * __builtin_amdgcn_rcpf(C), tB_A = -B * __builtin_amdgcn_rcpf(A), B2 = 2.0f * B;
+    float dx0[4], dx1[4], ax[4], bx[4], tx[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        dx0[k] = (float)(4 * k) - u; dx1[k] = (float)(4 * k + 3) - u;
+        const float X = __builtin_amdgcn_fmed3f(0.0f, dx0[k], dx1[k]);
+        ax[k] = A * X * X; bx[k] = B2 * X; tx[k] = tB_C * X;
+    }
+    uint32_t m = 0u;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const float dy0 = (float)(4 * r) - v, dy1 = (float)(4 * r + 3) - v;
+        const float Y = __builtin_amdgcn_fmed3f(0.0f, dy0, dy1);
+        const float cy = C * Y * Y, by = B2 * Y, sy = tB_A * Y;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float t = __builtin_amdgcn_fmed3f(tx[k], dy0, dy1);          // minimiser of q on the line x = X, clamped to the rectangle
+            const float qx = ax[k] + (bx[k] + C * t) * t;
+            const float sc = __builtin_amdgcn_fmed3f(sy, dx0[k], dx1[k]);
+            const float qy = cy + (by + A * sc) * sc;
+            if (!(fminf(qx, qy) > chi_pad)) m |= 1u << (4 * r + k);             // NaN -> touched
+        }
+    }
+    return (A > 0.f && C > 0.f && A * C - B * B > 0.f) ? m : 0xFFu;
+}
+
+// MASK: 0 = box test, 1 = box and exact test, 2 = the mask the forward pass saved for this pair (c.saved_mask)
+template <int MAXQ, int MASK = 0, class Lds = RasterLds>
+__device__ __forceinline__ Staged stage_chunk(Lds& s, const Candidate& c, int n, int lane, float ox, float oy, uint32_t& m8,
+                                              uint64_t& ranks, float chi_pad = 0.f) {
+    constexpr int QS = Lds::QSLOTS;                         // 16-byte pieces of the queue block
+    static_assert(MAXQ >= CHUNK || MAXQ + 4 <= QS, "a capped queue is read up to MAXQ + 3");
+    __syncthreads();       // previous chunk's LDS reads are done (single-wave block: orders LDS traffic only)
+    m8 = 0u;
+    if (lane == 63) { s.r0[CHUNK] = f4{0.f, 0.f, 0.f, 0.f}; s.r1[CHUNK] = f4{0.f, 0.f, 0.f, 0.f}; s.r2[CHUNK] = f4{0.f, 0.f, 0.f, 0.f}; }
+    if (lane < n) {
+        // conic pre-scaled by k = -0.5 log2(e): the loop evaluates q' = k q and alpha = o * exp2(q') (v_exp_f32 directly)
+        s.r0[lane] = f4{c.q0.x, c.q0.y, QK * c.q0.z, (2.0f * QK) * c.q0.w};
+        s.r1[lane] = f4{QK * c.q1.x, c.q1.y, c.q2.x, c.q2.y};
+        s.r2[lane] = f4{c.q2.z, __uint_as_float(c.id), 0.f, 0.f};
+        if (MASK == 2) m8 = c.saved_mask;
+        else if (MASK == 1) m8 = subtile_mask_exact(c, ox, oy, chi_pad);      // (conservative by itself: the box test adds nothing)
+        else m8 = subtile_mask(c, ox, oy);
+    }
+    {   // every queue slot -> the null record (QCAP 16-byte pieces)
+        const uint32_t nn = NULL_OFF | (NULL_OFF << 16);
+        uint4* qv = reinterpret_cast<uint4*>(&s.q[0][0]);
+        if (QS >= 64 || lane < QS) qv[lane] = uint4{nn, nn, nn, nn};
+        if (QS > 64 && lane < QS - 64) qv[64 + lane] = uint4{nn, nn, nn, nn};
+    }
+    ranks = 0ull;
+    if (MAXQ >= CHUNK) {                      // no cap (forward): queue entries written as the ballots come
+        int maxc = 0;
+#pragma unroll
+        for (int t = 0; t < N_SUB; ++t) {
+            const bool hit = (m8 >> t) & 1u;
+            const unsigned long long b = __ballot(hit);
+            if (hit) s.q[t][__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u))] = (uint16_t)(lane * 16);
+            maxc = max(maxc, (int)__popcll(b));
+        }
+        __syncthreads();
+        return Staged{n, maxc};
+    }
+    unsigned long long bal[N_SUB];
+    int maxc = 0;
+#pragma unroll
+    for (int t = 0; t < N_SUB; ++t) {
+        bal[t] = __ballot((m8 >> t) & 1u);
+        maxc = max(maxc, (int)__popcll(bal[t]));
+    }
+    {
+        while (maxc > MAXQ) {                 // rare (dense lists of large Gaussians): scalar work only
+            n = max(n - 4, MAXQ);             // n = MAXQ always fits
+            const unsigned long long keep = (1ull << n) - 1ull;
+            maxc = 0;
+#pragma unroll
+            for (int t = 0; t < N_SUB; ++t) maxc = max(maxc, (int)__popcll(bal[t] & keep));
+        }
+        if (lane >= n) m8 = 0u;
+    }
+#pragma unroll
+    for (int t = 0; t < N_SUB; ++t) {
+        if ((m8 >> t) & 1u) {
+            const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[t] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[t], 0u));
+            s.q[t][r] = (uint16_t)(lane * 16);
+            ranks |= (uint64_t)r << (8 * t);
+        }
+    }
+    __syncthreads();
+    return Staged{n, maxc};
+}
+
+template <class T>
+__device__ __forceinline__ T lds_at(const T* base, uint32_t byte_off) {
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+
+// min as ONE v_min_f32 (fminf() first canonicalises a scalar operand with a v_max_f32 every time it is used; no NaNs here)
+// b is wave-uniform (a kernel argument): taken from its SGPR as src0, not copied to a VGPR first
+__device__ __forceinline__ float vmin(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %2, %1" : "=v"(r) : "v"(a), "s"(b));
+    return r;
+}
+
+// the first blocks of a launch (the longest lists) raise their wave priority (s_setprio takes a constant)
+__device__ __forceinline__ void raise_launch_priority(uint32_t b, uint32_t grid) {
+    const int prio = b * 64u < grid ? 3 : (b * 16u < grid ? 2 : (b * 4u < grid ? 1 : 0));
+    if (prio == 3) __builtin_amdgcn_s_setprio(3);
+    else if (prio == 2) __builtin_amdgcn_s_setprio(2);
+    else if (prio == 1) __builtin_amdgcn_s_setprio(1);
+}
+
+// one layer's contribution w = alpha T (two pixels) to the running colour
+__device__ __forceinline__ void add_colour(v2f& Cr, v2f& Cg, v2f& Cb, v2f w, float r, float g, float b) {
+    Cr += w * r; Cg += w * g; Cb += w * b;
+}
+
+// (6 waves per SIMD as the compiler leaves it: 76 VGPRs.  Forced to 7 -- 69 VGPRs, no spill -- 90 us against 87.5; to 8: spills, 99 us)
+// SAVE (a backward pass will follow: accum is given): the queues come from the exact ellipse / sub-tile test, which costs this
+// kernel 6 us more than it saves it, and the resulting mask is left per pair (pair_mask, one byte) for the backward, which then
+// needs no test of its own.
+template <bool SAVE>
+__global__ __launch_bounds__(64) void raster_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ ids,
+                                                            const Rec64* __restrict__ rec, const uint32_t* __restrict__ order,
+                                                            int lists_x, int H, int W, float chi, float alpha_max,
+                                                            float alpha_cutoff, float* __restrict__ image,
+                                                            float* __restrict__ accum, WaveStats* __restrict__ stats, uint32_t id_max,
+                                                            float* __restrict__ zero_rows, int64_t n_zero_rows, uint8_t* __restrict__ pair_mask) {
+    __shared__ RasterLds s;
+    const int lane = threadIdx.x;
+    if (zero_rows) {        // the coming backward accumulates into grad2d: clear this wave's share now (the kernel is VALU-bound,
+                            // the stores ride along; a separate 64 MB fill cost 10 us + a dependent launch)
+        const int64_t per = (n_zero_rows + gridDim.x - 1) / gridDim.x, r0 = (int64_t)blockIdx.x * per;
+        const int64_t r1 = r0 + per < n_zero_rows ? r0 + per : n_zero_rows;
+        const f4 z = f4{0.f, 0.f, 0.f, 0.f};
+        for (int64_t r = r0 + lane; r < r1; r += 64) {
+            f4* row = reinterpret_cast<f4*>(zero_rows + r * 16);
+            row[0] = z; row[1] = z; row[2] = z; row[3] = z;
+        }
+    }
+    const uint32_t list = order[blockIdx.x];
+    const int tx = list % lists_x, hy = list / lists_x;
+    raise_launch_priority(blockIdx.x, gridDim.x);
+    const unsigned long long t_begin = stats ? __builtin_amdgcn_s_memtime() : 0ull;
+    const unsigned long long t_real = stats ? __builtin_amdgcn_s_memrealtime() : 0ull;      // 100 MHz, one clock for the whole chip
+    uint32_t st_chunks = 0, st_visited = 0;
+    const int grp = lane >> 3, j = lane & 7;
+    const int px = tx * LIST_W + (grp & 3) * 4 + (j & 3);
+    const int pya = hy * LIST_H + (grp >> 2) * 4 + (j >> 2), pyb = pya + 2;
+    const bool va = (px < W) && (pya < H), vb = (px < W) && (pyb < H);
+    const float fpx = (float)px;
+    const v2f fpy = {(float)pya, (float)pyb};
+    const float ox = (float)(tx * LIST_W), oy = (float)(hy * LIST_H);
+    v2f T = {va ? 1.0f : 0.0f, vb ? 1.0f : 0.0f};
+    v2f Cr = {0.f, 0.f}, Cg = {0.f, 0.f}, Cb = {0.f, 0.f};
+    const uint2 rg = ranges[list];
+    const float chik = chi * QK;
+    bool alive_any = __any(va || vb);
+    uint32_t base = rg.x;
+    Candidate cand;
+    if (alive_any && base < rg.y) cand = fetch_candidate(lane, base, rg.y, ids, rec, id_max);
+    const uint16_t* myq = &s.q[grp][0];
+    while (alive_any && base < rg.y) {
+        uint32_t m8;
+        uint64_t ranks;
+        const int maxc = stage_chunk<CHUNK, SAVE ? 1 : 0>(s, cand, (int)min(rg.y - base, (uint32_t)CHUNK), lane, ox, oy, m8, ranks, chi * 1.001f + 1e-4f).maxc;
+        if (SAVE && base + (uint32_t)lane < rg.y) pair_mask[base + lane] = (uint8_t)m8;     // 64 contiguous bytes per chunk
+        base += CHUNK;
+        if (base < rg.y) cand = fetch_candidate(lane, base, rg.y, ids, rec, id_max);   // in flight during the loop below
+        ++st_chunks;
+        st_visited += (uint32_t)maxc;
+        // The queue's entries two at a time, every group its own queue; the terms join the running colour directly.  Every 16
+        // entries the wave asks whether any pixel is still alive.
+        for (int k0 = 0; k0 < maxc; k0 += 16) {
+          const int k1 = min(k0 + 16, maxc);
+          for (int k = k0; k < k1; k += 2) {
+            const uint32_t offs = *reinterpret_cast<const uint32_t*>(myq + k);       // two queue entries
+            const uint32_t o0 = offs & 0xFFFFu, o1 = offs >> 16;
+            const f4 a0 = lds_at(s.r0, o0), b0 = lds_at(s.r1, o0), a1 = lds_at(s.r0, o1), b1 = lds_at(s.r1, o1);
+            const float cb0 = lds_at(reinterpret_cast<const float*>(s.r2), o0), cb1 = lds_at(reinterpret_cast<const float*>(s.r2), o1);
+            const float du0 = fpx - a0.x, du1 = fpx - a1.x;
+            const v2f dv0 = fpy - a0.y, dv1 = fpy - a1.y;
+            const v2f q0 = (a0.z * du0 * du0) + dv0 * ((a0.w * du0) + b0.x * dv0);        // k q  (k < 0)
+            const v2f q1 = (a1.z * du1 * du1) + dv1 * ((a1.w * du1) + b1.x * dv1);
+            const bool i00 = q0.x >= chik, i01 = q0.y >= chik, i10 = q1.x >= chik, i11 = q1.y >= chik;   // q <= chi
+            v2f g0, g1;
+            g0.x = __builtin_amdgcn_exp2f(q0.x); g0.y = __builtin_amdgcn_exp2f(q0.y);
+            g1.x = __builtin_amdgcn_exp2f(q1.x); g1.y = __builtin_amdgcn_exp2f(q1.y);
+            v2f al0 = b0.y * g0, al1 = b1.y * g1;
+            al0.x = vmin(al0.x, alpha_max); al0.y = vmin(al0.y, alpha_max);
+            al1.x = vmin(al1.x, alpha_max); al1.y = vmin(al1.y, alpha_max);
+            // alpha = 0 outside the chi-square clip, below the cutoff, and on a dead pixel (T <= 5e-5: the term is masked, and a dead
+            // pixel stays dead whether or not its T keeps shrinking) -- ONE select for the three, and w = alpha T needs none
+            al0.x = (i00 && al0.x >= alpha_cutoff && T.x > 5e-5f) ? al0.x : 0.0f;
+            al0.y = (i01 && al0.y >= alpha_cutoff && T.y > 5e-5f) ? al0.y : 0.0f;
+            const v2f w0 = al0 * T;
+            T = T - al0 * T;
+            al1.x = (i10 && al1.x >= alpha_cutoff && T.x > 5e-5f) ? al1.x : 0.0f;
+            al1.y = (i11 && al1.y >= alpha_cutoff && T.y > 5e-5f) ? al1.y : 0.0f;
+            const v2f w1 = al1 * T;
+            T = T - al1 * T;
+            add_colour(Cr, Cg, Cb, w0, b0.z, b0.w, cb0);
+            add_colour(Cr, Cg, Cb, w1, b1.z, b1.w, cb1);
+          }
+          if (!__any(T.x > 5e-5f || T.y > 5e-5f)) break;       // every 16 entries: all pixels dead
+        }
+        alive_any = __any(T.x > 5e-5f || T.y > 5e-5f);        // dead pixels stay dead
+    }
+    if (stats && lane == 0)
+        stats[list] = WaveStats{rg.y - rg.x, (st_chunks & 0xFFFu) | ((uint32_t)(__builtin_amdgcn_s_memrealtime() - t_real) << 12), st_visited, (uint32_t)(__builtin_amdgcn_s_memtime() - t_begin), (uint32_t)t_real, blockIdx.x | (xcc_id() << 24)};
+    // one pixel: the clamped colour, and (a backward pass will follow) the colour before the clamp
+    const auto put = [&](int py, float r, float g, float b) {
+        const int64_t o = ((int64_t)py * W + px) * 3;
+        image[o + 0] = fminf(fmaxf(r, 0.0f), 1.0f); image[o + 1] = fminf(fmaxf(g, 0.0f), 1.0f); image[o + 2] = fminf(fmaxf(b, 0.0f), 1.0f);
+        if (accum) { accum[o + 0] = r; accum[o + 1] = g; accum[o + 2] = b; }
+    };
+    if (va) put(pya, Cr.x, Cg.x, Cb.x);
+    if (vb) put(pyb, Cr.y, Cg.y, Cb.y);
+}
+
+// x + y of a two-pixel value as ONE v_add_f32 the SLP vectoriser cannot see: left to itself it pairs these horizontal adds
+// into v_pk_add_f32 and pays three v_mov shuffles per pair (-2.5 % on the backward kernel).
+__device__ __forceinline__ float hadd(v2f a) {
+    float r;
+    asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a.x), "v"(a.y));
+    return r;
+}
+
+// Eight per-lane partial sums v[0..7] -> their totals over the lane's GROUP of 8 lanes, total i delivered in lane i of the
+// group: a reduce-scatter inside every group at once (the 8 groups of the wave reduce 8 different Gaussians' sums in the
+// same instructions).  Every level halves the number of live values while it sums over one more lane pairing:
+//   row_half_mirror (l <-> 7 - l), quad_perm [2,3,0,1] (l <-> l ^ 2), quad_perm [1,0,3,2] (l <-> l ^ 1):
+// levels 2 and 3: two selects and a DPP add per pair of values; level 1: two bank-masked DPP adds (17 instructions for 8 sums).
+__device__ __forceinline__ float reduce_scatter8(float (&v)[8], int lane) {
+    const bool b1 = lane & 2, b0 = lane & 1;
+    // level 1 without selects: lane bit 2 is the parity of the lane's DPP bank (4 lanes), so two bank-masked DPP adds write the
+    // two halves of the result: banks 0, 2 (lanes 0-3 of every group) get v[i] + mirror(v[i]), banks 1, 3 get v[i+4] + mirror(v[i+4])
+    {
+        float t0, t1, t2, t3;
+        asm("s_nop 1\n"
+            "v_add_f32_dpp %0, %4, %4 row_half_mirror row_mask:0xf bank_mask:0x5\n"
+            "v_add_f32_dpp %1, %5, %5 row_half_mirror row_mask:0xf bank_mask:0x5\n"
+            "v_add_f32_dpp %2, %6, %6 row_half_mirror row_mask:0xf bank_mask:0x5\n"
+            "v_add_f32_dpp %3, %7, %7 row_half_mirror row_mask:0xf bank_mask:0x5\n"
+            "v_add_f32_dpp %0, %8, %8 row_half_mirror row_mask:0xf bank_mask:0xa\n"
+            "v_add_f32_dpp %1, %9, %9 row_half_mirror row_mask:0xf bank_mask:0xa\n"
+            "v_add_f32_dpp %2, %10, %10 row_half_mirror row_mask:0xf bank_mask:0xa\n"
+            "v_add_f32_dpp %3, %11, %11 row_half_mirror row_mask:0xf bank_mask:0xa"
+            : "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)
+            : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
+        v[0] = t0; v[1] = t1; v[2] = t2; v[3] = t3;
+    }
+    // levels 2, 3: per pair of values (a, b) and partner lane p, this lane keeps one of the two sums and gives the other to its
+    // partner: keep = mine(kept) + partner's(given) -- two selects (1.3 ns each) and ONE DPP add (1.8 ns)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const float keep = b1 ? v[i + 2] : v[i], give = b1 ? v[i] : v[i + 2];
+        v[i] = keep + dpp<0x4E>(give);                                                    // quad_perm [2,3,0,1]
+    }
+    const float keep = b0 ? v[1] : v[0], give = b0 ? v[0] : v[1];
+    return keep + dpp<0xB1>(give);                                                        // quad_perm [1,0,3,2]
+}
+// total of x over the lane's group of 8, in every lane of the group
+__device__ __forceinline__ float all_reduce8(float x) {
+    x += dpp<0x141>(x);                                                                     // row_half_mirror
+    x += dpp<0x4E>(x);
+    return x + dpp<0xB1>(x);
+}
+
+// backward: longest queue per chunk (sizes the slot block below; see the occupancy note at RasterLdsBwd).
+constexpr int MAXQ_BWD = 24;                             // (even: the loop evaluates entries in pairs)
+constexpr int QSLOTS_BWD = (MAXQ_BWD + 4 + 7) / 8 * 8;   // the loop reads entries k + 2, k + 3 ahead; rows of 16 bytes
+
+// LDS of the backward kernel.  LDS float atomics are slow on this hardware (a ds_add_f32 wave-instruction with 64 lanes cost
+// ~100 LDS cycles here: 230 us of a 450 us kernel), so nothing is accumulated with them: every group writes the nine sums of
+// iteration k to its own slot (plain stores), and after the chunk each entry's lane adds up the slots of the sub-tiles it
+// was queued in (it knows its rank in every queue) and leaves the row in `acc` for the flush.
+// LDS per wave decides the occupancy here (12.8 KB -> 12 waves per CU): the chunk's rows `acc` [entry][9] reuse the record
+// arrays, which are dead once the chunk's loop is over (the null record is rewritten by every stage_chunk).
+using RasterLdsB = RasterLdsT<QSLOTS_BWD>;
+template <bool DET>
+struct RasterLdsBwd {
+    RasterLdsB f;
+    float slots[N_SUB * MAXQ_BWD * 9];   // [sub-tile][queue position][9 sums]
+    uint32_t eid[CHUNK];                 // Gaussian id of every entry of the chunk
+    uint32_t eslot[DET ? CHUNK : 1];     // (deterministic mode) the row's slot
+};
+// LDS is handed out in coarse pieces (1280 B by the look of it): at 12 848 B per wave 11 waves were resident per CU (measured with
+// tools/raster_stats.py: 2816 waves), at 12 608 B twelve (231 -> 221 us), at 11 456 B and 128 VGPRs fourteen (214 us); sixteen
+// (queue cap 18: 10 KB) lose more to chunks cut short than they gain (228 us).
+static_assert(sizeof(RasterLdsBwd<false>) <= 11520, "the backward kernel's LDS per wave decides its occupancy");
+static_assert(sizeof(f4) * 3 * (CHUNK + 1) >= sizeof(float) * CHUNK * 9, "acc must fit into the record arrays");
+
+// K7: same traversal as K6 (identical T_i and alive decisions).  For pixel p and Gaussian i:
+//   d alpha_i = alive_i T_i (c_i . Gc) - (sum_{k>i} w_k (c_k . Gc)) / (1 - alpha_i),
+// the suffix sum being (total - running prefix), total = Gc . C_unclamped, Gc = dL/dO masked by the output clamp.
+// Every group reduces its Gaussian's nine sums over its 8 lanes (reduce-scatter: 8 Gaussians at once in the same
+// instructions); the rows of a chunk leave with ONE 36-byte global atomic request per (list, Gaussian) pair, 7 rows per
+// instruction (the memory-side atomic units take ~20 G requests/s: per sub-tile requests would cost 3x the time).
+//
+// DET (deterministic gradients): float atomics add in arrival order, so gradients differ from run to run at the 1e-6 level.
+// With DET the rows are STORED instead, one row per (list, Gaussian) pair at slot pair_base[Gaussian] + (ordinal of the list
+// in the Gaussian's own rectangle), and pair_reduce_kernel adds each Gaussian's rows in that fixed order: bitwise
+// reproducible (the sums inside a wave are already in a fixed order).
+struct DetArgs {
+    const u2* rect; const uint32_t* mask; const uint32_t* tiles; const uint32_t* pair_base;
+    float* part;             // [pair capacity][9]
+    uint32_t capacity;
+};
+
+// (4 waves per SIMD: the kernel needs 131 VGPRs left alone, 128 -- no spill -- when asked; with 11.4 KB of LDS 14 waves fit a CU)
+template <bool DET>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void raster_backward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ ids,
+                                                             const Rec64* __restrict__ rec, const uint32_t* __restrict__ order,
+                                                             int lists_x, int H, int W, float chi, float alpha_max,
+                                                             float alpha_cutoff, const float* __restrict__ accum,
+                                                             const float* __restrict__ gimg, float* __restrict__ grad2d,
+                                                             WaveStats* __restrict__ stats, uint32_t id_max, DetArgs det,
+                                                             const uint8_t* __restrict__ pair_mask) {
+    __shared__ RasterLdsBwd<DET> sb;
+    RasterLdsB& s = sb.f;
+    const int lane = threadIdx.x;
+    const uint32_t list = order[blockIdx.x];
+    const uint2 rg = ranges[list];
+    if (rg.x >= rg.y) return;
+    raise_launch_priority(blockIdx.x, gridDim.x);
+    const unsigned long long t_begin = stats ? __builtin_amdgcn_s_memtime() : 0ull;
+    const unsigned long long t_real = stats ? __builtin_amdgcn_s_memrealtime() : 0ull;      // 100 MHz, one clock for the whole chip
+    uint32_t st_chunks = 0, st_visited = 0;
+    const int tx = list % lists_x, hy = list / lists_x;
+    const int grp = lane >> 3, j = lane & 7;
+    const int px = tx * LIST_W + (grp & 3) * 4 + (j & 3);
+    const int pya = hy * LIST_H + (grp >> 2) * 4 + (j >> 2), pyb = pya + 2;
+    const bool va = (px < W) && (pya < H), vb = (px < W) && (pyb < H);
+    const float fpx = (float)px;
+    const v2f fpy = {(float)pya, (float)pyb};
+    const float ox = (float)(tx * LIST_W), oy = (float)(hy * LIST_H);
+    v2f T = {va ? 1.0f : 0.0f, vb ? 1.0f : 0.0f};
+    v2f Gr = {0.f, 0.f}, Gg = {0.f, 0.f}, Gb = {0.f, 0.f}, suffix = {0.f, 0.f};
+    {
+        float g[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}}, sfx[2] = {0.f, 0.f};
+        const bool vv[2] = {va, vb};
+        const int py[2] = {pya, pyb};
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (vv[k]) {
+                const int64_t o = ((int64_t)py[k] * W + px) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float cu = accum[o + c];
+                    // clamp(C, 0, 1) passes the gradient where 0 <= C <= 1 (render.py:410)
+                    const float gv = (cu >= 0.0f && cu <= 1.0f) ? gimg[o + c] : 0.0f;
+                    g[k][c] = gv;
+                    sfx[k] += gv * cu;
+                }
+            }
+        }
+        Gr = v2f{g[0][0], g[1][0]}; Gg = v2f{g[0][1], g[1][1]}; Gb = v2f{g[0][2], g[1][2]};
+        suffix = v2f{sfx[0], sfx[1]};
+    }
+    const float chik = chi * QK, amax = alpha_max;
+    bool alive_any = __any(va || vb);
+    uint32_t base = rg.x;
+    Candidate cand;
+    if (alive_any) cand = fetch_candidate(lane, base, rg.y, ids, rec, id_max, pair_mask);
+    const int my_g = lane / 9, my_k = lane - 9 * my_g;             // flush: lane i carries sum my_k of the round's row my_g
+    const uint16_t* myq = &s.q[grp][0];
+    float* const myslot = &sb.slots[grp * MAXQ_BWD * 9 + j];       // + 9 k: where lane j of the group puts sum j of iteration k
+    float* const acc = reinterpret_cast<float*>(&sb.f);            // [entry][9]: over the record arrays, between a chunk's loop and the next stage
+    while (alive_any && base < rg.y) {
+        uint32_t m8;
+        uint64_t ranks;
+        const Staged sg = stage_chunk<MAXQ_BWD, 2, RasterLdsB>(s, cand, (int)min(rg.y - base, (uint32_t)CHUNK), lane, ox, oy, m8, ranks);
+        const int n = sg.n, maxc = sg.maxc;
+        sb.eid[lane] = cand.id;
+        base += (uint32_t)n;
+        if (base < rg.y) cand = fetch_candidate(lane, base, rg.y, ids, rec, id_max, pair_mask);   // in flight during the loop below
+        ++st_chunks;
+        st_visited += (uint32_t)maxc;
+        int kdone = 0;                       // iterations executed (uniform): slots [0, kdone) of every queue are valid
+        // One queue entry: the group's 16 pixels against one Gaussian; the nine sums go to slot k of the group's queue.
+        auto entry = [&](const f4& a, const f4& b, const float cbl, const int k) {
+            const float go = b.y;
+            const float du = fpx - a.x;
+            const v2f dv = fpy - a.y;
+            const float c0 = a.z * du * du, c1 = a.w * du;
+            const v2f q = c0 + dv * (c1 + b.x * dv);                                   // k q  (k < 0)
+            const bool i0 = q.x >= chik, i1 = q.y >= chik;                              // q <= chi
+            v2f g;
+            g.x = __builtin_amdgcn_exp2f(q.x);
+            g.y = __builtin_amdgcn_exp2f(q.y);
+            const v2f og = go * g;
+            // alpha = min(o g, alpha_max) where q <= chi and that is >= alpha_cutoff (<=> o g >= alpha_cutoff: cutoff <= alpha_max), else 0
+            // (NOT folded with the alive test as in the forward kernel: alpha would then wait for the previous entry's T, and the
+            //  chain alpha -> 1 / (1 - alpha) -> d alpha of two consecutive entries could no longer overlap: +7 us, measured)
+            const bool p0 = i0 && og.x >= alpha_cutoff, p1 = i1 && og.y >= alpha_cutoff;
+            const float cl0 = vmin(og.x, amax), cl1 = vmin(og.y, amax);                 // (unconditional: a select, not a branch)
+            v2f al;
+            al.x = p0 ? cl0 : 0.0f; al.y = p1 ? cl1 : 0.0f;
+            const bool alive0 = T.x > 5e-5f, alive1 = T.y > 5e-5f;
+            v2f w = al * T;
+            w.x = alive0 ? w.x : 0.0f; w.y = alive1 ? w.y : 0.0f;
+            const v2f sdot = b.z * Gr + b.w * Gg + cbl * Gb;
+            const v2f ar = w * Gr, ag = w * Gg, ab = w * Gb;
+            suffix -= w * sdot;                                            // now the sum over k > i
+            const v2f sfx = suffix;
+            v2f om = 1.0f - al;
+            om.x = __builtin_amdgcn_rcpf(om.x); om.y = __builtin_amdgcn_rcpf(om.y);   // 1 - alpha >= 0.01
+            v2f dal = T * sdot - sfx * om;
+            // the pixel is alive, alpha passed its two tests, and clamp_max passes the gradient where o g <= alpha_max (render.py:372)
+            dal.x = (alive0 && p0 && og.x <= alpha_max) ? dal.x : 0.0f;
+            dal.y = (alive1 && p1 && og.y <= alpha_max) ? dal.y : 0.0f;
+            // a = dL/d alpha * g.  dL/d opacity = sum a, and dL/dq = -0.5 o a: the factor -0.5 o is the same for all pixels of a
+            // Gaussian, so the moments are taken of `a` and project_backward_kernel multiplies once per Gaussian:
+            //   d u = o (A11 Mx + A12 My), d v = o (A12 Mx + A22 My), d A11 = -0.5 o Mxx, d A12 = -o Mxy, d A22 = -0.5 o Myy
+            const v2f ao = dal * g;
+            const v2f dva = dv * ao;
+            const float m0 = hadd(ao), my = hadd(dva);
+            float r[8];
+            r[0] = du * m0;                                                // Mx  = sum du a
+            r[1] = my;                                                     // My  = sum dv a
+            r[2] = du * r[0];                                              // Mxx = sum du^2 a
+            r[3] = du * my;                                                // Mxy = sum du dv a
+            r[4] = hadd(dv * dva);                                         // Myy = sum dv^2 a
+            r[5] = m0;                                                     // M0  = sum a = dL/d opacity
+            r[6] = hadd(ar); r[7] = hadd(ag);                              // d r, d g
+            const float tot_b = all_reduce8(hadd(ab));                     // d b
+            myslot[k * 9] = reduce_scatter8(r, lane);
+            if (j == 0) myslot[k * 9 + 8] = tot_b;         // (two unconditional stores instead -- 3 instructions fewer -- measured no gain)
+            T = T - al * T;
+        };
+        // Software pipeline over the queue (LDS latency is not covered by occupancy here: 3 waves per SIMD), two entries per step
+        // in two register sets: entry k + 2 is requested into set 0 as soon as entry k has been evaluated from it, while entry
+        // k + 1 is evaluated from set 1, and so on -- no register copies.  An odd queue ends on a null record (its slot gets zeros).
+        const float* r2f = reinterpret_cast<const float*>(s.r2);
+        uint32_t oo = *reinterpret_cast<const uint32_t*>(myq);
+        f4 a0 = lds_at(s.r0, oo & 0xFFFFu), b0 = lds_at(s.r1, oo & 0xFFFFu), a1 = lds_at(s.r0, oo >> 16), b1 = lds_at(s.r1, oo >> 16);
+        float cb0 = lds_at(r2f, oo & 0xFFFFu), cb1 = lds_at(r2f, oo >> 16);
+        for (int k0 = 0; k0 < maxc; k0 += 8) {
+          const int k1 = min(k0 + 8, maxc);
+          for (int k = k0; k < k1; k += 2) {
+            oo = *reinterpret_cast<const uint32_t*>(myq + k + 2);                       // entries k + 2, k + 3 (null past the end; k + 3 < QCAP)
+            entry(a0, b0, cb0, k);
+            a0 = lds_at(s.r0, oo & 0xFFFFu); b0 = lds_at(s.r1, oo & 0xFFFFu); cb0 = lds_at(r2f, oo & 0xFFFFu);
+            entry(a1, b1, cb1, k + 1);
+            a1 = lds_at(s.r0, oo >> 16); b1 = lds_at(s.r1, oo >> 16); cb1 = lds_at(r2f, oo >> 16);
+          }
+          kdone = k1;
+          if (!__any(T.x > 5e-5f || T.y > 5e-5f)) break;          // every 8 entries: all pixels dead
+        }
+        alive_any = __any(T.x > 5e-5f || T.y > 5e-5f);        // dead pixels stay dead
+        __syncthreads();
+        {   // entry `lane`: add up the slots of the sub-tiles it was queued in
+            float tot[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < N_SUB; ++t) {
+                const int r = (int)((ranks >> (8 * t)) & 0xFFu);
+                if (((m8 >> t) & 1u) && r < kdone) {
+                    const float* p = &sb.slots[(t * MAXQ_BWD + r) * 9];
+#pragma unroll
+                    for (int v = 0; v < 9; ++v) tot[v] += p[v];
+                }
+            }
+#pragma unroll
+            for (int v = 0; v < 9; ++v) acc[lane * 9 + v] = tot[v];
+        }
+        if (DET && lane < n) {       // entry `lane`: its row's slot = first slot of its Gaussian + ordinal of this list in its rectangle
+            const uint32_t id = sb.eid[lane];
+            const u2 rc = det.rect[id];
+            const uint32_t mk = det.mask[id], nt = det.tiles[id];
+            const int x0 = (int)(rc.x & 0xFFFFu), y0 = (int)(rc.x >> 16), x1 = (int)(rc.y & 0xFFFFu);
+            const uint32_t bit = (uint32_t)((hy - y0) * (x1 - x0 + 1) + (tx - x0));          // row-major, like for_each_list
+            uint32_t ord;
+            if (rect_is_big(rc)) {               // a large Gaussian: its lists are row spans (for_each_big_row): lists in the rows above + offset in this row
+                const Rec64* r = rec + id;
+                const f4 q0 = r->r0, q1 = r->r1, q3 = r->pad;
+                const float kk[4] = {q3.x, q3.y, q3.z, q3.w};
+                const BigSpanK bk = big_span_setup(q0.x, q0.y, q1.z, q1.w, kk, x0, x1);
+                ord = 0u;
+                for (int y = y0; y < hy; ++y) {
+                    const RowSpan sp = big_row_span(bk, y);
+                    if (sp.xb >= sp.xa) ord += (uint32_t)(sp.xb - sp.xa + 1);
+                }
+                ord += (uint32_t)(tx - big_row_span(bk, hy).xa);
+            } else {
+                ord = (uint32_t)__popc(mk & ((1u << (bit & 31u)) - 1u));
+            }
+            (void)nt;
+            sb.eslot[lane] = det.pair_base[id] + ord;
+        }
+        __syncthreads();
+        // the chunk's rows -> grad2d: 7 rows x 9 sums per atomic instruction, one 36-byte request per row
+        for (int t0 = 0; t0 < n; t0 += 7) {
+            const int c = t0 + my_g;
+            if (lane < 63 && c < n) {
+                const float val = acc[c * 9 + my_k];
+                if (DET) {
+                    const uint32_t slot = sb.eslot[c];
+                    if (slot < det.capacity) det.part[(int64_t)slot * 9 + my_k] = val;
+                } else if (val != 0.0f) {
+                    atomicAdd(&grad2d[(int64_t)sb.eid[c] * 16 + my_k], val);
+                }
+            }
+        }
+    }
+    if (stats && lane == 0)
+        stats[list] = WaveStats{rg.y - rg.x, (st_chunks & 0xFFFu) | ((uint32_t)(__builtin_amdgcn_s_memrealtime() - t_real) << 12), st_visited, (uint32_t)(__builtin_amdgcn_s_memtime() - t_begin), (uint32_t)t_real, blockIdx.x | (xcc_id() << 24)};
+}
+
+// ---- deterministic mode: slots of the (list, Gaussian) rows and their fixed-order sum ------------------------------------
+
+__global__ __launch_bounds__(256) void tile_block_sum_kernel(int64_t n, const uint32_t* __restrict__ tiles, uint32_t* __restrict__ block_sum) {
+    __shared__ uint32_t ws[4];
+    uint32_t t = 0u;
+    for (int k = 0; k < PB_BLOCK / 256; ++k) {
+        const int64_t i = (int64_t)blockIdx.x * PB_BLOCK + k * 256 + threadIdx.x;
+        t += i < n ? tiles[i] : 0u;
+    }
+    for (int sft = 32; sft > 0; sft >>= 1) t += (uint32_t)__shfl_xor((int)t, sft);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) block_sum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+}
+
+// pair_base[i] = number of rows of the Gaussians before i (exclusive scan of tiles[]): thread t of a block owns 8 CONSECUTIVE
+// Gaussians, so the scan order is the index order.
+__global__ __launch_bounds__(256) void pair_base_kernel(int64_t n, const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ block_sum,
+                                                        uint32_t* __restrict__ pair_base) {
+    __shared__ uint32_t ws[4], s_base;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t before = 0u;
+    for (int b = tid; b < (int)blockIdx.x; b += 256) before += block_sum[b];
+    for (int sft = 32; sft > 0; sft >>= 1) before += (uint32_t)__shfl_xor((int)before, sft);
+    if (lane == 0) ws[wave] = before;
+    __syncthreads();
+    if (tid == 0) s_base = ws[0] + ws[1] + ws[2] + ws[3];
+    __syncthreads();
+    constexpr int K = PB_BLOCK / 256;
+    uint32_t v[K], run = 0u;
+    const int64_t i0 = (int64_t)blockIdx.x * PB_BLOCK + (int64_t)tid * K;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { v[k] = i0 + k < n ? tiles[i0 + k] : 0u; run += v[k]; }
+    const uint32_t incl = wave_inclusive_scan(run);
+    __syncthreads();
+    if (lane == 63) ws[wave] = incl;
+    __syncthreads();
+    uint32_t st = s_base + incl - run;
+    for (int k = 0; k < wave; ++k) st += ws[k];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if (i0 + k < n) pair_base[i0 + k] = st;
+        st += v[k];
+    }
+}
+
+// grad2d[i][0..8] = sum of Gaussian i's rows, in the order of its lists (row-major in its rectangle): the same order every run.
+__global__ __launch_bounds__(256) void pair_reduce_kernel(int64_t n, const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ pair_base,
+                                                          const float* __restrict__ part, uint32_t capacity, float* __restrict__ grad2d) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float t[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const uint32_t nt = tiles[i], pb = pair_base[i];
+    for (uint32_t k = 0; k < nt && pb + k < capacity; ++k) {
+        const float* row = part + (int64_t)(pb + k) * 9;
+#pragma unroll
+        for (int v = 0; v < 9; ++v) t[v] += row[v];
+    }
+    float* o = grad2d + i * 16;
+#pragma unroll
+    for (int v = 0; v < 9; ++v) o[v] = t[v];
+}
+
+}  // namespace

@@ -7,7 +7,7 @@ A "list" is one 16 x 8-pixel region (list L = ly * lists_x + lx); pairs of list 
 import numpy as np
 
 LIST_W, LIST_H = 16, 8
-# sort size classes of the launch plan (csrc/gsplat_kernels.hip, K4: SORT_CLASSES / class_first_bucket): class c holds the lists of
+# sort size classes of the launch plan (csrc/gs_sort.h, K5: SORT_CLASSES / class_first_bucket): class c holds the lists of
 # CLASS_MIN_LEN[c] <= length < CLASS_MIN_LEN[c - 1]; class_bounds[c] = lists in classes 0 .. c, so class_bounds[3] = the non-empty
 # lists, and the empty ones fill the rest of `order`.  (Whether the 4096+ class gets a launch of its own is gsplat_bin's business:
 # without one the launch of the next class takes its lists too; the bounds are the same either way.)

@@ -6,9 +6,7 @@ set -e
 root=$(cd "$(dirname "$0")/.." && pwd)
 pkg=3d-gaussian-splatting-for-novel-view-synthesis_amd
 tmp=$(mktemp -d)
-mkdir -p $tmp/$pkg/csrc $tmp/include
-git -C $root show HEAD:include/gsplat_mi355x.h > $tmp/include/gsplat_mi355x.h
-for f in gs_math.h gs_body.h gsplat_kernels.hip gsplat_loss.hip gsplat_optim.hip; do git -C $root show HEAD:$pkg/csrc/$f > $tmp/$pkg/csrc/$f; done
+git -C $root archive HEAD $pkg/csrc include | tar -x -C $tmp          # the whole of HEAD's csrc/ and include/, whatever files they hold
 (cd $tmp/$pkg/csrc && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -fno-gpu-rdc -Wno-unused-result -o head.so gsplat_kernels.hip gsplat_loss.hip gsplat_optim.hip)
 mkdir -p $root/$pkg/csrc/exp
 cp $tmp/$pkg/csrc/head.so $root/$pkg/csrc/exp/head.so

@@ -1,0 +1,37 @@
+#!/usr/bin/env python3
+"""Do two gfx950 code objects hold the same kernels, instruction for instruction?  The proof a kernel refactor needs.
+    python tools/isa_diff.py A.out B.out        (the ...-gfx950.out files `hipcc --save-temps=obj` leaves)
+Disassembles both, drops what follows `//` on every line (addresses, encodings) and compares the text per kernel symbol.
+Prints the kernels that differ or exist on one side only; exit status 1 if there are any."""
+import re
+import subprocess
+import sys
+
+OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+
+
+def kernels(path):
+    txt = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", "--no-leading-addr", path], check=True, capture_output=True, text=True).stdout
+    out, cur = {}, None
+    for line in txt.split("\n"):
+        m = re.match(r"^(?:[0-9a-f]+ )?<(\S+)>:$", line)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+        elif cur is not None and line.split("//")[0].strip() not in ("", "..."):      # ("...": padding objdump skipped)
+            cur.append(line.split("//")[0].strip())
+    return out
+
+
+a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+bad = 0
+for name in sorted(set(a) | set(b)):
+    if name not in a or name not in b:
+        print(f"only in {'A' if name in a else 'B'}: {name}")
+    elif a[name] != b[name]:
+        first = next((i for i, (x, y) in enumerate(zip(a[name], b[name])) if x != y), min(len(a[name]), len(b[name])))
+        print(f"differs: {name}  ({len(a[name])} / {len(b[name])} instructions, first difference at {first})")
+    else:
+        continue
+    bad += 1
+print(f"{len(set(a) | set(b))} kernels, {bad} differ")
+sys.exit(1 if bad else 0)
