@@ -16,7 +16,7 @@ GSPLAT_ERR_WORKSPACE = 3
 GSPLAT_SCENE_OK = 0
 GSPLAT_SCENE_ALL_CULLED = 10
 GSPLAT_SCENE_ALL_OFFSCREEN = 11
-ABI_VERSION = 11
+ABI_VERSION = 12
 GSPLAT_PROJECT_COLOUR_FUSED = 1
 GSPLAT_PROJECT_COUNTS_MAPPED = 2
 GSPLAT_PROJECT_SAVE_SH_JACOBIAN = 4
@@ -28,6 +28,7 @@ GSPLAT_BACKWARD_PHASE_RASTER = 2
 GSPLAT_BACKWARD_PHASE_PROJECT = 4
 GSPLAT_BACKWARD_GRAD2D_DIRTY = 8
 GSPLAT_BACKWARD_ACCUMULATE = 16
+GSPLAT_BACKWARD_DEPTH = 64
 
 _F = C.POINTER(C.c_float)
 
@@ -88,7 +89,10 @@ SIGNATURES = {
     "gsplat_project": (_INT, [_PG, _VP, _PV, _VP, _VP, _I64, _VP, _VP, C.c_int32, _VP]),
     "gsplat_bin": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _I64, _VP]),
     "gsplat_rasterize_forward": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "gsplat_rasterize_forward_aux": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _VP]),
     "gsplat_rasterize_backward_scratch_bytes": (_I64, [_I64, _I64]),
+    "gsplat_rasterize_backward_aux_scratch_bytes": (_I64, [_I64, _I64]),
+    "gsplat_rasterize_backward_aux": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _VP, C.c_int32, _VP, _I64, _VP]),
     "gsplat_rasterize_backward": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP, _VP, C.c_int32, _VP, _I64, _VP]),
     "gsplat_project_backward": (_INT, [_PG, _VP, _PV, _VP, _VP, _PGG, C.c_int32, _VP]),
     "gsplat_pose_scratch_bytes": (_I64, [_I64]),

@@ -154,10 +154,11 @@ GS_HD RecOut project_core(const GaussIn& in, bool fused, Coef coef, const Camera
 // d A11 = -0.5 o Mxx, d A12 = -o Mxy, d A22 = -0.5 o Myy.  moments = false: r9[0..5] are those gradients themselves.
 // kj (nullable): the 12 values the forward saved with sh_colour_jac; then `coef` is not read.
 // POSE: g_W receives this Gaussian's dL/dW (gs_math.h pose_grad_w; zeros for a Gaussian that is not visible).
-template <bool POSE = false, class Coef, class Emit>
+// DEPTH: g_z = dL/d(camera depth) of this Gaussian (column 9 of grad2d behind the depth / opacity raster backward).
+template <bool POSE = false, bool DEPTH = false, class Coef, class Emit>
 GS_HD GradOut project_backward_core(const GaussIn& in, bool fused, Coef coef, Emit emit_sh, const Camera& cam, const ViewK& vk,
                                     bool vis, const float r9[9], bool moments = false, const float* kj = nullptr,
-                                    float* g_W = nullptr) {
+                                    float* g_W = nullptr, float g_z = 0.f) {
     GradOut g;
     for (int k = 0; k < 3; ++k) { g.p[k] = 0.f; g.sr[k] = 0.f; g.col[k] = 0.f; }
     for (int k = 0; k < 4; ++k) g.qr[k] = 0.f;
@@ -178,7 +179,8 @@ GS_HD GradOut project_backward_core(const GaussIn& in, bool fused, Coef coef, Em
             gb = -o.opacity * r9[3];
             gc = -0.5f * o.opacity * r9[4];
         }
-        if constexpr (POSE) project_gaussian_backward<true>(m, o, cam, vk, gu, gv, ga, gb, gc, r9[5], g.p, g.S9, g.o_raw, in.p, S, g_W);
+        if constexpr (POSE) project_gaussian_backward<true, DEPTH>(m, o, cam, vk, gu, gv, ga, gb, gc, r9[5], g.p, g.S9, g.o_raw, in.p, S, g_W, g_z);
+        else if constexpr (DEPTH) project_gaussian_backward<false, true>(m, o, cam, vk, gu, gv, ga, gb, gc, r9[5], g.p, g.S9, g.o_raw, nullptr, nullptr, nullptr, g_z);
         else project_gaussian_backward(m, o, cam, vk, gu, gv, ga, gb, gc, r9[5], g.p, g.S9, g.o_raw);
         g.col[0] = r9[6]; g.col[1] = r9[7]; g.col[2] = r9[8];
         if (fused) {

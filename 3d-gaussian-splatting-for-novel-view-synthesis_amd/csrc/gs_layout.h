@@ -136,13 +136,14 @@ inline int64_t bin_state_bytes(int64_t pair_capacity) {
     return up(cap * 4) + up(cap);
 }
 
-// Scratch of the deterministic backward: one row per (list, Gaussian) pair, each Gaussian's first slot, sums per block.
+// Scratch of the deterministic backward: one row of `row` floats per (list, Gaussian) pair (9; 10 with the depth / opacity
+// channels), each Gaussian's first slot, sums per block.
 constexpr int PB_BLOCK = 2048;                       // Gaussians per block of tile_block_sum_kernel / pair_base_kernel
 struct DetScratch { float* part; uint32_t* pair_base; uint32_t* block_sum; int64_t bytes; };
-DetScratch carve_det(void* base, int64_t n, int64_t capacity) {
+DetScratch carve_det(void* base, int64_t n, int64_t capacity, int row = 9) {
     DetScratch d;
     Carver c{(char*)base};
-    d.part = c.take<float>((capacity > 0 ? capacity : 1) * 36);
+    d.part = c.take<float>((capacity > 0 ? capacity : 1) * 4 * row);
     d.pair_base = c.take<uint32_t>((n > 0 ? n : 1) * 4);
     d.block_sum = c.take<uint32_t>(((n > 0 ? n : 1) + PB_BLOCK - 1) / PB_BLOCK * 4);
     d.bytes = c.o;

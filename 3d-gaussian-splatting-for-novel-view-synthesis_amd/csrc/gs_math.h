@@ -584,10 +584,13 @@ GS_HD void pose_grad_w(const float g_pc[3], const float dC[9], const float w[9],
 // project_gaussian).  Outputs: g_p[3] (position), G_S[9] (full symmetric world-covariance gradient), g_o_raw.
 // POSE: also g_W = dL/dW of this Gaussian (pose_grad_w), from its position p and the world covariance S the forward projected.
 // (A template flag, not a null pointer: the code of the variants without it stays exactly what it was.)
-template <bool POSE = false>
+// DEPTH: the loss also reads the camera depth z_c directly (the rasteriser's depth map: g_z = dL/dz of this Gaussian, the sum S_z of
+// the depth / opacity raster backward); it joins d z_c, so position and pose get it through the chain that is there.
+template <bool POSE = false, bool DEPTH = false>
 GS_HD void project_gaussian_backward(const ProjMid& m, const Proj& o, const Camera& cam, const ViewK& vk, float g_u, float g_v,
                                      float g_A11, float g_A12, float g_A22, float g_opacity, float g_p[3], float G_S[9],
-                                     float& g_o_raw, const float* p = nullptr, const float* S = nullptr, float* g_W = nullptr) {
+                                     float& g_o_raw, const float* p = nullptr, const float* S = nullptr, float* g_W = nullptr,
+                                     float g_z = 0.f) {
     // opacity = clamp(sigmoid, 0, 0.999)
     g_o_raw = (m.sg <= 0.999f) ? g_opacity * m.sg * (1.f - m.sg) : 0.f;
     // min_conis clamp (render.py:310-311): gradient passes where the value is >= the bound
@@ -653,6 +656,8 @@ GS_HD void project_gaussian_backward(const ProjMid& m, const Proj& o, const Came
     const float rz = 1.0f / m.zc;
     dxc += vk.fx * rz * g_u; dzc += -vk.fx * m.xc * rz * rz * g_u;
     dyc += vk.fy * rz * g_v; dzc += -vk.fy * m.yc * rz * rz * g_v;
+    if constexpr (DEPTH) dzc += g_z;
+    else (void)g_z;
     g_p[0] = w[0] * dxc + w[3] * dyc + w[6] * dzc;
     g_p[1] = w[1] * dxc + w[4] * dyc + w[7] * dzc;
     g_p[2] = w[2] * dxc + w[5] * dyc + w[8] * dzc;

@@ -23,7 +23,9 @@ namespace {
 // and dL/dp -- the wave adds them up in a fixed order (wave_sum_f) and stores ONE 64-byte row per block into pose_rows[blockIdx.x]
 // (every block writes its row: nothing to clear); pose_reduce_kernel adds the rows.  out.pos == NULL: no gradient row is stored
 // (pose only).
-template <bool FUSED, bool JAC = false, bool ADAM = false, bool ACC = false, bool POSE = false>
+// DEPTH (not with ADAM / ACC): column 9 of grad2d holds dL/dz of the Gaussian's camera depth (gsplat_rasterize_backward_aux); it joins
+// the camera-space z gradient, from where position and pose get it.
+template <bool FUSED, bool JAC = false, bool ADAM = false, bool ACC = false, bool POSE = false, bool DEPTH = false>
 __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g, const Camera* __restrict__ camp, ViewK vk,
                                                               const uint32_t* __restrict__ tiles, const float* __restrict__ grad2d,
                                                               gsplat_gaussian_grads out, bool factored, const float* __restrict__ kj_in,
@@ -31,6 +33,7 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
     static_assert(!ADAM || (FUSED && JAC), "the in-place step needs the direct path");
     static_assert(!ACC || (FUSED && JAC && !ADAM), "accumulation is built for the direct path");
     static_assert(!POSE || (!ADAM && !ACC), "the pose gradient is built for the plain backward");
+    static_assert(!DEPTH || (!ADAM && !ACC), "the depth gradient is built for the plain backward");
     // DIRECT (fused inputs, saved Jacobian): nothing is staged IN (the 44 bytes of geometry are loaded by the lanes), and of the
     // gradients only the 45 f_rest rows go OUT through LDS (the rows of 1 / 3 / 4 floats are stored by the lanes): 11 520 B per
     // wave instead of 15 104 -> 14 waves per CU instead of 10.
@@ -45,6 +48,7 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
     const bool vis = (i < g.n) && tiles[i] != 0;
     const bool any_vis = __any(vis);
     float r9[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float g_z = 0.f;                                      // (DEPTH)
     float kj[12];
     GaussIn in;
     if (any_vis) {
@@ -75,6 +79,7 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
             const f4 g0 = *reinterpret_cast<const f4*>(grad2d + i * 16), g1 = *reinterpret_cast<const f4*>(grad2d + i * 16 + 4);
             r9[0] = g0.x; r9[1] = g0.y; r9[2] = g0.z; r9[3] = g0.w; r9[4] = g1.x; r9[5] = g1.y; r9[6] = g1.z; r9[7] = g1.w;
             r9[8] = grad2d[i * 16 + 8];
+            if (DEPTH) g_z = grad2d[i * 16 + 9];
         }
     }
     if (!DIRECT) __syncthreads();
@@ -84,9 +89,9 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
     float gw[9];                                          // (POSE) d L / d W of this lane's Gaussian
     if (vis) {
         if (!DIRECT) in = gauss_from_lds<FUSED>(s, lane);
-        go = project_backward_core<POSE>(in, FUSED, ShCoefLds{dc_rows, s_rest + lane * 45},
+        go = project_backward_core<POSE, DEPTH>(in, FUSED, ShCoefLds{dc_rows, s_rest + lane * 45},
                                    ShEmitLds{dc_rows, s_rest + lane * 45}, cam, vk, true, r9, true, JAC ? kj : nullptr,
-                                   POSE ? gw : nullptr);
+                                   POSE ? gw : nullptr, g_z);
     } else {
         go = GradOut{};
         if (FUSED) {

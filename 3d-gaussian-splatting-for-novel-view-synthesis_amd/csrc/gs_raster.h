@@ -64,7 +64,7 @@ struct RasterLdsT {
     static constexpr int QSLOTS = Q;
     f4 r0[CHUNK + 1];          // u, v, k A11, 2 k A12                    [CHUNK] = the null record
     f4 r1[CHUNK + 1];          // k A22, opacity, r, g
-    f4 r2[CHUNK + 1];          // b, Gaussian id (bits), 0, 0
+    f4 r2[CHUNK + 1];          // b, Gaussian id (bits), camera depth z (the depth / opacity variants; else 0), 0
     uint16_t q[N_SUB][Q];      // per sub-tile: record offsets (16 * entry) of the entries that touch it, depth order
 };
 using RasterLds = RasterLdsT<QCAP>;
@@ -151,7 +151,8 @@ __device__ __forceinline__ uint32_t subtile_mask_exact(const Candidate& c, float
 }
 
 // MASK: 0 = box test, 1 = box and exact test, 2 = the mask the forward pass saved for this pair (c.saved_mask)
-template <int MAXQ, int MASK = 0, class Lds = RasterLds>
+// Z: the record's camera depth is staged too (r2.z: the depth / opacity variants composite it as a fourth channel)
+template <int MAXQ, int MASK = 0, class Lds = RasterLds, bool Z = false>
 __device__ __forceinline__ Staged stage_chunk(Lds& s, const Candidate& c, int n, int lane, float ox, float oy, uint32_t& m8,
                                               uint64_t& ranks, float chi_pad = 0.f) {
     constexpr int QS = Lds::QSLOTS;                         // 16-byte pieces of the queue block
@@ -163,7 +164,7 @@ __device__ __forceinline__ Staged stage_chunk(Lds& s, const Candidate& c, int n,
         // conic pre-scaled by k = -0.5 log2(e): the loop evaluates q' = k q and alpha = o * exp2(q') (v_exp_f32 directly)
         s.r0[lane] = f4{c.q0.x, c.q0.y, QK * c.q0.z, (2.0f * QK) * c.q0.w};
         s.r1[lane] = f4{QK * c.q1.x, c.q1.y, c.q2.x, c.q2.y};
-        s.r2[lane] = f4{c.q2.z, __uint_as_float(c.id), 0.f, 0.f};
+        s.r2[lane] = f4{c.q2.z, __uint_as_float(c.id), Z ? c.q2.w : 0.f, 0.f};
         if (MASK == 2) m8 = c.saved_mask;
         else if (MASK == 1) m8 = subtile_mask_exact(c, ox, oy, chi_pad);      // (conservative by itself: the box test adds nothing)
         else m8 = subtile_mask(c, ox, oy);
@@ -246,13 +247,27 @@ __device__ __forceinline__ void add_colour(v2f& Cr, v2f& Cg, v2f& Cb, v2f w, flo
 // SAVE (a backward pass will follow: accum is given): the queues come from the exact ellipse / sub-tile test, which costs this
 // kernel 6 us more than it saves it, and the resulting mask is left per pair (pair_mask, one byte) for the backward, which then
 // needs no test of its own.
-template <bool SAVE>
+//
+// AUX (gsplat_rasterize_forward_aux): depth and opacity beside the colour.  With w_i = alpha_i T_i [T_i > 5e-5] the wave also
+// accumulates A = sum w_i and D = sum w_i z_i (z_i = the record's camera depth, staged in r2.z: no LDS more), two packed
+// accumulators more; the pixel gets image = clamp(C + (1 - A) bg), depth = D, alpha = A (neither clamped nor normalised), and,
+// for a backward pass, accum = C as always and accum_aux = (D, A).
+struct AuxFwd {
+    float* depth; float* alpha;      // [H,W] each, nullable (a background alone)
+    float* accum_aux;                // [H,W,2]: (D, A) for the backward pass, given with accum
+    float bg[3]; int has_bg;
+};
+// the composited, un-clamped colour: ONE fma, the same in the forward kernel and where the backward kernel rebuilds the clamp mask
+__device__ __forceinline__ float over_background(float c, float a, float bg) { return __builtin_fmaf(1.0f - a, bg, c); }
+
+template <bool SAVE, bool AUX = false>
 __global__ __launch_bounds__(64) void raster_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ ids,
                                                             const Rec64* __restrict__ rec, const uint32_t* __restrict__ order,
                                                             int lists_x, int H, int W, float chi, float alpha_max,
                                                             float alpha_cutoff, float* __restrict__ image,
                                                             float* __restrict__ accum, WaveStats* __restrict__ stats, uint32_t id_max,
-                                                            float* __restrict__ zero_rows, int64_t n_zero_rows, uint8_t* __restrict__ pair_mask) {
+                                                            float* __restrict__ zero_rows, int64_t n_zero_rows, uint8_t* __restrict__ pair_mask,
+                                                            AuxFwd aux = AuxFwd{}) {
     __shared__ RasterLds s;
     const int lane = threadIdx.x;
     if (zero_rows) {        // the coming backward accumulates into grad2d: clear this wave's share now (the kernel is VALU-bound,
@@ -280,6 +295,7 @@ __global__ __launch_bounds__(64) void raster_forward_kernel(const uint2* __restr
     const float ox = (float)(tx * LIST_W), oy = (float)(hy * LIST_H);
     v2f T = {va ? 1.0f : 0.0f, vb ? 1.0f : 0.0f};
     v2f Cr = {0.f, 0.f}, Cg = {0.f, 0.f}, Cb = {0.f, 0.f};
+    v2f Dz = {0.f, 0.f}, Aw = {0.f, 0.f};                    // (AUX) sum w z, sum w
     const uint2 rg = ranges[list];
     const float chik = chi * QK;
     bool alive_any = __any(va || vb);
@@ -290,7 +306,7 @@ __global__ __launch_bounds__(64) void raster_forward_kernel(const uint2* __restr
     while (alive_any && base < rg.y) {
         uint32_t m8;
         uint64_t ranks;
-        const int maxc = stage_chunk<CHUNK, SAVE ? 1 : 0>(s, cand, (int)min(rg.y - base, (uint32_t)CHUNK), lane, ox, oy, m8, ranks, chi * 1.001f + 1e-4f).maxc;
+        const int maxc = stage_chunk<CHUNK, SAVE ? 1 : 0, RasterLds, AUX>(s, cand, (int)min(rg.y - base, (uint32_t)CHUNK), lane, ox, oy, m8, ranks, chi * 1.001f + 1e-4f).maxc;
         if (SAVE && base + (uint32_t)lane < rg.y) pair_mask[base + lane] = (uint8_t)m8;     // 64 contiguous bytes per chunk
         base += CHUNK;
         if (base < rg.y) cand = fetch_candidate(lane, base, rg.y, ids, rec, id_max);   // in flight during the loop below
@@ -328,6 +344,11 @@ __global__ __launch_bounds__(64) void raster_forward_kernel(const uint2* __restr
             T = T - al1 * T;
             add_colour(Cr, Cg, Cb, w0, b0.z, b0.w, cb0);
             add_colour(Cr, Cg, Cb, w1, b1.z, b1.w, cb1);
+            if (AUX) {
+                const float z0 = lds_at(reinterpret_cast<const float*>(s.r2) + 2, o0), z1 = lds_at(reinterpret_cast<const float*>(s.r2) + 2, o1);
+                Dz += w0 * z0; Aw += w0;
+                Dz += w1 * z1; Aw += w1;
+            }
           }
           if (!__any(T.x > 5e-5f || T.y > 5e-5f)) break;       // every 16 entries: all pixels dead
         }
@@ -341,8 +362,22 @@ __global__ __launch_bounds__(64) void raster_forward_kernel(const uint2* __restr
         image[o + 0] = fminf(fmaxf(r, 0.0f), 1.0f); image[o + 1] = fminf(fmaxf(g, 0.0f), 1.0f); image[o + 2] = fminf(fmaxf(b, 0.0f), 1.0f);
         if (accum) { accum[o + 0] = r; accum[o + 1] = g; accum[o + 2] = b; }
     };
-    if (va) put(pya, Cr.x, Cg.x, Cb.x);
-    if (vb) put(pyb, Cr.y, Cg.y, Cb.y);
+    if (!AUX) {
+        if (va) put(pya, Cr.x, Cg.x, Cb.x);
+        if (vb) put(pyb, Cr.y, Cg.y, Cb.y);
+        return;
+    }
+    // (AUX) one pixel: the colour over the background, clamped; depth and opacity as they are; for a backward pass C, D, A unclamped
+    const auto put_aux = [&](int py, float r, float g, float b, float d, float a) {
+        const int64_t p = (int64_t)py * W + px, o = p * 3;
+        if (accum) { accum[o + 0] = r; accum[o + 1] = g; accum[o + 2] = b; aux.accum_aux[p * 2] = d; aux.accum_aux[p * 2 + 1] = a; }
+        if (aux.has_bg) { r = over_background(r, a, aux.bg[0]); g = over_background(g, a, aux.bg[1]); b = over_background(b, a, aux.bg[2]); }
+        image[o + 0] = fminf(fmaxf(r, 0.0f), 1.0f); image[o + 1] = fminf(fmaxf(g, 0.0f), 1.0f); image[o + 2] = fminf(fmaxf(b, 0.0f), 1.0f);
+        if (aux.depth) aux.depth[p] = d;
+        if (aux.alpha) aux.alpha[p] = a;
+    };
+    if (va) put_aux(pya, Cr.x, Cg.x, Cb.x, Dz.x, Aw.x);
+    if (vb) put_aux(pyb, Cr.y, Cg.y, Cb.y, Dz.y, Aw.y);
 }
 
 // x + y of a two-pixel value as ONE v_add_f32 the SLP vectoriser cannot see: left to itself it pairs these horizontal adds
@@ -405,10 +440,10 @@ constexpr int QSLOTS_BWD = (MAXQ_BWD + 4 + 7) / 8 * 8;   // the loop reads entri
 // LDS per wave decides the occupancy here (12.8 KB -> 12 waves per CU): the chunk's rows `acc` [entry][9] reuse the record
 // arrays, which are dead once the chunk's loop is over (the null record is rewritten by every stage_chunk).
 using RasterLdsB = RasterLdsT<QSLOTS_BWD>;
-template <bool DET>
+template <bool DET, int NS = 9>              // NS = sums per (sub-tile, Gaussian): 9, or 10 with the depth / opacity channels (S_z)
 struct RasterLdsBwd {
     RasterLdsB f;
-    float slots[N_SUB * MAXQ_BWD * 9];   // [sub-tile][queue position][9 sums]
+    float slots[N_SUB * MAXQ_BWD * NS];  // [sub-tile][queue position][NS sums]
     uint32_t eid[CHUNK];                 // Gaussian id of every entry of the chunk
     uint32_t eslot[DET ? CHUNK : 1];     // (deterministic mode) the row's slot
 };
@@ -416,7 +451,9 @@ struct RasterLdsBwd {
 // tools/raster_stats.py: 2816 waves), at 12 608 B twelve (231 -> 221 us), at 11 456 B and 128 VGPRs fourteen (214 us); sixteen
 // (queue cap 18: 10 KB) lose more to chunks cut short than they gain (228 us).
 static_assert(sizeof(RasterLdsBwd<false>) <= 11520, "the backward kernel's LDS per wave decides its occupancy");
-static_assert(sizeof(f4) * 3 * (CHUNK + 1) >= sizeof(float) * CHUNK * 9, "acc must fit into the record arrays");
+static_assert(sizeof(f4) * 3 * (CHUNK + 1) >= sizeof(float) * CHUNK * 10, "acc must fit into the record arrays");
+// The depth / opacity variant (NS = 10) keeps the queue cap and runs at 3 waves per SIMD = 12 per CU, which 12 800 B each allow
+static_assert(sizeof(RasterLdsBwd<true, 10>) <= 12800, "the depth / opacity backward kernel's LDS per wave: 12 waves per CU");
 
 // K7: same traversal as K6 (identical T_i and alive decisions).  For pixel p and Gaussian i:
 //   d alpha_i = alive_i T_i (c_i . Gc) - (sum_{k>i} w_k (c_k . Gc)) / (1 - alpha_i),
@@ -431,20 +468,35 @@ static_assert(sizeof(f4) * 3 * (CHUNK + 1) >= sizeof(float) * CHUNK * 9, "acc mu
 // reproducible (the sums inside a wave are already in a fixed order).
 struct DetArgs {
     const u2* rect; const uint32_t* mask; const uint32_t* tiles; const uint32_t* pair_base;
-    float* part;             // [pair capacity][9]
+    float* part;             // [pair capacity][9] ([10] for the depth / opacity variant)
     uint32_t capacity;
 };
 
-// (4 waves per SIMD: the kernel needs 131 VGPRs left alone, 128 -- no spill -- when asked; with 11.4 KB of LDS 14 waves fit a CU)
-template <bool DET>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void raster_backward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ ids,
+//
+// AUX (gsplat_rasterize_backward_aux): the loss also reads depth D = sum w z and opacity A = sum w, and the image may lie over a
+// background: image = clamp(C + (1 - A) bg).  (z, 1) are two more colour channels: with c+ = (r, g, b, z, 1) and
+// G+ = (Gr, Gg, Gb, G_D, G_A - sum_c G_c bg_c) -- G_c masked by the clamp of the COMPOSITED value -- the formula above holds with
+// c+ . G+ for c . Gc and total = G+ . (C, D, A).  One sum more per pair: S_z = sum_px w G_D = dL/dz (column 9 of grad2d; slots and
+// rows of 10, 6 rows per atomic instruction).  A missing upstream gradient (NULL) is zeros.
+struct AuxBwd {
+    const float* accum_aux;          // [H,W,2]: (D, A) unclamped, from the forward pass
+    const float* gdepth; const float* galpha;      // [H,W] each, nullable
+    float bg[3]; int has_bg;
+};
+
+// (4 waves per SIMD: the kernel needs 131 VGPRs left alone, 128 -- no spill -- when asked; with 11.4 KB of LDS 14 waves fit a CU.
+//  AUX: 3 waves per SIMD -- up to 168 VGPRs, and the 12 waves of a CU may have 12.8 KB each: the slots of 10 with the same queue cap)
+template <bool DET, bool AUX = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AUX ? 3 : 4, AUX ? 3 : 4))) void raster_backward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ ids,
                                                              const Rec64* __restrict__ rec, const uint32_t* __restrict__ order,
                                                              int lists_x, int H, int W, float chi, float alpha_max,
                                                              float alpha_cutoff, const float* __restrict__ accum,
                                                              const float* __restrict__ gimg, float* __restrict__ grad2d,
                                                              WaveStats* __restrict__ stats, uint32_t id_max, DetArgs det,
-                                                             const uint8_t* __restrict__ pair_mask) {
-    __shared__ RasterLdsBwd<DET> sb;
+                                                             const uint8_t* __restrict__ pair_mask, AuxBwd aux = AuxBwd{}) {
+    constexpr int NS = AUX ? 10 : 9;               // sums per (list, Gaussian) pair
+    constexpr int RPI = 64 / NS;                   // rows per flush instruction
+    __shared__ RasterLdsBwd<DET, NS> sb;
     RasterLdsB& s = sb.f;
     const int lane = threadIdx.x;
     const uint32_t list = order[blockIdx.x];
@@ -464,7 +516,34 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const float ox = (float)(tx * LIST_W), oy = (float)(hy * LIST_H);
     v2f T = {va ? 1.0f : 0.0f, vb ? 1.0f : 0.0f};
     v2f Gr = {0.f, 0.f}, Gg = {0.f, 0.f}, Gb = {0.f, 0.f}, suffix = {0.f, 0.f};
-    {
+    v2f Gd = {0.f, 0.f}, Ga = {0.f, 0.f};          // (AUX) dL/dD, dL/dA - sum_c G_c bg_c
+    if (AUX) {
+        float g[2][5] = {{0.f, 0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f, 0.f}}, sfx[2] = {0.f, 0.f};
+        const bool vv[2] = {va, vb};
+        const int py[2] = {pya, pyb};
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (vv[k]) {
+                const int64_t p = (int64_t)py[k] * W + px, o = p * 3;
+                const float D = aux.accum_aux[p * 2], A = aux.accum_aux[p * 2 + 1];
+                g[k][3] = aux.gdepth ? aux.gdepth[p] : 0.0f;
+                g[k][4] = aux.galpha ? aux.galpha[p] : 0.0f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float cu = accum[o + c];
+                    const float shown = aux.has_bg ? over_background(cu, A, aux.bg[c]) : cu;       // what the forward clamped
+                    const float gv = (gimg && shown >= 0.0f && shown <= 1.0f) ? gimg[o + c] : 0.0f;
+                    g[k][c] = gv;
+                    sfx[k] += gv * cu;
+                    if (aux.has_bg) g[k][4] -= gv * aux.bg[c];
+                }
+                sfx[k] += g[k][3] * D + g[k][4] * A;
+            }
+        }
+        Gr = v2f{g[0][0], g[1][0]}; Gg = v2f{g[0][1], g[1][1]}; Gb = v2f{g[0][2], g[1][2]};
+        Gd = v2f{g[0][3], g[1][3]}; Ga = v2f{g[0][4], g[1][4]};
+        suffix = v2f{sfx[0], sfx[1]};
+    } else {
         float g[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}}, sfx[2] = {0.f, 0.f};
         const bool vv[2] = {va, vb};
         const int py[2] = {pya, pyb};
@@ -490,14 +569,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     uint32_t base = rg.x;
     Candidate cand;
     if (alive_any) cand = fetch_candidate(lane, base, rg.y, ids, rec, id_max, pair_mask);
-    const int my_g = lane / 9, my_k = lane - 9 * my_g;             // flush: lane i carries sum my_k of the round's row my_g
+    const int my_g = lane / NS, my_k = lane - NS * my_g;           // flush: lane i carries sum my_k of the round's row my_g
     const uint16_t* myq = &s.q[grp][0];
-    float* const myslot = &sb.slots[grp * MAXQ_BWD * 9 + j];       // + 9 k: where lane j of the group puts sum j of iteration k
-    float* const acc = reinterpret_cast<float*>(&sb.f);            // [entry][9]: over the record arrays, between a chunk's loop and the next stage
+    float* const myslot = &sb.slots[grp * MAXQ_BWD * NS + j];      // + NS k: where lane j of the group puts sum j of iteration k
+    float* const acc = reinterpret_cast<float*>(&sb.f);            // [entry][NS]: over the record arrays, between a chunk's loop and the next stage
     while (alive_any && base < rg.y) {
         uint32_t m8;
         uint64_t ranks;
-        const Staged sg = stage_chunk<MAXQ_BWD, 2, RasterLdsB>(s, cand, (int)min(rg.y - base, (uint32_t)CHUNK), lane, ox, oy, m8, ranks);
+        const Staged sg = stage_chunk<MAXQ_BWD, 2, RasterLdsB, AUX>(s, cand, (int)min(rg.y - base, (uint32_t)CHUNK), lane, ox, oy, m8, ranks);
         const int n = sg.n, maxc = sg.maxc;
         sb.eid[lane] = cand.id;
         base += (uint32_t)n;
@@ -506,7 +585,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         st_visited += (uint32_t)maxc;
         int kdone = 0;                       // iterations executed (uniform): slots [0, kdone) of every queue are valid
         // One queue entry: the group's 16 pixels against one Gaussian; the nine sums go to slot k of the group's queue.
-        auto entry = [&](const f4& a, const f4& b, const float cbl, const int k) {
+        auto entry = [&](const f4& a, const f4& b, const float cbl, const float zl, const int k) {
             const float go = b.y;
             const float du = fpx - a.x;
             const v2f dv = fpy - a.y;
@@ -527,7 +606,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             const bool alive0 = T.x > 5e-5f, alive1 = T.y > 5e-5f;
             v2f w = al * T;
             w.x = alive0 ? w.x : 0.0f; w.y = alive1 ? w.y : 0.0f;
-            const v2f sdot = b.z * Gr + b.w * Gg + cbl * Gb;
+            v2f sdot = b.z * Gr + b.w * Gg + cbl * Gb;
+            if (AUX) sdot += zl * Gd + Ga;                                 // c+ . G+
             const v2f ar = w * Gr, ag = w * Gg, ab = w * Gb;
             suffix -= w * sdot;                                            // now the sum over k > i
             const v2f sfx = suffix;
@@ -552,8 +632,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             r[5] = m0;                                                     // M0  = sum a = dL/d opacity
             r[6] = hadd(ar); r[7] = hadd(ag);                              // d r, d g
             const float tot_b = all_reduce8(hadd(ab));                     // d b
-            myslot[k * 9] = reduce_scatter8(r, lane);
-            if (j == 0) myslot[k * 9 + 8] = tot_b;         // (two unconditional stores instead -- 3 instructions fewer -- measured no gain)
+            myslot[k * NS] = reduce_scatter8(r, lane);
+            if (j == 0) myslot[k * NS + 8] = tot_b;        // (two unconditional stores instead -- 3 instructions fewer -- measured no gain)
+            if (AUX) {
+                const float tot_z = all_reduce8(hadd(w * Gd));             // S_z = dL/dz
+                if (j == 1) myslot[k * NS + 8] = tot_z;                    // (lane 1 of the group: slot index 9)
+            }
             T = T - al * T;
         };
         // Software pipeline over the queue (LDS latency is not covered by occupancy here: 3 waves per SIMD), two entries per step
@@ -563,14 +647,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         uint32_t oo = *reinterpret_cast<const uint32_t*>(myq);
         f4 a0 = lds_at(s.r0, oo & 0xFFFFu), b0 = lds_at(s.r1, oo & 0xFFFFu), a1 = lds_at(s.r0, oo >> 16), b1 = lds_at(s.r1, oo >> 16);
         float cb0 = lds_at(r2f, oo & 0xFFFFu), cb1 = lds_at(r2f, oo >> 16);
+        float z0 = 0.f, z1 = 0.f;
+        if (AUX) { z0 = lds_at(r2f + 2, oo & 0xFFFFu); z1 = lds_at(r2f + 2, oo >> 16); }
         for (int k0 = 0; k0 < maxc; k0 += 8) {
           const int k1 = min(k0 + 8, maxc);
           for (int k = k0; k < k1; k += 2) {
             oo = *reinterpret_cast<const uint32_t*>(myq + k + 2);                       // entries k + 2, k + 3 (null past the end; k + 3 < QCAP)
-            entry(a0, b0, cb0, k);
+            entry(a0, b0, cb0, z0, k);
             a0 = lds_at(s.r0, oo & 0xFFFFu); b0 = lds_at(s.r1, oo & 0xFFFFu); cb0 = lds_at(r2f, oo & 0xFFFFu);
-            entry(a1, b1, cb1, k + 1);
+            if (AUX) z0 = lds_at(r2f + 2, oo & 0xFFFFu);
+            entry(a1, b1, cb1, z1, k + 1);
             a1 = lds_at(s.r0, oo >> 16); b1 = lds_at(s.r1, oo >> 16); cb1 = lds_at(r2f, oo >> 16);
+            if (AUX) z1 = lds_at(r2f + 2, oo >> 16);
           }
           kdone = k1;
           if (!__any(T.x > 5e-5f || T.y > 5e-5f)) break;          // every 8 entries: all pixels dead
@@ -578,18 +666,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         alive_any = __any(T.x > 5e-5f || T.y > 5e-5f);        // dead pixels stay dead
         __syncthreads();
         {   // entry `lane`: add up the slots of the sub-tiles it was queued in
-            float tot[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            float tot[NS];
+#pragma unroll
+            for (int v = 0; v < NS; ++v) tot[v] = 0.f;
 #pragma unroll
             for (int t = 0; t < N_SUB; ++t) {
                 const int r = (int)((ranks >> (8 * t)) & 0xFFu);
                 if (((m8 >> t) & 1u) && r < kdone) {
-                    const float* p = &sb.slots[(t * MAXQ_BWD + r) * 9];
+                    const float* p = &sb.slots[(t * MAXQ_BWD + r) * NS];
 #pragma unroll
-                    for (int v = 0; v < 9; ++v) tot[v] += p[v];
+                    for (int v = 0; v < NS; ++v) tot[v] += p[v];
                 }
             }
 #pragma unroll
-            for (int v = 0; v < 9; ++v) acc[lane * 9 + v] = tot[v];
+            for (int v = 0; v < NS; ++v) acc[lane * NS + v] = tot[v];
         }
         if (DET && lane < n) {       // entry `lane`: its row's slot = first slot of its Gaussian + ordinal of this list in its rectangle
             const uint32_t id = sb.eid[lane];
@@ -616,14 +706,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             sb.eslot[lane] = det.pair_base[id] + ord;
         }
         __syncthreads();
-        // the chunk's rows -> grad2d: 7 rows x 9 sums per atomic instruction, one 36-byte request per row
-        for (int t0 = 0; t0 < n; t0 += 7) {
+        // the chunk's rows -> grad2d: 7 rows x 9 sums per atomic instruction, one 36-byte request per row (AUX: 6 x 10, 40 bytes)
+        for (int t0 = 0; t0 < n; t0 += RPI) {
             const int c = t0 + my_g;
-            if (lane < 63 && c < n) {
-                const float val = acc[c * 9 + my_k];
+            if (lane < RPI * NS && c < n) {
+                const float val = acc[c * NS + my_k];
                 if (DET) {
                     const uint32_t slot = sb.eslot[c];
-                    if (slot < det.capacity) det.part[(int64_t)slot * 9 + my_k] = val;
+                    if (slot < det.capacity) det.part[(int64_t)slot * NS + my_k] = val;
                 } else if (val != 0.0f) {
                     atomicAdd(&grad2d[(int64_t)sb.eid[c] * 16 + my_k], val);
                 }
@@ -680,21 +770,25 @@ __global__ __launch_bounds__(256) void pair_base_kernel(int64_t n, const uint32_
     }
 }
 
-// grad2d[i][0..8] = sum of Gaussian i's rows, in the order of its lists (row-major in its rectangle): the same order every run.
+// grad2d[i][0..NS-1] = sum of Gaussian i's rows, in the order of its lists (row-major in its rectangle): the same order every run.
+// NS = floats per row: 9, or 10 behind the depth / opacity backward.
+template <int NS = 9>
 __global__ __launch_bounds__(256) void pair_reduce_kernel(int64_t n, const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ pair_base,
                                                           const float* __restrict__ part, uint32_t capacity, float* __restrict__ grad2d) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    float t[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float t[NS];
+#pragma unroll
+    for (int v = 0; v < NS; ++v) t[v] = 0.f;
     const uint32_t nt = tiles[i], pb = pair_base[i];
     for (uint32_t k = 0; k < nt && pb + k < capacity; ++k) {
-        const float* row = part + (int64_t)(pb + k) * 9;
+        const float* row = part + (int64_t)(pb + k) * NS;
 #pragma unroll
-        for (int v = 0; v < 9; ++v) t[v] += row[v];
+        for (int v = 0; v < NS; ++v) t[v] += row[v];
     }
     float* o = grad2d + i * 16;
 #pragma unroll
-    for (int v = 0; v < 9; ++v) o[v] = t[v];
+    for (int v = 0; v < NS; ++v) o[v] = t[v];
 }
 
 }  // namespace

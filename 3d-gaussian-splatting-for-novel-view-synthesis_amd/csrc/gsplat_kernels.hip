@@ -9,6 +9,7 @@
 //   K5  plan_kernel            longest-first launch order of the lists, sort size classes
 //   K6  raster_forward_kernel  one wave64 per 16 x 8-pixel list = eight 8-lane groups, one 4 x 4 sub-tile each   [F14, F15]
 //   K7  raster_backward_kernel same traversal, analytic gradients, sums per group -> LDS slots -> one atomic per pair   [B1]
+//       (K6, K7 <AUX>: depth and opacity maps beside the colour, a background under it -- not in the reference)
 //       (+ tile_block_sum / pair_base / pair_reduce_kernel: deterministic mode)
 //   K8  project_backward_kernel chain rule to the reference's input tensors                     [B2, B3]
 //
@@ -95,9 +96,10 @@ auto project_kernel_for(bool late) { return late ? project_kernel<FUSED, COLOUR,
 
 // the flag bits the backward entries define; a call with any other bit is refused before it does anything (a library that ignored
 // a flag it does not know would, for GSPLAT_BACKWARD_ACCUMULATE, overwrite where the caller adds)
-constexpr int32_t PROJECT_BACKWARD_FLAGS = GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_ACCUMULATE;
-constexpr int32_t BACKWARD_FLAGS = PROJECT_BACKWARD_FLAGS | GSPLAT_BACKWARD_PHASE_RASTER | GSPLAT_BACKWARD_PHASE_PROJECT |
-                                   GSPLAT_BACKWARD_GRAD2D_DIRTY;
+// (GSPLAT_BACKWARD_DEPTH: the two projection entries only -- the composite entries have no depth / opacity frame)
+constexpr int32_t PROJECT_BACKWARD_FLAGS = GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_ACCUMULATE | GSPLAT_BACKWARD_DEPTH;
+constexpr int32_t BACKWARD_FLAGS = GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_ACCUMULATE | GSPLAT_BACKWARD_PHASE_RASTER |
+                                   GSPLAT_BACKWARD_PHASE_PROJECT | GSPLAT_BACKWARD_GRAD2D_DIRTY;
 
 // K8 for gsplat_project_backward, the composite entries (ar: the in-place f_rest step) and gsplat_project_backward_pose (pose: where
 // the camera-pose gradient goes; `out` may then be NULL = pose only).
@@ -122,6 +124,8 @@ int project_backward_impl(const gsplat_gaussians* g, const float* c2w, const gsp
     const bool factored = !pose && fused && !out->f_dc && !out->f_rest;
     const bool jac = fused && (flags & GSPLAT_BACKWARD_SH_JACOBIAN) != 0;
     const bool acc = (flags & GSPLAT_BACKWARD_ACCUMULATE) != 0;
+    const bool depth = (flags & GSPLAT_BACKWARD_DEPTH) != 0;
+    if (depth && (acc || ar)) return fail(GSPLAT_ERR_BAD_ARG, "GSPLAT_BACKWARD_DEPTH goes with the plain backward (no accumulation, no in-place step)");
     if (out) {
         if (!out->pos || !out->opacity_raw) return fail(GSPLAT_ERR_BAD_ARG, "grad pos / opacity_raw is NULL");
         if (acc && (ar || !(jac && !factored)))
@@ -140,9 +144,15 @@ int project_backward_impl(const gsplat_gaussians* g, const float* c2w, const gsp
     AdamRest a = {nullptr, nullptr, nullptr, {0.f, 0.f, 0.f, 0.f, 0.f}, nullptr, 0};
     if (ar) { a = *ar; a.counts = c.ps.counts; }
     const gsplat_gaussian_grads o = out ? *out : gsplat_gaussian_grads{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    // <FUSED, JAC, ADAM, ACC, POSE>: every instantiation there is
+    // <FUSED, JAC, ADAM, ACC, POSE, DEPTH>: every instantiation there is
     const auto kernel = ar    ? project_backward_kernel<true, true, true>
                         : acc ? project_backward_kernel<true, true, false, true>
+                        : depth ? (pose ? (jac     ? project_backward_kernel<true, true, false, false, true, true>
+                                           : fused ? project_backward_kernel<true, false, false, false, true, true>
+                                                   : project_backward_kernel<false, false, false, false, true, true>)
+                                        : (jac     ? project_backward_kernel<true, true, false, false, false, true>
+                                           : fused ? project_backward_kernel<true, false, false, false, false, true>
+                                                   : project_backward_kernel<false, false, false, false, false, true>))
                         : pose ? (jac     ? project_backward_kernel<true, true, false, false, true>
                                   : fused ? project_backward_kernel<true, false, false, false, true>
                                           : project_backward_kernel<false, false, false, false, true>)
@@ -158,6 +168,52 @@ int project_backward_impl(const gsplat_gaussians* g, const float* c2w, const gsp
         LAUNCH("pose_reduce_kernel<final>", pose_reduce_kernel<true>, dim3(1), dim3(256), 0, c.st, prs.part, (int64_t)POSE_PARTS, 1, pose->grad_c2w);
     } else {
         LAUNCH("pose_reduce_kernel<final>", pose_reduce_kernel<true>, dim3(1), dim3(256), 0, c.st, rows, prs.nrows, 1, pose->grad_c2w);
+    }
+    return GSPLAT_OK;
+}
+
+// the background of the depth / opacity entries: 3 host floats, NULL = none (the kernels then add nothing)
+template <class Aux>
+void set_background(Aux& a, const float* background) {
+    a.has_bg = background != nullptr;
+    for (int k = 0; k < 3; ++k) a.bg[k] = background ? background[k] : 0.f;
+}
+
+// K7 and (deterministic mode) the kernels around it, for gsplat_rasterize_backward and gsplat_rasterize_backward_aux (aux: the
+// depth / opacity variant, rows of 10).
+int raster_backward_impl(int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, const void* bin_state,
+                         const float* accum, const float* grad_image, float* grad2d, int32_t grad2d_zeroed, void* det_scratch,
+                         int64_t det_scratch_bytes, void* stream_, const AuxBwd* aux) {
+    const auto [st, vk, nl, nb, ps] = open_ctx(n, v, project_state, stream_);
+    const bool det = det_scratch != nullptr;
+    const int row = aux ? 10 : 9;
+    if (!grad2d_zeroed && !det) HIP_TRY(hipMemsetAsync(grad2d, 0, (size_t)(n > 0 ? n : 0) * 16 * sizeof(float), st));
+    if (n == 0) return GSPLAT_OK;
+    if (n_binned == 0) {
+        if (det) HIP_TRY(hipMemsetAsync(grad2d, 0, (size_t)n * 16 * sizeof(float), st));
+        return GSPLAT_OK;
+    }
+    // deterministic: rows stored per (list, Gaussian) pair, then added per Gaussian in a fixed order
+    const DetScratch ds = carve_det(det_scratch, n, n_binned, row);
+    if (det) {
+        if (ds.bytes > det_scratch_bytes) return fail(GSPLAT_ERR_WORKSPACE, "deterministic-backward scratch too small");
+        const unsigned pb_blocks = (unsigned)((n + PB_BLOCK - 1) / PB_BLOCK);
+        HIP_TRY(hipMemsetAsync(ds.part, 0, (size_t)n_binned * 4 * row, st));          // rows of entries a saturated list never reaches
+        LAUNCH("tile_block_sum_kernel", tile_block_sum_kernel, dim3(pb_blocks), dim3(256), 0, st, n, ps.tiles, ds.block_sum);
+        LAUNCH("pair_base_kernel", pair_base_kernel, dim3(pb_blocks), dim3(256), 0, st, n, ps.tiles, ds.block_sum, ds.pair_base);
+    }
+    const DetArgs da = det ? DetArgs{ps.rect, ps.mask, ps.tiles, ds.pair_base, ds.part, (uint32_t)n_binned} : DetArgs{};
+    if (aux) {
+        LAUNCH(det ? "raster_backward_kernel<deterministic, aux>" : "raster_backward_kernel<aux>", (det ? raster_backward_kernel<true, true> : raster_backward_kernel<false, true>),
+               dim3((unsigned)nl), dim3(64), 0, st, ps.ranges, (const uint32_t*)bin_state, ps.rec, ps.order, vk.lists_x, vk.H, vk.W, vk.chi_clip,
+               vk.alpha_max, vk.alpha_cutoff, accum, grad_image, grad2d, STATS_BWD, (uint32_t)(n - 1), da, pair_mask_of(bin_state, n_binned), *aux);
+    } else {
+        LAUNCH(det ? "raster_backward_kernel<deterministic>" : "raster_backward_kernel", det ? raster_backward_kernel<true> : raster_backward_kernel<false>, dim3((unsigned)nl), dim3(64), 0, st, ps.ranges,
+               (const uint32_t*)bin_state, ps.rec, ps.order, vk.lists_x, vk.H, vk.W, vk.chi_clip, vk.alpha_max, vk.alpha_cutoff,
+               accum, grad_image, grad2d, STATS_BWD, (uint32_t)(n - 1), da, pair_mask_of(bin_state, n_binned), AuxBwd{});
+    }
+    if (det) {
+        LAUNCH("pair_reduce_kernel", aux ? pair_reduce_kernel<10> : pair_reduce_kernel<9>, dim3(blocks256(n)), dim3(256), 0, st, n, ps.tiles, ds.pair_base, ds.part, (uint32_t)n_binned, grad2d);
     }
     return GSPLAT_OK;
 }
@@ -205,6 +261,8 @@ int64_t gsplat_bin_scratch_bytes(int64_t pair_capacity, const gsplat_view* v) {
 }
 
 int64_t gsplat_rasterize_backward_scratch_bytes(int64_t n, int64_t pair_capacity) { return carve_det(nullptr, n, pair_capacity).bytes; }
+
+int64_t gsplat_rasterize_backward_aux_scratch_bytes(int64_t n, int64_t pair_capacity) { return carve_det(nullptr, n, pair_capacity, 10).bytes; }
 
 int64_t gsplat_pose_scratch_bytes(int64_t n) { return n < 0 ? -1 : carve_pose(nullptr, n).bytes; }
 
@@ -341,7 +399,24 @@ int gsplat_rasterize_forward(int64_t n, int64_t n_binned, const gsplat_view* v, 
     LAUNCH("raster_forward_kernel", accum ? raster_forward_kernel<true> : raster_forward_kernel<false>, dim3((unsigned)c.nl), dim3(64), 0, c.st, c.ps.ranges,
            (const uint32_t*)bin_state, c.ps.rec, c.ps.order, c.vk.lists_x, c.vk.H, c.vk.W, c.vk.chi_clip, c.vk.alpha_max, c.vk.alpha_cutoff,
            image, accum, STATS_FWD, (uint32_t)(n > 0 ? n - 1 : 0), grad2d, grad2d ? n : 0,
-           accum ? pair_mask_of(bin_state, n_binned) : nullptr);
+           accum ? pair_mask_of(bin_state, n_binned) : nullptr, AuxFwd{});
+    return GSPLAT_OK;
+}
+
+int gsplat_rasterize_forward_aux(int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, void* bin_state,
+                                 float* image, float* depth, float* alpha, float* accum, float* accum_aux, float* grad2d,
+                                 const float* background, void* stream_) {
+    int rc = check_view(v);
+    if (rc) return rc;
+    if (!project_state || !bin_state || !image) return fail(GSPLAT_ERR_BAD_ARG, "state / image is NULL");
+    if (!accum != !accum_aux) return fail(GSPLAT_ERR_BAD_ARG, "accum and accum_aux go together");
+    const Ctx c = open_ctx(n, v, project_state, stream_);
+    AuxFwd aux = {depth, alpha, accum_aux, {0.f, 0.f, 0.f}, 0};
+    set_background(aux, background);
+    LAUNCH("raster_forward_kernel<aux>", (accum ? raster_forward_kernel<true, true> : raster_forward_kernel<false, true>), dim3((unsigned)c.nl), dim3(64), 0, c.st,
+           c.ps.ranges, (const uint32_t*)bin_state, c.ps.rec, c.ps.order, c.vk.lists_x, c.vk.H, c.vk.W, c.vk.chi_clip, c.vk.alpha_max,
+           c.vk.alpha_cutoff, image, accum, STATS_FWD, (uint32_t)(n > 0 ? n - 1 : 0), grad2d, grad2d ? n : 0,
+           accum ? pair_mask_of(bin_state, n_binned) : nullptr, aux);
     return GSPLAT_OK;
 }
 
@@ -351,32 +426,22 @@ int gsplat_rasterize_backward(int64_t n, int64_t n_binned, const gsplat_view* v,
     int rc = check_view(v);
     if (rc) return rc;
     if (!project_state || !bin_state || !accum || !grad_image || !grad2d) return fail(GSPLAT_ERR_BAD_ARG, "NULL argument");
-    const auto [st, vk, nl, nb, ps] = open_ctx(n, v, project_state, stream_);
-    const bool det = det_scratch != nullptr;
-    if (!grad2d_zeroed && !det) HIP_TRY(hipMemsetAsync(grad2d, 0, (size_t)(n > 0 ? n : 0) * 16 * sizeof(float), st));
-    if (n == 0) return GSPLAT_OK;
-    if (n_binned == 0) {
-        if (det) HIP_TRY(hipMemsetAsync(grad2d, 0, (size_t)n * 16 * sizeof(float), st));
-        return GSPLAT_OK;
-    }
-    // deterministic: rows stored per (list, Gaussian) pair, then added per Gaussian in a fixed order
-    const DetScratch ds = carve_det(det_scratch, n, n_binned);
-    if (det) {
-        if (ds.bytes > det_scratch_bytes) return fail(GSPLAT_ERR_WORKSPACE, "deterministic-backward scratch too small");
-        const unsigned pb_blocks = (unsigned)((n + PB_BLOCK - 1) / PB_BLOCK);
-        HIP_TRY(hipMemsetAsync(ds.part, 0, (size_t)n_binned * 36, st));          // rows of entries a saturated list never reaches
-        LAUNCH("tile_block_sum_kernel", tile_block_sum_kernel, dim3(pb_blocks), dim3(256), 0, st, n, ps.tiles, ds.block_sum);
-        LAUNCH("pair_base_kernel", pair_base_kernel, dim3(pb_blocks), dim3(256), 0, st, n, ps.tiles, ds.block_sum, ds.pair_base);
-    }
-    LAUNCH(det ? "raster_backward_kernel<deterministic>" : "raster_backward_kernel", det ? raster_backward_kernel<true> : raster_backward_kernel<false>, dim3((unsigned)nl), dim3(64), 0, st, ps.ranges,
-           (const uint32_t*)bin_state, ps.rec, ps.order, vk.lists_x, vk.H, vk.W, vk.chi_clip, vk.alpha_max, vk.alpha_cutoff,
-           accum, grad_image, grad2d, STATS_BWD, (uint32_t)(n - 1),
-           det ? DetArgs{ps.rect, ps.mask, ps.tiles, ds.pair_base, ds.part, (uint32_t)n_binned} : DetArgs{},
-           pair_mask_of(bin_state, n_binned));
-    if (det) {
-        LAUNCH("pair_reduce_kernel", pair_reduce_kernel, dim3(blocks256(n)), dim3(256), 0, st, n, ps.tiles, ds.pair_base, ds.part, (uint32_t)n_binned, grad2d);
-    }
-    return GSPLAT_OK;
+    return raster_backward_impl(n, n_binned, v, project_state, bin_state, accum, grad_image, grad2d, grad2d_zeroed, det_scratch, det_scratch_bytes,
+                                stream_, nullptr);
+}
+
+int gsplat_rasterize_backward_aux(int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, const void* bin_state,
+                                  const float* accum, const float* accum_aux, const float* grad_image, const float* grad_depth,
+                                  const float* grad_alpha, const float* background, float* grad2d, int32_t grad2d_zeroed,
+                                  void* det_scratch, int64_t det_scratch_bytes, void* stream_) {
+    int rc = check_view(v);
+    if (rc) return rc;
+    if (!grad_image && !grad_depth && !grad_alpha) return fail(GSPLAT_ERR_BAD_ARG, "grad_image, grad_depth and grad_alpha are all NULL");
+    if (!project_state || !bin_state || !accum || !accum_aux || !grad2d) return fail(GSPLAT_ERR_BAD_ARG, "NULL argument");
+    AuxBwd aux = {accum_aux, grad_depth, grad_alpha, {0.f, 0.f, 0.f}, 0};
+    set_background(aux, background);
+    return raster_backward_impl(n, n_binned, v, project_state, bin_state, accum, grad_image, grad2d, grad2d_zeroed, det_scratch, det_scratch_bytes,
+                                stream_, &aux);
 }
 
 int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state,
@@ -388,7 +453,7 @@ int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const g
 int gsplat_project_backward_pose(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state,
                                  const float* grad2d, const gsplat_gaussian_grads* out, float* grad_c2w, void* pose_scratch,
                                  int64_t pose_scratch_bytes, int32_t flags, void* stream_) {
-    if (flags & ~GSPLAT_BACKWARD_SH_JACOBIAN) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
+    if (flags & ~(GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_DEPTH)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
     const PoseOut pose = {grad_c2w, pose_scratch, pose_scratch_bytes};
     return project_backward_impl(g, c2w, v, project_state, grad2d, out, flags, stream_, nullptr, &pose);
 }

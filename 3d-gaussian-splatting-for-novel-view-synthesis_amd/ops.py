@@ -4,6 +4,7 @@ Mirrors the reference's operator interface (same names, argument meaning, defaul
 
     render(pos, color, opacity_raw, sigma, c2w, H, W, fx, fy, cx, cy, near=0.01, far=100.0, pix_guard=32, T=16,
            min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1/128.)      reference render.py:62-64
+           (+ keyword-only aux=False, background=None: depth and opacity maps, a background colour -- not in the reference)
     build_sigma_from_params(scale_raw, q_raw)                                               reference gaussian.py:71
     evaluate_sh(f_dc, f_rest, points, c2w)                                   reference spherical_harmonics.py:70
 
@@ -352,7 +353,7 @@ class _Frame:
     (project_state | bin_state | accum | grad2d, carved by the library); one that went through the separate calls keeps them
     as separate buffers."""
     __slots__ = ("view", "n", "n_pairs", "proj_state", "bin_state", "accum", "fused", "inputs", "c2w", "empty", "grad2d", "sh_jacobian",
-                 "arena", "gaussians", "dirty", "src_ptrs", "route", "pose")
+                 "arena", "gaussians", "dirty", "src_ptrs", "route", "pose", "aux", "background", "accum_aux")
 
 
 class _Pending:
@@ -377,7 +378,8 @@ def _new_frame(fused, view, n, pos32, opa32, c2w32, ins, c, d):
     fr.view, fr.n, fr.fused, fr.c2w, fr.empty, fr.sh_jacobian = view, n, fused, c2w32, False, False
     fr.inputs = dict(pos=pos32, opacity_raw=opa32, **ins)
     fr.arena = fr.gaussians = fr.proj_state = fr.bin_state = fr.accum = fr.grad2d = fr.route = None
-    fr.dirty = fr.pose = False
+    fr.dirty = fr.pose = fr.aux = False
+    fr.background = fr.accum_aux = None
     # the caller's own SH tensors (before any dtype / layout conversion): what dp.FactoredExchange.owns() compares
     fr.src_ptrs = (c.data_ptr(), d.data_ptr()) if fused else None
     return fr
@@ -388,21 +390,28 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
     (pending, None), or (None, result) when nothing is left to do: zero Gaussians, or -- inside a deferred_checks() block once a
     pair capacity is known for this image size -- the whole forward pass was queued by ONE library call
     (gsplat_forward_deferred) and the result is there.  view.pose (set by _RenderFn): the backward pass will also form dL/dc2w
-    (a pose frame: always the separate library calls, never a gradient route)."""
+    (a pose frame: always the separate library calls, never a gradient route).  view.aux / view.background (set by render() and
+    render_gaussians()): an aux frame -- depth and opacity maps, or an image over a background -- which takes the separate library
+    calls like a pose frame; its result is the tuple (image, depth, alpha), depth and alpha None without aux=True."""
     pose = getattr(view, "pose", False)
     if pose and _route.get() is not None:
         raise RuntimeError("a camera-pose gradient (c2w.requires_grad) is not available inside a gradient_route() block "
                            "(factored exchange, folded f_rest step, accumulate_grads): render the pose frame outside it")
+    auxf = _is_aux(view)
+    if auxf and _route.get() is not None:
+        raise RuntimeError("depth / opacity maps and a background (aux=True, background=...) are not available inside a gradient_route() "
+                           "block (factored exchange, folded f_rest step, accumulate_grads): render the frame outside it")
     lib = _abi.lib()
     dev = pos.device
     n = pos.shape[0]
     pos32, opa32, c2w32, ins = _convert_inputs(fused, n, pos, opacity_raw, c2w, a, b, c, d)
     fr = _new_frame(fused, view, n, pos32, opa32, c2w32, ins, c, d)
     fr.pose = pose
+    fr.aux, fr.background = auxf, view.background if auxf else None
     if n == 0:      # nothing survives by construction: the reference returns the zero image (render.py:109-112)
         fr.empty = True
         fr.route = _route_of(fr, False) if need_grad else None
-        return None, (torch.zeros((view.H, view.W, 3), dtype=torch.float32, device=dev), fr, _abi.Counts(0, 0, 0, 0, 0, 0))
+        return None, (_empty_result(view, dev), fr, _abi.Counts(0, 0, 0, 0, 0, 0))
     g = _make_gaussians(n, pos32, opa32, **ins)
     ckey = capacity_key(dev, view, n)
     capacity = _ws.pair_capacity(ckey) if _deferred_stack else 0
@@ -419,7 +428,7 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
     pinned, slot = _ws.next_pinned(dev, key, chk)
     ready = _ws.get_event(dev, fresh=deferred, key=key)
     wants_stages = _timer is not None and _timer.wants(_FORWARD_STAGES)
-    composite = deferred and _composite and not wants_stages and not pose
+    composite = deferred and _composite and not wants_stages and not pose and not auxf
     fr.route = _route_of(fr, composite) if need_grad else None
     if composite:
         # ---- the whole forward pass in one call, on one arena
@@ -453,6 +462,30 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
                                       counters.numel(), C.c_void_p(pinned.data_ptr()), C.c_void_p(ready.cuda_event),
                                       flags, st), "gsplat_project")
     return pend, None
+
+
+def _is_aux(view):
+    return view.aux or view.background is not None
+
+
+def _empty_result(view, dev):
+    """What a frame without a survivor returns: the zero image; an aux frame (image, depth, alpha) -- the image is the clamped
+    background where one is given, the maps are zero (None without aux=True)."""
+    H, W = view.H, view.W
+    if not _is_aux(view):
+        return torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+    if view.background is None:
+        image = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+    else:
+        image = torch.tensor(view.background, dtype=torch.float32, device=dev).clamp_(0.0, 1.0).expand(H, W, 3).contiguous()
+    if not view.aux:
+        return image, None, None
+    return image, torch.zeros((H, W), dtype=torch.float32, device=dev), torch.zeros((H, W), dtype=torch.float32, device=dev)
+
+
+def _background_arg(background):
+    """The 3 host floats the aux entries read during the call (NULL = no background)."""
+    return (C.c_float * 3)(*background) if background is not None else None
 
 
 _COUNTER_BYTES = 0
@@ -499,7 +532,7 @@ def _forward_end(pend, need_grad):
         if scene == _abi.GSPLAT_SCENE_ALL_CULLED:
             fr.empty = True
             fr.proj_state = None
-            return image.zero_(), fr, counts
+            return (_empty_result(view, dev) if fr.aux else image.zero_()), fr, counts
         fr.n_pairs = int(counts.n_binned)        # pairs actually binned (16 x 8 lists); counts.n_pairs = the reference's P
     fr.bin_state = torch.empty(lib.gsplat_bin_state_bytes(fr.n_pairs, C.byref(view)), dtype=torch.uint8, device=dev)
     scratch = _ws.get_scratch(dev, lib.gsplat_bin_scratch_bytes(fr.n_pairs, C.byref(view)), pend.key)
@@ -511,6 +544,16 @@ def _forward_end(pend, need_grad):
     # there are so few lists that a wave's share would be long
     lists = ((W + 15) // 16) * ((H + 7) // 8)
     fr.grad2d = torch.empty((n, 16), dtype=torch.float32, device=dev) if need_grad and n <= 256 * lists else None
+    if fr.aux:
+        # depth and opacity beside the colour (and the colour over the background): the aux variant of the raster kernel
+        depth = torch.empty((H, W), dtype=torch.float32, device=dev) if view.aux else None
+        alpha = torch.empty((H, W), dtype=torch.float32, device=dev) if view.aux else None
+        fr.accum_aux = torch.empty((H, W, 2), dtype=torch.float32, device=dev) if need_grad else None
+        with _stage("raster_forward"):
+            _abi.check(lib.gsplat_rasterize_forward_aux(n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state), _p(image),
+                                                        _p(depth), _p(alpha), _p(fr.accum), _p(fr.accum_aux), _p(fr.grad2d),
+                                                        _background_arg(fr.background), st), "gsplat_rasterize_forward_aux")
+        return (image, depth, alpha), fr, counts
     with _stage("raster_forward"):
         _abi.check(lib.gsplat_rasterize_forward(n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state),
                                                 _p(image), _p(fr.accum), _p(fr.grad2d), st), "gsplat_rasterize_forward")
@@ -643,27 +686,28 @@ _SH = ("f_dc", "f_rest")
 _GRAD_FIELDS = tuple(name for name, _ in _abi.GaussianGrads._fields_)
 
 
-def _backward_impl(fr, grad_image, need_params=True):
+def _backward_impl(fr, grad_image, need_params=True, grad_depth=None, grad_alpha=None):
     """Returns a dict name -> fp32 gradient tensor of the inputs of the forward call (a missing name: fr.route took that gradient);
-    a pose frame adds "c2w" (fp32 [4, 4]).  need_params = False (pose frames): only the pose gradient is wanted."""
+    a pose frame adds "c2w" (fp32 [4, 4]).  need_params = False (pose frames): only the pose gradient is wanted.  An aux frame:
+    grad_image, grad_depth, grad_alpha are the upstream gradients of its three outputs, None where the loss does not read one."""
     lib = _abi.lib()
     ins, route = fr.inputs, fr.route
     dev = ins["pos"].device
     factored = isinstance(route, dp.FactoredExchange)
-    if fr.empty or fr.n == 0:
+    if fr.empty or fr.n == 0 or (fr.aux and grad_image is None and grad_depth is None and grad_alpha is None):
         if factored:
             route.add(torch.zeros((fr.n, 3), dtype=torch.float32, device=dev), fr.c2w[:3, 3])
         out = {k: torch.zeros_like(v) for k, v in ins.items() if not (factored and k in _SH)}
         if fr.pose:
             out["c2w"] = torch.zeros((4, 4), dtype=torch.float32, device=dev)
         return out
-    gi = _f32(grad_image, (fr.view.H, fr.view.W, 3), "grad_image")
+    gi = _f32(grad_image, (fr.view.H, fr.view.W, 3), "grad_image") if grad_image is not None else None
     if torch.cuda.current_device() != dev.index:
         torch.cuda.set_device(dev)
     stream = torch.cuda.current_stream(dev)
     st = C.c_void_p(stream.cuda_stream)
-    det = (_ws.get_scratch(dev, lib.gsplat_rasterize_backward_scratch_bytes(fr.n, fr.n_pairs), (dev.type, dev.index, stream.cuda_stream))
-           if _deterministic else None)
+    det_bytes = lib.gsplat_rasterize_backward_aux_scratch_bytes if fr.aux else lib.gsplat_rasterize_backward_scratch_bytes
+    det = _ws.get_scratch(dev, det_bytes(fr.n, fr.n_pairs), (dev.type, dev.index, stream.cuda_stream)) if _deterministic else None
     staged = _timer is not None and _timer.wants(_BACKWARD_STAGES)
     # only known now, each sending the frame down the ordinary backward: a timed pass (phase by phase), a second pass through the
     # frame (views' sum), a step of f_rest already applied (folded step)
@@ -682,10 +726,21 @@ def _backward_impl(fr, grad_image, need_params=True):
         zeroed = fr.grad2d is not None
         grad2d = fr.grad2d if zeroed else torch.empty((fr.n, 16), dtype=torch.float32, device=dev)
         fr.grad2d = None                       # a second backward through the same graph must not reuse a dirty buffer
-        with _stage("raster_backward"):
-            _abi.check(lib.gsplat_rasterize_backward(fr.n, fr.n_pairs, C.byref(fr.view), _p(fr.proj_state), _p(fr.bin_state),
-                                                     _p(fr.accum), _p(gi), _p(grad2d), int(zeroed), _p(det),
-                                                     det.numel() if det is not None else 0, st), "gsplat_rasterize_backward")
+        if fr.aux:
+            # (z, 1) as two more colour channels; column 9 of grad2d = dL/dz, which the projection backward picks up (DEPTH)
+            gd = _f32(grad_depth, (fr.view.H, fr.view.W), "grad_depth") if grad_depth is not None else None
+            ga = _f32(grad_alpha, (fr.view.H, fr.view.W), "grad_alpha") if grad_alpha is not None else None
+            with _stage("raster_backward"):
+                _abi.check(lib.gsplat_rasterize_backward_aux(fr.n, fr.n_pairs, C.byref(fr.view), _p(fr.proj_state), _p(fr.bin_state),
+                                                             _p(fr.accum), _p(fr.accum_aux), _p(gi), _p(gd), _p(ga),
+                                                             _background_arg(fr.background), _p(grad2d), int(zeroed), _p(det),
+                                                             det.numel() if det is not None else 0, st), "gsplat_rasterize_backward_aux")
+            jac |= _abi.GSPLAT_BACKWARD_DEPTH
+        else:
+            with _stage("raster_backward"):
+                _abi.check(lib.gsplat_rasterize_backward(fr.n, fr.n_pairs, C.byref(fr.view), _p(fr.proj_state), _p(fr.bin_state),
+                                                         _p(fr.accum), _p(gi), _p(grad2d), int(zeroed), _p(det),
+                                                         det.numel() if det is not None else 0, st), "gsplat_rasterize_backward")
         if factored:
             # logit gradients first: the exchange may start on them while the projection backward runs
             glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=dev)
@@ -753,7 +808,8 @@ def sh_accumulate(pos, eyes, grad_logit, scale=1.0):
 
 
 class _RenderFn(torch.autograd.Function):
-    """Autograd node for both entry points; gradients for the tensor inputs, c2w included (the scalars get None)."""
+    """Autograd node for both entry points; gradients for the tensor inputs, c2w included (the scalars get None).  One output, the
+    image -- or, with view.aux, the three outputs (image, depth, alpha)."""
 
     @staticmethod
     def forward(ctx, fused, view, c2w, pos, opacity_raw, a, b, c, d):
@@ -762,6 +818,10 @@ class _RenderFn(torch.autograd.Function):
         need = view.grad_mode and any(ctx.needs_input_grad)
         view.pose = bool(view.grad_mode and ctx.needs_input_grad[2])     # a pose frame: c2w wants a gradient too (Python-side attribute)
         image, fr, counts = _forward_impl(fused, view, c2w, pos, opacity_raw, a, b, c, d, need)
+        depth = alpha = None
+        if fr.aux:
+            image, depth, alpha = image
+            ctx.set_materialize_grads(False)     # an output the loss does not read: None, not a map of zeros
         ctx.frame = fr
         ctx.c2w_dtype = c2w.dtype
         ctx.dtypes = [t.dtype if isinstance(t, torch.Tensor) else None for t in (pos, opacity_raw, a, b, c, d)]
@@ -770,12 +830,16 @@ class _RenderFn(torch.autograd.Function):
         if counts is not None:                   # (a deferred frame's counters are read in DeferredChecks.verify())
             ctx.counts = _last_counts = (counts.n_survivors, counts.n_visible, int(counts.n_pairs))
             _last_binned = int(counts.n_binned)
-        return image if pos.dtype == torch.float32 else image.to(pos.dtype)
+        if pos.dtype != torch.float32:
+            image = image.to(pos.dtype)
+        if not view.aux:
+            return image
+        return image, depth.to(pos.dtype), alpha.to(pos.dtype)
 
     @staticmethod
-    def backward(ctx, grad_image):
+    def backward(ctx, grad_image, grad_depth=None, grad_alpha=None):
         fr = ctx.frame
-        g = _backward_impl(fr, grad_image, any(ctx.needs_input_grad[3:]))
+        g = _backward_impl(fr, grad_image, any(ctx.needs_input_grad[3:]), grad_depth, grad_alpha)
         names = ("pos", "opacity_raw") + (("scale_raw", "q_raw", "f_dc", "f_rest") if fr.fused else ("color", "sigma", None, None))
         outs = []
         for i, nm in enumerate(names):
@@ -798,11 +862,24 @@ def _view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_c
     view = _abi.make_view(int(H), int(W), float(fx), float(fy), float(cx), float(cy), near, far, pix_guard, T, min_conis,
                           chi_square_clip, alpha_max, alpha_cutoff)
     view.grad_mode = torch.is_grad_enabled()            # Python-side attribute (not part of the C struct)
+    view.aux, view.background = False, None             # (likewise: set by _aux_view)
+    return view
+
+
+def _aux_view(view, aux, background):
+    """aux = True: the render also returns the depth and the opacity map; background (3 numbers, a sequence or a tensor): the image
+    is composited over that colour.  The background is a constant: it gets no gradient."""
+    view.aux = bool(aux)
+    if background is not None:
+        vals = background.detach().reshape(-1).tolist() if isinstance(background, torch.Tensor) else list(background)
+        if len(vals) != 3:
+            raise ValueError("background must hold 3 numbers (r, g, b)")
+        view.background = tuple(float(x) for x in vals)
     return view
 
 
 def render(pos, color, opacity_raw, sigma, c2w, H, W, fx, fy, cx, cy, near=0.01, far=100.0, pix_guard=32, T=16,
-           min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128.):
+           min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128., *, aux=False, background=None):
     """Drop-in for the reference render() (gaussian_splatting/render.py:62-410).
 
     Returns the image [H, W, 3] in [0, 1], same dtype/device as `pos`, differentiable w.r.t. pos, color, opacity_raw,
@@ -810,18 +887,27 @@ def render(pos, color, opacity_raw, sigma, c2w, H, W, fx, fy, cx, cy, near=0.01,
     the separate library calls and may not be rendered inside a gradient_route() block).  No opacity / frustum / finite
     survivor -> zero image with zero gradients; survivors but none on screen -> Exception("All projected points are
     off-screen"), as in the reference.
+
+    Beyond the reference (keyword-only; the defaults are the reference's call).  With w_i = alpha_i T_i [T_i > 5e-5] of the
+    composite, C = sum w_i c_i, A = sum w_i, D = sum w_i z_i (z_i = camera-space depth of Gaussian i):
+      aux=True          returns (image, depth, alpha): depth = D and alpha = A, [H, W] each in pos.dtype, neither clamped nor
+                        normalised (the expected depth is depth / alpha), differentiable like the image, c2w included.
+      background=(r, g, b)   image = clamp(C + (1 - A) * background, 0, 1); a constant (sequence or tensor of 3 numbers), no
+                        gradient.  No survivor: the clamped background, zero maps.
+    Such a frame takes the separate library calls and may not be rendered inside a gradient_route() block.
     """
-    view = _view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff)
+    view = _aux_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), aux, background)
     return _RenderFn.apply(False, view, c2w, pos, opacity_raw, color, sigma, None, None)
 
 
 def render_gaussians(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2w, H, W, fx, fy, cx, cy, near=0.01, far=100.0,
-                     pix_guard=32, T=16, min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128.):
+                     pix_guard=32, T=16, min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128., *, aux=False,
+                     background=None):
     """Fused entry: render(pos, evaluate_sh(f_dc, f_rest, pos, c2w), opacity_raw, build_sigma_from_params(scale_raw,
     q_raw), c2w, ...) in one pass (the reference's three-call sequence, scripts/train.py:463,502,505-508).  Differentiable
     w.r.t. the six parameter tensors and c2w (through the camera transform, the covariance rotation and the SH view
-    direction), as render() is."""
-    view = _view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff)
+    direction), as render() is.  aux, background: as for render()."""
+    view = _aux_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), aux, background)
     return _RenderFn.apply(True, view, c2w, pos, opacity_raw, scale_raw, q_raw, f_dc, f_rest)
 
 

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define GSPLAT_ABI_VERSION 11
+#define GSPLAT_ABI_VERSION 12
 
 /* call status */
 #define GSPLAT_OK 0
@@ -198,6 +198,19 @@ int gsplat_bin(int64_t n, int64_t pair_capacity, const gsplat_view* v, const voi
 int gsplat_rasterize_forward(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state,
                              void* bin_state, float* image, float* accum, float* grad2d, void* stream);
 
+/* The same compositing with a depth map, an opacity map and a background (no counterpart in the reference).  With
+ * w_i = alpha_i T_i [T_i > 5e-5] (the reference's alpha, T and alive rule) a pixel gets
+ *     C = sum w_i c_i,   A = sum w_i,   D = sum w_i z_i      (z_i = camera-space depth of Gaussian i)
+ *     image = clamp(C + (1 - A) bg, 0, 1),   depth = D,   alpha = A     (D and A neither clamped nor normalised: the expected
+ *                                                                        depth is D / A, formed by the caller)
+ *   depth, alpha   [H,W] each, nullable (a background alone).
+ *   accum, accum_aux  both or neither; for gsplat_rasterize_backward_aux: accum[H,W,3] = C as above, accum_aux[H,W,2] = (D, A).
+ *   background     3 floats in HOST memory, read during the call; NULL = none (the image is gsplat_rasterize_forward's).
+ * Everything else as for gsplat_rasterize_forward.                                                                        */
+int gsplat_rasterize_forward_aux(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state,
+                                 void* bin_state, float* image, float* depth, float* alpha, float* accum, float* accum_aux,
+                                 float* grad2d, const float* background, void* stream);
+
 /* ---- backward ---------------------------------------------------------------------------------- */
 /* B1: gradient of the compositing w.r.t. the per-Gaussian 2D quantities.  grad2d is [n,16] floats, private to the
  * library (moments of dL/dq over the pixels for the centre and the conic, then opacity, r, g, b, padding); it is zeroed
@@ -213,6 +226,19 @@ int gsplat_rasterize_backward(int64_t n, int64_t pair_capacity, const gsplat_vie
                               float* grad2d, int32_t grad2d_zeroed, void* det_scratch, int64_t det_scratch_bytes,
                               void* stream);
 
+/* B1 behind gsplat_rasterize_forward_aux: upstream gradients of the image, the depth map and the opacity map ([H,W,3], [H,W],
+ * [H,W]; a NULL one means zeros, all three NULL is GSPLAT_ERR_BAD_ARG).  (z, 1) are two more colour channels: with
+ * c+ = (r, g, b, z, 1) and G+ = (G_r, G_g, G_b, G_D, G_A - sum_c G_c bg_c), G_c masked by the clamp of C + (1 - A) bg,
+ *     d alpha_i = alive_i T_i (c+_i . G+) - (sum_{k>i} w_k c+_k . G+) / (1 - alpha_i).
+ * grad2d gets one column more: column 9 = dL/dz_i = sum over the pixels of w_i G_D, which gsplat_project_backward[_pose] adds to
+ * the camera-space depth gradient when given GSPLAT_BACKWARD_DEPTH.  `background` as in the forward call (the same values).
+ * Deterministic mode as for gsplat_rasterize_backward, with a scratch of gsplat_rasterize_backward_aux_scratch_bytes (rows of 10). */
+int64_t gsplat_rasterize_backward_aux_scratch_bytes(int64_t n, int64_t pair_capacity);
+int gsplat_rasterize_backward_aux(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state,
+                                  const void* bin_state, const float* accum, const float* accum_aux, const float* grad_image,
+                                  const float* grad_depth, const float* grad_alpha, const float* background, float* grad2d,
+                                  int32_t grad2d_zeroed, void* det_scratch, int64_t det_scratch_bytes, void* stream);
+
 /* B2 (+B3 when fused): chain the 2D gradients back to the inputs of gsplat_project.
  * Factored form (fused inputs; out->f_dc and out->f_rest NULL): instead of the 48 SH-coefficient
  * gradients per Gaussian, out->color[n,3] (if given) receives the gradient w.r.t. the colour LOGIT (the sigmoid's argument,
@@ -220,8 +246,11 @@ int gsplat_rasterize_backward(int64_t n, int64_t pair_capacity, const gsplat_vie
  *   flags          GSPLAT_BACKWARD_SH_JACOBIAN: project_state was filled by gsplat_project with
  *                  GSPLAT_PROJECT_SAVE_SH_JACOBIAN for the SAME g and c2w (same results up to fp32 rounding, 144 bytes
  *                  less HBM traffic per visible Gaussian).  Without the flag the SH coefficients are read again.
+ *                  GSPLAT_BACKWARD_DEPTH: grad2d comes from gsplat_rasterize_backward_aux -- its column 9 holds dL/dz of the
+ *                  Gaussian's camera-space depth, which joins the position (and pose) gradient.  Not with ACCUMULATE.
  *                  Also GSPLAT_BACKWARD_ACCUMULATE (below); any other bit is refused with GSPLAT_ERR_BAD_ARG.             */
 #define GSPLAT_BACKWARD_SH_JACOBIAN 1
+#define GSPLAT_BACKWARD_DEPTH 64
 int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v,
                             const void* project_state, const float* grad2d, const gsplat_gaussian_grads* out,
                             int32_t flags, void* stream);
@@ -230,7 +259,7 @@ int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const g
  * the same grad2d (render.py:122,156-159 and spherical_harmonics.py:132 differentiated w.r.t. c2w; its last row is 0).
  *   out            as for gsplat_project_backward (all gradients of the inputs, not factored), or NULL: the pose gradient only.
  *   pose_scratch   gsplat_pose_scratch_bytes(n) bytes, 64-byte aligned, caller-owned; nothing needs clearing.
- *   flags          GSPLAT_BACKWARD_SH_JACOBIAN only; any other bit is refused with GSPLAT_ERR_BAD_ARG.
+ *   flags          GSPLAT_BACKWARD_SH_JACOBIAN and GSPLAT_BACKWARD_DEPTH; any other bit is refused with GSPLAT_ERR_BAD_ARG.
  * The per-Gaussian terms are added in a fixed order, without atomics: the same inputs give the same bits.  NULL grad_c2w is
  * GSPLAT_ERR_BAD_ARG, a scratch below the size GSPLAT_ERR_WORKSPACE.                                                       */
 int64_t gsplat_pose_scratch_bytes(int64_t n);
@@ -259,7 +288,8 @@ int gsplat_project_backward_pose(const gsplat_gaussians* g, const float* c2w, co
  *                 with GSPLAT_FRAME_BACKWARD from fused inputs without GSPLAT_FRAME_NO_SH_JACOBIAN);
  *                 GSPLAT_BACKWARD_PHASE_RASTER / _PROJECT: only that half (a data-parallel host starts exchanging grad_logit
  *                 between the two); GSPLAT_BACKWARD_GRAD2D_DIRTY: a second backward pass through the same frame;
- *                 GSPLAT_BACKWARD_ACCUMULATE (below).  Any other bit is refused with GSPLAT_ERR_BAD_ARG.                      */
+ *                 GSPLAT_BACKWARD_ACCUMULATE (below).  Any other bit is refused with GSPLAT_ERR_BAD_ARG, GSPLAT_BACKWARD_DEPTH
+ *                 included: a depth / opacity frame takes the separate calls.                                               */
 #define GSPLAT_FRAME_BACKWARD 1
 #define GSPLAT_FRAME_NO_SH_JACOBIAN 2
 #define GSPLAT_BACKWARD_PHASE_RASTER 2

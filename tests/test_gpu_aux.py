@@ -1,0 +1,379 @@
+"""GPU tests of the depth map, the opacity map and the background: render(..., aux=True, background=...) against the float64 oracle
+of tests/aux_oracle.py.  The bounds are tests/util.py's (check_image, check_grad, K_CAL), each calibrated by the float32 run of the
+same oracle on the same inputs, as tests/test_gpu_pose_grad.py calibrates with torch_port.render_fused.  Image and alpha are compared
+as they are, depth after dividing both sides by max|depth| of the float64 frame (one chi-square flip is then worth at most the
+4.4e-2 it is worth in the image).  References are computed once per (scene, background, loss) and shared."""
+import ctypes as C
+import functools
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import torch_port as tp
+from tests import aux_oracle, device_frame, util
+
+pytestmark = pytest.mark.gpu
+abi = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd._abi")
+DEV = "cuda:0"
+F32, F64 = torch.float32, torch.float64
+NAMES = ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")
+UNFUSED = ("pos", "color", "opacity_raw", "sigma")
+STACKED = "stacked"
+BG = (1.0, 0.5, 0.25)
+
+
+# ---- scenes and loss weights ---------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def _scene(name):
+    """A golden, or the scene of the capped-queue path: ONE 16 x 8 list holding 300 low-opacity Gaussians -- 5 chunks, and every
+    central sub-tile queue is cut at the backward kernel's cap."""
+    if name != STACKED:
+        d = util.load(name)
+        rng = np.random.default_rng(11)
+        d["w_img"] = d["wrand"]
+    else:
+        rng = np.random.default_rng(5)
+        n, H, W, f = 300, 8, 16, 20.0
+        z = rng.uniform(3, 6, n)
+        pos = np.stack([rng.uniform(-0.3, 0.3, n), rng.uniform(-0.15, 0.15, n), z], 1)
+        d = dict(pos=pos, scale_raw=np.log(rng.uniform(0.3, 0.7, (n, 3))), q_raw=rng.normal(0, 1, (n, 4)),
+                 opacity_raw=rng.uniform(-4.2, -3.4, n), f_dc=0.5 * rng.normal(0, 1, (n, 3)), f_rest=0.1 * rng.normal(0, 1, (n, 45)))
+        d = {k: v.astype(np.float32) for k, v in d.items()}
+        d.update(c2w=np.eye(4, dtype=np.float32), H=H, W=W, fx=f, fy=f, cx=W / 2, cy=H / 2, kwargs={})
+        rng = np.random.default_rng(11)
+        d["w_img"] = rng.uniform(0, 1, (H, W, 3))
+    d["w_depth"] = rng.uniform(0, 1, (d["H"], d["W"])) / 8
+    d["w_alpha"] = rng.uniform(-1, 1, (d["H"], d["W"]))
+    return d
+
+
+def _loss(out, d, dtype, device, which):
+    """L = sum image * w_img + sum depth * w_depth + sum alpha * w_alpha, or one of the three terms."""
+    terms = dict(image=(out[0], "w_img"), depth=(out[1], "w_depth"), alpha=(out[2], "w_alpha"))
+    use = terms if which == "all" else {which: terms[which]}
+    return sum((t * torch.as_tensor(np.asarray(d[w]), dtype=dtype, device=device)).sum() for t, w in use.values())
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(name, dtype, background=None, which="all"):
+    """(image, depth, alpha, gradients incl. c2w) of the oracle in `dtype`, as float64 numpy arrays."""
+    d = _scene(name)
+    p = {k: torch.tensor(d[k], dtype=dtype, requires_grad=True) for k in NAMES}
+    c = torch.tensor(d["c2w"], dtype=dtype, requires_grad=True)
+    out = aux_oracle.render_aux(*[p[k] for k in NAMES], c, *util.cam_args(d), background=background, **d["kwargs"])
+    _loss(out, d, dtype, "cpu", which).backward()
+    grads = {k: v.grad.double().numpy() for k, v in p.items()}
+    grads["c2w"] = c.grad.double().numpy()
+    return tuple(t.detach().double().numpy() for t in out) + (grads,)
+
+
+def _render(gs, name, which="all", aux=True, background=None, c2w_grad=True, fn=None):
+    d = _scene(name)
+    p = {k: torch.tensor(d[k], dtype=F32, device=DEV, requires_grad=True) for k in NAMES}
+    c = torch.tensor(d["c2w"], dtype=F32, device=DEV, requires_grad=c2w_grad)
+    kw = dict(d["kwargs"], aux=aux)
+    if background is not None:
+        kw["background"] = background
+    out = gs.render_gaussians(*[p[k] for k in NAMES], c, *util.cam_args(d), **kw)
+    if fn is not None:
+        fn(out)
+    if aux:
+        _loss(out, d, F32, DEV, which).backward()
+    else:
+        (out * torch.as_tensor(np.asarray(d["w_img"]), dtype=F32, device=DEV)).sum().backward()
+    torch.cuda.synchronize()
+    grads = {k: v.grad for k, v in p.items()}
+    grads["c2w"] = c.grad
+    return out, grads
+
+
+def _check_maps(out, ref, cal, what):
+    img, depth, alpha = (t.detach().double().cpu().numpy() for t in out)
+    assert out[0].dtype == out[1].dtype == out[2].dtype == F32
+    assert depth.shape == alpha.shape == img.shape[:2]
+    util.check_image(img, ref[0], cal=cal[0], what=f"{what} image")
+    util.check_image(alpha, ref[2], cal=cal[2], what=f"{what} alpha")
+    scale = max(float(np.abs(ref[1]).max()), 1e-30)
+    util.check_image(depth / scale, ref[1] / scale, cal=cal[1] / scale, what=f"{what} depth / max")
+
+
+def _check_grads(grads, ref, cal, what, names=NAMES + ("c2w",)):
+    for k in names:
+        util.check_grad(grads[k].double().cpu().numpy(), ref[3][k], f"{what} {k}", cal=cal[3][k])
+
+
+# ---- 1, 2: maps and gradients against float64 ------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", util.RENDER_CASES + [STACKED])
+def test_maps_and_gradients_of_render_gaussians_vs_oracle(gs, name):
+    ref, cal = _reference(name, F64), _reference(name, F32)
+    out, grads = _render(gs, name)
+    _check_maps(out, ref, cal, name)
+    _check_grads(grads, ref, cal, name)
+
+
+def test_stacked_scene_runs_the_capped_multi_chunk_path(gs):
+    """What the scene is for: one list, more than 4 x 64 entries, and more Gaussians on the central sub-tiles than a queue holds."""
+    d = _scene(STACKED)
+    assert (d["H"], d["W"]) == (8, 16)
+    _render(gs, STACKED)
+    assert gs.ops.binned_pairs() > 4 * 64                    # 5 chunks
+    # every projected centre lies on the 4 central sub-tiles (|u - 8| <= 2, |v - 4| <= 1): 300 entries for 4 queues of 24 per chunk
+    u, v = 20.0 * d["pos"][:, 0] / d["pos"][:, 2] + 8, 20.0 * d["pos"][:, 1] / d["pos"][:, 2] + 4
+    assert bool(((u >= 4) & (u < 12) & (v >= 2) & (v < 6)).all())
+
+
+@pytest.mark.parametrize("name", ["g1_generic", "g2_ragged"])
+def test_maps_and_gradients_of_unfused_render_vs_oracle(gs, name):
+    d = _scene(name)
+
+    def inputs(dtype, device):
+        q = {k: torch.tensor(d[k], dtype=F64) for k in NAMES}
+        c64 = torch.tensor(d["c2w"], dtype=F64)
+        vals = dict(pos=q["pos"], color=tp.sh_colour(q["f_dc"], q["f_rest"], q["pos"], c64), opacity_raw=q["opacity_raw"],
+                    sigma=tp.covariance_from_params(q["scale_raw"], q["q_raw"]))
+        p = {k: v.to(F32).to(dtype).to(device).contiguous().requires_grad_(True) for k, v in vals.items()}      # the same fp32 values for all
+        return p, torch.tensor(d["c2w"], dtype=dtype, device=device, requires_grad=True)
+
+    def oracle(dtype):
+        p, c = inputs(dtype, "cpu")
+        out = aux_oracle.render_aux_unfused(p["pos"], p["color"], p["opacity_raw"], p["sigma"], c, *util.cam_args(d), **d["kwargs"])
+        _loss(out, d, dtype, "cpu", "all").backward()
+        g = {k: v.grad.double().numpy() for k, v in p.items()}
+        g["c2w"] = c.grad.double().numpy()
+        return tuple(t.detach().double().numpy() for t in out) + (g,)
+
+    ref, cal = oracle(F64), oracle(F32)
+    p, c = inputs(F32, DEV)
+    out = gs.render(p["pos"], p["color"], p["opacity_raw"], p["sigma"], c, *util.cam_args(d), **d["kwargs"], aux=True)
+    _loss(out, d, F32, DEV, "all").backward()
+    torch.cuda.synchronize()
+    grads = {k: v.grad for k, v in p.items()}
+    grads["c2w"] = c.grad
+    _check_maps(out, ref, cal, f"render {name}")
+    _check_grads(grads, ref, cal, f"render {name}", names=UNFUSED + ("c2w",))
+
+
+# ---- 3: the aux image is the plain image -----------------------------------------------------------------------------------------
+
+def test_aux_image_is_the_plain_image(gs):
+    worst = 0.0
+    for name in util.RENDER_CASES + [STACKED]:
+        d = _scene(name)
+        p = [torch.tensor(d[k], device=DEV) for k in NAMES]
+        c = torch.tensor(d["c2w"], device=DEV)
+        with torch.no_grad():
+            plain = gs.render_gaussians(*p, c, *util.cam_args(d), **d["kwargs"])
+            img, _, _ = gs.render_gaussians(*p, c, *util.cam_args(d), **d["kwargs"], aux=True)
+        delta = float((img - plain).abs().max())
+        print(f"{name}: max |aux image - plain image| = {delta:.3e}")
+        worst = max(worst, delta)
+        assert delta <= util.IMG_TOL_BULK, name
+    print(f"all scenes: max |aux image - plain image| = {worst:.3e}")
+
+
+# ---- 4, 5: losses that read one output -----------------------------------------------------------------------------------------
+
+def test_depth_only_loss(gs):
+    name = "g1_generic"
+    ref, cal = _reference(name, F64, which="depth"), _reference(name, F32, which="depth")
+    out, grads = _render(gs, name, which="depth")
+    assert float(grads["f_dc"].abs().max()) == 0.0 and float(grads["f_rest"].abs().max()) == 0.0
+    _check_grads(grads, ref, cal, "depth only", names=("pos", "c2w"))
+    g, s = grads["c2w"].double().cpu(), -grads["pos"].double().sum(0).cpu()          # the translation identity
+    assert float((g[:3, 3] - s).abs().max()) <= 1e-5 * float(grads["pos"].double().abs().sum()), (g[:3, 3], s)
+    assert bool((grads["c2w"][3] == 0).all())
+
+
+def test_alpha_only_and_image_only_losses(gs):
+    name = "g2_ragged"
+    ref, cal = _reference(name, F64, which="alpha"), _reference(name, F32, which="alpha")
+    _, grads = _render(gs, name, which="alpha")
+    assert float(grads["f_dc"].abs().max()) == 0.0 and float(grads["f_rest"].abs().max()) == 0.0
+    _check_grads(grads, ref, cal, "alpha only", names=("pos", "opacity_raw", "scale_raw", "q_raw", "c2w"))
+    # image only: the aux call and the plain call against the same float64 reference
+    ref, cal = _reference(name, F64, which="image"), _reference(name, F32, which="image")
+    _, g_aux = _render(gs, name, which="image")
+    _, g_plain = _render(gs, name, aux=False)
+    _check_grads(g_aux, ref, cal, "image only (aux)")
+    _check_grads(g_plain, ref, cal, "image only (plain)")
+
+
+# ---- 6: background -------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", ["g1_generic", "g3_occlusion"])
+def test_background(gs, name):
+    ref, cal = _reference(name, F64, background=BG), _reference(name, F32, background=BG)
+    out, grads = _render(gs, name, background=BG)
+    _check_maps(out, ref, cal, f"{name} over a background")
+    _check_grads(grads, ref, cal, f"{name} over a background")
+    # without aux: ONE tensor, the aux call's image; its gradients are those of the image term
+    one, g_one = _render(gs, name, aux=False, background=torch.tensor(BG))
+    assert isinstance(one, torch.Tensor) and one.shape == out[0].shape
+    assert torch.equal(one.detach(), out[0].detach())
+    ref_i, cal_i = _reference(name, F64, background=BG, which="image"), _reference(name, F32, background=BG, which="image")
+    _check_grads(g_one, ref_i, cal_i, f"{name} background only")
+
+
+# ---- 7: deterministic mode ---------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", [STACKED, "g6_huge"])
+def test_deterministic_mode(gs, name):
+    ref, cal = _reference(name, F64), _reference(name, F32)
+    old = gs.set_deterministic(True)
+    try:
+        _, g1 = _render(gs, name)
+        _, g2 = _render(gs, name)
+    finally:
+        gs.set_deterministic(old)
+    for k in g1:
+        assert torch.equal(g1[k], g2[k]), k
+    _check_grads(g1, ref, cal, f"{name} deterministic")
+
+
+# ---- 8: deferred checks, no_grad ---------------------------------------------------------------------------------------------------
+
+def test_deferred_frame_gives_the_waited_frame(gs):
+    name = "g3_occlusion"
+    ref, cal = _reference(name, F64), _reference(name, F32)
+    out_w, g_w = _render(gs, name)                                   # (also sizes the kept capacity)
+    before = dict(gs.ops.forward_modes), dict(gs.ops.composite_calls)
+    with gs.deferred_checks() as chk:
+        out_d, g_d = _render(gs, name)
+    chk.verify()
+    assert gs.ops.forward_modes["deferred"] == before[0]["deferred"] + 1          # not waited for ...
+    assert gs.ops.composite_calls == before[1]                                   # ... and through the separate calls
+    _check_maps(out_d, ref, cal, "deferred")
+    _check_maps(out_w, ref, cal, "waited")
+    print("max |deferred - waited|:", [float((a.detach() - b.detach()).abs().max()) for a, b in zip(out_d, out_w)])
+    _check_grads(g_d, ref, cal, "deferred")
+    _check_grads(g_w, ref, cal, "waited")
+
+
+def test_no_grad_saves_nothing(gs):
+    name = "g1_generic"
+    d = _scene(name)
+    kept = {}
+    out, _ = _render(gs, name, fn=lambda o: kept.update(frame=o[0].grad_fn.frame))
+    assert kept["frame"].accum is not None and kept["frame"].accum_aux is not None
+    p = [torch.tensor(d[k], device=DEV, requires_grad=True) for k in NAMES]
+    with torch.no_grad():
+        quiet = gs.render_gaussians(*p, torch.tensor(d["c2w"], device=DEV, requires_grad=True), *util.cam_args(d), **d["kwargs"], aux=True)
+    assert all(t.grad_fn is None and not t.requires_grad for t in quiet)
+    for a, b in zip(quiet, out):
+        assert torch.equal(a, b.detach())
+    # the frame of a render without gradients keeps neither accum nor accum_aux
+    seen = {}
+    impl = gs.ops._forward_impl
+
+    def spy(*args):
+        res = impl(*args)
+        seen["frame"] = res[1]
+        return res
+    gs.ops._forward_impl = spy
+    try:
+        with torch.no_grad():
+            gs.render_gaussians(*p, torch.tensor(d["c2w"], device=DEV), *util.cam_args(d), **d["kwargs"], aux=True)
+    finally:
+        gs.ops._forward_impl = impl
+    assert seen["frame"].aux and seen["frame"].accum is None and seen["frame"].accum_aux is None and seen["frame"].grad2d is None
+
+
+# ---- 9: empty scenes, the off-screen exception, gradient routes ---------------------------------------------------------------
+
+@pytest.mark.parametrize("name", util.EMPTY_CASES)
+def test_empty_scenes(gs, name):
+    out, grads = _render(gs, name)
+    assert all(float(t.detach().abs().max()) == 0.0 for t in out)
+    assert out[1].shape == out[2].shape == out[0].shape[:2]
+    assert all(g is not None and float(g.abs().max()) == 0.0 for g in grads.values())
+    out, grads = _render(gs, name, background=(2.0, 0.5, -1.0))
+    want = torch.tensor([1.0, 0.5, 0.0], device=DEV).expand_as(out[0])
+    assert torch.equal(out[0].detach(), want)
+    assert float(out[1].detach().abs().max()) == 0.0 and float(out[2].detach().abs().max()) == 0.0
+    assert all(g is not None and float(g.abs().max()) == 0.0 for g in grads.values())
+
+
+def test_offscreen_aux_frame_still_raises(gs):
+    d = util.load("g10_offscreen")
+    p = [torch.tensor(d[k], device=DEV) for k in NAMES]
+    with pytest.raises(Exception, match=str(d["raises"])):
+        gs.render_gaussians(*p, torch.tensor(d["c2w"], device=DEV), *util.cam_args(d), **d["kwargs"], aux=True)
+
+
+def test_aux_frame_inside_a_gradient_route_raises(gs):
+    d = _scene("g1_generic")
+    p = util.tensors(d, F32, device=DEV, grad=True)
+    c = torch.tensor(d["c2w"], device=DEV)
+    with gs.ops.accumulate_grads(p):
+        for kw in (dict(aux=True), dict(background=BG)):
+            with pytest.raises(RuntimeError, match="gradient_route"):
+                gs.render_gaussians(*[p[k] for k in NAMES], c, *util.cam_args(d), **d["kwargs"], **kw)
+        gs.render_gaussians(*[p[k] for k in NAMES], c, *util.cam_args(d), **d["kwargs"])          # the plain frame is routed as before
+
+
+# ---- 10: guard margins through the raw ABI ---------------------------------------------------------------------------------------
+
+GUARD = 256        # bytes of sentinel on either side
+SENTINEL = 0x5A
+
+
+class _Guarded:
+    """A device buffer of `nbytes` with GUARD bytes of sentinel on either side (the payload 256-byte aligned)."""
+
+    def __init__(self, nbytes, fill=0):
+        self.nbytes = int(nbytes)
+        self.raw = torch.full((self.nbytes + 2 * GUARD + 256,), SENTINEL, dtype=torch.uint8, device=DEV)
+        self.off = GUARD + (-(self.raw.data_ptr() + GUARD)) % 256
+        self.raw[self.off:self.off + self.nbytes] = fill
+        self.ptr = C.c_void_p(self.raw.data_ptr() + self.off)
+
+    def floats(self):
+        return self.raw[self.off:self.off + self.nbytes].view(torch.float32)
+
+    def intact(self):
+        r = self.raw
+        return bool((r[:self.off] == SENTINEL).all()) and bool((r[self.off + self.nbytes:] == SENTINEL).all())
+
+
+def test_depth_alpha_and_deterministic_scratch_stay_inside_their_buffers():
+    d = dict(_scene("g1_generic"))
+    H, W = 50, 70
+    d.update(H=H, W=W, cx=W / 2, cy=H / 2)
+    fr = device_frame.Frame(d)
+    lib, vp = fr.lib, device_frame._vp
+    counts = fr.project(device_frame.F)
+    assert counts.n_binned > 0
+    fr.bin(counts.n_binned)
+    image, accum = torch.empty(H, W, 3, device=DEV), torch.empty(H, W, 3, device=DEV)
+    depth, alpha, accum_aux = _Guarded(H * W * 4, 0xFF), _Guarded(H * W * 4, 0xFF), _Guarded(H * W * 8, 0xFF)
+    bg = (C.c_float * 3)(*BG)
+    abi.check(lib.gsplat_rasterize_forward_aux(fr.n, fr.capacity, C.byref(fr.view), vp(fr.state), vp(fr.bin_state), vp(image), depth.ptr,
+                                               alpha.ptr, vp(accum), accum_aux.ptr, None, bg, fr.st), "gsplat_rasterize_forward_aux")
+    torch.cuda.synchronize()
+    assert depth.intact() and alpha.intact() and accum_aux.intact() and fr.canaries_intact()
+    dm, am = depth.floats().view(H, W), alpha.floats().view(H, W)
+    assert bool(torch.isfinite(dm).all()) and bool(torch.isfinite(am).all())              # every pixel written (the fill is a NaN pattern)
+    assert torch.equal(accum_aux.floats().view(H, W, 2)[..., 0], dm) and torch.equal(accum_aux.floats().view(H, W, 2)[..., 1], am)
+    ref, cal = (aux_oracle.render_aux(*[torch.tensor(d[k], dtype=t) for k in NAMES], torch.tensor(d["c2w"], dtype=t), H, W, d["fx"], d["fy"],
+                                      d["cx"], d["cy"], background=BG, **d["kwargs"]) for t in (F64, F32))
+    util.check_image(image.cpu().numpy(), ref[0].numpy(), cal=cal[0].numpy(), what="raw ABI image")
+    util.check_image(am.cpu().numpy(), ref[2].numpy(), cal=cal[2].numpy(), what="raw ABI alpha")
+    # the deterministic backward: rows of 10 floats per pair in a scratch of exactly the size the library asks for
+    nbytes = lib.gsplat_rasterize_backward_aux_scratch_bytes(fr.n, fr.capacity)
+    assert nbytes >= fr.capacity * 40
+    scratch = _Guarded(nbytes, 0xFF)
+    grad2d = _Guarded(fr.n * 64, 0xFF)
+    gd, ga = torch.rand(H, W, device=DEV), torch.rand(H, W, device=DEV)
+    assert lib.gsplat_rasterize_backward_aux(fr.n, fr.capacity, C.byref(fr.view), vp(fr.state), vp(fr.bin_state), vp(accum), accum_aux.ptr, None,
+                                             vp(gd), vp(ga), bg, grad2d.ptr, 0, scratch.ptr, nbytes - 256, fr.st) == abi.GSPLAT_ERR_WORKSPACE
+    abi.check(lib.gsplat_rasterize_backward_aux(fr.n, fr.capacity, C.byref(fr.view), vp(fr.state), vp(fr.bin_state), vp(accum), accum_aux.ptr, None,
+                                                vp(gd), vp(ga), bg, grad2d.ptr, 0, scratch.ptr, nbytes, fr.st), "gsplat_rasterize_backward_aux")
+    torch.cuda.synchronize()
+    assert scratch.intact() and grad2d.intact() and fr.canaries_intact()
+    rows = grad2d.floats().view(fr.n, 16)[:, :10]
+    assert bool(torch.isfinite(rows).all()) and float(rows[:, 9].abs().max()) > 0.0          # column 9: dL/dz
+    assert float(rows[:, 6:9].abs().max()) == 0.0                                           # no image gradient: no colour sums
