@@ -12,6 +12,7 @@
 //       (K6, K7 <AUX>: depth and opacity maps beside the colour, a background under it -- not in the reference)
 //       (+ tile_block_sum / pair_base / pair_reduce_kernel: deterministic mode)
 //   K8  project_backward_kernel chain rule to the reference's input tensors                     [B2, B3]
+//   K9  densify_stats_kernel / densify_stats_merge_kernel   screen-space densification statistics behind K7 (not in the reference)
 //
 // Everything is hand-written HIP for gfx950; no library kernels.  No MFMA: there is no dense contraction on this path.
 // No CPU fallback: without a GPU every entry point returns GSPLAT_ERR_HIP.
@@ -28,6 +29,7 @@
 #include "gs_sort.h"
 #include "gs_raster.h"
 #include "gs_project_backward.h"
+#include "gs_densify.h"
 #include "gs_ops.h"
 
 thread_local char gsplat_err_buf[512] = "";      // shared with gsplat_loss.hip; read through gsplat_last_error()
@@ -215,6 +217,21 @@ int raster_backward_impl(int64_t n, int64_t n_binned, const gsplat_view* v, cons
     if (det) {
         LAUNCH("pair_reduce_kernel", aux ? pair_reduce_kernel<10> : pair_reduce_kernel<9>, dim3(blocks256(n)), dim3(256), 0, st, n, ps.tiles, ds.pair_base, ds.part, (uint32_t)n_binned, grad2d);
     }
+    return GSPLAT_OK;
+}
+
+// gsplat_densify_stats / gsplat_frame_densify_stats behind their argument checks (every message names the entry)
+int densify_stats_impl(const char* name, int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, const float* grad2d,
+                       float* stats, void* stream_) {
+    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
+    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
+    if (n < 0 || n > (int64_t)ID_MASK + 1 || pair_capacity < 0) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
+    if (!project_state || !grad2d || !stats) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
+    if (!aligned16(stats) || !aligned16(grad2d)) return fail(GSPLAT_ERR_BAD_ARG, "%s: stats / grad2d must be 16-byte aligned", name);
+    if (n == 0) return GSPLAT_OK;
+    const Ctx c = open_ctx(n, v, project_state, stream_);
+    LAUNCH("densify_stats_kernel", densify_stats_kernel, dim3(blocks256(n)), dim3(256), 0, c.st, n, c.ps.counts, (long long)pair_capacity, c.ps.tiles,
+           c.ps.rec, grad2d, 0.5f * (float)v->W, 0.5f * (float)v->H, reinterpret_cast<f4*>(stats));
     return GSPLAT_OK;
 }
 
@@ -597,6 +614,38 @@ int gsplat_sh_accumulate(int64_t n, int32_t n_views, const float* pos, const flo
     if (!aligned16(pos) || !aligned16(grad_f_dc) || !aligned16(grad_f_rest)) return fail(GSPLAT_ERR_BAD_ARG, "arrays must be 16-byte aligned");
     LAUNCH("sh_accumulate_kernel", sh_accumulate_kernel, dim3(blocks64(n)), dim3(64), 0, (hipStream_t)stream_, n, (int)n_views, pos, eyes, grad_logit,
            scale, grad_f_dc, grad_f_rest);
+    return GSPLAT_OK;
+}
+
+// ---- screen-space densification statistics (include/gsplat_mi355x.h; the kernels: gs_densify.h) ------------------------------
+int gsplat_densify_stats(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, const float* grad2d,
+                         float* stats, void* stream_) {
+    return densify_stats_impl("gsplat_densify_stats", n, pair_capacity, v, project_state, grad2d, stats, stream_);
+}
+
+int gsplat_frame_densify_stats(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame, int64_t frame_bytes,
+                               float* stats, void* stream_) {
+    const char* name = "gsplat_frame_densify_stats";
+    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
+    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
+    if (n < 0 || pair_capacity < 0) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
+    if (!frame || !stats) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
+    if (reinterpret_cast<uintptr_t>(frame) & 255u) return fail(GSPLAT_ERR_BAD_ARG, "%s: frame must be 256-byte aligned", name);
+    const FrameParts f = frame_parts(n, pair_capacity, v, GSPLAT_FRAME_BACKWARD);
+    if (f.total > frame_bytes) return fail(GSPLAT_ERR_BAD_ARG, "%s: frame arena too small: was it made with GSPLAT_FRAME_BACKWARD?", name);
+    const char* base = (const char*)frame;
+    return densify_stats_impl(name, n, pair_capacity, v, base + f.project_state, (const float*)(base + f.grad2d), stats, stream_);
+}
+
+int gsplat_densify_stats_merge(int64_t n, float* pass, float* total, void* stream_) {
+    const char* name = "gsplat_densify_stats_merge";
+    if (n < 0) return fail(GSPLAT_ERR_BAD_ARG, "%s: n < 0", name);
+    if (!pass || !total) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
+    if (pass == total) return fail(GSPLAT_ERR_BAD_ARG, "%s: pass and total are the same record", name);
+    if (!aligned16(pass) || !aligned16(total)) return fail(GSPLAT_ERR_BAD_ARG, "%s: records must be 16-byte aligned", name);
+    if (n == 0) return GSPLAT_OK;
+    LAUNCH("densify_stats_merge_kernel", densify_stats_merge_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream_, n, reinterpret_cast<f4*>(pass),
+           reinterpret_cast<f4*>(total));
     return GSPLAT_OK;
 }
 

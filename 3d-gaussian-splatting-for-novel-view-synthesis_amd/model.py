@@ -3,6 +3,8 @@
     GaussianModel(initial_params, device)                     scripts/train.py:48-86
       .densify_and_prune(grads, opacity_threshold=0.01, max_grad=0.01, scale_threshold=0.01, max_screen_size=20)
                                                               scripts/train.py:89-141
+      .densify_and_prune_screen(stats, opacity_threshold=0.01, grad_threshold=0.0002, scale_threshold=0.01, max_screen_size=None)
+                                                              the paper's criterion on ops.DensifyStats (not in the reference)
       ._prune_points / ._split_points / ._clone_points        scripts/train.py:143-195
       .reset_opacity(threshold=0.01, bump=0.01)               scripts/train.py:564-569 (inline in the loop there)
       .save_checkpoint / .load_checkpoint                     scripts/train.py:197-219 (-> harness.py)
@@ -11,7 +13,7 @@ Semantics kept (checked against the reference's own methods, tests/golden/densif
   * prune first (`sigmoid(opacity_raw) < opacity_threshold`), gradients are re-indexed with the same mask;
   * split keeps the parent and appends ONE child per selected Gaussian: position + randn * exp(scale_raw) * 0.1, scale_raw - 0.5,
     everything else copied; clone appends an exact copy; children go to the end, in mask order; split children before clones;
-  * `max_screen_size` is accepted and unused, as in the reference;
+  * `max_screen_size` is accepted and unused by densify_and_prune, as in the reference (densify_and_prune_screen applies it);
   * the optimiser state is not carried over (the reference builds a fresh Adam after every densification, :554-561).
 
 One documented divergence: in the reference the clone mask is computed before the split and applied after it
@@ -54,16 +56,39 @@ class GaussianModel:
                     grads[key] = grads[key][~prune_mask]
         if grads is not None and grads.get('pos') is not None:
             grad_norm = grads['pos'].norm(dim=-1)
-            max_scale = torch.exp(self.scale_raw).max(dim=-1)[0]
-            hot = grad_norm > max_grad
-            split_mask = (max_scale > scale_threshold) & hot
-            clone_mask = (max_scale <= scale_threshold) & hot
-            n_before = self.pos.shape[0]
-            self._split_points(split_mask, generator=generator)
-            grown = self.pos.shape[0] - n_before
-            if grown:       # the clone mask belongs to the pre-split rows (see the module docstring)
-                clone_mask = torch.cat([clone_mask, clone_mask.new_zeros(grown)])
-            self._clone_points(clone_mask)
+            self._densify(grad_norm > max_grad, scale_threshold, generator)
+
+    def densify_and_prune_screen(self, stats, opacity_threshold=0.01, grad_threshold=0.0002, scale_threshold=0.01, max_screen_size=None,
+                                 generator=None):
+        """The paper's criterion, from the screen-space statistics of ops.DensifyStats (`stats`: one, or its [N, 4] tensor =
+        (grad_sum, count, extent_max, 0) on the parameters' device, a row per Gaussian): prune `sigmoid(opacity_raw) <
+        opacity_threshold` and -- with max_screen_size -- `extent_max > max_screen_size` (pixels); then, of the surviving rows,
+        `hot = grad_sum / max(count, 1) >= grad_threshold` (a Gaussian no view saw is never hot); split the hot ones whose largest
+        scale exceeds scale_threshold, clone the others: the same split / clone and the same order as densify_and_prune."""
+        data = getattr(stats, "data", stats)
+        if tuple(data.shape) != (self.pos.shape[0], 4):
+            raise ValueError(f"the statistics have shape {tuple(data.shape)}, the model has {self.pos.shape[0]} Gaussians")
+        data = data.detach().to(self.pos.device)
+        prune_mask = torch.sigmoid(self.opacity_raw) < opacity_threshold
+        if max_screen_size is not None:
+            prune_mask = prune_mask | (data[:, 2] > max_screen_size)
+        self._prune_points(prune_mask)
+        kept = data[~prune_mask]
+        hot = kept[:, 0] / kept[:, 1].clamp(min=1) >= grad_threshold
+        self._densify(hot, scale_threshold, generator)
+
+    def _densify(self, hot, scale_threshold, generator):
+        """Split the `hot` Gaussians whose largest scale exceeds scale_threshold, clone the other hot ones (children at the end:
+        split children first, then clones)."""
+        max_scale = torch.exp(self.scale_raw).max(dim=-1)[0]
+        split_mask = (max_scale > scale_threshold) & hot
+        clone_mask = (max_scale <= scale_threshold) & hot
+        n_before = self.pos.shape[0]
+        self._split_points(split_mask, generator=generator)
+        grown = self.pos.shape[0] - n_before
+        if grown:       # the clone mask belongs to the pre-split rows (see the module docstring)
+            clone_mask = torch.cat([clone_mask, clone_mask.new_zeros(grown)])
+        self._clone_points(clone_mask)
 
     def _replace(self, new):
         for k in PARAM_KEYS:

@@ -353,7 +353,7 @@ class _Frame:
     (project_state | bin_state | accum | grad2d, carved by the library); one that went through the separate calls keeps them
     as separate buffers."""
     __slots__ = ("view", "n", "n_pairs", "proj_state", "bin_state", "accum", "fused", "inputs", "c2w", "empty", "grad2d", "sh_jacobian",
-                 "arena", "gaussians", "dirty", "src_ptrs", "route", "pose", "aux", "background", "accum_aux")
+                 "arena", "gaussians", "dirty", "src_ptrs", "route", "pose", "aux", "background", "accum_aux", "stats")
 
 
 class _Pending:
@@ -379,7 +379,7 @@ def _new_frame(fused, view, n, pos32, opa32, c2w32, ins, c, d):
     fr.inputs = dict(pos=pos32, opacity_raw=opa32, **ins)
     fr.arena = fr.gaussians = fr.proj_state = fr.bin_state = fr.accum = fr.grad2d = fr.route = None
     fr.dirty = fr.pose = fr.aux = False
-    fr.background = fr.accum_aux = None
+    fr.background = fr.accum_aux = fr.stats = None
     # the caller's own SH tensors (before any dtype / layout conversion): what dp.FactoredExchange.owns() compares
     fr.src_ptrs = (c.data_ptr(), d.data_ptr()) if fused else None
     return fr
@@ -401,12 +401,14 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
     if auxf and _route.get() is not None:
         raise RuntimeError("depth / opacity maps and a background (aux=True, background=...) are not available inside a gradient_route() "
                            "block (factored exchange, folded f_rest step, accumulate_grads): render the frame outside it")
+    stats = _stats_record(pos)              # (checked before anything else: a wrong record is refused even where nothing is rendered)
     lib = _abi.lib()
     dev = pos.device
     n = pos.shape[0]
     pos32, opa32, c2w32, ins = _convert_inputs(fused, n, pos, opacity_raw, c2w, a, b, c, d)
     fr = _new_frame(fused, view, n, pos32, opa32, c2w32, ins, c, d)
     fr.pose = pose
+    fr.stats = stats if need_grad else None
     fr.aux, fr.background = auxf, view.background if auxf else None
     if n == 0:      # nothing survives by construction: the reference returns the zero image (render.py:109-112)
         fr.empty = True
@@ -741,6 +743,9 @@ def _backward_impl(fr, grad_image, need_params=True, grad_depth=None, grad_alpha
                 _abi.check(lib.gsplat_rasterize_backward(fr.n, fr.n_pairs, C.byref(fr.view), _p(fr.proj_state), _p(fr.bin_state),
                                                          _p(fr.accum), _p(gi), _p(grad2d), int(zeroed), _p(det),
                                                          det.numel() if det is not None else 0, st), "gsplat_rasterize_backward")
+        if fr.stats is not None:
+            _abi.check(lib.gsplat_densify_stats(fr.n, fr.n_pairs, C.byref(fr.view), _p(fr.proj_state), _p(grad2d), _p(fr.stats), st),
+                       "gsplat_densify_stats")
         if factored:
             # logit gradients first: the exchange may start on them while the projection backward runs
             glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=dev)
@@ -780,15 +785,111 @@ def _backward_impl(fr, grad_image, need_params=True, grad_depth=None, grad_alpha
             _backward_call(fr, gi, gg, flags | _abi.GSPLAT_BACKWARD_PHASE_RASTER, st, det, glogit)
         if factored:                           # logit gradients first: the exchange may start on them while the projection backward runs
             route.add(glogit, fr.c2w[:3, 3])
+        _frame_stats(fr, st)
         with _stage("project_backward"):
             _backward_call(fr, gi, gg, jac | _abi.GSPLAT_BACKWARD_PHASE_PROJECT, st)
     else:
         _backward_call(fr, gi, gg, flags, st, det)
+    if not (factored or staged):
+        _frame_stats(fr, st)                   # (the projection phase only reads grad2d)
     composite_calls["backward"] += 1
     return {} if summed else dst
 
 
 _BACKWARD_STAGES = frozenset(("raster_backward", "project_backward"))
+
+
+def _frame_stats(fr, st):
+    """The densification statistics of a frame on an arena, once its raster phase is queued (fr.stats: ops.densify_stats)."""
+    if fr.stats is not None:
+        _abi.check(_abi.lib().gsplat_frame_densify_stats(fr.n, fr.n_pairs, C.byref(fr.view), _p(fr.arena), fr.arena.numel(), _p(fr.stats), st),
+                   "gsplat_frame_densify_stats")
+
+
+class DensifyStats:
+    """Screen-space densification statistics of N Gaussians: `.data` [N, 4] float32 = (grad_sum, count, extent_max, 0).
+
+        stats = ops.DensifyStats(n, device)
+        with ops.densify_stats(stats):
+            loss(render_gaussians(...)).backward()          # every backward pass of a frame rendered here adds that frame
+        hot = stats.mean_grad() >= 0.0002
+
+    Per frame, every Gaussian binned into at least one list adds the norm of the gradient of its projected centre (NDC units: the
+    paper's 0.0002 carries over) to grad_sum and 1 to count, and raises extent_max to its screen half-extent (pixels, at most 250).
+    The accumulation is a plain read-modify-write: backward passes that add into one record must be ordered on one stream."""
+
+    def __init__(self, n, device):
+        self.data = torch.zeros((int(n), 4), dtype=torch.float32, device=device)
+
+    grad_sum = property(lambda self: self.data[:, 0])
+    count = property(lambda self: self.data[:, 1])
+    extent_max = property(lambda self: self.data[:, 2])
+
+    def mean_grad(self):
+        return self.grad_sum / self.count.clamp(min=1)
+
+    def reset(self, n=None):
+        """Zero the record; with another n, a fresh record of n rows (after a densification)."""
+        if n is None or int(n) == self.data.shape[0]:
+            self.data.zero_()
+        else:
+            self.data = torch.zeros((int(n), 4), dtype=torch.float32, device=self.data.device)
+        return self
+
+    def merge_(self, other):
+        """self (+)= other -- (sum, sum, max) -- on the current stream; `other` is zero afterwards (the merge kernel clears the
+        rows it consumed)."""
+        a, b = self.data, other.data
+        if not a.is_cuda:
+            raise RuntimeError(f"the record is on {a.device}: the merge kernel needs GPU tensors (there is no CPU fallback)")
+        if b.shape != a.shape or b.device != a.device or b.dtype != torch.float32 or not b.is_contiguous() or other is self:
+            raise ValueError(f"merge_: the other record must be another float32 {tuple(a.shape)} record on {a.device}")
+        with torch.cuda.device(a.device):
+            _abi.check(_abi.lib().gsplat_densify_stats_merge(a.shape[0], _p(b), _p(a), _stream_ptr(a.device)), "gsplat_densify_stats_merge")
+        return self
+
+    def all_reduce(self, group=None):
+        """Sum grad_sum and count, take the maximum of extent_max over the ranks of `group` (plain torch.distributed on contiguous
+        copies: CPU tensors over gloo work too).  Every rank ends with the same bits."""
+        import torch.distributed as dist
+        sums, ext = self.data[:, :2].contiguous(), self.data[:, 2].contiguous()
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(ext, op=dist.ReduceOp.MAX, group=group)
+        self.data[:, :2] = sums
+        self.data[:, 2] = ext
+        return self
+
+
+# The record the frames rendered inside a densify_stats() block add to.  A slot of its own (not a gradient route: it combines with
+# any route), read once, in the caller's thread, when a frame is rendered (fr.stats), like fr.route.
+_stats = contextvars.ContextVar("gsplat_densify_stats", default=None)
+
+
+@contextlib.contextmanager
+def densify_stats(rec):
+    """Every backward pass of a frame rendered inside the block adds that frame's statistics to `rec` (a DensifyStats, or its
+    float32 [N, 4] tensor), once, on the backward's stream, behind its raster phase -- whatever route the gradients take.  Empty and
+    all-culled frames, frames rendered under torch.no_grad() and frames that overflowed their pair capacity add nothing.  A record
+    that does not fit the frame (float32 [n, 4], contiguous, on the frame's device) raises ValueError when the frame is rendered."""
+    data = rec.data if isinstance(rec, DensifyStats) else rec
+    if not isinstance(data, torch.Tensor):
+        raise TypeError("densify_stats() takes a DensifyStats or its [N, 4] tensor")
+    token = _stats.set(data)
+    try:
+        yield rec
+    finally:
+        _stats.reset(token)
+
+
+def _stats_record(pos):
+    data = _stats.get()
+    if data is None:
+        return None
+    n = pos.shape[0]
+    if data.dtype != torch.float32 or tuple(data.shape) != (n, 4) or data.device != pos.device or not data.is_contiguous() or data.data_ptr() % 16:
+        raise ValueError(f"densify_stats: the record is {data.dtype} {tuple(data.shape)} on {data.device}; this frame needs a contiguous "
+                         f"float32 {(n, 4)} record on {pos.device}")
+    return data
 
 
 def sh_accumulate(pos, eyes, grad_logit, scale=1.0):

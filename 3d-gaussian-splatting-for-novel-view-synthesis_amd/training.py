@@ -12,6 +12,8 @@ Follows scripts/train.py:446-569 statement by statement, on the fused pieces of 
     clip_grad_norm_(pos, 1.0) + step (:536-538) GaussianAdam.clip_grad_norm_ / .step (device-side coefficient, no host sync)
     densify / prune every `densification_interval` (:544-561)   model.GaussianModel.densify_and_prune + a fresh optimiser
                                                with the CURRENT position learning rate, as there
+                                               (TrainConfig.densify_rule = "screen": densify_and_prune_screen on the screen-space
+                                               statistics of the views since the last densification -- not in the reference)
     opacity reset every `opacity_reset_interval` (:564-569)     GaussianModel.reset_opacity
 
 With data parallelism every rank holds the full model, renders its share of the batch's views and divides by the GLOBAL
@@ -61,6 +63,14 @@ class TrainConfig:
     # an iteration of SEVERAL views on one process: the projection backward adds each view's gradients to one buffer itself
     # (ops.accumulate_grads) instead of autograd's accumulation pass per view -- the same sums in the same order.
     sum_views_in_kernel: bool = True
+    # the densification criterion.  "reference": the reference's -- the world-space position gradient of the densification
+    # iteration itself against max_grad.  "screen" (not in the reference; the paper's adaptive density control): the
+    # gradient of the projected centre in NDC units, averaged over the views that saw the Gaussian since the last densification
+    # (ops.DensifyStats), against densify_grad_threshold; Gaussians whose screen half-extent exceeded max_screen_size pixels are
+    # pruned once iteration > opacity_reset_interval.
+    densify_rule: str = "reference"
+    densify_grad_threshold: float = 0.0002
+    max_screen_size: float = 20.0
 
 
 _side_streams = {}           # per device: the two streams the views of an iteration alternate between (TrainConfig.view_streams)
@@ -74,8 +84,15 @@ class Trainer:
         self.model = model
         self.cfg = config or TrainConfig()
         self.group = group
+        if self.cfg.densify_rule not in ("reference", "screen"):
+            raise ValueError(f"densify_rule must be 'reference' or 'screen', not {self.cfg.densify_rule!r}")
         self.optimizer = self._new_optimizer(self.cfg.position_lr_init)
         self._gen = None
+        # densify_rule = "screen": the statistics since the last densification (None until the first such step; not stored in
+        # checkpoints: a resumed run starts its window at zero), and one pass record per view of an iteration
+        self.densify_stats = None
+        self._pass_stats = []
+        self._pass_dirty = False
 
     def _new_optimizer(self, pos_lr):
         c = self.cfg
@@ -94,6 +111,29 @@ class Trainer:
             if quiet is not None:
                 quiet(False)
         return got
+
+    def _prepare_stats(self, dev, n_views):
+        """The pass records of this iteration's views: one per VIEW, merged into self.densify_stats in view order once the pass is
+        agreed good -- so no two streams ever read-modify-write the same rows, a repeated pass counts nothing twice, and the sums
+        are the same bits whatever streams the views ran on."""
+        n = self.model.get_num_gaussians()
+        if self.densify_stats is None or self.densify_stats.data.shape[0] != n:
+            self.densify_stats = ops.DensifyStats(n, dev)
+        if self._pass_stats and self._pass_stats[0].data.shape[0] != n:
+            self._pass_stats, self._pass_dirty = [], False
+        if self._pass_dirty:                      # an exception left the last pass half way
+            self._clear_pass_stats(dev)
+        while len(self._pass_stats) < n_views:
+            self._pass_stats.append(ops.DensifyStats(n, dev))
+        return self._pass_stats[:n_views]
+
+    def _clear_pass_stats(self, dev):
+        main = torch.cuda.current_stream(dev)
+        for st in _side_streams.get((dev.type, dev.index), ()):
+            main.wait_stream(st)
+        for rec in self._pass_stats:
+            rec.data.zero_()
+        self._pass_dirty = False
 
     def _world(self):
         if dist.is_available() and dist.is_initialized():
@@ -123,6 +163,8 @@ class Trainer:
         pos_lr = optim.position_lr(iteration, c.position_lr_init, c.position_lr_final, c.position_lr_delay_mult,
                                    c.position_lr_max_steps)
         self.optimizer.param_groups[0]['lr'] = pos_lr
+        screen = c.densify_rule == "screen" and iteration < c.densify_until_iter
+        pass_stats = self._prepare_stats(dev, len(views)) if screen else None
         for attempt in range(4):
             self.optimizer.zero_grad()
             acc = torch.zeros(3, dtype=torch.float32, device=dev)
@@ -146,12 +188,14 @@ class Trainer:
                     for st in side:
                         st.wait_stream(main)                                           # parameters, zeroed gradients
                     per_view = []
+                    self._pass_dirty = screen
                     for k, v in enumerate(views):
                         with (torch.cuda.stream(side[k % len(side)]) if side else contextlib.nullcontext()):
                             image_gt = torch.as_tensor(v['image']).to(dev)
                             c2w = torch.as_tensor(v['c2w'], dtype=torch.float32).to(dev)
-                            rendered = ops.render_gaussians(m.pos, m.f_dc, m.f_rest, m.opacity_raw, m.scale_raw, m.q_raw, c2w,
-                                                            int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']))
+                            with (ops.densify_stats(pass_stats[k]) if screen else contextlib.nullcontext()):
+                                rendered = ops.render_gaussians(m.pos, m.f_dc, m.f_rest, m.opacity_raw, m.scale_raw, m.q_raw, c2w,
+                                                                int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']))
                             loss, vals = losses.compute_loss_device(rendered, image_gt, c.lambda_l1, c.lambda_ssim, scale=1.0 / n_global)
                             loss.backward()                            # (loss / batch size: the division is inside the loss kernels)
                             per_view.append(vals)
@@ -190,6 +234,15 @@ class Trainer:
                 if exchange is not None:
                     exchange.pad_views(len(views))          # (a pass that stopped early: keep the sequence of collectives aligned)
                 status = dp.agree_status(status, self.group, device=dev)
+            if screen:
+                # the caller's stream has waited for the views' streams: the pass records join the window in view order (and are zero
+                # again); a pass that is repeated or fails counts nothing -- its valid views would otherwise count twice
+                if status == dp.STATUS_OK:
+                    for rec in pass_stats:
+                        self.densify_stats.merge_(rec)
+                    self._pass_dirty = False
+                else:
+                    self._clear_pass_stats(dev)
             if exchange is not None:
                 if status != dp.STATUS_OK:
                     exchange.abandon()
@@ -215,9 +268,18 @@ class Trainer:
         self.optimizer.step()
         densified = False
         if iteration < c.densify_until_iter and iteration % c.densification_interval == 0:
-            grads = {'pos': m.pos.grad, 'opacity_raw': m.opacity_raw.grad}
-            m.densify_and_prune(grads, opacity_threshold=c.prune_opacity_threshold, max_grad=c.max_grad,
-                                scale_threshold=c.scale_threshold, generator=self._densify_generator(iteration))
+            if screen:
+                if world > 1:                     # every rank decides from the statistics of all views: the replicas stay bit-identical
+                    self.densify_stats.all_reduce(self.group)
+                m.densify_and_prune_screen(self.densify_stats, opacity_threshold=c.prune_opacity_threshold,
+                                           grad_threshold=c.densify_grad_threshold, scale_threshold=c.scale_threshold,
+                                           max_screen_size=c.max_screen_size if iteration > c.opacity_reset_interval else None,
+                                           generator=self._densify_generator(iteration))
+                self.densify_stats.reset(m.get_num_gaussians())       # the next window, over the new set of Gaussians
+            else:
+                grads = {'pos': m.pos.grad, 'opacity_raw': m.opacity_raw.grad}
+                m.densify_and_prune(grads, opacity_threshold=c.prune_opacity_threshold, max_grad=c.max_grad,
+                                    scale_threshold=c.scale_threshold, generator=self._densify_generator(iteration))
             self.optimizer = self._new_optimizer(pos_lr)
             densified = True
         if iteration % c.opacity_reset_interval == 0:

@@ -320,6 +320,32 @@ int gsplat_sh_accumulate(int64_t n, int32_t n_views, const float* pos, const flo
 int gsplat_logit_grad(int64_t n, const gsplat_view* v, const void* project_state, const float* grad2d,
                       float* grad_logit, void* stream);
 
+/* ---- screen-space densification statistics (no counterpart in the reference) -----------------------------
+ * A record is [n,4] floats, 16-byte aligned, one row per Gaussian: (grad_sum, count, extent_max, 0).  Behind the raster backward of
+ * ONE frame, every Gaussian binned into at least one list of that frame ("visible") adds, with the frame's own record
+ * (u, v, A11, A12, A22, opacity o, ex, ey) and the moments (Mx, My) in columns 0-1 of grad2d,
+ *     g_u = o (A11 Mx + A12 My),  g_v = o (A12 Mx + A22 My)        (the gradient of the projected centre, pixels)
+ *     grad_sum += sqrt((g_u W/2)^2 + (g_v H/2)^2)                  (NDC units)
+ *     count    += 1
+ *     extent_max = max(extent_max, min(max(ex, ey), 250))          (half-extents of {q <= chi_square_clip}, pixels)
+ * Rows of Gaussians that are not visible are not touched.  A frame with nothing on screen, or one whose pairs outgrew
+ * pair_capacity (n_binned > pair_capacity in its device counters: its grad2d is garbage), adds nothing -- decided on the device,
+ * as in gsplat_backward_adam_rest.
+ *   gsplat_densify_stats        after gsplat_rasterize_backward[_aux] on the same project_state and grad2d.
+ *   gsplat_frame_densify_stats  the same on the arena of gsplat_forward_deferred built with GSPLAT_FRAME_BACKWARD, after the raster
+ *                               phase of gsplat_backward / gsplat_backward_adam_rest (before or after the projection phase).
+ *   gsplat_densify_stats_merge  total (+)= pass -- (sum, sum, max) -- for the rows with pass.count > 0, which are then written back
+ *                               as zeros: a pass record is zero again after a merge.  pass != total.
+ * ORDERING: the accumulation is a plain read-modify-write without atomics.  Calls that add into (or merge) the same record must
+ * be ordered on one stream, or by events between streams.
+ * GSPLAT_ERR_BAD_ARG (the text names the entry): a NULL pointer, n < 0, pair_capacity < 0, a record that is not 16-byte aligned,
+ * frame_bytes below gsplat_frame_bytes(n, pair_capacity, v, GSPLAT_FRAME_BACKWARD).  n == 0: GSPLAT_OK, nothing is launched.        */
+int gsplat_densify_stats(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state,
+                         const float* grad2d, float* stats, void* stream);
+int gsplat_frame_densify_stats(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame,
+                               int64_t frame_bytes, float* stats, void* stream);
+int gsplat_densify_stats_merge(int64_t n, float* pass, float* total, void* stream);
+
 /* ---- the two small exported functions as stand-alone ops --------------------------------------- */
 int gsplat_build_sigma(int64_t n, const float* scale_raw, const float* q_raw, float* sigma, void* stream);
 int gsplat_build_sigma_backward(int64_t n, const float* scale_raw, const float* q_raw, const float* grad_sigma,
