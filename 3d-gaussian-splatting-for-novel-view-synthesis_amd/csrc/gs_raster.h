@@ -770,7 +770,8 @@ __global__ __launch_bounds__(256) void pair_base_kernel(int64_t n, const uint32_
     }
 }
 
-// grad2d[i][0..NS-1] = sum of Gaussian i's rows, in the order of its lists (row-major in its rectangle): the same order every run.
+// grad2d[i][0..NS-1] = sum of Gaussian i's rows, in the order of its lists (row-major in its rectangle): the same order every run;
+// columns NS .. 15 = 0.
 // NS = floats per row: 9, or 10 behind the depth / opacity backward.
 template <int NS = 9>
 __global__ __launch_bounds__(256) void pair_reduce_kernel(int64_t n, const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ pair_base,
@@ -789,6 +790,8 @@ __global__ __launch_bounds__(256) void pair_reduce_kernel(int64_t n, const uint3
     float* o = grad2d + i * 16;
 #pragma unroll
     for (int v = 0; v < NS; ++v) o[v] = t[v];
+#pragma unroll
+    for (int v = NS; v < 16; ++v) o[v] = 0.f;        // the whole row: deterministic mode never clears grad2d (a dirty one kept its padding)
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
 """One frame driven through the C ABI with ctypes and buffers of the test's own (gsplat_project, wait for the counters, gsplat_bin,
 gsplat_rasterize_forward with `accum`), and the state copied back: what tests/test_gpu_lists.py and
-tests/test_gpu_project_backward.py look at.  The array offsets come from gsplat_project_state_layout / gsplat_bin_state_layout."""
+tests/test_gpu_project_backward.py look at.  forward() / backward() call the four raster entries on buffers with canaries
+(tests/test_gpu_raster.py).  The array offsets come from gsplat_project_state_layout / gsplat_bin_state_layout."""
 import ctypes as C
 import importlib
 
@@ -74,7 +75,72 @@ class Frame:
         torch.cuda.synchronize()
 
     def canaries_intact(self):
-        return bool((self.bin_state[self.blay.bytes:] == CANARY_BYTE).all()) and bool((self.scratch[self.scratch_bytes:] == CANARY_BYTE).all())
+        return (bool((self.bin_state[self.blay.bytes:] == CANARY_BYTE).all()) and bool((self.scratch[self.scratch_bytes:] == CANARY_BYTE).all())
+                and all(bool((t[nb:] == CANARY_BYTE).all()) for t, nb in getattr(self, "bufs", {}).values()))
+
+    # ---- the raster entries on buffers of their own, each followed inside its allocation by a canary -----------------------------
+    def _buf(self, name, nbytes, fill=0xFF):
+        """A device buffer of nbytes filled with `fill` (0xFF: NaNs as floats) + the canary; kept under `name` until replaced."""
+        if not hasattr(self, "bufs"):
+            self.bufs = {}
+        t = torch.full((int(nbytes) + CANARY,), fill, dtype=torch.uint8, device=DEV)
+        t[int(nbytes):] = CANARY_BYTE
+        self.bufs[name] = (t, int(nbytes))
+        return _vp(t)
+
+    def _floats(self, name, shape):
+        t, nb = self.bufs[name]
+        return t[:nb].view(torch.float32).view(shape).cpu().numpy()
+
+    def forward(self, accum=True, aux=False, bg=None, zero_grad2d=False):
+        """gsplat_rasterize_forward, or with aux gsplat_rasterize_forward_aux (depth, alpha, background bg).  accum: with the buffers
+        the backward pass needs (and the exact sub-tile masks saved per pair); zero_grad2d: hands the call a grad2d full of 0xFF bytes
+        to clear.  Returns the outputs as numpy arrays."""
+        H, W = self.s["H"], self.s["W"]
+        px = H * W * 4
+        image = self._buf("image", 3 * px)
+        acc = self._buf("accum", 3 * px) if accum else None
+        g2d = self._buf("grad2d", self.n * 64) if zero_grad2d else None
+        names = dict(image=(H, W, 3))
+        if accum:
+            names["accum"] = (H, W, 3)
+        if not aux:
+            abi.check(self.lib.gsplat_rasterize_forward(self.n, self.capacity, C.byref(self.view), _vp(self.state), _vp(self.bin_state), image, acc, g2d,
+                                                        self.st), "gsplat_rasterize_forward")
+        else:
+            depth, alpha = self._buf("depth", px), self._buf("alpha", px)
+            acc_aux = self._buf("accum_aux", 2 * px) if accum else None
+            names.update(depth=(H, W), alpha=(H, W))
+            if accum:
+                names["accum_aux"] = (H, W, 2)
+            bgp = None if bg is None else (C.c_float * 3)(*bg)
+            abi.check(self.lib.gsplat_rasterize_forward_aux(self.n, self.capacity, C.byref(self.view), _vp(self.state), _vp(self.bin_state), image, depth,
+                                                            alpha, acc, acc_aux, g2d, bgp, self.st), "gsplat_rasterize_forward_aux")
+        torch.cuda.synchronize()
+        self.fwd_aux = aux
+        return {k: self._floats(k, shape) for k, shape in names.items()}
+
+    def backward(self, g_img, g_depth=None, g_alpha=None, aux=False, det=False, bg=None, zeroed=False):
+        """gsplat_rasterize_backward[_aux] behind forward(accum=True, aux=aux).  det: with a det_scratch of exactly the size the library
+        asks for.  zeroed: grad2d is the one forward(zero_grad2d=True) cleared and grad2d_zeroed = 1; else a grad2d full of 0xFF bytes
+        and grad2d_zeroed = 0.  Returns grad2d [n,16]."""
+        assert self.fwd_aux == aux and "accum" in self.bufs
+        dev = {k: torch.tensor(np.ascontiguousarray(a, np.float32), device=DEV) for k, a in (("gi", g_img), ("gd", g_depth), ("ga", g_alpha)) if a is not None}
+        g2d = _vp(self.bufs["grad2d"][0]) if zeroed else self._buf("grad2d", self.n * 64)
+        nbytes = (self.lib.gsplat_rasterize_backward_aux_scratch_bytes if aux else self.lib.gsplat_rasterize_backward_scratch_bytes)(self.n, self.capacity)
+        scratch = self._buf("det_scratch", nbytes) if det else None
+        acc = _vp(self.bufs["accum"][0])
+        if not aux:
+            abi.check(self.lib.gsplat_rasterize_backward(self.n, self.capacity, C.byref(self.view), _vp(self.state), _vp(self.bin_state), acc, _vp(dev["gi"]),
+                                                         g2d, int(zeroed), scratch, nbytes if det else 0, self.st), "gsplat_rasterize_backward")
+        else:
+            bgp = None if bg is None else (C.c_float * 3)(*bg)
+            abi.check(self.lib.gsplat_rasterize_backward_aux(self.n, self.capacity, C.byref(self.view), _vp(self.state), _vp(self.bin_state), acc,
+                                                             _vp(self.bufs["accum_aux"][0]), _vp(dev["gi"]) if "gi" in dev else None,
+                                                             _vp(dev["gd"]) if "gd" in dev else None, _vp(dev["ga"]) if "ga" in dev else None, bgp, g2d,
+                                                             int(zeroed), scratch, nbytes if det else 0, self.st), "gsplat_rasterize_backward_aux")
+        torch.cuda.synchronize()
+        return self._floats("grad2d", (self.n, 16))
 
     def rasterize(self):
         H, W = self.s["H"], self.s["W"]

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from oracle import torch_port as tp
-from tests import aux_oracle, device_frame, util
+from tests import aux_oracle, device_frame, list_scenes, util
 
 pytestmark = pytest.mark.gpu
 abi = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd._abi")
@@ -35,14 +35,9 @@ def _scene(name):
         rng = np.random.default_rng(11)
         d["w_img"] = d["wrand"]
     else:
-        rng = np.random.default_rng(5)
-        n, H, W, f = 300, 8, 16, 20.0
-        z = rng.uniform(3, 6, n)
-        pos = np.stack([rng.uniform(-0.3, 0.3, n), rng.uniform(-0.15, 0.15, n), z], 1)
-        d = dict(pos=pos, scale_raw=np.log(rng.uniform(0.3, 0.7, (n, 3))), q_raw=rng.normal(0, 1, (n, 4)),
-                 opacity_raw=rng.uniform(-4.2, -3.4, n), f_dc=0.5 * rng.normal(0, 1, (n, 3)), f_rest=0.1 * rng.normal(0, 1, (n, 45)))
-        d = {k: v.astype(np.float32) for k, v in d.items()}
-        d.update(c2w=np.eye(4, dtype=np.float32), H=H, W=W, fx=f, fy=f, cx=W / 2, cy=H / 2, kwargs={})
+        s = list_scenes.stacked()
+        d = {k: s[k] for k in NAMES + ("c2w", "H", "W", "fx", "fy", "cx", "cy", "kwargs")}
+        H, W = d["H"], d["W"]
         rng = np.random.default_rng(11)
         d["w_img"] = rng.uniform(0, 1, (H, W, 3))
     d["w_depth"] = rng.uniform(0, 1, (d["H"], d["W"])) / 8

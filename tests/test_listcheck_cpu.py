@@ -2,81 +2,11 @@
 (records from the host build of the projection, lists in numpy from its rectangles / masks / row spans, masks from a float64
 restatement of the exact sub-tile test), the checker accepts it, and rejects each of eight ways of breaking it by naming the right
 list.  This is what shows that tests/test_gpu_lists.py can fail."""
-import ctypes as C
-import importlib
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from tests import list_scenes, listcheck, util
-
-abi = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd._abi")
-CSRC = os.path.join(os.path.dirname(abi.__file__), "csrc")
-
-
-@pytest.fixture(scope="module")
-def hm():
-    so = os.path.join(CSRC, "libgsmath_host.so")
-    srcs = [os.path.join(CSRC, f) for f in ("host_math_check.cpp", "gs_math.h", "gs_body.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, srcs[0]])
-    return C.CDLL(so)
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def cpu_state(hm, s):
-    """Everything the device leaves behind, built on the CPU for scene s."""
-    n = len(s["pos"])
-    view = abi.make_view(*list_scenes.cam_args(s), **s["kwargs"])
-    rec = np.zeros((n, 16), np.float32)
-    rect, brect = np.zeros((n, 2), np.uint32), np.zeros((n, 2), np.uint32)
-    depth = np.zeros(n, np.float32)
-    tiles, btiles, bmask = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-    vis = np.zeros(n, np.int32)
-    g = abi.Gaussians(n, _ptr(s["pos"]), _ptr(s["opacity_raw"]), None, None, _ptr(s["scale_raw"]), _ptr(s["q_raw"]), _ptr(s["f_dc"]),
-                      _ptr(s["f_rest"]))
-    hm.hm_project(C.byref(g), _ptr(s["c2w"]), C.byref(view), _ptr(rec), _ptr(rect), _ptr(depth), _ptr(tiles), _ptr(vis), _ptr(brect),
-                  _ptr(btiles), _ptr(bmask))
-    lists_x, lists_y = (s["W"] + 15) // 16, (s["H"] + 7) // 8
-    x0, y0, x1, y1 = listcheck.unpack_rect(brect)
-    w = x1 - x0 + 1
-    area = w * (y1 - y0 + 1)
-    pl, pi = [], []
-    for i in np.nonzero(btiles > 0)[0]:
-        if area[i] <= 32:
-            k = np.nonzero((int(bmask[i]) >> np.arange(32)) & 1)[0]
-            pl.append((y0[i] + k // w[i]) * lists_x + x0[i] + k % w[i])
-        else:
-            h = int(y1[i] - y0[i] + 1)
-            xa, xb = np.zeros(h, np.int32), np.zeros(h, np.int32)
-            hm.hm_row_spans(_ptr(np.ascontiguousarray(rec[i, :8])), C.c_uint32(int(brect[i, 0])), C.c_uint32(int(brect[i, 1])), C.byref(view),
-                            _ptr(xa), _ptr(xb))
-            pl.append(np.concatenate([(y0[i] + r) * lists_x + np.arange(xa[r], xb[r] + 1) for r in range(h)]).astype(np.int64))
-        pi.append(np.full(len(pl[-1]), i, np.int64))
-    pl, pi = np.concatenate(pl), np.concatenate(pi)
-    o = np.lexsort((pi, depth.view(np.uint32)[pi], pl))               # by list, then (depth bits, id)
-    pl, pi = pl[o], pi[o]
-    nl = lists_x * lists_y
-    ln = np.bincount(pl, minlength=nl)
-    end = np.cumsum(ln)
-    ranges = np.stack([end - ln, end], 1).astype(np.uint32)
-    order = np.argsort(-listcheck.work_bucket(ln), kind="stable").astype(np.uint32)
-    cb = np.zeros(8, np.uint32)
-    cb[:4] = [(ln >= m).sum() for m in listcheck.CLASS_MIN_LEN]
-    # pair masks: the exact test (min of q over the sub-tile's rectangle of pixel centres <= chi_pad; non-PD: all eight) in float64
-    r64 = rec.astype(np.float64)
-    chi = s["kwargs"].get("chi_square_clip", 6.25)
-    a, b, c = r64[pi, 2], r64[pi, 3], r64[pi, 4]
-    q = listcheck.min_q_subtiles(r64[pi, 0], r64[pi, 1], a, b, c, (pl % lists_x) * 16, (pl // lists_x) * 8)
-    pm = ((q <= chi * 1.001 + 1e-4) * (1 << np.arange(8))[None, :]).sum(1).astype(np.uint8)
-    pm[~((a > 0) & (c > 0) & (a * c - b * b > 0))] = 0xFF
-    return dict(n=n, rec=rec, rect=brect, depth=depth, tiles=btiles, mask=bmask, ranges=ranges, sorted_ids=pi.astype(np.uint32), order=order,
-                class_bounds=cb, pair_mask=pm, n_binned=len(pi), lists_x=lists_x, lists_y=lists_y, chi=chi, vis=vis)
+from tests.cpu_frame import cpu_state, hm  # noqa: F401  (hm is a fixture)
 
 
 def run_checker(st, s, o):
