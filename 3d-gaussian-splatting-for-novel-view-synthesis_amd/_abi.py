@@ -30,6 +30,27 @@ GSPLAT_BACKWARD_GRAD2D_DIRTY = 8
 GSPLAT_BACKWARD_ACCUMULATE = 16
 GSPLAT_BACKWARD_DEPTH = 64
 
+
+def sh_bands_dropped(degree):
+    """3 - degree for an SH degree that is one of the integers 0..3 (bool, float and anything else: ValueError)."""
+    if type(degree) is not int or not 0 <= degree <= 3:
+        raise ValueError(f"sh_degree must be one of the integers 0, 1, 2, 3, not {degree!r}")
+    return 3 - degree
+
+
+# the function-like macros of the header: the SH degree of a fused render in two flag bits, as "bands dropped" (0 = degree 3)
+def GSPLAT_PROJECT_SH_DEGREE(d):
+    return sh_bands_dropped(d) << 4
+
+
+def GSPLAT_FRAME_SH_DEGREE(d):
+    return sh_bands_dropped(d) << 4
+
+
+def GSPLAT_BACKWARD_SH_DEGREE(d):
+    return sh_bands_dropped(d) << 8
+
+
 _F = C.POINTER(C.c_float)
 
 
@@ -105,6 +126,7 @@ SIGNATURES = {
     "gsplat_forward_deferred": (_INT, [_PG, _VP, _PV, _VP, _I64, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, C.c_int32, _VP]),
     "gsplat_backward": (_INT, [_PG, _VP, _PV, _VP, _I64, _I64, _VP, _PGG, _VP, _VP, _I64, C.c_int32, _VP]),
     "gsplat_sh_accumulate": (_INT, [_I64, C.c_int32, _VP, _VP, _VP, C.c_float, _VP, _VP, _VP]),
+    "gsplat_sh_accumulate_degree": (_INT, [_I64, C.c_int32, _VP, _VP, _VP, C.c_float, _VP, _VP, C.c_int32, _VP]),
     "gsplat_build_sigma": (_INT, [_I64, _VP, _VP, _VP, _VP]),
     "gsplat_build_sigma_backward": (_INT, [_I64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "gsplat_evaluate_sh": (_INT, [_I64, _VP, _VP, _VP, _VP, _VP, _VP]),

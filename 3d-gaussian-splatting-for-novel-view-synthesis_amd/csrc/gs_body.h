@@ -59,6 +59,19 @@ struct ShCoefGlobal {
     GS_HD float operator()(int k, int ch) const { return k == 0 ? dc[ch] : rest[ch * 15 + (k - 1)]; }
 };
 
+// Host-side dispatch from a run-time SH degree (0..3, checked by the caller) to the compile-time count of active bases:
+// f(ShBases<NB>{}) is called with NB = 1, 4, 9 or 16, and every call must return the same type (a kernel pointer, a status).
+template <int N> struct ShBases { static constexpr int value = N; };
+template <class F>
+inline auto with_sh_bases(int degree, F f) {
+    switch (degree) {
+        case 0: return f(ShBases<1>{});
+        case 1: return f(ShBases<4>{});
+        case 2: return f(ShBases<9>{});
+        default: return f(ShBases<16>{});
+    }
+}
+
 GS_HD void load_cov6(const float* sigma9, float S[6]) {
     // symmetrised: the projected 2x2 is symmetrised by the reference (render.py:175), which equals projecting sym(Sigma)
     S[0] = sigma9[0]; S[1] = 0.5f * (sigma9[1] + sigma9[3]); S[2] = 0.5f * (sigma9[2] + sigma9[6]);
@@ -101,7 +114,8 @@ GS_HD Proj project_geometry(const GaussIn& in, bool fused, const Camera& cam, co
 // K1 core, part 2: colour of a visible Gaussian (SH when fused) and the record.
 // with_colour = false (fused inputs only): the SH colour is filled in later by colour_kernel; rgb = 0 here.
 // kj (nullable, fused inputs with colour): receives the 12 values sh_colour_jac leaves for the backward.
-template <class Coef>
+// NB: the active SH bases of the render's degree (gs_math.h sh_active_bases).
+template <int NB = 16, class Coef>
 GS_HD RecOut project_finish(const GaussIn& in, const Proj& o, bool fused, Coef coef, const Camera& cam, bool with_colour = true,
                             float* kj = nullptr) {
     RecOut r;
@@ -118,8 +132,8 @@ GS_HD RecOut project_finish(const GaussIn& in, const Proj& o, bool fused, Coef c
             if (with_colour) {
                 ShMid sm;
                 sh_basis(in.p, cam.eye, sm);
-                if (kj) sh_colour_jac(sm, coef, rgb, kj);
-                else sh_colour(sm, coef, rgb);
+                if (kj) sh_colour_jac<NB>(sm, coef, rgb, kj);
+                else sh_colour<NB>(sm, coef, rgb);
             }
         } else {
             rgb[0] = in.col[0]; rgb[1] = in.col[1]; rgb[2] = in.col[2];
@@ -155,7 +169,8 @@ GS_HD RecOut project_core(const GaussIn& in, bool fused, Coef coef, const Camera
 // kj (nullable): the 12 values the forward saved with sh_colour_jac; then `coef` is not read.
 // POSE: g_W receives this Gaussian's dL/dW (gs_math.h pose_grad_w; zeros for a Gaussian that is not visible).
 // DEPTH: g_z = dL/d(camera depth) of this Gaussian (column 9 of grad2d behind the depth / opacity raster backward).
-template <bool POSE = false, bool DEPTH = false, class Coef, class Emit>
+// NB: the active SH bases of the forward that this is the backward of; emit_sh receives exact zeros for k >= NB.
+template <bool POSE = false, bool DEPTH = false, int NB = 16, class Coef, class Emit>
 GS_HD GradOut project_backward_core(const GaussIn& in, bool fused, Coef coef, Emit emit_sh, const Camera& cam, const ViewK& vk,
                                     bool vis, const float r9[9], bool moments = false, const float* kj = nullptr,
                                     float* g_W = nullptr, float g_z = 0.f) {
@@ -189,11 +204,11 @@ GS_HD GradOut project_backward_core(const GaussIn& in, bool fused, Coef coef, Em
             sh_basis(in.p, cam.eye, sm);
             float gps[3];
             if (kj) {
-                sh_colour_backward_jac(sm, kj, g.col, emit_sh, gps);
+                sh_colour_backward_jac<NB>(sm, kj, g.col, emit_sh, gps);
             } else {
                 float rgb[3];
-                sh_colour(sm, coef, rgb);
-                sh_colour_backward(sm, coef, rgb, g.col, emit_sh, gps);
+                sh_colour<NB>(sm, coef, rgb);
+                sh_colour_backward<NB>(sm, coef, rgb, g.col, emit_sh, gps);
             }
             g.p[0] += gps[0]; g.p[1] += gps[1]; g.p[2] += gps[2];
         }

@@ -229,13 +229,21 @@ GS_HD void sh_basis(const float p[3], const float eye[3], ShMid& m) {
     Y[14] = GS_K3E * z * (xx - yy); Y[15] = GS_K3A * x * (xx - 3.f * yy);
 }
 
+// The SH degree L of a render (0..3) selects NB = (L + 1)^2 = 1, 4, 9 or 16 ACTIVE basis functions; the colour is
+// sigmoid(sum_{k < NB} f_k Y_k).  The rule sits in the loop bounds of the four functions below and nowhere else: they never call
+// coef(k, ch) for k >= NB (so whatever an inactive slot holds -- a NaN included -- reaches nothing), and they emit(k, ch, 0.f) for
+// k >= NB (so every gradient slot is written, the inactive ones with an exact zero).  NB is a compile-time constant: at NB = 16 the
+// code is what it was before there was a degree, instruction for instruction, and the shorter chains are unrolled like the full one.
+// The chain of fmaf below cut at NB gives the bits of the full chain over zeroed coefficients: fmaf(0, Y, acc) == acc.
+GS_HD constexpr int sh_active_bases(int degree) { return (degree + 1) * (degree + 1); }
+
 // coef(k, ch) returns the SH coefficient of basis k, channel ch.
-template <class Coef>
+template <int NB = 16, class Coef>
 GS_HD void sh_colour(const ShMid& m, Coef coef, float rgb[3]) {
     GS_NO_CONTRACT
     for (int ch = 0; ch < 3; ++ch) {
         float acc = 0.f;
-        for (int k = 0; k < 16; ++k) acc = fmaf(coef(k, ch), m.Y[k], acc);
+        for (int k = 0; k < NB; ++k) acc = fmaf(coef(k, ch), m.Y[k], acc);
         rgb[ch] = sigmoidf_(acc);
     }
 }
@@ -265,17 +273,18 @@ GS_HD void sh_dir_to_point(const ShMid& m, const float dd[3], float g_p[3]) {
 }
 
 // B3 (colour part).  g_rgb = dL/d colour.  Emits dL/dcoef through `emit(k, ch, value)`; returns dL/dp in g_p.
-template <class Coef, class Emit>
+template <int NB = 16, class Coef, class Emit>
 GS_HD void sh_colour_backward(const ShMid& m, Coef coef, const float rgb[3], const float g_rgb[3], Emit emit, float g_p[3]) {
     float dY[16];
     for (int k = 0; k < 16; ++k) dY[k] = 0.f;
     for (int ch = 0; ch < 3; ++ch) {
         const float dpre = g_rgb[ch] * rgb[ch] * (1.f - rgb[ch]);
-        for (int k = 0; k < 16; ++k) {
+        for (int k = 0; k < NB; ++k) {
             const float cf = coef(k, ch);       // read before emit(): callers may alias the gradient onto the coefficient
             emit(k, ch, dpre * m.Y[k]);
             dY[k] += dpre * cf;
         }
+        for (int k = NB; k < 16; ++k) emit(k, ch, 0.f);
     }
     float dd[3];
     sh_basis_grad(m, dY, dd);
@@ -284,12 +293,13 @@ GS_HD void sh_colour_backward(const ShMid& m, Coef coef, const float rgb[3], con
 
 // F3 together with what its backward needs, so that the backward does not have to read the 48 coefficients again (192 of
 // the 236 input bytes of a Gaussian):  KJ[ch] = d rgb_ch / d logit_ch,  KJ[3 + 3 ch + m] = d logit_ch / d p_m.
-template <class Coef>
+template <int NB = 16, class Coef>
 GS_HD void sh_colour_jac(const ShMid& m, Coef coef, float rgb[3], float KJ[12]) {
-    sh_colour(m, coef, rgb);                                 // (the same instructions as without the Jacobian: see sh_basis)
+    sh_colour<NB>(m, coef, rgb);                             // (the same instructions as without the Jacobian: see sh_basis)
     for (int ch = 0; ch < 3; ++ch) {
         float cf[16];
-        for (int k = 0; k < 16; ++k) cf[k] = coef(k, ch);
+        for (int k = 0; k < NB; ++k) cf[k] = coef(k, ch);
+        for (int k = NB; k < 16; ++k) cf[k] = 0.f;           // (KJ carries the active bands only: the backward needs NB for emit alone)
         KJ[ch] = rgb[ch] * (1.f - rgb[ch]);
         float dd[3];
         sh_basis_grad(m, cf, dd);
@@ -298,12 +308,13 @@ GS_HD void sh_colour_jac(const ShMid& m, Coef coef, float rgb[3], float KJ[12]) 
 }
 
 // B3 from the saved KJ: dL/dcoef(k, ch) = dpre_ch Y_k, dL/dp = sum_ch dpre_ch (d logit_ch / d p).
-template <class Emit>
+template <int NB = 16, class Emit>
 GS_HD void sh_colour_backward_jac(const ShMid& m, const float KJ[12], const float g_rgb[3], Emit emit, float g_p[3]) {
     g_p[0] = g_p[1] = g_p[2] = 0.f;
     for (int ch = 0; ch < 3; ++ch) {
         const float dpre = g_rgb[ch] * KJ[ch];
-        for (int k = 0; k < 16; ++k) emit(k, ch, dpre * m.Y[k]);
+        for (int k = 0; k < NB; ++k) emit(k, ch, dpre * m.Y[k]);
+        for (int k = NB; k < 16; ++k) emit(k, ch, 0.f);
         for (int mm = 0; mm < 3; ++mm) g_p[mm] += dpre * KJ[3 + 3 * ch + mm];
     }
 }

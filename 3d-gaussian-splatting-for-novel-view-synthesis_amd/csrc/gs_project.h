@@ -68,11 +68,15 @@ __device__ __forceinline__ void stage_geometry(ProjectLds<FUSED>& s, const gspla
 // TOTALS = false (GSPLAT_PROJECT_COUNTS_LATE): the waves only add to the sharded counters and leave; bin_count_kernel, queued
 // right behind, totals and clears them.  (With the totals in here every wave waits for ALL its stores and atomics and then for
 // a returning arrival atomic before it can retire: a quarter of a wave's life.)
+// NB (FUSED && COLOUR): the active SH bases of the render's degree, 1 / 4 / 9 / 16 (gs_math.h).  NB = 1 (degree 0) needs no f_rest:
+// nothing of it is staged and its 11 520 B of LDS are not reserved (with them goes the barrier that waited for the coefficients).
+// NB = 4, 9 stage whole rows like NB = 16: the global_load_lds image of a block of rows is contiguous, three runs of 3 or 8 floats
+// per row are not.
 // (Workgroups of 2 / 4 waves instead of one: 89 / 91 us against 90 -- the kernel is not held by the rate at which one-wave
 // workgroups can be dispatched.  As a STREAM -- 6 persistent waves per CU, two sets of LDS rows, block k + 1 requested before
 // block k is computed -- 158 us against 96: with 1.5 waves per SIMD the long dependent chains of the geometry math issue at a
 // fraction of the VALU rate; this kernel lives on wave-level parallelism.)
-template <bool FUSED, bool COLOUR, bool JAC = false, bool TOTALS = true>
+template <bool FUSED, bool COLOUR, bool JAC = false, bool TOTALS = true, int NB = 16>
 __global__ __launch_bounds__(64) void project_kernel(gsplat_gaussians g, const float* __restrict__ c2w, Camera* __restrict__ cam_out, ViewK vk,
                                                      Records out, CounterBlock* cb, DevCounts* counts, DevCounts* counts_mapped,
                                                      uint32_t* __restrict__ bin_total, int nb, float* __restrict__ kj_out,
@@ -81,9 +85,11 @@ __global__ __launch_bounds__(64) void project_kernel(gsplat_gaussians g, const f
     // of 3 / 4 floats coalesce well enough) and only the 180 bytes of f_rest go through LDS: 11 520 B per wave instead of
     // 15 104 -> 12 waves per CU instead of 10, and the geometry math starts while the coefficients are still arriving.
     constexpr bool DIRECT = FUSED && COLOUR;
+    constexpr bool REST = FUSED && COLOUR && NB > 1;         // does the colour read f_rest at all?
+    static_assert(NB == 16 || DIRECT, "the SH degree belongs to the kernels that evaluate the colour");
     __shared__ float s_geo[DIRECT ? 4 : sizeof(ProjectLds<FUSED>) / 4];
     ProjectLds<FUSED>& s = *reinterpret_cast<ProjectLds<FUSED>*>(s_geo);
-    __shared__ float s_rest[FUSED && COLOUR ? 64 * 45 : 4];
+    __shared__ float s_rest[REST ? 64 * 45 : 4];
     const int lane = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * 64, i = row0 + lane;
     GaussIn in;
@@ -104,7 +110,7 @@ __global__ __launch_bounds__(64) void project_kernel(gsplat_gaussians g, const f
     } else {
         stage_geometry<FUSED>(s, g, row0, lane);
     }
-    if (FUSED && COLOUR) stage_rows<45>(s_rest, g.f_rest, row0, g.n, lane);          // all inputs of the wave in flight at once
+    if (REST) stage_rows<45>(s_rest, g.f_rest, row0, g.n, lane);                     // all inputs of the wave in flight at once
     Camera cam;                                              // (derived while the inputs are in flight)
     {
         float m[16];
@@ -121,12 +127,12 @@ __global__ __launch_bounds__(64) void project_kernel(gsplat_gaussians g, const f
         if (!DIRECT) in = gauss_from_lds<FUSED>(s, lane);
         o = project_geometry(in, FUSED, cam, vk);
     }
-    if (DIRECT) __syncthreads();                             // the SH coefficients have arrived
+    if (REST) __syncthreads();                               // the SH coefficients have arrived
     RecOut r;
     r.vis = o.vis; r.tiles = 0; r.mask = 0u; r.ref_tiles = 0; r.rect = u2{0u, 0u}; r.ref_rect = u2{0u, 0u};
     float kj[12];
     if (FUSED) {
-        if (o.vis == VIS_OK) r = project_finish(in, o, true, ShCoefLds{dc, s_rest + lane * 45}, cam, COLOUR, JAC ? kj : nullptr);
+        if (o.vis == VIS_OK) r = project_finish<NB>(in, o, true, ShCoefLds{dc, s_rest + lane * 45}, cam, COLOUR, JAC ? kj : nullptr);
     } else if (o.vis == VIS_OK) {
         r = project_finish(in, o, false, ShCoefLds{nullptr, nullptr}, cam);
     }
@@ -213,17 +219,18 @@ __global__ __launch_bounds__(64) void project_kernel(gsplat_gaussians g, const f
 // ---- K1b: SH colour (fused inputs) -------------------------------------------------------------------
 // F3 for the Gaussians that were binned: 192 of the 236 input bytes per Gaussian are SH coefficients.  Writes r, g, b into
 // the record line the geometry pass left (z stays).
-template <bool JAC>
+// NB: as in project_kernel (NB = 1: f_rest is neither staged nor given LDS).
+template <bool JAC, int NB = 16>
 __global__ __launch_bounds__(64) void colour_kernel(gsplat_gaussians g, const Camera* __restrict__ camp, const uint32_t* __restrict__ tiles,
                                                     Rec64* __restrict__ rec, float* __restrict__ kj_out) {
-    __shared__ float s_pos[64 * 3], s_dc[64 * 3], s_rest[64 * 45];
+    __shared__ float s_pos[64 * 3], s_dc[64 * 3], s_rest[NB > 1 ? 64 * 45 : 4];
     const int lane = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * 64, i = row0 + lane;
     const bool need = i < g.n && tiles[i] != 0u;
     if (!__any(need)) return;                                // wave-uniform: skip 204 B / Gaussian when none is binned
     stage_rows<3>(s_pos, g.pos, row0, g.n, lane);
     stage_rows<3>(s_dc, g.f_dc, row0, g.n, lane);
-    stage_rows<45>(s_rest, g.f_rest, row0, g.n, lane);
+    if (NB > 1) stage_rows<45>(s_rest, g.f_rest, row0, g.n, lane);
     const Camera cam = *camp;
     __syncthreads();
     if (need) {
@@ -233,10 +240,10 @@ __global__ __launch_bounds__(64) void colour_kernel(gsplat_gaussians g, const Ca
         float rgb[3];
         if (JAC) {
             float kj[12];
-            sh_colour_jac(sm, ShCoefLds{s_dc + lane * 3, s_rest + lane * 45}, rgb, kj);
+            sh_colour_jac<NB>(sm, ShCoefLds{s_dc + lane * 3, s_rest + lane * 45}, rgb, kj);
             store_kj(kj_out, i, kj);
         } else {
-            sh_colour(sm, ShCoefLds{s_dc + lane * 3, s_rest + lane * 45}, rgb);
+            sh_colour<NB>(sm, ShCoefLds{s_dc + lane * 3, s_rest + lane * 45}, rgb);
         }
         float* r2 = reinterpret_cast<float*>(&rec[i].r2);
         r2[0] = rgb[0]; r2[1] = rgb[1]; r2[2] = rgb[2];

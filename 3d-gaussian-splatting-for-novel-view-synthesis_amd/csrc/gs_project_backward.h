@@ -25,7 +25,11 @@ namespace {
 // (pose only).
 // DEPTH (not with ADAM / ACC): column 9 of grad2d holds dL/dz of the Gaussian's camera depth (gsplat_rasterize_backward_aux); it joins
 // the camera-space z gradient, from where position and pose get it.
-template <bool FUSED, bool JAC = false, bool ADAM = false, bool ACC = false, bool POSE = false, bool DEPTH = false>
+// NB (fused inputs): the active SH bases of the forward that filled the frame (gs_math.h).  The inactive columns of the f_rest
+// gradient are exact zeros (NB = 4, 9: written into the LDS rows by the emitter, so the rows leave as before).  NB = 1 (degree 0): f_rest
+// is not read, its gradient is not formed and has no LDS -- the rows are stored as zeros (zero_rows), stepped with a zero gradient
+// (ADAM) or left alone (ACC).
+template <bool FUSED, bool JAC = false, bool ADAM = false, bool ACC = false, bool POSE = false, bool DEPTH = false, int NB = 16>
 __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g, const Camera* __restrict__ camp, ViewK vk,
                                                               const uint32_t* __restrict__ tiles, const float* __restrict__ grad2d,
                                                               gsplat_gaussian_grads out, bool factored, const float* __restrict__ kj_in,
@@ -37,11 +41,13 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
     // DIRECT (fused inputs, saved Jacobian): nothing is staged IN (the 44 bytes of geometry are loaded by the lanes), and of the
     // gradients only the 45 f_rest rows go OUT through LDS (the rows of 1 / 3 / 4 floats are stored by the lanes): 11 520 B per
     // wave instead of 15 104 -> 14 waves per CU instead of 10.
+    static_assert(NB == 16 || FUSED, "the SH degree belongs to fused inputs");
     constexpr bool DIRECT = FUSED && JAC;
+    constexpr bool REST = FUSED && NB > 1;                // are there f_rest gradients to form?
     __shared__ float s_geo[DIRECT ? 4 : sizeof(ProjectLds<FUSED>) / 4];
     ProjectLds<FUSED>& s = *reinterpret_cast<ProjectLds<FUSED>*>(s_geo);
     __shared__ float s_dc[FUSED && !DIRECT ? 64 * 3 : 4];
-    __shared__ float s_rest[FUSED ? 64 * 45 : 4];
+    __shared__ float s_rest[REST ? 64 * 45 : 4];
     const int lane = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * 64, i = row0 + lane;
     const Camera cam = *camp;
@@ -67,7 +73,7 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
         }
         if (FUSED && !JAC) {
             stage_rows<3>(s_dc, g.f_dc, row0, g.n, lane);
-            stage_rows<45>(s_rest, g.f_rest, row0, g.n, lane);
+            if (REST) stage_rows<45>(s_rest, g.f_rest, row0, g.n, lane);
         }
         if (JAC && vis) {
             const f4* src = reinterpret_cast<const f4*>(kj_in + i * 12);
@@ -89,15 +95,16 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
     float gw[9];                                          // (POSE) d L / d W of this lane's Gaussian
     if (vis) {
         if (!DIRECT) in = gauss_from_lds<FUSED>(s, lane);
-        go = project_backward_core<POSE, DEPTH>(in, FUSED, ShCoefLds{dc_rows, s_rest + lane * 45},
-                                   ShEmitLds{dc_rows, s_rest + lane * 45}, cam, vk, true, r9, true, JAC ? kj : nullptr,
+        go = project_backward_core<POSE, DEPTH, NB>(in, FUSED, ShCoefLds{dc_rows, s_rest + lane * 45},
+                                   ShEmitFor<NB>{dc_rows, s_rest + lane * 45}, cam, vk, true, r9, true, JAC ? kj : nullptr,
                                    POSE ? gw : nullptr, g_z);
     } else {
         go = GradOut{};
         if (FUSED) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) dc_rows[k] = 0.f;
-            for (int k = 0; k < 45; ++k) s_rest[lane * 45 + k] = 0.f;
+            if (REST)
+                for (int k = 0; k < 45; ++k) s_rest[lane * 45 + k] = 0.f;
         }
         if (POSE) {
 #pragma unroll
@@ -132,7 +139,7 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
 #pragma unroll
                 for (int k = 0; k < 3; ++k) out.f_dc[i * 3 + k] += gdc[k];
             }
-            if (any_vis) {
+            if (REST && any_vis) {                          // (degree 0 adds nothing to f_rest)
                 __syncthreads();
                 unstage_rows<45, true>(out.f_rest, s_rest, row0, g.n, lane);
             }
@@ -157,12 +164,14 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
             }
         }
         if (!factored) {
-            __syncthreads();
+            if (REST) __syncthreads();
             if (ADAM) {
                 const DevCounts* cnt = reinterpret_cast<const DevCounts*>(ar.counts);
-                if (cnt->n_visible > 0 && cnt->n_binned <= ar.capacity) adam_rows<45>(ar, s_rest, row0, g.n, lane);      // (uniform)
-            } else {
+                if (cnt->n_visible > 0 && cnt->n_binned <= ar.capacity) adam_rows<45, !REST>(ar, s_rest, row0, g.n, lane);      // (uniform)
+            } else if (REST) {
                 unstage_rows<45>(out.f_rest, s_rest, row0, g.n, lane);
+            } else {
+                zero_rows<45>(out.f_rest, row0, g.n, lane);
             }
         }
         return;
@@ -197,7 +206,8 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
             if (out.color) unstage_rows<3>(out.color, s_dc, row0, g.n, lane);
         } else {
             unstage_rows<3>(out.f_dc, s_dc, row0, g.n, lane);
-            unstage_rows<45>(out.f_rest, s_rest, row0, g.n, lane);
+            if (REST) unstage_rows<45>(out.f_rest, s_rest, row0, g.n, lane);
+            else zero_rows<45>(out.f_rest, row0, g.n, lane);
         }
     } else {
         unstage_rows<9>(out.sigma, s.a, row0, g.n, lane);
@@ -256,6 +266,8 @@ __global__ __launch_bounds__(256) void logit_grad_kernel(int64_t n, const uint32
 // ---- SH gradients from logit gradients (data-parallel exchange) ---------------------------------------
 // grad f_dc[i, ch] = scale * sum_v glogit[v, i, ch] * Y0,  grad f_rest[i, ch * 15 + k - 1] = scale * sum_v glogit[v, i, ch] * Y_k(d_v(i)),
 // d_v(i) = unit vector from camera v's position to Gaussian i (spherical_harmonics.py:132-133).
+// NB: the active SH bases of the views' renders; the columns of the inactive ones are written as zeros.
+template <int NB = 16>
 __global__ __launch_bounds__(64) void sh_accumulate_kernel(int64_t n, int n_views, const float* __restrict__ pos, const float* __restrict__ eyes,
                                                            const float* __restrict__ glogit, float scale, float* __restrict__ grad_f_dc,
                                                            float* __restrict__ grad_f_rest) {
@@ -277,7 +289,7 @@ __global__ __launch_bounds__(64) void sh_accumulate_kernel(int64_t n, int n_view
             ShMid sm;
             sh_basis(p, eye, sm);
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
+            for (int k = 0; k < NB; ++k) {
                 acc[k] += g0 * sm.Y[k]; acc[16 + k] += g1 * sm.Y[k]; acc[32 + k] += g2 * sm.Y[k];
             }
         }
@@ -286,7 +298,7 @@ __global__ __launch_bounds__(64) void sh_accumulate_kernel(int64_t n, int n_view
     for (int ch = 0; ch < 3; ++ch) {
         s_dc[lane * 3 + ch] = scale * acc[ch * 16];
 #pragma unroll
-        for (int k = 1; k < 16; ++k) s_rest[lane * 45 + ch * 15 + (k - 1)] = scale * acc[ch * 16 + k];
+        for (int k = 1; k < 16; ++k) s_rest[lane * 45 + ch * 15 + (k - 1)] = k < NB ? scale * acc[ch * 16 + k] : 0.f;
     }
     __syncthreads();
     unstage_rows<3>(grad_f_dc, s_dc, row0, n, lane);

@@ -67,14 +67,34 @@ __device__ __forceinline__ void unstage_rows(float* __restrict__ g, const float*
     }
 }
 
+// Rows [row0, row0 + 64) of g written as zeros, with the pieces of unstage_rows (SH degree 0: the f_rest gradient is not formed).
+template <int R>
+__device__ __forceinline__ void zero_rows(float* __restrict__ g, int64_t row0, int64_t n, int lane) {
+    const int64_t left = n - row0;
+    const int total = (int)(left < 64 ? left : 64) * R;
+    float* __restrict__ dst = g + row0 * R;
+    constexpr int PIECES = 64 * R / 4;
+#pragma unroll
+    for (int it = 0; it < (PIECES + 63) / 64; ++it) {
+        const int piece = it * 64 + lane;
+        if (piece * 4 + 3 < total) {
+            *reinterpret_cast<f4*>(dst + piece * 4) = f4{0.f, 0.f, 0.f, 0.f};
+        } else if (piece * 4 < total) {
+            for (int k = piece * 4; k < total; ++k) dst[k] = 0.f;
+        }
+    }
+}
+
 // The rows of a wave's R-float gradients (in LDS, as unstage_rows would write them) applied to the parameter instead: one Adam step
 // of rows [row0, row0 + 64) of p with the moments m, v -- 16-byte pieces, the same lanes reading and writing them.
 // counts / capacity: the frame's device counters and the pair capacity it was queued with -- a frame that outgrew its buffers (its
 // gradients are garbage and the host will render it again) or that has nothing on screen (the host will raise the reference's
 // exception) must not step anything: the guard is on the device because the host has not looked at the counters yet.
+// ZERO (SH degree 0): the gradient of every value is 0 and `lds` is not read -- the same adam_one, so moments left from a higher
+// degree decay as they do in the optimiser's own kernel.
 struct AdamRest { float* p; float* m; float* v; AdamStep k; const void* counts; long long capacity; };
 typedef float fv4 __attribute__((ext_vector_type(4)));
-template <int R>
+template <int R, bool ZERO = false>
 __device__ __forceinline__ void adam_rows(const AdamRest& a, const float* __restrict__ lds, int64_t row0, int64_t n, int lane) {
     const int64_t left = n - row0;
     const int total = (int)(left < 64 ? left : 64) * R;
@@ -84,7 +104,8 @@ __device__ __forceinline__ void adam_rows(const AdamRest& a, const float* __rest
     for (int it = 0; it < (PIECES + 63) / 64; ++it) {
         const int piece = it * 64 + lane;
         if (piece * 4 + 3 < total) {
-            fv4 p = *reinterpret_cast<const fv4*>(P + piece * 4), g = *reinterpret_cast<const fv4*>(lds + piece * 4);
+            fv4 p = *reinterpret_cast<const fv4*>(P + piece * 4), g = {0.f, 0.f, 0.f, 0.f};
+            if (!ZERO) g = *reinterpret_cast<const fv4*>(lds + piece * 4);
             fv4 m = __builtin_nontemporal_load(reinterpret_cast<const fv4*>(M + piece * 4)), v = __builtin_nontemporal_load(reinterpret_cast<const fv4*>(V + piece * 4));
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -97,7 +118,7 @@ __device__ __forceinline__ void adam_rows(const AdamRest& a, const float* __rest
             *reinterpret_cast<fv4*>(P + piece * 4) = p;
         } else if (piece * 4 < total) {
             for (int k = piece * 4; k < total; ++k) {
-                float gk = lds[k];
+                float gk = ZERO ? 0.f : lds[k];
                 adam_one(P[k], gk, M[k], V[k], 1.0f, false, a.k.step_size, a.k.b1, a.k.b2, a.k.inv_sqrt_bc2, a.k.eps);
             }
         }
@@ -117,6 +138,17 @@ struct ShEmitLds {
         if (k == 0) dc[ch] = v; else rest[ch * 15 + (k - 1)] = v;
     }
 };
+
+// SH degree 0: only f_dc has a gradient (the f_rest rows are zeros, written without passing through LDS)
+struct ShEmitDc {
+    float* dc;
+    float* rest;            // (not used: the same two fields as ShEmitLds, so that one expression builds either)
+    __device__ __forceinline__ void operator()(int k, int ch, float v) const {
+        if (k == 0) dc[ch] = v;
+    }
+};
+// the emitter of a render with NB active bases
+template <int NB> using ShEmitFor = std::conditional_t<(NB > 1), ShEmitLds, ShEmitDc>;
 
 __device__ __forceinline__ bool rect_is_big(u2 rect) {
     const int w = (int)(rect.y & 0xFFFF) - (int)(rect.x & 0xFFFF) + 1, h = (int)(rect.y >> 16) - (int)(rect.x >> 16) + 1;

@@ -93,8 +93,19 @@ Ctx open_ctx(int64_t n, const gsplat_view* v, const void* project_state, void* s
 }
 
 // TOTALS = !late (GSPLAT_PROJECT_COUNTS_LATE)
-template <bool FUSED, bool COLOUR, bool JAC>
-auto project_kernel_for(bool late) { return late ? project_kernel<FUSED, COLOUR, JAC, false> : project_kernel<FUSED, COLOUR, JAC, true>; }
+template <bool FUSED, bool COLOUR, bool JAC, int NB = 16>
+auto project_kernel_for(bool late) { return late ? project_kernel<FUSED, COLOUR, JAC, false, NB> : project_kernel<FUSED, COLOUR, JAC, true, NB>; }
+
+// The SH degree of a fused render travels in two flag bits as "bands dropped" = 3 - degree, so that flags of 0 stay degree 3:
+// bits 4-5 of gsplat_project / gsplat_forward_deferred, bits 8-9 of the backward entries (include/gsplat_mi355x.h).
+constexpr int32_t PROJECT_SH_BITS = GSPLAT_PROJECT_SH_DEGREE(0), BACKWARD_SH_BITS = GSPLAT_BACKWARD_SH_DEGREE(0);
+static_assert(GSPLAT_FRAME_SH_DEGREE(0) == PROJECT_SH_BITS, "gsplat_forward_deferred hands its degree bits to gsplat_project as they are");
+inline int project_sh_degree(int32_t flags) { return 3 - ((flags & PROJECT_SH_BITS) >> 4); }
+inline int backward_sh_degree(int32_t flags) { return 3 - ((flags & BACKWARD_SH_BITS) >> 8); }
+int check_sh_degree(const char* entry, int degree, bool fused) {
+    if (degree != 3 && !fused) return fail(GSPLAT_ERR_BAD_ARG, "%s: an SH degree below 3 needs fused inputs (scale_raw, q_raw, f_dc, f_rest): color + sigma carry no SH", entry);
+    return GSPLAT_OK;
+}
 
 // the flag bits the backward entries define; a call with any other bit is refused before it does anything (a library that ignored
 // a flag it does not know would, for GSPLAT_BACKWARD_ACCUMULATE, overwrite where the caller adds)
@@ -106,11 +117,29 @@ constexpr int32_t BACKWARD_FLAGS = GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD
 // K8 for gsplat_project_backward, the composite entries (ar: the in-place f_rest step) and gsplat_project_backward_pose (pose: where
 // the camera-pose gradient goes; `out` may then be NULL = pose only).
 struct PoseOut { float* grad_c2w; void* scratch; int64_t scratch_bytes; };
-int project_backward_impl(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state, const float* grad2d,
+// K8 of fused inputs at NB active SH bases -- <FUSED, JAC, ADAM, ACC, POSE, DEPTH, NB>: every fused instantiation there is
+template <int NB>
+auto fused_backward_kernel_for(bool adam, bool acc, bool depth, bool pose, bool jac) {
+    return adam    ? project_backward_kernel<true, true, true, false, false, false, NB>
+           : acc   ? project_backward_kernel<true, true, false, true, false, false, NB>
+           : depth ? (pose ? (jac ? project_backward_kernel<true, true, false, false, true, true, NB>
+                                  : project_backward_kernel<true, false, false, false, true, true, NB>)
+                           : (jac ? project_backward_kernel<true, true, false, false, false, true, NB>
+                                  : project_backward_kernel<true, false, false, false, false, true, NB>))
+           : pose  ? (jac ? project_backward_kernel<true, true, false, false, true, false, NB>
+                          : project_backward_kernel<true, false, false, false, true, false, NB>)
+                   : (jac ? project_backward_kernel<true, true, false, false, false, false, NB>
+                          : project_backward_kernel<true, false, false, false, false, false, NB>);
+}
+
+// entry: the name of the C ABI entry, for the messages that must carry it
+int project_backward_impl(const char* entry, const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state, const float* grad2d,
                           const gsplat_gaussian_grads* out, int32_t flags, void* stream_, const AdamRest* ar, const PoseOut* pose = nullptr) {
     bool fused = false;
     int rc = check_gaussians(g, &fused);
     if (rc) return rc;
+    const int degree = backward_sh_degree(flags);
+    if ((rc = check_sh_degree(entry, degree, fused))) return rc;
     if ((rc = check_view(v))) return rc;
     if (pose && !pose->grad_c2w) return fail(GSPLAT_ERR_BAD_ARG, "grad_c2w is NULL");
     if (!c2w || !project_state || !grad2d || (!pose && !out)) return fail(GSPLAT_ERR_BAD_ARG, "NULL argument");
@@ -146,21 +175,10 @@ int project_backward_impl(const gsplat_gaussians* g, const float* c2w, const gsp
     AdamRest a = {nullptr, nullptr, nullptr, {0.f, 0.f, 0.f, 0.f, 0.f}, nullptr, 0};
     if (ar) { a = *ar; a.counts = c.ps.counts; }
     const gsplat_gaussian_grads o = out ? *out : gsplat_gaussian_grads{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    // <FUSED, JAC, ADAM, ACC, POSE, DEPTH>: every instantiation there is
-    const auto kernel = ar    ? project_backward_kernel<true, true, true>
-                        : acc ? project_backward_kernel<true, true, false, true>
-                        : depth ? (pose ? (jac     ? project_backward_kernel<true, true, false, false, true, true>
-                                           : fused ? project_backward_kernel<true, false, false, false, true, true>
-                                                   : project_backward_kernel<false, false, false, false, true, true>)
-                                        : (jac     ? project_backward_kernel<true, true, false, false, false, true>
-                                           : fused ? project_backward_kernel<true, false, false, false, false, true>
-                                                   : project_backward_kernel<false, false, false, false, false, true>))
-                        : pose ? (jac     ? project_backward_kernel<true, true, false, false, true>
-                                  : fused ? project_backward_kernel<true, false, false, false, true>
-                                          : project_backward_kernel<false, false, false, false, true>)
-                               : (jac     ? project_backward_kernel<true, true>
-                                  : fused ? project_backward_kernel<true, false>
-                                          : project_backward_kernel<false, false>);
+    // (ar and acc have been checked to come with fused inputs)
+    const auto kernel = fused   ? with_sh_bases(degree, [&](auto nb) { return fused_backward_kernel_for<decltype(nb)::value>(ar != nullptr, acc, depth, pose != nullptr, jac); })
+                        : depth ? (pose ? project_backward_kernel<false, false, false, false, true, true> : project_backward_kernel<false, false, false, false, false, true>)
+                                : (pose ? project_backward_kernel<false, false, false, false, true> : project_backward_kernel<false, false>);
     LAUNCH(pose ? "project_backward_kernel<pose>" : "project_backward_kernel", kernel, dim3(blocks64(g->n)), dim3(64), 0, c.st, *g, c.ps.cam, c.vk, c.ps.tiles, grad2d, o, factored,
            jac ? c.ps.kj : nullptr, a, prs.rows);
     if (!pose) return GSPLAT_OK;
@@ -317,6 +335,7 @@ int gsplat_project(const gsplat_gaussians* g, const float* c2w, const gsplat_vie
     bool fused = false;
     int rc = check_gaussians(g, &fused);
     if (rc) return rc;
+    if ((rc = check_sh_degree("gsplat_project", project_sh_degree(flags), fused))) return rc;
     if ((rc = check_view(v))) return rc;
     if (!c2w || !project_state) return fail(GSPLAT_ERR_BAD_ARG, "c2w / project_state is NULL");
     if (!scratch || scratch_bytes < (int64_t)sizeof(CounterBlock)) return fail(GSPLAT_ERR_WORKSPACE, "project scratch (counter block) too small");
@@ -327,13 +346,16 @@ int gsplat_project(const gsplat_gaussians* g, const float* c2w, const gsplat_vie
     const bool colour_inside = !fused || (flags & GSPLAT_PROJECT_COLOUR_FUSED) != 0;
     const bool jac = fused && (flags & GSPLAT_PROJECT_SAVE_SH_JACOBIAN) != 0;
     const bool late = (flags & GSPLAT_PROJECT_COUNTS_LATE) != 0 && n > 0;      // counters totalled by bin_count_kernel
+    const int degree = project_sh_degree(flags);
     if (n > 0) {
         const Records out{ps.rec, ps.rect, ps.depth, ps.tiles, ps.mask, REF_RECT, REF_TILES};
         DevCounts* cm = mapped ? (DevCounts*)counts_host : nullptr;
-        const auto kernel = !fused                 ? project_kernel_for<false, true, false>(late)
-                            : colour_inside && jac ? project_kernel_for<true, true, true>(late)
-                            : colour_inside        ? project_kernel_for<true, true, false>(late)
-                                                   : project_kernel_for<true, false, false>(late);
+        const auto kernel = !fused          ? project_kernel_for<false, true, false>(late)
+                            : colour_inside ? with_sh_bases(degree, [&](auto nb) {
+                                  constexpr int NB = decltype(nb)::value;
+                                  return jac ? project_kernel_for<true, true, true, NB>(late) : project_kernel_for<true, true, false, NB>(late);
+                              })
+                                            : project_kernel_for<true, false, false>(late);
         LAUNCH("project_kernel", kernel, dim3(blocks64(n)), dim3(64), 0, st, *g, c2w, ps.cam, vk, out, (CounterBlock*)scratch, ps.counts, cm,
                ps.bin_total, (int)nb, colour_inside && jac ? ps.kj : nullptr, ps.big_flag);
         if (counts_host && !mapped && !late) HIP_TRY(hipMemcpyAsync(counts_host, ps.counts, sizeof(gsplat_counts), hipMemcpyDeviceToHost, st));
@@ -352,8 +374,11 @@ int gsplat_project(const gsplat_gaussians* g, const float* c2w, const gsplat_vie
             if (counts_event) HIP_TRY(hipEventRecord((hipEvent_t)counts_event, st));
         }
         if (!colour_inside) {
-            LAUNCH("colour_kernel", jac ? colour_kernel<true> : colour_kernel<false>, dim3(blocks64(n)), dim3(64), 0, st, *g, ps.cam, ps.tiles, ps.rec,
-                   jac ? ps.kj : nullptr);
+            const auto colour = with_sh_bases(degree, [&](auto nb) {
+                constexpr int NB = decltype(nb)::value;
+                return jac ? colour_kernel<true, NB> : colour_kernel<false, NB>;
+            });
+            LAUNCH("colour_kernel", colour, dim3(blocks64(n)), dim3(64), 0, st, *g, ps.cam, ps.tiles, ps.rec, jac ? ps.kj : nullptr);
         }
     }
     return GSPLAT_OK;
@@ -463,16 +488,16 @@ int gsplat_rasterize_backward_aux(int64_t n, int64_t n_binned, const gsplat_view
 
 int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state,
                             const float* grad2d, const gsplat_gaussian_grads* out, int32_t flags, void* stream_) {
-    if (flags & ~PROJECT_BACKWARD_FLAGS) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
-    return project_backward_impl(g, c2w, v, project_state, grad2d, out, flags, stream_, nullptr);
+    if (flags & ~(PROJECT_BACKWARD_FLAGS | BACKWARD_SH_BITS)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
+    return project_backward_impl("gsplat_project_backward", g, c2w, v, project_state, grad2d, out, flags, stream_, nullptr);
 }
 
 int gsplat_project_backward_pose(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state,
                                  const float* grad2d, const gsplat_gaussian_grads* out, float* grad_c2w, void* pose_scratch,
                                  int64_t pose_scratch_bytes, int32_t flags, void* stream_) {
-    if (flags & ~(GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_DEPTH)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
+    if (flags & ~(GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_DEPTH | BACKWARD_SH_BITS)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
     const PoseOut pose = {grad_c2w, pose_scratch, pose_scratch_bytes};
-    return project_backward_impl(g, c2w, v, project_state, grad2d, out, flags, stream_, nullptr, &pose);
+    return project_backward_impl("gsplat_project_backward_pose", g, c2w, v, project_state, grad2d, out, flags, stream_, nullptr, &pose);
 }
 
 // ---- one call per direction (include/gsplat_mi355x.h: "composite entries"; the frame arena: gs_layout.h frame_parts) ---------
@@ -480,8 +505,9 @@ int gsplat_forward_deferred(const gsplat_gaussians* g, const float* c2w, const g
                             int64_t pair_capacity, void* counters, int64_t counters_bytes, void* bin_scratch, int64_t bin_scratch_bytes,
                             gsplat_counts* counts_host, void* counts_event, float* image, int32_t flags, void* stream_) {
     if (!g || !v) return fail(GSPLAT_ERR_BAD_ARG, "gaussians / view is NULL");
-    int rc = check_view(v);
+    int rc = check_sh_degree("gsplat_forward_deferred", project_sh_degree(flags), g->scale_raw != nullptr);
     if (rc) return rc;
+    if ((rc = check_view(v))) return rc;
     if (!frame || !image) return fail(GSPLAT_ERR_BAD_ARG, "frame / image is NULL");
     if (reinterpret_cast<uintptr_t>(frame) & 255u) return fail(GSPLAT_ERR_BAD_ARG, "frame must be 256-byte aligned");
     if (pair_capacity < 1) return fail(GSPLAT_ERR_BAD_ARG, "pair_capacity must be positive (a capacity kept from earlier frames)");
@@ -490,7 +516,7 @@ int gsplat_forward_deferred(const gsplat_gaussians* g, const float* c2w, const g
     char* base = (char*)frame;
     const bool bwd = (flags & GSPLAT_FRAME_BACKWARD) != 0;
     const bool fused = g->scale_raw != nullptr;
-    int32_t pf = GSPLAT_PROJECT_COLOUR_FUSED | GSPLAT_PROJECT_COUNTS_LATE | (counts_host ? GSPLAT_PROJECT_COUNTS_MAPPED : 0);
+    int32_t pf = GSPLAT_PROJECT_COLOUR_FUSED | GSPLAT_PROJECT_COUNTS_LATE | (counts_host ? GSPLAT_PROJECT_COUNTS_MAPPED : 0) | (flags & PROJECT_SH_BITS);
     if (bwd && fused && !(flags & GSPLAT_FRAME_NO_SH_JACOBIAN)) pf |= GSPLAT_PROJECT_SAVE_SH_JACOBIAN;
     if ((rc = gsplat_project(g, c2w, v, base + f.project_state, counters, counters_bytes, counts_host, counts_event, pf, stream_))) return rc;
     if ((rc = gsplat_bin(g->n, pair_capacity, v, base + f.project_state, base + f.bin_state, bin_scratch, bin_scratch_bytes, stream_))) return rc;
@@ -501,12 +527,13 @@ int gsplat_forward_deferred(const gsplat_gaussians* g, const float* c2w, const g
 
 // (a helper inside the extern "C" block must be `static`: an anonymous namespace does not stop a function with C linkage from
 //  being exported, and the product library exports nothing but the gsplat_* entry points -- tests/test_abi_cpu.py)
-static int backward_impl(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, void* frame, int64_t frame_bytes,
+static int backward_impl(const char* entry, const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, void* frame, int64_t frame_bytes,
                          int64_t pair_capacity, const float* grad_image, const gsplat_gaussian_grads* out, float* grad_logit,
                          void* det_scratch, int64_t det_scratch_bytes, int32_t flags, void* stream_, const AdamRest* ar) {
     if (!g || !v) return fail(GSPLAT_ERR_BAD_ARG, "gaussians / view is NULL");
-    int rc = check_view(v);
+    int rc = check_sh_degree(entry, backward_sh_degree(flags), g->scale_raw != nullptr);
     if (rc) return rc;
+    if ((rc = check_view(v))) return rc;
     if (!frame) return fail(GSPLAT_ERR_BAD_ARG, "frame is NULL");
     const FrameParts f = frame_parts(g->n, pair_capacity, v, GSPLAT_FRAME_BACKWARD);
     if (f.total > frame_bytes) return fail(GSPLAT_ERR_WORKSPACE, "frame arena too small: was it made with GSPLAT_FRAME_BACKWARD?");
@@ -522,8 +549,8 @@ static int backward_impl(const gsplat_gaussians* g, const float* c2w, const gspl
     }
     if (both || (flags & GSPLAT_BACKWARD_PHASE_PROJECT)) {
         if (!out) return fail(GSPLAT_ERR_BAD_ARG, "grads is NULL");
-        if ((rc = project_backward_impl(g, c2w, v, base + f.project_state, grad2d, out,
-                                        flags & (GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_ACCUMULATE), stream_, ar))) return rc;
+        if ((rc = project_backward_impl(entry, g, c2w, v, base + f.project_state, grad2d, out,
+                                        flags & (GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_ACCUMULATE | BACKWARD_SH_BITS), stream_, ar))) return rc;
     }
     return GSPLAT_OK;
 }
@@ -531,8 +558,8 @@ static int backward_impl(const gsplat_gaussians* g, const float* c2w, const gspl
 int gsplat_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, void* frame, int64_t frame_bytes,
                     int64_t pair_capacity, const float* grad_image, const gsplat_gaussian_grads* out, float* grad_logit,
                     void* det_scratch, int64_t det_scratch_bytes, int32_t flags, void* stream_) {
-    if (flags & ~BACKWARD_FLAGS) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
-    return backward_impl(g, c2w, v, frame, frame_bytes, pair_capacity, grad_image, out, grad_logit, det_scratch, det_scratch_bytes, flags,
+    if (flags & ~(BACKWARD_FLAGS | BACKWARD_SH_BITS)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
+    return backward_impl("gsplat_backward", g, c2w, v, frame, frame_bytes, pair_capacity, grad_image, out, grad_logit, det_scratch, det_scratch_bytes, flags,
                          stream_, nullptr);
 }
 
@@ -540,8 +567,9 @@ int gsplat_backward_adam_rest(const gsplat_gaussians* g, const float* c2w, const
                               int64_t pair_capacity, const float* grad_image, const gsplat_gaussian_grads* out, void* det_scratch,
                               int64_t det_scratch_bytes, int32_t flags, const gsplat_adam_group* f_rest, float beta1, float beta2, float eps,
                               void* stream_) {
-    if (flags & ~BACKWARD_FLAGS) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
+    if (flags & ~(BACKWARD_FLAGS | BACKWARD_SH_BITS)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
     if (!g || !f_rest) return fail(GSPLAT_ERR_BAD_ARG, "gaussians / f_rest update is NULL");
+    if (int rc = check_sh_degree("gsplat_backward_adam_rest", backward_sh_degree(flags), g->scale_raw != nullptr)) return rc;
     if (flags & (GSPLAT_BACKWARD_PHASE_RASTER | GSPLAT_BACKWARD_PHASE_PROJECT)) return fail(GSPLAT_ERR_BAD_ARG, "the in-place step runs the whole backward pass");
     if (f_rest->n != g->n * 45 || f_rest->step < 1 || !f_rest->param || !f_rest->exp_avg || !f_rest->exp_avg_sq || f_rest->grad_scale ||
         f_rest->param != g->f_rest)
@@ -551,7 +579,7 @@ int gsplat_backward_adam_rest(const gsplat_gaussians* g, const float* c2w, const
     const double bc1 = 1.0 - pow((double)beta1, (double)f_rest->step), bc2 = 1.0 - pow((double)beta2, (double)f_rest->step);
     const AdamRest ar = {f_rest->param, f_rest->exp_avg, f_rest->exp_avg_sq,
                          {(float)((double)f_rest->lr / bc1), (float)(1.0 / sqrt(bc2)), beta1, beta2, eps}, nullptr, (long long)pair_capacity};
-    return backward_impl(g, c2w, v, frame, frame_bytes, pair_capacity, grad_image, out, nullptr, det_scratch, det_scratch_bytes, flags, stream_, &ar);
+    return backward_impl("gsplat_backward_adam_rest", g, c2w, v, frame, frame_bytes, pair_capacity, grad_image, out, nullptr, det_scratch, det_scratch_bytes, flags, stream_, &ar);
 }
 
 int gsplat_build_sigma(int64_t n, const float* scale_raw, const float* q_raw, float* sigma, void* stream_) {
@@ -608,11 +636,18 @@ int gsplat_logit_grad(int64_t n, const gsplat_view* v, const void* project_state
 
 int gsplat_sh_accumulate(int64_t n, int32_t n_views, const float* pos, const float* eyes, const float* grad_logit, float scale,
                          float* grad_f_dc, float* grad_f_rest, void* stream_) {
+    return gsplat_sh_accumulate_degree(n, n_views, pos, eyes, grad_logit, scale, grad_f_dc, grad_f_rest, 3, stream_);
+}
+
+int gsplat_sh_accumulate_degree(int64_t n, int32_t n_views, const float* pos, const float* eyes, const float* grad_logit, float scale,
+                                float* grad_f_dc, float* grad_f_rest, int32_t sh_degree, void* stream_) {
+    if (sh_degree < 0 || sh_degree > 3) return fail(GSPLAT_ERR_BAD_ARG, "gsplat_sh_accumulate_degree: sh_degree must be 0, 1, 2 or 3");
     if (n < 0 || n_views < 0) return fail(GSPLAT_ERR_BAD_ARG, "n / n_views < 0");
     if (n == 0) return GSPLAT_OK;
     if (!pos || !grad_f_dc || !grad_f_rest || (n_views > 0 && (!eyes || !grad_logit))) return fail(GSPLAT_ERR_BAD_ARG, "NULL argument");
     if (!aligned16(pos) || !aligned16(grad_f_dc) || !aligned16(grad_f_rest)) return fail(GSPLAT_ERR_BAD_ARG, "arrays must be 16-byte aligned");
-    LAUNCH("sh_accumulate_kernel", sh_accumulate_kernel, dim3(blocks64(n)), dim3(64), 0, (hipStream_t)stream_, n, (int)n_views, pos, eyes, grad_logit,
+    const auto kernel = with_sh_bases(sh_degree, [](auto nb) { return sh_accumulate_kernel<decltype(nb)::value>; });
+    LAUNCH("sh_accumulate_kernel", kernel, dim3(blocks64(n)), dim3(64), 0, (hipStream_t)stream_, n, (int)n_views, pos, eyes, grad_logit,
            scale, grad_f_dc, grad_f_rest);
     return GSPLAT_OK;
 }

@@ -98,4 +98,46 @@ void hm_evaluate_sh_backward(int64_t n, const float* f_dc, const float* f_rest, 
     Camera cam; build_camera(c2w, cam);
     for (int64_t i = 0; i < n; ++i) evaluate_sh_backward_one(i, f_dc, f_rest, pts, cam, grad_color, g_dc, g_rest, g_pts);
 }
+
+// ---- the SH colour at a degree (0..3): the code the projection kernels run with NB = (degree + 1)^2 active bases --------------
+// Both return 0, or 1 for a degree outside 0..3 (nothing is written then).
+// color[n,3]; kj[n,12] = the saved Jacobian of sh_colour_jac (d rgb / d logit [3], d logit / d point [3][3]).
+int hm_sh_colour_degree(int64_t n, const float* f_dc, const float* f_rest, const float* pts, const float* c2w, int32_t degree,
+                        float* color, float* kj) {
+    if (degree < 0 || degree > 3) return 1;
+    Camera cam; build_camera(c2w, cam);
+    return with_sh_bases(degree, [&](auto nb) {
+        for (int64_t i = 0; i < n; ++i) {
+            ShMid sm;
+            sh_basis(pts + i * 3, cam.eye, sm);
+            sh_colour_jac<decltype(nb)::value>(sm, ShCoefGlobal{f_dc + i * 3, f_rest + i * 45}, color + i * 3, kj + i * 12);
+        }
+        return 0;
+    });
+}
+// The backward of that colour: from_jac = 0 from the coefficients (sh_colour_backward), 1 from the saved Jacobian
+// (sh_colour_backward_jac, which does not read f_dc / f_rest again).  Every slot of g_dc[n,3], g_rest[n,45], g_pts[n,3] is written.
+int hm_sh_backward_degree(int64_t n, const float* f_dc, const float* f_rest, const float* pts, const float* c2w,
+                          const float* grad_color, int32_t degree, int32_t from_jac, float* g_dc, float* g_rest, float* g_pts) {
+    if (degree < 0 || degree > 3) return 1;
+    Camera cam; build_camera(c2w, cam);
+    return with_sh_bases(degree, [&](auto nb) {
+        constexpr int NB = decltype(nb)::value;
+        for (int64_t i = 0; i < n; ++i) {
+            ShMid sm;
+            sh_basis(pts + i * 3, cam.eye, sm);
+            const ShCoefGlobal coef{f_dc + i * 3, f_rest + i * 45};
+            const ShEmitGlobal emit{g_dc + i * 3, g_rest + i * 45};
+            float rgb[3], kj[12];
+            if (from_jac) {
+                sh_colour_jac<NB>(sm, coef, rgb, kj);
+                sh_colour_backward_jac<NB>(sm, kj, grad_color + i * 3, emit, g_pts + i * 3);
+            } else {
+                sh_colour<NB>(sm, coef, rgb);
+                sh_colour_backward<NB>(sm, coef, rgb, grad_color + i * 3, emit, g_pts + i * 3);
+            }
+        }
+        return 0;
+    });
+}
 }

@@ -201,7 +201,7 @@ class FactoredExchange:
 
     SMALL = ("pos", "opacity_raw", "scale_raw", "q_raw")
 
-    def __init__(self, params, world_views, group=None, accumulate=None, force_collectives=False, equal_views=True):
+    def __init__(self, params, world_views, group=None, accumulate=None, force_collectives=False, equal_views=True, sh_degree=None):
         self.params, self.world_views, self.group = params, world_views, group
         self.equal_views = equal_views
         self.logits, self.eyes, self._early = [], [], []
@@ -209,6 +209,9 @@ class FactoredExchange:
         self._accumulate = accumulate
         self._force = force_collectives          # tests: issue the collectives even in a one-rank group
         self.n_added = 0                         # views handed in by the render backward (Trainer.step checks it against its views)
+        # the SH degree of the pass's views (one per pass: the rebuild leaves the inactive columns zero).  Given by a caller that
+        # knows it (Trainer: a rank whose views all failed must still rebuild at its peers' degree); None: learnt from the first view
+        self._given_degree = self.sh_degree = sh_degree
 
     def owns(self, inputs, src_ptrs=None):
         """Is this render differentiating the parameters this exchange was built for (same f_dc / f_rest storage)?
@@ -226,9 +229,14 @@ class FactoredExchange:
     def _distributed(self):
         return dist.is_available() and dist.is_initialized() and (dist.get_world_size(self.group) > 1 or self._force)
 
-    def add(self, grad_logit, eye):
+    def add(self, grad_logit, eye, sh_degree=3):
         """Called by the render backward with one view's logit gradients BEFORE it launches the projection backward: with
-        equal view counts the all-gather of this view starts here (async) and overlaps that kernel."""
+        equal view counts the all-gather of this view starts here (async) and overlaps that kernel.  sh_degree: the degree the
+        view was rendered at -- the rebuild in finish() leaves the inactive columns zero, and needs ONE degree for all views."""
+        if self.sh_degree is None:
+            self.sh_degree = sh_degree
+        elif sh_degree != self.sh_degree:
+            raise RuntimeError(f"the views of one factored exchange were rendered at SH degrees {self.sh_degree} and {sh_degree}: one degree per pass")
         eye = eye.detach().to(torch.float32).contiguous()
         self.n_added += 1
         if self._distributed() and self.equal_views and not (dist.get_backend(self.group) == "gloo" and grad_logit.is_cuda):
@@ -258,7 +266,8 @@ class FactoredExchange:
         n = self.params["pos"].shape[0]
         dev = self.params["pos"].device
         while self.n_added < int(expected):
-            self.add(torch.zeros((n, 3), dtype=torch.float32, device=dev), torch.zeros(3, dtype=torch.float32, device=dev))
+            self.add(torch.zeros((n, 3), dtype=torch.float32, device=dev), torch.zeros(3, dtype=torch.float32, device=dev),
+                     3 if self.sh_degree is None else self.sh_degree)
 
     def abandon(self):
         """Drop what was collected (the pass is being repeated): collectives already in flight are waited for, nothing is kept."""
@@ -267,6 +276,7 @@ class FactoredExchange:
                 w.wait()
         self.logits, self.eyes, self._early = [], [], []
         self.n_added = 0
+        self.sh_degree = self._given_degree
 
     def finish(self):
         p = self.params
@@ -309,7 +319,9 @@ class FactoredExchange:
             acc = ops.sh_accumulate
         # the SH rebuild only needs the gathered logit gradients: it runs while the all-reduce of the small gradients is
         # still in flight on the collective's stream
-        g_dc, g_rest = acc(p["pos"].detach(), eyes, logits, 1.0 / self.world_views)
+        degree = 3 if self.sh_degree is None else self.sh_degree          # (an `accumulate` of the older four-argument form still serves degree 3)
+        g_dc, g_rest = (acc(p["pos"].detach(), eyes, logits, 1.0 / self.world_views) if degree == 3 else
+                        acc(p["pos"].detach(), eyes, logits, 1.0 / self.world_views, sh_degree=degree))
         for k, g in (("f_dc", g_dc), ("f_rest", g_rest)):
             g = g.to(p[k].dtype)
             p[k].grad = g if p[k].grad is None else p[k].grad + g
@@ -319,3 +331,4 @@ class FactoredExchange:
                 base.mul_(1.0 / self.world_views)
         self.logits, self.eyes, self._early = [], [], []
         self.n_added = 0
+        self.sh_degree = self._given_degree

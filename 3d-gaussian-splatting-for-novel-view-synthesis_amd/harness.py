@@ -84,10 +84,13 @@ def load_parameters(checkpoint_dir, iteration='final', device="cuda"):
                             f"(looked for {path.name} and {', '.join(f.name for f in loose.values())})")
 
 
-def benchmark_orbit(params, c2ws, H, W, fx, fy, cx, cy, fused=True, on_frame=None):
+def benchmark_orbit(params, c2ws, H, W, fx, fy, cx, cy, fused=True, on_frame=None, sh_degree=3):
     """Per-frame render times over a trajectory with the reference's protocol: one un-timed warm-up frame, then for each
     frame synchronize -> wall clock -> (SH + render) -> synchronize -> wall clock.  `fused=False` issues the reference's
-    own call sequence (evaluate_sh + render with a pre-built sigma, covariance build outside the timed region)."""
+    own call sequence (evaluate_sh + render with a pre-built sigma, covariance build outside the timed region).
+    sh_degree: as for ops.render_gaussians (fused frames only: the reference's sequence has no degree)."""
+    if not fused and sh_degree != 3:
+        raise ValueError("sh_degree needs fused=True: evaluate_sh + render is the reference's degree-3 sequence")
     dev = params["pos"].device
     kw = dict(pix_guard=32, chi_square_clip=6.25, alpha_cutoff=1 / 128.)
     sigma = None if fused else ops.build_sigma_from_params(params["scale_raw"], params["q_raw"])
@@ -95,7 +98,7 @@ def benchmark_orbit(params, c2ws, H, W, fx, fy, cx, cy, fused=True, on_frame=Non
     def frame(c2w):
         if fused:
             return ops.render_gaussians(params["pos"], params["f_dc"], params["f_rest"], params["opacity_raw"], params["scale_raw"],
-                                        params["q_raw"], c2w, H, W, fx, fy, cx, cy, **kw)
+                                        params["q_raw"], c2w, H, W, fx, fy, cx, cy, sh_degree=sh_degree, **kw)
         col = ops.evaluate_sh(params["f_dc"], params["f_rest"], params["pos"], c2w)
         return ops.render(params["pos"], col, params["opacity_raw"], sigma, c2w, H, W, fx, fy, cx, cy, **kw)
 
@@ -120,17 +123,17 @@ def benchmark_orbit(params, c2ws, H, W, fx, fy, cx, cy, fused=True, on_frame=Non
             "fps_min": fps.min(), "fps_max": fps.max(), "times": t}
 
 
-def throughput_orbit(params, c2ws, H, W, fx, fy, cx, cy, on_frame=None):
+def throughput_orbit(params, c2ws, H, W, fx, fy, cx, cy, on_frame=None, sh_degree=3):
     """Frames per second over a trajectory when frames need not be timed one by one: ops.render_frames pipelines them over
     two streams (frame k + 1's projection / binning overlaps frame k's rasterisation).  Not the reference's protocol
-    (benchmark_orbit is): a serving-style number."""
+    (benchmark_orbit is): a serving-style number.  sh_degree: as for ops.render_frames."""
     dev = params["pos"].device
     args = (params["pos"], params["f_dc"], params["f_rest"], params["opacity_raw"], params["scale_raw"], params["q_raw"])
     cams = [torch.as_tensor(np.asarray(c), dtype=torch.float32, device=dev) for c in c2ws]
-    ops.render_frames(*args, cams[:2], H, W, fx, fy, cx, cy, on_frame=lambda k, im: None)       # warm-up
+    ops.render_frames(*args, cams[:2], H, W, fx, fy, cx, cy, on_frame=lambda k, im: None, sh_degree=sh_degree)       # warm-up
     torch.cuda.synchronize(dev)
     t0 = time.time()
-    ops.render_frames(*args, cams, H, W, fx, fy, cx, cy, on_frame=on_frame or (lambda k, im: None))
+    ops.render_frames(*args, cams, H, W, fx, fy, cx, cy, on_frame=on_frame or (lambda k, im: None), sh_degree=sh_degree)
     torch.cuda.synchronize(dev)
     dt = time.time() - t0
     return {"frames": len(cams), "seconds": dt, "fps": len(cams) / dt if dt > 0 else float("inf")}

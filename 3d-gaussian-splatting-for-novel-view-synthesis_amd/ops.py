@@ -9,7 +9,8 @@ Mirrors the reference's operator interface (same names, argument meaning, defaul
     evaluate_sh(f_dc, f_rest, points, c2w)                                   reference spherical_harmonics.py:70
 
 plus the fused entry `render_gaussians(...)`, which takes the six raw parameter tensors and folds the covariance build
-and the SH evaluation into the projection kernel (the Sigma[N,3,3] and colour[N,3] tensors are never materialised).
+and the SH evaluation into the projection kernel (the Sigma[N,3,3] and colour[N,3] tensors are never materialised); its
+keyword sh_degree (0..3, default 3) renders with the first (sh_degree + 1)^2 SH bases only.
 
 PyTorch is plumbing here (device memory, streams, autograd bookkeeping); all arithmetic runs in the HIP library.
 There is no CPU path: CPU tensors, or a missing library, raise.
@@ -353,7 +354,7 @@ class _Frame:
     (project_state | bin_state | accum | grad2d, carved by the library); one that went through the separate calls keeps them
     as separate buffers."""
     __slots__ = ("view", "n", "n_pairs", "proj_state", "bin_state", "accum", "fused", "inputs", "c2w", "empty", "grad2d", "sh_jacobian",
-                 "arena", "gaussians", "dirty", "src_ptrs", "route", "pose", "aux", "background", "accum_aux", "stats")
+                 "arena", "gaussians", "dirty", "src_ptrs", "route", "pose", "aux", "background", "accum_aux", "stats", "sh_degree")
 
 
 class _Pending:
@@ -380,6 +381,8 @@ def _new_frame(fused, view, n, pos32, opa32, c2w32, ins, c, d):
     fr.arena = fr.gaussians = fr.proj_state = fr.bin_state = fr.accum = fr.grad2d = fr.route = None
     fr.dirty = fr.pose = fr.aux = False
     fr.background = fr.accum_aux = fr.stats = None
+    # the SH degree of the forward pass, kept on the frame: every backward route reads it here, so it cannot differ
+    fr.sh_degree = view.sh_degree if fused else 3
     # the caller's own SH tensors (before any dtype / layout conversion): what dp.FactoredExchange.owns() compares
     fr.src_ptrs = (c.data_ptr(), d.data_ptr()) if fused else None
     return fr
@@ -437,6 +440,7 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
         H, W = view.H, view.W
         flags = (_abi.GSPLAT_FRAME_BACKWARD if need_grad else 0) | (0 if _sh_jacobian else _abi.GSPLAT_FRAME_NO_SH_JACOBIAN)
         frame_bytes, scratch_bytes = _ws.frame_sizes(lib, n, capacity, view, flags)
+        flags |= _FRAME_DEGREE[fr.sh_degree]
         fr.arena = torch.empty(frame_bytes, dtype=torch.uint8, device=dev)
         image = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
         scratch = _ws.get_scratch(dev, scratch_bytes, key)
@@ -459,6 +463,7 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
     flags = _abi.GSPLAT_PROJECT_COUNTS_MAPPED | ((_abi.GSPLAT_PROJECT_COLOUR_FUSED | _abi.GSPLAT_PROJECT_COUNTS_LATE) if deferred else 0)
     if fr.sh_jacobian:
         flags |= _abi.GSPLAT_PROJECT_SAVE_SH_JACOBIAN
+    flags |= _PROJECT_DEGREE[fr.sh_degree]
     with _stage("project"):
         _abi.check(lib.gsplat_project(C.byref(g), _p(c2w32), C.byref(view), _p(fr.proj_state), _p(counters),
                                       counters.numel(), C.c_void_p(pinned.data_ptr()), C.c_void_p(ready.cuda_event),
@@ -491,6 +496,10 @@ def _background_arg(background):
 
 
 _COUNTER_BYTES = 0
+# the flag bits of an SH degree, per entry family (index = degree; 0 for degree 3)
+_PROJECT_DEGREE = tuple(_abi.GSPLAT_PROJECT_SH_DEGREE(d) for d in range(4))
+_FRAME_DEGREE = tuple(_abi.GSPLAT_FRAME_SH_DEGREE(d) for d in range(4))
+_BACKWARD_DEGREE = tuple(_abi.GSPLAT_BACKWARD_SH_DEGREE(d) for d in range(4))
 _FORWARD_STAGES = frozenset(("project", "bin", "raster_forward"))
 
 
@@ -698,7 +707,7 @@ def _backward_impl(fr, grad_image, need_params=True, grad_depth=None, grad_alpha
     factored = isinstance(route, dp.FactoredExchange)
     if fr.empty or fr.n == 0 or (fr.aux and grad_image is None and grad_depth is None and grad_alpha is None):
         if factored:
-            route.add(torch.zeros((fr.n, 3), dtype=torch.float32, device=dev), fr.c2w[:3, 3])
+            route.add(torch.zeros((fr.n, 3), dtype=torch.float32, device=dev), fr.c2w[:3, 3], fr.sh_degree)
         out = {k: torch.zeros_like(v) for k, v in ins.items() if not (factored and k in _SH)}
         if fr.pose:
             out["c2w"] = torch.zeros((4, 4), dtype=torch.float32, device=dev)
@@ -723,7 +732,8 @@ def _backward_impl(fr, grad_image, need_params=True, grad_depth=None, grad_alpha
     else:
         dst = _flat_like({k: v for k, v in ins.items() if not (factored and k in _SH or folded and k == "f_rest")})
     gg = _abi.GaussianGrads(*map(_p, map(dst.get, _GRAD_FIELDS)))
-    jac = _abi.GSPLAT_BACKWARD_SH_JACOBIAN if fr.sh_jacobian else 0
+    # (`jac` goes into the flags of every projection backward below: the saved Jacobian and the degree of the frame's forward pass)
+    jac = (_abi.GSPLAT_BACKWARD_SH_JACOBIAN if fr.sh_jacobian else 0) | _BACKWARD_DEGREE[fr.sh_degree]
     if fr.arena is None:                       # ---- the frame went through the separate calls
         zeroed = fr.grad2d is not None
         grad2d = fr.grad2d if zeroed else torch.empty((fr.n, 16), dtype=torch.float32, device=dev)
@@ -750,7 +760,7 @@ def _backward_impl(fr, grad_image, need_params=True, grad_depth=None, grad_alpha
             # logit gradients first: the exchange may start on them while the projection backward runs
             glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=dev)
             _abi.check(lib.gsplat_logit_grad(fr.n, C.byref(fr.view), _p(fr.proj_state), _p(grad2d), _p(glogit), st), "gsplat_logit_grad")
-            route.add(glogit, fr.c2w[:3, 3])
+            route.add(glogit, fr.c2w[:3, 3], fr.sh_degree)
         g = _make_gaussians(fr.n, **ins)
         if fr.pose:
             # the same chain rule plus dL/dc2w: per-block rows of the pose terms, added in a fixed order (no gradient rows if
@@ -784,7 +794,7 @@ def _backward_impl(fr, grad_image, need_params=True, grad_depth=None, grad_alpha
         with _stage("raster_backward"):
             _backward_call(fr, gi, gg, flags | _abi.GSPLAT_BACKWARD_PHASE_RASTER, st, det, glogit)
         if factored:                           # logit gradients first: the exchange may start on them while the projection backward runs
-            route.add(glogit, fr.c2w[:3, 3])
+            route.add(glogit, fr.c2w[:3, 3], fr.sh_degree)
         _frame_stats(fr, st)
         with _stage("project_backward"):
             _backward_call(fr, gi, gg, jac | _abi.GSPLAT_BACKWARD_PHASE_PROJECT, st)
@@ -892,8 +902,10 @@ def _stats_record(pos):
     return data
 
 
-def sh_accumulate(pos, eyes, grad_logit, scale=1.0):
-    """(grad_f_dc [N,3], grad_f_rest [N,45]) = scale * sum over views of grad_logit[v] (x) Y(direction from eyes[v] to pos)."""
+def sh_accumulate(pos, eyes, grad_logit, scale=1.0, sh_degree=3):
+    """(grad_f_dc [N,3], grad_f_rest [N,45]) = scale * sum over views of grad_logit[v] (x) Y(direction from eyes[v] to pos).
+    sh_degree: the degree the views were rendered at; the columns of the inactive bases are zeros."""
+    _abi.sh_bands_dropped(sh_degree)
     lib = _abi.lib()
     n = pos.shape[0]
     v = grad_logit.shape[0]
@@ -903,8 +915,8 @@ def sh_accumulate(pos, eyes, grad_logit, scale=1.0):
         off = (n * 3 + 63) // 64 * 64                     # both views 256-byte aligned inside one buffer
         flat = torch.empty(off + n * 45, dtype=torch.float32, device=dev)
         g_dc, g_rest = flat[:n * 3].view(n, 3), flat[off:off + n * 45].view(n, 45)
-        _abi.check(lib.gsplat_sh_accumulate(n, v, _p(pos32), _p(eyes32), _p(gl32), float(scale), _p(g_dc), _p(g_rest),
-                                            _stream_ptr(dev)), "gsplat_sh_accumulate")
+        _abi.check(lib.gsplat_sh_accumulate_degree(n, v, _p(pos32), _p(eyes32), _p(gl32), float(scale), _p(g_dc), _p(g_rest),
+                                                   sh_degree, _stream_ptr(dev)), "gsplat_sh_accumulate_degree")
     return g_dc, g_rest
 
 
@@ -964,6 +976,12 @@ def _view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_c
                           chi_square_clip, alpha_max, alpha_cutoff)
     view.grad_mode = torch.is_grad_enabled()            # Python-side attribute (not part of the C struct)
     view.aux, view.background = False, None             # (likewise: set by _aux_view)
+    view.sh_degree = 3                                  # (likewise: set by _degree_view)
+    return view
+
+
+def _degree_view(view, sh_degree):
+    view.sh_degree = sh_degree
     return view
 
 
@@ -1003,25 +1021,34 @@ def render(pos, color, opacity_raw, sigma, c2w, H, W, fx, fy, cx, cy, near=0.01,
 
 def render_gaussians(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2w, H, W, fx, fy, cx, cy, near=0.01, far=100.0,
                      pix_guard=32, T=16, min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128., *, aux=False,
-                     background=None):
+                     background=None, sh_degree=3):
     """Fused entry: render(pos, evaluate_sh(f_dc, f_rest, pos, c2w), opacity_raw, build_sigma_from_params(scale_raw,
     q_raw), c2w, ...) in one pass (the reference's three-call sequence, scripts/train.py:463,502,505-508).  Differentiable
     w.r.t. the six parameter tensors and c2w (through the camera transform, the covariance rotation and the SH view
-    direction), as render() is.  aux, background: as for render()."""
-    view = _aux_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), aux, background)
+    direction), as render() is.  aux, background: as for render().
+
+    sh_degree (one of the integers 0, 1, 2, 3; anything else raises ValueError before anything is queued): the colour is
+    sigmoid(sum_{k < (sh_degree + 1)^2} f_k Y_k).  f_rest stays [N, 45]; its inactive entries -- columns ch * 15 + j with
+    j >= (sh_degree + 1)^2 - 1 -- are ignored: their values (a NaN included) change no output bit, their gradient is exactly
+    zero on every backward route, and the image equals the default render of the same scene with zeros there.  The degree
+    is kept on the frame, so the backward pass cannot be given another one."""
+    _abi.sh_bands_dropped(sh_degree)
+    view = _degree_view(_aux_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), aux, background),
+                        sh_degree)
     return _RenderFn.apply(True, view, c2w, pos, opacity_raw, scale_raw, q_raw, f_dc, f_rest)
 
 
 @torch.no_grad()
 def render_frames(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2ws, H, W, fx, fy, cx, cy, near=0.01, far=100.0,
-                  pix_guard=32, T=16, min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128., on_frame=None):
+                  pix_guard=32, T=16, min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128., on_frame=None, sh_degree=3):
     """Forward-only rendering of a sequence of camera poses with the frames software-pipelined over two HIP streams:
     frame k + 1's projection / binning front (latency- and bandwidth-bound) overlaps frame k's rasterisation (VALU-bound).
     Same images as render_gaussians() frame by frame.  Returns the list of images (or calls on_frame(k, image) and returns
     None); the caller's current stream waits for all of them.  Without on_frame, and once a pair capacity is known for the
     device, no frame waits for its counters either (deferred_checks: the per-frame checks are made after the last frame is
-    queued; a sequence that outgrows the buffers is rendered again)."""
-    view = _view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff)
+    queued; a sequence that outgrows the buffers is rendered again).  sh_degree: as for render_gaussians()."""
+    _abi.sh_bands_dropped(sh_degree)
+    view = _degree_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), sh_degree)
     dev = pos.device
     cams = [torch.as_tensor(c, dtype=torch.float32, device=dev) if not isinstance(c, torch.Tensor) else c for c in c2ws]
     args = (view, dev, cams, pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw)

@@ -71,6 +71,11 @@ class TrainConfig:
     densify_rule: str = "reference"
     densify_grad_threshold: float = 0.0002
     max_screen_size: float = 20.0
+    # the paper's SH schedule (not in the reference, which always evaluates degree 3).  0: degree 3 always.  k > 0: iteration i renders
+    # every view at SH degree min(3, i // k) (the paper: k = 1000) -- until a band is switched on its coefficients colour nothing and
+    # get a zero gradient (ops.render_gaussians sh_degree).  A function of the iteration alone: checkpoints store
+    # nothing for it and data-parallel ranks agree without a message.
+    sh_degree_interval: int = 0
 
 
 _side_streams = {}           # per device: the two streams the views of an iteration alternate between (TrainConfig.view_streams)
@@ -86,6 +91,8 @@ class Trainer:
         self.group = group
         if self.cfg.densify_rule not in ("reference", "screen"):
             raise ValueError(f"densify_rule must be 'reference' or 'screen', not {self.cfg.densify_rule!r}")
+        if type(self.cfg.sh_degree_interval) is not int or self.cfg.sh_degree_interval < 0:
+            raise ValueError(f"sh_degree_interval must be an integer >= 0, not {self.cfg.sh_degree_interval!r}")
         self.optimizer = self._new_optimizer(self.cfg.position_lr_init)
         self._gen = None
         # densify_rule = "screen": the statistics since the last densification (None until the first such step; not stored in
@@ -146,6 +153,11 @@ class Trainer:
         g.manual_seed(self.cfg.densify_seed * 1000003 + iteration)
         return g
 
+    def sh_degree(self, iteration):
+        """The SH degree iteration `iteration` renders at (TrainConfig.sh_degree_interval)."""
+        k = self.cfg.sh_degree_interval
+        return 3 if k == 0 else max(0, min(3, int(iteration) // k))
+
     def step(self, iteration, views, global_views=None, views_per_rank=None):
         """One iteration on this rank's `views` (list of dicts with image [H,W,3], c2w [4,4], H, W, fx, fy, cx, cy — the
         sample dict of data.GaussianDataset).  Data parallel: the ranks may hold different numbers of views; how many each
@@ -153,8 +165,10 @@ class Trainer:
         per rank, the same list on every rank) or leave it None and the counts are exchanged with one tiny all-gather.
         `global_views` (views of the whole batch over all ranks) is only checked against that.  Returns {'loss', 'l1',
         'ssim'} as device scalars (this rank's share, already divided by the global batch), 'gaussians', 'lr_pos',
-        'densified'."""
+        'densified', 'sh_degree' (the SH degree the views were rendered at)."""
         c, m = self.cfg, self.model
+        sh_degree = self.sh_degree(iteration)
+        degree_kw = {} if sh_degree == 3 else {'sh_degree': sh_degree}      # (without a schedule the render call is the reference's)
         world = self._world()
         dev = m.pos.device
         even, n_global = dp.agree_on_views(len(views), self.group, views_per_rank, device=dev)
@@ -170,7 +184,8 @@ class Trainer:
             acc = torch.zeros(3, dtype=torch.float32, device=dev)
             # the route of the gradients (ops.gradient_route): data parallel, SH gradients in factored form (dp.FactoredExchange, 2.6x
             # fewer bytes over xGMI at 8 views); one view, the Adam step of f_rest inside its backward; several, their sum in the backward
-            exchange = dp.FactoredExchange(m.get_params(), world_views=1, group=self.group, equal_views=even) if world > 1 else None
+            exchange = (dp.FactoredExchange(m.get_params(), world_views=1, group=self.group, equal_views=even, sh_degree=sh_degree)
+                        if world > 1 else None)
             fold = exchange is None and len(views) == 1 and c.fold_rest_step
             sum_in_kernel = exchange is None and len(views) > 1 and c.sum_views_in_kernel
             route = (exchange if exchange is not None else self.optimizer.fused_rest_update(m.f_rest) if fold
@@ -195,7 +210,8 @@ class Trainer:
                             c2w = torch.as_tensor(v['c2w'], dtype=torch.float32).to(dev)
                             with (ops.densify_stats(pass_stats[k]) if screen else contextlib.nullcontext()):
                                 rendered = ops.render_gaussians(m.pos, m.f_dc, m.f_rest, m.opacity_raw, m.scale_raw, m.q_raw, c2w,
-                                                                int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']))
+                                                                int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']),
+                                                                **degree_kw)
                             loss, vals = losses.compute_loss_device(rendered, image_gt, c.lambda_l1, c.lambda_ssim, scale=1.0 / n_global)
                             loss.backward()                            # (loss / batch size: the division is inside the loss kernels)
                             per_view.append(vals)
@@ -285,4 +301,4 @@ class Trainer:
         if iteration % c.opacity_reset_interval == 0:
             m.reset_opacity()
         return {'loss': acc[2], 'l1': acc[0], 'ssim': acc[1], 'gaussians': m.get_num_gaussians(), 'lr_pos': pos_lr,
-                'densified': densified}
+                'densified': densified, 'sh_degree': sh_degree}

@@ -168,6 +168,14 @@ int gsplat_bin_state_layout(int64_t pair_capacity, const gsplat_view* v, gsplat_
 #define GSPLAT_PROJECT_COUNTS_MAPPED 2
 #define GSPLAT_PROJECT_SAVE_SH_JACOBIAN 4
 #define GSPLAT_PROJECT_COUNTS_LATE 8
+/* The SH degree of a fused render, 0..3 (bits 4-5 hold the bands dropped, 3 - degree, so flags without them mean degree 3, as
+ * before there was a degree): the colour is sigmoid(sum_{k < (d+1)^2} f_k Y_k).  f_rest stays [n,45] channel-major; the ACTIVE
+ * entries of a row are the columns ch * 15 + j with j < (d+1)^2 - 1 (0, 3, 8 or 15 per channel).  Inactive entries are ignored:
+ * their values, NaN included, change no output bit, and the image equals the degree-3 image of the same scene with zeros there.
+ * Degree 0 does not read f_rest at all.  A degree below 3 with un-fused inputs (color + sigma) is GSPLAT_ERR_BAD_ARG.  Every
+ * backward call on the state must be given the SAME degree (GSPLAT_BACKWARD_SH_DEGREE): the saved SH Jacobian holds the active
+ * bands only.  gsplat_forward_deferred takes the degree in the same bits of ITS flags (GSPLAT_FRAME_SH_DEGREE).              */
+#define GSPLAT_PROJECT_SH_DEGREE(d) ((3 - (d)) << 4)
 int gsplat_project(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, void* project_state,
                    void* scratch, int64_t scratch_bytes, gsplat_counts* counts_host, void* counts_event, int32_t flags,
                    void* stream);
@@ -251,6 +259,13 @@ int gsplat_rasterize_backward_aux(int64_t n, int64_t pair_capacity, const gsplat
  *                  Also GSPLAT_BACKWARD_ACCUMULATE (below); any other bit is refused with GSPLAT_ERR_BAD_ARG.             */
 #define GSPLAT_BACKWARD_SH_JACOBIAN 1
 #define GSPLAT_BACKWARD_DEPTH 64
+/* The SH degree of the forward call that filled project_state / the frame (bits 8-9 hold 3 - degree; without them: degree 3).
+ * It MUST be that call's degree, in every backward entry: gsplat_project_backward[_pose], gsplat_backward,
+ * gsplat_backward_adam_rest.  The gradient of every inactive f_rest entry is then an exact zero (every row is still written;
+ * with GSPLAT_BACKWARD_ACCUMULATE at degree 0 the f_rest gradient is not touched), d colour / d pos carries the active bands only,
+ * and the in-place step of gsplat_backward_adam_rest steps the inactive entries with a zero gradient, as gsplat_adam_step would.
+ * A degree below 3 with un-fused inputs is GSPLAT_ERR_BAD_ARG (the text names the entry).                                     */
+#define GSPLAT_BACKWARD_SH_DEGREE(d) ((3 - (d)) << 8)
 int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v,
                             const void* project_state, const float* grad2d, const gsplat_gaussian_grads* out,
                             int32_t flags, void* stream);
@@ -292,6 +307,7 @@ int gsplat_project_backward_pose(const gsplat_gaussians* g, const float* c2w, co
  *                 included: a depth / opacity frame takes the separate calls.                                               */
 #define GSPLAT_FRAME_BACKWARD 1
 #define GSPLAT_FRAME_NO_SH_JACOBIAN 2
+#define GSPLAT_FRAME_SH_DEGREE(d) ((3 - (d)) << 4)    /* gsplat_forward_deferred: as GSPLAT_PROJECT_SH_DEGREE; not a gsplat_frame_bytes flag */
 #define GSPLAT_BACKWARD_PHASE_RASTER 2
 #define GSPLAT_BACKWARD_PHASE_PROJECT 4
 #define GSPLAT_BACKWARD_GRAD2D_DIRTY 8
@@ -314,6 +330,10 @@ int gsplat_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_vi
  * pos[n,3]; eyes[n_views,3] = camera positions (c2w[:3,3]) on the DEVICE; grad_logit[n_views,n,3].                        */
 int gsplat_sh_accumulate(int64_t n, int32_t n_views, const float* pos, const float* eyes, const float* grad_logit,
                          float scale, float* grad_f_dc, float* grad_f_rest, void* stream);
+/* The same for views rendered at SH degree sh_degree (0..3, else GSPLAT_ERR_BAD_ARG): the inactive columns of grad_f_rest are
+ * written as zeros.  gsplat_sh_accumulate is this with sh_degree = 3.                                                          */
+int gsplat_sh_accumulate_degree(int64_t n, int32_t n_views, const float* pos, const float* eyes, const float* grad_logit,
+                                float scale, float* grad_f_dc, float* grad_f_rest, int32_t sh_degree, void* stream);
 /* The same colour-logit gradients [n,3] straight from gsplat_rasterize_backward's grad2d (and the colours kept in
  * project_state), without waiting for gsplat_project_backward: the exchange of the logit gradients can overlap it.
  * (In the factored form of gsplat_project_backward out->color may then be NULL.)                                      */

@@ -1,0 +1,247 @@
+"""CPU checks of the SH degree: the host build of the per-Gaussian SH code (csrc/gs_math.h through
+csrc/host_math_check.cpp) at degrees 0..3 against the float64 oracle on masked coefficients, and the degree's flag bits in the C ABI.
+
+At degree L the colour is sigmoid(sum_{k < (L+1)^2} f_k Y_k): the float64 reference is oracle.torch_port.sh_colour on f_rest with the
+inactive columns (ch * 15 + j, j >= (L+1)^2 - 1) multiplied by zero.
+
+Tolerances are those test_product_math_cpu.py holds the same functions to at degree 3 (colour 1e-6 absolute; gradients rel-L2 and
+max/max 1e-5, position gradients max/max 2e-5): a chain of at most 16 fp32 fma and one sigmoid is good for a few 1e-7, and a chain cut
+short rounds less often, not more.
+"""
+import ctypes as C
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import torch_port as tp
+from tests import util
+
+abi = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd._abi")
+ops = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd.ops")
+CSRC = os.path.join(os.path.dirname(abi.__file__), "csrc")
+DEGREES = (0, 1, 2, 3)
+
+
+@pytest.fixture(scope="module")
+def hm():
+    if os.environ.get("GSPLAT_HOSTMATH_LIB"):
+        return C.CDLL(os.environ["GSPLAT_HOSTMATH_LIB"])
+    so = os.path.join(CSRC, "libgsmath_host.so")
+    srcs = [os.path.join(CSRC, f) for f in ("host_math_check.cpp", "gs_math.h", "gs_body.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, srcs[0]])
+    return C.CDLL(so)
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def inactive_columns(degree):
+    """Boolean [45]: the f_rest columns a render at `degree` ignores."""
+    active = (degree + 1) ** 2 - 1
+    return np.tile(np.arange(15) >= active, 3)
+
+
+@pytest.fixture(scope="module")
+def scene():
+    """The SH inputs of g1_generic (600 Gaussians) and a fixed upstream gradient of the colour."""
+    d = util.load("g1_generic")
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)
+    s = dict(f_dc=f32(d["f_dc"]), f_rest=f32(d["f_rest"]), pos=f32(d["pos"]), c2w=f32(d["c2w"]))
+    s["w"] = f32(np.random.default_rng(5).uniform(-1, 1, (len(s["pos"]), 3)))
+    assert np.abs(s["f_rest"]).max() > 0.1            # (the higher bands of this scene do colour it)
+    return s
+
+
+def _reference(s, degree):
+    """float64: colour, d colour / d pos [n, 3, 3], and the gradients of sum(w * colour)."""
+    t = {k: torch.tensor(s[k], dtype=torch.float64) for k in ("f_dc", "f_rest", "pos", "c2w")}
+    mask = torch.tensor(~inactive_columns(degree), dtype=torch.float64)
+    for k in ("f_dc", "f_rest", "pos"):
+        t[k].requires_grad_(True)
+    col = tp.sh_colour(t["f_dc"], t["f_rest"] * mask, t["pos"], t["c2w"])
+    jac = torch.stack([torch.autograd.grad(col[:, ch].sum(), t["pos"], retain_graph=True)[0] for ch in range(3)], 1)
+    g = torch.autograd.grad((col * torch.tensor(s["w"], dtype=torch.float64)).sum(), [t["f_dc"], t["f_rest"], t["pos"]])
+    return col.detach().numpy(), jac.numpy(), [x.numpy() for x in g]
+
+
+def _colour(hm, s, degree, f_rest=None):
+    n = len(s["pos"])
+    col, kj = np.zeros((n, 3), np.float32), np.zeros((n, 12), np.float32)
+    rc = hm.hm_sh_colour_degree(C.c_int64(n), _ptr(s["f_dc"]), _ptr(s["f_rest"] if f_rest is None else f_rest), _ptr(s["pos"]), _ptr(s["c2w"]),
+                                C.c_int32(degree), _ptr(col), _ptr(kj))
+    assert rc == 0
+    return col, kj
+
+
+def _backward(hm, s, degree, from_jac, f_rest=None):
+    n = len(s["pos"])
+    g_dc, g_rest, g_pos = np.full((n, 3), 7, np.float32), np.full((n, 45), 7, np.float32), np.full((n, 3), 7, np.float32)
+    rc = hm.hm_sh_backward_degree(C.c_int64(n), _ptr(s["f_dc"]), _ptr(s["f_rest"] if f_rest is None else f_rest), _ptr(s["pos"]), _ptr(s["c2w"]),
+                                  _ptr(s["w"]), C.c_int32(degree), C.c_int32(from_jac), _ptr(g_dc), _ptr(g_rest), _ptr(g_pos))
+    assert rc == 0
+    return g_dc, g_rest, g_pos
+
+
+@pytest.mark.parametrize("degree", DEGREES)
+def test_host_math_at_a_degree_matches_the_oracle_on_masked_coefficients(hm, scene, degree):
+    ref_col, ref_jac, (ref_dc, ref_rest, ref_pos) = _reference(scene, degree)
+    col, kj = _colour(hm, scene, degree)
+    assert np.abs(col - ref_col).max() < 1e-6
+    # the saved Jacobian: d colour_ch / d pos_m = KJ[ch] * KJ[3 + 3 ch + m] -- the active bands only
+    jac = kj[:, :3, None] * kj[:, 3:].reshape(-1, 3, 3)
+    util.check_grad(jac, ref_jac, "d colour / d pos (KJ)", l2=1e-5, mx=2e-5)
+    if degree == 0:
+        assert np.abs(jac).max() == 0                    # (the constant band has no direction)
+    inactive = inactive_columns(degree)
+    for from_jac in (0, 1):
+        g_dc, g_rest, g_pos = _backward(hm, scene, degree, from_jac)
+        util.check_grad(g_dc, ref_dc, "f_dc", l2=1e-5, mx=1e-5)
+        util.check_grad(g_rest, ref_rest, "f_rest", l2=1e-5, mx=1e-5)
+        util.check_grad(g_pos, ref_pos, "pos", l2=1e-5, mx=2e-5)
+        assert np.all(g_rest[:, inactive] == 0), "the gradient of an inactive coefficient is an exact zero"
+        if degree > 0:
+            assert np.abs(g_rest[:, ~inactive]).max() > 1e-2
+
+
+def test_degree_three_is_evaluate_sh_bit_for_bit(hm, scene):
+    n = len(scene["pos"])
+    col, _ = _colour(hm, scene, 3)
+    ref = np.zeros((n, 3), np.float32)
+    hm.hm_evaluate_sh(C.c_int64(n), _ptr(scene["f_dc"]), _ptr(scene["f_rest"]), _ptr(scene["pos"]), _ptr(scene["c2w"]), _ptr(ref))
+    assert np.array_equal(col.view(np.uint32), ref.view(np.uint32))
+    g = _backward(hm, scene, 3, 0)
+    r = [np.zeros((n, 3), np.float32), np.zeros((n, 45), np.float32), np.zeros((n, 3), np.float32)]
+    hm.hm_evaluate_sh_backward(C.c_int64(n), _ptr(scene["f_dc"]), _ptr(scene["f_rest"]), _ptr(scene["pos"]), _ptr(scene["c2w"]), _ptr(scene["w"]),
+                               *map(_ptr, r))
+    for a, b in zip(g, r):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+@pytest.mark.parametrize("degree", (0, 1, 2))
+def test_nan_in_every_inactive_slot_changes_no_bit(hm, scene, degree):
+    """Inactive coefficients are ignored, not multiplied by zero: the same bits with NaN there as with zeros there -- which in turn
+    are the colour bits of the full degree-3 chain over those zeros."""
+    inactive = inactive_columns(degree)
+    zeros, nans = scene["f_rest"].copy(), scene["f_rest"].copy()
+    zeros[:, inactive] = 0.0
+    nans[:, inactive] = np.nan
+    cz, kz = _colour(hm, scene, degree, zeros)
+    cn, kn = _colour(hm, scene, degree, nans)
+    assert np.array_equal(cz.view(np.uint32), cn.view(np.uint32)) and np.array_equal(kz.view(np.uint32), kn.view(np.uint32))
+    full, _ = _colour(hm, scene, 3, zeros)
+    assert np.array_equal(cz, full), "a chain cut at the degree has the value of the full chain over zeroed coefficients"
+    for from_jac in (0, 1):
+        for a, b in zip(_backward(hm, scene, degree, from_jac, zeros), _backward(hm, scene, degree, from_jac, nans)):
+            assert np.isfinite(b).all() and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def test_host_math_refuses_a_degree_outside_0_to_3(hm, scene):
+    n = len(scene["pos"])
+    col, kj = np.full((n, 3), 7, np.float32), np.full((n, 12), 7, np.float32)
+    for bad in (-1, 4):
+        assert hm.hm_sh_colour_degree(C.c_int64(n), _ptr(scene["f_dc"]), _ptr(scene["f_rest"]), _ptr(scene["pos"]), _ptr(scene["c2w"]),
+                                      C.c_int32(bad), _ptr(col), _ptr(kj)) == 1
+    assert np.all(col == 7) and np.all(kj == 7)
+
+
+# ---- the C ABI -----------------------------------------------------------------------------------------------------------
+
+def _macros():
+    """The three function-like degree macros of the header, evaluated by the C compiler for d = 0..3."""
+    import re
+    txt = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "gsplat_mi355x.h")).read()
+    found = dict(re.findall(r"^#define\s+(GSPLAT_[A-Z]+_SH_DEGREE)\(d\)\s+(\(\(3 - \(d\)\) << \d+\))", txt, flags=re.M))
+    return {name: [eval(body.replace("(d)", f"({d})")) for d in range(4)] for name, body in found.items()}
+
+
+def test_degree_macros_and_their_python_mirrors_agree():
+    m = _macros()
+    assert sorted(m) == ["GSPLAT_BACKWARD_SH_DEGREE", "GSPLAT_FRAME_SH_DEGREE", "GSPLAT_PROJECT_SH_DEGREE"]
+    for name, vals in m.items():
+        assert vals == [getattr(abi, name)(d) for d in range(4)], name
+        assert vals[3] == 0, "flags without the bits mean degree 3"
+    assert m["GSPLAT_PROJECT_SH_DEGREE"] == [3 << 4, 2 << 4, 1 << 4, 0] == m["GSPLAT_FRAME_SH_DEGREE"]       # bits 4-5: bands dropped
+    assert m["GSPLAT_BACKWARD_SH_DEGREE"] == [3 << 8, 2 << 8, 1 << 8, 0]                                      # bits 8-9
+    assert abi.ABI_VERSION == 12 and abi.lib().gsplat_abi_version() == 12
+    for bad in (4, -1, 1.5, True, None):
+        with pytest.raises(ValueError):
+            abi.GSPLAT_PROJECT_SH_DEGREE(bad)
+
+
+def _unfused():
+    """Un-fused Gaussians (color + sigma; host memory that is never followed).  Every other pointer of the calls below is NULL: the
+    degree is refused from host arguments alone, and a library that did not refuse it would stop at the NULL checks."""
+    buf = np.zeros(64, np.float32)
+    p = C.c_void_p(buf.ctypes.data - buf.ctypes.data % 16 + 16)
+    return buf, abi.Gaussians(1, p, p, p, p, None, None, None, None)
+
+
+def test_dropped_bands_with_unfused_inputs_are_refused_with_the_entrys_name():
+    lib = abi.lib()
+    keep, g = _unfused()
+    v = abi.make_view(64, 64, 50.0, 50.0, 32.0, 32.0)
+    group = abi.AdamGroup()
+    fwd, bwd = abi.GSPLAT_PROJECT_SH_DEGREE(1), abi.GSPLAT_BACKWARD_SH_DEGREE(1)
+    calls = {
+        "gsplat_project": lambda f: lib.gsplat_project(C.byref(g), None, C.byref(v), None, None, 0, None, None, f, None),
+        "gsplat_forward_deferred": lambda f: lib.gsplat_forward_deferred(C.byref(g), None, C.byref(v), None, 0, 1, None, 0, None, 0, None, None, None, f, None),
+        "gsplat_project_backward": lambda f: lib.gsplat_project_backward(C.byref(g), None, C.byref(v), None, None, None, f, None),
+        "gsplat_project_backward_pose": lambda f: lib.gsplat_project_backward_pose(C.byref(g), None, C.byref(v), None, None, None, None, None, 0, f, None),
+        "gsplat_backward": lambda f: lib.gsplat_backward(C.byref(g), None, C.byref(v), None, 0, 1, None, None, None, None, 0, f, None),
+        "gsplat_backward_adam_rest": lambda f: lib.gsplat_backward_adam_rest(C.byref(g), None, C.byref(v), None, 0, 1, None, None, None, 0, f,
+                                                                             C.byref(group), 0.9, 0.999, 1e-15, None),
+    }
+    for name, call in calls.items():
+        flags = fwd if name in ("gsplat_project", "gsplat_forward_deferred") else bwd
+        assert call(flags) == abi.GSPLAT_ERR_BAD_ARG, name
+        msg = lib.gsplat_last_error().decode()
+        assert name + ":" in msg and "SH degree" in msg, (name, msg)
+
+
+def test_bit_five_is_still_unknown_to_every_backward_entry_and_the_degree_bits_are_not():
+    lib = abi.lib()
+    v = abi.make_view(64, 64, 50.0, 50.0, 32.0, 32.0)
+    group = abi.AdamGroup()
+    for flags, known in ((1 << 5, False), (abi.GSPLAT_BACKWARD_SH_DEGREE(0), True), (abi.GSPLAT_BACKWARD_SH_DEGREE(2), True), (1 << 10, False)):
+        rcs = [lib.gsplat_backward(None, None, C.byref(v), None, 0, 0, None, None, None, None, 0, flags, None)]
+        texts = [lib.gsplat_last_error()]
+        rcs.append(lib.gsplat_backward_adam_rest(None, None, C.byref(v), None, 0, 0, None, None, None, 0, flags, C.byref(group), 0.9, 0.999, 1e-15, None))
+        texts.append(lib.gsplat_last_error())
+        rcs.append(lib.gsplat_project_backward(None, None, C.byref(v), None, None, None, flags, None))
+        texts.append(lib.gsplat_last_error())
+        rcs.append(lib.gsplat_project_backward_pose(None, None, C.byref(v), None, None, None, None, None, 0, flags, None))
+        texts.append(lib.gsplat_last_error())
+        assert rcs == [abi.GSPLAT_ERR_BAD_ARG] * 4           # (NULL arguments: a known flag gets as far as the argument checks)
+        assert all((b"unknown flag" in t) != known for t in texts), (flags, texts)
+
+
+def test_sh_accumulate_degree_refuses_a_degree_outside_0_to_3():
+    lib = abi.lib()
+    for bad in (-1, 4):
+        assert lib.gsplat_sh_accumulate_degree(0, 0, None, None, None, 1.0, None, None, bad, None) == abi.GSPLAT_ERR_BAD_ARG
+        assert b"gsplat_sh_accumulate_degree" in lib.gsplat_last_error()
+    for ok in DEGREES:                                        # (n = 0: nothing is launched)
+        assert lib.gsplat_sh_accumulate_degree(0, 0, None, None, None, 1.0, None, None, ok, None) == abi.GSPLAT_OK
+    assert lib.gsplat_sh_accumulate(0, 0, None, None, None, 1.0, None, None, None) == abi.GSPLAT_OK
+
+
+@pytest.mark.parametrize("bad", (4, -1, 1.5))
+def test_render_entries_refuse_a_bad_degree_before_anything_else(bad):
+    """ValueError comes first: before the "no CPU fallback" error of CPU tensors, so before anything could be queued."""
+    n = 5
+    t = [torch.zeros(n, 3), torch.zeros(n, 3), torch.zeros(n, 45), torch.zeros(n), torch.zeros(n, 3), torch.zeros(n, 4)]
+    cam = (torch.eye(4), 8, 8, 4.0, 4.0, 4.0, 4.0)
+    with pytest.raises(ValueError, match="sh_degree"):
+        ops.render_gaussians(*t, *cam, sh_degree=bad)
+    with pytest.raises(ValueError, match="sh_degree"):
+        ops.render_frames(*t, [torch.eye(4)], *cam[1:], sh_degree=bad)
+    with pytest.raises(ValueError, match="sh_degree"):
+        ops.sh_accumulate(torch.zeros(n, 3), torch.zeros(1, 3), torch.zeros(1, n, 3), sh_degree=bad)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):          # a good degree on CPU tensors gets as far as that
+        ops.render_gaussians(*t, *cam, sh_degree=1)

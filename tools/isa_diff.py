@@ -2,7 +2,9 @@
 """Do two gfx950 code objects hold the same kernels, instruction for instruction?  The proof a kernel refactor needs.
     python tools/isa_diff.py A.out B.out        (the ...-gfx950.out files `hipcc --save-temps=obj` leaves)
 Disassembles both, drops what follows `//` on every line (addresses, encodings) and compares the text per kernel symbol.
-Prints the kernels that differ or exist on one side only; exit status 1 if there are any."""
+Prints the kernels that differ or exist on one side only; exit status 1 if there are any.
+A kernel whose SYMBOL changed (a template that gained a defaulted parameter gets another mangled name) is paired with the kernel of
+the other side that has the same instructions and reported as "renamed, same instructions": that is no difference."""
 import re
 import subprocess
 import sys
@@ -24,7 +26,21 @@ def kernels(path):
 
 a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
 bad = 0
+# symbols of one side only: pair those of A with those of B that hold the same instructions (each B symbol at most once)
+lonely_b = {}
+for name in sorted(set(b) - set(a)):
+    lonely_b.setdefault(tuple(b[name]), []).append(name)
+renamed = {}
+for name in sorted(set(a) - set(b)):
+    twins = lonely_b.get(tuple(a[name]))
+    if twins:
+        renamed[name] = twins.pop(0)
 for name in sorted(set(a) | set(b)):
+    if name in renamed:
+        print(f"renamed, same instructions: {name} -> {renamed[name]}")
+        continue
+    if name in renamed.values():
+        continue
     if name not in a or name not in b:
         print(f"only in {'A' if name in a else 'B'}: {name}")
     elif a[name] != b[name]:
