@@ -51,6 +51,37 @@ def GSPLAT_BACKWARD_SH_DEGREE(d):
     return sh_bands_dropped(d) << 8
 
 
+# the screen-space low-pass, in the same bits of the flags of the six entries that run the projection math
+GSPLAT_FILTER_ANTIALIAS = 65536
+
+
+def GSPLAT_FILTER_LOWPASS(c):
+    return c << 17
+
+
+def filter_bits(lowpass=0.0, antialias=False):
+    """The GSPLAT_FILTER_* bits of a render's (lowpass, antialias), 0 for the default; ValueError for anything the kernels cannot do:
+    lowpass off the 0.01 grid or outside [0, 2.55], an antialias that is not a bool, antialias without a low-pass."""
+    if type(antialias) is not bool:
+        raise ValueError(f"antialias must be a bool, not {antialias!r}")
+    try:
+        x = float(lowpass) * 100.0
+        c = round(x)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"lowpass must be a multiple of 0.01 in [0, 2.55], not {lowpass!r}") from None
+    if isinstance(lowpass, bool) or not abs(x - c) <= 1e-6 or not 0 <= c <= 255:
+        raise ValueError(f"lowpass must be a multiple of 0.01 in [0, 2.55], not {lowpass!r}")
+    if antialias and c == 0:
+        raise ValueError("antialias=True needs lowpass > 0")
+    return GSPLAT_FILTER_LOWPASS(c) | (GSPLAT_FILTER_ANTIALIAS if antialias else 0)
+
+
+def filter_kwargs(lowpass=0.0, antialias=False):
+    """The keyword arguments that carry a filter mode to the render entries: none for the default, so the default call stays the
+    reference's (validated as filter_bits does)."""
+    return dict(lowpass=lowpass, antialias=antialias) if filter_bits(lowpass, antialias) else {}
+
+
 _F = C.POINTER(C.c_float)
 
 

@@ -34,7 +34,9 @@ struct Records {
     uint32_t* ref_tiles;   // nullable
 };
 
-GS_HD ViewK make_viewk(const gsplat_view& v) {
+// filter: the GSPLAT_FILTER_* bits of the entry's flags (0: no low-pass; the FILTER variants of the bodies are then not selected).
+GS_HD int filter_hundredths(int32_t filter) { return (int)(((uint32_t)filter >> 17) & 255u); }
+GS_HD ViewK make_viewk(const gsplat_view& v, int32_t filter = 0) {
     ViewK k;
     k.fx = v.fx; k.fy = v.fy; k.cx = v.cx; k.cy = v.cy;
     k.near_z = v.near_z; k.far_z = v.far_z;
@@ -49,6 +51,8 @@ GS_HD ViewK make_viewk(const gsplat_view& v) {
     k.H = v.H; k.W = v.W; k.tile = v.tile;
     k.tiles_x = (v.W + v.tile - 1) / v.tile; k.tiles_y = (v.H + v.tile - 1) / v.tile;
     k.lists_x = (v.W + LIST_W - 1) / LIST_W; k.lists_y = (v.H + LIST_H - 1) / LIST_H;
+    k.lowpass = (float)((double)filter_hundredths(filter) * 0.01);          // rounded once, like chi_pad
+    k.antialias = (filter & GSPLAT_FILTER_ANTIALIAS) ? 1 : 0;
     return k;
 }
 
@@ -101,13 +105,15 @@ struct GradOut {            // what K8 stores for one Gaussian
 };
 
 // K1 core, part 1: everything except the colour.
+// FILTER: the low-pass variant of the projection (gs_math.h project_gaussian).
+template <bool FILTER = false>
 GS_HD Proj project_geometry(const GaussIn& in, bool fused, const Camera& cam, const ViewK& vk) {
     float S[6];
     CovMid cm;
     if (fused) cov_from_params(in.sr, in.qr, S, cm);
     else load_cov6(in.S9, S);
     Proj o; ProjMid m;
-    project_gaussian(in.p, S, in.o_raw, cam, vk, o, m, fused ? &cm : nullptr);
+    project_gaussian<FILTER>(in.p, S, in.o_raw, cam, vk, o, m, fused ? &cm : nullptr);
     return o;
 }
 
@@ -154,9 +160,9 @@ GS_HD RecOut project_finish(const GaussIn& in, const Proj& o, bool fused, Coef c
     return r;
 }
 
-template <class Coef>
+template <bool FILTER = false, class Coef>
 GS_HD RecOut project_core(const GaussIn& in, bool fused, Coef coef, const Camera& cam, const ViewK& vk) {
-    return project_finish(in, project_geometry(in, fused, cam, vk), fused, coef, cam);
+    return project_finish(in, project_geometry<FILTER>(in, fused, cam, vk), fused, coef, cam);
 }
 
 // K8 core.  r9 = (g_u, g_v, g_A11, g_A12, g_A22, g_opacity, g_r, g_g, g_b) of a visible Gaussian.
@@ -170,7 +176,8 @@ GS_HD RecOut project_core(const GaussIn& in, bool fused, Coef coef, const Camera
 // POSE: g_W receives this Gaussian's dL/dW (gs_math.h pose_grad_w; zeros for a Gaussian that is not visible).
 // DEPTH: g_z = dL/d(camera depth) of this Gaussian (column 9 of grad2d behind the depth / opacity raster backward).
 // NB: the active SH bases of the forward that this is the backward of; emit_sh receives exact zeros for k >= NB.
-template <bool POSE = false, bool DEPTH = false, int NB = 16, class Coef, class Emit>
+// FILTER: the forward ran the low-pass variant (vk carries the same s and antialias switch).
+template <bool POSE = false, bool DEPTH = false, int NB = 16, bool FILTER = false, class Coef, class Emit>
 GS_HD GradOut project_backward_core(const GaussIn& in, bool fused, Coef coef, Emit emit_sh, const Camera& cam, const ViewK& vk,
                                     bool vis, const float r9[9], bool moments = false, const float* kj = nullptr,
                                     float* g_W = nullptr, float g_z = 0.f) {
@@ -185,7 +192,7 @@ GS_HD GradOut project_backward_core(const GaussIn& in, bool fused, Coef coef, Em
         if (fused) cov_from_params(in.sr, in.qr, S, cm);
         else load_cov6(in.S9, S);
         Proj o; ProjMid m;
-        project_gaussian(in.p, S, in.o_raw, cam, vk, o, m, fused ? &cm : nullptr);
+        project_gaussian<FILTER>(in.p, S, in.o_raw, cam, vk, o, m, fused ? &cm : nullptr);
         float gu = r9[0], gv = r9[1], ga = r9[2], gb = r9[3], gc = r9[4];
         if (moments) {
             gu = o.opacity * (o.A11 * r9[0] + o.A12 * r9[1]);
@@ -194,9 +201,9 @@ GS_HD GradOut project_backward_core(const GaussIn& in, bool fused, Coef coef, Em
             gb = -o.opacity * r9[3];
             gc = -0.5f * o.opacity * r9[4];
         }
-        if constexpr (POSE) project_gaussian_backward<true, DEPTH>(m, o, cam, vk, gu, gv, ga, gb, gc, r9[5], g.p, g.S9, g.o_raw, in.p, S, g_W, g_z);
-        else if constexpr (DEPTH) project_gaussian_backward<false, true>(m, o, cam, vk, gu, gv, ga, gb, gc, r9[5], g.p, g.S9, g.o_raw, nullptr, nullptr, nullptr, g_z);
-        else project_gaussian_backward(m, o, cam, vk, gu, gv, ga, gb, gc, r9[5], g.p, g.S9, g.o_raw);
+        if constexpr (POSE) project_gaussian_backward<true, DEPTH, FILTER>(m, o, cam, vk, gu, gv, ga, gb, gc, r9[5], g.p, g.S9, g.o_raw, in.p, S, g_W, g_z);
+        else if constexpr (DEPTH) project_gaussian_backward<false, true, FILTER>(m, o, cam, vk, gu, gv, ga, gb, gc, r9[5], g.p, g.S9, g.o_raw, nullptr, nullptr, nullptr, g_z);
+        else project_gaussian_backward<false, false, FILTER>(m, o, cam, vk, gu, gv, ga, gb, gc, r9[5], g.p, g.S9, g.o_raw);
         g.col[0] = r9[6]; g.col[1] = r9[7]; g.col[2] = r9[8];
         if (fused) {
             cov_from_params_backward(in.qr, cm, g.S9, g.sr, g.qr);
@@ -240,10 +247,10 @@ GS_HD GaussIn load_gauss_global(int64_t i, const gsplat_gaussians& g, bool fused
 }
 
 // Reference-layout wrappers (host unit test; the kernels stage through LDS instead, see gsplat_kernels.hip).
-template <class Coef>
+template <bool FILTER = false, class Coef>
 GS_HD int project_one(int64_t i, const gsplat_gaussians& g, bool fused, Coef coef, const Camera& cam, const ViewK& vk,
                       const Records& out) {
-    const RecOut r = project_core(load_gauss_global(i, g, fused), fused, coef, cam, vk);
+    const RecOut r = project_core<FILTER>(load_gauss_global(i, g, fused), fused, coef, cam, vk);
     if (r.vis == VIS_OK) {
         out.rec[i].r0 = r.r0; out.rec[i].r1 = r.r1; out.rec[i].r2 = r.r2; out.rec[i].pad = r.r3;
         out.rect[i] = r.rect; out.depth[i] = r.r2.w; out.mask[i] = r.mask;
@@ -256,13 +263,13 @@ GS_HD int project_one(int64_t i, const gsplat_gaussians& g, bool fused, Coef coe
 
 // g_W (nullable): this Gaussian's dL/dW; then `out` may be NULL (pose only: no row is written) and the returned GradOut holds the
 // position gradient the pose sum needs.
-template <class Coef, class Emit>
+template <bool FILTER = false, class Coef, class Emit>
 GS_HD GradOut project_backward_one(int64_t i, const gsplat_gaussians& g, bool fused, Coef coef, Emit emit_sh, const Camera& cam,
                                    const ViewK& vk, const uint32_t* tiles, const float* grad2d,
                                    const gsplat_gaussian_grads* out_p, float* g_W = nullptr) {
     const GaussIn in = load_gauss_global(i, g, fused);
-    const GradOut o = g_W ? project_backward_core<true>(in, fused, coef, emit_sh, cam, vk, tiles[i] != 0, grad2d + i * 16, false, nullptr, g_W)
-                          : project_backward_core(in, fused, coef, emit_sh, cam, vk, tiles[i] != 0, grad2d + i * 16);
+    const GradOut o = g_W ? project_backward_core<true, false, 16, FILTER>(in, fused, coef, emit_sh, cam, vk, tiles[i] != 0, grad2d + i * 16, false, nullptr, g_W)
+                          : project_backward_core<false, false, 16, FILTER>(in, fused, coef, emit_sh, cam, vk, tiles[i] != 0, grad2d + i * 16);
     if (!out_p) return o;
     const gsplat_gaussian_grads& out = *out_p;
     out.pos[i * 3 + 0] = o.p[0]; out.pos[i * 3 + 1] = o.p[1]; out.pos[i * 3 + 2] = o.p[2];

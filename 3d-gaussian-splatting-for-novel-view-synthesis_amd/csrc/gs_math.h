@@ -45,6 +45,9 @@ struct ViewK {
                                 // Gaussian (projection, binning, deterministic backward) must see the same float
     int32_t H, W, tiles_x, tiles_y, tile;     // tile = the reference's T (render.py:62): only F10/F11's rectangle and pair count use it
     int32_t lists_x, lists_y;                 // grid of LIST_W x LIST_H-pixel lists: what is actually binned and rasterised
+    float lowpass;                            // s of the screen-space low-pass Sigma + s I (px^2), rounded ONCE on the host from the flags'
+                                              // hundredths; read by the FILTER variants of the projection only
+    int32_t antialias;                        // (FILTER variants) scale the record's opacity by rho = sqrt(det Sigma / det(Sigma + s I))
 };
 
 // A "list" is the depth-ordered set of Gaussians of one 16 x 8-pixel region: the unit one wave64 rasterises.  Fixed:
@@ -334,6 +337,9 @@ struct ProjMid {
     float a2, b2, d2;             // after the eigen clamp (render.py:177-179)
     float det, sdet;              // utils.py:184-185
     float i00, i11;               // inverse diagonal before the min_conis clamp
+    float rho, det0, dets;        // (FILTER) opacity compensation sqrt(det0 / dets); det0 = max(det Sigma, 0), dets = det(Sigma + s I),
+                                  // both before the clamp.  rho = 1 without antialias.  (a, b, d stay the entries of the UNFILTERED Sigma;
+                                  // l1, l2 and everything behind them belong to Sigma + s I)
 };
 
 struct Proj {
@@ -429,6 +435,13 @@ GS_HD uint32_t binned_mask(const Proj& o, const ViewK& vk) {
 // formed WITHOUT the cancellation of a d - b^2 (a needle seen along its length: eigenvalues 0.17 and 1200 px^2 lose 4 digits there,
 // and the conic -- its entries are entries of the covariance over the determinant -- with them):
 //   det(J C J^T) = n^T adj(C) n,  n = j0 x j1,  C = Q diag(s^2) Q^T (Q = W R)  =>  det = sum_k (s_i s_j (Q^T n)_k)^2,  a sum of squares.
+// FILTER: the screen-space low-pass of the paper's rasteriser.  The eigen clamp is applied to Sigma + s I (s = vk.lowpass): the same
+// eigenvectors, eigenvalues l_i + s, and everything downstream -- radius, rectangles, conic, tight box, masks -- follows the clamped
+// filtered matrix.  det(Sigma + s I) = det Sigma + s (a + d) + s^2 is a sum of non-negative terms: it takes det_exact's place for the
+// small eigenvalue and for the unclamped conic's determinant.  With vk.antialias the record's opacity is scaled by
+// rho = sqrt(max(det Sigma, 0) / det(Sigma + s I)) (both before the clamp), so a sub-pixel splat keeps its energy; the opacity
+// pre-filter F4 stays on the unscaled value.  (A template flag: the instantiations without it are the code they were.)
+template <bool FILTER = false>
 GS_HD void project_gaussian(const float p[3], const float S[6], float o_raw, const Camera& cam, const ViewK& vk, Proj& o,
                             ProjMid& m, const CovMid* cmid = nullptr) {
     o.vis = VIS_CULLED;
@@ -479,7 +492,9 @@ GS_HD void project_gaussian(const float p[3], const float S[6], float o_raw, con
     m.b = r0y * m.j11 + r0z * m.j12;
     m.d = r1y * m.j11 + r1z * m.j12;
     // F8 eigenvalues of the symmetric 2x2, clamp to [1e-6, 1e4], recomposition
-    const float mid = 0.5f * (m.a + m.d);
+    [[maybe_unused]] const float ls = FILTER ? vk.lowpass : 0.f;             // (read by the FILTER branches only)
+    float mid = 0.5f * (m.a + m.d);
+    if constexpr (FILTER) mid += ls;
     m.diff = 0.5f * (m.a - m.d);
     m.rad = sqrtf(m.diff * m.diff + m.b * m.b);
     m.l1 = mid + m.rad; m.l2 = mid - m.rad;
@@ -492,15 +507,27 @@ GS_HD void project_gaussian(const float p[3], const float S[6], float o_raw, con
         const float e1 = cmid->s[0] * cmid->s[2] * (R[1] * t0 + R[4] * t1 + R[7] * t2);
         const float e2 = cmid->s[0] * cmid->s[1] * (R[2] * t0 + R[5] * t1 + R[8] * t2);
         det_exact = e0 * e0 + e1 * e1 + e2 * e2;
+        if constexpr (FILTER) {
+            m.det0 = det_exact;
+            det_exact = det_exact + ls * (m.a + m.d) + ls * ls;                      // det(Sigma + s I): still no cancellation
+        }
         if (m.l1 > 1e-30f && det_exact < 3e38f) m.l2 = det_exact / m.l1;            // the small eigenvalue without mid - rad
         else det_exact = -1.f;
+    }
+    if constexpr (FILTER) {
+        if (det_exact < 0.f) m.det0 = fmaxf(m.a * m.d - m.b * m.b, 0.f);             // un-fused inputs (or no usable sum of squares)
+        m.dets = m.det0 + ls * (m.a + m.d) + ls * ls;
+        m.rho = (vk.antialias && m.dets > 0.f) ? sqrtf(m.det0 / m.dets) : 1.f;
+        if (!(m.rho <= 1.f)) m.rho = 1.f;                                            // (a + d < 0 by rounding, NaN inputs: no compensation)
+        o.opacity *= m.rho;
     }
     m.f1 = clampf_(m.l1, 1e-6f, 1e4f); m.f2 = clampf_(m.l2, 1e-6f, 1e4f);
     m.clamped = (m.f1 != m.l1) || (m.f2 != m.l2);
     float a2, b2, d2;        // (locals, stored once: stores to m inside the branches were merged into a store through a pointer phi,
                              //  which kept a field of m in scratch memory)
     if (!m.clamped) {
-        a2 = m.a; b2 = m.b; d2 = m.d;
+        if constexpr (FILTER) { a2 = m.a + ls; b2 = m.b; d2 = m.d + ls; }
+        else { a2 = m.a; b2 = m.b; d2 = m.d; }
     } else if (m.rad > 0.f) {
         // f(S) = f2 I + k (S - l2 I), k = (f1 - f2) / (l1 - l2); (S - l2 I) computed without cancellation
         const float k = (m.f1 - m.f2) / (2.f * m.rad);
@@ -597,13 +624,18 @@ GS_HD void pose_grad_w(const float g_pc[3], const float dC[9], const float w[9],
 // (A template flag, not a null pointer: the code of the variants without it stays exactly what it was.)
 // DEPTH: the loss also reads the camera depth z_c directly (the rasteriser's depth map: g_z = dL/dz of this Gaussian, the sum S_z of
 // the depth / opacity raster backward); it joins d z_c, so position and pose get it through the chain that is there.
-template <bool POSE = false, bool DEPTH = false>
+// FILTER: the forward was project_gaussian<true>.  The added constant s I changes nothing in dL/d(a, b, d) through the clamp (m.l1, m.l2
+// are the filtered eigenvalues already); the opacity compensation rho = sqrt(det0 / dets) is a function of the UNCLAMPED (a, b, d):
+//   d rho = (rho / 2) (d det0 / det0 - d dets / dets),  d det0 = d da + a dd - 2 b db,  d dets = d det0 + s (da + dd),
+// added behind the Daleckii-Krein block with dL/d rho = g_opacity clamp(sigmoid); the opacity's own gradient gets the factor rho.
+template <bool POSE = false, bool DEPTH = false, bool FILTER = false>
 GS_HD void project_gaussian_backward(const ProjMid& m, const Proj& o, const Camera& cam, const ViewK& vk, float g_u, float g_v,
                                      float g_A11, float g_A12, float g_A22, float g_opacity, float g_p[3], float G_S[9],
                                      float& g_o_raw, const float* p = nullptr, const float* S = nullptr, float* g_W = nullptr,
                                      float g_z = 0.f) {
     // opacity = clamp(sigmoid, 0, 0.999)
     g_o_raw = (m.sg <= 0.999f) ? g_opacity * m.sg * (1.f - m.sg) : 0.f;
+    if constexpr (FILTER) g_o_raw *= m.rho;
     // min_conis clamp (render.py:310-311): gradient passes where the value is >= the bound
     const float g00 = (m.i00 >= vk.min_conis) ? g_A11 : 0.f;
     const float g11 = (m.i11 >= vk.min_conis) ? g_A22 : 0.f;
@@ -635,6 +667,17 @@ GS_HD void project_gaussian_backward(const ProjMid& m, const Proj& o, const Came
         Ga = h11 * cx_ * cx_ - 2.f * h12 * cx_ * sx_ + h22 * sx_ * sx_;
         Gb = h11 * cx_ * sx_ + h12 * (cx_ * cx_ - sx_ * sx_) - h22 * cx_ * sx_;
         Gd = h11 * sx_ * sx_ + 2.f * h12 * cx_ * sx_ + h22 * cx_ * cx_;
+    }
+    if constexpr (FILTER) {
+        // (det0 clamped at 0 or rho capped: no gradient.  d sqrt(x) is unbounded at x = 0: below 1e-30 px^4 -- a splat 1e-15 of a
+        //  pixel wide, which no float32 evaluation resolves -- det0 counts as clamped, so a zero cotangent never meets an infinity)
+        if (vk.antialias && m.det0 > 1e-30f && m.rho < 1.f) {
+            const float g_rho = g_opacity * clampf_(m.sg, 0.f, 0.999f);
+            const float h0 = 0.5f / (m.rho * m.dets), hs = 0.5f * m.rho / m.dets, hd = g_rho * (h0 - hs);      // h0 = rho / (2 det0)
+            Ga += hd * m.d - g_rho * hs * vk.lowpass;
+            Gd += hd * m.a - g_rho * hs * vk.lowpass;
+            Gb -= hd * m.b;                                          // (dL = Ga da + 2 Gb db + Gd dd)
+        }
     }
     // S2 = J C J^T :  dC = J^T G J,  dJ = 2 G J C
     const float* C = m.C;

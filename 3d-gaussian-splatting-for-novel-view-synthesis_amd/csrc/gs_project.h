@@ -76,7 +76,9 @@ __device__ __forceinline__ void stage_geometry(ProjectLds<FUSED>& s, const gspla
 // workgroups can be dispatched.  As a STREAM -- 6 persistent waves per CU, two sets of LDS rows, block k + 1 requested before
 // block k is computed -- 158 us against 96: with 1.5 waves per SIMD the long dependent chains of the geometry math issue at a
 // fraction of the VALU rate; this kernel lives on wave-level parallelism.)
-template <bool FUSED, bool COLOUR, bool JAC = false, bool TOTALS = true, int NB = 16>
+// FILTER: the screen-space low-pass (and, with vk.antialias, the opacity compensation) of gs_math.h project_gaussian<true>; the
+// instantiations without it are the kernels they were.
+template <bool FUSED, bool COLOUR, bool JAC = false, bool TOTALS = true, int NB = 16, bool FILTER = false>
 __global__ __launch_bounds__(64) void project_kernel(gsplat_gaussians g, const float* __restrict__ c2w, Camera* __restrict__ cam_out, ViewK vk,
                                                      Records out, CounterBlock* cb, DevCounts* counts, DevCounts* counts_mapped,
                                                      uint32_t* __restrict__ bin_total, int nb, float* __restrict__ kj_out,
@@ -125,7 +127,7 @@ __global__ __launch_bounds__(64) void project_kernel(gsplat_gaussians g, const f
     o.vis = VIS_CULLED;
     if (i < g.n) {
         if (!DIRECT) in = gauss_from_lds<FUSED>(s, lane);
-        o = project_geometry(in, FUSED, cam, vk);
+        o = project_geometry<FILTER>(in, FUSED, cam, vk);
     }
     if (REST) __syncthreads();                               // the SH coefficients have arrived
     RecOut r;

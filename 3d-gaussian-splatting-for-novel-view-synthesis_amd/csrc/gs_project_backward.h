@@ -29,7 +29,9 @@ namespace {
 // gradient are exact zeros (NB = 4, 9: written into the LDS rows by the emitter, so the rows leave as before).  NB = 1 (degree 0): f_rest
 // is not read, its gradient is not formed and has no LDS -- the rows are stored as zeros (zero_rows), stepped with a zero gradient
 // (ADAM) or left alone (ACC).
-template <bool FUSED, bool JAC = false, bool ADAM = false, bool ACC = false, bool POSE = false, bool DEPTH = false, int NB = 16>
+// FILTER: the state was projected with the low-pass (gs_math.h project_gaussian<true>): the recomputed projection adds the same s, and
+// with vk.antialias the opacity compensation rho joins the covariance gradient and scales the opacity's own.
+template <bool FUSED, bool JAC = false, bool ADAM = false, bool ACC = false, bool POSE = false, bool DEPTH = false, int NB = 16, bool FILTER = false>
 __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g, const Camera* __restrict__ camp, ViewK vk,
                                                               const uint32_t* __restrict__ tiles, const float* __restrict__ grad2d,
                                                               gsplat_gaussian_grads out, bool factored, const float* __restrict__ kj_in,
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
     float gw[9];                                          // (POSE) d L / d W of this lane's Gaussian
     if (vis) {
         if (!DIRECT) in = gauss_from_lds<FUSED>(s, lane);
-        go = project_backward_core<POSE, DEPTH, NB>(in, FUSED, ShCoefLds{dc_rows, s_rest + lane * 45},
+        go = project_backward_core<POSE, DEPTH, NB, FILTER>(in, FUSED, ShCoefLds{dc_rows, s_rest + lane * 45},
                                    ShEmitFor<NB>{dc_rows, s_rest + lane * 45}, cam, vk, true, r9, true, JAC ? kj : nullptr,
                                    POSE ? gw : nullptr, g_z);
     } else {

@@ -19,6 +19,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
+#include <type_traits>
+#include <unordered_map>
 
 #include <hip/hip_runtime.h>
 
@@ -87,14 +90,49 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 
 // What an entry that works on a frame needs, built once (host arithmetic only; after the entry's argument checks).
 struct Ctx { hipStream_t st; ViewK vk; int64_t nl, nb; ProjectState ps; };
-Ctx open_ctx(int64_t n, const gsplat_view* v, const void* project_state, void* stream_) {
+Ctx open_ctx(int64_t n, const gsplat_view* v, const void* project_state, void* stream_, int32_t filter = 0) {
     const int64_t nl = n_lists(v);
-    return Ctx{(hipStream_t)stream_, make_viewk(*v), nl, n_bins(nl), carve_project((void*)project_state, n > 0 ? n : 1, nl)};
+    return Ctx{(hipStream_t)stream_, make_viewk(*v, filter), nl, n_bins(nl), carve_project((void*)project_state, n > 0 ? n : 1, nl)};
 }
 
 // TOTALS = !late (GSPLAT_PROJECT_COUNTS_LATE)
-template <bool FUSED, bool COLOUR, bool JAC, int NB = 16>
-auto project_kernel_for(bool late) { return late ? project_kernel<FUSED, COLOUR, JAC, false, NB> : project_kernel<FUSED, COLOUR, JAC, true, NB>; }
+template <bool FUSED, bool COLOUR, bool JAC, int NB = 16, bool FILTER = false>
+auto project_kernel_for(bool late) { return late ? project_kernel<FUSED, COLOUR, JAC, false, NB, FILTER> : project_kernel<FUSED, COLOUR, JAC, true, NB, FILTER>; }
+
+// The screen-space low-pass travels in the same bits of the flags of the six entries that run the projection math
+// (include/gsplat_mi355x.h: GSPLAT_FILTER_ANTIALIAS, GSPLAT_FILTER_LOWPASS).  Host dispatch from the bits to the FILTER variants:
+// f(std::true_type / std::false_type), like with_sh_bases.
+constexpr int32_t FILTER_BITS = GSPLAT_FILTER_ANTIALIAS | GSPLAT_FILTER_LOWPASS(255);
+template <class F>
+inline auto with_filter(int32_t filter, F f) { return filter ? f(std::true_type{}) : f(std::false_type{}); }
+int check_filter(const char* entry, int32_t flags) {
+    if ((flags & GSPLAT_FILTER_ANTIALIAS) && !(flags & GSPLAT_FILTER_LOWPASS(255)))
+        return fail(GSPLAT_ERR_BAD_ARG, "%s: GSPLAT_FILTER_ANTIALIAS needs a low-pass (GSPLAT_FILTER_LOWPASS(c) with c > 0)", entry);
+    return GSPLAT_OK;
+}
+// Which filter bits was a project_state last projected with?  Kept on the HOST (the state itself is device memory, and a backward call
+// is refused before anything is launched): only filtered states have an entry, so the default path erases from an empty map.  An
+// entry outlives its state until the address is projected again; the table is cleared should it ever hold 65 536 of them.
+std::mutex g_filter_mutex;
+std::unordered_map<const void*, int32_t> g_filter_of;
+void note_filter(const void* project_state, int32_t filter) {
+    std::lock_guard<std::mutex> lock(g_filter_mutex);
+    if (!filter) { if (!g_filter_of.empty()) g_filter_of.erase(project_state); return; }
+    if (g_filter_of.size() >= 65536) g_filter_of.clear();
+    g_filter_of[project_state] = filter;
+}
+int check_filter_of(const char* entry, const void* project_state, int32_t filter) {
+    int32_t was = 0;
+    {
+        std::lock_guard<std::mutex> lock(g_filter_mutex);
+        if (!g_filter_of.empty()) {
+            const auto it = g_filter_of.find(project_state);
+            if (it != g_filter_of.end()) was = it->second;
+        }
+    }
+    if (was != filter) return fail(GSPLAT_ERR_BAD_ARG, "%s: the GSPLAT_FILTER_* bits differ from those the state was projected with", entry);
+    return GSPLAT_OK;
+}
 
 // The SH degree of a fused render travels in two flag bits as "bands dropped" = 3 - degree, so that flags of 0 stay degree 3:
 // bits 4-5 of gsplat_project / gsplat_forward_deferred, bits 8-9 of the backward entries (include/gsplat_mi355x.h).
@@ -117,33 +155,42 @@ constexpr int32_t BACKWARD_FLAGS = GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD
 // K8 for gsplat_project_backward, the composite entries (ar: the in-place f_rest step) and gsplat_project_backward_pose (pose: where
 // the camera-pose gradient goes; `out` may then be NULL = pose only).
 struct PoseOut { float* grad_c2w; void* scratch; int64_t scratch_bytes; };
-// K8 of fused inputs at NB active SH bases -- <FUSED, JAC, ADAM, ACC, POSE, DEPTH, NB>: every fused instantiation there is
-template <int NB>
+// K8 of fused inputs at NB active SH bases -- <FUSED, JAC, ADAM, ACC, POSE, DEPTH, NB, FILTER>: every fused instantiation there is
+template <int NB, bool FILTER = false>
 auto fused_backward_kernel_for(bool adam, bool acc, bool depth, bool pose, bool jac) {
-    return adam    ? project_backward_kernel<true, true, true, false, false, false, NB>
-           : acc   ? project_backward_kernel<true, true, false, true, false, false, NB>
-           : depth ? (pose ? (jac ? project_backward_kernel<true, true, false, false, true, true, NB>
-                                  : project_backward_kernel<true, false, false, false, true, true, NB>)
-                           : (jac ? project_backward_kernel<true, true, false, false, false, true, NB>
-                                  : project_backward_kernel<true, false, false, false, false, true, NB>))
-           : pose  ? (jac ? project_backward_kernel<true, true, false, false, true, false, NB>
-                          : project_backward_kernel<true, false, false, false, true, false, NB>)
-                   : (jac ? project_backward_kernel<true, true, false, false, false, false, NB>
-                          : project_backward_kernel<true, false, false, false, false, false, NB>);
+    return adam    ? project_backward_kernel<true, true, true, false, false, false, NB, FILTER>
+           : acc   ? project_backward_kernel<true, true, false, true, false, false, NB, FILTER>
+           : depth ? (pose ? (jac ? project_backward_kernel<true, true, false, false, true, true, NB, FILTER>
+                                  : project_backward_kernel<true, false, false, false, true, true, NB, FILTER>)
+                           : (jac ? project_backward_kernel<true, true, false, false, false, true, NB, FILTER>
+                                  : project_backward_kernel<true, false, false, false, false, true, NB, FILTER>))
+           : pose  ? (jac ? project_backward_kernel<true, true, false, false, true, false, NB, FILTER>
+                          : project_backward_kernel<true, false, false, false, true, false, NB, FILTER>)
+                   : (jac ? project_backward_kernel<true, true, false, false, false, false, NB, FILTER>
+                          : project_backward_kernel<true, false, false, false, false, false, NB, FILTER>);
+}
+// ... and of un-fused inputs
+template <bool FILTER = false>
+auto unfused_backward_kernel_for(bool depth, bool pose) {
+    return depth ? (pose ? project_backward_kernel<false, false, false, false, true, true, 16, FILTER> : project_backward_kernel<false, false, false, false, false, true, 16, FILTER>)
+                 : (pose ? project_backward_kernel<false, false, false, false, true, false, 16, FILTER> : project_backward_kernel<false, false, false, false, false, false, 16, FILTER>);
 }
 
 // entry: the name of the C ABI entry, for the messages that must carry it
 int project_backward_impl(const char* entry, const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state, const float* grad2d,
                           const gsplat_gaussian_grads* out, int32_t flags, void* stream_, const AdamRest* ar, const PoseOut* pose = nullptr) {
     bool fused = false;
-    int rc = check_gaussians(g, &fused);
+    const int32_t filter = flags & FILTER_BITS;
+    int rc = check_filter(entry, flags);
     if (rc) return rc;
+    if ((rc = check_gaussians(g, &fused))) return rc;
     const int degree = backward_sh_degree(flags);
     if ((rc = check_sh_degree(entry, degree, fused))) return rc;
     if ((rc = check_view(v))) return rc;
     if (pose && !pose->grad_c2w) return fail(GSPLAT_ERR_BAD_ARG, "grad_c2w is NULL");
     if (!c2w || !project_state || !grad2d || (!pose && !out)) return fail(GSPLAT_ERR_BAD_ARG, "NULL argument");
     PoseScratch prs = {nullptr, nullptr, 0, 0};
+    if ((rc = check_filter_of(entry, project_state, filter))) return rc;
     if (pose) {
         prs = carve_pose(pose->scratch, g->n);
         if (!pose->scratch || pose->scratch_bytes < prs.bytes) return fail(GSPLAT_ERR_WORKSPACE, "pose scratch too small (gsplat_pose_scratch_bytes)");
@@ -167,7 +214,7 @@ int project_backward_impl(const char* entry, const gsplat_gaussians* g, const fl
         if (factored && !(out->scale_raw && out->q_raw)) return fail(GSPLAT_ERR_BAD_ARG, "fused grads incomplete");
         if (!fused && !(out->color && out->sigma)) return fail(GSPLAT_ERR_BAD_ARG, "grad color / sigma is NULL");
     }
-    const Ctx c = open_ctx(g->n, v, project_state, stream_);
+    const Ctx c = open_ctx(g->n, v, project_state, stream_, filter);
     if (g->n == 0) {                // (pose only: the other entries have left)
         HIP_TRY(hipMemsetAsync(pose->grad_c2w, 0, 16 * sizeof(float), c.st));
         return GSPLAT_OK;
@@ -176,9 +223,11 @@ int project_backward_impl(const char* entry, const gsplat_gaussians* g, const fl
     if (ar) { a = *ar; a.counts = c.ps.counts; }
     const gsplat_gaussian_grads o = out ? *out : gsplat_gaussian_grads{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // (ar and acc have been checked to come with fused inputs)
-    const auto kernel = fused   ? with_sh_bases(degree, [&](auto nb) { return fused_backward_kernel_for<decltype(nb)::value>(ar != nullptr, acc, depth, pose != nullptr, jac); })
-                        : depth ? (pose ? project_backward_kernel<false, false, false, false, true, true> : project_backward_kernel<false, false, false, false, false, true>)
-                                : (pose ? project_backward_kernel<false, false, false, false, true> : project_backward_kernel<false, false>);
+    const auto kernel = with_filter(filter, [&](auto filt) {
+        constexpr bool FILTER = decltype(filt)::value;
+        return fused ? with_sh_bases(degree, [&](auto nb) { return fused_backward_kernel_for<decltype(nb)::value, FILTER>(ar != nullptr, acc, depth, pose != nullptr, jac); })
+                     : unfused_backward_kernel_for<FILTER>(depth, pose != nullptr);
+    });
     LAUNCH(pose ? "project_backward_kernel<pose>" : "project_backward_kernel", kernel, dim3(blocks64(g->n)), dim3(64), 0, c.st, *g, c.ps.cam, c.vk, c.ps.tiles, grad2d, o, factored,
            jac ? c.ps.kj : nullptr, a, prs.rows);
     if (!pose) return GSPLAT_OK;
@@ -333,15 +382,18 @@ int gsplat_bin_state_layout(int64_t pair_capacity, const gsplat_view* v, gsplat_
 int gsplat_project(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, void* project_state, void* scratch,
                    int64_t scratch_bytes, gsplat_counts* counts_host, void* counts_event, int32_t flags, void* stream_) {
     bool fused = false;
-    int rc = check_gaussians(g, &fused);
+    int rc = check_filter("gsplat_project", flags);
     if (rc) return rc;
+    if ((rc = check_gaussians(g, &fused))) return rc;
     if ((rc = check_sh_degree("gsplat_project", project_sh_degree(flags), fused))) return rc;
+    const int32_t filter = flags & FILTER_BITS;
     if ((rc = check_view(v))) return rc;
     if (!c2w || !project_state) return fail(GSPLAT_ERR_BAD_ARG, "c2w / project_state is NULL");
     if (!scratch || scratch_bytes < (int64_t)sizeof(CounterBlock)) return fail(GSPLAT_ERR_WORKSPACE, "project scratch (counter block) too small");
     if (reinterpret_cast<uintptr_t>(scratch) & 63u) return fail(GSPLAT_ERR_BAD_ARG, "project scratch must be 64-byte aligned");
     const int64_t n = g->n;
-    const auto [st, vk, nl, nb, ps] = open_ctx(n, v, project_state, stream_);
+    const auto [st, vk, nl, nb, ps] = open_ctx(n, v, project_state, stream_, filter);
+    note_filter(project_state, filter);
     const bool mapped = (flags & GSPLAT_PROJECT_COUNTS_MAPPED) != 0;
     const bool colour_inside = !fused || (flags & GSPLAT_PROJECT_COLOUR_FUSED) != 0;
     const bool jac = fused && (flags & GSPLAT_PROJECT_SAVE_SH_JACOBIAN) != 0;
@@ -350,12 +402,15 @@ int gsplat_project(const gsplat_gaussians* g, const float* c2w, const gsplat_vie
     if (n > 0) {
         const Records out{ps.rec, ps.rect, ps.depth, ps.tiles, ps.mask, REF_RECT, REF_TILES};
         DevCounts* cm = mapped ? (DevCounts*)counts_host : nullptr;
-        const auto kernel = !fused          ? project_kernel_for<false, true, false>(late)
-                            : colour_inside ? with_sh_bases(degree, [&](auto nb) {
-                                  constexpr int NB = decltype(nb)::value;
-                                  return jac ? project_kernel_for<true, true, true, NB>(late) : project_kernel_for<true, true, false, NB>(late);
-                              })
-                                            : project_kernel_for<true, false, false>(late);
+        const auto kernel = with_filter(filter, [&](auto filt) {
+            constexpr bool FILTER = decltype(filt)::value;
+            return !fused          ? project_kernel_for<false, true, false, 16, FILTER>(late)
+                   : colour_inside ? with_sh_bases(degree, [&](auto nb) {
+                         constexpr int NB = decltype(nb)::value;
+                         return jac ? project_kernel_for<true, true, true, NB, FILTER>(late) : project_kernel_for<true, true, false, NB, FILTER>(late);
+                     })
+                                   : project_kernel_for<true, false, false, 16, FILTER>(late);
+        });
         LAUNCH("project_kernel", kernel, dim3(blocks64(n)), dim3(64), 0, st, *g, c2w, ps.cam, vk, out, (CounterBlock*)scratch, ps.counts, cm,
                ps.bin_total, (int)nb, colour_inside && jac ? ps.kj : nullptr, ps.big_flag);
         if (counts_host && !mapped && !late) HIP_TRY(hipMemcpyAsync(counts_host, ps.counts, sizeof(gsplat_counts), hipMemcpyDeviceToHost, st));
@@ -488,14 +543,14 @@ int gsplat_rasterize_backward_aux(int64_t n, int64_t n_binned, const gsplat_view
 
 int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state,
                             const float* grad2d, const gsplat_gaussian_grads* out, int32_t flags, void* stream_) {
-    if (flags & ~(PROJECT_BACKWARD_FLAGS | BACKWARD_SH_BITS)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
+    if (flags & ~(PROJECT_BACKWARD_FLAGS | BACKWARD_SH_BITS | FILTER_BITS)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
     return project_backward_impl("gsplat_project_backward", g, c2w, v, project_state, grad2d, out, flags, stream_, nullptr);
 }
 
 int gsplat_project_backward_pose(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state,
                                  const float* grad2d, const gsplat_gaussian_grads* out, float* grad_c2w, void* pose_scratch,
                                  int64_t pose_scratch_bytes, int32_t flags, void* stream_) {
-    if (flags & ~(GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_DEPTH | BACKWARD_SH_BITS)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
+    if (flags & ~(GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_DEPTH | BACKWARD_SH_BITS | FILTER_BITS)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
     const PoseOut pose = {grad_c2w, pose_scratch, pose_scratch_bytes};
     return project_backward_impl("gsplat_project_backward_pose", g, c2w, v, project_state, grad2d, out, flags, stream_, nullptr, &pose);
 }
@@ -504,9 +559,10 @@ int gsplat_project_backward_pose(const gsplat_gaussians* g, const float* c2w, co
 int gsplat_forward_deferred(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, void* frame, int64_t frame_bytes,
                             int64_t pair_capacity, void* counters, int64_t counters_bytes, void* bin_scratch, int64_t bin_scratch_bytes,
                             gsplat_counts* counts_host, void* counts_event, float* image, int32_t flags, void* stream_) {
-    if (!g || !v) return fail(GSPLAT_ERR_BAD_ARG, "gaussians / view is NULL");
-    int rc = check_sh_degree("gsplat_forward_deferred", project_sh_degree(flags), g->scale_raw != nullptr);
+    int rc = check_filter("gsplat_forward_deferred", flags);
     if (rc) return rc;
+    if (!g || !v) return fail(GSPLAT_ERR_BAD_ARG, "gaussians / view is NULL");
+    if ((rc = check_sh_degree("gsplat_forward_deferred", project_sh_degree(flags), g->scale_raw != nullptr))) return rc;
     if ((rc = check_view(v))) return rc;
     if (!frame || !image) return fail(GSPLAT_ERR_BAD_ARG, "frame / image is NULL");
     if (reinterpret_cast<uintptr_t>(frame) & 255u) return fail(GSPLAT_ERR_BAD_ARG, "frame must be 256-byte aligned");
@@ -516,7 +572,7 @@ int gsplat_forward_deferred(const gsplat_gaussians* g, const float* c2w, const g
     char* base = (char*)frame;
     const bool bwd = (flags & GSPLAT_FRAME_BACKWARD) != 0;
     const bool fused = g->scale_raw != nullptr;
-    int32_t pf = GSPLAT_PROJECT_COLOUR_FUSED | GSPLAT_PROJECT_COUNTS_LATE | (counts_host ? GSPLAT_PROJECT_COUNTS_MAPPED : 0) | (flags & PROJECT_SH_BITS);
+    int32_t pf = GSPLAT_PROJECT_COLOUR_FUSED | GSPLAT_PROJECT_COUNTS_LATE | (counts_host ? GSPLAT_PROJECT_COUNTS_MAPPED : 0) | (flags & (PROJECT_SH_BITS | FILTER_BITS));
     if (bwd && fused && !(flags & GSPLAT_FRAME_NO_SH_JACOBIAN)) pf |= GSPLAT_PROJECT_SAVE_SH_JACOBIAN;
     if ((rc = gsplat_project(g, c2w, v, base + f.project_state, counters, counters_bytes, counts_host, counts_event, pf, stream_))) return rc;
     if ((rc = gsplat_bin(g->n, pair_capacity, v, base + f.project_state, base + f.bin_state, bin_scratch, bin_scratch_bytes, stream_))) return rc;
@@ -530,14 +586,16 @@ int gsplat_forward_deferred(const gsplat_gaussians* g, const float* c2w, const g
 static int backward_impl(const char* entry, const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, void* frame, int64_t frame_bytes,
                          int64_t pair_capacity, const float* grad_image, const gsplat_gaussian_grads* out, float* grad_logit,
                          void* det_scratch, int64_t det_scratch_bytes, int32_t flags, void* stream_, const AdamRest* ar) {
-    if (!g || !v) return fail(GSPLAT_ERR_BAD_ARG, "gaussians / view is NULL");
-    int rc = check_sh_degree(entry, backward_sh_degree(flags), g->scale_raw != nullptr);
+    int rc = check_filter(entry, flags);
     if (rc) return rc;
+    if (!g || !v) return fail(GSPLAT_ERR_BAD_ARG, "gaussians / view is NULL");
+    if ((rc = check_sh_degree(entry, backward_sh_degree(flags), g->scale_raw != nullptr))) return rc;
     if ((rc = check_view(v))) return rc;
     if (!frame) return fail(GSPLAT_ERR_BAD_ARG, "frame is NULL");
     const FrameParts f = frame_parts(g->n, pair_capacity, v, GSPLAT_FRAME_BACKWARD);
     if (f.total > frame_bytes) return fail(GSPLAT_ERR_WORKSPACE, "frame arena too small: was it made with GSPLAT_FRAME_BACKWARD?");
     char* base = (char*)frame;
+    if ((rc = check_filter_of(entry, base + f.project_state, flags & FILTER_BITS))) return rc;      // (before the raster phase, too)
     float* grad2d = (float*)(base + f.grad2d);
     const bool both = !(flags & (GSPLAT_BACKWARD_PHASE_RASTER | GSPLAT_BACKWARD_PHASE_PROJECT));
     if (both || (flags & GSPLAT_BACKWARD_PHASE_RASTER)) {
@@ -550,7 +608,7 @@ static int backward_impl(const char* entry, const gsplat_gaussians* g, const flo
     if (both || (flags & GSPLAT_BACKWARD_PHASE_PROJECT)) {
         if (!out) return fail(GSPLAT_ERR_BAD_ARG, "grads is NULL");
         if ((rc = project_backward_impl(entry, g, c2w, v, base + f.project_state, grad2d, out,
-                                        flags & (GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_ACCUMULATE | BACKWARD_SH_BITS), stream_, ar))) return rc;
+                                        flags & (GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_ACCUMULATE | BACKWARD_SH_BITS | FILTER_BITS), stream_, ar))) return rc;
     }
     return GSPLAT_OK;
 }
@@ -558,7 +616,7 @@ static int backward_impl(const char* entry, const gsplat_gaussians* g, const flo
 int gsplat_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, void* frame, int64_t frame_bytes,
                     int64_t pair_capacity, const float* grad_image, const gsplat_gaussian_grads* out, float* grad_logit,
                     void* det_scratch, int64_t det_scratch_bytes, int32_t flags, void* stream_) {
-    if (flags & ~(BACKWARD_FLAGS | BACKWARD_SH_BITS)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
+    if (flags & ~(BACKWARD_FLAGS | BACKWARD_SH_BITS | FILTER_BITS)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
     return backward_impl("gsplat_backward", g, c2w, v, frame, frame_bytes, pair_capacity, grad_image, out, grad_logit, det_scratch, det_scratch_bytes, flags,
                          stream_, nullptr);
 }
@@ -567,7 +625,8 @@ int gsplat_backward_adam_rest(const gsplat_gaussians* g, const float* c2w, const
                               int64_t pair_capacity, const float* grad_image, const gsplat_gaussian_grads* out, void* det_scratch,
                               int64_t det_scratch_bytes, int32_t flags, const gsplat_adam_group* f_rest, float beta1, float beta2, float eps,
                               void* stream_) {
-    if (flags & ~(BACKWARD_FLAGS | BACKWARD_SH_BITS)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
+    if (flags & ~(BACKWARD_FLAGS | BACKWARD_SH_BITS | FILTER_BITS)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
+    if (int rc = check_filter("gsplat_backward_adam_rest", flags)) return rc;
     if (!g || !f_rest) return fail(GSPLAT_ERR_BAD_ARG, "gaussians / f_rest update is NULL");
     if (int rc = check_sh_degree("gsplat_backward_adam_rest", backward_sh_degree(flags), g->scale_raw != nullptr)) return rc;
     if (flags & (GSPLAT_BACKWARD_PHASE_RASTER | GSPLAT_BACKWARD_PHASE_PROJECT)) return fail(GSPLAT_ERR_BAD_ARG, "the in-place step runs the whole backward pass");

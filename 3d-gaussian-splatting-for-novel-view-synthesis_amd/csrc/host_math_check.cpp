@@ -35,6 +35,51 @@ void hm_project_backward(const gsplat_gaussians* g, const float* c2w, const gspl
     }
 }
 
+// The same two with the GSPLAT_FILTER_* bits of `flags` (the screen-space low-pass and the opacity compensation): the FILTER
+// variants of the bodies, as the kernels select them.  flags without those bits: exactly hm_project / hm_project_backward.
+void hm_project_flags(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, int32_t flags, float* rec64, uint32_t* rect,
+                      float* depth, uint32_t* tiles, int32_t* vis, uint32_t* brect, uint32_t* btiles, uint32_t* bmask) {
+    if (!(flags & GSPLAT_FILTER_LOWPASS(255))) return hm_project(g, c2w, v, rec64, rect, depth, tiles, vis, brect, btiles, bmask);
+    Camera cam; build_camera(c2w, cam);
+    const ViewK vk = make_viewk(*v, flags);
+    const bool fused = g->scale_raw != nullptr;
+    Records out{(Rec64*)rec64, (u2*)brect, depth, btiles, bmask, (u2*)rect, tiles};
+    for (int64_t i = 0; i < g->n; ++i) {
+        ShCoefGlobal coef{fused ? g->f_dc + i * 3 : nullptr, fused ? g->f_rest + i * 45 : nullptr};
+        vis[i] = project_one<true>(i, *g, fused, coef, cam, vk, out);
+    }
+}
+
+void hm_project_backward_flags(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, int32_t flags, const uint32_t* tiles,
+                               const float* grad2d, const gsplat_gaussian_grads* out) {
+    if (!(flags & GSPLAT_FILTER_LOWPASS(255))) return hm_project_backward(g, c2w, v, tiles, grad2d, out);
+    Camera cam; build_camera(c2w, cam);
+    const ViewK vk = make_viewk(*v, flags);
+    const bool fused = g->scale_raw != nullptr;
+    for (int64_t i = 0; i < g->n; ++i) {
+        ShCoefGlobal coef{fused ? g->f_dc + i * 3 : nullptr, fused ? g->f_rest + i * 45 : nullptr};
+        ShEmitGlobal emit{fused ? out->f_dc + i * 3 : nullptr, fused ? out->f_rest + i * 45 : nullptr};
+        project_backward_one<true>(i, *g, fused, coef, emit, cam, vk, tiles, grad2d, out);
+    }
+}
+
+// rho[n] of the FILTER projection (1 without GSPLAT_FILTER_ANTIALIAS; 0 for a Gaussian that is not projected): for the needle test
+void hm_filter_rho(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, int32_t flags, float* rho) {
+    Camera cam; build_camera(c2w, cam);
+    const ViewK vk = make_viewk(*v, flags);
+    const bool fused = g->scale_raw != nullptr;
+    for (int64_t i = 0; i < g->n; ++i) {
+        const GaussIn in = load_gauss_global(i, *g, fused);
+        float S[6]; CovMid cm;
+        if (fused) cov_from_params(in.sr, in.qr, S, cm);
+        else load_cov6(in.S9, S);
+        Proj o; ProjMid m;
+        m.rho = 0.f;
+        project_gaussian<true>(in.p, S, in.o_raw, cam, vk, o, m, fused ? &cm : nullptr);
+        rho[i] = o.vis == VIS_CULLED ? 0.f : m.rho;
+    }
+}
+
 namespace {
 struct ShEmitNullable {     // ShEmitGlobal that drops the values when there is no gradient row (pose only)
     float* dc;
@@ -62,6 +107,28 @@ void hm_project_backward_pose(const gsplat_gaussians* g, const float* c2w, const
         for (int k = 0; k < 3; ++k) sp[k] += o.p[k];
     }
     // W = c2w[:3,:3]^T: dL/dc2w[:3,:3] = (dL/dW)^T; dL/dc2w[:3,3] = -sum dL/dp; the last row is constant
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) grad_c2w[r * 4 + c] = (float)sw[c * 3 + r];
+        grad_c2w[r * 4 + 3] = (float)-sp[r];
+    }
+    for (int c = 0; c < 4; ++c) grad_c2w[12 + c] = 0.f;
+}
+
+void hm_project_backward_pose_flags(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, int32_t flags, const uint32_t* tiles,
+                                    const float* grad2d, const gsplat_gaussian_grads* out, float* grad_c2w) {
+    if (!(flags & GSPLAT_FILTER_LOWPASS(255))) return hm_project_backward_pose(g, c2w, v, tiles, grad2d, out, grad_c2w);
+    Camera cam; build_camera(c2w, cam);
+    const ViewK vk = make_viewk(*v, flags);
+    const bool fused = g->scale_raw != nullptr;
+    double sw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, sp[3] = {0, 0, 0};
+    for (int64_t i = 0; i < g->n; ++i) {
+        ShCoefGlobal coef{fused ? g->f_dc + i * 3 : nullptr, fused ? g->f_rest + i * 45 : nullptr};
+        ShEmitNullable emit{fused && out ? out->f_dc + i * 3 : nullptr, fused && out ? out->f_rest + i * 45 : nullptr};
+        float gw[9];
+        const GradOut o = project_backward_one<true>(i, *g, fused, coef, emit, cam, vk, tiles, grad2d, out, gw);
+        for (int k = 0; k < 9; ++k) sw[k] += gw[k];
+        for (int k = 0; k < 3; ++k) sp[k] += o.p[k];
+    }
     for (int r = 0; r < 3; ++r) {
         for (int c = 0; c < 3; ++c) grad_c2w[r * 4 + c] = (float)sw[c * 3 + r];
         grad_c2w[r * 4 + 3] = (float)-sp[r];

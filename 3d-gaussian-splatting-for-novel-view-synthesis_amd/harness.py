@@ -14,7 +14,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import ops
+from . import _abi, ops
 
 PARAM_KEYS = ("pos", "opacity_raw", "f_dc", "f_rest", "scale_raw", "q_raw")
 _FILE_STEM = {"pos": "pos", "opacity_raw": "opacity_raw", "f_dc": "f_dc", "f_rest": "f_rest", "scale_raw": "scale_raw",
@@ -84,13 +84,15 @@ def load_parameters(checkpoint_dir, iteration='final', device="cuda"):
                             f"(looked for {path.name} and {', '.join(f.name for f in loose.values())})")
 
 
-def benchmark_orbit(params, c2ws, H, W, fx, fy, cx, cy, fused=True, on_frame=None, sh_degree=3):
+def benchmark_orbit(params, c2ws, H, W, fx, fy, cx, cy, fused=True, on_frame=None, sh_degree=3, *, lowpass=0.0, antialias=False):
     """Per-frame render times over a trajectory with the reference's protocol: one un-timed warm-up frame, then for each
     frame synchronize -> wall clock -> (SH + render) -> synchronize -> wall clock.  `fused=False` issues the reference's
     own call sequence (evaluate_sh + render with a pre-built sigma, covariance build outside the timed region).
-    sh_degree: as for ops.render_gaussians (fused frames only: the reference's sequence has no degree)."""
+    sh_degree: as for ops.render_gaussians (fused frames only: the reference's sequence has no degree).  lowpass, antialias: the
+    screen-space low-pass and the opacity compensation of ops.render / ops.render_gaussians, for both settings of `fused`."""
     if not fused and sh_degree != 3:
         raise ValueError("sh_degree needs fused=True: evaluate_sh + render is the reference's degree-3 sequence")
+    filter_kw = _abi.filter_kwargs(lowpass, antialias)          # (none for the default: the call stays the reference's)
     dev = params["pos"].device
     kw = dict(pix_guard=32, chi_square_clip=6.25, alpha_cutoff=1 / 128.)
     sigma = None if fused else ops.build_sigma_from_params(params["scale_raw"], params["q_raw"])
@@ -98,9 +100,9 @@ def benchmark_orbit(params, c2ws, H, W, fx, fy, cx, cy, fused=True, on_frame=Non
     def frame(c2w):
         if fused:
             return ops.render_gaussians(params["pos"], params["f_dc"], params["f_rest"], params["opacity_raw"], params["scale_raw"],
-                                        params["q_raw"], c2w, H, W, fx, fy, cx, cy, sh_degree=sh_degree, **kw)
+                                        params["q_raw"], c2w, H, W, fx, fy, cx, cy, sh_degree=sh_degree, **kw, **filter_kw)
         col = ops.evaluate_sh(params["f_dc"], params["f_rest"], params["pos"], c2w)
-        return ops.render(params["pos"], col, params["opacity_raw"], sigma, c2w, H, W, fx, fy, cx, cy, **kw)
+        return ops.render(params["pos"], col, params["opacity_raw"], sigma, c2w, H, W, fx, fy, cx, cy, **kw, **filter_kw)
 
     times = []
     with torch.no_grad():
@@ -123,17 +125,18 @@ def benchmark_orbit(params, c2ws, H, W, fx, fy, cx, cy, fused=True, on_frame=Non
             "fps_min": fps.min(), "fps_max": fps.max(), "times": t}
 
 
-def throughput_orbit(params, c2ws, H, W, fx, fy, cx, cy, on_frame=None, sh_degree=3):
+def throughput_orbit(params, c2ws, H, W, fx, fy, cx, cy, on_frame=None, sh_degree=3, *, lowpass=0.0, antialias=False):
     """Frames per second over a trajectory when frames need not be timed one by one: ops.render_frames pipelines them over
     two streams (frame k + 1's projection / binning overlaps frame k's rasterisation).  Not the reference's protocol
-    (benchmark_orbit is): a serving-style number.  sh_degree: as for ops.render_frames."""
+    (benchmark_orbit is): a serving-style number.  sh_degree, lowpass, antialias: as for ops.render_frames."""
+    filter_kw = _abi.filter_kwargs(lowpass, antialias)
     dev = params["pos"].device
     args = (params["pos"], params["f_dc"], params["f_rest"], params["opacity_raw"], params["scale_raw"], params["q_raw"])
     cams = [torch.as_tensor(np.asarray(c), dtype=torch.float32, device=dev) for c in c2ws]
-    ops.render_frames(*args, cams[:2], H, W, fx, fy, cx, cy, on_frame=lambda k, im: None, sh_degree=sh_degree)       # warm-up
+    ops.render_frames(*args, cams[:2], H, W, fx, fy, cx, cy, on_frame=lambda k, im: None, sh_degree=sh_degree, **filter_kw)       # warm-up
     torch.cuda.synchronize(dev)
     t0 = time.time()
-    ops.render_frames(*args, cams, H, W, fx, fy, cx, cy, on_frame=on_frame or (lambda k, im: None), sh_degree=sh_degree)
+    ops.render_frames(*args, cams, H, W, fx, fy, cx, cy, on_frame=on_frame or (lambda k, im: None), sh_degree=sh_degree, **filter_kw)
     torch.cuda.synchronize(dev)
     dt = time.time() - t0
     return {"frames": len(cams), "seconds": dt, "fps": len(cams) / dt if dt > 0 else float("inf")}

@@ -10,7 +10,9 @@ Mirrors the reference's operator interface (same names, argument meaning, defaul
 
 plus the fused entry `render_gaussians(...)`, which takes the six raw parameter tensors and folds the covariance build
 and the SH evaluation into the projection kernel (the Sigma[N,3,3] and colour[N,3] tensors are never materialised); its
-keyword sh_degree (0..3, default 3) renders with the first (sh_degree + 1)^2 SH bases only.
+keyword sh_degree (0..3, default 3) renders with the first (sh_degree + 1)^2 SH bases only.  Every render entry
+takes the keywords lowpass=0.0, antialias=False: the screen-space low-pass of the paper's rasteriser and the opacity compensation of
+its antialiased variant.
 
 PyTorch is plumbing here (device memory, streams, autograd bookkeeping); all arithmetic runs in the HIP library.
 There is no CPU path: CPU tensors, or a missing library, raise.
@@ -65,9 +67,10 @@ PINNED_SLOTS = 256      # counter blocks in flight per (device, stream) before o
 
 
 def capacity_key(device, view, n):
-    """Pair capacities are kept per (device, image size, power-of-two bucket of the Gaussian count): one large scene does not
-    make every later frame of a small one allocate, launch over and (deterministic mode) clear its buffers."""
-    return (device.type, device.index, view.H, view.W, max(int(n), 1).bit_length())
+    """Pair capacities are kept per (device, image size, power-of-two bucket of the Gaussian count, filter mode): one large scene
+    does not make every later frame of a small one allocate, launch over and (deterministic mode) clear its buffers, and a
+    filtered frame -- the low-pass grows every footprint, and the pair count with it -- learns its own capacity."""
+    return (device.type, device.index, view.H, view.W, max(int(n), 1).bit_length(), getattr(view, "filter", 0))
 
 
 class _Workspace:
@@ -162,7 +165,7 @@ class _Workspace:
         return buf
 
     def frame_sizes(self, lib, n, capacity, view, flags):
-        k = (n, capacity, view.H, view.W, flags)
+        k = (n, capacity, view.H, view.W, flags)                  # (the filter bits change no size)
         got = self.sizes.get(k)
         if got is None:
             if len(self.sizes) > 4096:
@@ -354,7 +357,7 @@ class _Frame:
     (project_state | bin_state | accum | grad2d, carved by the library); one that went through the separate calls keeps them
     as separate buffers."""
     __slots__ = ("view", "n", "n_pairs", "proj_state", "bin_state", "accum", "fused", "inputs", "c2w", "empty", "grad2d", "sh_jacobian",
-                 "arena", "gaussians", "dirty", "src_ptrs", "route", "pose", "aux", "background", "accum_aux", "stats", "sh_degree")
+                 "arena", "gaussians", "dirty", "src_ptrs", "route", "pose", "aux", "background", "accum_aux", "stats", "sh_degree", "filter")
 
 
 class _Pending:
@@ -383,6 +386,8 @@ def _new_frame(fused, view, n, pos32, opa32, c2w32, ins, c, d):
     fr.background = fr.accum_aux = fr.stats = None
     # the SH degree of the forward pass, kept on the frame: every backward route reads it here, so it cannot differ
     fr.sh_degree = view.sh_degree if fused else 3
+    # ... and the GSPLAT_FILTER_* bits (lowpass, antialias): the same bits in the flags of every entry that runs the projection math
+    fr.filter = view.filter
     # the caller's own SH tensors (before any dtype / layout conversion): what dp.FactoredExchange.owns() compares
     fr.src_ptrs = (c.data_ptr(), d.data_ptr()) if fused else None
     return fr
@@ -440,7 +445,7 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
         H, W = view.H, view.W
         flags = (_abi.GSPLAT_FRAME_BACKWARD if need_grad else 0) | (0 if _sh_jacobian else _abi.GSPLAT_FRAME_NO_SH_JACOBIAN)
         frame_bytes, scratch_bytes = _ws.frame_sizes(lib, n, capacity, view, flags)
-        flags |= _FRAME_DEGREE[fr.sh_degree]
+        flags |= _FRAME_DEGREE[fr.sh_degree] | fr.filter
         fr.arena = torch.empty(frame_bytes, dtype=torch.uint8, device=dev)
         image = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
         scratch = _ws.get_scratch(dev, scratch_bytes, key)
@@ -463,7 +468,7 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
     flags = _abi.GSPLAT_PROJECT_COUNTS_MAPPED | ((_abi.GSPLAT_PROJECT_COLOUR_FUSED | _abi.GSPLAT_PROJECT_COUNTS_LATE) if deferred else 0)
     if fr.sh_jacobian:
         flags |= _abi.GSPLAT_PROJECT_SAVE_SH_JACOBIAN
-    flags |= _PROJECT_DEGREE[fr.sh_degree]
+    flags |= _PROJECT_DEGREE[fr.sh_degree] | fr.filter
     with _stage("project"):
         _abi.check(lib.gsplat_project(C.byref(g), _p(c2w32), C.byref(view), _p(fr.proj_state), _p(counters),
                                       counters.numel(), C.c_void_p(pinned.data_ptr()), C.c_void_p(ready.cuda_event),
@@ -733,7 +738,7 @@ def _backward_impl(fr, grad_image, need_params=True, grad_depth=None, grad_alpha
         dst = _flat_like({k: v for k, v in ins.items() if not (factored and k in _SH or folded and k == "f_rest")})
     gg = _abi.GaussianGrads(*map(_p, map(dst.get, _GRAD_FIELDS)))
     # (`jac` goes into the flags of every projection backward below: the saved Jacobian and the degree of the frame's forward pass)
-    jac = (_abi.GSPLAT_BACKWARD_SH_JACOBIAN if fr.sh_jacobian else 0) | _BACKWARD_DEGREE[fr.sh_degree]
+    jac = (_abi.GSPLAT_BACKWARD_SH_JACOBIAN if fr.sh_jacobian else 0) | _BACKWARD_DEGREE[fr.sh_degree] | fr.filter
     if fr.arena is None:                       # ---- the frame went through the separate calls
         zeroed = fr.grad2d is not None
         grad2d = fr.grad2d if zeroed else torch.empty((fr.n, 16), dtype=torch.float32, device=dev)
@@ -977,6 +982,12 @@ def _view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_c
     view.grad_mode = torch.is_grad_enabled()            # Python-side attribute (not part of the C struct)
     view.aux, view.background = False, None             # (likewise: set by _aux_view)
     view.sh_degree = 3                                  # (likewise: set by _degree_view)
+    view.filter = 0                                     # (likewise: the GSPLAT_FILTER_* bits, set by _filter_view)
+    return view
+
+
+def _filter_view(view, bits):
+    view.filter = bits
     return view
 
 
@@ -998,7 +1009,8 @@ def _aux_view(view, aux, background):
 
 
 def render(pos, color, opacity_raw, sigma, c2w, H, W, fx, fy, cx, cy, near=0.01, far=100.0, pix_guard=32, T=16,
-           min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128., *, aux=False, background=None):
+           min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128., *, aux=False, background=None, lowpass=0.0,
+           antialias=False):
     """Drop-in for the reference render() (gaussian_splatting/render.py:62-410).
 
     Returns the image [H, W, 3] in [0, 1], same dtype/device as `pos`, differentiable w.r.t. pos, color, opacity_raw,
@@ -1014,18 +1026,25 @@ def render(pos, color, opacity_raw, sigma, c2w, H, W, fx, fy, cx, cy, near=0.01,
       background=(r, g, b)   image = clamp(C + (1 - A) * background, 0, 1); a constant (sequence or tensor of 3 numbers), no
                         gradient.  No survivor: the clamped background, zero maps.
     Such a frame takes the separate library calls and may not be rendered inside a gradient_route() block.
+      lowpass=s         (a multiple of 0.01 in [0, 2.55], px^2; the paper's rasteriser uses 0.3) the eigen clamp is applied to the
+                        projected covariance + s I: radius, rectangles, pair count, conic and the densification extent follow.
+      antialias=True    (a bool; needs lowpass > 0) the opacity of every splat is scaled by sqrt(det Sigma / det(Sigma + s I)), so a
+                        sub-pixel splat keeps its energy; differentiable through Sigma.
+    Anything else raises ValueError before anything is queued.  The mode is kept on the frame: the backward pass cannot be given
+    another one.  The default is the reference's render, bit for bit.
     """
-    view = _aux_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), aux, background)
+    bits = _abi.filter_bits(lowpass, antialias)
+    view = _filter_view(_aux_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), aux, background), bits)
     return _RenderFn.apply(False, view, c2w, pos, opacity_raw, color, sigma, None, None)
 
 
 def render_gaussians(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2w, H, W, fx, fy, cx, cy, near=0.01, far=100.0,
                      pix_guard=32, T=16, min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128., *, aux=False,
-                     background=None, sh_degree=3):
+                     background=None, sh_degree=3, lowpass=0.0, antialias=False):
     """Fused entry: render(pos, evaluate_sh(f_dc, f_rest, pos, c2w), opacity_raw, build_sigma_from_params(scale_raw,
     q_raw), c2w, ...) in one pass (the reference's three-call sequence, scripts/train.py:463,502,505-508).  Differentiable
     w.r.t. the six parameter tensors and c2w (through the camera transform, the covariance rotation and the SH view
-    direction), as render() is.  aux, background: as for render().
+    direction), as render() is.  aux, background, lowpass, antialias: as for render().
 
     sh_degree (one of the integers 0, 1, 2, 3; anything else raises ValueError before anything is queued): the colour is
     sigmoid(sum_{k < (sh_degree + 1)^2} f_k Y_k).  f_rest stays [N, 45]; its inactive entries -- columns ch * 15 + j with
@@ -1033,22 +1052,26 @@ def render_gaussians(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2w, H, W
     zero on every backward route, and the image equals the default render of the same scene with zeros there.  The degree
     is kept on the frame, so the backward pass cannot be given another one."""
     _abi.sh_bands_dropped(sh_degree)
+    bits = _abi.filter_bits(lowpass, antialias)
     view = _degree_view(_aux_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), aux, background),
                         sh_degree)
+    view.filter = bits
     return _RenderFn.apply(True, view, c2w, pos, opacity_raw, scale_raw, q_raw, f_dc, f_rest)
 
 
 @torch.no_grad()
 def render_frames(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2ws, H, W, fx, fy, cx, cy, near=0.01, far=100.0,
-                  pix_guard=32, T=16, min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128., on_frame=None, sh_degree=3):
+                  pix_guard=32, T=16, min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128., on_frame=None, sh_degree=3,
+                  *, lowpass=0.0, antialias=False):
     """Forward-only rendering of a sequence of camera poses with the frames software-pipelined over two HIP streams:
     frame k + 1's projection / binning front (latency- and bandwidth-bound) overlaps frame k's rasterisation (VALU-bound).
     Same images as render_gaussians() frame by frame.  Returns the list of images (or calls on_frame(k, image) and returns
     None); the caller's current stream waits for all of them.  Without on_frame, and once a pair capacity is known for the
     device, no frame waits for its counters either (deferred_checks: the per-frame checks are made after the last frame is
-    queued; a sequence that outgrows the buffers is rendered again).  sh_degree: as for render_gaussians()."""
+    queued; a sequence that outgrows the buffers is rendered again).  sh_degree, lowpass, antialias: as for render_gaussians()."""
     _abi.sh_bands_dropped(sh_degree)
-    view = _degree_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), sh_degree)
+    bits = _abi.filter_bits(lowpass, antialias)
+    view = _filter_view(_degree_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), sh_degree), bits)
     dev = pos.device
     cams = [torch.as_tensor(c, dtype=torch.float32, device=dev) if not isinstance(c, torch.Tensor) else c for c in c2ws]
     args = (view, dev, cams, pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw)

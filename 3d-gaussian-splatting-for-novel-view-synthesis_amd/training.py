@@ -26,7 +26,7 @@ from dataclasses import dataclass
 import torch
 import torch.distributed as dist
 
-from . import dp, losses, ops, optim
+from . import _abi, dp, losses, ops, optim
 
 
 @dataclass
@@ -76,6 +76,11 @@ class TrainConfig:
     # get a zero gradient (ops.render_gaussians sh_degree).  A function of the iteration alone: checkpoints store
     # nothing for it and data-parallel ranks agree without a message.
     sh_degree_interval: int = 0
+    # the screen-space low-pass of the paper's rasteriser and the opacity compensation of its antialiased variant (not in the reference;
+    # ops.render_gaussians lowpass / antialias), given to every view.  The paper: lowpass = 0.3.  Without it a Gaussian
+    # may shrink to a needle that one pixel centre sees.
+    lowpass: float = 0.0
+    antialias: bool = False
 
 
 _side_streams = {}           # per device: the two streams the views of an iteration alternate between (TrainConfig.view_streams)
@@ -93,6 +98,7 @@ class Trainer:
             raise ValueError(f"densify_rule must be 'reference' or 'screen', not {self.cfg.densify_rule!r}")
         if type(self.cfg.sh_degree_interval) is not int or self.cfg.sh_degree_interval < 0:
             raise ValueError(f"sh_degree_interval must be an integer >= 0, not {self.cfg.sh_degree_interval!r}")
+        self._filter_kw = _abi.filter_kwargs(self.cfg.lowpass, self.cfg.antialias)      # (ValueError for a mode the kernels cannot do)
         self.optimizer = self._new_optimizer(self.cfg.position_lr_init)
         self._gen = None
         # densify_rule = "screen": the statistics since the last densification (None until the first such step; not stored in
@@ -211,7 +217,7 @@ class Trainer:
                             with (ops.densify_stats(pass_stats[k]) if screen else contextlib.nullcontext()):
                                 rendered = ops.render_gaussians(m.pos, m.f_dc, m.f_rest, m.opacity_raw, m.scale_raw, m.q_raw, c2w,
                                                                 int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']),
-                                                                **degree_kw)
+                                                                **degree_kw, **self._filter_kw)
                             loss, vals = losses.compute_loss_device(rendered, image_gt, c.lambda_l1, c.lambda_ssim, scale=1.0 / n_global)
                             loss.backward()                            # (loss / batch size: the division is inside the loss kernels)
                             per_view.append(vals)

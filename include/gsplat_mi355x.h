@@ -176,6 +176,17 @@ int gsplat_bin_state_layout(int64_t pair_capacity, const gsplat_view* v, gsplat_
  * backward call on the state must be given the SAME degree (GSPLAT_BACKWARD_SH_DEGREE): the saved SH Jacobian holds the active
  * bands only.  gsplat_forward_deferred takes the degree in the same bits of ITS flags (GSPLAT_FRAME_SH_DEGREE).              */
 #define GSPLAT_PROJECT_SH_DEGREE(d) ((3 - (d)) << 4)
+/* The screen-space low-pass of the paper's rasteriser, in the SAME bits of the flags of the six entries that run the
+ * projection math: gsplat_project, gsplat_forward_deferred, gsplat_project_backward[_pose], gsplat_backward,
+ * gsplat_backward_adam_rest.  The eigen clamp is applied to Sigma + s I instead of the projected covariance Sigma; radius,
+ * rectangles, pair counts, conic and masks follow.  GSPLAT_FILTER_LOWPASS(c): s = c / 100 px^2, c = 0..255 (bits 17-24; 0 = no
+ * filter, today's render bit for bit).  GSPLAT_FILTER_ANTIALIAS (needs c > 0, else GSPLAT_ERR_BAD_ARG): the opacity in the record is
+ * clamp(sigmoid(o), 0, 0.999) * sqrt(max(det Sigma, 0) / det(Sigma + s I)), both determinants before the clamp; the opacity pre-filter
+ * stays on the unscaled value.  Every backward call must carry the bits of the forward call that filled project_state / the frame:
+ * other bits are refused with GSPLAT_ERR_BAD_ARG before anything is launched (the library remembers, on the host, the bits each
+ * state was last projected with).  Any other entry refuses the bits as unknown flags; the size queries ignore them.              */
+#define GSPLAT_FILTER_ANTIALIAS 65536
+#define GSPLAT_FILTER_LOWPASS(c) ((c) << 17)
 int gsplat_project(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, void* project_state,
                    void* scratch, int64_t scratch_bytes, gsplat_counts* counts_host, void* counts_event, int32_t flags,
                    void* stream);

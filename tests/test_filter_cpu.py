@@ -1,0 +1,404 @@
+"""CPU tests of the screen-space low-pass and the antialiased opacity: the oracle helper (tests/filter_oracle.py)
+against the oracle itself, the host build of the FILTER variants of csrc/gs_math.h against the helper's stages and autograd, the flag
+bits of the C ABI, and the validation of the Python keywords.  Nothing here needs a GPU."""
+import ctypes as C
+import importlib
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import torch_port as tp
+from tests import filter_oracle as fo
+from tests import listcheck, util
+
+abi = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd._abi")
+ops = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd.ops")
+harness = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd.harness")
+training = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd.training")
+CSRC = os.path.join(os.path.dirname(abi.__file__), "csrc")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FUSED = ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")
+MODES = ((0.3, False), (0.3, True))
+
+
+@pytest.fixture(scope="module")
+def hm():
+    so = os.path.join(CSRC, "libgsmath_host.so")
+    srcs = [os.path.join(CSRC, f) for f in ("host_math_check.cpp", "gs_math.h", "gs_body.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, srcs[0]])
+    return C.CDLL(so)
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _bits(lowpass, antialias):
+    return abi.filter_bits(lowpass, antialias)
+
+
+def _fused_args(d, dt, grad=False):
+    p = util.tensors(d, dt, grad=grad)
+    return p, [p[k] for k in FUSED]
+
+
+# ---- 1. the helper ----------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", ["g1_generic", "g2_ragged", "g4_thresholds", "g6_huge", "g7_tiny"])
+def test_helper_without_a_filter_is_the_oracle_bit_for_bit(name):
+    d = util.load(name)
+    _, args = _fused_args(d, torch.float64)
+    c2w = torch.tensor(d["c2w"], dtype=torch.float64)
+    ref = tp.render_fused(*args, c2w, *util.cam_args(d), **d["kwargs"])
+    img, depth, alpha = fo.render(*args, c2w, *util.cam_args(d), lowpass=0.0, antialias=False, **d["kwargs"])
+    assert torch.equal(img, ref)
+    assert torch.isfinite(depth).all() and torch.isfinite(alpha).all()
+
+
+@pytest.mark.parametrize("name", ["g1_generic", "g6_huge", "g7_tiny"])
+def test_helper_filter_equals_an_explicit_eigh_of_sigma_plus_s(name):
+    """lambda + s from the wrapper against torch.linalg.eigh(Sigma + s I) itself: conics to rounding, tile rectangles and pairs equal."""
+    d = util.load(name)
+    _, args = _fused_args(d, torch.float64)
+    c2w = torch.tensor(d["c2w"], dtype=torch.float64)
+    s = fo.lowpass_value(0.3)
+    st = {}
+    fo.render(*args, c2w, *util.cam_args(d), lowpass=0.3, stages=st, stop_after_binning=True, **d["kwargs"])
+    real = torch.linalg.eigh
+    ex = {}
+    torch.linalg.eigh = lambda A: real(A + s * torch.eye(2, dtype=A.dtype))
+    try:
+        tp.render_fused(*args, c2w, *util.cam_args(d), stages=ex, stop_after_binning=True, **d["kwargs"])
+    finally:
+        torch.linalg.eigh = real
+    assert torch.equal(st["ids"], ex["ids"])
+    assert torch.equal(st["tile_rect"], ex["tile_rect"]) and torch.equal(st["pair_gauss"], ex["pair_gauss"])
+    scale = ex["conic"].abs().max(1, keepdim=True).values
+    assert ((st["conic"] - ex["conic"]).abs() <= 1e-9 * scale).all()
+    assert fo.pair_count(st) == int(ex["pair_gauss"].shape[0])
+    # the filter does something on this scene: footprints grow
+    un = {}
+    tp.render_fused(*args, c2w, *util.cam_args(d), stages=un, stop_after_binning=True, **d["kwargs"])
+    assert fo.pair_count(st) >= int(un["pair_gauss"].shape[0])
+    assert not torch.equal(st["conic"], un["conic"][: st["conic"].shape[0]]) or st["conic"].shape != un["conic"].shape
+
+
+# ---- 2. / 3. the host build --------------------------------------------------------------------------------------------
+
+def _gaussians(arrs, fused=True, color=None, sigma=None):
+    n = len(arrs["pos"])
+    if fused:
+        return abi.Gaussians(n, _ptr(arrs["pos"]), _ptr(arrs["opacity_raw"]), None, None, _ptr(arrs["scale_raw"]),
+                             _ptr(arrs["q_raw"]), _ptr(arrs["f_dc"]), _ptr(arrs["f_rest"]))
+    return abi.Gaussians(n, _ptr(arrs["pos"]), _ptr(arrs["opacity_raw"]), _ptr(color), _ptr(sigma), None, None, None, None)
+
+
+def _project(hm, d, arrs, flags, fused=True, color=None, sigma=None):
+    n = len(arrs["pos"])
+    view = abi.make_view(*util.cam_args(d), **d["kwargs"])
+    rec64 = np.zeros((n, 16), np.float32)
+    rect, brect = np.zeros((n, 2), np.uint32), np.zeros((n, 2), np.uint32)
+    depth = np.zeros(n, np.float32)
+    tiles, btiles, bmask = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    vis = np.zeros(n, np.int32)
+    g = _gaussians(arrs, fused, color, sigma)
+    c2w = np.ascontiguousarray(d["c2w"], np.float32)
+    hm.hm_project_flags(C.byref(g), _ptr(c2w), C.byref(view), C.c_int32(flags), _ptr(rec64), _ptr(rect), _ptr(depth), _ptr(tiles),
+                        _ptr(vis), _ptr(brect), _ptr(btiles), _ptr(bmask))
+    rec = [rec64[:, 0:4], rec64[:, 4:8], rec64[:, 8:12], rect, brect, btiles, bmask]
+    return rec, tiles, vis, view, g, c2w
+
+
+def _unfused_inputs(d):
+    """color / sigma of the scene as float32 arrays (what the reference's three-call sequence hands to render())."""
+    p = util.tensors(d, torch.float64)
+    c2w = torch.tensor(d["c2w"], dtype=torch.float64)
+    color = tp.sh_colour(p["f_dc"], p["f_rest"], p["pos"], c2w).numpy().astype(np.float32)
+    sigma = tp.covariance_from_params(p["scale_raw"], p["q_raw"]).numpy().astype(np.float32)
+    return np.ascontiguousarray(color), np.ascontiguousarray(sigma)
+
+
+def _helper_stages(d, lowpass, antialias, fused=True, color=None, sigma=None, grad=False, pose=False):
+    dt = torch.float64
+    p = util.tensors(d, dt, grad=grad)
+    c2w = torch.tensor(d["c2w"], dtype=dt, requires_grad=pose)
+    st = {}
+    if fused:
+        leaves = [p[k] for k in util.PARAMS]
+        fo.render(*[p[k] for k in FUSED], c2w, *util.cam_args(d), lowpass=lowpass, antialias=antialias, stages=st,
+                  stop_after_binning=True, **d["kwargs"])
+    else:
+        col = torch.tensor(color, dtype=dt, requires_grad=grad)
+        sig = torch.tensor(sigma, dtype=dt, requires_grad=grad)
+        leaves = [p["pos"], p["opacity_raw"], col, sig]
+        fo.render_unfused(p["pos"], col, p["opacity_raw"], sig, c2w, *util.cam_args(d), lowpass=lowpass, antialias=antialias, stages=st,
+                          stop_after_binning=True, **d["kwargs"])
+    return st, leaves, c2w
+
+
+def _as_golden(d, st):
+    """The helper's stages in the layout listcheck.check_records reads from a golden file."""
+    con = st["conic"].detach().numpy()
+    conic = np.stack([np.stack([con[:, 0], con[:, 1]], 1), np.stack([con[:, 1], con[:, 2]], 1)], 1)
+    return dict(im_ids=st["ids"].numpy(), im_u=st["u"].detach().numpy(), im_v=st["v"].detach().numpy(), im_conic=conic,
+                im_evals=st["evals"].detach().numpy(), im_opacity=st["opacity_record"].detach().numpy(),
+                im_color=st["color"].detach().numpy(), im_tile_rect=st["tile_rect"].numpy(), kwargs=d["kwargs"], H=d["H"], W=d["W"])
+
+
+def _check_forward(hm, d, lowpass, antialias, fused=True):
+    arrs = {k: np.ascontiguousarray(d[k], np.float32) for k in util.PARAMS}
+    color, sigma = (None, None) if fused else _unfused_inputs(d)
+    st, _, _ = _helper_stages(d, lowpass, antialias, fused, color, sigma)
+    rec, tiles, vis, view, *_ = _project(hm, d, arrs, _bits(lowpass, antialias), fused, color, sigma)
+    gold = _as_golden(d, st)
+    ids = gold["im_ids"]
+
+    def row_spans(k):
+        bl, bh = rec[4][ids[k], 0], rec[4][ids[k], 1]
+        h = int((bh >> 16) - (bl >> 16) + 1)
+        xa, xb = np.zeros(h, np.int32), np.zeros(h, np.int32)
+        r16 = np.ascontiguousarray(np.concatenate([rec[0][ids[k]], rec[1][ids[k]]]), np.float32)
+        hm.hm_row_spans(_ptr(r16), C.c_uint32(int(bl)), C.c_uint32(int(bh)), C.byref(view), _ptr(xa), _ptr(xb))
+        return xa, xb
+
+    listcheck.check_records(gold, rec[0], rec[1], rec[2], tiles, np.nonzero(vis == 0)[0], rec[4], rec[5], rec[6], ref_rect=rec[3],
+                            row_spans=row_spans)
+    if antialias:               # the compensation does something here, and never brightens
+        rho = st["rho"].numpy()
+        assert rho.max() <= 1.0 and rho.min() < 0.95
+    return st, rec
+
+
+@pytest.mark.parametrize("lowpass,antialias", MODES)
+@pytest.mark.parametrize("name", ["g1_generic", "g7_tiny", "g6_huge"])
+def test_host_forward_records_vs_helper_stages(hm, name, lowpass, antialias):
+    _check_forward(hm, util.load(name), lowpass, antialias)
+
+
+@pytest.mark.parametrize("lowpass,antialias", MODES)
+def test_host_forward_records_unfused(hm, lowpass, antialias):
+    _check_forward(hm, util.load("g1_generic"), lowpass, antialias, fused=False)
+
+
+def test_host_forward_without_filter_bits_is_hm_project(hm):
+    d = util.load("g1_generic")
+    arrs = {k: np.ascontiguousarray(d[k], np.float32) for k in util.PARAMS}
+    rec, tiles, vis, view, g, c2w = _project(hm, d, arrs, 0)
+    n = len(arrs["pos"])
+    rec64, rect, depth = np.zeros((n, 16), np.float32), np.zeros((n, 2), np.uint32), np.zeros(n, np.float32)
+    t2, v2, brect, btiles, bmask = np.zeros(n, np.uint32), np.zeros(n, np.int32), np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    hm.hm_project(C.byref(g), _ptr(c2w), C.byref(view), _ptr(rec64), _ptr(rect), _ptr(depth), _ptr(t2), _ptr(v2), _ptr(brect), _ptr(btiles), _ptr(bmask))
+    assert np.array_equal(rec64[:, :12].view(np.uint32), np.concatenate(rec[:3], 1).view(np.uint32))
+    assert np.array_equal(t2, tiles) and np.array_equal(v2, vis) and np.array_equal(brect, rec[4]) and np.array_equal(bmask, rec[6])
+
+
+def _stage_grads(d, lowpass, antialias, fused=True, color=None, sigma=None, pose=False, seed=0):
+    """tests/test_product_math_cpu.py _oracle_stage_grads on the helper's stages: random cotangents on (u, v, conic, the record's
+    opacity = opacity * rho, colour), so rho's own term is exercised.  With pose the last gradient is c2w's."""
+    st, leaves, c2w = _helper_stages(d, lowpass, antialias, fused, color, sigma, grad=True, pose=pose)
+    rng = np.random.default_rng(seed)
+    ids = st["ids"].numpy()
+    n = len(d["pos"])
+    g2d = np.zeros((n, 16), np.float32)
+    g2d[ids, :9] = rng.normal(0, 1, (len(ids), 9)).astype(np.float32)
+    conic = st["conic"].detach().numpy()
+    g2d[ids, 2:5] /= (np.abs(conic).max(1, keepdims=True) + 1.0).astype(np.float32)
+    ev = st["evals"].detach().numpy()
+    g2d[ids[ev[:, 1] / ev[:, 0] > 1e4]] = 0
+    ct = torch.tensor(g2d[ids].astype(np.float64))
+    outs = [st["u"], st["v"], st["conic"], st["opacity_record"], st["color"]]
+    cts = [ct[:, 0], ct[:, 1], ct[:, 2:5], ct[:, 5], ct[:, 6:9]]
+    grads = torch.autograd.grad(outs, leaves + ([c2w] if pose else []), cts, allow_unused=True)
+    return g2d, [g.numpy() if g is not None else None for g in grads]
+
+
+@pytest.mark.parametrize("lowpass,antialias", MODES + ((0.1, True),))
+@pytest.mark.parametrize("name", ["g1_generic", "g7_tiny", "g6_huge"])
+def test_host_backward_fused_vs_helper_autograd(hm, name, lowpass, antialias):
+    d = util.load(name)
+    arrs = {k: np.ascontiguousarray(d[k], np.float32) for k in util.PARAMS}
+    flags = _bits(lowpass, antialias)
+    g2d, ref = _stage_grads(d, lowpass, antialias)
+    rec, tiles, vis, view, g, c2w = _project(hm, d, arrs, flags)
+    out = {k: np.full_like(arrs[k], np.nan) for k in util.PARAMS}
+    gg = abi.GaussianGrads(_ptr(out["pos"]), _ptr(out["opacity_raw"]), None, None, _ptr(out["scale_raw"]),
+                           _ptr(out["q_raw"]), _ptr(out["f_dc"]), _ptr(out["f_rest"]))
+    hm.hm_project_backward_flags(C.byref(g), _ptr(c2w), C.byref(view), C.c_int32(flags), _ptr(tiles), _ptr(g2d), C.byref(gg))
+    for k, r in zip(util.PARAMS, ref):
+        util.check_grad(out[k], r, k)
+    # pose: the same rows, and dL/dc2w
+    g2d, ref = _stage_grads(d, lowpass, antialias, pose=True)
+    gc2w = np.full((4, 4), np.nan, np.float32)
+    hm.hm_project_backward_pose_flags(C.byref(g), _ptr(c2w), C.byref(view), C.c_int32(flags), _ptr(tiles), _ptr(g2d), C.byref(gg), _ptr(gc2w))
+    for k, r in zip(util.PARAMS, ref):
+        util.check_grad(out[k], r, k)
+    util.check_grad(gc2w[:3, :3], ref[-1][:3, :3], f"{name} c2w[:3,:3]")
+    util.check_grad(gc2w, ref[-1], f"{name} c2w")
+    assert np.all(gc2w[3] == 0.0)
+
+
+def test_host_backward_unfused_vs_helper_autograd(hm):
+    d = util.load("g1_generic")
+    arrs = {k: np.ascontiguousarray(d[k], np.float32) for k in util.PARAMS}
+    color, sigma = _unfused_inputs(d)
+    flags = _bits(0.3, True)
+    g2d, ref = _stage_grads(d, 0.3, True, fused=False, color=color, sigma=sigma)
+    rec, tiles, vis, view, g, c2w = _project(hm, d, arrs, flags, fused=False, color=color, sigma=sigma)
+    out = dict(pos=np.full_like(arrs["pos"], np.nan), opacity_raw=np.full_like(arrs["opacity_raw"], np.nan),
+               color=np.full_like(color, np.nan), sigma=np.full_like(sigma, np.nan))
+    gg = abi.GaussianGrads(_ptr(out["pos"]), _ptr(out["opacity_raw"]), _ptr(out["color"]), _ptr(out["sigma"]), None, None, None, None)
+    hm.hm_project_backward_flags(C.byref(g), _ptr(c2w), C.byref(view), C.c_int32(flags), _ptr(tiles), _ptr(g2d), C.byref(gg))
+    for k, r in zip(("pos", "opacity_raw", "color", "sigma"), ref):
+        if k == "sigma":                     # the projection sees sym(Sigma) only: compare the symmetric parts
+            r = 0.5 * (r + r.transpose(0, 2, 1))
+            out[k] = 0.5 * (out[k] + out[k].transpose(0, 2, 1))
+        util.check_grad(out[k], r, k)
+
+
+def test_filtered_needles_have_no_determinant_cancellation(hm):
+    """The needle set of test_conic_of_needle_gaussians_has_no_determinant_cancellation under the filter: det(Sigma + s I) =
+    det_exact + s (a + d) + s^2 is a sum of non-negative terms, so the conic and rho keep that test's bound, 2e-5, at every aspect."""
+    rng = np.random.default_rng(7)
+    n = 3000
+    H, W, fx = 200, 300, 250.0
+    flags = _bits(0.3, True)
+    for aspect_log, bound in ((2.0, 2e-5), (4.0, 2e-5), (5.0, 2e-5)):
+        pos = np.concatenate([rng.uniform(-1.0, 1.0, (n, 2)), rng.uniform(3.0, 6.0, (n, 1))], 1).astype(np.float32)
+        sr = rng.normal(-4.0, 0.3, (n, 3)).astype(np.float32)
+        sr[np.arange(n), rng.integers(0, 3, n)] += aspect_log
+        arrs = dict(pos=pos, scale_raw=sr, q_raw=rng.normal(0, 1, (n, 4)).astype(np.float32), opacity_raw=rng.normal(1, 1, n).astype(np.float32),
+                    f_dc=rng.normal(0, 1, (n, 3)).astype(np.float32), f_rest=np.zeros((n, 45), np.float32))
+        d = dict(c2w=np.eye(4, dtype=np.float32), H=H, W=W, fx=fx, fy=fx, cx=W / 2, cy=H / 2, kwargs={})
+        rec, tiles, vis, view, g, c2w = _project(hm, d, arrs, flags)
+        rho = np.zeros(n, np.float32)
+        hm.hm_filter_rho(C.byref(g), _ptr(c2w), C.byref(view), C.c_int32(flags), _ptr(rho))
+        st = {}
+        fo.render(*[torch.tensor(arrs[k]).double() for k in FUSED], torch.eye(4, dtype=torch.float64), H, W, fx, fx, W / 2, H / 2,
+                  lowpass=0.3, antialias=True, stages=st, stop_after_binning=True)
+        ids, con, ev = st["ids"].numpy(), st["conic"].numpy(), st["evals"].numpy()
+        inside = (ev[:, 0] > 2e-6) & (ev[:, 1] < 0.99e4)
+        assert inside.sum() > n // 8
+        mine = np.stack([rec[0][ids, 2], rec[0][ids, 3], rec[1][ids, 0]], 1).astype(np.float64)
+        err = (np.abs(mine - con).max(1) / np.abs(con).max(1))[inside]
+        r64 = st["rho"].numpy()
+        rerr = (np.abs(rho[ids].astype(np.float64) - r64) / r64)[inside & (r64 > 0)]
+        print(aspect_log, "conic", err.max(), "rho", rerr.max(), "smallest rho", r64[inside].min())
+        assert err.max() <= bound, (aspect_log, err.max())
+        assert rerr.max() <= bound, (aspect_log, rerr.max())
+
+
+# ---- 4. the flags --------------------------------------------------------------------------------------------------------
+
+def test_filter_macros_and_their_python_mirror_agree():
+    txt = open(os.path.join(ROOT, "include", "gsplat_mi355x.h")).read()
+    aa = re.search(r"^#define\s+GSPLAT_FILTER_ANTIALIAS\s+(\d+)\s*$", txt, flags=re.M)
+    lp = re.search(r"^#define\s+GSPLAT_FILTER_LOWPASS\(c\)\s+(\(\(c\) << \d+\))\s*$", txt, flags=re.M)
+    assert aa and lp
+    assert int(aa.group(1)) == abi.GSPLAT_FILTER_ANTIALIAS == 1 << 16
+    for c in (0, 1, 30, 255):
+        assert eval(lp.group(1).replace("(c)", f"({c})")) == abi.GSPLAT_FILTER_LOWPASS(c) == c << 17
+    assert not [k for k in ("GSPLAT_FILTER_ANTIALIAS", "GSPLAT_FILTER_LOWPASS") if k.startswith("GSPLAT_PROJECT_")]
+    assert abi.filter_bits(0.3, True) == (30 << 17) | (1 << 16) and abi.filter_bits(0.0, False) == 0 and abi.filter_bits(2.55) == 255 << 17
+    assert abi.ABI_VERSION == 12 and abi.lib().gsplat_abi_version() == 12
+    assert C.sizeof(abi.View) == 56
+
+
+def _entries(lib, v, g=None):
+    group = abi.AdamGroup()
+    gp = C.byref(g) if g is not None else None
+    return {
+        "gsplat_project": lambda f: lib.gsplat_project(gp, None, C.byref(v), None, None, 0, None, None, f, None),
+        "gsplat_forward_deferred": lambda f: lib.gsplat_forward_deferred(gp, None, C.byref(v), None, 0, 1, None, 0, None, 0, None, None, None, f, None),
+        "gsplat_project_backward": lambda f: lib.gsplat_project_backward(gp, None, C.byref(v), None, None, None, f, None),
+        "gsplat_project_backward_pose": lambda f: lib.gsplat_project_backward_pose(gp, None, C.byref(v), None, None, None, None, None, 0, f, None),
+        "gsplat_backward": lambda f: lib.gsplat_backward(gp, None, C.byref(v), None, 0, 1, None, None, None, None, 0, f, None),
+        "gsplat_backward_adam_rest": lambda f: lib.gsplat_backward_adam_rest(gp, None, C.byref(v), None, 0, 1, None, None, None, 0, f,
+                                                                             C.byref(group), 0.9, 0.999, 1e-15, None),
+    }
+
+
+def test_the_six_entries_take_the_filter_bits_and_refuse_antialias_without_a_lowpass():
+    lib = abi.lib()
+    v = abi.make_view(64, 64, 50.0, 50.0, 32.0, 32.0)
+    for name, call in _entries(lib, v).items():
+        for flags in (abi.filter_bits(0.3), abi.filter_bits(0.3, True), abi.filter_bits(2.55, True)):
+            # NULL arguments: a known flag gets as far as the argument checks
+            assert call(flags) == abi.GSPLAT_ERR_BAD_ARG, name
+            msg = lib.gsplat_last_error()
+            assert b"unknown flag" not in msg and b"GSPLAT_FILTER" not in msg, (name, msg)
+        assert call(abi.GSPLAT_FILTER_ANTIALIAS) == abi.GSPLAT_ERR_BAD_ARG, name
+        msg = lib.gsplat_last_error().decode()
+        assert name + ":" in msg and "GSPLAT_FILTER_ANTIALIAS" in msg, (name, msg)
+    # bit 25, next to the filter's, is nobody's; bit 5 stays unknown to the backward entries
+    for name, call in _entries(lib, v).items():
+        if name in ("gsplat_project", "gsplat_forward_deferred"):
+            continue
+        for flags in (1 << 25, 1 << 5):
+            assert call(flags) == abi.GSPLAT_ERR_BAD_ARG and b"unknown flag" in lib.gsplat_last_error(), (name, flags)
+
+
+def test_size_queries_ignore_the_filter_bits():
+    lib = abi.lib()
+    v = abi.make_view(64, 96, 50.0, 50.0, 48.0, 32.0)
+    bits = abi.filter_bits(0.3, True)
+    for flags in (0, abi.GSPLAT_FRAME_BACKWARD):
+        assert lib.gsplat_frame_bytes(600, 5000, C.byref(v), flags | bits) == lib.gsplat_frame_bytes(600, 5000, C.byref(v), flags) > 0
+
+
+# ---- 5. the Python keywords ------------------------------------------------------------------------------------------------
+
+BAD_MODES = (dict(lowpass=-0.1), dict(lowpass=0.305), dict(lowpass=2.56), dict(lowpass=float("nan")), dict(lowpass=0.3, antialias=1),
+             dict(lowpass=0.0, antialias=True))
+
+
+@pytest.mark.parametrize("kw", BAD_MODES)
+def test_render_entries_refuse_a_bad_mode_before_anything_else(kw, monkeypatch):
+    """ValueError, with no library call made: the library loader is made to fail, and CPU tensors would raise RuntimeError."""
+    def no_lib():
+        raise AssertionError("the library was called")
+    monkeypatch.setattr(abi, "lib", no_lib)
+    n = 5
+    t = [torch.zeros(n, 3), torch.zeros(n, 3), torch.zeros(n, 45), torch.zeros(n), torch.zeros(n, 3), torch.zeros(n, 4)]
+    cam = (torch.eye(4), 8, 8, 4.0, 4.0, 4.0, 4.0)
+    with pytest.raises(ValueError, match="lowpass|antialias"):
+        ops.render_gaussians(*t, *cam, **kw)
+    with pytest.raises(ValueError, match="lowpass|antialias"):
+        ops.render(t[0], torch.zeros(n, 3), t[3], torch.zeros(n, 3, 3), *cam, **kw)
+    with pytest.raises(ValueError, match="lowpass|antialias"):
+        ops.render_frames(*t, [torch.eye(4)], *cam[1:], **kw)
+    params = dict(zip(FUSED, t))
+    for fused in (True, False):
+        with pytest.raises(ValueError, match="lowpass|antialias"):
+            harness.benchmark_orbit(params, [np.eye(4)], *cam[1:], fused=fused, **kw)
+    with pytest.raises(ValueError, match="lowpass|antialias"):
+        harness.throughput_orbit(params, [np.eye(4)], *cam[1:], **kw)
+    with pytest.raises(ValueError, match="lowpass|antialias"):
+        abi.filter_kwargs(**kw)
+
+
+def test_good_modes_and_the_default():
+    assert abi.filter_kwargs() == {} and abi.filter_kwargs(0.0, False) == {}
+    assert abi.filter_kwargs(0.3, True) == dict(lowpass=0.3, antialias=True)
+    for c in range(256):                      # every grid point survives the float round trip
+        assert abi.filter_bits(c / 100.0) == c << 17 and abi.filter_bits(c * 0.01) == c << 17
+    cfg = training.TrainConfig()
+    assert cfg.lowpass == 0.0 and cfg.antialias is False
+    n = 5
+    t = [torch.zeros(n, 3), torch.zeros(n, 3), torch.zeros(n, 45), torch.zeros(n), torch.zeros(n, 3), torch.zeros(n, 4)]
+    with pytest.raises(RuntimeError, match="no CPU fallback"):          # a good mode on CPU tensors gets as far as that
+        ops.render_gaussians(*t, torch.eye(4), 8, 8, 4.0, 4.0, 4.0, 4.0, lowpass=0.3, antialias=True)
+
+
+def test_capacity_key_tells_filtered_frames_apart():
+    v = ops._view(64, 96, 50.0, 50.0, 48.0, 32.0, 0.01, 100.0, 32, 16, 1e-6, 6.25, 0.99, 1 / 128.)
+    dev = torch.device("cuda", 0)
+    k0 = ops.capacity_key(dev, v, 600)
+    v.filter = abi.filter_bits(0.3, True)
+    k1 = ops.capacity_key(dev, v, 600)
+    v.filter = abi.filter_bits(0.3, False)
+    assert len({k0, k1, ops.capacity_key(dev, v, 600)}) == 3
