@@ -499,7 +499,10 @@ GS_HD void project_gaussian(const float p[3], const float S[6], float o_raw, con
     m.rad = sqrtf(m.diff * m.diff + m.b * m.b);
     m.l1 = mid + m.rad; m.l2 = mid - m.rad;
     float det_exact = -1.f;                                                          // (< 0: not available)
-    if (cmid) {
+    // (the sum of squares needs an orthogonal R: q = q_raw / (|q_raw| + 1e-9) is a unit quaternion up to 1e-9 / |q_raw|, and the
+    //  determinant comes out wrong by ~6e-9 / |q_raw| -- 1 % at |q_raw| = 1e-6.  Below 1e-2, where cov_from_params_backward leaves the
+    //  torque form for the same reason, the determinant is a d - b^2 as for un-fused inputs)
+    if (cmid && cmid->qn > 1e-2f) {
         const float n0 = -m.j02 * m.j11, n1 = -m.j00 * m.j12, n2 = m.j00 * m.j11;    // j0 x j1
         const float t0 = w[0] * n0 + w[3] * n1 + w[6] * n2, t1 = w[1] * n0 + w[4] * n1 + w[7] * n2, t2 = w[2] * n0 + w[5] * n1 + w[8] * n2;
         const float* R = cmid->R;
@@ -660,9 +663,23 @@ GS_HD void project_gaussian_backward(const ProjMid& m, const Proj& o, const Came
         const float k22 = (m.l2 >= 1e-6f && m.l2 <= 1e4f) ? 1.f : 0.f;
         const float k12 = (m.rad > 0.f) ? (m.f1 - m.f2) / (2.f * m.rad) : k11;
         // v1 = (c, s), v2 = (-s, c)
-        const float t11 = cx_ * (Ga * cx_ + Gb * sx_) + sx_ * (Gb * cx_ + Gd * sx_);
-        const float t12 = cx_ * (-Ga * sx_ + Gb * cx_) + sx_ * (-Gb * sx_ + Gd * cx_);
-        const float t22 = -sx_ * (-Ga * sx_ + Gb * cx_) + cx_ * (-Gb * sx_ + Gd * cx_);
+        float t11, t12, t22;
+        if (m.rad > 0.f && m.det >= 1e-12f) {
+            // V^T Gs V without the 2x2 inverse's cancellation.  The recomposed matrix is V diag(f1, f2) V^T and the conic its inverse
+            // V diag(1/f1, 1/f2) V^T (det = f1 f2), so Gs = -A g A has (V^T Gs V)_ij = -(V^T g V)_ij / (f_i f_j), with
+            // g = [[g00, g01 / 2], [g01 / 2, g11]].  Through (ga, gb, gd) the entry t11 of a needle clamped at f2 = 1e-6 is the
+            // difference of terms g / (f1 f2)^2 ~ 1e11 g that cancel to g / f1^2: float32 left 1e4 g there, and the gradient of the
+            // needle's long axis came out 1e4 times its size.
+            const float h = 0.5f * g01;
+            const float q11 = cx_ * (g00 * cx_ + h * sx_) + sx_ * (h * cx_ + g11 * sx_);
+            const float q12 = cx_ * (-g00 * sx_ + h * cx_) + sx_ * (-h * sx_ + g11 * cx_);
+            const float q22 = -sx_ * (-g00 * sx_ + h * cx_) + cx_ * (-h * sx_ + g11 * cx_);
+            t11 = -q11 / (m.f1 * m.f1); t12 = -q12 / (m.f1 * m.f2); t22 = -q22 / (m.f2 * m.f2);
+        } else {
+            t11 = cx_ * (Ga * cx_ + Gb * sx_) + sx_ * (Gb * cx_ + Gd * sx_);
+            t12 = cx_ * (-Ga * sx_ + Gb * cx_) + sx_ * (-Gb * sx_ + Gd * cx_);
+            t22 = -sx_ * (-Ga * sx_ + Gb * cx_) + cx_ * (-Gb * sx_ + Gd * cx_);
+        }
         const float h11 = k11 * t11, h12 = k12 * t12, h22 = k22 * t22;
         Ga = h11 * cx_ * cx_ - 2.f * h12 * cx_ * sx_ + h22 * sx_ * sx_;
         Gb = h11 * cx_ * sx_ + h12 * (cx_ * cx_ - sx_ * sx_) - h22 * cx_ * sx_;
@@ -673,7 +690,11 @@ GS_HD void project_gaussian_backward(const ProjMid& m, const Proj& o, const Came
         //  pixel wide, which no float32 evaluation resolves -- det0 counts as clamped, so a zero cotangent never meets an infinity)
         if (vk.antialias && m.det0 > 1e-30f && m.rho < 1.f) {
             const float g_rho = g_opacity * clampf_(m.sg, 0.f, 0.999f);
-            const float h0 = 0.5f / (m.rho * m.dets), hs = 0.5f * m.rho / m.dets, hd = g_rho * (h0 - hs);      // h0 = rho / (2 det0)
+            // d rho = h0 d det0 - hs d dets with h0 = rho / (2 det0) = 1 / (2 rho dets), hs = rho / (2 dets); d det0 carries
+            // h0 - hs = (1 - rho^2) / (2 rho dets) = (dets - det0) / (2 rho dets^2), written with dets - det0 = s (a + d) + s^2 as a sum: for
+            // a large splat rho is 1 - 1e-5 and the difference of h0 and hs kept two digits
+            const float hs = 0.5f * m.rho / m.dets;
+            const float hd = g_rho * (0.5f * (vk.lowpass * (m.a + m.d) + vk.lowpass * vk.lowpass) / (m.rho * m.dets)) / m.dets;
             Ga += hd * m.d - g_rho * hs * vk.lowpass;
             Gd += hd * m.a - g_rho * hs * vk.lowpass;
             Gb -= hd * m.b;                                          // (dL = Ga da + 2 Gb db + Gd dd)

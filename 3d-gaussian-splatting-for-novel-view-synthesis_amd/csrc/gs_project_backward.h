@@ -169,7 +169,9 @@ __global__ __launch_bounds__(64) void project_backward_kernel(gsplat_gaussians g
             if (REST) __syncthreads();
             if (ADAM) {
                 const DevCounts* cnt = reinterpret_cast<const DevCounts*>(ar.counts);
-                if (cnt->n_visible > 0 && cnt->n_binned <= ar.capacity) adam_rows<45, !REST>(ar, s_rest, row0, g.n, lane);      // (uniform)
+                // skipped only for the frames the host rolls back: an overflow, or survivors that are all off screen.  A frame with
+                // no survivor at all is a valid zero image: every gradient row is zero and the rows take the zero-gradient step
+                if (cnt->n_binned <= ar.capacity && !(cnt->n_survivors > 0 && cnt->n_visible == 0)) adam_rows<45, !REST>(ar, s_rest, row0, g.n, lane);      // (uniform)
             } else if (REST) {
                 unstage_rows<45>(out.f_rest, s_rest, row0, g.n, lane);
             } else {

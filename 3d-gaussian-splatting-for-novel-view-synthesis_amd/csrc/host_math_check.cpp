@@ -3,6 +3,8 @@
 // NOT part of the product path: the product library (libgsplat_mi355x.so) contains only HIP kernels and fails
 // loudly without a GPU.  This file lets `pytest -m "not gpu"` check the projection math (forward and analytic
 // backward) against the oracle on a machine with no GPU, before any GPU time is spent.
+#include <type_traits>
+
 #include "gs_body.h"
 
 using namespace gsm;
@@ -134,6 +136,80 @@ void hm_project_backward_pose_flags(const gsplat_gaussians* g, const float* c2w,
         grad_c2w[r * 4 + 3] = (float)-sp[r];
     }
     for (int c = 0; c < 4; ++c) grad_c2w[12 + c] = 0.f;
+}
+
+extern "C++" {      // (a template cannot have C linkage)
+namespace {
+// one instantiation of the K8 body, over every Gaussian, the way project_backward_kernel calls it: `moments` rows, the Jacobian
+// sh_colour_jac<NB> leaves (from_jac) instead of the coefficients, dL/dz from column 9 of grad2d (DEPTH)
+template <bool POSE, bool DEPTH, int NB, bool FILTER>
+void backward_variant(const gsplat_gaussians& g, const Camera& cam, const ViewK& vk, bool moments, bool from_jac, const uint32_t* tiles,
+                      const float* grad2d, const gsplat_gaussian_grads* out, float* grad_c2w) {
+    const bool fused = g.scale_raw != nullptr;
+    double sw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, sp[3] = {0, 0, 0};
+    for (int64_t i = 0; i < g.n; ++i) {
+        const GaussIn in = load_gauss_global(i, g, fused);
+        const bool vis = tiles[i] != 0;
+        ShCoefGlobal coef{fused ? g.f_dc + i * 3 : nullptr, fused ? g.f_rest + i * 45 : nullptr};
+        ShEmitNullable emit{fused && out ? out->f_dc + i * 3 : nullptr, fused && out ? out->f_rest + i * 45 : nullptr};
+        float kj[12], rgb[3], gw[9];
+        const bool jac = fused && from_jac;
+        if (jac && vis) {
+            ShMid sm;
+            sh_basis(in.p, cam.eye, sm);
+            sh_colour_jac<NB>(sm, coef, rgb, kj);
+        }
+        const GradOut o = project_backward_core<POSE, DEPTH, NB, FILTER>(in, fused, coef, emit, cam, vk, vis, grad2d + i * 16, moments,
+                                                                         jac ? kj : nullptr, POSE ? gw : nullptr, DEPTH ? grad2d[i * 16 + 9] : 0.f);
+        if (POSE) {
+            for (int k = 0; k < 9; ++k) sw[k] += gw[k];
+            for (int k = 0; k < 3; ++k) sp[k] += o.p[k];
+        }
+        if (!out) continue;
+        for (int k = 0; k < 3; ++k) out->pos[i * 3 + k] = o.p[k];
+        out->opacity_raw[i] = o.o_raw;
+        if (fused) {
+            for (int k = 0; k < 3; ++k) out->scale_raw[i * 3 + k] = o.sr[k];
+            for (int k = 0; k < 4; ++k) out->q_raw[i * 4 + k] = o.qr[k];
+        } else {
+            for (int k = 0; k < 9; ++k) out->sigma[i * 9 + k] = o.S9[k];
+            for (int k = 0; k < 3; ++k) out->color[i * 3 + k] = o.col[k];
+        }
+    }
+    if (POSE) {
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) grad_c2w[r * 4 + c] = (float)sw[c * 3 + r];
+            grad_c2w[r * 4 + 3] = (float)-sp[r];
+        }
+        for (int c = 0; c < 4; ++c) grad_c2w[12 + c] = 0.f;
+    }
+}
+}  // namespace
+}  // extern "C++"
+
+// The K8 body in any of its <POSE, DEPTH, NB, FILTER> instantiations: flags = the GSPLAT_FILTER_* bits (FILTER = a low-pass is set),
+// degree 0..3 (NB = (degree + 1)^2; un-fused inputs: 3), depth: column 9 of grad2d is dL/dz, moments: columns 0..5 are the raster
+// backward's moment sums (else the 2-D gradients themselves), from_jac: the colour backward from sh_colour_jac's 12 values.
+// grad_c2w == NULL: no pose; out == NULL with a pose: pose only.  Returns 0, or 1 for arguments outside that.
+int hm_project_backward_variant(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, int32_t flags, int32_t degree, int32_t depth,
+                                int32_t moments, int32_t from_jac, const uint32_t* tiles, const float* grad2d,
+                                const gsplat_gaussian_grads* out, float* grad_c2w) {
+    if (degree < 0 || degree > 3 || (!out && !grad_c2w) || (!g->scale_raw && degree != 3)) return 1;
+    Camera cam; build_camera(c2w, cam);
+    const bool filter = (flags & GSPLAT_FILTER_LOWPASS(255)) != 0;
+    const ViewK vk = make_viewk(*v, filter ? flags : 0);
+    const bool m = moments != 0, j = from_jac != 0;
+    return with_sh_bases(degree, [&](auto nb) {
+        constexpr int NB = decltype(nb)::value;
+        auto run = [&](auto pose, auto dep, auto filt) {
+            backward_variant<decltype(pose)::value, decltype(dep)::value, NB, decltype(filt)::value>(*g, cam, vk, m, j, tiles, grad2d, out, grad_c2w);
+        };
+        auto with_bool = [](bool b, auto f) { if (b) f(std::true_type{}); else f(std::false_type{}); };
+        with_bool(grad_c2w != nullptr, [&](auto pose) {
+            with_bool(depth != 0, [&](auto dep) { with_bool(filter, [&](auto filt) { run(pose, dep, filt); }); });
+        });
+        return 0;
+    });
 }
 
 // the row spans of a large Gaussian's rectangle (gs_math.h big_row_span), as the binning kernels enumerate them: xa[r], xb[r] for the

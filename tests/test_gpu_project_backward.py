@@ -1,7 +1,30 @@
 """K8 (gsplat_project_backward) on the device, isolated from the raster backward: a hand-made grad2d of moment rows goes in, and the
 gradients are compared with float64 autograd through the oracle's per-Gaussian stage.  (The host build of the same body is
-checked in tests/test_product_math_cpu.py; there the rows are the 2-D gradients themselves, here they are what K7 accumulates.)"""
+checked in tests/test_product_math_cpu.py; there the rows are the 2-D gradients themselves, here they are what K7 accumulates.)
+
+The first two tests hold four instantiations to util.check_grad's tensor-wide bounds.  The tests below them run EVERY instantiation the
+host dispatch (gsplat_kernels.hip fused_backward_kernel_for / unfused_backward_kernel_for) can select, and hold each Gaussian's row
+to the per-row bound of tests/project_backward_oracle.py.  project_backward_kernel<FUSED, JAC, ADAM, ACC, POSE, DEPTH, NB, FILTER>:
+
+    form (fused_backward_kernel_for)       flags / entry                                   reached by
+    <1,0,0,0,0,0>  plain                   gsplat_project_backward 0                       test_every_fused_form_... `plain`, `factored`
+    <1,1,0,0,0,0>  saved Jacobian          ... JAC                                         `jac`, `factored jac`
+    <1,1,0,1,0,0>  accumulate              ... JAC | ACC                                   `acc`
+    <1,0,0,0,0,1>  depth                   ... DEPTH                                       `depth`
+    <1,1,0,0,0,1>  depth, Jacobian         ... DEPTH | JAC                                 `depth jac`
+    <1,0,0,0,1,0>  pose                    gsplat_project_backward_pose 0                  `pose`, `pose only` (out == NULL)
+    <1,1,0,0,1,0>  pose, Jacobian          ... JAC                                         `pose jac`
+    <1,0,0,0,1,1>  pose, depth             ... DEPTH                                       `pose depth`
+    <1,1,0,0,1,1>  pose, depth, Jacobian   ... DEPTH | JAC                                 `pose depth jac`
+    <1,1,1,0,0,0>  in-place f_rest step    gsplat_backward_adam_rest                       test_folded_step_at_every_degree_and_filter_...
+  each at NB = 1, 4, 9, 16 (degree 0..3) and FILTER = 0, 1: test_every_fused_form_gaussian_by_gaussian[scene-degree-filter] runs the
+  first nine forms at its (degree, filter) -- filter `off` is FILTER = 0, `lowpass` and `antialias` are FILTER = 1 with vk.antialias
+  0 / 1; the in-place step at (3, off), (1, off), (3, antialias) is run by tests/test_gpu_training.py, test_gpu_sh_degree.py and
+  test_gpu_filter.py, at the other nine (degree, filter) by the folded-step test here.
+    <0,0,0,0,P,D,16,FILTER> (unfused_backward_kernel_for): test_every_unfused_form_gaussian_by_gaussian[filter], P, D = 0, 1.
+"""
 import ctypes as C
+import importlib
 
 import numpy as np
 import pytest
@@ -10,6 +33,7 @@ import torch
 from oracle import torch_port as tp
 from tests import device_frame as dfm
 from tests import list_scenes, util
+from tests import project_backward_oracle as pbo
 
 pytestmark = pytest.mark.gpu
 abi = dfm.abi
@@ -112,3 +136,223 @@ def test_project_backward_unfused_with_a_known_grad2d():
     for k in names:
         util.check_grad(got[k], ref[k], k)
         assert not got[k].reshape(fr.n, -1)[tiles == 0].any(), f"{k}: the row of a Gaussian that is binned nowhere is not exactly zero"
+
+
+# ---- every instantiation, Gaussian by Gaussian ------------------------------------------------------------------------------------
+PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
+JAC, ACC, DEPTH = abi.GSPLAT_BACKWARD_SH_JACOBIAN, abi.GSPLAT_BACKWARD_ACCUMULATE, abi.GSPLAT_BACKWARD_DEPTH
+SCENES = tuple(f"synth{n}" for n in pbo.SIZES) + pbo.GOLDENS
+SHAPES = dict(pos=3, opacity_raw=1, scale_raw=3, q_raw=4, f_dc=3, f_rest=45, color=3, sigma=9)
+ORDER = ("pos", "opacity_raw", "color", "sigma", "scale_raw", "q_raw", "f_dc", "f_rest")
+
+
+class _Run:
+    """One frame projected at (degree, filter), its reference and K, and the backward entries on buffers with canaries."""
+
+    def __init__(self, name, degree, filt):
+        self.name, self.degree, self.filt = name, degree, filt
+        lowpass, aa = pbo.FILTERS[filt]
+        self.s, self.color, self.sigma = pbo.scene(name)
+        self.fused = self.color is None
+        self.bits = abi.filter_bits(lowpass, aa)
+        fr = self.fr = dfm.Frame(self.s, unfused=None if self.fused else (self.color, self.sigma))
+        fr.project((dfm.F | dfm.L | dfm.J | abi.GSPLAT_PROJECT_SH_DEGREE(degree) if self.fused else 0) | self.bits)
+        self.n = fr.n
+        self.tiles = fr.arrays(lists=False)["tiles"]
+        kw = dict(degree=degree, lowpass=lowpass, antialias=aa, color=self.color, sigma=self.sigma)
+        st64 = pbo.Stage(self.s, dtype=torch.float64, **kw)
+        st32 = pbo.Stage(self.s, dtype=torch.float32, **kw)
+        self.g2d, self.zero = pbo.moment_rows(st64, self.tiles)
+        self.ref = pbo.reference(self.s, self.g2d, stage=st64, **kw)
+        self.K = pbo.calibration(self.s, self.tiles, st64, st32, **kw)
+        self.known = pbo.KNOWN_ROWS.get((name, filt))
+        self.g2d_dev = torch.tensor(self.g2d, device=dfm.DEV)
+        self.flags = (abi.GSPLAT_BACKWARD_SH_DEGREE(degree) if self.fused else 0) | self.bits
+        self.worst = {}
+
+    def backward(self, names, flags, prior=None, pose=False, rows=True):
+        """gsplat_project_backward[_pose] into NaN-filled (or prior-filled) buffers with canaries; the gradients by name."""
+        fr, n = self.fr, self.n
+        ptr = {}
+        for k in names if rows else ():
+            ptr[k] = fr._buf("g_" + k, n * SHAPES[k] * 4)
+            if prior is not None:
+                t, nb = fr.bufs["g_" + k]
+                t[:nb].view(torch.float32).copy_(prior[k].reshape(-1))
+        gg = abi.GaussianGrads(*[ptr.get(k) for k in ORDER])
+        args = (C.byref(fr.g), C.c_void_p(fr.c2w.data_ptr()), C.byref(fr.view), C.c_void_p(fr.state.data_ptr()), C.c_void_p(self.g2d_dev.data_ptr()),
+                C.byref(gg) if rows else None)
+        if pose:
+            nb = fr.lib.gsplat_pose_scratch_bytes(n)
+            abi.check(fr.lib.gsplat_project_backward_pose(*args, fr._buf("g_c2w", 64), fr._buf("pose_scratch", nb), nb, self.flags | flags, fr.st),
+                      "gsplat_project_backward_pose")
+        else:
+            abi.check(fr.lib.gsplat_project_backward(*args, self.flags | flags, fr.st), "gsplat_project_backward")
+        torch.cuda.synchronize()
+        for k, (t, nb) in fr.bufs.items():
+            assert bool((t[nb:] == dfm.CANARY_BYTE).all()), f"a backward entry wrote past the end of {k}"
+        out = {k: fr._floats("g_" + k, (n,) if SHAPES[k] == 1 else ((n, 3, 3) if k == "sigma" else (n, SHAPES[k]))) for k in ptr}
+        if pose:
+            out["c2w"] = fr._floats("g_c2w", (4, 4))
+        return out
+
+    def check(self, got, what, depth=False, K=None):
+        tag = f"{self.name} degree {self.degree} {self.filt}: {what}"
+        for key, v in pbo.check(got, self.ref, self.K if K is None else K, tag, depth=depth, known=self.known).items():
+            self.worst[key] = max(self.worst.get(key, 0.0), v)
+        for k, g in got.items():
+            if k == "c2w":
+                assert not g[3].any(), tag
+                continue
+            rows = g.reshape(self.n, -1)
+            assert not rows[self.tiles == 0].any(), f"{tag}: {k}: the row of a Gaussian that is binned nowhere is not exactly zero"
+            assert not rows[self.zero].any(), f"{tag}: {k}: a visible Gaussian with an all-zero grad2d row must get exact zeros"
+            if k == "f_rest":
+                assert not rows[:, pbo.inactive_columns(self.degree)].any(), f"{tag}: an inactive f_rest column is not exactly zero"
+
+    def agree(self, a, b, what, depth=False):
+        """Two forms of the same gradient agree within the per-row bound (their difference held like an error)."""
+        want = self.ref.grad(depth)
+        self.check({k: want[k] + (a[k].astype(np.float64) - b[k]) for k in a if k in b}, what, depth)
+
+    def report(self):
+        for key in sorted(self.worst):
+            K = self.K.get(key, float("nan"))
+            print(f"{self.name} degree {self.degree} {self.filt}: {key[0]:12s} {key[1]:16s} device {self.worst[key]:10.3g}   K {K:10.3g}{'  (cap)' if K == pbo.K_CAP else ''}")
+
+
+@pytest.mark.parametrize("filt", list(pbo.FILTERS))
+@pytest.mark.parametrize("degree", (0, 1, 2, 3))
+@pytest.mark.parametrize("name", SCENES)
+def test_every_fused_form_gaussian_by_gaussian(name, degree, filt):
+    r = _Run(name, degree, filt)
+    n, ref = r.n, r.ref
+    if name.startswith("synth"):
+        assert pbo.boundary_share(ref) == 0 and not r.tiles[r.s["culled"]].any()
+        pbo.assert_block_layout(name, r.tiles)
+    assert pbo.boundary_share(ref) <= 0.01
+    res = {}
+    for what, flags in (("plain", 0), ("jac", JAC), ("depth", DEPTH), ("depth jac", DEPTH | JAC)):
+        res[what] = r.backward(FUSED_OUT, flags)
+        r.check(res[what], what, depth=bool(flags & DEPTH))
+    r.agree(res["jac"], res["plain"], "jac against plain")
+    r.agree(res["depth jac"], res["depth"], "depth jac against depth", depth=True)
+    # accumulate: (result - prior) against the reference, with the one more rounding of the sum; untouched rows are the prior's bits
+    gen = torch.Generator().manual_seed(5)
+    prior = {k: torch.randn((n, SHAPES[k]), generator=gen) for k in FUSED_OUT}
+    acc = r.backward(FUSED_OUT, JAC | ACC, prior=prior)
+    pr = {k: prior[k].numpy().reshape(acc[k].shape) for k in FUSED_OUT}
+    for k in FUSED_OUT:
+        rows, p = acc[k].reshape(n, -1), pr[k].reshape(n, -1)
+        assert np.array_equal(rows[r.tiles == 0], p[r.tiles == 0]), f"accumulate {k}: a Gaussian that is binned nowhere lost its prior"
+        if k == "f_rest":
+            cols = pbo.inactive_columns(degree)
+            vis = r.tiles != 0
+            assert degree == 0 or np.array_equal(rows[vis][:, cols], (p[vis][:, cols] + np.float32(0.0))), "accumulate: inactive f_rest columns"
+            if degree == 0:
+                assert np.array_equal(rows.view(np.uint32), p.view(np.uint32)), "accumulate at degree 0 touched f_rest"
+    minus = {k: acc[k].astype(np.float64) - pr[k] for k in FUSED_OUT}
+    tag = f"{name} degree {degree} {filt}: acc"
+    pbo.check(minus, ref, pbo.acc_K(ref, pr, r.K), tag, known=r.known)
+    # the factored form: the colour-logit gradients instead of the SH gradients
+    for what, flags in (("factored", 0), ("factored jac", JAC)):
+        fac = r.backward(("pos", "opacity_raw", "scale_raw", "q_raw", "color"), flags)
+        col = fac.pop("color")
+        r.check(fac, what)
+        res[what] = fac
+        r.check({"f_dc": col.astype(np.float64) * 0.28209479177387814}, what + " colour row * K0 against f_dc")
+        assert not col[r.tiles == 0].any()
+    r.agree(res["factored jac"], res["factored"], "factored jac against factored")
+    # pose
+    for what, flags in (("pose", 0), ("pose jac", JAC), ("pose depth", DEPTH), ("pose depth jac", DEPTH | JAC)):
+        res[what] = r.backward(FUSED_OUT, flags, pose=True)
+        r.check(res[what], what, depth=bool(flags & DEPTH))
+    r.agree(res["pose jac"], res["pose"], "pose jac against pose")
+    r.agree(res["pose depth jac"], res["pose depth"], "pose depth jac against pose depth", depth=True)
+    only = r.backward((), DEPTH | JAC, pose=True, rows=False)
+    assert np.array_equal(only["c2w"].view(np.uint32), res["pose depth jac"]["c2w"].view(np.uint32)), "pose only differs from the full call"
+    r.report()
+
+
+@pytest.mark.parametrize("filt", list(pbo.FILTERS))
+def test_every_unfused_form_gaussian_by_gaussian(filt):
+    r = _Run("g11_unfused", 3, filt)
+    assert pbo.boundary_share(r.ref) <= 0.01
+    res = {}
+    for what, flags, pose in (("plain", 0, False), ("depth", DEPTH, False), ("pose", 0, True), ("pose depth", DEPTH, True)):
+        res[what] = r.backward(pbo.UNFUSED, flags, pose=pose)
+        r.check(res[what], what, depth=bool(flags & DEPTH))
+    only = r.backward((), DEPTH, pose=True, rows=False)
+    assert np.array_equal(only["c2w"].view(np.uint32), res["pose depth"]["c2w"].view(np.uint32))
+    r.report()
+
+
+# ---- the in-place f_rest step (the ADAM instantiations) ----------------------------------------------------------------------------
+NAMES = ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")
+ELSEWHERE = {(3, "off"), (1, "off"), (3, "antialias")}        # tests/test_gpu_training.py, test_gpu_sh_degree.py, test_gpu_filter.py
+
+
+def _trainer_pair(s, view, steps, first, cfg, seed_moments=False):
+    """[unfolded, folded]: (losses, parameters, exp_avg, exp_avg_sq, step) after `steps` deferred one-view iterations from iteration
+    `first` on (the frame before them waits for its counters: the ordinary backward)."""
+    gs = importlib.import_module(PKG)
+    model_mod, training, ops = (importlib.import_module(PKG + "." + m) for m in ("model", "training", "ops"))
+    res = []
+    old = gs.set_deterministic(True)
+    try:
+        for fold in (False, True):
+            model = model_mod.GaussianModel({k: torch.tensor(s[k]) for k in NAMES}, device=dfm.DEV)
+            tr = training.Trainer(model, training.TrainConfig(densify_until_iter=0, opacity_reset_interval=10 ** 9, fold_rest_step=fold, **cfg))
+            st = tr.optimizer._state(model.f_rest)
+            if seed_moments:
+                gen = torch.Generator(dfm.DEV).manual_seed(8)
+                st["exp_avg"].copy_(1e-3 * torch.randn(model.f_rest.shape, device=dfm.DEV, generator=gen))
+                st["exp_avg_sq"].copy_(1e-6 * (0.5 + torch.rand(model.f_rest.shape, device=dfm.DEV, generator=gen)))
+            tr.step(first, [view])
+            calls = ops.composite_calls["backward"]
+            losses = [float(tr.step(first + 1 + k, [view])["loss"]) for k in range(steps)]
+            assert ops.composite_calls["backward"] == calls + steps, "the iterations did not take the composite backward"
+            torch.cuda.synchronize()
+            res.append((losses, {k: getattr(model, k).detach().clone() for k in NAMES}, st["exp_avg"].clone(), st["exp_avg_sq"].clone(), int(st["step"]),
+                        model.f_rest.grad is None))
+    finally:
+        gs.set_deterministic(old)
+    return res
+
+
+def _assert_same_step(res, steps):
+    plain, fold = res
+    assert plain[4] == fold[4] == steps + 1 and fold[5] and not plain[5]
+    assert plain[0] == fold[0]
+    for k in NAMES:
+        assert torch.equal(plain[1][k], fold[1][k]), k
+    assert torch.equal(plain[2], fold[2]) and torch.equal(plain[3], fold[3])
+
+
+@pytest.mark.parametrize("degree,filt", [(d, f) for d in (0, 1, 2, 3) for f in pbo.FILTERS if (d, f) not in ELSEWHERE])
+def test_folded_step_at_every_degree_and_filter_is_the_optimisers_step(degree, filt):
+    """As test_adam_step_of_f_rest_inside_the_backward_pass_is_the_optimisers_step, on the n = 129 scene: f_rest and its moments equal
+    the optimiser's step of the plain gradient, the other five parameters are bit-equal."""
+    s = pbo.synthetic(129)
+    lowpass, aa = pbo.FILTERS[filt]
+    view = dict(image=np.random.default_rng(5).uniform(0, 1, (s["H"], s["W"], 3)).astype(np.float32), c2w=s["c2w"],
+                **{k: s[k] for k in ("H", "W", "fx", "fy", "cx", "cy")})
+    cfg = dict(lowpass=lowpass, antialias=aa) if lowpass else {}
+    if degree < 3:
+        cfg["sh_degree_interval"] = 10
+    res = _trainer_pair(s, view, 3, 10 * degree if degree < 3 else 1, cfg, seed_moments=True)
+    _assert_same_step(res, 3)
+    assert not torch.equal(res[1][1]["f_rest"], torch.tensor(s["f_rest"], device=dfm.DEV))
+
+
+@pytest.mark.parametrize("name", util.EMPTY_CASES)
+def test_folded_step_of_a_frame_without_survivors_is_the_zero_gradient_step(name):
+    """A frame whose Gaussians are all culled is a valid zero image: the reference and the unfolded path give f_rest a zero gradient and
+    Adam steps it (the moments decay, the parameter moves by m / (sqrt(v) + eps)).  The folded step inside K8 must do the same."""
+    s = list_scenes.golden(name)
+    view = dict(image=np.random.default_rng(6).uniform(0, 1, (s["H"], s["W"], 3)).astype(np.float32), c2w=s["c2w"],
+                **{k: s[k] for k in ("H", "W", "fx", "fy", "cx", "cy")})
+    res = _trainer_pair(s, view, 3, 1, {}, seed_moments=True)
+    _assert_same_step(res, 3)
+    start = torch.tensor(s["f_rest"], device=dfm.DEV)
+    assert not torch.equal(res[1][1]["f_rest"], start), "the zero-gradient step moves f_rest by its moments"
