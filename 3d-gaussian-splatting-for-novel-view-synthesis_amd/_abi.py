@@ -166,6 +166,11 @@ SIGNATURES = {
     "gsplat_loss": (_INT, [_VP, _VP, _I64, C.c_int32, C.c_int32, C.c_float, C.c_float, _VP, _VP, _VP, _VP]),
     "gsplat_loss_forward": (_INT, [_VP, _VP, _I64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, _VP, _VP, _VP, C.c_int32, _VP]),
     "gsplat_loss_backward": (_INT, [_VP, _VP, _I64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, _VP, _VP, _VP, _VP]),
+    "gsplat_aux_loss_scratch_bytes": (_I64, [_I64, C.c_int32, C.c_int32]),
+    "gsplat_aux_loss_forward": (_INT, [_VP, _VP, _VP, _VP, _I64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, _VP, _VP, _VP, _VP]),
+    "gsplat_aux_loss_backward": (_INT, [_VP, _VP, _VP, _VP, _I64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, _VP, _VP, _VP, _VP,
+                                        _VP]),
+    "gsplat_composite_target": (_INT, [_VP, _VP, _F, _I64, C.c_int32, C.c_int32, _VP, _VP]),
     "gsplat_clip_scratch_bytes": (_I64, []),
     "gsplat_clip_grad_norm": (_INT, [_I64, _VP, C.c_float, _VP, _VP, _VP]),
     "gsplat_adam_step": (_INT, [_I64, _VP, _VP, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, _VP, _VP]),

@@ -32,11 +32,14 @@
 // the tile holds in its three first passes: 432 FMAs per value, 0.24 ms at 1080p, VALU-bound.  Cut in two at the maps, each half
 // has one 5-pixel halo: 230 FMAs per value for 72 B per pixel of extra traffic that stays in the 256 MB cache.
 // Sums: one pair per workgroup, added up in a fixed order by block 0 of the second kernel (no atomics: the value is reproducible).
+#include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 
 #include <hip/hip_runtime.h>
 
 #include "../../include/gsplat_mi355x.h"
+#include "gs_aux_loss.h"
 
 namespace {
 
@@ -434,6 +437,84 @@ int gsplat_loss_backward(const float* pred, const float* target, int64_t batch, 
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_loss_backward launch: %s", hipGetErrorString(e));
+        return GSPLAT_ERR_HIP;
+    }
+    return GSPLAT_OK;
+}
+
+/* ---- the auxiliary loss on the depth / opacity maps, and a target over a background (gs_aux_loss.h) ---- */
+// scratch = [256 bytes: n_v = max(1, number of valid target depths) as a double, left by the forward for the backward |
+//            three partial sums (|A - M|, v |D - A Z|, v) per workgroup of 1024 pixels, rounded up to 256 bytes]
+static int64_t aux_blocks(int64_t batch, int32_t H, int32_t W) { return (batch * (int64_t)H * W + AUX_BLOCK_PIX - 1) / AUX_BLOCK_PIX; }
+static bool aux_shape_ok(int64_t batch, int32_t H, int32_t W) {
+    return batch > 0 && H > 0 && W > 0 && batch <= 65535 && aux_blocks(batch, H, W) <= 0x3FFFFFFF;
+}
+static int aux_aligned(std::initializer_list<const void*> ptrs) {
+    for (const void* q : ptrs)
+        if ((uintptr_t)q % 16) return 0;
+    return 1;
+}
+int64_t gsplat_aux_loss_scratch_bytes(int64_t batch, int32_t H, int32_t W) {
+    if (batch <= 0 || H <= 0 || W <= 0) return -1;
+    return AUX_HEADER_BYTES + 256 * ((aux_blocks(batch, H, W) * 3 * (int64_t)sizeof(float) + 255) / 256);
+}
+
+int gsplat_aux_loss_forward(const float* depth, const float* alpha, const float* target_depth, const float* target_alpha, int64_t batch,
+                            int32_t H, int32_t W, float lambda_depth, float lambda_alpha, float scale, float* values, float* total,
+                            void* scratch, void* stream_) {
+    if (!alpha || !values || !scratch || (target_depth && !depth) || !aux_shape_ok(batch, H, W)) {
+        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_aux_loss_forward: bad argument");
+        return GSPLAT_ERR_BAD_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream_;
+    const int64_t n = batch * (int64_t)H * W, blocks = aux_blocks(batch, H, W);
+    float* partial = (float*)((char*)scratch + AUX_HEADER_BYTES);
+    const int vec = aux_aligned({depth, alpha, target_depth, target_alpha});
+    hipLaunchKernelGGL(aux_loss_sums_kernel, dim3((unsigned)blocks), dim3(AUX_THREADS), 0, st, depth, alpha, target_depth, target_alpha, n, vec,
+                       partial);
+    hipLaunchKernelGGL(aux_loss_finish_kernel, dim3(1), dim3(AUX_THREADS), 0, st, (const float*)partial, (int)blocks, 1.0 / (double)n,
+                       lambda_depth, lambda_alpha, (double)scale, values, total, (double*)scratch);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_aux_loss_forward launch: %s", hipGetErrorString(e));
+        return GSPLAT_ERR_HIP;
+    }
+    return GSPLAT_OK;
+}
+
+int gsplat_aux_loss_backward(const float* depth, const float* alpha, const float* target_depth, const float* target_alpha, int64_t batch,
+                             int32_t H, int32_t W, float lambda_depth, float lambda_alpha, float scale, const float* upstream,
+                             float* grad_depth, float* grad_alpha, void* scratch, void* stream_) {
+    if (!alpha || !grad_alpha || !scratch || (target_depth && (!depth || !grad_depth)) || !aux_shape_ok(batch, H, W)) {
+        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_aux_loss_backward: bad argument");
+        return GSPLAT_ERR_BAD_ARG;
+    }
+    const int64_t n = batch * (int64_t)H * W, blocks = aux_blocks(batch, H, W);
+    const int vec = aux_aligned({depth, alpha, target_depth, target_alpha, grad_depth, grad_alpha});
+    hipLaunchKernelGGL(aux_loss_grad_kernel, dim3((unsigned)blocks), dim3(AUX_THREADS), 0, (hipStream_t)stream_, depth, alpha, target_depth,
+                       target_alpha, n, vec, (double)scale * (double)lambda_alpha / (double)n, (double)scale * (double)lambda_depth,
+                       (const double*)scratch, upstream, grad_depth, grad_alpha);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_aux_loss_backward launch: %s", hipGetErrorString(e));
+        return GSPLAT_ERR_HIP;
+    }
+    return GSPLAT_OK;
+}
+
+int gsplat_composite_target(const float* rgb, const float* alpha, const float* background, int64_t batch, int32_t H, int32_t W, float* out,
+                            void* stream_) {
+    if (!rgb || !alpha || !background || !out || !aux_shape_ok(batch, H, W)) {
+        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_composite_target: bad argument");
+        return GSPLAT_ERR_BAD_ARG;
+    }
+    const int64_t n = batch * (int64_t)H * W;
+    const AuxBackground bg{{background[0], background[1], background[2]}};
+    hipLaunchKernelGGL(composite_target_kernel, dim3((unsigned)aux_blocks(batch, H, W)), dim3(AUX_THREADS), 0, (hipStream_t)stream_, rgb, alpha, bg,
+                       n, aux_aligned({rgb, alpha, out}), out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_composite_target launch: %s", hipGetErrorString(e));
         return GSPLAT_ERR_HIP;
     }
     return GSPLAT_OK;

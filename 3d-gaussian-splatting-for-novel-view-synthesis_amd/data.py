@@ -21,6 +21,17 @@ def load_image(image_path):
     return torch.from_numpy(np.array(Image.open(image_path).convert('RGB'), dtype=np.float32) / 255.0)
 
 
+def load_image_alpha(image_path):
+    """([H, W, 3], [H, W]) float32 in [0, 1]: the colour as load_image gives it and the file's alpha channel, 1.0 everywhere for a
+    file without one."""
+    from PIL import Image
+    im = Image.open(image_path)
+    rgb = torch.from_numpy(np.array(im.convert('RGB'), dtype=np.float32) / 255.0)
+    if 'A' in im.getbands() or 'transparency' in im.info:
+        return rgb, torch.from_numpy(np.array(im.convert('RGBA'), dtype=np.float32)[..., 3] / 255.0)
+    return rgb, torch.ones(rgb.shape[:2], dtype=torch.float32)
+
+
 class _MetaUnpickler(pickle.Unpickler):
     """Unpickler for cam_meta.npy that can only rebuild numpy arrays / scalars / dtypes and plain Python containers:
     a crafted file cannot name any other callable, so loading a dataset directory executes nothing from it."""
@@ -106,9 +117,14 @@ def load_point_cloud(pcd_path):
 
 class GaussianDataset:
     """Images + intrinsics + camera-to-world poses in the reference layout (data_loader.py:153-284); same constructor
-    arguments (scale_factor defaults to 0.5 there too) and the same sample dict."""
+    arguments (scale_factor defaults to 0.5 there too) and the same sample dict.  Not in the reference (keyword-only, off by
+    default): alpha=True adds sample['alpha'] [H, W], the file's alpha channel (1.0 for a file without one), rescaled bilinearly with
+    the image; depth_dir='depth' adds sample['depth'] [H, W] from <data_dir>/<depth_dir>/<image stem>.npy (float32 camera-space z, <= 0
+    or non-finite = no data), rescaled with mode='nearest' so that the zeros do not bleed into valid depths."""
 
-    def __init__(self, data_dir, image_dir='images', cam_meta_path=None, scale_factor=0.5):
+    def __init__(self, data_dir, image_dir='images', cam_meta_path=None, scale_factor=0.5, *, alpha=False, depth_dir=None):
+        self.alpha = bool(alpha)
+        self.depth_dir = depth_dir
         self.data_dir = Path(data_dir)
         self.image_dir = self.data_dir / image_dir
         self.scale_factor = scale_factor
@@ -131,18 +147,32 @@ class GaussianDataset:
         return len(self.image_files)
 
     def __getitem__(self, idx):
-        image = load_image(self.image_files[idx])
+        extra = {}
+        if self.alpha:
+            image, extra['alpha'] = load_image_alpha(self.image_files[idx])
+        else:
+            image = load_image(self.image_files[idx])
+        if self.depth_dir is not None:
+            depth = torch.from_numpy(np.asarray(np.load(self.data_dir / self.depth_dir / (self.image_files[idx].stem + '.npy')), dtype=np.float32))
+            if tuple(depth.shape) != tuple(image.shape[:2]):
+                raise ValueError(f"depth map of {self.image_files[idx].name} is {tuple(depth.shape)}, the image {tuple(image.shape[:2])}")
+            extra['depth'] = depth
         if self.scale_factor != 1.0:
             h, w = image.shape[:2]
+            size = (int(h * self.scale_factor), int(w * self.scale_factor))
             image = torch.nn.functional.interpolate(image.permute(2, 0, 1).unsqueeze(0),
-                                                    size=(int(h * self.scale_factor), int(w * self.scale_factor)),
+                                                    size=size,
                                                     mode='bilinear', align_corners=False).squeeze(0).permute(1, 2, 0)
+            if 'alpha' in extra:
+                extra['alpha'] = torch.nn.functional.interpolate(extra['alpha'][None, None], size=size, mode='bilinear', align_corners=False)[0, 0]
+            if 'depth' in extra:
+                extra['depth'] = torch.nn.functional.interpolate(extra['depth'][None, None], size=size, mode='nearest')[0, 0]
         H, W = image.shape[:2]
         c2w = self.c2w_matrices[idx] if self.c2w_matrices is not None else torch.eye(4, dtype=torch.float32)
         cp, s = self.cam_params, self.scale_factor
         has_c = 'cx' in cp and 'cy' in cp
         return {'image': image, 'c2w': c2w, 'fx': cp['fx'] * s, 'fy': cp['fy'] * s, 'cx': cp['cx'] * s if has_c else W / 2.0,
-                'cy': cp['cy'] * s if has_c else H / 2.0, 'H': H, 'W': W, 'idx': idx}
+                'cy': cp['cy'] * s if has_c else H / 2.0, 'H': H, 'W': W, 'idx': idx, **extra}
 
 
 def initialize_gaussians_from_pointcloud(points, num_sh_bands=3):
@@ -168,14 +198,26 @@ def initialize_gaussians_from_pointcloud(points, num_sh_bands=3):
             'scale_raw': scale_raw, 'q_raw': q_raw}
 
 
-def write_dataset(data_dir, images, fx, fy, poses, points=None, cx=None, cy=None):
-    """Write a scene in the reference layout: images/000000.png ..., cam_meta.npy, poses.npy, pointcloud.ply (ASCII)."""
+def write_dataset(data_dir, images, fx, fy, poses, points=None, cx=None, cy=None, alphas=None, depths=None):
+    """Write a scene in the reference layout: images/000000.png ..., cam_meta.npy, poses.npy, pointcloud.ply (ASCII).  alphas (one
+    [H, W] per image): the PNGs are RGBA; depths (one [H, W] per image): depth/000000.npy ... in float32 (GaussianDataset alpha=True,
+    depth_dir='depth')."""
     from PIL import Image
     d = Path(data_dir)
     (d / 'images').mkdir(parents=True, exist_ok=True)
+
+    def host(t):
+        return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
     for i, im in enumerate(images):
         a = im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
+        if alphas is not None:
+            a = np.concatenate([a[..., :3], host(alphas[i])[..., None]], axis=-1)
         Image.fromarray((np.clip(a, 0, 1) * 255).round().astype(np.uint8)).save(d / 'images' / f'{i:06d}.png')
+    if depths is not None:
+        (d / 'depth').mkdir(parents=True, exist_ok=True)
+        for i, z in enumerate(depths):
+            np.save(d / 'depth' / f'{i:06d}.npy', host(z).astype(np.float32))
     h, w = (images[0].shape[0], images[0].shape[1])
     meta = {'fx': float(fx), 'fy': float(fy), 'height': int(h), 'width': int(w)}
     if cx is not None and cy is not None:

@@ -84,15 +84,19 @@ def load_parameters(checkpoint_dir, iteration='final', device="cuda"):
                             f"(looked for {path.name} and {', '.join(f.name for f in loose.values())})")
 
 
-def benchmark_orbit(params, c2ws, H, W, fx, fy, cx, cy, fused=True, on_frame=None, sh_degree=3, *, lowpass=0.0, antialias=False):
+def benchmark_orbit(params, c2ws, H, W, fx, fy, cx, cy, fused=True, on_frame=None, sh_degree=3, *, lowpass=0.0, antialias=False,
+                    background=None):
     """Per-frame render times over a trajectory with the reference's protocol: one un-timed warm-up frame, then for each
     frame synchronize -> wall clock -> (SH + render) -> synchronize -> wall clock.  `fused=False` issues the reference's
     own call sequence (evaluate_sh + render with a pre-built sigma, covariance build outside the timed region).
     sh_degree: as for ops.render_gaussians (fused frames only: the reference's sequence has no degree).  lowpass, antialias: the
-    screen-space low-pass and the opacity compensation of ops.render / ops.render_gaussians, for both settings of `fused`."""
+    screen-space low-pass and the opacity compensation of ops.render / ops.render_gaussians, for both settings of `fused`.
+    background: the colour the frames are composited over, as for ops.render (a model trained on white is viewed on white)."""
     if not fused and sh_degree != 3:
         raise ValueError("sh_degree needs fused=True: evaluate_sh + render is the reference's degree-3 sequence")
     filter_kw = _abi.filter_kwargs(lowpass, antialias)          # (none for the default: the call stays the reference's)
+    if background is not None:
+        filter_kw = dict(filter_kw, background=background)
     dev = params["pos"].device
     kw = dict(pix_guard=32, chi_square_clip=6.25, alpha_cutoff=1 / 128.)
     sigma = None if fused else ops.build_sigma_from_params(params["scale_raw"], params["q_raw"])
@@ -125,11 +129,13 @@ def benchmark_orbit(params, c2ws, H, W, fx, fy, cx, cy, fused=True, on_frame=Non
             "fps_min": fps.min(), "fps_max": fps.max(), "times": t}
 
 
-def throughput_orbit(params, c2ws, H, W, fx, fy, cx, cy, on_frame=None, sh_degree=3, *, lowpass=0.0, antialias=False):
+def throughput_orbit(params, c2ws, H, W, fx, fy, cx, cy, on_frame=None, sh_degree=3, *, lowpass=0.0, antialias=False, background=None):
     """Frames per second over a trajectory when frames need not be timed one by one: ops.render_frames pipelines them over
     two streams (frame k + 1's projection / binning overlaps frame k's rasterisation).  Not the reference's protocol
-    (benchmark_orbit is): a serving-style number.  sh_degree, lowpass, antialias: as for ops.render_frames."""
+    (benchmark_orbit is): a serving-style number.  sh_degree, lowpass, antialias, background: as for ops.render_frames."""
     filter_kw = _abi.filter_kwargs(lowpass, antialias)
+    if background is not None:
+        filter_kw = dict(filter_kw, background=background)
     dev = params["pos"].device
     args = (params["pos"], params["f_dc"], params["f_rest"], params["opacity_raw"], params["scale_raw"], params["q_raw"])
     cams = [torch.as_tensor(np.asarray(c), dtype=torch.float32, device=dev) for c in c2ws]

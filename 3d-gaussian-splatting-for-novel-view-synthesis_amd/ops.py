@@ -406,7 +406,9 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
         raise RuntimeError("a camera-pose gradient (c2w.requires_grad) is not available inside a gradient_route() block "
                            "(factored exchange, folded f_rest step, accumulate_grads): render the pose frame outside it")
     auxf = _is_aux(view)
-    if auxf and _route.get() is not None:
+    # (the factored exchange takes an aux frame: it goes through the separate calls, whose backward forms the logit gradients from
+    #  grad2d whatever filled it; the other two routes live on the composite entries, which have no aux variant)
+    if auxf and _route.get() is not None and not isinstance(_route.get(), dp.FactoredExchange):
         raise RuntimeError("depth / opacity maps and a background (aux=True, background=...) are not available inside a gradient_route() "
                            "block (factored exchange, folded f_rest step, accumulate_grads): render the frame outside it")
     stats = _stats_record(pos)              # (checked before anything else: a wrong record is refused even where nothing is rendered)
@@ -1062,16 +1064,21 @@ def render_gaussians(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2w, H, W
 @torch.no_grad()
 def render_frames(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2ws, H, W, fx, fy, cx, cy, near=0.01, far=100.0,
                   pix_guard=32, T=16, min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128., on_frame=None, sh_degree=3,
-                  *, lowpass=0.0, antialias=False):
+                  *, lowpass=0.0, antialias=False, aux=False, background=None):
     """Forward-only rendering of a sequence of camera poses with the frames software-pipelined over two HIP streams:
     frame k + 1's projection / binning front (latency- and bandwidth-bound) overlaps frame k's rasterisation (VALU-bound).
     Same images as render_gaussians() frame by frame.  Returns the list of images (or calls on_frame(k, image) and returns
     None); the caller's current stream waits for all of them.  Without on_frame, and once a pair capacity is known for the
     device, no frame waits for its counters either (deferred_checks: the per-frame checks are made after the last frame is
-    queued; a sequence that outgrows the buffers is rendered again).  sh_degree, lowpass, antialias: as for render_gaussians()."""
+    queued; a sequence that outgrows the buffers is rendered again).  sh_degree, lowpass, antialias: as for render_gaussians().
+    aux, background: as for render_gaussians() -- every element of the result (and the argument of on_frame) is then what
+    render_gaussians() returns for the same arguments, bit for bit: (image, depth, alpha) with aux=True, the image over the
+    background with a background alone."""
     _abi.sh_bands_dropped(sh_degree)
     bits = _abi.filter_bits(lowpass, antialias)
     view = _filter_view(_degree_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), sh_degree), bits)
+    if aux or background is not None:
+        view = _aux_view(view, aux, background)
     dev = pos.device
     cams = [torch.as_tensor(c, dtype=torch.float32, device=dev) if not isinstance(c, torch.Tensor) else c for c in c2ws]
     args = (view, dev, cams, pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw)
@@ -1094,6 +1101,8 @@ def _render_frames(view, dev, cams, pos, f_dc, f_rest, opacity_raw, scale_raw, q
         pend, done = started
         with torch.cuda.stream(streams[k % 2]):
             image = (done if pend is None else _forward_end(pend, False))[0]
+        if isinstance(image, tuple):                           # an aux frame: (image, depth, alpha), the maps None without aux=True
+            image = image if view.aux else image[0]
         return image
 
     images = []
@@ -1102,7 +1111,8 @@ def _render_frames(view, dev, cams, pos, f_dc, f_rest, opacity_raw, scale_raw, q
         nxt = begin(k + 1) if k + 1 < len(cams) else None      # queue the next frame's front before waiting for this one's counters
         image = end(k, started)
         started = nxt
-        image.record_stream(main)                              # allocated on a side stream, consumed on the caller's
+        for t in (image if isinstance(image, tuple) else (image,)):
+            t.record_stream(main)                              # allocated on a side stream, consumed on the caller's
         if on_frame is not None:
             main.wait_stream(streams[k % 2])                   # GPU-side dependency only: the host does not block
             on_frame(k, image)

@@ -81,6 +81,19 @@ class TrainConfig:
     # may shrink to a needle that one pixel centre sees.
     lowpass: float = 0.0
     antialias: bool = False
+    # training with a background, an opacity target and depth maps (not in the reference).  All off by default, and
+    # an iteration is then exactly the one above.  Any of them on makes the iteration an AUX PASS: the views are rendered with
+    # ops.render_gaussians(aux=..., background=...) outside the folded step and the in-kernel view sum (those live on the composite
+    # entries, which have no aux variant), and each view's loss is compute_loss_device + losses.aux_loss.
+    #   background      None | (r, g, b) in [0, 1] | "random": the colour the render is composited over -- and a view's target too,
+    #                   where the view has an alpha ('alpha', or a 4-channel 'image').  "random": one colour per iteration, a function
+    #                   of (background_seed, iteration) alone, so its views and all ranks share it without a message.
+    #   lambda_alpha    weight of mean |A - M| against the view's 'alpha'
+    #   lambda_depth    weight of the composited depth residual |D - A Z| over the valid pixels of the view's 'depth'
+    background: object = None
+    background_seed: int = 0
+    lambda_alpha: float = 0.0
+    lambda_depth: float = 0.0
 
 
 _side_streams = {}           # per device: the two streams the views of an iteration alternate between (TrainConfig.view_streams)
@@ -99,6 +112,13 @@ class Trainer:
         if type(self.cfg.sh_degree_interval) is not int or self.cfg.sh_degree_interval < 0:
             raise ValueError(f"sh_degree_interval must be an integer >= 0, not {self.cfg.sh_degree_interval!r}")
         self._filter_kw = _abi.filter_kwargs(self.cfg.lowpass, self.cfg.antialias)      # (ValueError for a mode the kernels cannot do)
+        self._background = _check_background(self.cfg.background)
+        if type(self.cfg.background_seed) is not int:
+            raise ValueError(f"background_seed must be an integer, not {self.cfg.background_seed!r}")
+        for name in ("lambda_alpha", "lambda_depth"):
+            x = getattr(self.cfg, name)
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not 0.0 <= x < float("inf"):
+                raise ValueError(f"{name} must be a finite number >= 0, not {x!r}")
         self.optimizer = self._new_optimizer(self.cfg.position_lr_init)
         self._gen = None
         # densify_rule = "screen": the statistics since the last densification (None until the first such step; not stored in
@@ -159,6 +179,38 @@ class Trainer:
         g.manual_seed(self.cfg.densify_seed * 1000003 + iteration)
         return g
 
+    def background(self, iteration):
+        """The background colour of iteration `iteration` (TrainConfig.background): None, the configured colour, or -- "random" --
+        three uniform numbers from a CPU generator keyed by (background_seed, iteration): the same on every rank and in a repeated
+        pass, with no message."""
+        if self._background != "random":
+            return self._background
+        g = torch.Generator()
+        g.manual_seed(self.cfg.background_seed * 1000003 + int(iteration))
+        return tuple(torch.rand(3, generator=g).tolist())
+
+    def _view_targets(self, v, dev, bg):
+        """(image, alpha, depth) targets of one view of an aux pass, on the device: the image over the background where the view
+        has an alpha (over black without a background), alpha / depth None unless their weight is > 0 -- and then a view
+        without one is an error of that view (ValueError)."""
+        c = self.cfg
+        image = torch.as_tensor(v['image']).to(dev)
+        alpha = v.get('alpha')
+        if alpha is not None:
+            alpha = torch.as_tensor(alpha).to(dev)
+        if image.shape[-1] == 4:
+            if alpha is None:
+                alpha = image[..., 3]
+            image = image[..., :3]
+        if c.lambda_alpha > 0 and alpha is None:
+            raise ValueError("lambda_alpha > 0 needs an 'alpha' (or a 4-channel 'image') in every view")
+        if c.lambda_depth > 0 and v.get('depth') is None:
+            raise ValueError("lambda_depth > 0 needs a 'depth' in every view")
+        if alpha is not None:
+            image = losses.composite_over(image, alpha, bg if bg is not None else (0.0, 0.0, 0.0))
+        depth = torch.as_tensor(v['depth']).to(dev) if c.lambda_depth > 0 else None
+        return image, (alpha if c.lambda_alpha > 0 else None), depth
+
     def sh_degree(self, iteration):
         """The SH degree iteration `iteration` renders at (TrainConfig.sh_degree_interval)."""
         k = self.cfg.sh_degree_interval
@@ -171,8 +223,16 @@ class Trainer:
         per rank, the same list on every rank) or leave it None and the counts are exchanged with one tiny all-gather.
         `global_views` (views of the whole batch over all ranks) is only checked against that.  Returns {'loss', 'l1',
         'ssim'} as device scalars (this rank's share, already divided by the global batch), 'gaussians', 'lr_pos',
-        'densified', 'sh_degree' (the SH degree the views were rendered at)."""
+        'densified', 'sh_degree' (the SH degree the views were rendered at).
+        An aux pass (TrainConfig.background / lambda_alpha / lambda_depth): a view may also carry 'alpha' [H, W] in [0, 1] (an
+        'image' of [H, W, 4] is shorthand for rgb + alpha) and 'depth' [H, W] (camera-space z; <= 0 or non-finite: no data); the
+        dict also has 'l_alpha' and 'l_depth' (device scalars like 'l1', 0 for a term that is off) and 'loss' is the whole total.
+        Otherwise those keys of a view are ignored, except that a 4-channel image is composited over black."""
         c, m = self.cfg, self.model
+        aux_maps = c.lambda_alpha > 0 or c.lambda_depth > 0
+        aux_pass = aux_maps or self._background is not None
+        bg = self.background(iteration)
+        aux_kw = dict(aux=aux_maps, background=bg) if aux_pass else {}
         sh_degree = self.sh_degree(iteration)
         degree_kw = {} if sh_degree == 3 else {'sh_degree': sh_degree}      # (without a schedule the render call is the reference's)
         world = self._world()
@@ -188,12 +248,14 @@ class Trainer:
         for attempt in range(4):
             self.optimizer.zero_grad()
             acc = torch.zeros(3, dtype=torch.float32, device=dev)
+            acc_aux = torch.zeros(3, dtype=torch.float32, device=dev) if aux_pass else None
             # the route of the gradients (ops.gradient_route): data parallel, SH gradients in factored form (dp.FactoredExchange, 2.6x
             # fewer bytes over xGMI at 8 views); one view, the Adam step of f_rest inside its backward; several, their sum in the backward
             exchange = (dp.FactoredExchange(m.get_params(), world_views=1, group=self.group, equal_views=even, sh_degree=sh_degree)
                         if world > 1 else None)
-            fold = exchange is None and len(views) == 1 and c.fold_rest_step
-            sum_in_kernel = exchange is None and len(views) > 1 and c.sum_views_in_kernel
+            # (an aux pass: no route on one process -- its frames take the separate library calls)
+            fold = exchange is None and len(views) == 1 and c.fold_rest_step and not aux_pass
+            sum_in_kernel = exchange is None and len(views) > 1 and c.sum_views_in_kernel and not aux_pass
             route = (exchange if exchange is not None else self.optimizer.fused_rest_update(m.f_rest) if fold
                      else ops.accumulate_grads(m.get_params()) if sum_in_kernel else None)
             pass_error = checks = consumer = None
@@ -208,18 +270,31 @@ class Trainer:
                     main = torch.cuda.current_stream(dev) if side else None
                     for st in side:
                         st.wait_stream(main)                                           # parameters, zeroed gradients
-                    per_view = []
+                    per_view, per_view_aux = [], []
                     self._pass_dirty = screen
                     for k, v in enumerate(views):
                         with (torch.cuda.stream(side[k % len(side)]) if side else contextlib.nullcontext()):
-                            image_gt = torch.as_tensor(v['image']).to(dev)
+                            if aux_pass:
+                                image_gt, alpha_gt, depth_gt = self._view_targets(v, dev, bg)
+                            else:
+                                image_gt = torch.as_tensor(v['image']).to(dev)
+                                if image_gt.shape[-1] == 4:            # rgb + alpha: over black
+                                    image_gt = losses.composite_over(image_gt[..., :3], image_gt[..., 3], (0.0, 0.0, 0.0))
                             c2w = torch.as_tensor(v['c2w'], dtype=torch.float32).to(dev)
                             with (ops.densify_stats(pass_stats[k]) if screen else contextlib.nullcontext()):
                                 rendered = ops.render_gaussians(m.pos, m.f_dc, m.f_rest, m.opacity_raw, m.scale_raw, m.q_raw, c2w,
                                                                 int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']),
-                                                                **degree_kw, **self._filter_kw)
+                                                                **degree_kw, **self._filter_kw, **aux_kw)
+                            if aux_maps:
+                                rendered, depth, alpha = rendered
                             loss, vals = losses.compute_loss_device(rendered, image_gt, c.lambda_l1, c.lambda_ssim, scale=1.0 / n_global)
-                            loss.backward()                            # (loss / batch size: the division is inside the loss kernels)
+                            if aux_maps:
+                                aux_total, aux_vals = losses.aux_loss(depth, alpha, depth_gt, alpha_gt, c.lambda_depth, c.lambda_alpha,
+                                                                      scale=1.0 / n_global)
+                                torch.autograd.backward((loss, aux_total))      # loss + aux_total, one pass through the render's backward
+                                per_view_aux.append(aux_vals)
+                            else:
+                                loss.backward()                        # (loss / batch size: the division is inside the loss kernels)
                             per_view.append(vals)
                     for st in side:
                         main.wait_stream(st)
@@ -229,6 +304,10 @@ class Trainer:
                         if side:
                             vals.record_stream(main)
                         acc += vals
+                    for vals in per_view_aux:
+                        if side:
+                            vals.record_stream(main)
+                        acc_aux += vals
             except Exception as e:                # single process: nothing to agree on, the exception leaves as it is
                 if world == 1:
                     raise
@@ -306,5 +385,21 @@ class Trainer:
             densified = True
         if iteration % c.opacity_reset_interval == 0:
             m.reset_opacity()
-        return {'loss': acc[2], 'l1': acc[0], 'ssim': acc[1], 'gaussians': m.get_num_gaussians(), 'lr_pos': pos_lr,
-                'densified': densified, 'sh_degree': sh_degree}
+        out = {'loss': acc[2], 'l1': acc[0], 'ssim': acc[1], 'gaussians': m.get_num_gaussians(), 'lr_pos': pos_lr,
+               'densified': densified, 'sh_degree': sh_degree}
+        if aux_pass:
+            out.update(loss=acc[2] + acc_aux[2], l_alpha=acc_aux[0], l_depth=acc_aux[1])
+        return out
+
+
+def _check_background(background):
+    """TrainConfig.background as the trainer keeps it: None, "random" or a tuple of three floats in [0, 1] (ValueError otherwise)."""
+    if background is None or (isinstance(background, str) and background == "random"):
+        return background
+    try:
+        vals = tuple(float(x) for x in background) if not isinstance(background, str) else None
+    except (TypeError, ValueError):
+        vals = None
+    if vals is None or len(vals) != 3 or not all(0.0 <= x <= 1.0 for x in vals):
+        raise ValueError(f"background must be None, 'random' or three numbers (r, g, b) in [0, 1], not {background!r}")
+    return vals

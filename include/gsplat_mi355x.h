@@ -405,6 +405,31 @@ int gsplat_loss_forward(const float* pred, const float* target, int64_t batch, i
 int gsplat_loss_backward(const float* pred, const float* target, int64_t batch, int32_t H, int32_t W, float lambda_l1,
                          float lambda_ssim, float scale, const float* upstream, float* grad_pred, void* scratch, void* stream);
 
+/* ---- training with a background, an opacity target and depth maps ----------------------------------------
+ * The auxiliary loss on the maps of an aux render.  depth = D, alpha = A of the render, target_depth = Z (camera-space z, the unit
+ * of D; a pixel counts iff Z is finite and > 0), target_alpha = M: [batch, H, W] fp32 device arrays.  With n = batch H W,
+ * v = [Z valid], n_v = max(1, sum v):
+ *   L_alpha = sum |A - M| / n,   L_depth = sum v |D - A Z| / n_v,   values[3] = scale * (L_alpha, L_depth, lambda_alpha L_alpha +
+ *   lambda_depth L_depth),   *total (nullable) = values[2].
+ * A NULL target switches its term off (value 0); depth may be NULL when target_depth is.  The sums (the count of valid pixels
+ * included) are one partial per workgroup added in a fixed order in double: no atomics, the same bits every call.  The forward
+ * leaves n_v in scratch for the backward, which writes
+ *   grad_depth = scale up lambda_depth v sign(D - A Z) / n_v                                  (nullable when target_depth is NULL)
+ *   grad_alpha = scale up (lambda_alpha sign(A - M) / n - lambda_depth v Z sign(D - A Z) / n_v),        sign(0) = 0,
+ * up = *upstream (device scalar, NULL = 1), multiplied in by the kernel.  scratch: the bytes the size query returns (256 + 12
+ * per 1024 pixels, rounded up to 256).  batch <= 65535, as for the image loss.                                                */
+int64_t gsplat_aux_loss_scratch_bytes(int64_t batch, int32_t H, int32_t W);
+int gsplat_aux_loss_forward(const float* depth, const float* alpha, const float* target_depth, const float* target_alpha, int64_t batch,
+                            int32_t H, int32_t W, float lambda_depth, float lambda_alpha, float scale, float* values, float* total,
+                            void* scratch, void* stream);
+int gsplat_aux_loss_backward(const float* depth, const float* alpha, const float* target_depth, const float* target_alpha, int64_t batch,
+                             int32_t H, int32_t W, float lambda_depth, float lambda_alpha, float scale, const float* upstream,
+                             float* grad_depth, float* grad_alpha, void* scratch, void* stream);
+/* A target image over a background: out = rgb * alpha + (1 - alpha) * background.  rgb [batch, H, W, 3] is straight colour (not
+ * pre-multiplied), alpha [batch, H, W], background: 3 HOST floats read during the call; inputs in [0, 1], nothing is clamped.   */
+int gsplat_composite_target(const float* rgb, const float* alpha, const float* background, int64_t batch, int32_t H, int32_t W,
+                            float* out, void* stream);
+
 /* ---- next row 2: the optimiser step of scripts/train.py:394-401, 536-538 ---------------------
  * gsplat_clip_grad_norm = torch.nn.utils.clip_grad_norm_ on one tensor: coef_and_norm[2] (device) receives
  * (min(1, max_norm / (||grad|| + 1e-6)), ||grad||); nothing is scaled yet and nothing is read back to the host.

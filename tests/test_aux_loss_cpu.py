@@ -1,0 +1,206 @@
+"""CPU checks of training with a background, an opacity target and depth maps: the float64 oracle of the
+auxiliary loss against hand-computed cases and autograd, the dataset round trip, TrainConfig validation, the random background, and
+the host-side argument refusals of the three new entries."""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+from tests import aux_loss_oracle as alo
+
+PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
+abi = importlib.import_module(PKG + "._abi")
+data = importlib.import_module(PKG + ".data")
+training = importlib.import_module(PKG + ".training")
+NAN, INF = float("nan"), float("inf")
+
+
+# ---- the oracle ------------------------------------------------------------------------------------------------------------------
+
+def test_oracle_matches_a_hand_computed_2x2_case():
+    """Pixel (0,0) has both terms; (0,1) an invalid depth (0); (1,0) is an empty pixel (A = D = 0) under a valid depth; (1,1) has
+    A == M and a NaN depth.  n = 4, n_v = 2."""
+    A = torch.tensor([[0.5, 0.5], [0.0, 0.25]])
+    M = torch.tensor([[0.25, 1.0], [0.5, 0.25]])
+    Z = torch.tensor([[2.0, 0.0], [4.0, NAN]])
+    D = torch.tensor([[2.0, 3.0], [0.0, 1.0]])
+    r = alo.aux_loss(D, A, Z, M, lambda_depth=2.0, lambda_alpha=4.0, scale=0.5, upstream=3.0)
+    # L_alpha = (0.25 + 0.5 + 0.5 + 0) / 4, L_depth = (|2 - 0.5 * 2| + |0 - 0 * 4|) / 2
+    assert r["values"].tolist() == [0.5 * 0.3125, 0.5 * 0.5, 0.5 * (4 * 0.3125 + 2 * 0.5)]
+    assert r["valid"].tolist() == [[True, False], [True, False]]
+    assert r["grad_depth"].tolist() == [[1.5, 0.0], [0.0, 0.0]]                    # 0.5 * 3 * 2 / 2 at the one pixel with a residual
+    assert r["grad_alpha"].tolist() == [[1.5 - 3.0, -1.5], [-1.5, 0.0]]            # 0.5 * 3 * 4 / 4 = 1.5 per sign; - 1.5 * Z at (0,0)
+    assert np.isfinite(r["values"]).all() and torch.isfinite(r["grad_alpha"]).all()
+    # every kind of "no data": nothing counts, n_v = max(1, 0)
+    none = alo.aux_loss(D, A, torch.tensor([[0.0, -1.0], [NAN, INF]]), None)
+    assert none["values"].tolist() == [0.0, 0.0, 0.0] and not none["grad_depth"].any() and not none["grad_alpha"].any()
+    # a term without a target is off
+    only_a = alo.aux_loss(None, A, None, M, lambda_alpha=4.0)
+    assert only_a["values"].tolist() == [0.3125, 0.0, 1.25] and only_a["grad_depth"] is None
+    only_d = alo.aux_loss(D, A, Z, None, lambda_depth=2.0)
+    assert only_d["values"].tolist() == [0.0, 0.5, 1.0] and only_d["grad_alpha"].tolist() == [[-2.0, 0.0], [0.0, 0.0]]
+
+
+def test_oracle_composite_matches_a_hand_computed_pixel():
+    out = alo.composite_over(torch.tensor([[[0.5, 0.25, 1.0]]]), torch.tensor([[0.5]]), (1.0, 0.0, 0.5))
+    assert out.tolist() == [[[0.75, 0.125, 0.75]]]
+    rgb = torch.rand(3, 5, 3, generator=torch.Generator().manual_seed(1))
+    assert torch.equal(alo.composite_over(rgb, torch.ones(3, 5), (0.3, 0.6, 0.9)), rgb.double())
+    a = torch.rand(3, 5, generator=torch.Generator().manual_seed(2))
+    assert torch.equal(alo.composite_over(rgb, a, (0, 0, 0)), rgb.double() * a.double().unsqueeze(-1))
+
+
+@pytest.mark.parametrize("shape", alo.SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_oracle_matches_autograd_of_the_plain_formula_and_inputs_are_unambiguous(shape):
+    D, A, Z, M = alo.make_inputs(shape, seed=100 + len(shape) + 3 * shape[-1])
+    for ld, la, z, m in ((1.0, 1.0, Z, M), (0.3, 1.7, Z, M), (1.0, 1.0, None, M), (1.0, 1.0, Z, None)):
+        ref = alo.aux_loss(D, A, z, m, ld, la, scale=0.25, upstream=3.0)
+        alo.assert_unambiguous(ref)
+        d64, a64 = D.double().requires_grad_(True), A.double().requires_grad_(True)
+        total = alo.aux_loss_plain(d64, a64, None if z is None else z.double(), None if m is None else m.double(), ld, la, scale=0.25)
+        (3.0 * total).backward()
+        assert abs(float(total.detach()) - ref["values"][2]) <= 1e-14 * max(1.0, abs(ref["values"][2]))
+        assert torch.allclose(a64.grad, ref["grad_alpha"], rtol=1e-13, atol=1e-16)
+        if z is not None:
+            assert torch.allclose(d64.grad, ref["grad_depth"], rtol=1e-13, atol=1e-16)
+            assert bool((ref["grad_depth"][~ref["valid"]] == 0).all())
+    if np.prod(shape) > 500:          # the recipe: about a seventh exact zeros, about a fifth invalid depths
+        ref = alo.aux_loss(D, A, Z, M)
+        assert 0.03 < float((ref["res_alpha"] == 0).double().mean()) < 0.12
+        assert 0.12 < float((~ref["valid"]).double().mean()) < 0.28
+        assert bool(((A == 0) & (D == 0)).any())
+
+
+# ---- the dataset -----------------------------------------------------------------------------------------------------------------
+
+def test_dataset_round_trip_of_alpha_and_depth(tmp_path):
+    g = torch.Generator().manual_seed(4)
+    H, W, K = 12, 16, 2
+    images = [torch.randint(0, 256, (H, W, 3), generator=g).float() / 255 for _ in range(K)]
+    alphas = [torch.randint(0, 256, (H, W), generator=g).float() / 255 for _ in range(K)]
+    depths = [torch.rand(H, W, generator=g) * 5 for _ in range(K)]
+    for z in depths:
+        z[::3, ::4] = 0.0                                                       # no data
+    poses = np.tile(np.eye(4, dtype=np.float32), (K, 1, 1))
+    data.write_dataset(tmp_path, images, 20.0, 21.0, poses, alphas=alphas, depths=depths)
+    full = data.GaussianDataset(tmp_path, scale_factor=1.0, alpha=True, depth_dir='depth')
+    plain_keys = set(data.GaussianDataset(tmp_path, scale_factor=1.0)[0])
+    assert plain_keys == {'image', 'c2w', 'fx', 'fy', 'cx', 'cy', 'H', 'W', 'idx'}          # the default constructor: today's sample
+    for i in range(K):
+        s = full[i]
+        assert set(s) == plain_keys | {'alpha', 'depth'}
+        assert torch.equal(s['image'], images[i]) and s['image'].shape == (H, W, 3)
+        assert torch.equal(s['alpha'], alphas[i]) and torch.equal(s['depth'], depths[i])
+        assert torch.equal(data.GaussianDataset(tmp_path, scale_factor=1.0)[i]['image'], images[i])
+    half = data.GaussianDataset(tmp_path, scale_factor=0.5, alpha=True, depth_dir='depth')[0]
+    assert half['image'].shape == (6, 8, 3) and half['alpha'].shape == (6, 8) and half['depth'].shape == (6, 8) and (half['H'], half['W']) == (6, 8)
+    # bilinear at exactly half size = the mean of each 2 x 2 block; nearest = one of the source values: zeros do not bleed
+    assert torch.allclose(half['alpha'], alphas[0].reshape(6, 2, 8, 2).mean(dim=(1, 3)), atol=1e-6)
+    assert torch.equal(half['depth'], depths[0][::2, ::2])
+    assert bool((half['depth'] == 0).any())
+    # a file without an alpha channel: 1.0 everywhere
+    data.write_dataset(tmp_path / "rgb", images, 20.0, 21.0, poses)
+    s = data.GaussianDataset(tmp_path / "rgb", scale_factor=1.0, alpha=True)[0]
+    assert torch.equal(s['alpha'], torch.ones(H, W)) and 'depth' not in s
+
+
+# ---- TrainConfig -----------------------------------------------------------------------------------------------------------------
+
+class _Model:
+    """All Trainer.__init__ reads of a model: the six parameter tensors (on the CPU: nothing is rendered here)."""
+
+    def __init__(self):
+        for k, w in (("pos", 3), ("opacity_raw", 0), ("f_dc", 3), ("f_rest", 45), ("scale_raw", 3), ("q_raw", 4)):
+            setattr(self, k, torch.nn.Parameter(torch.zeros((4, w) if w else (4,))))
+
+
+@pytest.mark.parametrize("bad", [dict(background="white"), dict(background=(1.0, 1.0)), dict(background=(0.5, 0.5, 1.5)),
+                                 dict(background=(0.1, -0.1, 0.2)), dict(background=0.5), dict(background=("a", "b", "c")),
+                                 dict(background_seed=1.5), dict(lambda_alpha=-0.1), dict(lambda_depth=-1.0), dict(lambda_depth=INF),
+                                 dict(lambda_alpha=NAN), dict(lambda_alpha="1"), dict(lambda_depth=True)],
+                         ids=lambda d: "-".join(f"{k}={v}" for k, v in d.items()))
+def test_trainconfig_validation_errors(bad):
+    with pytest.raises(ValueError, match=next(iter(bad))):
+        training.Trainer(_Model(), training.TrainConfig(**bad))
+
+
+def test_trainconfig_defaults_are_off():
+    cfg = training.TrainConfig()
+    assert cfg.background is None and cfg.background_seed == 0 and cfg.lambda_alpha == 0.0 and cfg.lambda_depth == 0.0
+
+
+def test_random_background_is_a_function_of_seed_and_iteration_only():
+    def colours(seed, its, **kw):
+        tr = training.Trainer(_Model(), training.TrainConfig(background="random", background_seed=seed, **kw))
+        return [tr.background(it) for it in its]
+
+    a = colours(3, (0, 1, 2, 7))
+    assert a == colours(3, (0, 1, 2, 7), lambda_alpha=0.5, densify_seed=9)           # nothing else enters
+    assert a[3] == colours(3, (7,))[0]                                               # no hidden state: not the number of calls before
+    torch.manual_seed(123)
+    assert a == colours(3, (0, 1, 2, 7))                                             # nor the global generator
+    assert len(set(a)) == 4 and a != colours(4, (0, 1, 2, 7))
+    assert all(len(c) == 3 and all(0.0 <= x < 1.0 for x in c) for c in a)
+    assert training.Trainer(_Model(), training.TrainConfig(background=[1, 0.5, 0])).background(5) == (1.0, 0.5, 0.0)
+    assert training.Trainer(_Model(), training.TrainConfig()).background(5) is None
+
+
+# ---- the entries' argument checks (host only: nothing is launched) -----------------------------------------------------------------
+
+def _host_words(n=16):
+    buf = (C.c_float * n)()
+    return buf, C.cast(buf, C.c_void_p)
+
+
+def _refused(lib, status, name):
+    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, status)
+    assert name.encode() in lib.gsplat_last_error(), (name, lib.gsplat_last_error())
+
+
+def test_aux_entries_reject_bad_arguments_on_the_host():
+    """A NULL required pointer, H, W or batch <= 0 and batch > 65535 come back as GSPLAT_ERR_BAD_ARG with a message naming the entry.
+    Required: alpha, values / grad_alpha, scratch; depth (and grad_depth in the backward) once a target depth is given."""
+    lib = abi.lib()
+    keep, p = _host_words()
+    bg = (C.c_float * 3)(1.0, 1.0, 1.0)
+
+    def fwd(depth=p, alpha=p, tdepth=p, talpha=p, batch=1, H=4, W=4, values=p, total=p, scratch=p):
+        return lib.gsplat_aux_loss_forward(depth, alpha, tdepth, talpha, batch, H, W, 1.0, 1.0, 1.0, values, total, scratch, None)
+
+    def bwd(depth=p, alpha=p, tdepth=p, talpha=p, batch=1, H=4, W=4, upstream=p, gdepth=p, galpha=p, scratch=p):
+        return lib.gsplat_aux_loss_backward(depth, alpha, tdepth, talpha, batch, H, W, 1.0, 1.0, 1.0, upstream, gdepth, galpha, scratch, None)
+
+    def comp(rgb=p, alpha=p, background=bg, batch=1, H=4, W=4, out=p):
+        return lib.gsplat_composite_target(rgb, alpha, background, batch, H, W, out, None)
+
+    for fn, name, required in ((fwd, "gsplat_aux_loss_forward", ("alpha", "values", "scratch", "depth")),
+                               (bwd, "gsplat_aux_loss_backward", ("alpha", "galpha", "scratch", "depth", "gdepth")),
+                               (comp, "gsplat_composite_target", ("rgb", "alpha", "background", "out"))):
+        for arg in required:
+            _refused(lib, fn(**{arg: None}), name)
+        for bad in (dict(H=0), dict(H=-3), dict(W=0), dict(W=-1), dict(batch=0), dict(batch=-2), dict(batch=65536), dict(batch=1 << 40)):
+            _refused(lib, fn(**bad), name)
+    del keep
+
+
+def test_aux_loss_scratch_bytes_matches_the_documented_layout():
+    """[256 bytes: n_v as a double | three partial sums (floats) per workgroup of 1024 pixels, rounded up to 256 bytes]; -1 for a
+    size that is none."""
+    lib = abi.lib()
+    for batch, H, W in ((1, 1, 1), (3, 17, 33), (1, 32, 32), (1, 32, 33), (2, 1080, 1920), (1,) + alo.THREE_WORKGROUPS_PLUS_5, (65535, 16, 32)):
+        groups = (batch * H * W + 1023) // 1024
+        assert lib.gsplat_aux_loss_scratch_bytes(batch, H, W) == 256 + 256 * ((groups * 3 * 4 + 255) // 256)
+    assert lib.gsplat_aux_loss_scratch_bytes(1, *alo.THREE_WORKGROUPS_PLUS_5) == 256 + 256      # four workgroups: 48 bytes of partials
+    for batch, H, W in ((0, 4, 4), (1, 0, 4), (1, 4, 0), (-1, 4, 4), (1, -4, 4)):
+        assert lib.gsplat_aux_loss_scratch_bytes(batch, H, W) == -1
+
+
+def test_aux_loss_and_composite_have_no_cpu_fallback():
+    losses = importlib.import_module(PKG + ".losses")
+    z = torch.zeros
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        losses.aux_loss(z(4, 4), z(4, 4), z(4, 4), z(4, 4))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        losses.composite_over(z(4, 4, 3), z(4, 4), (1.0, 1.0, 1.0))
