@@ -48,12 +48,7 @@ def agree_on_views(n_local, group=None, views_per_rank=None, device=None):
 
 def any_rank(flag, group=None, device=None):
     """Logical OR of a host-side flag over the ranks (one tiny all-reduce; the caller has just synchronised anyway)."""
-    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
-        return int(bool(flag))
-    on_gpu = dist.get_backend(group) != "gloo"
-    t = torch.tensor([int(bool(flag))], dtype=torch.int32, device=device if on_gpu and device is not None else "cpu")
-    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
-    return int(t.item())
+    return agree_status(bool(flag), group, device)
 
 
 STATUS_OK, STATUS_REDO, STATUS_OFFSCREEN, STATUS_ERROR = 0, 1, 2, 3
@@ -200,12 +195,12 @@ class FactoredExchange:
     collective per step).  Works unchanged in a single process (no collective)."""
 
     SMALL = ("pos", "opacity_raw", "scale_raw", "q_raw")
+    route_kind = "factored"                      # (ops.gradient_route: what the render backward hands this consumer)
 
     def __init__(self, params, world_views, group=None, accumulate=None, force_collectives=False, equal_views=True, sh_degree=None):
         self.params, self.world_views, self.group = params, world_views, group
         self.equal_views = equal_views
-        self.logits, self.eyes, self._early = [], [], []
-        self._early = []                         # (gathered logits, gathered eyes, pending collectives) per local view
+        self.logits, self.eyes, self._early = [], [], []      # _early: (gathered logits, gathered eyes, pending collectives) per local view
         self._accumulate = accumulate
         self._force = force_collectives          # tests: issue the collectives even in a one-rank group
         self.n_added = 0                         # views handed in by the render backward (Trainer.step checks it against its views)

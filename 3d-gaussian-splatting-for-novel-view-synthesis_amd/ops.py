@@ -16,15 +16,20 @@ its antialiased variant.
 
 PyTorch is plumbing here (device memory, streams, autograd bookkeeping); all arithmetic runs in the HIP library.
 There is no CPU path: CPU tensors, or a missing library, raise.
+
+The render entries turn their arguments into ONE immutable FrameSpec (_frame_spec: camera, mode, input names), which the forward
+pass keeps on the frame (_Frame.spec) for the backward pass; the facts of one autograd call (pose, need_grad, route) lie beside it.
 """
+import collections
 import contextlib
 import contextvars
 import ctypes as C
+import dataclasses
 import weakref
 
 import torch
 
-from . import _abi, dp
+from . import _abi
 
 OFFSCREEN_MSG = "All projected points are off-screen"      # reference render.py:236
 
@@ -261,38 +266,37 @@ class DeferredChecks:
     hands them to another frame (_Workspace.next_pinned): no block is ever reused unread."""
 
     def __init__(self):
-        self.pending = []          # [pinned counter block, event, capacity, device, capacity key, (ring key, slot)]
+        self.pending = []          # _Unread, one per frame whose counters have not been looked at, in frame order
         self.counts = []
         self._overflow = self._offscreen = False
 
     def add(self, pinned, event, capacity, device, ckey, slot):
-        self.pending.append((pinned, event, capacity, device, ckey, slot))
+        self.pending.append(_Unread(pinned, event, capacity, device, ckey, slot))
         if len(self.pending) >= PINNED_SLOTS // 2:           # long sequences: look at the oldest frames before their pinned
             self._drain(len(self.pending) // 2)              # counter blocks come round again (they finished long ago)
 
     def _drain(self, count):
-        global _last_counts, _last_binned
-        for pinned, ev, cap, dev, ckey, slot in self.pending[:count]:
-            ev.synchronize()
-            counts = _abi.Counts.from_buffer_copy(pinned.numpy().tobytes())
+        for entry in self.pending[:count]:
+            entry.event.synchronize()
+            counts = _abi.Counts.from_buffer_copy(entry.pinned.numpy().tobytes())
             self.counts.append(counts)
-            _ws.note_pairs(ckey, counts.n_binned)
-            self._overflow |= cap is not None and counts.n_binned > cap
+            _ws.note_pairs(entry.ckey, counts.n_binned)
+            self._overflow |= entry.capacity is not None and counts.n_binned > entry.capacity
             self._offscreen |= _abi.lib().gsplat_classify_counts(C.byref(counts)) == _abi.GSPLAT_SCENE_ALL_OFFSCREEN
-            _last_counts = (counts.n_survivors, counts.n_visible, int(counts.n_pairs))
-            _last_binned = int(counts.n_binned)
-            _ws.recycle_event(dev, ev)
-            owners = _ws.owners.get(slot[0])
+            _note_counts(counts)
+            _ws.recycle_event(entry.device, entry.event)
+            ring_key, index = entry.slot
+            owners = _ws.owners.get(ring_key)
             if owners is not None:
-                ref = owners.get(slot[1])
+                ref = owners.get(index)
                 if ref is not None and ref() is self:
-                    del owners[slot[1]]
+                    del owners[index]
         del self.pending[:count]
 
     def _release_slot(self, ring_key, index):
         """The ring is about to hand slot `index` to another frame: read everything up to the frame that holds it."""
         for k, entry in enumerate(self.pending):
-            if entry[5] == (ring_key, index):
+            if entry.slot == (ring_key, index):
                 self._drain(k + 1)
                 return
 
@@ -320,6 +324,10 @@ class DeferredChecks:
         return self.counts
 
 
+# a frame whose counters are still unread (between the halves of its forward pass, or in a DeferredChecks): its pinned counter block,
+# the event recorded behind the counters, the pair capacity its buffers were sized with (None: it waits for its own count), its device
+# and capacity_key(), and slot = (ring key, index) of the block in the ring, ring key = (device type, device index, stream)
+_Unread = collections.namedtuple("_Unread", "pinned event capacity device ckey slot")
 _deferred_stack = []
 forward_modes = {"waited": 0, "deferred": 0}     # forward passes that waited for their counters / that did not (diagnostics, tests)
 composite_calls = {"forward": 0, "backward": 0}  # passes queued through ONE library call (gsplat_forward_deferred / gsplat_backward)
@@ -344,125 +352,143 @@ def run_deferred(fn, attempts=4):
     raise RuntimeError(f"the pair buffers overflowed {attempts} times in a row")
 
 
-def _make_gaussians(n, pos, opacity_raw, color=None, sigma=None, scale_raw=None, q_raw=None, f_dc=None, f_rest=None):
-    return _abi.Gaussians(n, _p(pos), _p(opacity_raw), _p(color), _p(sigma), _p(scale_raw), _p(q_raw), _p(f_dc), _p(f_rest))
-
-
 _sh_jacobian = True      # tests / ablations switch it off: the backward then reads the SH coefficients again (same gradients)
 _composite = True        # tests / ablations switch it off: a deferred frame then goes through the separate library calls
+_FUSED_NAMES = ("pos", "opacity_raw", "scale_raw", "q_raw", "f_dc", "f_rest")
+_PLAIN_NAMES = ("pos", "opacity_raw", "color", "sigma")
+_ROW_SHAPE = dict(pos=(3,), color=(3,), sigma=(3, 3), scale_raw=(3,), q_raw=(4,), f_dc=(3,), f_rest=(45,))      # per Gaussian
+_SH = ("f_dc", "f_rest")
+_GRAD_FIELDS = tuple(name for name, _ in _abi.GaussianGrads._fields_)
+_INPUT_FIELDS = tuple(name for name, _ in _abi.Gaussians._fields_[1:])        # (behind n: one address per input, NULL where the entry has none)
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class FrameSpec:
+    """The render mode of one public call: built once, by _frame_spec(), and never changed -- the forward pass, the frame and every
+    backward route read the same object, so they cannot disagree.  `view` carries the C fields only."""
+    __slots__ = ("view", "fused", "grad_mode", "aux", "background", "sh_degree", "filter", "names")
+    view: _abi.View
+    fused: bool            # render_gaussians / render_frames (six raw parameter tensors) or render (colour and Sigma given)
+    grad_mode: bool        # torch.is_grad_enabled() of the caller (the autograd node's forward() always runs with grad disabled)
+    aux: bool              # the call also returns the depth and the opacity map
+    background: tuple      # (r, g, b) the image is composited over, or None
+    sh_degree: int         # of the forward pass; 3 when not fused
+    filter: int            # the GSPLAT_FILTER_* bits (lowpass, antialias): the same bits in the flags of every projection entry
+    names: tuple           # the tensor inputs of the entry, in the order _RenderFn takes them and returns their gradients
+    H = property(lambda self: self.view.H)
+    W = property(lambda self: self.view.W)
+    is_aux = property(lambda self: self.aux or self.background is not None)      # the aux variant of the raster kernels
+
+    def __eq__(self, other):                           # (a ctypes structure compares by identity: compare the camera's bytes)
+        key = lambda s: (bytes(s.view),) + tuple(getattr(s, k) for k in FrameSpec.__slots__[1:])
+        return isinstance(other, FrameSpec) and key(self) == key(other)
+
+
+def _frame_spec(fused, H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff, *,
+                aux=False, background=None, sh_degree=3, lowpass=0.0, antialias=False):
+    """The FrameSpec of a public call, for all three entries; every bad mode argument is refused here (ValueError), in one order: SH
+    degree (fused entries), filter, T, background.  Needs no GPU and queues nothing."""
+    if fused:
+        _abi.sh_bands_dropped(sh_degree)
+    bits = _abi.filter_bits(lowpass, antialias)
+    # every T of the reference is accepted: the image does not depend on it (SURVEY.md 8a); T only sets the reference's
+    # tile rectangles, i.e. the reported pair count P.  The kernels always bin 16 x 8-pixel lists.
+    if int(T) < 1:
+        raise ValueError("tile size T must be >= 1")
+    # H, W may arrive as 0-d tensors from DataLoader collate (reference scripts/train.py:499)
+    view = _abi.make_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff)
+    if background is not None:             # a constant (3 numbers, a sequence or a tensor): it gets no gradient
+        vals = background.detach().reshape(-1).tolist() if isinstance(background, torch.Tensor) else list(background)
+        if len(vals) != 3:
+            raise ValueError("background must hold 3 numbers (r, g, b)")
+        background = tuple(float(x) for x in vals)
+    return FrameSpec(view, fused, torch.is_grad_enabled(), bool(aux), background, sh_degree if fused else 3, bits,
+                     _FUSED_NAMES if fused else _PLAIN_NAMES)
 
 
 class _Frame:
-    """Everything the backward pass needs from one forward call.  A frame queued by gsplat_forward_deferred keeps ONE arena
-    (project_state | bin_state | accum | grad2d, carved by the library); one that went through the separate calls keeps them
-    as separate buffers."""
-    __slots__ = ("view", "n", "n_pairs", "proj_state", "bin_state", "accum", "fused", "inputs", "c2w", "empty", "grad2d", "sh_jacobian",
-                 "arena", "gaussians", "dirty", "src_ptrs", "route", "pose", "aux", "background", "accum_aux", "stats", "sh_degree", "filter")
+    """Everything the backward pass needs from one forward call: the call's FrameSpec (`spec`: camera and mode), the converted inputs
+    by name, and the facts of this autograd call -- `need_grad`, `pose` (the backward also forms dL/dc2w), `stats` (the
+    densify_stats() record, if any) and the gradient route (`route`, `route_kind`: _route_of).  A frame queued by
+    gsplat_forward_deferred keeps ONE arena (project_state | bin_state | accum | grad2d, carved by the library); one that went
+    through the separate calls keeps them as separate buffers."""
+    __slots__ = ("spec", "n", "n_pairs", "proj_state", "bin_state", "accum", "inputs", "c2w", "empty", "grad2d", "sh_jacobian", "arena",
+                 "gaussians", "dirty", "src_ptrs", "route", "route_kind", "pose", "need_grad", "accum_aux", "stats")
 
 
-class _Pending:
-    """A forward call between its two halves: projection queued, counters not read yet."""
-    __slots__ = ("frame", "gaussians", "pinned", "ready", "device", "stream", "capacity", "key", "st", "ckey", "slot")
-
-
-def _convert_inputs(fused, n, pos, opacity_raw, c2w, a, b, c, d):
-    pos32 = _f32(pos, (n, 3), "pos")
-    opa32 = _f32(opacity_raw if opacity_raw.dim() == 1 else opacity_raw.reshape(-1), (n,), "opacity_raw")
-    c2w32 = _f32(c2w, (4, 4), "c2w")
-    if fused:
-        ins = dict(scale_raw=_f32(a, (n, 3), "scale_raw"), q_raw=_f32(b, (n, 4), "q_raw"), f_dc=_f32(c, (n, 3), "f_dc"),
-                   f_rest=_f32(d, (n, 45), "f_rest"))
-    else:
-        ins = dict(color=_f32(a, (n, 3), "color"), sigma=_f32(b, (n, 3, 3), "sigma"))
-    return pos32, opa32, c2w32, ins
-
-
-def _new_frame(fused, view, n, pos32, opa32, c2w32, ins, c, d):
-    fr = _Frame()
-    fr.view, fr.n, fr.fused, fr.c2w, fr.empty, fr.sh_jacobian = view, n, fused, c2w32, False, False
-    fr.inputs = dict(pos=pos32, opacity_raw=opa32, **ins)
-    fr.arena = fr.gaussians = fr.proj_state = fr.bin_state = fr.accum = fr.grad2d = fr.route = None
-    fr.dirty = fr.pose = fr.aux = False
-    fr.background = fr.accum_aux = fr.stats = None
-    # the SH degree of the forward pass, kept on the frame: every backward route reads it here, so it cannot differ
-    fr.sh_degree = view.sh_degree if fused else 3
-    # ... and the GSPLAT_FILTER_* bits (lowpass, antialias): the same bits in the flags of every entry that runs the projection math
-    fr.filter = view.filter
-    # the caller's own SH tensors (before any dtype / layout conversion): what dp.FactoredExchange.owns() compares
-    fr.src_ptrs = (c.data_ptr(), d.data_ptr()) if fused else None
-    return fr
-
-
-def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=False):
-    """First half of the forward pass: everything up to (not including) the host's wait for the counters.  Returns
-    (pending, None), or (None, result) when nothing is left to do: zero Gaussians, or -- inside a deferred_checks() block once a
-    pair capacity is known for this image size -- the whole forward pass was queued by ONE library call
-    (gsplat_forward_deferred) and the result is there.  view.pose (set by _RenderFn): the backward pass will also form dL/dc2w
-    (a pose frame: always the separate library calls, never a gradient route).  view.aux / view.background (set by render() and
-    render_gaussians()): an aux frame -- depth and opacity maps, or an image over a background -- which takes the separate library
-    calls like a pose frame; its result is the tuple (image, depth, alpha), depth and alpha None without aux=True."""
-    pose = getattr(view, "pose", False)
-    if pose and _route.get() is not None:
+def _forward_begin(spec, c2w, tensors, pose=False, need_grad=False):
+    """First half of the forward pass of `tensors` ({name: tensor} for spec.names): everything up to (not including) the host's wait
+    for the counters.  Returns (pending, None), or (None, (result, frame, counts)) when nothing is left to do: zero Gaussians, or --
+    inside a deferred_checks() block once a pair capacity is known for this image size -- the whole forward pass was queued by ONE
+    library call (gsplat_forward_deferred) and the result is there.  The result is always (image, depth, alpha), the maps None where
+    the frame has none (_deliver turns it into what the caller gets).  pose (from _RenderFn): the backward pass will also form
+    dL/dc2w -- a pose frame: always the separate library calls, never a gradient route.  spec.is_aux: an aux frame -- depth and
+    opacity maps, or an image over a background -- which takes the separate library calls like a pose frame."""
+    route = _route.get()
+    if pose and route is not None:
         raise RuntimeError("a camera-pose gradient (c2w.requires_grad) is not available inside a gradient_route() block "
                            "(factored exchange, folded f_rest step, accumulate_grads): render the pose frame outside it")
-    auxf = _is_aux(view)
+    auxf = spec.is_aux
     # (the factored exchange takes an aux frame: it goes through the separate calls, whose backward forms the logit gradients from
     #  grad2d whatever filled it; the other two routes live on the composite entries, which have no aux variant)
-    if auxf and _route.get() is not None and not isinstance(_route.get(), dp.FactoredExchange):
+    if auxf and route is not None and route.route_kind != FACTORED:
         raise RuntimeError("depth / opacity maps and a background (aux=True, background=...) are not available inside a gradient_route() "
                            "block (factored exchange, folded f_rest step, accumulate_grads): render the frame outside it")
+    pos = tensors["pos"]
     stats = _stats_record(pos)              # (checked before anything else: a wrong record is refused even where nothing is rendered)
     lib = _abi.lib()
     dev = pos.device
-    n = pos.shape[0]
-    pos32, opa32, c2w32, ins = _convert_inputs(fused, n, pos, opacity_raw, c2w, a, b, c, d)
-    fr = _new_frame(fused, view, n, pos32, opa32, c2w32, ins, c, d)
-    fr.pose = pose
-    fr.stats = stats if need_grad else None
-    fr.aux, fr.background = auxf, view.background if auxf else None
+    fr = _Frame()
+    fr.spec, fr.pose, fr.need_grad, fr.stats = spec, pose, need_grad, stats if need_grad else None
+    fr.route, fr.route_kind = None, PLAIN       # (until _route_of finds a consumer for this frame)
+    n, view, opa = pos.shape[0], spec.view, tensors["opacity_raw"]
+    fr.n, fr.inputs = n, dict(pos=_f32(pos, (n, 3), "pos"), opacity_raw=_f32(opa if opa.dim() == 1 else opa.reshape(-1), (n,), "opacity_raw"))
+    c2w32 = fr.c2w = _f32(c2w, (4, 4), "c2w")
+    for name in spec.names[2:]:
+        fr.inputs[name] = _f32(tensors[name], (n,) + _ROW_SHAPE[name], name)
+    fr.arena = fr.gaussians = fr.proj_state = fr.bin_state = fr.accum = fr.grad2d = fr.accum_aux = None
+    fr.empty = fr.sh_jacobian = fr.dirty = False
+    # the caller's own SH tensors (before any dtype / layout conversion): what dp.FactoredExchange.owns() compares
+    fr.src_ptrs = (tensors["f_dc"].data_ptr(), tensors["f_rest"].data_ptr()) if spec.fused else None
     if n == 0:      # nothing survives by construction: the reference returns the zero image (render.py:109-112)
         fr.empty = True
-        fr.route = _route_of(fr, False) if need_grad else None
-        return None, (_empty_result(view, dev), fr, _abi.Counts(0, 0, 0, 0, 0, 0))
-    g = _make_gaussians(n, pos32, opa32, **ins)
-    ckey = capacity_key(dev, view, n)
+        _route_of(fr, False)
+        return None, (_empty_result(spec, dev), fr, _abi.Counts(0, 0, 0, 0, 0, 0))
+    g = fr.gaussians = _abi.Gaussians(n, *map(_p, map(fr.inputs.get, _INPUT_FIELDS)))      # (addresses of fr.inputs, which the frame keeps)
+    ckey = capacity_key(dev, spec, n)
     capacity = _ws.pair_capacity(ckey) if _deferred_stack else 0
     deferred = capacity > 0
     if torch.cuda.current_device() != dev.index:
         torch.cuda.set_device(dev)            # (a context manager per call costs more than the call: the one-process-per-GPU host never switches)
-    stream = torch.cuda.current_stream(dev)                       # looked up ONCE per forward pass
-    sp = stream.cuda_stream
+    sp = torch.cuda.current_stream(dev).cuda_stream               # looked up ONCE per forward pass
     key = (dev.type, dev.index, sp)
     st = C.c_void_p(sp)
     counters = _ws.get_counter_block(dev, _COUNTER_BYTES or _counter_bytes(lib), key)
-    fr.sh_jacobian = bool(fused and need_grad and _sh_jacobian)   # 48 bytes per Gaussian that spare the backward the 192 bytes of SH coefficients
+    fr.sh_jacobian = bool(spec.fused and need_grad and _sh_jacobian)   # 48 bytes per Gaussian that spare the backward the 192 bytes of SH coefficients
     chk = _deferred_stack[-1] if deferred else None
     pinned, slot = _ws.next_pinned(dev, key, chk)
     ready = _ws.get_event(dev, fresh=deferred, key=key)
     wants_stages = _timer is not None and _timer.wants(_FORWARD_STAGES)
     composite = deferred and _composite and not wants_stages and not pose and not auxf
-    fr.route = _route_of(fr, composite) if need_grad else None
+    _route_of(fr, composite)
     if composite:
         # ---- the whole forward pass in one call, on one arena
-        H, W = view.H, view.W
+        H, W = spec.H, spec.W
         flags = (_abi.GSPLAT_FRAME_BACKWARD if need_grad else 0) | (0 if _sh_jacobian else _abi.GSPLAT_FRAME_NO_SH_JACOBIAN)
         frame_bytes, scratch_bytes = _ws.frame_sizes(lib, n, capacity, view, flags)
-        flags |= _FRAME_DEGREE[fr.sh_degree] | fr.filter
+        flags |= _FRAME_DEGREE[spec.sh_degree] | spec.filter
         fr.arena = torch.empty(frame_bytes, dtype=torch.uint8, device=dev)
         image = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
         scratch = _ws.get_scratch(dev, scratch_bytes, key)
-        fr.gaussians, fr.n_pairs = g, capacity
+        fr.n_pairs = capacity
         _abi.check(lib.gsplat_forward_deferred(g, c2w32.data_ptr(), view, fr.arena.data_ptr(), frame_bytes, capacity, counters.data_ptr(),
                                                counters.numel(), scratch.data_ptr(), scratch.numel(), pinned.data_ptr(), ready.cuda_event,
                                                image.data_ptr(), flags, st), "gsplat_forward_deferred")
         forward_modes["deferred"] += 1
         composite_calls["forward"] += 1
         chk.add(pinned, ready, capacity, dev, ckey, (key, slot))
-        return None, (image, fr, None)
-    pend = _Pending()
-    pend.frame, pend.gaussians, pend.device, pend.stream, pend.key, pend.st = fr, g, dev, stream, key, st
-    pend.capacity = capacity if deferred else None
-    pend.pinned, pend.ready, pend.ckey, pend.slot = pinned, ready, ckey, (key, slot)
+        return None, ((image, None, None), fr, None)
+    pend = fr, _Unread(pinned, ready, capacity if deferred else None, dev, ckey, (key, slot))
     fr.proj_state = torch.empty(lib.gsplat_project_state_bytes(n, C.byref(view)), dtype=torch.uint8, device=dev)
     # the counters go straight into the pinned block (mapped into the device's address space: no copy operation);
     # a frame that will not wait for them evaluates the SH colour inside the projection kernel and lets the first binning
@@ -470,7 +496,7 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
     flags = _abi.GSPLAT_PROJECT_COUNTS_MAPPED | ((_abi.GSPLAT_PROJECT_COLOUR_FUSED | _abi.GSPLAT_PROJECT_COUNTS_LATE) if deferred else 0)
     if fr.sh_jacobian:
         flags |= _abi.GSPLAT_PROJECT_SAVE_SH_JACOBIAN
-    flags |= _PROJECT_DEGREE[fr.sh_degree] | fr.filter
+    flags |= _PROJECT_DEGREE[spec.sh_degree] | spec.filter
     with _stage("project"):
         _abi.check(lib.gsplat_project(C.byref(g), _p(c2w32), C.byref(view), _p(fr.proj_state), _p(counters),
                                       counters.numel(), C.c_void_p(pinned.data_ptr()), C.c_void_p(ready.cuda_event),
@@ -478,23 +504,24 @@ def _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad=Fal
     return pend, None
 
 
-def _is_aux(view):
-    return view.aux or view.background is not None
-
-
-def _empty_result(view, dev):
-    """What a frame without a survivor returns: the zero image; an aux frame (image, depth, alpha) -- the image is the clamped
-    background where one is given, the maps are zero (None without aux=True)."""
-    H, W = view.H, view.W
-    if not _is_aux(view):
-        return torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
-    if view.background is None:
+def _empty_result(spec, dev):
+    """(image, depth, alpha) of a frame without a survivor: the zero image -- the clamped background where one is given -- and zero
+    maps (None without aux=True)."""
+    H, W = spec.H, spec.W
+    if spec.background is None:
         image = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
     else:
-        image = torch.tensor(view.background, dtype=torch.float32, device=dev).clamp_(0.0, 1.0).expand(H, W, 3).contiguous()
-    if not view.aux:
+        image = torch.tensor(spec.background, dtype=torch.float32, device=dev).clamp_(0.0, 1.0).expand(H, W, 3).contiguous()
+    if not spec.aux:
         return image, None, None
     return image, torch.zeros((H, W), dtype=torch.float32, device=dev), torch.zeros((H, W), dtype=torch.float32, device=dev)
+
+
+def _deliver(spec, result, dtype=torch.float32):
+    """The one place the (image, depth, alpha) of the forward pass becomes what the caller gets: the image, or the triple with
+    aux=True (in `dtype`, the caller's)."""
+    out = tuple(t if t is None or t.dtype == dtype else t.to(dtype) for t in result)
+    return out if spec.aux else out[0]
 
 
 def _background_arg(background):
@@ -508,6 +535,7 @@ _PROJECT_DEGREE = tuple(_abi.GSPLAT_PROJECT_SH_DEGREE(d) for d in range(4))
 _FRAME_DEGREE = tuple(_abi.GSPLAT_FRAME_SH_DEGREE(d) for d in range(4))
 _BACKWARD_DEGREE = tuple(_abi.GSPLAT_BACKWARD_SH_DEGREE(d) for d in range(4))
 _FORWARD_STAGES = frozenset(("project", "bin", "raster_forward"))
+_BACKWARD_STAGES = frozenset(("raster_backward", "project_backward"))
 
 
 def _counter_bytes(lib):
@@ -516,30 +544,29 @@ def _counter_bytes(lib):
     return _COUNTER_BYTES
 
 
-def _forward_end(pend, need_grad):
-    """Second half: wait for the counters, size the pair buffers, bin, rasterise.  Must run with the same current stream
-    as the first half."""
+def _forward_end(fr, unread):
+    """Second half, of a call between its halves (projection queued, counters `unread`): wait for the counters, size the pair
+    buffers, bin, rasterise.  Must run with the same current stream as the first half.  Returns ((image, depth, alpha), frame, counts)."""
     lib = _abi.lib()
-    fr, dev = pend.frame, pend.device
-    view, n = fr.view, fr.n
-    H, W = view.H, view.W
-    st = pend.st                                 # (the same current stream as in the first half: the caller's contract)
+    spec, n, need_grad, dev = fr.spec, fr.n, fr.need_grad, unread.device
+    view, H, W = spec.view, spec.H, spec.W
+    key = unread.slot[0]                         # (device, stream) of the first half: the same current stream is the caller's contract
+    st = C.c_void_p(key[2])
     # the one host wait of the forward pass: the pair count sizes the binning buffers, and the reference's empty /
     # off-screen conventions need the survivor counts.  Only the counters are waited for: the first binning kernel and
     # (fused inputs) the SH colour pass are queued behind them and run during this round trip.
-    image = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-    if pend.capacity is not None:
+    if unread.capacity is not None:
         # deferred: no wait.  Buffers of the capacity kept from earlier frames; the kernels read the real count on the
         # device; the host looks at the counters in DeferredChecks.verify()
         counts = None
-        fr.n_pairs = int(pend.capacity)
+        fr.n_pairs = int(unread.capacity)
         forward_modes["deferred"] += 1
-        _deferred_stack[-1].add(pend.pinned, pend.ready, fr.n_pairs, dev, pend.ckey, pend.slot)
+        _deferred_stack[-1].add(*unread)
     else:
-        pend.ready.synchronize()
+        unread.event.synchronize()
         forward_modes["waited"] += 1
-        counts = _abi.Counts.from_buffer_copy(pend.pinned.numpy().tobytes())
-        _ws.note_pairs(pend.ckey, counts.n_binned)
+        counts = _abi.Counts.from_buffer_copy(unread.pinned.numpy().tobytes())
+        _ws.note_pairs(unread.ckey, counts.n_binned)
         if _deferred_stack:                      # a frame that had to wait inside a deferred block (first of its size): verify() still
             chk = _deferred_stack[-1]            # returns one entry per frame, in frame order (the earlier frames are done by now)
             chk._drain(len(chk.pending))
@@ -550,10 +577,11 @@ def _forward_end(pend, need_grad):
         if scene == _abi.GSPLAT_SCENE_ALL_CULLED:
             fr.empty = True
             fr.proj_state = None
-            return (_empty_result(view, dev) if fr.aux else image.zero_()), fr, counts
+            return _empty_result(spec, dev), fr, counts
         fr.n_pairs = int(counts.n_binned)        # pairs actually binned (16 x 8 lists); counts.n_pairs = the reference's P
+    image = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
     fr.bin_state = torch.empty(lib.gsplat_bin_state_bytes(fr.n_pairs, C.byref(view)), dtype=torch.uint8, device=dev)
-    scratch = _ws.get_scratch(dev, lib.gsplat_bin_scratch_bytes(fr.n_pairs, C.byref(view)), pend.key)
+    scratch = _ws.get_scratch(dev, lib.gsplat_bin_scratch_bytes(fr.n_pairs, C.byref(view)), key)
     with _stage("bin"):
         _abi.check(lib.gsplat_bin(n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state), _p(scratch),
                                   scratch.numel(), st), "gsplat_bin")
@@ -562,25 +590,25 @@ def _forward_end(pend, need_grad):
     # there are so few lists that a wave's share would be long
     lists = ((W + 15) // 16) * ((H + 7) // 8)
     fr.grad2d = torch.empty((n, 16), dtype=torch.float32, device=dev) if need_grad and n <= 256 * lists else None
-    if fr.aux:
+    if spec.is_aux:
         # depth and opacity beside the colour (and the colour over the background): the aux variant of the raster kernel
-        depth = torch.empty((H, W), dtype=torch.float32, device=dev) if view.aux else None
-        alpha = torch.empty((H, W), dtype=torch.float32, device=dev) if view.aux else None
+        depth = torch.empty((H, W), dtype=torch.float32, device=dev) if spec.aux else None
+        alpha = torch.empty((H, W), dtype=torch.float32, device=dev) if spec.aux else None
         fr.accum_aux = torch.empty((H, W, 2), dtype=torch.float32, device=dev) if need_grad else None
         with _stage("raster_forward"):
             _abi.check(lib.gsplat_rasterize_forward_aux(n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state), _p(image),
                                                         _p(depth), _p(alpha), _p(fr.accum), _p(fr.accum_aux), _p(fr.grad2d),
-                                                        _background_arg(fr.background), st), "gsplat_rasterize_forward_aux")
+                                                        _background_arg(spec.background), st), "gsplat_rasterize_forward_aux")
         return (image, depth, alpha), fr, counts
     with _stage("raster_forward"):
         _abi.check(lib.gsplat_rasterize_forward(n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state),
                                                 _p(image), _p(fr.accum), _p(fr.grad2d), st), "gsplat_rasterize_forward")
-    return image, fr, counts
+    return (image, None, None), fr, counts
 
 
-def _forward_impl(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad):
-    pend, done = _forward_begin(fused, view, c2w, pos, opacity_raw, a, b, c, d, need_grad)
-    return done if pend is None else _forward_end(pend, need_grad)
+def _forward_impl(spec, c2w, tensors, pose, need_grad):
+    pend, done = _forward_begin(spec, c2w, tensors, pose, need_grad)
+    return done if pend is None else _forward_end(*pend)
 
 
 def _flat_like(ins):
@@ -614,7 +642,8 @@ class GradAccumulation:
     A render of other tensors, a frame that waited for its counters or a timed pass keep the ordinary backward.  assign()
     sets param.grad (views of the buffer) -- summing in what the ordinary backward may have produced for some views."""
 
-    NAMES = ("pos", "opacity_raw", "scale_raw", "q_raw", "f_dc", "f_rest")
+    NAMES = _FUSED_NAMES
+    route_kind = "summed"
 
     def __init__(self, params):
         self.params = {k: params[k] for k in self.NAMES}
@@ -656,11 +685,12 @@ def accumulate_grads(params):
 
 
 # The route of a frame's gradients: at most one consumer takes them in place of autograd's .grad, for the frames rendered inside
-# its gradient_route() block -- dp.FactoredExchange (data parallel: 3 colour-logit gradients per Gaussian instead of 48 SH ones,
-# DESIGN.md §7), optim._RestUpdate (the Adam step of f_rest inside the backward) or GradAccumulation (the views of an iteration
-# summed by the backward).  The slot is read once, in the caller's thread, when a frame is rendered (fr.route): the backward pass,
-# on autograd's thread, reads fr.route only.
+# its gradient_route() block.  A consumer names its kind (`route_kind`): dp.FactoredExchange is FACTORED (data parallel: 3 colour-logit
+# gradients per Gaussian instead of 48 SH ones), GradAccumulation SUMMED (the views of an iteration summed by the
+# backward), optim._RestUpdate FOLDED (the Adam step of f_rest inside the backward).  The slot is read once, in the caller's thread,
+# when a frame is rendered (_route_of): the backward pass, on autograd's thread, reads fr.route and fr.route_kind only.
 _route = contextvars.ContextVar("gsplat_gradient_route", default=None)
+PLAIN, FACTORED, SUMMED, FOLDED = "plain", "factored", "summed", "folded"       # PLAIN: no consumer, autograd gets every gradient
 
 
 @contextlib.contextmanager
@@ -675,151 +705,172 @@ def gradient_route(consumer):
 
 
 def _route_of(fr, composite):
-    """The active route's consumer if it takes the gradients of this frame (composite: queued by gsplat_forward_deferred), else None."""
+    """Decide, once, where the gradients of a frame go (composite: queued by gsplat_forward_deferred): fr.route = the active route's
+    consumer and fr.route_kind = its kind if it takes them, else (None, PLAIN)."""
     r = _route.get()
-    if r is None or not fr.fused:
-        return None
-    if isinstance(r, dp.FactoredExchange):
-        return r if r.owns(fr.inputs, fr.src_ptrs) else None
-    if not (composite and fr.sh_jacobian):
-        return None
-    if isinstance(r, GradAccumulation):
-        return r if r.matches(fr.inputs) else None
-    return r if r.matches(fr.inputs["f_rest"], fr.src_ptrs[1]) else None          # optim._RestUpdate
+    if r is None or not (fr.need_grad and fr.spec.fused):
+        return
+    kind = r.route_kind
+    if kind == FACTORED:
+        takes = r.owns(fr.inputs, fr.src_ptrs)
+    else:                                             # the other two routes live on the composite entries and the saved Jacobian
+        takes = composite and fr.sh_jacobian and (r.matches(fr.inputs) if kind == SUMMED else r.matches(fr.inputs["f_rest"], fr.src_ptrs[1]))
+    if takes:
+        fr.route, fr.route_kind = r, kind
 
 
-def _backward_call(fr, gi, gg, flags, st, det=None, glogit=None, rest=None):
-    """gsplat_backward on the frame's arena, or gsplat_backward_adam_rest with rest = (AdamGroup, beta1, beta2, eps)."""
-    lib = _abi.lib()
-    args = (fr.gaussians, fr.c2w.data_ptr(), fr.view, fr.arena.data_ptr(), fr.arena.numel(), fr.n_pairs, gi.data_ptr(), gg)
-    scratch = (det.data_ptr(), det.numel()) if det is not None else (None, 0)
-    if rest is None:
-        _abi.check(lib.gsplat_backward(*args, _p(glogit), *scratch, flags, st), "gsplat_backward")
-    else:
-        group, b1, b2, eps = rest
-        _abi.check(lib.gsplat_backward_adam_rest(*args, *scratch, flags, C.byref(group), b1, b2, eps, st), "gsplat_backward_adam_rest")
-
-
-_SH = ("f_dc", "f_rest")
-_GRAD_FIELDS = tuple(name for name, _ in _abi.GaussianGrads._fields_)
+class _BackwardPass:
+    """What _backward_impl prepares for either call sequence: the route kind of THIS pass, timed pass?, fp32 grad_image, the stream and
+    its handle, deterministic scratch, destination buffers (dict and C struct), SUMMED: add to them?, flag bits of the projection backward."""
+    __slots__ = ("kind", "staged", "gi", "stream", "st", "det", "dst", "gg", "add", "jac")
 
 
 def _backward_impl(fr, grad_image, need_params=True, grad_depth=None, grad_alpha=None):
     """Returns a dict name -> fp32 gradient tensor of the inputs of the forward call (a missing name: fr.route took that gradient);
     a pose frame adds "c2w" (fp32 [4, 4]).  need_params = False (pose frames): only the pose gradient is wanted.  An aux frame:
-    grad_image, grad_depth, grad_alpha are the upstream gradients of its three outputs, None where the loss does not read one."""
+    grad_image, grad_depth, grad_alpha are the upstream gradients of its three outputs, None where the loss does not read one.
+    Here: the prologue that the two call sequences share."""
+    spec, ins = fr.spec, fr.inputs
+    if fr.empty or fr.n == 0 or (spec.is_aux and grad_image is None and grad_depth is None and grad_alpha is None):
+        return _backward_empty(fr)
     lib = _abi.lib()
-    ins, route = fr.inputs, fr.route
     dev = ins["pos"].device
-    factored = isinstance(route, dp.FactoredExchange)
-    if fr.empty or fr.n == 0 or (fr.aux and grad_image is None and grad_depth is None and grad_alpha is None):
-        if factored:
-            route.add(torch.zeros((fr.n, 3), dtype=torch.float32, device=dev), fr.c2w[:3, 3], fr.sh_degree)
-        out = {k: torch.zeros_like(v) for k, v in ins.items() if not (factored and k in _SH)}
-        if fr.pose:
-            out["c2w"] = torch.zeros((4, 4), dtype=torch.float32, device=dev)
-        return out
-    gi = _f32(grad_image, (fr.view.H, fr.view.W, 3), "grad_image") if grad_image is not None else None
+    bp = _BackwardPass()
+    bp.gi = _f32(grad_image, (spec.H, spec.W, 3), "grad_image") if grad_image is not None else None
     if torch.cuda.current_device() != dev.index:
         torch.cuda.set_device(dev)
-    stream = torch.cuda.current_stream(dev)
-    st = C.c_void_p(stream.cuda_stream)
-    det_bytes = lib.gsplat_rasterize_backward_aux_scratch_bytes if fr.aux else lib.gsplat_rasterize_backward_scratch_bytes
-    det = _ws.get_scratch(dev, det_bytes(fr.n, fr.n_pairs), (dev.type, dev.index, stream.cuda_stream)) if _deterministic else None
-    staged = _timer is not None and _timer.wants(_BACKWARD_STAGES)
+    stream = bp.stream = torch.cuda.current_stream(dev)
+    bp.st = C.c_void_p(stream.cuda_stream)
+    det_bytes = lib.gsplat_rasterize_backward_aux_scratch_bytes if spec.is_aux else lib.gsplat_rasterize_backward_scratch_bytes
+    bp.det = _ws.get_scratch(dev, det_bytes(fr.n, fr.n_pairs), (dev.type, dev.index, stream.cuda_stream)) if _deterministic else None
+    staged = bp.staged = _timer is not None and _timer.wants(_BACKWARD_STAGES)
     # only known now, each sending the frame down the ordinary backward: a timed pass (phase by phase), a second pass through the
     # frame (views' sum), a step of f_rest already applied (folded step)
-    summing = isinstance(route, GradAccumulation)
-    summed = summing and not (staged or fr.dirty)
-    folded = route is not None and not (factored or summing or staged or route.applied)          # optim._RestUpdate
-    if summed:
-        dst, add = route.begin(stream)
+    kind = fr.route_kind
+    if kind == SUMMED and (staged or fr.dirty) or kind == FOLDED and (staged or fr.route.applied):
+        kind = PLAIN
+    bp.kind, bp.add = kind, False
+    if kind == SUMMED:
+        bp.dst, bp.add = fr.route.begin(stream)
     elif fr.pose and not need_params:
-        dst = {}
+        bp.dst = {}
     else:
-        dst = _flat_like({k: v for k, v in ins.items() if not (factored and k in _SH or folded and k == "f_rest")})
-    gg = _abi.GaussianGrads(*map(_p, map(dst.get, _GRAD_FIELDS)))
-    # (`jac` goes into the flags of every projection backward below: the saved Jacobian and the degree of the frame's forward pass)
-    jac = (_abi.GSPLAT_BACKWARD_SH_JACOBIAN if fr.sh_jacobian else 0) | _BACKWARD_DEGREE[fr.sh_degree] | fr.filter
-    if fr.arena is None:                       # ---- the frame went through the separate calls
-        zeroed = fr.grad2d is not None
-        grad2d = fr.grad2d if zeroed else torch.empty((fr.n, 16), dtype=torch.float32, device=dev)
-        fr.grad2d = None                       # a second backward through the same graph must not reuse a dirty buffer
-        if fr.aux:
+        bp.dst = _flat_like({k: v for k, v in ins.items() if not (kind == FACTORED and k in _SH or kind == FOLDED and k == "f_rest")})
+    bp.gg = _abi.GaussianGrads(*map(_p, map(bp.dst.get, _GRAD_FIELDS)))
+    # (`jac` goes into the flags of every projection backward: the saved Jacobian, the degree and the filter of the frame's forward pass)
+    bp.jac = (_abi.GSPLAT_BACKWARD_SH_JACOBIAN if fr.sh_jacobian else 0) | _BACKWARD_DEGREE[spec.sh_degree] | spec.filter
+    if fr.arena is None:
+        return _backward_separate(fr, bp, grad_depth, grad_alpha, need_params)
+    return _backward_arena(fr, bp)
+
+
+def _backward_empty(fr):
+    """A frame without a survivor, or an aux frame none of whose outputs the loss reads: zero gradients, nothing queued but them."""
+    dev = fr.inputs["pos"].device
+    factored = fr.route_kind == FACTORED
+    if factored:
+        fr.route.add(torch.zeros((fr.n, 3), dtype=torch.float32, device=dev), fr.c2w[:3, 3], fr.spec.sh_degree)
+    out = {k: torch.zeros_like(v) for k, v in fr.inputs.items() if not (factored and k in _SH)}
+    if fr.pose:
+        out["c2w"] = torch.zeros((4, 4), dtype=torch.float32, device=dev)
+    return out
+
+
+def _backward_separate(fr, bp, grad_depth, grad_alpha, need_params):
+    """The frame went through the separate calls (waited, timed, pose and aux frames): raster backward, statistics, logit gradients
+    for a factored exchange, projection backward.  Its route is FACTORED or PLAIN."""
+    lib = _abi.lib()
+    spec, dst, gg, jac, st, det = fr.spec, bp.dst, bp.gg, bp.jac, bp.st, bp.det
+    view, dev = spec.view, fr.inputs["pos"].device
+    zeroed = fr.grad2d is not None
+    grad2d = fr.grad2d if zeroed else torch.empty((fr.n, 16), dtype=torch.float32, device=dev)
+    fr.grad2d = None                       # a second backward through the same graph must not reuse a dirty buffer
+    gd = _f32(grad_depth, (spec.H, spec.W), "grad_depth") if grad_depth is not None else None
+    ga = _f32(grad_alpha, (spec.H, spec.W), "grad_alpha") if grad_alpha is not None else None
+    with _stage("raster_backward"):
+        if spec.is_aux:
             # (z, 1) as two more colour channels; column 9 of grad2d = dL/dz, which the projection backward picks up (DEPTH)
-            gd = _f32(grad_depth, (fr.view.H, fr.view.W), "grad_depth") if grad_depth is not None else None
-            ga = _f32(grad_alpha, (fr.view.H, fr.view.W), "grad_alpha") if grad_alpha is not None else None
-            with _stage("raster_backward"):
-                _abi.check(lib.gsplat_rasterize_backward_aux(fr.n, fr.n_pairs, C.byref(fr.view), _p(fr.proj_state), _p(fr.bin_state),
-                                                             _p(fr.accum), _p(fr.accum_aux), _p(gi), _p(gd), _p(ga),
-                                                             _background_arg(fr.background), _p(grad2d), int(zeroed), _p(det),
-                                                             det.numel() if det is not None else 0, st), "gsplat_rasterize_backward_aux")
+            _abi.check(lib.gsplat_rasterize_backward_aux(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state),
+                                                         _p(fr.accum), _p(fr.accum_aux), _p(bp.gi), _p(gd), _p(ga),
+                                                         _background_arg(spec.background), _p(grad2d), int(zeroed), _p(det),
+                                                         det.numel() if det is not None else 0, st), "gsplat_rasterize_backward_aux")
             jac |= _abi.GSPLAT_BACKWARD_DEPTH
         else:
-            with _stage("raster_backward"):
-                _abi.check(lib.gsplat_rasterize_backward(fr.n, fr.n_pairs, C.byref(fr.view), _p(fr.proj_state), _p(fr.bin_state),
-                                                         _p(fr.accum), _p(gi), _p(grad2d), int(zeroed), _p(det),
-                                                         det.numel() if det is not None else 0, st), "gsplat_rasterize_backward")
-        if fr.stats is not None:
-            _abi.check(lib.gsplat_densify_stats(fr.n, fr.n_pairs, C.byref(fr.view), _p(fr.proj_state), _p(grad2d), _p(fr.stats), st),
-                       "gsplat_densify_stats")
-        if factored:
-            # logit gradients first: the exchange may start on them while the projection backward runs
-            glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=dev)
-            _abi.check(lib.gsplat_logit_grad(fr.n, C.byref(fr.view), _p(fr.proj_state), _p(grad2d), _p(glogit), st), "gsplat_logit_grad")
-            route.add(glogit, fr.c2w[:3, 3], fr.sh_degree)
-        g = _make_gaussians(fr.n, **ins)
-        if fr.pose:
-            # the same chain rule plus dL/dc2w: per-block rows of the pose terms, added in a fixed order (no gradient rows if
-            # nothing but the pose is wanted)
-            gc2w = torch.empty((4, 4), dtype=torch.float32, device=dev)
-            nbytes = lib.gsplat_pose_scratch_bytes(fr.n)
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            with _stage("project_backward"):
-                _abi.check(lib.gsplat_project_backward_pose(C.byref(g), _p(fr.c2w), C.byref(fr.view), _p(fr.proj_state), _p(grad2d),
-                                                            C.byref(gg) if need_params else None, _p(gc2w), _p(scratch), nbytes, jac,
-                                                            st), "gsplat_project_backward_pose")
-            dst = dict(dst, c2w=gc2w)
-            return dst
+            _abi.check(lib.gsplat_rasterize_backward(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state),
+                                                     _p(fr.accum), _p(bp.gi), _p(grad2d), int(zeroed), _p(det),
+                                                     det.numel() if det is not None else 0, st), "gsplat_rasterize_backward")
+    if fr.stats is not None:
+        _abi.check(lib.gsplat_densify_stats(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(grad2d), _p(fr.stats), st),
+                   "gsplat_densify_stats")
+    if bp.kind == FACTORED:
+        # logit gradients first: the exchange may start on them while the projection backward runs
+        glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=dev)
+        _abi.check(lib.gsplat_logit_grad(fr.n, C.byref(view), _p(fr.proj_state), _p(grad2d), _p(glogit), st), "gsplat_logit_grad")
+        fr.route.add(glogit, fr.c2w[:3, 3], spec.sh_degree)
+    if fr.pose:
+        # the same chain rule plus dL/dc2w: per-block rows of the pose terms, added in a fixed order (no gradient rows if
+        # nothing but the pose is wanted)
+        gc2w = torch.empty((4, 4), dtype=torch.float32, device=dev)
+        nbytes = lib.gsplat_pose_scratch_bytes(fr.n)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         with _stage("project_backward"):
-            _abi.check(lib.gsplat_project_backward(C.byref(g), _p(fr.c2w), C.byref(fr.view), _p(fr.proj_state), _p(grad2d),
-                                                   C.byref(gg), jac, st), "gsplat_project_backward")
-        return dst
-    # ---- the frame was queued by gsplat_forward_deferred: one call for the whole backward pass (two, phase by phase)
+            _abi.check(lib.gsplat_project_backward_pose(C.byref(fr.gaussians), _p(fr.c2w), C.byref(view), _p(fr.proj_state), _p(grad2d),
+                                                        C.byref(gg) if need_params else None, _p(gc2w), _p(scratch), nbytes, jac,
+                                                        st), "gsplat_project_backward_pose")
+        return dict(dst, c2w=gc2w)
+    with _stage("project_backward"):
+        _abi.check(lib.gsplat_project_backward(C.byref(fr.gaussians), _p(fr.c2w), C.byref(view), _p(fr.proj_state), _p(grad2d),
+                                               C.byref(gg), jac, st), "gsplat_project_backward")
+    return dst
+
+
+def _backward_call(fr, bp, flags, det=None, glogit=None, rest=None):
+    """gsplat_backward on the frame's arena, or gsplat_backward_adam_rest with rest = (AdamGroup, beta1, beta2, eps)."""
+    lib = _abi.lib()
+    args = (fr.gaussians, fr.c2w.data_ptr(), fr.spec.view, fr.arena.data_ptr(), fr.arena.numel(), fr.n_pairs, bp.gi.data_ptr(), bp.gg)
+    scratch = (det.data_ptr(), det.numel()) if det is not None else (None, 0)
+    if rest is None:
+        _abi.check(lib.gsplat_backward(*args, _p(glogit), *scratch, flags, bp.st), "gsplat_backward")
+    else:
+        group, b1, b2, eps = rest
+        _abi.check(lib.gsplat_backward_adam_rest(*args, *scratch, flags, C.byref(group), b1, b2, eps, bp.st), "gsplat_backward_adam_rest")
+
+
+def _backward_arena(fr, bp):
+    """The frame was queued by gsplat_forward_deferred: one call for the whole backward pass (two, phase by phase, for a factored
+    exchange or a timed pass)."""
+    kind, route, jac, det = bp.kind, fr.route, bp.jac, bp.det
     flags = jac | (_abi.GSPLAT_BACKWARD_GRAD2D_DIRTY if fr.dirty else 0)
     fr.dirty = True                            # a second backward through the same graph must not reuse a dirty buffer
-    if summed:
-        # the views of an iteration summed in the accumulation's own buffer by the projection backward: autograd gets no gradient
-        _backward_call(fr, gi, gg, flags | (_abi.GSPLAT_BACKWARD_ACCUMULATE if add else 0), st, det)
-        route.done(stream)
-    elif folded:
-        # the Adam step of f_rest inside the projection backward: its 192 bytes of gradient per Gaussian are never written
-        _backward_call(fr, gi, gg, flags, st, det, rest=route.begin())
-        route.commit()
-    elif factored or staged:
-        glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=dev) if factored else None
+    if kind == FACTORED or bp.staged:
+        glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=fr.arena.device) if kind == FACTORED else None
         with _stage("raster_backward"):
-            _backward_call(fr, gi, gg, flags | _abi.GSPLAT_BACKWARD_PHASE_RASTER, st, det, glogit)
-        if factored:                           # logit gradients first: the exchange may start on them while the projection backward runs
-            route.add(glogit, fr.c2w[:3, 3], fr.sh_degree)
-        _frame_stats(fr, st)
+            _backward_call(fr, bp, flags | _abi.GSPLAT_BACKWARD_PHASE_RASTER, det, glogit)
+        if kind == FACTORED:                   # logit gradients first: the exchange may start on them while the projection backward runs
+            route.add(glogit, fr.c2w[:3, 3], fr.spec.sh_degree)
+        _frame_stats(fr, bp.st)
         with _stage("project_backward"):
-            _backward_call(fr, gi, gg, jac | _abi.GSPLAT_BACKWARD_PHASE_PROJECT, st)
+            _backward_call(fr, bp, jac | _abi.GSPLAT_BACKWARD_PHASE_PROJECT)
     else:
-        _backward_call(fr, gi, gg, flags, st, det)
-    if not (factored or staged):
-        _frame_stats(fr, st)                   # (the projection phase only reads grad2d)
+        if kind == SUMMED:
+            # the views of an iteration summed in the accumulation's own buffer by the projection backward: autograd gets no gradient
+            _backward_call(fr, bp, flags | (_abi.GSPLAT_BACKWARD_ACCUMULATE if bp.add else 0), det)
+            route.done(bp.stream)
+        elif kind == FOLDED:
+            # the Adam step of f_rest inside the projection backward: its 192 bytes of gradient per Gaussian are never written
+            _backward_call(fr, bp, flags, det, rest=route.begin())
+            route.commit()
+        else:
+            _backward_call(fr, bp, flags, det)
+        _frame_stats(fr, bp.st)                # (the projection phase only reads grad2d)
     composite_calls["backward"] += 1
-    return {} if summed else dst
-
-
-_BACKWARD_STAGES = frozenset(("raster_backward", "project_backward"))
+    return {} if kind == SUMMED else bp.dst
 
 
 def _frame_stats(fr, st):
     """The densification statistics of a frame on an arena, once its raster phase is queued (fr.stats: ops.densify_stats)."""
     if fr.stats is not None:
-        _abi.check(_abi.lib().gsplat_frame_densify_stats(fr.n, fr.n_pairs, C.byref(fr.view), _p(fr.arena), fr.arena.numel(), _p(fr.stats), st),
+        _abi.check(_abi.lib().gsplat_frame_densify_stats(fr.n, fr.n_pairs, C.byref(fr.spec.view), _p(fr.arena), fr.arena.numel(), _p(fr.stats), st),
                    "gsplat_frame_densify_stats")
 
 
@@ -928,86 +979,41 @@ def sh_accumulate(pos, eyes, grad_logit, scale=1.0, sh_degree=3):
 
 
 class _RenderFn(torch.autograd.Function):
-    """Autograd node for both entry points; gradients for the tensor inputs, c2w included (the scalars get None).  One output, the
-    image -- or, with view.aux, the three outputs (image, depth, alpha)."""
+    """Autograd node for both entry points: apply(spec, c2w, *tensors) with exactly the tensors of spec.names; gradients for c2w and
+    for the tensors, in that order.  One output, the image -- or, with spec.aux, the three outputs (image, depth, alpha)."""
 
     @staticmethod
-    def forward(ctx, fused, view, c2w, pos, opacity_raw, a, b, c, d):
+    def forward(ctx, spec, c2w, *tensors):
         # needs_input_grad ignores the grad mode (and forward() itself always runs with grad disabled): the caller's grad mode
-        # travels in view.grad_mode.  Under torch.no_grad() nothing is saved for a backward that cannot come.
-        need = view.grad_mode and any(ctx.needs_input_grad)
-        view.pose = bool(view.grad_mode and ctx.needs_input_grad[2])     # a pose frame: c2w wants a gradient too (Python-side attribute)
-        image, fr, counts = _forward_impl(fused, view, c2w, pos, opacity_raw, a, b, c, d, need)
-        depth = alpha = None
-        if fr.aux:
-            image, depth, alpha = image
+        # travels in spec.grad_mode.  Under torch.no_grad() nothing is saved for a backward that cannot come.
+        need = spec.grad_mode and any(ctx.needs_input_grad)
+        pose = bool(spec.grad_mode and ctx.needs_input_grad[1])          # a pose frame: c2w wants a gradient too
+        result, fr, counts = _forward_impl(spec, c2w, dict(zip(spec.names, tensors)), pose, need)
+        if spec.is_aux:
             ctx.set_materialize_grads(False)     # an output the loss does not read: None, not a map of zeros
         ctx.frame = fr
         ctx.c2w_dtype = c2w.dtype
-        ctx.dtypes = [t.dtype if isinstance(t, torch.Tensor) else None for t in (pos, opacity_raw, a, b, c, d)]
-        ctx.opa_shape = opacity_raw.shape
-        global _last_counts, _last_binned
+        ctx.dtypes = [t.dtype for t in tensors]
+        ctx.opa_shape = tensors[1].shape         # (opacity_raw: second of both entries' names)
         if counts is not None:                   # (a deferred frame's counters are read in DeferredChecks.verify())
-            ctx.counts = _last_counts = (counts.n_survivors, counts.n_visible, int(counts.n_pairs))
-            _last_binned = int(counts.n_binned)
-        if pos.dtype != torch.float32:
-            image = image.to(pos.dtype)
-        if not view.aux:
-            return image
-        return image, depth.to(pos.dtype), alpha.to(pos.dtype)
+            ctx.counts = _note_counts(counts)
+        return _deliver(spec, result, tensors[0].dtype)
 
     @staticmethod
     def backward(ctx, grad_image, grad_depth=None, grad_alpha=None):
         fr = ctx.frame
-        g = _backward_impl(fr, grad_image, any(ctx.needs_input_grad[3:]), grad_depth, grad_alpha)
-        names = ("pos", "opacity_raw") + (("scale_raw", "q_raw", "f_dc", "f_rest") if fr.fused else ("color", "sigma", None, None))
+        wanted = ctx.needs_input_grad[2:]
+        g = _backward_impl(fr, grad_image, any(wanted), grad_depth, grad_alpha)
         outs = []
-        for i, nm in enumerate(names):
-            t = g.get(nm) if ctx.needs_input_grad[3 + i] else None        # (None also where the frame's route took the gradient)
+        for nm, dtype, want in zip(fr.spec.names, ctx.dtypes, wanted):
+            t = g.get(nm) if want else None      # (None also where the frame's route took the gradient)
             if t is not None and nm == "opacity_raw":
                 t = t.reshape(ctx.opa_shape)
-            outs.append(t if t is None or ctx.dtypes[i] == torch.float32 else t.to(ctx.dtypes[i]))
-        gc2w = g.get("c2w") if ctx.needs_input_grad[2] else None
+            outs.append(t if t is None or dtype == torch.float32 else t.to(dtype))
+        gc2w = g.get("c2w") if ctx.needs_input_grad[1] else None
         if gc2w is not None and ctx.c2w_dtype != torch.float32:
             gc2w = gc2w.to(ctx.c2w_dtype)
-        return (None, None, gc2w, *outs)
-
-
-def _view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff):
-    # H, W may arrive as 0-d tensors from DataLoader collate (reference scripts/train.py:499)
-    # every T of the reference is accepted: the image does not depend on it (SURVEY.md 8a); T only sets the reference's
-    # tile rectangles, i.e. the reported pair count P.  The kernels always bin 16 x 8-pixel lists.
-    if int(T) < 1:
-        raise ValueError("tile size T must be >= 1")
-    view = _abi.make_view(int(H), int(W), float(fx), float(fy), float(cx), float(cy), near, far, pix_guard, T, min_conis,
-                          chi_square_clip, alpha_max, alpha_cutoff)
-    view.grad_mode = torch.is_grad_enabled()            # Python-side attribute (not part of the C struct)
-    view.aux, view.background = False, None             # (likewise: set by _aux_view)
-    view.sh_degree = 3                                  # (likewise: set by _degree_view)
-    view.filter = 0                                     # (likewise: the GSPLAT_FILTER_* bits, set by _filter_view)
-    return view
-
-
-def _filter_view(view, bits):
-    view.filter = bits
-    return view
-
-
-def _degree_view(view, sh_degree):
-    view.sh_degree = sh_degree
-    return view
-
-
-def _aux_view(view, aux, background):
-    """aux = True: the render also returns the depth and the opacity map; background (3 numbers, a sequence or a tensor): the image
-    is composited over that colour.  The background is a constant: it gets no gradient."""
-    view.aux = bool(aux)
-    if background is not None:
-        vals = background.detach().reshape(-1).tolist() if isinstance(background, torch.Tensor) else list(background)
-        if len(vals) != 3:
-            raise ValueError("background must hold 3 numbers (r, g, b)")
-        view.background = tuple(float(x) for x in vals)
-    return view
+        return (None, gc2w, *outs)
 
 
 def render(pos, color, opacity_raw, sigma, c2w, H, W, fx, fy, cx, cy, near=0.01, far=100.0, pix_guard=32, T=16,
@@ -1035,9 +1041,9 @@ def render(pos, color, opacity_raw, sigma, c2w, H, W, fx, fy, cx, cy, near=0.01,
     Anything else raises ValueError before anything is queued.  The mode is kept on the frame: the backward pass cannot be given
     another one.  The default is the reference's render, bit for bit.
     """
-    bits = _abi.filter_bits(lowpass, antialias)
-    view = _filter_view(_aux_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), aux, background), bits)
-    return _RenderFn.apply(False, view, c2w, pos, opacity_raw, color, sigma, None, None)
+    spec = _frame_spec(False, H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff,
+                       aux=aux, background=background, lowpass=lowpass, antialias=antialias)
+    return _RenderFn.apply(spec, c2w, pos, opacity_raw, color, sigma)
 
 
 def render_gaussians(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2w, H, W, fx, fy, cx, cy, near=0.01, far=100.0,
@@ -1053,12 +1059,9 @@ def render_gaussians(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2w, H, W
     j >= (sh_degree + 1)^2 - 1 -- are ignored: their values (a NaN included) change no output bit, their gradient is exactly
     zero on every backward route, and the image equals the default render of the same scene with zeros there.  The degree
     is kept on the frame, so the backward pass cannot be given another one."""
-    _abi.sh_bands_dropped(sh_degree)
-    bits = _abi.filter_bits(lowpass, antialias)
-    view = _degree_view(_aux_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), aux, background),
-                        sh_degree)
-    view.filter = bits
-    return _RenderFn.apply(True, view, c2w, pos, opacity_raw, scale_raw, q_raw, f_dc, f_rest)
+    spec = _frame_spec(True, H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff,
+                       aux=aux, background=background, sh_degree=sh_degree, lowpass=lowpass, antialias=antialias)
+    return _RenderFn.apply(spec, c2w, pos, opacity_raw, scale_raw, q_raw, f_dc, f_rest)
 
 
 @torch.no_grad()
@@ -1074,20 +1077,17 @@ def render_frames(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2ws, H, W, 
     aux, background: as for render_gaussians() -- every element of the result (and the argument of on_frame) is then what
     render_gaussians() returns for the same arguments, bit for bit: (image, depth, alpha) with aux=True, the image over the
     background with a background alone."""
-    _abi.sh_bands_dropped(sh_degree)
-    bits = _abi.filter_bits(lowpass, antialias)
-    view = _filter_view(_degree_view(_view(H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff), sh_degree), bits)
-    if aux or background is not None:
-        view = _aux_view(view, aux, background)
+    spec = _frame_spec(True, H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff,
+                       aux=aux, background=background, sh_degree=sh_degree, lowpass=lowpass, antialias=antialias)
     dev = pos.device
     cams = [torch.as_tensor(c, dtype=torch.float32, device=dev) if not isinstance(c, torch.Tensor) else c for c in c2ws]
-    args = (view, dev, cams, pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw)
-    if on_frame is not None or _ws.pair_capacity(capacity_key(dev, view, pos.shape[0])) == 0 or _deferred_stack:
-        return _render_frames(*args, on_frame)
-    return run_deferred(lambda: _render_frames(*args, None))
+    tensors = dict(zip(spec.names, (pos, opacity_raw, scale_raw, q_raw, f_dc, f_rest)))
+    if on_frame is not None or _ws.pair_capacity(capacity_key(dev, spec, pos.shape[0])) == 0 or _deferred_stack:
+        return _render_frames(spec, dev, cams, tensors, on_frame)
+    return run_deferred(lambda: _render_frames(spec, dev, cams, tensors, None))
 
 
-def _render_frames(view, dev, cams, pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, on_frame):
+def _render_frames(spec, dev, cams, tensors, on_frame):
     main = torch.cuda.current_stream(dev)
     streams = _pipeline_streams(dev)
     for st in streams:
@@ -1095,24 +1095,20 @@ def _render_frames(view, dev, cams, pos, f_dc, f_rest, opacity_raw, scale_raw, q
 
     def begin(k):
         with torch.cuda.stream(streams[k % 2]):
-            return _forward_begin(True, view, cams[k], pos, opacity_raw, scale_raw, q_raw, f_dc, f_rest)
-
-    def end(k, started):
-        pend, done = started
-        with torch.cuda.stream(streams[k % 2]):
-            image = (done if pend is None else _forward_end(pend, False))[0]
-        if isinstance(image, tuple):                           # an aux frame: (image, depth, alpha), the maps None without aux=True
-            image = image if view.aux else image[0]
-        return image
+            return _forward_begin(spec, cams[k], tensors)
 
     images = []
     started = begin(0) if cams else None
     for k in range(len(cams)):
         nxt = begin(k + 1) if k + 1 < len(cams) else None      # queue the next frame's front before waiting for this one's counters
-        image = end(k, started)
+        pend, done = started
+        with torch.cuda.stream(streams[k % 2]):
+            result = (done if pend is None else _forward_end(*pend))[0]
         started = nxt
-        for t in (image if isinstance(image, tuple) else (image,)):
-            t.record_stream(main)                              # allocated on a side stream, consumed on the caller's
+        for t in result:
+            if t is not None:
+                t.record_stream(main)                          # allocated on a side stream, consumed on the caller's
+        image = _deliver(spec, result)
         if on_frame is not None:
             main.wait_stream(streams[k % 2])                   # GPU-side dependency only: the host does not block
             on_frame(k, image)
@@ -1136,6 +1132,14 @@ def _pipeline_streams(dev):
 
 _last_counts = None
 _last_binned = None
+
+
+def _note_counts(counts):
+    """Keep the counters of the most recent call for render_stats() / binned_pairs(); returns the render_stats() triple."""
+    global _last_counts, _last_binned
+    _last_counts = (counts.n_survivors, counts.n_visible, int(counts.n_pairs))
+    _last_binned = int(counts.n_binned)
+    return _last_counts
 
 
 def binned_pairs():

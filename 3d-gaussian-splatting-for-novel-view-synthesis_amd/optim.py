@@ -38,6 +38,7 @@ def reference_param_groups(model, position_lr_init=0.00016, feature_lr=0.0025, o
 
 class _RestUpdate:
     """What ops._backward_impl needs to fold the Adam step of one parameter (f_rest) into the backward pass."""
+    route_kind = "folded"
 
     def __init__(self, opt, param, lr):
         self.opt, self.param, self.lr, self.applied = opt, param, lr, False

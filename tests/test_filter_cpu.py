@@ -395,10 +395,8 @@ def test_good_modes_and_the_default():
 
 
 def test_capacity_key_tells_filtered_frames_apart():
-    v = ops._view(64, 96, 50.0, 50.0, 48.0, 32.0, 0.01, 100.0, 32, 16, 1e-6, 6.25, 0.99, 1 / 128.)
+    camera = (64, 96, 50.0, 50.0, 48.0, 32.0, 0.01, 100.0, 32, 16, 1e-6, 6.25, 0.99, 1 / 128.)
     dev = torch.device("cuda", 0)
-    k0 = ops.capacity_key(dev, v, 600)
-    v.filter = abi.filter_bits(0.3, True)
-    k1 = ops.capacity_key(dev, v, 600)
-    v.filter = abi.filter_bits(0.3, False)
-    assert len({k0, k1, ops.capacity_key(dev, v, 600)}) == 3
+    specs = [ops._frame_spec(True, *camera, **mode) for mode in ({}, dict(lowpass=0.3, antialias=True), dict(lowpass=0.3))]
+    assert [s.filter for s in specs] == [0, abi.filter_bits(0.3, True), abi.filter_bits(0.3, False)]
+    assert len({ops.capacity_key(dev, s, 600) for s in specs}) == 3

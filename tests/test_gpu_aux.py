@@ -274,7 +274,7 @@ def test_no_grad_saves_nothing(gs):
             gs.render_gaussians(*p, torch.tensor(d["c2w"], device=DEV), *util.cam_args(d), **d["kwargs"], aux=True)
     finally:
         gs.ops._forward_impl = impl
-    assert seen["frame"].aux and seen["frame"].accum is None and seen["frame"].accum_aux is None and seen["frame"].grad2d is None
+    assert seen["frame"].spec.aux and seen["frame"].accum is None and seen["frame"].accum_aux is None and seen["frame"].grad2d is None
 
 
 # ---- 9: empty scenes, the off-screen exception, gradient routes ---------------------------------------------------------------

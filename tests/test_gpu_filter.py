@@ -346,10 +346,9 @@ def test_filtered_and_default_frames_of_one_view_keep_their_own_capacity_and_mod
         counts = chk.verify()
     for a, b in zip(eager, deferred):
         assert torch.equal(a, b)
-    view = ops._view(*util.cam_args(d), 0.01, 100.0, 32, 16, 1e-6, 6.25, 0.99, 1 / 128.)
-    k_plain = ops.capacity_key(dev, view, len(d["pos"]))
-    view.filter = abi.filter_bits(**ON)
-    k_on = ops.capacity_key(dev, view, len(d["pos"]))
+    camera = (*util.cam_args(d), 0.01, 100.0, 32, 16, 1e-6, 6.25, 0.99, 1 / 128.)
+    k_plain = ops.capacity_key(dev, ops._frame_spec(True, *camera), len(d["pos"]))
+    k_on = ops.capacity_key(dev, ops._frame_spec(True, *camera, **ON), len(d["pos"]))
     assert k_plain != k_on and ops._ws.pair_capacity(k_plain) > 0 and ops._ws.pair_capacity(k_on) > 0
     assert counts[0].n_binned == counts[2].n_binned >= counts[1].n_binned and counts[0].n_pairs > counts[1].n_pairs
 

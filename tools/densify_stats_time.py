@@ -68,8 +68,9 @@ res["backward_with_stats_us"] = round(statistics.median(backward_us(rec) for _ i
 # the kernels alone: a waited frame keeps project_state and grad2d as separate buffers
 lib = abi.lib()
 p = {k: v.detach().requires_grad_(True) for k, v in pdev.items()}
-view = ops._view(*camargs, 0.01, 100.0, 32, 16, 1e-6, 6.25, 0.99, 1 / 128.)
-img, fr, counts = ops._forward_impl(True, view, c2w, p["pos"], p["opacity_raw"], p["scale_raw"], p["q_raw"], p["f_dc"], p["f_rest"], True)
+spec = ops._frame_spec(True, *camargs, 0.01, 100.0, 32, 16, 1e-6, 6.25, 0.99, 1 / 128.)
+view = spec.view
+(img, _, _), fr, counts = ops._forward_impl(spec, c2w, {k: p[k] for k in spec.names}, False, True)
 grad2d, state, pairs = fr.grad2d if fr.grad2d is not None else torch.zeros(n, 16, device=dev), fr.proj_state, fr.n_pairs
 ops._backward_impl(fr, gimg)             # leaves the frame's grad2d filled (the tensor above is the frame's own)
 torch.cuda.synchronize()
