@@ -1,6 +1,8 @@
-"""Everything the device leaves behind for the raster kernels, built on the CPU: records from the host build of the projection, lists in
-numpy from its rectangles / masks / row spans, pair masks from a float64 restatement of the exact sub-tile test.  Shared by
-tests/test_listcheck_cpu.py and tests/test_raster_oracle_cpu.py (`hm` is a pytest fixture: import it by name)."""
+"""The CPU harness around the host build of the projection math (csrc/host_math_check.cpp -> libgsmath_host.so), shared by the
+*_cpu.py tests: the library (`hm` is a pytest fixture: import it by name), the ABI structs over numpy arrays, the host projection, the
+oracle's per-Gaussian stage gradients -- and cpu_state(), everything the device leaves behind for the raster kernels, built on the
+CPU: records from the host build of the projection, lists in numpy from its rectangles / masks / row spans, pair masks from a float64
+restatement of the exact sub-tile test."""
 import ctypes as C
 import importlib
 import os
@@ -8,8 +10,10 @@ import subprocess
 
 import numpy as np
 import pytest
+import torch
 
-from tests import list_scenes, listcheck
+from oracle import torch_port as tp
+from tests import listcheck, util
 
 abi = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd._abi")
 CSRC = os.path.join(os.path.dirname(abi.__file__), "csrc")
@@ -17,6 +21,8 @@ CSRC = os.path.join(os.path.dirname(abi.__file__), "csrc")
 
 @pytest.fixture(scope="module")
 def hm():
+    if os.environ.get("GSPLAT_HOSTMATH_LIB"):              # `make check-asan`: the AddressSanitizer / UBSan build of the same sources
+        return C.CDLL(os.environ["GSPLAT_HOSTMATH_LIB"])
     so = os.path.join(CSRC, "libgsmath_host.so")
     srcs = [os.path.join(CSRC, f) for f in ("host_math_check.cpp", "gs_math.h", "gs_body.h")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
@@ -24,24 +30,92 @@ def hm():
     return C.CDLL(so)
 
 
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
+def ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def gaussians(arrs, fused=True, color=None, sigma=None):
+    n = len(arrs["pos"])
+    if fused:
+        return abi.Gaussians(n, ptr(arrs["pos"]), ptr(arrs["opacity_raw"]), None, None, ptr(arrs["scale_raw"]),
+                             ptr(arrs["q_raw"]), ptr(arrs["f_dc"]), ptr(arrs["f_rest"]))
+    return abi.Gaussians(n, ptr(arrs["pos"]), ptr(arrs["opacity_raw"]), ptr(color), ptr(sigma), None, None, None, None)
+
+
+def project(hm, d, arrs, flags=0, fused=True, color=None, sigma=None):
+    """The host projection of the float32 arrays `arrs` under the camera of d (a golden or a scene of tests/list_scenes.py) and the
+    filter bits `flags` (none: hm_project).  Returns rec, tiles, vis (0: visible), view, g, c2w; rec = [record columns 0:4, 4:8, 8:12,
+    rect, brect, btiles, bmask, the whole 64-byte records [n, 16], depth]."""
+    n = len(arrs["pos"])
+    view = abi.make_view(*util.cam_args(d), **d["kwargs"])
+    rec64 = np.zeros((n, 16), np.float32)        # one 64-byte record per Gaussian
+    rect, brect = np.zeros((n, 2), np.uint32), np.zeros((n, 2), np.uint32)
+    depth = np.zeros(n, np.float32)
+    tiles, btiles, bmask = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    vis = np.zeros(n, np.int32)
+    g = gaussians(arrs, fused, color, sigma)
+    c2w = np.ascontiguousarray(d["c2w"], np.float32)
+    hm.hm_project_flags(C.byref(g), ptr(c2w), C.byref(view), C.c_int32(flags), ptr(rec64), ptr(rect), ptr(depth), ptr(tiles), ptr(vis),
+                        ptr(brect), ptr(btiles), ptr(bmask))
+    assert np.array_equal(depth[vis == 0], rec64[vis == 0, 11])
+    rec = [rec64[:, 0:4], rec64[:, 4:8], rec64[:, 8:12], rect, brect, btiles, bmask, rec64, depth]
+    return rec, tiles, vis, view, g, c2w
+
+
+def row_spans(hm, rec, view, ids):
+    """row_spans(k) for listcheck.check_records: the spans of large Gaussian ids[k], as the binning kernels enumerate them."""
+    def spans(k):
+        bl, bh = rec[4][ids[k], 0], rec[4][ids[k], 1]
+        h = int((bh >> 16) - (bl >> 16) + 1)
+        xa, xb = np.zeros(h, np.int32), np.zeros(h, np.int32)
+        r16 = np.ascontiguousarray(np.concatenate([rec[0][ids[k]], rec[1][ids[k]]]), np.float32)
+        hm.hm_row_spans(ptr(r16), C.c_uint32(int(bl)), C.c_uint32(int(bh)), C.byref(view), ptr(xa), ptr(xb))
+        return xa, xb
+    return spans
+
+
+def oracle_stage_grads(d, fused=True, color=None, sigma=None, seed=0, pose=False, **mode):
+    """Autograd through the oracle's per-Gaussian stage: random cotangents on (u, v, conic, the record's opacity, colour).  Returns
+    the rows g2d [n, 16] and the gradients of the leaves; with pose c2w is a leaf too and its gradient the last.  mode: lowpass,
+    antialias (the record's opacity is opacity * rho, so rho's own term is exercised)."""
+    dt = torch.float64
+    p = util.tensors(d, dt, grad=True)
+    c2w = torch.tensor(d["c2w"], dtype=dt, requires_grad=pose)
+    stages = {}
+    if fused:
+        leaves = [p[k] for k in util.PARAMS]
+        tp.render_fused(p["pos"], p["f_dc"], p["f_rest"], p["opacity_raw"], p["scale_raw"], p["q_raw"], c2w,
+                        *util.cam_args(d), stages=stages, stop_after_binning=True, **mode, **d["kwargs"])
+    else:
+        col = torch.tensor(color, dtype=dt, requires_grad=True)
+        sig = torch.tensor(sigma, dtype=dt, requires_grad=True)
+        leaves = [p["pos"], p["opacity_raw"], col, sig]
+        tp.render(p["pos"], col, p["opacity_raw"], sig, c2w, *util.cam_args(d), stages=stages, stop_after_binning=True, **mode, **d["kwargs"])
+    rng = np.random.default_rng(seed)
+    ids = stages["ids"].numpy()
+    n = len(d["pos"])
+    g2d = np.zeros((n, 16), np.float32)
+    g2d[ids, :9] = rng.normal(0, 1, (len(ids), 9)).astype(np.float32)
+    # scale the conic cotangents so that every term contributes at a similar magnitude
+    conic = stages["conic"].detach().numpy()
+    g2d[ids, 2:5] /= (np.abs(conic).max(1, keepdims=True) + 1.0).astype(np.float32)
+    # fp32 cannot resolve the small eigenvalue of a 2D covariance with condition number > 1e4 (neither can the
+    # reference's own fp32 path); these synthetic cotangents would only measure that, so leave such rows out.
+    ev = stages["evals"].detach().numpy()
+    g2d[ids[ev[:, 1] / ev[:, 0] > 1e4]] = 0
+    ct = torch.tensor(g2d[ids].astype(np.float64))
+    outs = [stages["u"], stages["v"], stages["conic"], stages["opacity_record"], stages["color"]]
+    cts = [ct[:, 0], ct[:, 1], ct[:, 2:5], ct[:, 5], ct[:, 6:9]]
+    grads = torch.autograd.grad(outs, leaves + ([c2w] if pose else []), cts, allow_unused=True)
+    return g2d, [g.numpy() if g is not None else None for g in grads]
 
 
 def cpu_state(hm, s):
     """Everything the device leaves behind, built on the CPU for scene s.  A scene with `color` (the un-fused entry's input,
     list_scenes.clamps) gets that colour in its records: the raster reads nothing else of it."""
     n = len(s["pos"])
-    view = abi.make_view(*list_scenes.cam_args(s), **s["kwargs"])
-    rec = np.zeros((n, 16), np.float32)
-    rect, brect = np.zeros((n, 2), np.uint32), np.zeros((n, 2), np.uint32)
-    depth = np.zeros(n, np.float32)
-    tiles, btiles, bmask = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-    vis = np.zeros(n, np.int32)
-    g = abi.Gaussians(n, _ptr(s["pos"]), _ptr(s["opacity_raw"]), None, None, _ptr(s["scale_raw"]), _ptr(s["q_raw"]), _ptr(s["f_dc"]),
-                      _ptr(s["f_rest"]))
-    hm.hm_project(C.byref(g), _ptr(s["c2w"]), C.byref(view), _ptr(rec), _ptr(rect), _ptr(depth), _ptr(tiles), _ptr(vis), _ptr(brect),
-                  _ptr(btiles), _ptr(bmask))
+    parts, _, vis, view, _, _ = project(hm, s, s)
+    rec, brect, btiles, bmask, depth = parts[7], parts[4], parts[5], parts[6], parts[8]
     if "color" in s:
         rec[:, 8:11] = s["color"]
     lists_x, lists_y = (s["W"] + 15) // 16, (s["H"] + 7) // 8
@@ -56,8 +130,8 @@ def cpu_state(hm, s):
         else:
             h = int(y1[i] - y0[i] + 1)
             xa, xb = np.zeros(h, np.int32), np.zeros(h, np.int32)
-            hm.hm_row_spans(_ptr(np.ascontiguousarray(rec[i, :8])), C.c_uint32(int(brect[i, 0])), C.c_uint32(int(brect[i, 1])), C.byref(view),
-                            _ptr(xa), _ptr(xb))
+            hm.hm_row_spans(ptr(np.ascontiguousarray(rec[i, :8])), C.c_uint32(int(brect[i, 0])), C.c_uint32(int(brect[i, 1])), C.byref(view),
+                            ptr(xa), ptr(xb))
             pl.append(np.concatenate([(y0[i] + r) * lists_x + np.arange(xa[r], xb[r] + 1) for r in range(h)]).astype(np.int64))
         pi.append(np.full(len(pl[-1]), i, np.int64))
     pl, pi = np.concatenate(pl), np.concatenate(pi)

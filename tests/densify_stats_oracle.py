@@ -1,6 +1,6 @@
 """Oracle of the screen-space densification statistics (helper, not a test).
 
-Built on oracle/torch_port.py without changing it: the oracle renders with `stages`, the projected centres u, v keep their
+Built on oracle/torch_port.py: the oracle renders with `stages`, the projected centres u, v keep their
 gradients (retain_grad), and after the backward pass of sum(image * w)
 
     g[i]   = sqrt((dL/du_i W/2)^2 + (dL/dv_i H/2)^2)                        (NDC units)
@@ -18,9 +18,9 @@ NAMES = ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")
 EXTENT_MAX = 250.0
 
 
-def frame_stats(s, w, dtype=torch.float64, c2w=None):
+def frame_stats(s, w, dtype=torch.float64, c2w=None, lowpass=0.0, antialias=False):
     """s: a scene (util.load(...) or tests/list_scenes.py); w [H, W, 3]: the upstream gradient of the image; c2w: another camera
-    than the scene's.  Returns float64 numpy arrays g [N], ext [N], seen [N] (bool)."""
+    than the scene's; lowpass, antialias: the oracle's filter.  Returns float64 numpy arrays g [N], ext [N], seen [N] (bool)."""
     torch.set_num_threads(16)
     p = {k: torch.tensor(np.asarray(s[k])).to(dtype).requires_grad_(True) for k in NAMES}
     cam = torch.tensor(np.asarray(s["c2w"] if c2w is None else c2w)).to(dtype)
@@ -30,7 +30,8 @@ def frame_stats(s, w, dtype=torch.float64, c2w=None):
     st = {}
     sigma = tp.covariance_from_params(p["scale_raw"], p["q_raw"])
     color = tp.sh_colour(p["f_dc"], p["f_rest"], p["pos"], cam)
-    img = tp.render(p["pos"], color, p["opacity_raw"], sigma, cam, H, W, s["fx"], s["fy"], s["cx"], s["cy"], stages=st, **s["kwargs"])
+    img = tp.render(p["pos"], color, p["opacity_raw"], sigma, cam, H, W, s["fx"], s["fy"], s["cx"], s["cy"], stages=st, lowpass=lowpass,
+                    antialias=antialias, **s["kwargs"])
     if "u" not in st:                                   # no survivor: the zero image, nothing on screen
         return g, ext, seen
     st["u"].retain_grad()

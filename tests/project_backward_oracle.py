@@ -1,6 +1,6 @@
 """Float64 reference of K8 (project_backward_kernel) for any of its modes, Gaussian by Gaussian (helper, not a test).
 
-Built on oracle/torch_port.py and tests/filter_oracle.py without changing them.  The rows of grad2d -- columns 0..8 the moments and
+Built on the stages of oracle/torch_port.py (any SH degree, low-pass and antialiasing).  The rows of grad2d -- columns 0..8 the moments and
 colour sums of the raster backward, column 9 dL/dz -- become cotangents of the oracle's per-Gaussian stage
 (u, v, conic, opacity_record, colour, z) by the relation documented at project_backward_core (csrc/gs_body.h); then autograd runs,
 ONE PASS PER STAGE COLUMN.  Gaussians are independent, so the pass of column j hands every parameter entry its own term
@@ -16,13 +16,10 @@ scale_row the largest scale of the row within the tensor, floor = 2^-24 * 2^-24 
 kinds from float64 quantities alone (kinds()); K comes from the same evaluation in float32 (calibrate()): 3 x (util.K_CAL) the
 largest ratio of the float32 oracle in that (tensor, kind) of the same scene and mode, never above util.GRAD_TOL_MAX / 2^-24.
 """
-import contextlib
-
 import numpy as np
 import torch
 
 from oracle import torch_port as tp
-from tests import filter_oracle as fo
 from tests import list_scenes, util
 
 EPS = 2.0 ** -24
@@ -35,11 +32,6 @@ ISO = 1e-2                # a free row whose three scales differ by less (relati
 SIZES = (1, 63, 64, 65, 129, 200)
 GOLDENS = ("g1_generic", "g6_huge", "g7_tiny")
 FILTERS = {"off": (0.0, False), "lowpass": (0.3, False), "antialias": (0.3, True)}
-
-
-def inactive_columns(degree):
-    """Boolean [45]: the f_rest columns a render at `degree` ignores."""
-    return np.tile(np.arange(15) >= (degree + 1) ** 2 - 1, 3)
 
 
 # ---- scenes ----------------------------------------------------------------------------------------------------------------
@@ -162,53 +154,32 @@ def scene(name):
 
 # ---- the stage -------------------------------------------------------------------------------------------------------------
 
-@contextlib.contextmanager
-def _spy_eigh():
-    """Records the eigenvalues torch.linalg.eigh returns (under filter_oracle's wrapper: the unfiltered ones)."""
-    seen = []
-    real = torch.linalg.eigh
-
-    def eigh(A, *args, **kw):
-        lam, vec = real(A, *args, **kw)
-        seen.append(lam.detach())
-        return lam, vec
-
-    torch.linalg.eigh = eigh
-    try:
-        yield seen
-    finally:
-        torch.linalg.eigh = real
-
-
 class Stage:
     """The oracle's per-Gaussian stage of scene s in `dtype`, with the parameters (and c2w) as leaves: names, leaves{}, c2w, st
-    (filter_oracle's stages), ids, out [V,10] (COLUMNS), lam0 [V,2] (unfiltered, unclamped eigenvalues), s (the low-pass)."""
+    (the oracle's stages), ids, out [V,10] (COLUMNS), lam0 [V,2] (unfiltered, unclamped eigenvalues), s (the low-pass)."""
 
     def __init__(self, s, degree=3, lowpass=0.0, antialias=False, color=None, sigma=None, dtype=torch.float64):
         self.fused = color is None
         self.n = len(s["pos"])
         self.s, self.degree, self.antialias = s, degree, antialias
-        self.lowpass = fo.lowpass_value(lowpass)
+        self.lowpass = tp.lowpass_value(lowpass)
         kw = s["kwargs"]
         t = lambda a: torch.tensor(np.asarray(a), dtype=dtype, requires_grad=True)
         self.c2w = t(s["c2w"])
         st = {}
-        cam = list_scenes.cam_args(s)
-        with _spy_eigh() as seen:
-            if self.fused:
-                self.names = FUSED
-                self.leaves = {k: t(s[k]) for k in FUSED}
-                p = self.leaves
-                mask = torch.tensor(~inactive_columns(degree), dtype=dtype)
-                early = fo.render(p["pos"], p["f_dc"], p["f_rest"] * mask, p["opacity_raw"], p["scale_raw"], p["q_raw"], self.c2w, *cam,
-                                  lowpass=lowpass, antialias=antialias, stages=st, stop_after_binning=True, **kw)
-            else:
-                assert degree == 3
-                self.names = UNFUSED
-                self.leaves = dict(pos=t(s["pos"]), opacity_raw=t(s["opacity_raw"]), color=t(color), sigma=t(sigma))
-                p = self.leaves
-                early = fo.render_unfused(p["pos"], p["color"], p["opacity_raw"], p["sigma"], self.c2w, *cam, lowpass=lowpass,
-                                          antialias=antialias, stages=st, stop_after_binning=True, **kw)
+        mode = dict(lowpass=lowpass, antialias=antialias, stages=st, stop_after_binning=True)
+        if self.fused:
+            self.names = FUSED
+            self.leaves = {k: t(s[k]) for k in FUSED}
+            p = self.leaves
+            early = tp.render_fused(p["pos"], p["f_dc"], p["f_rest"], p["opacity_raw"], p["scale_raw"], p["q_raw"], self.c2w,
+                                    *list_scenes.cam_args(s), sh_degree=degree, **mode, **kw)
+        else:
+            assert degree == 3
+            self.names = UNFUSED
+            self.leaves = dict(pos=t(s["pos"]), opacity_raw=t(s["opacity_raw"]), color=t(color), sigma=t(sigma))
+            p = self.leaves
+            early = tp.render(p["pos"], p["color"], p["opacity_raw"], p["sigma"], self.c2w, *list_scenes.cam_args(s), **mode, **kw)
         self.st = st
         if early is not None or "ids" not in st:                 # no survivor
             self.ids = np.zeros(0, np.int64)
@@ -216,19 +187,9 @@ class Stage:
             self.lam0 = np.zeros((0, 2))
             return
         self.ids = st["ids"].numpy()
-        z = tp.to_camera(p["pos"], self.c2w)[2][st["ids"]]
         self.out = torch.cat([st["u"].unsqueeze(1), st["v"].unsqueeze(1), st["conic"], st["opacity_record"].unsqueeze(1), st["color"],
-                              z.unsqueeze(1)], 1)
-        # the Gaussians the eigh call saw: the survivors of F4 and F6 in input order (as filter_oracle maps them)
-        with torch.no_grad():
-            keep = torch.sigmoid(p["opacity_raw"]).clamp(0, 0.999) >= kw.get("alpha_cutoff", 1 / 128.) * 0.5
-            x_, y_, z_ = tp.to_camera(p["pos"], self.c2w)
-            H, W, fx, fy, cx, cy = cam
-            keep = keep & tp.in_frustum(x_, y_, z_, fx, fy, cx, cy, H, W, kw.get("near", 0.01), kw.get("far", 100.0), kw.get("pix_guard", 32))
-        assert seen[0].shape[0] == int(keep.sum())
-        slot = torch.full((self.n,), -1, dtype=torch.int64)
-        slot[keep] = torch.arange(seen[0].shape[0])
-        self.lam0 = seen[0][slot[st["ids"]]].double().numpy()
+                              st["z"].unsqueeze(1)], 1)
+        self.lam0 = st["evals_unfiltered"].detach().double().numpy()
 
     def jacobian_c2w(self):
         """{(r, c): d out / d c2w[r, c] as [V,10]}, computed once: (J^T v) is linear in v, so the gradient of its entry (r, c) w.r.t. v
@@ -489,7 +450,7 @@ def check(got, ref, K, what, depth=False, names=None, other=None, known=None):
                             f"{_rows(got[k], len(r))[i, col[i]]!r} against {_rows(ref.grad(depth)[k], len(r))[i, col[i]]!r}, "
                             f"ratio {r[i]:.3g} > K = {bound:.3g}"))
     if "f_rest" in rat and ref.degree < 3:      # (below the floor, but structural: the degree's inactive columns are exact zeros)
-        cols = inactive_columns(ref.degree)
+        cols = tp.inactive_columns(ref.degree)
         g = _rows(got["f_rest"], ref.n)
         for i in np.nonzero((g[:, cols] != 0).any(1))[0]:
             bad.append((np.inf, f"{what}: f_rest[{i}] (kind {ref.kind[i]}, lane {i % 64}): an inactive column of degree {ref.degree} holds "

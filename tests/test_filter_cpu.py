@@ -1,41 +1,26 @@
-"""CPU tests of the screen-space low-pass and the antialiased opacity: the oracle helper (tests/filter_oracle.py)
-against the oracle itself, the host build of the FILTER variants of csrc/gs_math.h against the helper's stages and autograd, the flag
+"""CPU tests of the screen-space low-pass and the antialiased opacity: the oracle's filter modes (oracle/torch_port.py)
+against its plain call, the host build of the FILTER variants of csrc/gs_math.h against the helper's stages and autograd, the flag
 bits of the C ABI, and the validation of the Python keywords.  Nothing here needs a GPU."""
 import ctypes as C
 import importlib
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import torch_port as tp
-from tests import filter_oracle as fo
 from tests import listcheck, util
+from tests.cpu_frame import hm, oracle_stage_grads, project, ptr, row_spans  # noqa: F401  (hm is a fixture)
 
 abi = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd._abi")
 ops = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd.ops")
 harness = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd.harness")
 training = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd.training")
-CSRC = os.path.join(os.path.dirname(abi.__file__), "csrc")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUSED = ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")
 MODES = ((0.3, False), (0.3, True))
-
-
-@pytest.fixture(scope="module")
-def hm():
-    so = os.path.join(CSRC, "libgsmath_host.so")
-    srcs = [os.path.join(CSRC, f) for f in ("host_math_check.cpp", "gs_math.h", "gs_body.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, srcs[0]])
-    return C.CDLL(so)
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def _bits(lowpass, antialias):
@@ -55,20 +40,20 @@ def test_helper_without_a_filter_is_the_oracle_bit_for_bit(name):
     _, args = _fused_args(d, torch.float64)
     c2w = torch.tensor(d["c2w"], dtype=torch.float64)
     ref = tp.render_fused(*args, c2w, *util.cam_args(d), **d["kwargs"])
-    img, depth, alpha = fo.render(*args, c2w, *util.cam_args(d), lowpass=0.0, antialias=False, **d["kwargs"])
+    img, depth, alpha = tp.render_fused(*args, c2w, *util.cam_args(d), lowpass=0.0, antialias=False, maps=True, **d["kwargs"])
     assert torch.equal(img, ref)
     assert torch.isfinite(depth).all() and torch.isfinite(alpha).all()
 
 
 @pytest.mark.parametrize("name", ["g1_generic", "g6_huge", "g7_tiny"])
 def test_helper_filter_equals_an_explicit_eigh_of_sigma_plus_s(name):
-    """lambda + s from the wrapper against torch.linalg.eigh(Sigma + s I) itself: conics to rounding, tile rectangles and pairs equal."""
+    """lambda + s of the oracle's low-pass against torch.linalg.eigh(Sigma + s I) itself: conics to rounding, tile rectangles and pairs equal."""
     d = util.load(name)
     _, args = _fused_args(d, torch.float64)
     c2w = torch.tensor(d["c2w"], dtype=torch.float64)
-    s = fo.lowpass_value(0.3)
+    s = tp.lowpass_value(0.3)
     st = {}
-    fo.render(*args, c2w, *util.cam_args(d), lowpass=0.3, stages=st, stop_after_binning=True, **d["kwargs"])
+    tp.render_fused(*args, c2w, *util.cam_args(d), lowpass=0.3, stages=st, stop_after_binning=True, **d["kwargs"])
     real = torch.linalg.eigh
     ex = {}
     torch.linalg.eigh = lambda A: real(A + s * torch.eye(2, dtype=A.dtype))
@@ -80,39 +65,15 @@ def test_helper_filter_equals_an_explicit_eigh_of_sigma_plus_s(name):
     assert torch.equal(st["tile_rect"], ex["tile_rect"]) and torch.equal(st["pair_gauss"], ex["pair_gauss"])
     scale = ex["conic"].abs().max(1, keepdim=True).values
     assert ((st["conic"] - ex["conic"]).abs() <= 1e-9 * scale).all()
-    assert fo.pair_count(st) == int(ex["pair_gauss"].shape[0])
+    assert int(st["pair_gauss"].shape[0]) == int(ex["pair_gauss"].shape[0])
     # the filter does something on this scene: footprints grow
     un = {}
     tp.render_fused(*args, c2w, *util.cam_args(d), stages=un, stop_after_binning=True, **d["kwargs"])
-    assert fo.pair_count(st) >= int(un["pair_gauss"].shape[0])
+    assert int(st["pair_gauss"].shape[0]) >= int(un["pair_gauss"].shape[0])
     assert not torch.equal(st["conic"], un["conic"][: st["conic"].shape[0]]) or st["conic"].shape != un["conic"].shape
 
 
 # ---- 2. / 3. the host build --------------------------------------------------------------------------------------------
-
-def _gaussians(arrs, fused=True, color=None, sigma=None):
-    n = len(arrs["pos"])
-    if fused:
-        return abi.Gaussians(n, _ptr(arrs["pos"]), _ptr(arrs["opacity_raw"]), None, None, _ptr(arrs["scale_raw"]),
-                             _ptr(arrs["q_raw"]), _ptr(arrs["f_dc"]), _ptr(arrs["f_rest"]))
-    return abi.Gaussians(n, _ptr(arrs["pos"]), _ptr(arrs["opacity_raw"]), _ptr(color), _ptr(sigma), None, None, None, None)
-
-
-def _project(hm, d, arrs, flags, fused=True, color=None, sigma=None):
-    n = len(arrs["pos"])
-    view = abi.make_view(*util.cam_args(d), **d["kwargs"])
-    rec64 = np.zeros((n, 16), np.float32)
-    rect, brect = np.zeros((n, 2), np.uint32), np.zeros((n, 2), np.uint32)
-    depth = np.zeros(n, np.float32)
-    tiles, btiles, bmask = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-    vis = np.zeros(n, np.int32)
-    g = _gaussians(arrs, fused, color, sigma)
-    c2w = np.ascontiguousarray(d["c2w"], np.float32)
-    hm.hm_project_flags(C.byref(g), _ptr(c2w), C.byref(view), C.c_int32(flags), _ptr(rec64), _ptr(rect), _ptr(depth), _ptr(tiles),
-                        _ptr(vis), _ptr(brect), _ptr(btiles), _ptr(bmask))
-    rec = [rec64[:, 0:4], rec64[:, 4:8], rec64[:, 8:12], rect, brect, btiles, bmask]
-    return rec, tiles, vis, view, g, c2w
-
 
 def _unfused_inputs(d):
     """color / sigma of the scene as float32 arrays (what the reference's three-call sequence hands to render())."""
@@ -123,22 +84,18 @@ def _unfused_inputs(d):
     return np.ascontiguousarray(color), np.ascontiguousarray(sigma)
 
 
-def _helper_stages(d, lowpass, antialias, fused=True, color=None, sigma=None, grad=False, pose=False):
+def _helper_stages(d, lowpass, antialias, fused=True, color=None, sigma=None):
     dt = torch.float64
-    p = util.tensors(d, dt, grad=grad)
-    c2w = torch.tensor(d["c2w"], dtype=dt, requires_grad=pose)
+    p = util.tensors(d, dt)
+    c2w = torch.tensor(d["c2w"], dtype=dt)
     st = {}
+    mode = dict(lowpass=lowpass, antialias=antialias, stages=st, stop_after_binning=True)
     if fused:
-        leaves = [p[k] for k in util.PARAMS]
-        fo.render(*[p[k] for k in FUSED], c2w, *util.cam_args(d), lowpass=lowpass, antialias=antialias, stages=st,
-                  stop_after_binning=True, **d["kwargs"])
+        tp.render_fused(*[p[k] for k in FUSED], c2w, *util.cam_args(d), **mode, **d["kwargs"])
     else:
-        col = torch.tensor(color, dtype=dt, requires_grad=grad)
-        sig = torch.tensor(sigma, dtype=dt, requires_grad=grad)
-        leaves = [p["pos"], p["opacity_raw"], col, sig]
-        fo.render_unfused(p["pos"], col, p["opacity_raw"], sig, c2w, *util.cam_args(d), lowpass=lowpass, antialias=antialias, stages=st,
-                          stop_after_binning=True, **d["kwargs"])
-    return st, leaves, c2w
+        tp.render(p["pos"], torch.tensor(color, dtype=dt), p["opacity_raw"], torch.tensor(sigma, dtype=dt), c2w, *util.cam_args(d), **mode,
+                  **d["kwargs"])
+    return st
 
 
 def _as_golden(d, st):
@@ -153,21 +110,11 @@ def _as_golden(d, st):
 def _check_forward(hm, d, lowpass, antialias, fused=True):
     arrs = {k: np.ascontiguousarray(d[k], np.float32) for k in util.PARAMS}
     color, sigma = (None, None) if fused else _unfused_inputs(d)
-    st, _, _ = _helper_stages(d, lowpass, antialias, fused, color, sigma)
-    rec, tiles, vis, view, *_ = _project(hm, d, arrs, _bits(lowpass, antialias), fused, color, sigma)
+    st = _helper_stages(d, lowpass, antialias, fused, color, sigma)
+    rec, tiles, vis, view, *_ = project(hm, d, arrs, _bits(lowpass, antialias), fused, color, sigma)
     gold = _as_golden(d, st)
-    ids = gold["im_ids"]
-
-    def row_spans(k):
-        bl, bh = rec[4][ids[k], 0], rec[4][ids[k], 1]
-        h = int((bh >> 16) - (bl >> 16) + 1)
-        xa, xb = np.zeros(h, np.int32), np.zeros(h, np.int32)
-        r16 = np.ascontiguousarray(np.concatenate([rec[0][ids[k]], rec[1][ids[k]]]), np.float32)
-        hm.hm_row_spans(_ptr(r16), C.c_uint32(int(bl)), C.c_uint32(int(bh)), C.byref(view), _ptr(xa), _ptr(xb))
-        return xa, xb
-
     listcheck.check_records(gold, rec[0], rec[1], rec[2], tiles, np.nonzero(vis == 0)[0], rec[4], rec[5], rec[6], ref_rect=rec[3],
-                            row_spans=row_spans)
+                            row_spans=row_spans(hm, rec, view, gold["im_ids"]))
     if antialias:               # the compensation does something here, and never brightens
         rho = st["rho"].numpy()
         assert rho.max() <= 1.0 and rho.min() < 0.95
@@ -188,33 +135,13 @@ def test_host_forward_records_unfused(hm, lowpass, antialias):
 def test_host_forward_without_filter_bits_is_hm_project(hm):
     d = util.load("g1_generic")
     arrs = {k: np.ascontiguousarray(d[k], np.float32) for k in util.PARAMS}
-    rec, tiles, vis, view, g, c2w = _project(hm, d, arrs, 0)
+    rec, tiles, vis, view, g, c2w = project(hm, d, arrs, 0)
     n = len(arrs["pos"])
     rec64, rect, depth = np.zeros((n, 16), np.float32), np.zeros((n, 2), np.uint32), np.zeros(n, np.float32)
     t2, v2, brect, btiles, bmask = np.zeros(n, np.uint32), np.zeros(n, np.int32), np.zeros((n, 2), np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-    hm.hm_project(C.byref(g), _ptr(c2w), C.byref(view), _ptr(rec64), _ptr(rect), _ptr(depth), _ptr(t2), _ptr(v2), _ptr(brect), _ptr(btiles), _ptr(bmask))
+    hm.hm_project(C.byref(g), ptr(c2w), C.byref(view), ptr(rec64), ptr(rect), ptr(depth), ptr(t2), ptr(v2), ptr(brect), ptr(btiles), ptr(bmask))
     assert np.array_equal(rec64[:, :12].view(np.uint32), np.concatenate(rec[:3], 1).view(np.uint32))
     assert np.array_equal(t2, tiles) and np.array_equal(v2, vis) and np.array_equal(brect, rec[4]) and np.array_equal(bmask, rec[6])
-
-
-def _stage_grads(d, lowpass, antialias, fused=True, color=None, sigma=None, pose=False, seed=0):
-    """tests/test_product_math_cpu.py _oracle_stage_grads on the helper's stages: random cotangents on (u, v, conic, the record's
-    opacity = opacity * rho, colour), so rho's own term is exercised.  With pose the last gradient is c2w's."""
-    st, leaves, c2w = _helper_stages(d, lowpass, antialias, fused, color, sigma, grad=True, pose=pose)
-    rng = np.random.default_rng(seed)
-    ids = st["ids"].numpy()
-    n = len(d["pos"])
-    g2d = np.zeros((n, 16), np.float32)
-    g2d[ids, :9] = rng.normal(0, 1, (len(ids), 9)).astype(np.float32)
-    conic = st["conic"].detach().numpy()
-    g2d[ids, 2:5] /= (np.abs(conic).max(1, keepdims=True) + 1.0).astype(np.float32)
-    ev = st["evals"].detach().numpy()
-    g2d[ids[ev[:, 1] / ev[:, 0] > 1e4]] = 0
-    ct = torch.tensor(g2d[ids].astype(np.float64))
-    outs = [st["u"], st["v"], st["conic"], st["opacity_record"], st["color"]]
-    cts = [ct[:, 0], ct[:, 1], ct[:, 2:5], ct[:, 5], ct[:, 6:9]]
-    grads = torch.autograd.grad(outs, leaves + ([c2w] if pose else []), cts, allow_unused=True)
-    return g2d, [g.numpy() if g is not None else None for g in grads]
 
 
 @pytest.mark.parametrize("lowpass,antialias", MODES + ((0.1, True),))
@@ -223,18 +150,18 @@ def test_host_backward_fused_vs_helper_autograd(hm, name, lowpass, antialias):
     d = util.load(name)
     arrs = {k: np.ascontiguousarray(d[k], np.float32) for k in util.PARAMS}
     flags = _bits(lowpass, antialias)
-    g2d, ref = _stage_grads(d, lowpass, antialias)
-    rec, tiles, vis, view, g, c2w = _project(hm, d, arrs, flags)
+    g2d, ref = oracle_stage_grads(d, lowpass=lowpass, antialias=antialias)
+    rec, tiles, vis, view, g, c2w = project(hm, d, arrs, flags)
     out = {k: np.full_like(arrs[k], np.nan) for k in util.PARAMS}
-    gg = abi.GaussianGrads(_ptr(out["pos"]), _ptr(out["opacity_raw"]), None, None, _ptr(out["scale_raw"]),
-                           _ptr(out["q_raw"]), _ptr(out["f_dc"]), _ptr(out["f_rest"]))
-    hm.hm_project_backward_flags(C.byref(g), _ptr(c2w), C.byref(view), C.c_int32(flags), _ptr(tiles), _ptr(g2d), C.byref(gg))
+    gg = abi.GaussianGrads(ptr(out["pos"]), ptr(out["opacity_raw"]), None, None, ptr(out["scale_raw"]),
+                           ptr(out["q_raw"]), ptr(out["f_dc"]), ptr(out["f_rest"]))
+    hm.hm_project_backward_flags(C.byref(g), ptr(c2w), C.byref(view), C.c_int32(flags), ptr(tiles), ptr(g2d), C.byref(gg))
     for k, r in zip(util.PARAMS, ref):
         util.check_grad(out[k], r, k)
     # pose: the same rows, and dL/dc2w
-    g2d, ref = _stage_grads(d, lowpass, antialias, pose=True)
+    g2d, ref = oracle_stage_grads(d, pose=True, lowpass=lowpass, antialias=antialias)
     gc2w = np.full((4, 4), np.nan, np.float32)
-    hm.hm_project_backward_pose_flags(C.byref(g), _ptr(c2w), C.byref(view), C.c_int32(flags), _ptr(tiles), _ptr(g2d), C.byref(gg), _ptr(gc2w))
+    hm.hm_project_backward_pose_flags(C.byref(g), ptr(c2w), C.byref(view), C.c_int32(flags), ptr(tiles), ptr(g2d), C.byref(gg), ptr(gc2w))
     for k, r in zip(util.PARAMS, ref):
         util.check_grad(out[k], r, k)
     util.check_grad(gc2w[:3, :3], ref[-1][:3, :3], f"{name} c2w[:3,:3]")
@@ -247,12 +174,12 @@ def test_host_backward_unfused_vs_helper_autograd(hm):
     arrs = {k: np.ascontiguousarray(d[k], np.float32) for k in util.PARAMS}
     color, sigma = _unfused_inputs(d)
     flags = _bits(0.3, True)
-    g2d, ref = _stage_grads(d, 0.3, True, fused=False, color=color, sigma=sigma)
-    rec, tiles, vis, view, g, c2w = _project(hm, d, arrs, flags, fused=False, color=color, sigma=sigma)
+    g2d, ref = oracle_stage_grads(d, fused=False, color=color, sigma=sigma, lowpass=0.3, antialias=True)
+    rec, tiles, vis, view, g, c2w = project(hm, d, arrs, flags, fused=False, color=color, sigma=sigma)
     out = dict(pos=np.full_like(arrs["pos"], np.nan), opacity_raw=np.full_like(arrs["opacity_raw"], np.nan),
                color=np.full_like(color, np.nan), sigma=np.full_like(sigma, np.nan))
-    gg = abi.GaussianGrads(_ptr(out["pos"]), _ptr(out["opacity_raw"]), _ptr(out["color"]), _ptr(out["sigma"]), None, None, None, None)
-    hm.hm_project_backward_flags(C.byref(g), _ptr(c2w), C.byref(view), C.c_int32(flags), _ptr(tiles), _ptr(g2d), C.byref(gg))
+    gg = abi.GaussianGrads(ptr(out["pos"]), ptr(out["opacity_raw"]), ptr(out["color"]), ptr(out["sigma"]), None, None, None, None)
+    hm.hm_project_backward_flags(C.byref(g), ptr(c2w), C.byref(view), C.c_int32(flags), ptr(tiles), ptr(g2d), C.byref(gg))
     for k, r in zip(("pos", "opacity_raw", "color", "sigma"), ref):
         if k == "sigma":                     # the projection sees sym(Sigma) only: compare the symmetric parts
             r = 0.5 * (r + r.transpose(0, 2, 1))
@@ -274,12 +201,12 @@ def test_filtered_needles_have_no_determinant_cancellation(hm):
         arrs = dict(pos=pos, scale_raw=sr, q_raw=rng.normal(0, 1, (n, 4)).astype(np.float32), opacity_raw=rng.normal(1, 1, n).astype(np.float32),
                     f_dc=rng.normal(0, 1, (n, 3)).astype(np.float32), f_rest=np.zeros((n, 45), np.float32))
         d = dict(c2w=np.eye(4, dtype=np.float32), H=H, W=W, fx=fx, fy=fx, cx=W / 2, cy=H / 2, kwargs={})
-        rec, tiles, vis, view, g, c2w = _project(hm, d, arrs, flags)
+        rec, tiles, vis, view, g, c2w = project(hm, d, arrs, flags)
         rho = np.zeros(n, np.float32)
-        hm.hm_filter_rho(C.byref(g), _ptr(c2w), C.byref(view), C.c_int32(flags), _ptr(rho))
+        hm.hm_filter_rho(C.byref(g), ptr(c2w), C.byref(view), C.c_int32(flags), ptr(rho))
         st = {}
-        fo.render(*[torch.tensor(arrs[k]).double() for k in FUSED], torch.eye(4, dtype=torch.float64), H, W, fx, fx, W / 2, H / 2,
-                  lowpass=0.3, antialias=True, stages=st, stop_after_binning=True)
+        tp.render_fused(*[torch.tensor(arrs[k]).double() for k in FUSED], torch.eye(4, dtype=torch.float64), H, W, fx, fx, W / 2, H / 2,
+                        lowpass=0.3, antialias=True, stages=st, stop_after_binning=True)
         ids, con, ev = st["ids"].numpy(), st["conic"].numpy(), st["evals"].numpy()
         inside = (ev[:, 0] > 2e-6) & (ev[:, 1] < 0.99e4)
         assert inside.sum() > n // 8

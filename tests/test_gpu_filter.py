@@ -1,8 +1,8 @@
 """GPU tests of the screen-space low-pass and the antialiased opacity: lowpass=s renders with the eigen clamp applied to
 Sigma + s I, antialias=True scales every splat's opacity by sqrt(det Sigma / det(Sigma + s I)).
 
-The float64 reference is tests/filter_oracle.py (the oracle under an eigenvalue wrapper, its compositing loop repeated with the scaled
-opacity); the same run in float32 is the calibration, so util.check_image / util.check_grad apply as they stand.  Where
+The float64 reference is oracle/torch_port.py with its lowpass / antialias modes (eigenvalues plus s before the clamp, the compositing
+opacity scaled by rho); the same run in float32 is the calibration, so util.check_image / util.check_grad apply as they stand.  Where
 two GPU results are compared with each other the bound is test_gpu_sh_degree.py's for the same pairs (2e-5 of the largest entry,
 image 1e-6), or bit equality where both sides run the same instructions on the same values."""
 import ctypes as C
@@ -16,7 +16,6 @@ import torch
 from oracle import scenes
 from oracle import torch_port as tp
 from tests import densify_stats_oracle as dso
-from tests import filter_oracle as fo
 from tests import util
 
 pytestmark = pytest.mark.gpu
@@ -58,8 +57,8 @@ def _oracle(name, lowpass, antialias, dtype, aux=False):
     p = {k: torch.tensor(d[k], dtype=dtype, requires_grad=True) for k in NAMES}
     c = torch.tensor(d["c2w"], dtype=dtype, requires_grad=True)
     st = {}
-    out = fo.render(*[p[k] for k in NAMES], c, *util.cam_args(d), lowpass=lowpass, antialias=antialias, background=BG if aux else None,
-                    stages=st, **d["kwargs"])
+    out = tp.render_fused(*[p[k] for k in NAMES], c, *util.cam_args(d), lowpass=lowpass, antialias=antialias, maps=True,
+                          background=BG if aux else None, stages=st, **d["kwargs"])
     loss = (out[0] * torch.tensor(d["wrand"], dtype=dtype)).sum()
     if aux:
         wd, wa = _aux_weights(d)
@@ -67,7 +66,7 @@ def _oracle(name, lowpass, antialias, dtype, aux=False):
     loss.backward()
     grads = {k: v.grad.double().numpy() for k, v in p.items()}
     grads["c2w"] = c.grad.double().numpy()
-    return tuple(t.detach().double().numpy() for t in out), grads, fo.pair_count(st), st
+    return tuple(t.detach().double().numpy() for t in out), grads, int(st["pair_gauss"].shape[0]), st
 
 
 def _params(d, grad=True):
@@ -141,7 +140,7 @@ def test_unfused_render_vs_the_helper(gs):
 
     def oracle(dtype):
         t = {k: torch.tensor(arrs[k], dtype=dtype, requires_grad=True) for k in UNFUSED}
-        out = fo.render_unfused(*[t[k] for k in UNFUSED], torch.tensor(d["c2w"], dtype=dtype), *util.cam_args(d), **ON, **d["kwargs"])
+        out = tp.render(*[t[k] for k in UNFUSED], torch.tensor(d["c2w"], dtype=dtype), *util.cam_args(d), maps=True, **ON, **d["kwargs"])
         (out[0] * torch.tensor(d["wrand"], dtype=dtype)).sum().backward()
         return out[0].detach().double().numpy(), {k: t[k].grad.double().numpy() for k in UNFUSED}
 
@@ -357,11 +356,8 @@ def test_filtered_and_default_frames_of_one_view_keep_their_own_capacity_and_mod
 def test_densify_statistics_follow_the_filter(gs):
     d = util.load("g1_generic")
     w = dso.upstream(d, 0)
-    s = fo.lowpass_value(0.3)
-    with fo.lowpass_eigh(s):
-        g64, e64, seen = dso.frame_stats(d, w, F64)
-    with fo.lowpass_eigh(s):
-        g32, e32, _ = dso.frame_stats(d, w, F32)
+    g64, e64, seen = dso.frame_stats(d, w, F64, lowpass=0.3)
+    g32, e32, _ = dso.frame_stats(d, w, F32, lowpass=0.3)
     rec = gs.DensifyStats(len(d["pos"]), DEV)
     p = _params(d)
     with gs.densify_stats(rec):

@@ -208,7 +208,7 @@ class _Run:
             assert not rows[self.tiles == 0].any(), f"{tag}: {k}: the row of a Gaussian that is binned nowhere is not exactly zero"
             assert not rows[self.zero].any(), f"{tag}: {k}: a visible Gaussian with an all-zero grad2d row must get exact zeros"
             if k == "f_rest":
-                assert not rows[:, pbo.inactive_columns(self.degree)].any(), f"{tag}: an inactive f_rest column is not exactly zero"
+                assert not rows[:, tp.inactive_columns(self.degree)].any(), f"{tag}: an inactive f_rest column is not exactly zero"
 
     def agree(self, a, b, what, depth=False):
         """Two forms of the same gradient agree within the per-row bound (their difference held like an error)."""
@@ -246,7 +246,7 @@ def test_every_fused_form_gaussian_by_gaussian(name, degree, filt):
         rows, p = acc[k].reshape(n, -1), pr[k].reshape(n, -1)
         assert np.array_equal(rows[r.tiles == 0], p[r.tiles == 0]), f"accumulate {k}: a Gaussian that is binned nowhere lost its prior"
         if k == "f_rest":
-            cols = pbo.inactive_columns(degree)
+            cols = tp.inactive_columns(degree)
             vis = r.tiles != 0
             assert degree == 0 or np.array_equal(rows[vis][:, cols], (p[vis][:, cols] + np.float32(0.0))), "accumulate: inactive f_rest columns"
             if degree == 0:

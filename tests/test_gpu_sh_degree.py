@@ -28,19 +28,14 @@ def _ops():
     return importlib.import_module(PKG + ".ops")
 
 
-def inactive_columns(degree):
-    """Boolean [45]: the f_rest columns a render at `degree` ignores."""
-    return np.tile(np.arange(15) >= (degree + 1) ** 2 - 1, 3)
-
-
 @functools.lru_cache(maxsize=None)
 def _oracle(name, degree, dtype):
     """(image, gradients by name, c2w gradient) of the oracle at `degree` in `dtype`, L = sum(image * wrand); computed once."""
     d = util.load(name)
     p = {k: torch.tensor(d[k], dtype=dtype, requires_grad=True) for k in NAMES}
     c = torch.tensor(d["c2w"], dtype=dtype, requires_grad=True)
-    mask = torch.tensor(~inactive_columns(degree), dtype=dtype)
-    img = tp.render_fused(p["pos"], p["f_dc"], p["f_rest"] * mask, p["opacity_raw"], p["scale_raw"], p["q_raw"], c, *util.cam_args(d), **d["kwargs"])
+    img = tp.render_fused(p["pos"], p["f_dc"], p["f_rest"], p["opacity_raw"], p["scale_raw"], p["q_raw"], c, *util.cam_args(d), sh_degree=degree,
+                          **d["kwargs"])
     (img * torch.tensor(d["wrand"], dtype=dtype)).sum().backward()
     return img.detach().double().numpy(), {k: v.grad.double().numpy() for k, v in p.items()}, c.grad.double().numpy()
 
@@ -49,7 +44,7 @@ def _params(d, fill=None, degree=None, grad=True):
     """The scene's six tensors on the GPU; fill: that value in every slot a render at `degree` ignores."""
     arrs = {k: np.array(d[k], np.float32) for k in NAMES}
     if fill is not None:
-        arrs["f_rest"][:, inactive_columns(degree)] = fill
+        arrs["f_rest"][:, tp.inactive_columns(degree)] = fill
     return {k: torch.tensor(arrs[k], device=DEV, requires_grad=grad) for k in NAMES}
 
 
@@ -67,7 +62,7 @@ def _grads(p):
 
 
 def _assert_inactive_zero(g_rest, degree, what=""):
-    bad = g_rest[:, torch.tensor(inactive_columns(degree), device=g_rest.device)]
+    bad = g_rest[:, torch.tensor(tp.inactive_columns(degree), device=g_rest.device)]
     assert bad.numel() == 0 or bool((bad == 0).all()), f"{what}: the gradient of an inactive coefficient must be an exact zero"
 
 
@@ -288,7 +283,7 @@ def test_factored_exchange_at_degree_one(gs):
     acc *= -0.5
     for degree in (0, 1, 2, 3):
         g_dc, g_rest = ops.sh_accumulate(pos.to(DEV), eyes.to(DEV), logits.to(DEV), -0.5, sh_degree=degree)
-        ref = acc[:, 1:, :].transpose(1, 2).reshape(n, 45) * torch.tensor(~inactive_columns(degree), dtype=torch.float64)
+        ref = acc[:, 1:, :].transpose(1, 2).reshape(n, 45) * torch.tensor(~tp.inactive_columns(degree), dtype=torch.float64)
         assert (g_dc.cpu().double() - acc[:, 0, :]).abs().max() < 1e-5
         assert (g_rest.cpu().double() - ref).abs().max() < 1e-5
         _assert_inactive_zero(g_rest, degree, "sh_accumulate")
@@ -313,7 +308,7 @@ def test_depth_and_opacity_frame_at_degree_one(gs):
         assert torch.equal(a, b)
     low, full = res[0][1], res[1][1]
     _assert_inactive_zero(low["f_rest"], 1)
-    inactive = torch.tensor(inactive_columns(1), device=DEV)
+    inactive = torch.tensor(tp.inactive_columns(1), device=DEV)
     assert float(full["f_rest"][:, inactive].abs().max()) > 1.0
     full["f_rest"][:, inactive] = 0.0
     _assert_close(low, full, "aux frame at degree 1 vs the default frame of the zeroed scene")
@@ -357,7 +352,7 @@ def test_folded_step_at_degree_one_is_the_optimisers_step(gs):
     ops = _ops()
     s, views = _training_scene()
     one = views[:1]
-    inactive = torch.tensor(inactive_columns(1), device=DEV)
+    inactive = torch.tensor(tp.inactive_columns(1), device=DEV)
     res = []
     with _deterministic(gs):
         for fold in (False, True):

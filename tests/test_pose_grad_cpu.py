@@ -2,93 +2,14 @@
 (hm_project_backward_pose), against autograd through the oracle with c2w as a leaf; and the new C-ABI entries' host-side checks."""
 import ctypes as C
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
-import torch
 
-from oracle import torch_port as tp
 from tests import util
+from tests.cpu_frame import gaussians, hm, oracle_stage_grads, project, ptr  # noqa: F401  (hm is a fixture)
 
 abi = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd._abi")
-CSRC = os.path.join(os.path.dirname(abi.__file__), "csrc")
-
-
-@pytest.fixture(scope="module")
-def hm():
-    if os.environ.get("GSPLAT_HOSTMATH_LIB"):              # `make check-asan`: the AddressSanitizer / UBSan build of the same sources
-        return C.CDLL(os.environ["GSPLAT_HOSTMATH_LIB"])
-    so = os.path.join(CSRC, "libgsmath_host.so")
-    srcs = [os.path.join(CSRC, f) for f in ("host_math_check.cpp", "gs_math.h", "gs_body.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, srcs[0]])
-    return C.CDLL(so)
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-def _gaussians(arrs, fused=True, color=None, sigma=None):
-    n = len(arrs["pos"])
-    if fused:
-        return abi.Gaussians(n, _ptr(arrs["pos"]), _ptr(arrs["opacity_raw"]), None, None, _ptr(arrs["scale_raw"]),
-                             _ptr(arrs["q_raw"]), _ptr(arrs["f_dc"]), _ptr(arrs["f_rest"]))
-    return abi.Gaussians(n, _ptr(arrs["pos"]), _ptr(arrs["opacity_raw"]), _ptr(color), _ptr(sigma), None, None, None, None)
-
-
-def _project(hm, d, arrs, fused=True, color=None, sigma=None):
-    """The host projection: what it needs here is the visibility flag per Gaussian (tiles > 0)."""
-    n = len(arrs["pos"])
-    view = abi.make_view(*util.cam_args(d), **d["kwargs"])
-    rec64 = np.zeros((n, 16), np.float32)
-    rect, brect = np.zeros((n, 2), np.uint32), np.zeros((n, 2), np.uint32)
-    depth = np.zeros(n, np.float32)
-    tiles, btiles, bmask = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-    vis = np.zeros(n, np.int32)
-    g = _gaussians(arrs, fused, color, sigma)
-    c2w = np.ascontiguousarray(d["c2w"], np.float32)
-    hm.hm_project(C.byref(g), _ptr(c2w), C.byref(view), _ptr(rec64), _ptr(rect), _ptr(depth), _ptr(tiles), _ptr(vis),
-                  _ptr(brect), _ptr(btiles), _ptr(bmask))
-    return tiles, view, g, c2w
-
-
-# (a copy of tests/test_product_math_cpu.py _oracle_stage_grads, with c2w a leaf too)
-def _oracle_stage_grads(d, fused=True, color=None, sigma=None, seed=0):
-    """Autograd through the oracle's per-Gaussian stage: random cotangents on (u, v, conic, opacity, colour).  The last gradient
-    returned is c2w's."""
-    dt = torch.float64
-    p = util.tensors(d, dt, grad=True)
-    c2w = torch.tensor(d["c2w"], dtype=dt, requires_grad=True)
-    stages = {}
-    if fused:
-        leaves = [p[k] for k in util.PARAMS]
-        tp.render_fused(p["pos"], p["f_dc"], p["f_rest"], p["opacity_raw"], p["scale_raw"], p["q_raw"], c2w,
-                        *util.cam_args(d), stages=stages, **d["kwargs"])
-    else:
-        col = torch.tensor(color, dtype=dt, requires_grad=True)
-        sig = torch.tensor(sigma, dtype=dt, requires_grad=True)
-        leaves = [p["pos"], p["opacity_raw"], col, sig]
-        tp.render(p["pos"], col, p["opacity_raw"], sig, c2w, *util.cam_args(d), stages=stages, **d["kwargs"])
-    rng = np.random.default_rng(seed)
-    ids = stages["ids"].numpy()
-    n = len(d["pos"])
-    g2d = np.zeros((n, 16), np.float32)
-    g2d[ids, :9] = rng.normal(0, 1, (len(ids), 9)).astype(np.float32)
-    # scale the conic cotangents so that every term contributes at a similar magnitude
-    conic = stages["conic"].detach().numpy()
-    g2d[ids, 2:5] /= (np.abs(conic).max(1, keepdims=True) + 1.0).astype(np.float32)
-    # fp32 cannot resolve the small eigenvalue of a 2D covariance with condition number > 1e4 (neither can the
-    # reference's own fp32 path); these synthetic cotangents would only measure that, so leave such rows out.
-    ev = stages["evals"].detach().numpy()
-    g2d[ids[ev[:, 1] / ev[:, 0] > 1e4]] = 0
-    ct = torch.tensor(g2d[ids].astype(np.float64))
-    outs = [stages["u"], stages["v"], stages["conic"], stages["opacity"], stages["color"]]
-    cts = [ct[:, 0], ct[:, 1], ct[:, 2:5], ct[:, 5], ct[:, 6:9]]
-    grads = torch.autograd.grad(outs, leaves + [c2w], cts, allow_unused=True)
-    return g2d, [g.numpy() if g is not None else None for g in grads]
 
 
 def _check_pose(gc2w, ref, gpos, name):
@@ -104,19 +25,19 @@ def _check_pose(gc2w, ref, gpos, name):
 def test_pose_gradient_fused_vs_oracle_autograd(hm, name):
     d = util.load(name)
     arrs = {k: np.ascontiguousarray(d[k], np.float32) for k in util.PARAMS}
-    g2d, ref = _oracle_stage_grads(d)
-    tiles, view, g, c2w = _project(hm, d, arrs)
+    g2d, ref = oracle_stage_grads(d, pose=True)
+    _, tiles, _, view, g, c2w = project(hm, d, arrs)
     out = {k: np.full_like(arrs[k], np.nan) for k in util.PARAMS}
-    gg = abi.GaussianGrads(_ptr(out["pos"]), _ptr(out["opacity_raw"]), None, None, _ptr(out["scale_raw"]),
-                           _ptr(out["q_raw"]), _ptr(out["f_dc"]), _ptr(out["f_rest"]))
+    gg = abi.GaussianGrads(ptr(out["pos"]), ptr(out["opacity_raw"]), None, None, ptr(out["scale_raw"]),
+                           ptr(out["q_raw"]), ptr(out["f_dc"]), ptr(out["f_rest"]))
     gc2w = np.full((4, 4), np.nan, np.float32)
-    hm.hm_project_backward_pose(C.byref(g), _ptr(c2w), C.byref(view), _ptr(tiles), _ptr(g2d), C.byref(gg), _ptr(gc2w))
+    hm.hm_project_backward_pose(C.byref(g), ptr(c2w), C.byref(view), ptr(tiles), ptr(g2d), C.byref(gg), ptr(gc2w))
     for k, r in zip(util.PARAMS, ref):                  # the rows are hm_project_backward's
         util.check_grad(out[k], r, k)
     _check_pose(gc2w, ref[-1], out["pos"], name)
     # pose only (no gradient rows): the same sum
     gc2w_only = np.full((4, 4), np.nan, np.float32)
-    hm.hm_project_backward_pose(C.byref(g), _ptr(c2w), C.byref(view), _ptr(tiles), _ptr(g2d), None, _ptr(gc2w_only))
+    hm.hm_project_backward_pose(C.byref(g), ptr(c2w), C.byref(view), ptr(tiles), ptr(g2d), None, ptr(gc2w_only))
     assert np.array_equal(gc2w_only, gc2w)
 
 
@@ -125,14 +46,14 @@ def test_pose_gradient_unfused_vs_oracle_autograd(hm):
     arrs = {k: np.ascontiguousarray(d[k], np.float32) for k in util.PARAMS}
     color = np.ascontiguousarray(d["color_in"], np.float32)
     sigma = np.ascontiguousarray(d["sigma_in"], np.float32)
-    g2d, ref = _oracle_stage_grads(d, fused=False, color=color, sigma=sigma)
-    tiles, view, g, c2w = _project(hm, d, arrs, fused=False, color=color, sigma=sigma)
+    g2d, ref = oracle_stage_grads(d, fused=False, color=color, sigma=sigma, pose=True)
+    _, tiles, _, view, g, c2w = project(hm, d, arrs, fused=False, color=color, sigma=sigma)
     out = dict(pos=np.full_like(arrs["pos"], np.nan), opacity_raw=np.full_like(arrs["opacity_raw"], np.nan),
                color=np.full_like(color, np.nan), sigma=np.full_like(sigma, np.nan))
-    gg = abi.GaussianGrads(_ptr(out["pos"]), _ptr(out["opacity_raw"]), _ptr(out["color"]), _ptr(out["sigma"]), None, None,
+    gg = abi.GaussianGrads(ptr(out["pos"]), ptr(out["opacity_raw"]), ptr(out["color"]), ptr(out["sigma"]), None, None,
                            None, None)
     gc2w = np.full((4, 4), np.nan, np.float32)
-    hm.hm_project_backward_pose(C.byref(g), _ptr(c2w), C.byref(view), _ptr(tiles), _ptr(g2d), C.byref(gg), _ptr(gc2w))
+    hm.hm_project_backward_pose(C.byref(g), ptr(c2w), C.byref(view), ptr(tiles), ptr(g2d), C.byref(gg), ptr(gc2w))
     for k, r in zip(("pos", "opacity_raw", "color", "sigma"), ref):
         util.check_grad(out[k], r, k)
     _check_pose(gc2w, ref[-1], out["pos"], "g11_unfused")
@@ -151,13 +72,13 @@ def test_pose_gradient_of_a_rotated_camera(hm):
     c2w[:3, 3] += [0.02, -0.03, 0.01]
     d["c2w"] = c2w.astype(np.float32).astype(np.float64)
     arrs = {k: np.ascontiguousarray(d[k], np.float32) for k in util.PARAMS}
-    g2d, ref = _oracle_stage_grads(d, seed=1)
-    tiles, view, g, c2w32 = _project(hm, d, arrs)
+    g2d, ref = oracle_stage_grads(d, seed=1, pose=True)
+    _, tiles, _, view, g, c2w32 = project(hm, d, arrs)
     out = {k: np.full_like(arrs[k], np.nan) for k in util.PARAMS}
-    gg = abi.GaussianGrads(_ptr(out["pos"]), _ptr(out["opacity_raw"]), None, None, _ptr(out["scale_raw"]),
-                           _ptr(out["q_raw"]), _ptr(out["f_dc"]), _ptr(out["f_rest"]))
+    gg = abi.GaussianGrads(ptr(out["pos"]), ptr(out["opacity_raw"]), None, None, ptr(out["scale_raw"]),
+                           ptr(out["q_raw"]), ptr(out["f_dc"]), ptr(out["f_rest"]))
     gc2w = np.full((4, 4), np.nan, np.float32)
-    hm.hm_project_backward_pose(C.byref(g), _ptr(c2w32), C.byref(view), _ptr(tiles), _ptr(g2d), C.byref(gg), _ptr(gc2w))
+    hm.hm_project_backward_pose(C.byref(g), ptr(c2w32), C.byref(view), ptr(tiles), ptr(g2d), C.byref(gg), ptr(gc2w))
     assert np.abs(ref[-1][:3, :3] - ref[-1][:3, :3].T).max() > 1e-3 * np.abs(ref[-1][:3, :3]).max()      # not symmetric: a transpose shows
     _check_pose(gc2w, ref[-1], out["pos"], "g1 rotated")
 
@@ -172,13 +93,13 @@ def test_pose_entries_refuse_bad_arguments_without_touching_the_gpu():
         assert b"unknown flag" in lib.gsplat_last_error()
     d = util.load("g1_generic")
     arrs = {k: np.ascontiguousarray(d[k], np.float32) for k in util.PARAMS}
-    g = _gaussians(arrs)            # (host addresses: the checks below refuse the call before any of them is used)
+    g = gaussians(arrs)            # (host addresses: the checks below refuse the call before any of them is used)
     c2w = np.ascontiguousarray(d["c2w"], np.float32)
-    assert lib.gsplat_project_backward_pose(C.byref(g), _ptr(c2w), C.byref(v), _ptr(c2w), _ptr(c2w), None, None, None, 0,
+    assert lib.gsplat_project_backward_pose(C.byref(g), ptr(c2w), C.byref(v), ptr(c2w), ptr(c2w), None, None, None, 0,
                                             abi.GSPLAT_BACKWARD_SH_JACOBIAN, None) == abi.GSPLAT_ERR_BAD_ARG
     assert b"grad_c2w" in lib.gsplat_last_error()
     need = lib.gsplat_pose_scratch_bytes(len(arrs["pos"]))
-    assert lib.gsplat_project_backward_pose(C.byref(g), _ptr(c2w), C.byref(v), _ptr(c2w), _ptr(c2w), None, gc2w, _ptr(c2w), need - 1,
+    assert lib.gsplat_project_backward_pose(C.byref(g), ptr(c2w), C.byref(v), ptr(c2w), ptr(c2w), None, gc2w, ptr(c2w), need - 1,
                                             abi.GSPLAT_BACKWARD_SH_JACOBIAN, None) == abi.GSPLAT_ERR_WORKSPACE
     assert b"scratch" in lib.gsplat_last_error()
     # the flag bits of the existing entries keep their meaning: 1 << 5 is still unknown to gsplat_project_backward

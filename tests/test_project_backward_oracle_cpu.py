@@ -2,63 +2,28 @@
 of the K8 body in every <POSE, DEPTH, NB, FILTER> instantiation with `moments` and the saved Jacobian on and off
 (hm_project_backward_variant, csrc/host_math_check.cpp).  Nothing here needs a GPU.
 
-1. the helper is right: the plain mode reproduces tests/test_product_math_cpu.py _oracle_stage_grads; with depth and pose it equals
-   float64 autograd through filter_oracle.render of a loss that is linear in the stage outputs;
+1. the helper is right: the plain mode reproduces tests/cpu_frame.py oracle_stage_grads; with depth and pose it equals
+   float64 autograd through the oracle's stages of a loss that is linear in the stage outputs;
 2. the host body: all 32 variants x moments x from_jac (under antialias both FILTER cases) on g1_generic, g6_huge, g7_tiny and the
    synthetic scenes, and the un-fused body on g11_unfused; no synthetic row is a boundary row, and at most 1 % of a golden's are;
 3. the checker rejects broken output and names the Gaussian."""
 import ctypes as C
 import functools
 import importlib
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from tests import filter_oracle as fo
+from oracle import torch_port as tp
 from tests import list_scenes, util
 from tests import project_backward_oracle as pbo
-from tests import test_product_math_cpu as pm
+from tests.cpu_frame import gaussians, hm, oracle_stage_grads, project, ptr  # noqa: F401  (hm is a fixture)
 
 abi = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd._abi")
-CSRC = os.path.join(os.path.dirname(abi.__file__), "csrc")
 SCENES = tuple(f"synth{n}" for n in pbo.SIZES) + pbo.GOLDENS
 MAX_BOUNDARY_SHARE = 0.01
-
-
-@pytest.fixture(scope="module")
-def hm():
-    so = os.path.join(CSRC, "libgsmath_host.so")
-    srcs = [os.path.join(CSRC, f) for f in ("host_math_check.cpp", "gs_math.h", "gs_body.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, srcs[0]])
-    return C.CDLL(so)
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-def _gaussians(s, color=None, sigma=None):
-    n = len(s["pos"])
-    if color is None:
-        return abi.Gaussians(n, _ptr(s["pos"]), _ptr(s["opacity_raw"]), None, None, _ptr(s["scale_raw"]), _ptr(s["q_raw"]), _ptr(s["f_dc"]), _ptr(s["f_rest"]))
-    return abi.Gaussians(n, _ptr(s["pos"]), _ptr(s["opacity_raw"]), _ptr(color), _ptr(sigma), None, None, None, None)
-
-
-def host_tiles(hm, s, flags, color=None, sigma=None):
-    """tiles[n] of the host build's projection (0: binned nowhere)."""
-    n = len(s["pos"])
-    view = abi.make_view(*list_scenes.cam_args(s), **s["kwargs"])
-    rec64, rect, brect = np.zeros((n, 16), np.float32), np.zeros((n, 2), np.uint32), np.zeros((n, 2), np.uint32)
-    depth, tiles, btiles, bmask, vis = np.zeros(n, np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.int32)
-    g = _gaussians(s, color, sigma)
-    hm.hm_project_flags(C.byref(g), _ptr(s["c2w"]), C.byref(view), C.c_int32(flags), _ptr(rec64), _ptr(rect), _ptr(depth), _ptr(tiles), _ptr(vis),
-                        _ptr(brect), _ptr(btiles), _ptr(bmask))
-    return tiles
 
 
 def host_backward(hm, s, flags, degree, depth, moments, from_jac, tiles, g2d, pose, rows=True, color=None, sigma=None):
@@ -69,13 +34,13 @@ def host_backward(hm, s, flags, degree, depth, moments, from_jac, tiles, g2d, po
     names = pbo.FUSED if fused else pbo.UNFUSED
     shapes = dict(pos=(n, 3), opacity_raw=(n,), scale_raw=(n, 3), q_raw=(n, 4), f_dc=(n, 3), f_rest=(n, 45), color=(n, 3), sigma=(n, 3, 3))
     out = {k: np.full(shapes[k], np.nan, np.float32) for k in names}
-    gg = abi.GaussianGrads(*[_ptr(out.get(k)) for k in ("pos", "opacity_raw", "color", "sigma", "scale_raw", "q_raw", "f_dc", "f_rest")])
+    gg = abi.GaussianGrads(*[ptr(out.get(k)) for k in ("pos", "opacity_raw", "color", "sigma", "scale_raw", "q_raw", "f_dc", "f_rest")])
     gc = np.full((4, 4), np.nan, np.float32)
-    g = _gaussians(s, color, sigma)
+    g = gaussians(s, color is None, color, sigma)
     hm.hm_project_backward_variant.restype = C.c_int
-    rc = hm.hm_project_backward_variant(C.byref(g), _ptr(s["c2w"]), C.byref(view), C.c_int32(flags), C.c_int32(degree), C.c_int32(int(depth)),
-                                        C.c_int32(int(moments)), C.c_int32(int(from_jac)), _ptr(tiles), _ptr(np.ascontiguousarray(g2d, np.float32)),
-                                        C.byref(gg) if rows else None, _ptr(gc) if pose else None)
+    rc = hm.hm_project_backward_variant(C.byref(g), ptr(s["c2w"]), C.byref(view), C.c_int32(flags), C.c_int32(degree), C.c_int32(int(depth)),
+                                        C.c_int32(int(moments)), C.c_int32(int(from_jac)), ptr(tiles), ptr(np.ascontiguousarray(g2d, np.float32)),
+                                        C.byref(gg) if rows else None, ptr(gc) if pose else None)
     assert rc == 0
     if not rows:
         out = {}
@@ -92,7 +57,7 @@ class Case:
         lowpass, aa = pbo.FILTERS[filt]
         self.s, self.color, self.sigma = pbo.scene(name)
         self.flags = abi.filter_bits(lowpass, aa)
-        self.tiles = host_tiles(hm, self.s, self.flags, self.color, self.sigma)
+        self.tiles = project(hm, self.s, self.s, self.flags, self.color is None, self.color, self.sigma)[1]   # (0: binned nowhere)
         kw = dict(degree=degree, lowpass=lowpass, antialias=aa, color=self.color, sigma=self.sigma)
         st64 = pbo.Stage(self.s, dtype=torch.float64, **kw)
         st32 = pbo.Stage(self.s, dtype=torch.float32, **kw)
@@ -116,7 +81,7 @@ def _case(hm, name, degree, filt):
 @pytest.mark.parametrize("name", ["g1_generic", "g7_tiny"])
 def test_plain_mode_reproduces_the_stage_gradients_of_the_host_math_test(name):
     d = util.load(name)
-    g2d, want = pm._oracle_stage_grads(d)                      # (its rows are 2-D gradients: moments = False)
+    g2d, want = oracle_stage_grads(d)                      # (its rows are 2-D gradients: moments = False)
     s = list_scenes.golden(name)
     ref = pbo.reference(s, g2d, moments=False)
     got = ref.grad(depth=False)
@@ -138,16 +103,14 @@ def test_depth_and_pose_equal_autograd_of_a_loss_linear_in_the_stage_outputs(nam
     stg = pbo.Stage(s, degree, lowpass, aa)
     g2d, _ = pbo.moment_rows(stg, np.ones(stg.n, np.uint32), seed=3)
     ref = pbo.reference(s, g2d, degree, lowpass, aa)
-    # the same loss by one backward pass through filter_oracle.render's stages
+    # the same loss by one backward pass through the oracle's stages
     dt = torch.float64
     p = {k: torch.tensor(s[k], dtype=dt, requires_grad=True) for k in pbo.FUSED}
     c2w = torch.tensor(s["c2w"], dtype=dt, requires_grad=True)
     st = {}
-    mask = torch.tensor(~pbo.inactive_columns(degree), dtype=dt)
-    fo.render(p["pos"], p["f_dc"], p["f_rest"] * mask, p["opacity_raw"], p["scale_raw"], p["q_raw"], c2w, *list_scenes.cam_args(s), lowpass=lowpass,
-              antialias=aa, stages=st, stop_after_binning=True, **s["kwargs"])
-    from oracle import torch_port as tp
-    z = tp.to_camera(p["pos"], c2w)[2][st["ids"]]
+    tp.render_fused(p["pos"], p["f_dc"], p["f_rest"], p["opacity_raw"], p["scale_raw"], p["q_raw"], c2w, *list_scenes.cam_args(s), sh_degree=degree,
+                    lowpass=lowpass, antialias=aa, stages=st, stop_after_binning=True, **s["kwargs"])
+    z = st["z"]
     ct = stg.cotangents(g2d).detach()
     loss = ((st["u"] * ct[:, 0]).sum() + (st["v"] * ct[:, 1]).sum() + (st["conic"] * ct[:, 2:5]).sum() + (st["opacity_record"] * ct[:, 5]).sum()
             + (st["color"] * ct[:, 6:9]).sum() + (z * ct[:, 9]).sum())
@@ -163,7 +126,7 @@ def test_depth_and_pose_equal_autograd_of_a_loss_linear_in_the_stage_outputs(nam
         tol = np.where(clamped, 1e-4, 1e-10).reshape((-1,) + (1,) * (w.ndim - 1))
         assert (np.abs(got[k] - w) <= tol * sc[k] + pbo.EPS ** 2 * sc[k].max()).all(), k
     assert (np.abs(got["c2w"] - c2w.grad.numpy()) <= 1e-10 * sc["c2w"] + 1e-300).all()
-    assert not got["f_rest"][:, pbo.inactive_columns(degree)].any()
+    assert not got["f_rest"][:, tp.inactive_columns(degree)].any()
     assert np.abs(ref.terms["pos"][9]).max() > 0 and np.abs(ref.terms["c2w"][9]).max() > 0          # the depth term is alive
     assert (np.abs(got["c2w"]) <= sc["c2w"] * (1 + 1e-9)).all() and (sc["c2w"][:3] > 0).all()
 
@@ -186,7 +149,7 @@ def test_host_body_in_every_variant_under_the_per_row_bound(hm, name, degree, fi
         assert not (c.ref[True].kind[c.s["culled"]] != "culled").any() and not c.tiles[c.s["culled"]].any()
         pbo.assert_block_layout(name, c.tiles)
     assert share <= MAX_BOUNDARY_SHARE, f"{name}: {share:.3%} of the visible rows are boundary rows"
-    inactive = pbo.inactive_columns(degree)
+    inactive = tp.inactive_columns(degree)
     worst = {}
     # FILTER = false is the body of the unfiltered frame; under a filter the frame's body is FILTER = true
     for moments in (True, False):
@@ -272,7 +235,7 @@ def test_checker_rejects_broken_output_and_names_the_gaussian(hm):
     bad = cp(); bad["opacity_raw"][192:] = np.roll(bad["opacity_raw"][192:], 1)
     _rejected(c, bad, True, "opacity_raw[19")
     # an inactive f_rest column set to 1e-30
-    col = int(np.nonzero(pbo.inactive_columns(2))[0][0])
+    col = int(np.nonzero(tp.inactive_columns(2))[0][0])
     bad = cp(); bad["f_rest"][i, col] = 1e-30
     _rejected(c, bad, True, f"f_rest[{i}]")
     # the depth term dropped from pos
@@ -314,7 +277,6 @@ def test_conic_of_a_small_quaternion_is_the_oracles(hm, qn):
     orthogonal R, put the conic 1.3 % off at |q_raw| = 1e-6.  At and below |q_raw| = 1e-2 the projection takes a d - b^2 instead, which
     on Gaussians of 2-D condition number below 100 keeps 100 eps of the determinant: the conic within 2e-5 of the float64 oracle's
     (the bound of test_conic_of_needle_gaussians_has_no_determinant_cancellation), on either side of the branch."""
-    from oracle import torch_port as tp
     rng = np.random.default_rng(11)
     n, H, W, fx = 500, 200, 300, 250.0
     q = rng.normal(0, 1, (n, 4))
@@ -322,7 +284,7 @@ def test_conic_of_a_small_quaternion_is_the_oracles(hm, qn):
                 scale_raw=rng.normal(-4.0, 0.3, (n, 3)).astype(np.float32), q_raw=(q / np.linalg.norm(q, axis=1, keepdims=True) * qn).astype(np.float32),
                 opacity_raw=rng.normal(1, 1, n).astype(np.float32), f_dc=rng.normal(0, 1, (n, 3)).astype(np.float32), f_rest=np.zeros((n, 45), np.float32))
     d = dict(c2w=np.eye(4, dtype=np.float32), H=H, W=W, fx=fx, fy=fx, cx=W / 2, cy=H / 2, kwargs={})
-    rec, *_ = pm._project(hm, d, arrs)
+    rec, *_ = project(hm, d, arrs)
     st = {}
     tp.render_fused(*[torch.tensor(arrs[k]).double() for k in ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")],
                     torch.eye(4, dtype=torch.float64), H, W, fx, fx, W / 2, H / 2, stages=st, stop_after_binning=True)
