@@ -153,6 +153,8 @@ SIGNATURES = {
     "gsplat_densify_stats": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP]),
     "gsplat_frame_densify_stats": (_INT, [_I64, _I64, _PV, _VP, _I64, _VP, _VP]),
     "gsplat_densify_stats_merge": (_INT, [_I64, _VP, _VP, _VP]),
+    "gsplat_contribution": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP]),
+    "gsplat_frame_contribution": (_INT, [_I64, _I64, _PV, _VP, _I64, _VP, _VP]),
     "gsplat_frame_bytes": (_I64, [_I64, _I64, _PV, C.c_int32]),
     "gsplat_forward_deferred": (_INT, [_PG, _VP, _PV, _VP, _I64, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, C.c_int32, _VP]),
     "gsplat_backward": (_INT, [_PG, _VP, _PV, _VP, _I64, _I64, _VP, _PGG, _VP, _VP, _I64, C.c_int32, _VP]),

@@ -13,6 +13,7 @@
 //       (+ tile_block_sum / pair_base / pair_reduce_kernel: deterministic mode)
 //   K8  project_backward_kernel chain rule to the reference's input tensors                     [B2, B3]
 //   K9  densify_stats_kernel / densify_stats_merge_kernel   screen-space densification statistics behind K7 (not in the reference)
+//   K10 raster_contrib_kernel  K6's traversal without colours: per-Gaussian blending-weight statistics (not in the reference)
 //
 // Everything is hand-written HIP for gfx950; no library kernels.  No MFMA: there is no dense contraction on this path.
 // No CPU fallback: without a GPU every entry point returns GSPLAT_ERR_HIP.
@@ -33,6 +34,7 @@
 #include "gs_raster.h"
 #include "gs_project_backward.h"
 #include "gs_densify.h"
+#include "gs_contrib.h"
 #include "gs_ops.h"
 
 thread_local char gsplat_err_buf[512] = "";      // shared with gsplat_loss.hip; read through gsplat_last_error()
@@ -299,6 +301,22 @@ int densify_stats_impl(const char* name, int64_t n, int64_t pair_capacity, const
     const Ctx c = open_ctx(n, v, project_state, stream_);
     LAUNCH("densify_stats_kernel", densify_stats_kernel, dim3(blocks256(n)), dim3(256), 0, c.st, n, c.ps.counts, (long long)pair_capacity, c.ps.tiles,
            c.ps.rec, grad2d, 0.5f * (float)v->W, 0.5f * (float)v->H, reinterpret_cast<f4*>(stats));
+    return GSPLAT_OK;
+}
+
+// gsplat_contribution / gsplat_frame_contribution behind their argument checks (every message names the entry)
+int contribution_impl(const char* name, int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, const void* bin_state,
+                      uint32_t* record, void* stream_) {
+    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
+    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
+    if (n < 0 || n > (int64_t)ID_MASK + 1 || pair_capacity < 0 || pair_capacity > 0xFFFFFFFFLL) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
+    if (!project_state || !bin_state || !record) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
+    if (!aligned16(record)) return fail(GSPLAT_ERR_BAD_ARG, "%s: record must be 16-byte aligned", name);
+    if (n == 0) return GSPLAT_OK;
+    const Ctx c = open_ctx(n, v, project_state, stream_);
+    LAUNCH("raster_contrib_kernel", raster_contrib_kernel, dim3((unsigned)c.nl), dim3(64), 0, c.st, c.ps.counts, (long long)pair_capacity, c.ps.ranges,
+           (const uint32_t*)bin_state, c.ps.rec, c.ps.order, c.vk.lists_x, c.vk.H, c.vk.W, c.vk.chi_clip, c.vk.alpha_max, c.vk.alpha_cutoff,
+           (uint32_t)(n - 1), record);
     return GSPLAT_OK;
 }
 
@@ -741,6 +759,26 @@ int gsplat_densify_stats_merge(int64_t n, float* pass, float* total, void* strea
     LAUNCH("densify_stats_merge_kernel", densify_stats_merge_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream_, n, reinterpret_cast<f4*>(pass),
            reinterpret_cast<f4*>(total));
     return GSPLAT_OK;
+}
+
+// ---- per-Gaussian contribution statistics (include/gsplat_mi355x.h; the kernel: gs_contrib.h) ----------------------------------
+int gsplat_contribution(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, const void* bin_state,
+                        uint32_t* record, void* stream_) {
+    return contribution_impl("gsplat_contribution", n, pair_capacity, v, project_state, bin_state, record, stream_);
+}
+
+int gsplat_frame_contribution(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame, int64_t frame_bytes,
+                              uint32_t* record, void* stream_) {
+    const char* name = "gsplat_frame_contribution";
+    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
+    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
+    if (n < 0 || pair_capacity < 0) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
+    if (!frame || !record) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
+    if (reinterpret_cast<uintptr_t>(frame) & 255u) return fail(GSPLAT_ERR_BAD_ARG, "%s: frame must be 256-byte aligned", name);
+    const FrameParts f = frame_parts(n, pair_capacity, v, 0);         // (project_state | bin_state lie at the same offsets with and without GSPLAT_FRAME_BACKWARD)
+    if (f.total > frame_bytes) return fail(GSPLAT_ERR_BAD_ARG, "%s: frame arena too small (gsplat_frame_bytes)", name);
+    const char* base = (const char*)frame;
+    return contribution_impl(name, n, pair_capacity, v, base + f.project_state, base + f.bin_state, record, stream_);
 }
 
 }  // extern "C"

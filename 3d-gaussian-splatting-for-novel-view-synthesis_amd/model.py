@@ -5,6 +5,8 @@
                                                               scripts/train.py:89-141
       .densify_and_prune_screen(stats, opacity_threshold=0.01, grad_threshold=0.0002, scale_threshold=0.01, max_screen_size=None)
                                                               the paper's criterion on ops.DensifyStats (not in the reference)
+      .prune_by_contribution(stats, min_weight_max=None, keep_fraction=None)
+                                                              contribution-based pruning on ops.ContributionStats (not in the reference)
       ._prune_points / ._split_points / ._clone_points        scripts/train.py:143-195
       .reset_opacity(threshold=0.01, bump=0.01)               scripts/train.py:564-569 (inline in the loop there)
       .save_checkpoint / .load_checkpoint                     scripts/train.py:197-219 (-> harness.py)
@@ -25,6 +27,8 @@ Host-side tensor bookkeeping (boolean masks + concatenation, run every `densific
 torch ops on whatever device the parameters live on; no kernel of its own.  `generator` makes the split noise
 reproducible and identical on every data-parallel rank.
 """
+import math
+
 import torch
 
 from . import harness
@@ -76,6 +80,38 @@ class GaussianModel:
         kept = data[~prune_mask]
         hot = kept[:, 0] / kept[:, 1].clamp(min=1) >= grad_threshold
         self._densify(hot, scale_threshold, generator)
+
+    def prune_by_contribution(self, stats, min_weight_max=None, keep_fraction=None):
+        """Remove the Gaussians that never matter in the composite of the views accumulated in `stats` (an ops.ContributionStats of
+        this model's N rows; on any device).  Returns the number removed.
+          min_weight_max   removes the rows with weight_max < min_weight_max -- every row is evaluated, never-seen ones included.
+                           0.0 removes nothing; torch.finfo(torch.float32).tiny removes exactly the rows with weight_max == 0.
+          keep_fraction    in (0, 1]: of the survivors of the first rule, keeps the ceil(keep_fraction * survivors) with the largest
+                           weight_sum -- a stable sort on the integer sum_q, descending, ties broken by the lower index, so the choice
+                           is the same on every rank and in every run.
+        The two rules apply in that order; a call with neither raises ValueError, like a record of another size."""
+        if min_weight_max is None and keep_fraction is None:
+            raise ValueError("prune_by_contribution needs min_weight_max, keep_fraction or both")
+        n = self.pos.shape[0]
+        data = getattr(stats, "data", None)
+        if not isinstance(data, torch.Tensor) or tuple(data.shape) != (n, 4) or data.dtype != torch.int32:
+            raise ValueError(f"the statistics must be an ops.ContributionStats of {n} rows (the model's Gaussians), not "
+                             f"{tuple(data.shape) if isinstance(data, torch.Tensor) else type(stats).__name__}")
+        if keep_fraction is not None and not 0.0 < float(keep_fraction) <= 1.0:
+            raise ValueError(f"keep_fraction must lie in (0, 1], not {keep_fraction!r}")
+        if min_weight_max is not None and not float(min_weight_max) >= 0.0:
+            raise ValueError(f"min_weight_max must be >= 0, not {min_weight_max!r}")
+        remove = torch.zeros(n, dtype=torch.bool, device=data.device)
+        if min_weight_max is not None:
+            remove = stats.weight_max < float(min_weight_max)
+        if keep_fraction is not None:
+            alive = torch.nonzero(~remove).reshape(-1)              # ascending index
+            keep = min(math.ceil(float(keep_fraction) * int(alive.numel())), int(alive.numel()))
+            order = torch.sort(stats.sum_q[alive], descending=True, stable=True).indices       # ties: the lower index first
+            remove[alive[order[keep:]]] = True
+        removed = int(remove.sum())
+        self._prune_points(remove.to(self.pos.device))
+        return removed
 
     def _densify(self, hot, scale_threshold, generator):
         """Split the `hot` Gaussians whose largest scale exceeds scale_threshold, clone the other hot ones (children at the end:

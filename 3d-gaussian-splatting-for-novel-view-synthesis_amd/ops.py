@@ -960,6 +960,129 @@ def _stats_record(pos):
     return data
 
 
+class ContributionStats:
+    """Per-Gaussian contribution statistics of N Gaussians: how much each Gaussian takes part in the composite of the
+    frames added so far.  `.data` [N, 4] int32 -- the 32-bit words of include/gsplat_mi355x.h, every one an order-independent integer:
+    words 0-1 the little-endian uint64 sum_q (units of 2^-32), word 2 the float32 bits of weight_max, word 3 the uint32 pixel count
+    (wraps after 2^32 pixel hits).
+
+        stats = ops.contribution(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2ws, H, W, fx, fy, cx, cy)
+        never_matters = stats.weight_max == 0
+
+    Adding is integer add / max, so the record holds the same bits whatever order frames, streams or ranks arrive in.  Works on
+    'cpu' too (accessors, merge_, all_reduce over gloo): only ops.contribution needs the GPU."""
+
+    def __init__(self, n, device):
+        self.data = torch.zeros((int(n), 4), dtype=torch.int32, device=device)
+        self.frames = 0                     # frames accumulated (a host count)
+
+    n = property(lambda self: self.data.shape[0])
+    sum_q = property(lambda self: self.data.view(torch.int64)[:, 0])                 # (read as unsigned: below 2^63 in practice)
+    weight_sum = property(lambda self: self.sum_q.to(torch.float64) * 2.0 ** -32)
+    weight_max = property(lambda self: self.data[:, 2].contiguous().view(torch.float32))
+    pixels = property(lambda self: self.data[:, 3].to(torch.int64) & 0xFFFFFFFF)
+
+    def reset(self, n=None):
+        """Zero the record; with another n, a fresh record of n rows (after a pruning)."""
+        if n is None or int(n) == self.data.shape[0]:
+            self.data.zero_()
+        else:
+            self.data = torch.zeros((int(n), 4), dtype=torch.int32, device=self.data.device)
+        self.frames = 0
+        return self
+
+    def merge_(self, other):
+        """self (+)= other -- (add, max, add) on the integer words, frames added; `other` is left as it is."""
+        a, b = self.data, other.data
+        if b.shape != a.shape or b.device != a.device or b.dtype != torch.int32 or not b.is_contiguous() or other is self:
+            raise ValueError(f"merge_: the other record must be another int32 {tuple(a.shape)} record on {a.device}")
+        a.view(torch.int64)[:, 0] += b.view(torch.int64)[:, 0]
+        a[:, 2] = torch.maximum(a[:, 2], b[:, 2])        # (non-negative floats order like their bits)
+        a[:, 3] += b[:, 3]                                # (int32 wraps like uint32)
+        self.frames += other.frames
+        return self
+
+    def all_reduce(self, group=None):
+        """SUM of sum_q and pixels, MAX of word 2 over the ranks of `group`, and the sum of .frames (plain torch.distributed on integer
+        copies: CPU tensors over gloo work too).  Every rank ends with the same bits."""
+        import torch.distributed as dist
+        sums = torch.stack([self.sum_q, self.pixels, torch.full_like(self.sum_q, int(self.frames))], 1).contiguous()      # int64 [N, 3]
+        if sums.shape[0] == 0:
+            sums = torch.tensor([[0, 0, int(self.frames)]], dtype=torch.int64, device=self.data.device)
+        mx = self.data[:, 2].contiguous()
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(mx, op=dist.ReduceOp.MAX, group=group)
+        self.frames = int(sums[0, 2])
+        if self.data.shape[0]:
+            self.data.view(torch.int64)[:, 0] = sums[:, 0]
+            self.data[:, 2] = mx
+            self.data[:, 3] = sums[:, 1].contiguous().view(torch.int32).view(-1, 2)[:, 0]      # the low words: pixels mod 2^32
+        return self
+
+
+@torch.no_grad()
+def contribution(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2ws, H, W, fx, fy, cx, cy, near=0.01, far=100.0, pix_guard=32, T=16,
+                 min_conis=1e-6, chi_square_clip=6.25, alpha_max=0.99, alpha_cutoff=1 / 128., sh_degree=3, *, lowpass=0.0, antialias=False,
+                 stats=None):
+    """The contribution statistics (ContributionStats) of the camera poses `c2ws`, arguments as for render_frames(): for every pose
+    project -> bin -> gsplat_contribution through the separate library calls; nothing is rasterised and no image exists.  Every
+    frame waits for its pair count like render_gaussians(), so its buffers are exact and nothing is repeated or counted twice.
+    Adds into `stats` (a ContributionStats of pos.shape[0] rows on pos.device; anything else raises ValueError before anything is
+    queued), or into a fresh record; returns it.  A pose without a survivor adds nothing; a pose with survivors but none on screen
+    raises the reference's off-screen Exception, and `stats` then holds the poses before it."""
+    spec = _frame_spec(True, H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis, chi_square_clip, alpha_max, alpha_cutoff,
+                       sh_degree=sh_degree, lowpass=lowpass, antialias=antialias)
+    if not isinstance(pos, torch.Tensor):
+        raise TypeError("pos must be a torch.Tensor")
+    n, dev = pos.shape[0], pos.device
+    if stats is not None:
+        data = getattr(stats, "data", None)
+        if (not isinstance(stats, ContributionStats) or data.dtype != torch.int32 or tuple(data.shape) != (n, 4) or data.device != dev
+                or not data.is_contiguous() or data.data_ptr() % 16):
+            raise ValueError(f"contribution: stats must be a ContributionStats of {n} rows (contiguous int32 {(n, 4)}) on {dev}, not "
+                             f"{type(stats).__name__}" + (f" {data.dtype} {tuple(data.shape)} on {data.device}" if isinstance(data, torch.Tensor) else ""))
+    opa = opacity_raw if opacity_raw.dim() == 1 else opacity_raw.reshape(-1)
+    ins = dict(pos=_f32(pos, (n, 3), "pos"), opacity_raw=_f32(opa, (n,), "opacity_raw"))
+    for name, t in (("scale_raw", scale_raw), ("q_raw", q_raw), ("f_dc", f_dc), ("f_rest", f_rest)):
+        ins[name] = _f32(t, (n,) + _ROW_SHAPE[name], name)
+    cams = [_f32(torch.as_tensor(c, dtype=torch.float32, device=dev) if not isinstance(c, torch.Tensor) else c, (4, 4), "c2w") for c in c2ws]
+    if stats is None:
+        stats = ContributionStats(n, dev)
+    if n == 0:                                  # nothing survives by construction
+        stats.frames += len(cams)
+        return stats
+    lib, view = _abi.lib(), spec.view
+    g = _abi.Gaussians(n, *map(_p, map(ins.get, _INPUT_FIELDS)))
+    if torch.cuda.current_device() != dev.index:
+        torch.cuda.set_device(dev)
+    sp = torch.cuda.current_stream(dev).cuda_stream
+    key, st = (dev.type, dev.index, sp), C.c_void_p(sp)
+    counters = _ws.get_counter_block(dev, _COUNTER_BYTES or _counter_bytes(lib), key)
+    proj_state = torch.empty(lib.gsplat_project_state_bytes(n, C.byref(view)), dtype=torch.uint8, device=dev)
+    flags = _abi.GSPLAT_PROJECT_COUNTS_MAPPED | _PROJECT_DEGREE[spec.sh_degree] | spec.filter
+    ckey = capacity_key(dev, spec, n)
+    for c2w in cams:
+        pinned, _ = _ws.next_pinned(dev, key)
+        ready = _ws.get_event(dev, key=key)
+        _abi.check(lib.gsplat_project(C.byref(g), _p(c2w), C.byref(view), _p(proj_state), _p(counters), counters.numel(),
+                                      C.c_void_p(pinned.data_ptr()), C.c_void_p(ready.cuda_event), flags, st), "gsplat_project")
+        ready.synchronize()                      # the one host wait of a frame: the pair count sizes the binning buffers
+        counts = _abi.Counts.from_buffer_copy(pinned.numpy().tobytes())
+        _ws.note_pairs(ckey, counts.n_binned)
+        scene = lib.gsplat_classify_counts(C.byref(counts))
+        if scene == _abi.GSPLAT_SCENE_ALL_OFFSCREEN:
+            raise Exception(OFFSCREEN_MSG)
+        stats.frames += 1
+        if scene == _abi.GSPLAT_SCENE_ALL_CULLED:
+            continue
+        pairs = int(counts.n_binned)
+        bin_state = torch.empty(lib.gsplat_bin_state_bytes(pairs, C.byref(view)), dtype=torch.uint8, device=dev)
+        scratch = _ws.get_scratch(dev, lib.gsplat_bin_scratch_bytes(pairs, C.byref(view)), key)
+        _abi.check(lib.gsplat_bin(n, pairs, C.byref(view), _p(proj_state), _p(bin_state), _p(scratch), scratch.numel(), st), "gsplat_bin")
+        _abi.check(lib.gsplat_contribution(n, pairs, C.byref(view), _p(proj_state), _p(bin_state), _p(stats.data), st), "gsplat_contribution")
+    return stats
+
+
 def sh_accumulate(pos, eyes, grad_logit, scale=1.0, sh_degree=3):
     """(grad_f_dc [N,3], grad_f_rest [N,45]) = scale * sum over views of grad_logit[v] (x) Y(direction from eyes[v] to pos).
     sh_degree: the degree the views were rendered at; the columns of the inactive bases are zeros."""

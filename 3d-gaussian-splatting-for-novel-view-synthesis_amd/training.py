@@ -216,6 +216,51 @@ class Trainer:
         k = self.cfg.sh_degree_interval
         return 3 if k == 0 else max(0, min(3, int(iteration) // k))
 
+    def prune_by_contribution(self, iteration, views, min_weight_max=None, keep_fraction=None):
+        """Contribution-based pruning (DESIGN.md §18): accumulate ops.contribution over this rank's `views` (the dicts step() takes;
+        the trainer's lowpass / antialias, the SH degree of `iteration`), all-reduce the integer record over the group when
+        world > 1 -- every rank then decides from the same bits --, GaussianModel.prune_by_contribution(stats, min_weight_max,
+        keep_fraction), and a fresh optimiser at the position learning rate of `iteration`, exactly as after a densification; the
+        densification window restarts over the new set.  Returns {'removed', 'gaussians', 'frames'}.  Not part of step().  Data parallel:
+        collective -- every rank calls it; a failure on one rank (an off-screen pose) raises on every rank before anything is pruned."""
+        if min_weight_max is None and keep_fraction is None:
+            raise ValueError("prune_by_contribution needs min_weight_max, keep_fraction or both")
+        c, m = self.cfg, self.model
+        dev = m.pos.device
+        stats = ops.ContributionStats(m.get_num_gaussians(), dev)
+        groups = {}
+        for v in views:                                        # poses that share a camera go through one call
+            cam = (int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']))
+            groups.setdefault(cam, []).append(torch.as_tensor(v['c2w'], dtype=torch.float32).to(dev))
+        world, err = self._world(), None
+        try:
+            for cam, poses in groups.items():
+                ops.contribution(m.pos, m.f_dc, m.f_rest, m.opacity_raw, m.scale_raw, m.q_raw, poses, *cam, sh_degree=self.sh_degree(iteration),
+                                 stats=stats, **self._filter_kw)
+        except Exception as e:                # single process: the exception leaves as it is
+            if world == 1:
+                raise
+            err = e
+        if world > 1:
+            # as in step(): what happened on this rank as ONE code and ONE agreement, so that a rank whose pose is off screen does not
+            # leave its peers waiting in the all-reduce -- every rank raises, or none does, and nothing is pruned anywhere
+            status = dp.STATUS_OK if err is None else (dp.STATUS_OFFSCREEN if str(err) == ops.OFFSCREEN_MSG else dp.STATUS_ERROR)
+            status = dp.agree_status(status, self.group, device=dev)
+            if status != dp.STATUS_OK:
+                if err is not None:
+                    raise err
+                if status == dp.STATUS_OFFSCREEN:
+                    raise Exception(ops.OFFSCREEN_MSG + " (on another rank of the data-parallel group)")
+                raise RuntimeError("another rank of the data-parallel group failed in prune_by_contribution")
+            stats.all_reduce(self.group)
+        removed = m.prune_by_contribution(stats, min_weight_max=min_weight_max, keep_fraction=keep_fraction)
+        pos_lr = optim.position_lr(iteration, c.position_lr_init, c.position_lr_final, c.position_lr_delay_mult, c.position_lr_max_steps)
+        self.optimizer = self._new_optimizer(pos_lr)
+        if self.densify_stats is not None:
+            self.densify_stats.reset(m.get_num_gaussians())
+        self._pass_stats, self._pass_dirty = [], False
+        return {'removed': removed, 'gaussians': m.get_num_gaussians(), 'frames': stats.frames}
+
     def step(self, iteration, views, global_views=None, views_per_rank=None):
         """One iteration on this rank's `views` (list of dicts with image [H,W,3], c2w [4,4], H, W, fx, fy, cx, cy — the
         sample dict of data.GaussianDataset).  Data parallel: the ranks may hold different numbers of views; how many each

@@ -377,6 +377,30 @@ int gsplat_frame_densify_stats(int64_t n, int64_t pair_capacity, const gsplat_vi
                                int64_t frame_bytes, float* stats, void* stream);
 int gsplat_densify_stats_merge(int64_t n, float* pass, float* total, void* stream);
 
+/* ---- per-Gaussian contribution statistics (not in the reference) ------------------------------------------------------------
+ * How much does each Gaussian take part in the composite?  With the blending weight w_i(p) = alpha_i T_i [T_i > 5e-5] of Gaussian i
+ * at pixel p, exactly as the forward rasteriser forms it, one frame adds to row i of `record`, over all pixels of all lists the
+ * Gaussian is binned into,
+ *     weight_sum += sum_p w_i(p)      weight_max = max(weight_max, max_p w_i(p))      pixels += #{p : w_i(p) > 0}.
+ * A record is [n,4] 32-bit words, 16-byte aligned, one row per Gaussian, every word an order-independent integer:
+ *     words 0-1  uint64 sum_q (little endian) in units of 2^-32: every (list, Gaussian) pair adds round_to_nearest(pair_sum * 2^32),
+ *                pair_sum = the float32 sum of w over the pair's <= 128 pixels (< 2^7: 2^25 such terms fit)
+ *     word 2     the float32 bits of weight_max (non-negative: an unsigned integer maximum)
+ *     word 3     uint32 pixels; wraps after 2^32 pixel hits (not guarded)
+ * The kernel adds with integer atomics, so the record is bitwise the same whatever the order of waves, streams, frames or ranks:
+ * calls on different streams may add into one record at the same time.  The caller zeroes a new record.  Rows of Gaussians in no
+ * list are not touched, and a pair without a pixel of w > 0 (everything behind an opaque surface) issues no memory operation.  A frame
+ * with nothing on screen, or one whose pairs outgrew pair_capacity (n_binned > pair_capacity in its device counters: its lists are
+ * garbage), adds nothing -- decided on the device, as in gsplat_densify_stats.  No image is written and no colour is read.
+ *   gsplat_contribution        after gsplat_bin on the same project_state / bin_state and pair_capacity; no raster call is needed.
+ *   gsplat_frame_contribution  the same on the arena of gsplat_forward_deferred (with or without GSPLAT_FRAME_BACKWARD).
+ * GSPLAT_ERR_BAD_ARG (the text names the entry): a NULL pointer, n < 0, pair_capacity < 0, a record that is not 16-byte aligned,
+ * frame_bytes below gsplat_frame_bytes(n, pair_capacity, v, 0).  n == 0: GSPLAT_OK, nothing is launched.                            */
+int gsplat_contribution(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state,
+                        const void* bin_state, uint32_t* record, void* stream);
+int gsplat_frame_contribution(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame,
+                              int64_t frame_bytes, uint32_t* record, void* stream);
+
 /* ---- the two small exported functions as stand-alone ops --------------------------------------- */
 int gsplat_build_sigma(int64_t n, const float* scale_raw, const float* q_raw, float* sigma, void* stream);
 int gsplat_build_sigma_backward(int64_t n, const float* scale_raw, const float* q_raw, const float* grad_sigma,
