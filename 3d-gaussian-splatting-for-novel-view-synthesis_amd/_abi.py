@@ -124,6 +124,17 @@ class BinLayout(C.Structure):
     _fields_ = [("bytes", C.c_int64), ("sorted_ids", C.c_int64), ("pair_mask", C.c_int64)]
 
 
+class McmcMoments(C.Structure):
+    """gsplat_mcmc_moments: (exp_avg, exp_avg_sq) of each parameter, NULL pairs allowed."""
+    _fields_ = [(k, C.c_void_p * 2) for k in ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")]
+
+
+class McmcLayout(C.Structure):
+    """gsplat_mcmc_layout: byte offsets inside the MCMC scratch and the two constants of the scan (tests and tools only)."""
+    _fields_ = [(k, C.c_int64) for k in ("bytes", "reg", "w", "prefix", "src", "count", "total", "block_sums")] + [
+        ("scan_block", C.c_int32), ("scan_chunk", C.c_int32)]
+
+
 _VP, _I64, _INT = C.c_void_p, C.c_int64, C.c_int
 _PV, _PG, _PGG, _PC = C.POINTER(View), C.POINTER(Gaussians), C.POINTER(GaussianGrads), C.POINTER(Counts)
 
@@ -179,6 +190,11 @@ SIGNATURES = {
     "gsplat_adam_step_multi": (_INT, [C.c_int32, C.POINTER(AdamGroup), C.c_float, C.c_float, C.c_float, _VP]),
     "gsplat_backward_adam_rest": (_INT, [_PG, _VP, _PV, _VP, _I64, _I64, _VP, _PGG, _VP, _I64, C.c_int32, C.POINTER(AdamGroup), C.c_float, C.c_float,
                                          C.c_float, _VP]),
+    "gsplat_mcmc_scratch_bytes": (_I64, [_I64]),
+    "gsplat_mcmc_scratch_layout": (_INT, [_I64, C.POINTER(McmcLayout)]),
+    "gsplat_mcmc_noise": (_INT, [_I64, _VP, _VP, _VP, _VP, C.c_float, C.c_uint64, C.c_uint32, _VP]),
+    "gsplat_mcmc_regularise": (_INT, [_I64, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP, _VP, _VP, _VP]),
+    "gsplat_mcmc_refine": (_INT, [_VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(McmcMoments), _I64, C.c_float, C.c_uint64, C.c_uint32, _VP, _VP]),
 }
 
 _lib = None

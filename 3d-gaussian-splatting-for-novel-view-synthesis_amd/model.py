@@ -7,6 +7,9 @@
                                                               the paper's criterion on ops.DensifyStats (not in the reference)
       .prune_by_contribution(stats, min_weight_max=None, keep_fraction=None)
                                                               contribution-based pruning on ops.ContributionStats (not in the reference)
+      .refine_mcmc(optimizer, cap_max, min_opacity=0.005, growth=1.05, seed=0, iteration=0)
+                                                              MCMC relocation at a fixed budget (not in the reference):
+                                                              the one rule that KEEPS the optimiser and its moments
       ._prune_points / ._split_points / ._clone_points        scripts/train.py:143-195
       .reset_opacity(threshold=0.01, bump=0.01)               scripts/train.py:564-569 (inline in the loop there)
       .save_checkpoint / .load_checkpoint                     scripts/train.py:197-219 (-> harness.py)
@@ -16,7 +19,8 @@ Semantics kept (checked against the reference's own methods, tests/golden/densif
   * split keeps the parent and appends ONE child per selected Gaussian: position + randn * exp(scale_raw) * 0.1, scale_raw - 0.5,
     everything else copied; clone appends an exact copy; children go to the end, in mask order; split children before clones;
   * `max_screen_size` is accepted and unused by densify_and_prune, as in the reference (densify_and_prune_screen applies it);
-  * the optimiser state is not carried over (the reference builds a fresh Adam after every densification, :554-561).
+  * the optimiser state is not carried over (the reference builds a fresh Adam after every densification, :554-561) -- by these
+    rules; refine_mcmc rewrites rows in place and carries it.
 
 One documented divergence: in the reference the clone mask is computed before the split and applied after it
 (:136-141), so when a split and a clone are both due it indexes [N+S]-row tensors with an [N]-row mask and raises
@@ -31,7 +35,7 @@ import math
 
 import torch
 
-from . import harness
+from . import harness, mcmc
 
 PARAM_KEYS = harness.PARAM_KEYS
 
@@ -112,6 +116,36 @@ class GaussianModel:
         removed = int(remove.sum())
         self._prune_points(remove.to(self.pos.device))
         return removed
+
+    @torch.no_grad()
+    def refine_mcmc(self, optimizer, cap_max, min_opacity=0.005, growth=1.05, seed=0, iteration=0):
+        """One MCMC refinement.  Growth: n_target = min(cap_max, int(growth N)); if that is more than N, dead rows are
+        appended (opacity_raw = -20, q_raw = (0, 0, 0, 1), everything else 0) and `optimizer` (a GaussianAdam over this model's
+        parameters, or None) follows with GaussianAdam.grow_rows -- moments zero-padded, step counts kept; N never shrinks.  Then one
+        library call (mcmc.relocate): every dead row, old or appended, becomes a copy of a live one drawn in proportion to the
+        opacities.  No host read anywhere: the number of rows is a function of (N, cap_max, growth) alone.  Returns the rows appended."""
+        n = self.get_num_gaussians()
+        if type(cap_max) is not int or cap_max < 1:
+            raise ValueError(f"cap_max must be an integer >= 1, not {cap_max!r}")
+        if not (isinstance(growth, (int, float)) and not isinstance(growth, bool) and 1.0 <= growth < float("inf")):
+            raise ValueError(f"growth must be a finite number >= 1, not {growth!r}")
+        if not (isinstance(min_opacity, float) and 0.0 < min_opacity < 1.0):
+            raise ValueError(f"min_opacity must be a float in (0, 1), not {min_opacity!r}")
+        extra = max(0, min(cap_max, int(growth * n)) - n)
+        if extra:
+            for k in PARAM_KEYS:
+                old = getattr(self, k)
+                pad = old.new_zeros((extra,) + tuple(old.shape[1:]))
+                if k == 'opacity_raw':
+                    pad.fill_(-20.0)
+                elif k == 'q_raw':
+                    pad[:, 3] = 1.0
+                new = torch.nn.Parameter(torch.cat([old.detach(), pad], dim=0))
+                if optimizer is not None:
+                    optimizer.grow_rows(old, new)
+                setattr(self, k, new)
+        mcmc.relocate(self, optimizer, min_opacity, seed, iteration)
+        return extra
 
     def _densify(self, hot, scale_threshold, generator):
         """Split the `hot` Gaussians whose largest scale exceeds scale_threshold, clone the other hot ones (children at the end:

@@ -97,6 +97,29 @@ class GaussianAdam:
                                   'exp_avg_sq': torch.zeros_like(p, memory_format=torch.contiguous_format)}
         return st
 
+    @torch.no_grad()
+    def grow_rows(self, old_param, new_param):
+        """`new_param` is `old_param` with rows appended (density control that keeps the optimiser, model.refine_mcmc): the state moves
+        to the new tensor -- both moments padded with zero rows, `step` kept -- and the parameter group holds the new tensor."""
+        if new_param.shape[1:] != old_param.shape[1:] or new_param.shape[0] < old_param.shape[0]:
+            raise ValueError(f"grow_rows: {tuple(old_param.shape)} cannot grow into {tuple(new_param.shape)}")
+        found = False
+        for g in self.param_groups:
+            for k, p in enumerate(g['params']):
+                if p is old_param:
+                    g['params'][k], found = new_param, True
+        if not found:
+            raise ValueError("grow_rows: the old parameter is not one of this optimiser's")
+        st = self.state.pop(old_param, None)
+        if st is not None:
+            extra = new_param.shape[0] - old_param.shape[0]
+            for key in ('exp_avg', 'exp_avg_sq'):
+                m = st[key]
+                st[key] = torch.cat([m, m.new_zeros((extra,) + tuple(m.shape[1:]))], dim=0) if extra else m
+            self.state[new_param] = st
+        if getattr(self, "_pending_clip", None) is not None and self._pending_clip[0] is old_param:
+            self._pending_clip = None
+
     def fused_rest_update(self, param):
         """For an iteration of ONE view rendered inside ops.deferred_checks(): the backward pass applies this optimiser's step of
         `param` (the model's f_rest: 81 % of all parameters) as the gradient is formed, param.grad stays None and step() skips it.

@@ -15,6 +15,10 @@ Follows scripts/train.py:446-569 statement by statement, on the fused pieces of 
                                                (TrainConfig.densify_rule = "screen": densify_and_prune_screen on the screen-space
                                                statistics of the views since the last densification -- not in the reference)
     opacity reset every `opacity_reset_interval` (:564-569)     GaussianModel.reset_opacity
+    [densify_rule = "mcmc", not in the reference; DESIGN.md §19]  a fixed budget cap_max instead of thresholds: the two regularisers join
+                                               the complete gradients (mcmc.regularise), the position noise follows the step
+                                               (mcmc.add_noise), and GaussianModel.refine_mcmc takes densification's place --
+                                               rows are rewritten in place and the optimiser is KEPT; no opacity reset
 
 With data parallelism every rank holds the full model, renders its share of the batch's views and divides by the GLOBAL
 number of views; the split noise of densification comes from a generator seeded identically on all ranks, so the
@@ -26,7 +30,7 @@ from dataclasses import dataclass
 import torch
 import torch.distributed as dist
 
-from . import _abi, dp, losses, ops, optim
+from . import _abi, dp, losses, mcmc, ops, optim
 
 
 @dataclass
@@ -94,6 +98,20 @@ class TrainConfig:
     background_seed: int = 0
     lambda_alpha: float = 0.0
     lambda_depth: float = 0.0
+    # densify_rule = "mcmc" (not in the reference; Kheradmand et al. 2024): the model grows by mcmc_growth per refinement
+    # up to cap_max Gaussians and stays there; every densification_interval iterations within [mcmc_start_iter, densify_until_iter)
+    # the Gaussians with sigmoid(opacity_raw) <= mcmc_min_opacity are moved onto live ones.  Every iteration adds
+    # mcmc_opacity_reg mean(opacity) + mcmc_scale_reg mean(scale) to the loss and, after the step, noise of size
+    # lr_pos mcmc_noise_lr to the positions of the transparent Gaussians.  mcmc_seed keys that noise and the relocation draw (with the
+    # iteration: the same on every rank).  All ignored by the other rules.
+    cap_max: int = 1_000_000
+    mcmc_start_iter: int = 500
+    mcmc_min_opacity: float = 0.005
+    mcmc_noise_lr: float = 5e5
+    mcmc_opacity_reg: float = 0.01
+    mcmc_scale_reg: float = 0.01
+    mcmc_growth: float = 1.05
+    mcmc_seed: int = 0
 
 
 _side_streams = {}           # per device: the two streams the views of an iteration alternate between (TrainConfig.view_streams)
@@ -107,8 +125,9 @@ class Trainer:
         self.model = model
         self.cfg = config or TrainConfig()
         self.group = group
-        if self.cfg.densify_rule not in ("reference", "screen"):
-            raise ValueError(f"densify_rule must be 'reference' or 'screen', not {self.cfg.densify_rule!r}")
+        if self.cfg.densify_rule not in ("reference", "screen", "mcmc"):
+            raise ValueError(f"densify_rule must be 'reference', 'screen' or 'mcmc', not {self.cfg.densify_rule!r}")
+        _check_mcmc(self.cfg)
         if type(self.cfg.sh_degree_interval) is not int or self.cfg.sh_degree_interval < 0:
             raise ValueError(f"sh_degree_interval must be an integer >= 0, not {self.cfg.sh_degree_interval!r}")
         self._filter_kw = _abi.filter_kwargs(self.cfg.lowpass, self.cfg.antialias)      # (ValueError for a mode the kernels cannot do)
@@ -410,9 +429,23 @@ class Trainer:
             p = getattr(m, k)
             if p.grad is None and not (folded and p is m.f_rest):
                 p.grad = torch.zeros_like(p)
+        use_mcmc = c.densify_rule == "mcmc"
+        if use_mcmc:
+            # the gradients are complete (every view, every rank): the regularisers join them, and the loss, in ONE launch
+            reg = mcmc.regularise(m, c.mcmc_opacity_reg, c.mcmc_scale_reg, base=acc[2] + acc_aux[2] if aux_pass else acc[2])
         self.optimizer.clip_grad_norm_(m.pos, max_norm=1.0)
         self.optimizer.step()
         densified = False
+        if use_mcmc:
+            mcmc.add_noise(m, pos_lr * c.mcmc_noise_lr, c.mcmc_seed, int(iteration))
+            if c.mcmc_start_iter <= iteration < c.densify_until_iter and iteration % c.densification_interval == 0:
+                # in place: the optimiser object and the moments of every row that did not change stay; nothing is read back
+                m.refine_mcmc(self.optimizer, cap_max=c.cap_max, min_opacity=c.mcmc_min_opacity, growth=c.mcmc_growth,
+                              seed=c.mcmc_seed, iteration=int(iteration))
+                densified = True
+            return {'loss': reg[2], 'l1': acc[0], 'ssim': acc[1], 'reg_opacity': reg[0], 'reg_scale': reg[1],
+                    'gaussians': m.get_num_gaussians(), 'lr_pos': pos_lr, 'densified': densified, 'sh_degree': sh_degree,
+                    **(dict(l_alpha=acc_aux[0], l_depth=acc_aux[1]) if aux_pass else {})}
         if iteration < c.densify_until_iter and iteration % c.densification_interval == 0:
             if screen:
                 if world > 1:                     # every rank decides from the statistics of all views: the replicas stay bit-identical
@@ -435,6 +468,26 @@ class Trainer:
         if aux_pass:
             out.update(loss=acc[2] + acc_aux[2], l_alpha=acc_aux[0], l_depth=acc_aux[1])
         return out
+
+
+def _check_mcmc(c):
+    """The MCMC fields of a TrainConfig (ValueError for a value the rule cannot run with), whatever the rule is."""
+    def real(x):
+        return isinstance(x, (int, float)) and not isinstance(x, bool) and x == x and abs(x) != float("inf")
+    if type(c.cap_max) is not int or not 1 <= c.cap_max < 2 ** 31:
+        raise ValueError(f"cap_max must be an integer in [1, 2^31), not {c.cap_max!r}")
+    if type(c.mcmc_start_iter) is not int or c.mcmc_start_iter < 0:
+        raise ValueError(f"mcmc_start_iter must be an integer >= 0, not {c.mcmc_start_iter!r}")
+    if not (isinstance(c.mcmc_min_opacity, float) and 0.0 < c.mcmc_min_opacity < 1.0):
+        raise ValueError(f"mcmc_min_opacity must be a float in (0, 1), not {c.mcmc_min_opacity!r}")
+    for name in ("mcmc_noise_lr", "mcmc_opacity_reg", "mcmc_scale_reg"):
+        x = getattr(c, name)
+        if not (real(x) and x >= 0):
+            raise ValueError(f"{name} must be a finite number >= 0, not {x!r}")
+    if not (real(c.mcmc_growth) and c.mcmc_growth >= 1.0):
+        raise ValueError(f"mcmc_growth must be a finite number >= 1, not {c.mcmc_growth!r}")
+    if type(c.mcmc_seed) is not int or not 0 <= c.mcmc_seed < 2 ** 64:
+        raise ValueError(f"mcmc_seed must be an integer in [0, 2^64), not {c.mcmc_seed!r}")
 
 
 def _check_background(background):

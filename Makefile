@@ -9,7 +9,8 @@ all:
 # Sanitizers run on the CPU builds only (GPU AddressSanitizer is not available on the pool): the host build of the projection
 # math (the same gs_math.h / gs_body.h the HIP kernels inline) and the plain-C oracle, each under AddressSanitizer + UBSan,
 # driven by their own test files.  Python is not instrumented, so the runtime is preloaded and leak checking is off.
-check-asan:
+# The MCMC arithmetic (gs_mcmc.h) goes through a stand-alone instrumented program of its own, which needs no preloaded runtime.
+check-asan: check-asan-mcmc
 	mkdir -p $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -std=c++17 -shared -fPIC -o $(ASAN_DIR)/libgsmath_host_asan.so $(PKG)/csrc/host_math_check.cpp
 	gcc $(ASAN_FLAGS) -std=c99 -fopenmp -shared -fPIC -o $(ASAN_DIR)/libgs_oracle_asan.so oracle/gs_oracle.c -lm
@@ -18,4 +19,9 @@ check-asan:
 	  GSPLAT_HOSTMATH_LIB=$(CURDIR)/$(ASAN_DIR)/libgsmath_host_asan.so GS_ORACLE_LIB=$(CURDIR)/$(ASAN_DIR)/libgs_oracle_asan.so \
 	  python -m pytest tests/test_product_math_cpu.py tests/test_pose_grad_cpu.py tests/test_c_oracle_golden.py -x -q -p no:cacheprovider
 
-.PHONY: all check-asan
+check-asan-mcmc:
+	mkdir -p $(ASAN_DIR)
+	g++ $(ASAN_FLAGS) -std=c++17 -o $(ASAN_DIR)/host_mcmc_selftest $(PKG)/csrc/host_mcmc_selftest.cpp
+	ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/host_mcmc_selftest
+
+.PHONY: all check-asan check-asan-mcmc

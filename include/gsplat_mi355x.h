@@ -492,6 +492,48 @@ int gsplat_backward_adam_rest(const gsplat_gaussians* g, const float* c2w, const
                               int64_t det_scratch_bytes, int32_t flags, const gsplat_adam_group* f_rest, float beta1, float beta2,
                               float eps, void* stream);
 
+/* ---- density control at a fixed budget: MCMC relocation, position noise, regularisers (not in the reference) ----
+ * Random numbers are Philox4x32-10 with key = the two halves of `seed` and counter = (row low, row high, iteration, stream), stream 0
+ * for the noise and 1 for the relocation: a function of its arguments alone, the same bits on every rank.  n < 2^31 everywhere.
+ *
+ * Noise: pos_i += Sigma_i (z_i scale g_i), Sigma the covariance the projection builds from (scale_raw, q_raw), z three
+ *   Box-Muller normals of the row, g = 1 / (1 + exp(100 sigmoid(opacity_raw) - 0.5)); a row whose g is 0 is not written.
+ * Regularise: values[3] (device) = (L_o, L_s, *base + L_o + L_s) with L_o = lambda_opacity mean sigmoid(opacity_raw), L_s =
+ *   lambda_scale mean exp(scale_raw), base a nullable device scalar; d L_o / d opacity_raw and d L_s / d scale_raw are ADDED to the
+ *   two gradient arrays (each nullable: values only).  One partial sum per workgroup, added in index order in double: the same
+ *   bits every call.  ONE launch.
+ * Refine: row i is dead iff sigmoid(opacity_raw_i) <= min_opacity; a live row weighs max(1, floor(sigmoid 2^24)).  Every dead row draws
+ *   a source in proportion to the weights (an exclusive uint64 prefix sum and a binary search: exact, order-free), becomes a bit copy
+ *   of its pos, f_dc, f_rest, q_raw, and source and copies get the opacity and the scale that leave the rendered image unchanged
+ *   (n = min(draws + 1, 51) Gaussians in place of one).  moments (nullable, and each parameter's pair nullable): the two Adam moments
+ *   of every parameter, zeroed on the rows that changed.  Six launches, nothing waits on the host or on another workgroup.
+ * scratch: gsplat_mcmc_scratch_bytes(n) device bytes, 256-byte aligned, shared by the regulariser and the refinement (they use
+ *   different parts).  The first 256 bytes (the regulariser's arrival counter) must be ZERO before the first call; every call leaves
+ *   them zero.  The layout query (tests and tools only, no stable contract) gives the byte offsets of the refinement's arrays:
+ *   w uint32[n], prefix uint64[n], src int32[n] (-1: drew nothing), count int32[n], total uint64, and the two constants of the scan.  */
+typedef struct gsplat_mcmc_moments {       /* [0] = exp_avg, [1] = exp_avg_sq */
+    float* pos[2];
+    float* f_dc[2];
+    float* f_rest[2];
+    float* opacity_raw[2];
+    float* scale_raw[2];
+    float* q_raw[2];
+} gsplat_mcmc_moments;
+typedef struct gsplat_mcmc_layout {
+    int64_t bytes, reg, w, prefix, src, count, total, block_sums;
+    int32_t scan_block;       /* rows per workgroup of the scan */
+    int32_t scan_chunk;       /* block sums one pass of the middle kernel holds */
+} gsplat_mcmc_layout;
+int64_t gsplat_mcmc_scratch_bytes(int64_t n);
+int gsplat_mcmc_scratch_layout(int64_t n, gsplat_mcmc_layout* out);
+int gsplat_mcmc_noise(int64_t n, float* pos, const float* opacity_raw, const float* scale_raw, const float* q_raw, float scale,
+                      uint64_t seed, uint32_t iteration, void* stream);
+int gsplat_mcmc_regularise(int64_t n, const float* opacity_raw, const float* scale_raw, float* grad_opacity_raw, float* grad_scale_raw,
+                           float lambda_opacity, float lambda_scale, const float* base, float* values, void* scratch, void* stream);
+int gsplat_mcmc_refine(float* pos, float* f_dc, float* f_rest, float* opacity_raw, float* scale_raw, float* q_raw,
+                       const gsplat_mcmc_moments* moments, int64_t n, float min_opacity, uint64_t seed, uint32_t iteration, void* scratch,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

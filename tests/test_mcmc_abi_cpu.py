@@ -1,0 +1,171 @@
+"""The C ABI of the MCMC density control and the trainer's side of it, without a GPU: the header declares the five
+entries, the Python mirror lists them, the library exports them and no helper, the ABI version is still 12, the layout query is a
+pure host function consistent with the size query, every bad argument comes back as GSPLAT_ERR_BAD_ARG with the entry's name before
+anything is launched -- and a Trainer of densify_rule="mcmc" constructs (its constructor launches nothing) and refuses bad fields."""
+import ctypes as C
+import dataclasses
+import importlib
+import os
+import re
+import subprocess
+
+import pytest
+import torch
+
+PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+abi = importlib.import_module(PKG + "._abi")
+ENTRIES = {"gsplat_mcmc_scratch_bytes": 1, "gsplat_mcmc_scratch_layout": 2, "gsplat_mcmc_noise": 9, "gsplat_mcmc_regularise": 11,
+           "gsplat_mcmc_refine": 13}
+
+
+def _refused(lib, status, name):
+    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, status)
+    assert name.encode() in lib.gsplat_last_error(), (name, lib.gsplat_last_error())
+
+
+def test_header_mirror_and_library_agree_and_the_version_stays_12():
+    header = open(os.path.join(ROOT, "include", "gsplat_mi355x.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    for name, n_args in ENTRIES.items():
+        m = re.search(rf"\b(?:int|int64_t)\s+{name}\s*\(([^)]*)\)\s*;", txt)
+        assert m, f"{name} is not declared in include/gsplat_mi355x.h"
+        assert len(m.group(1).split(",")) == n_args, name
+        assert name in abi.SIGNATURES and len(abi.SIGNATURES[name][1]) == n_args, name
+    assert "const gsplat_mcmc_moments* moments" in txt and "uint64_t seed, uint32_t iteration" in txt
+    assert re.search(r"^#define\s+GSPLAT_ABI_VERSION\s+12\s*$", header, flags=re.M) and abi.ABI_VERSION == 12
+    lib = abi.lib()
+    assert lib.gsplat_abi_version() == 12
+    out = subprocess.run(["nm", "-D", "--defined-only", abi.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TtWw"}
+    assert set(ENTRIES) <= exported
+    stray = [f for f in exported if ("mcmc" in f or "philox" in f or "relocat" in f) and f not in ENTRIES]
+    assert not stray, f"helpers of the MCMC entries exported: {stray}"
+    # the structs the entries take, field for field
+    assert C.sizeof(abi.McmcMoments) == 12 * 8 and C.sizeof(abi.McmcLayout) == 8 * 8 + 2 * 4
+    fields = re.search(r"typedef struct gsplat_mcmc_moments \{(.*?)\} gsplat_mcmc_moments;", txt, flags=re.S).group(1)
+    assert re.findall(r"float\*\s+(\w+)\[2\];", fields) == [k for k, _ in abi.McmcMoments._fields_]
+
+
+def test_layout_query_is_a_pure_host_function_consistent_with_the_size_query():
+    lib = abi.lib()
+    lay = abi.McmcLayout()
+    for n in (0, 1, 255, 256, 257, 65_537, 1_000_000, 2 ** 31 - 1):
+        assert lib.gsplat_mcmc_scratch_layout(n, C.byref(lay)) == abi.GSPLAT_OK
+        assert lay.bytes == lib.gsplat_mcmc_scratch_bytes(n)
+        assert lay.scan_block >= 64 and lay.scan_chunk >= 64
+        blocks = (n + lay.scan_block - 1) // lay.scan_block
+        need = dict(reg=256, total=8, w=n * 4, prefix=n * 8, src=n * 4, count=n * 4, block_sums=blocks * 8)
+        spans = sorted((getattr(lay, k), getattr(lay, k) + b, k) for k, b in need.items())
+        assert spans[0][0] == 0 and spans[-1][1] <= lay.bytes and all(o % 256 == 0 for o, _, _ in spans)
+        assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), spans
+        assert lay.reg == 0                                  # the counter that must start at zero does not move with n
+    assert lay.bytes < 2 ** 31 * 24
+    assert lib.gsplat_mcmc_scratch_bytes(-1) == -1 and lib.gsplat_mcmc_scratch_bytes(2 ** 31) == -1
+    _refused(lib, lib.gsplat_mcmc_scratch_layout(-1, C.byref(lay)), "gsplat_mcmc_scratch_layout")
+    _refused(lib, lib.gsplat_mcmc_scratch_layout(2 ** 31, C.byref(lay)), "gsplat_mcmc_scratch_layout")
+    _refused(lib, lib.gsplat_mcmc_scratch_layout(4, None), "gsplat_mcmc_scratch_layout")
+
+
+def test_entries_refuse_bad_arguments_on_the_host():
+    lib = abi.lib()
+    buf = (C.c_float * 1024)()
+    p = C.c_void_p((C.addressof(buf) + 255) // 256 * 256)                  # a 256-byte aligned host address: nothing is launched
+    odd = C.c_void_p(p.value + 4)
+    nan, inf = float("nan"), float("inf")
+
+    name, f = "gsplat_mcmc_noise", lib.gsplat_mcmc_noise
+    for status in (f(-1, p, p, p, p, 1.0, 0, 0, None), f(2 ** 31, p, p, p, p, 1.0, 0, 0, None), f(4, None, p, p, p, 1.0, 0, 0, None),
+                   f(4, p, None, p, p, 1.0, 0, 0, None), f(4, p, p, None, p, 1.0, 0, 0, None), f(4, p, p, p, None, 1.0, 0, 0, None),
+                   f(4, p, p, p, odd, 1.0, 0, 0, None), f(4, p, p, p, p, nan, 0, 0, None), f(4, p, p, p, p, inf, 0, 0, None)):
+        _refused(lib, status, name)
+    assert f(0, None, None, None, None, 1.0, 0, 0, None) == abi.GSPLAT_OK
+
+    name, f = "gsplat_mcmc_regularise", lib.gsplat_mcmc_regularise
+    for status in (f(-1, p, p, p, p, 0.01, 0.01, None, p, p, None), f(2 ** 31, p, p, p, p, 0.01, 0.01, None, p, p, None),
+                   f(4, None, p, p, p, 0.01, 0.01, None, p, p, None), f(4, p, None, p, p, 0.01, 0.01, None, p, p, None),
+                   f(4, p, p, p, p, 0.01, 0.01, None, None, p, None), f(4, p, p, p, p, 0.01, 0.01, None, p, None, None),
+                   f(4, p, p, p, p, 0.01, 0.01, None, p, odd, None), f(4, p, p, p, p, -0.01, 0.01, None, p, p, None),
+                   f(4, p, p, p, p, 0.01, nan, None, p, p, None), f(4, p, p, p, p, inf, 0.01, None, p, p, None)):
+        _refused(lib, status, name)
+    assert f(0, None, None, None, None, 0.01, 0.01, None, None, None, None) == abi.GSPLAT_OK
+
+    name, f = "gsplat_mcmc_refine", lib.gsplat_mcmc_refine
+    good = dict(pos=p, f_dc=p, f_rest=p, opacity_raw=p, scale_raw=p, q_raw=p, moments=None, n=4, min_opacity=0.005, seed=0, iteration=0, scratch=p)
+
+    def call(**kw):
+        a = {**good, **kw}
+        return f(a["pos"], a["f_dc"], a["f_rest"], a["opacity_raw"], a["scale_raw"], a["q_raw"], a["moments"], a["n"], a["min_opacity"],
+                 a["seed"], a["iteration"], a["scratch"], None)
+
+    half = abi.McmcMoments()
+    half.scale_raw[0] = p.value                                            # one moment of a pair without the other
+    for bad in ([dict([(k, None)]) for k in ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw", "scratch")]
+                + [dict(n=-1), dict(n=2 ** 31), dict(min_opacity=-0.1), dict(min_opacity=1.0), dict(min_opacity=nan), dict(scratch=odd),
+                   dict(moments=C.byref(half))]):
+        _refused(lib, call(**bad), name)
+    assert call(n=0, pos=None, scratch=None) == abi.GSPLAT_OK
+    del buf
+
+
+def test_python_side_fails_loudly_without_a_gpu(gs):
+    z = torch.zeros
+    t = dict(pos=z(4, 3), f_dc=z(4, 3), f_rest=z(4, 45), opacity_raw=z(4), scale_raw=z(4, 3), q_raw=z(4, 4))
+    for call in (lambda: gs.mcmc.add_noise(t, 1.0, 0, 0), lambda: gs.mcmc.regularise(t, 0.01, 0.01), lambda: gs.mcmc.relocate(t, None, 0.005, 0, 0)):
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            call()
+    for seed, it in ((-1, 0), (2 ** 64, 0), (0, -1), (0, 2 ** 32), (0.5, 0), (0, 1.0)):
+        with pytest.raises(ValueError):
+            gs.mcmc.add_noise(t, 1.0, seed, it)
+
+
+def test_grow_rows_moves_the_state_and_keeps_the_step():
+    optim = importlib.import_module(PKG + ".optim")
+    a, b = torch.nn.Parameter(torch.ones(3, 2)), torch.nn.Parameter(torch.ones(3))
+    opt = optim.GaussianAdam([{'params': [a], 'lr': 0.1, 'name': 'a'}, {'params': [b], 'lr': 0.2, 'name': 'b'}])
+    st = opt._state(a)
+    st['step'], st['exp_avg'], st['exp_avg_sq'] = 7, torch.full((3, 2), 0.5), torch.full((3, 2), 0.25)
+    a2 = torch.nn.Parameter(torch.cat([a.detach(), torch.zeros(2, 2)]))
+    opt.grow_rows(a, a2)
+    assert opt.param_groups[0]['params'][0] is a2 and opt.param_groups[0]['lr'] == 0.1 and a not in opt.state
+    st2 = opt.state[a2]
+    assert st2['step'] == 7 and st2['exp_avg'].shape == (5, 2)
+    assert torch.equal(st2['exp_avg'][:3], torch.full((3, 2), 0.5)) and not st2['exp_avg'][3:].any()
+    assert torch.equal(st2['exp_avg_sq'][:3], torch.full((3, 2), 0.25)) and not st2['exp_avg_sq'][3:].any()
+    b2 = torch.nn.Parameter(torch.ones(4))                  # a parameter without state yet: only the group changes
+    opt.grow_rows(b, b2)
+    assert opt.param_groups[1]['params'][0] is b2 and b2 not in opt.state
+    with pytest.raises(ValueError):
+        opt.grow_rows(a, a2)                                # no longer this optimiser's
+    with pytest.raises(ValueError):
+        opt.grow_rows(a2, torch.nn.Parameter(torch.ones(4, 2)))     # rows cannot leave
+
+
+def _model():
+    model_mod = importlib.import_module(PKG + ".model")
+    z = torch.zeros
+    return model_mod.GaussianModel(dict(pos=z(4, 3), f_dc=z(4, 3), f_rest=z(4, 45), opacity_raw=z(4), scale_raw=z(4, 3), q_raw=z(4, 4)), device="cpu")
+
+
+def test_trainer_of_the_mcmc_rule_constructs_and_keeps_the_defaults():
+    training = importlib.import_module(PKG + ".training")
+    c = training.TrainConfig()
+    assert (c.densify_rule, c.cap_max, c.mcmc_start_iter, c.mcmc_min_opacity, c.mcmc_noise_lr, c.mcmc_opacity_reg, c.mcmc_scale_reg,
+            c.mcmc_growth, c.mcmc_seed) == ("reference", 1_000_000, 500, 0.005, 5e5, 0.01, 0.01, 1.05, 0)
+    tr = training.Trainer(_model(), training.TrainConfig(densify_rule="mcmc"))
+    assert tr.cfg.densify_rule == "mcmc" and len(tr.optimizer.param_groups) == 6
+    with pytest.raises(ValueError, match="densify_rule"):
+        training.Trainer(_model(), training.TrainConfig(densify_rule="paper"))
+
+
+@pytest.mark.parametrize("field,value", [("cap_max", 0), ("cap_max", 1.5), ("cap_max", True), ("cap_max", 2 ** 31), ("mcmc_start_iter", -1),
+                                         ("mcmc_start_iter", 1.0), ("mcmc_min_opacity", 0.0), ("mcmc_min_opacity", 1.0), ("mcmc_min_opacity", 1),
+                                         ("mcmc_min_opacity", float("nan")), ("mcmc_noise_lr", -1.0), ("mcmc_noise_lr", float("inf")),
+                                         ("mcmc_opacity_reg", -0.01), ("mcmc_opacity_reg", float("nan")), ("mcmc_scale_reg", -0.01),
+                                         ("mcmc_scale_reg", "0.01"), ("mcmc_growth", 0.99), ("mcmc_growth", float("inf")), ("mcmc_growth", None),
+                                         ("mcmc_seed", -1), ("mcmc_seed", 2 ** 64), ("mcmc_seed", 0.5)])
+def test_trainer_refuses_bad_mcmc_fields(field, value):
+    training = importlib.import_module(PKG + ".training")
+    cfg = dataclasses.replace(training.TrainConfig(densify_rule="mcmc"), **{field: value})
+    with pytest.raises(ValueError, match=field):
+        training.Trainer(_model(), cfg)
