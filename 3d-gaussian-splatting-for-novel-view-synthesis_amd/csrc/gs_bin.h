@@ -62,7 +62,8 @@ __device__ __forceinline__ void for_each_big_row(bool big, u2 rect, f4 uvexy, f4
 // ---- K3: coarse bins (F11) -----------------------------------------------------------------------------
 // bin_count_kernel: a block of 2048 Gaussians histograms its (list, Gaussian) pairs over the coarse bins in LDS and takes
 // its share of every bin it touches with ONE returning global atomic per bin (device-scope atomics run at ~20 G/s and
-// serialise per address: one per pair was 10x slower than the radix sort this replaces; one per block and bin is noise).
+// serialise per address: one per pair was 10x slower than the radix sort this replaces; one per block and bin is noise --
+// once the blocks are spread over BIN_TOTAL_SHARDS words per bin).
 // Needs no pair buffer, so it is queued with the colour pass behind the counters and runs during the host round trip.
 struct BlockPairs {                    // the 8 Gaussians of one thread of a binning workgroup
     static constexpr int K = BIN_GAUSS / 256;
@@ -186,7 +187,7 @@ __device__ __forceinline__ void bin_count_big(int64_t n, const u2* __restrict__ 
     if (!any) return;                                      // (uniform; for_flagged_ranges ends with a barrier)
     for (int b = tid; b < nb; b += 256) {
         const uint32_t c = hist[b];
-        if (c) atomicAdd(&bin_total[nb + b], c);           // (no offset is drawn here: bin_scatter_kernel's big blocks draw theirs)
+        if (c) atomicAdd(&bin_total[BIN_TOTAL_SHARDS * nb + b], c);      // (no offset is drawn here: bin_scatter_kernel's big blocks draw theirs)
     }
 }
 
@@ -264,7 +265,8 @@ __global__ __launch_bounds__(256) void bin_count_kernel(int64_t n, const u2* __r
     __syncthreads();
     for (int b = tid; b < nb; b += 256) {
         const uint32_t c = hist[b];
-        if (c) block_off[(int64_t)blockIdx.x * nb + b] = atomicAdd(&bin_total[b], c);
+        // (the offset inside the block's SHARD of the bin: one word per bin took all 489 blocks of config 3 at about the same time)
+        if (c) block_off[(int64_t)blockIdx.x * nb + b] = atomicAdd(&bin_total[(blockIdx.x % BIN_TOTAL_SHARDS) * nb + b], c);
     }
 }
 
@@ -316,26 +318,60 @@ __device__ __forceinline__ void scatter_big_rows(const BigLane& bl, int lists_x,
     }
 }
 
-// A bin's region of the bin-ordered array: [ pairs of the small Gaussians | pairs of the large ones ]; the small blocks place theirs
-// with the offsets bin_count_kernel drew (block_off), the big blocks (same split of the grid as there) count their range again,
-// draw ONE offset per touched bin from the bin's cursor (bin_total + 2 nb) and scatter.
+// A bin's region of the bin-ordered array: [ small Gaussians, shard 0 | shard 1 | ... | pairs of the large ones ]; the small blocks
+// place theirs with the offsets bin_count_kernel drew inside their shard (block_off), the big blocks (same split of the grid as there)
+// count their range again, draw ONE offset per touched bin from the bin's cursor (the last row of bin_total) and scatter.
 //
 // Exclusive prefix of the bin totals (small + large) for both kinds of block: thread t owns a contiguous run of ceil(nb / 256) bins and
-// calls own(b, start of bin b, total of bin b, k) for each of them (k = index inside the run; the first four totals are in bt[]).
-// The first four of a thread's totals are loaded up front (all of them up to 1024 bins = 4 M pixels): one round trip, not three.
-struct BinPrefix { int per, first; uint32_t bt[4], small[4], run; };      // bt = small + large pairs of the bin, small = the small Gaussians' part
-__device__ __forceinline__ BinPrefix bin_prefix_load(const uint32_t* __restrict__ bin_total, int nb) {
+// calls own(b, start of bin b, total of bin b, k) for each of them (k = index inside the run; the first BIN_PRE totals are in bt[]).
+// The totals of a thread's first bin are loaded up front (BIN_PRE; all there are up to 256 bins), every shard of them: one round trip.
+// `shard`: the caller's own (a small block); its pairs lie behind those of the shards before it.
+// How many of a thread's bins have their totals loaded up front, all shards of each in flight together.  ONE: with four (every bin of a
+// thread up to 1024 bins) the scatter kernel held 4 x 9 totals and their addresses, 161 VGPRs instead of 79 -- 3 waves per SIMD, and
+// the large Gaussians' blocks, which live on occupancy, paid for it (config 6: bin stage 244 -> 270 us).  With one it needs 96 (5 waves);
+// an image of more than 256 bins pays one round trip per further bin of the thread.
+constexpr int BIN_PRE = 1;
+struct BinTotals { uint32_t before, small, all; };     // of one bin: the shards before `shard` | all shards | shards + the large Gaussians' pairs
+__device__ __forceinline__ BinTotals bin_totals_of(const uint32_t* __restrict__ bin_total, int nb, int b, int shard) {
+    uint32_t t[BIN_TOTAL_SHARDS + 1];
+#pragma unroll
+    for (int s = 0; s <= BIN_TOTAL_SHARDS; ++s) t[s] = bin_total[s * nb + b];          // (all in flight together)
+    BinTotals r{0u, 0u, 0u};
+#pragma unroll
+    for (int s = 0; s < BIN_TOTAL_SHARDS; ++s) {
+        r.before += s < shard ? t[s] : 0u;
+        r.small += t[s];
+    }
+    r.all = r.small + t[BIN_TOTAL_SHARDS];
+    return r;
+}
+struct BinPrefix { int per, first; uint32_t bt[BIN_PRE], small[BIN_PRE], before[BIN_PRE], run; };      // bt = small + large pairs of the bin, small = the small
+                                                                                     // Gaussians' part, before = its shards before the caller's
+__device__ __forceinline__ BinPrefix bin_prefix_load(const uint32_t* __restrict__ bin_total, int nb, int shard) {
     BinPrefix p;
     p.per = (nb + 255) / 256;
     p.first = (int)threadIdx.x * p.per;
+    uint32_t t[BIN_PRE][BIN_TOTAL_SHARDS + 1];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < BIN_PRE; ++k) {
         const bool in = k < p.per && p.first + k < nb;
-        p.small[k] = in ? bin_total[p.first + k] : 0u;
-        p.bt[k] = p.small[k] + (in ? bin_total[nb + p.first + k] : 0u);
+#pragma unroll
+        for (int s = 0; s <= BIN_TOTAL_SHARDS; ++s) t[k][s] = in ? bin_total[s * nb + p.first + k] : 0u;
     }
-    p.run = p.bt[0] + p.bt[1] + p.bt[2] + p.bt[3];
-    for (int k = 4; k < p.per; ++k) p.run += p.first + k < nb ? bin_total[p.first + k] + bin_total[nb + p.first + k] : 0u;
+#pragma unroll
+    for (int k = 0; k < BIN_PRE; ++k) {
+        p.before[k] = p.small[k] = 0u;
+#pragma unroll
+        for (int s = 0; s < BIN_TOTAL_SHARDS; ++s) {
+            p.before[k] += s < shard ? t[k][s] : 0u;
+            p.small[k] += t[k][s];
+        }
+        p.bt[k] = p.small[k] + t[k][BIN_TOTAL_SHARDS];
+    }
+    p.run = 0u;
+#pragma unroll
+    for (int k = 0; k < BIN_PRE; ++k) p.run += p.bt[k];
+    for (int k = BIN_PRE; k < p.per; ++k) p.run += p.first + k < nb ? bin_totals_of(bin_total, nb, p.first + k, 0).all : 0u;
     return p;
 }
 // start of the thread's first bin (one workgroup barrier inside)
@@ -361,7 +397,7 @@ __device__ __forceinline__ void bin_scatter_big(int64_t n, const u2* __restrict_
     for_flagged_ranges(big_flag, blockIdx.x - small_blocks, gridDim.x - small_blocks, ranges, fl, [&](int64_t range) {
         BigLane bl;
         if (!load_big_lane(range * 64 + lane, n, rect, tiles, rec, depth, bl, big_flag)) return;
-        const BinPrefix bpf = bin_prefix_load(bin_total, nb);
+        const BinPrefix bpf = bin_prefix_load(bin_total, nb, 0);
         for (int b = tid; b < nb; b += 256) cur[b] = 0u;
         __syncthreads();
         for_each_big_row(bl.big, bl.rect, bl.uvexy, bl.k4, 0ull, lists_x, lane, [&](uint32_t l0, uint32_t cnt, uint64_t) {
@@ -369,26 +405,27 @@ __device__ __forceinline__ void bin_scatter_big(int64_t n, const u2* __restrict_
         }, mine);
         uint32_t st = bin_prefix_scan(bpf, wsum);              // (its barrier also closes the counting)
         // start of the bin + its small part + what this block draws from the large part's cursor (ONE returning atomic per touched
-        // bin and block; the atomics of a thread's first four bins are in flight together: a range pays one round trip for them,
+        // bin and block; the atomics of a thread's first BIN_PRE bins are in flight together: a range pays one round trip for them,
         // not one per bin)
-        uint32_t mine4[4], got4[4];
+        uint32_t mine4[BIN_PRE], got4[BIN_PRE];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) mine4[k] = (k < bpf.per && bpf.first + k < nb) ? cur[bpf.first + k] : 0u;
+        for (int k = 0; k < BIN_PRE; ++k) mine4[k] = (k < bpf.per && bpf.first + k < nb) ? cur[bpf.first + k] : 0u;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) got4[k] = mine4[k] ? atomicAdd(&bin_total[2 * nb + bpf.first + k], mine4[k]) : 0u;
+        for (int k = 0; k < BIN_PRE; ++k) got4[k] = mine4[k] ? atomicAdd(&bin_total[(BIN_TOTAL_SHARDS + 1) * nb + bpf.first + k], mine4[k]) : 0u;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < BIN_PRE; ++k) {
             if (k < bpf.per && bpf.first + k < nb) {
                 if (mine4[k]) cur[bpf.first + k] = st + bpf.small[k] + got4[k];
                 st += bpf.bt[k];
             }
         }
-        for (int k = 4; k < bpf.per; ++k) {                    // (more than 1024 bins: images beyond 4 M pixels)
+        for (int k = BIN_PRE; k < bpf.per; ++k) {                    // (more than 1024 bins: images beyond 4 M pixels)
             const int b = bpf.first + k;
             if (b < nb) {
                 const uint32_t mine = cur[b];
-                if (mine) cur[b] = st + bin_total[b] + atomicAdd(&bin_total[2 * nb + b], mine);
-                st += bin_total[b] + bin_total[nb + b];
+                const BinTotals t = bin_totals_of(bin_total, nb, b, 0);
+                if (mine) cur[b] = st + t.small + atomicAdd(&bin_total[(BIN_TOTAL_SHARDS + 1) * nb + b], mine);
+                st += t.all;
             }
         }
         __syncthreads();
@@ -413,16 +450,19 @@ __global__ __launch_bounds__(256) void bin_scatter_kernel(int64_t n, const u2* _
         return;
     }
     BlockPairs bp = load_block_pairs(n, rect, tiles, mask, depth, (int64_t)blockIdx.x * batches);
-    const BinPrefix bpf = bin_prefix_load(bin_total, nb);
-    uint32_t bo[4];
+    const int shard = (int)(blockIdx.x % BIN_TOTAL_SHARDS);          // (the shard bin_count_kernel drew this block's offsets from)
+    const BinPrefix bpf = bin_prefix_load(bin_total, nb, shard);
+    uint32_t bo[BIN_PRE];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) bo[k] = (k < bpf.per && bpf.first + k < nb) ? block_off[(int64_t)blockIdx.x * nb + bpf.first + k] : 0u;
+    for (int k = 0; k < BIN_PRE; ++k) bo[k] = (k < bpf.per && bpf.first + k < nb) ? block_off[(int64_t)blockIdx.x * nb + bpf.first + k] : 0u;
     uint32_t st = bin_prefix_scan(bpf, wsum);
     for (int k = 0; k < bpf.per; ++k) {
         const int b = bpf.first + k;
         if (b < nb) {
-            const uint32_t c = k < 4 ? bpf.bt[k & 3] : bin_total[b] + bin_total[nb + b];
-            cur[b] = st + (k < 4 ? bo[k & 3] : block_off[(int64_t)blockIdx.x * nb + b]);   // garbage for bins this block never touches: unused
+            BinTotals t{bpf.before[k % BIN_PRE], 0u, bpf.bt[k % BIN_PRE]};
+            if (k >= BIN_PRE) t = bin_totals_of(bin_total, nb, b, shard);
+            const uint32_t c = t.all;
+            cur[b] = st + t.before + (k < BIN_PRE ? bo[k % BIN_PRE] : block_off[(int64_t)blockIdx.x * nb + b]);   // garbage for bins this block never touches: unused
             if (blockIdx.x == 0) {
                 bin_start[b] = st;
                 if (b == nb - 1) bin_start[nb] = st + c;

@@ -42,6 +42,9 @@ struct CounterBlock {
 // (bin_count_kernel / bin_scatter_kernel, blocks of 2048 Gaussians with an LDS histogram, one global atomic per block and
 // bin), then every bin is split into its 64 lists (split_count_kernel / split_scatter_kernel), then every list is sorted by depth.
 constexpr int BIN_SHIFT = 6;                 // 64 lists per coarse bin
+constexpr int BIN_TOTAL_SHARDS = 8;        // block blk of bin_count_kernel draws its offsets from shard blk % 8 of the bin totals: 489 blocks
+                                             // on ONE word per bin arrive together and a word takes ~88 returning atomics per microsecond
+constexpr int BIN_TOTAL_ROWS = BIN_TOTAL_SHARDS + 2;      // rows of bin_total[]: the shards | the large Gaussians' totals | their cursor
 constexpr int BIN_GAUSS = 2048;              // Gaussians per block of bin_count_kernel / bin_scatter_kernel
 constexpr int MAX_BINS = 8192;               // LDS histogram of the two kernels (32 KB): images up to 8192 x 8192 / 128 lists
 constexpr int SPLIT_CHUNK = 4096;            // pairs per block of split_count_kernel / split_scatter_kernel
@@ -58,8 +61,9 @@ struct ProjectState {
     float* depth;
     uint32_t* tiles;         // per Gaussian: number of lists (0 = contributes nowhere)
     uint32_t* mask;          // per Gaussian: which lists of the rectangle (ellipse / list test; all ones above 32 lists)
-    uint32_t* bin_total;     // [3 x bins] pairs per coarse bin of the small Gaussians | of the large ones (rectangles of more than 32
-                             //            lists: bin_total + bins) | the large ones' scatter cursor (bin_total + 2 bins); zero per frame
+    uint32_t* bin_total;     // [BIN_TOTAL_ROWS x bins] pairs per coarse bin of the small Gaussians, one row per shard | of the large ones
+                             //            (rectangles of more than 32 lists: row BIN_TOTAL_SHARDS) | the large ones' scatter cursor (the row
+                             //            behind it); zero per frame
     uint32_t* bin_start;     // [bins + 1] exclusive prefix of bin_total
     uint32_t* block_off;     // [blocks x bins] where a block's pairs start inside a bin
     uint32_t* list_count;    // [bins x 64] pairs per list (split_count_kernel)
@@ -91,7 +95,7 @@ ProjectState carve_project(void* base, int64_t n, int64_t nl) {
     s.depth = c.take<float>(n * 4);
     s.tiles = c.take<uint32_t>(n * 4);
     s.mask = c.take<uint32_t>(n * 4);
-    s.bin_total = c.take<uint32_t>(3 * nb * 4);
+    s.bin_total = c.take<uint32_t>(BIN_TOTAL_ROWS * nb * 4);
     s.bin_start = c.take<uint32_t>((nb + 1) * 4);
     s.block_off = c.take<uint32_t>(n_bin_blocks(n) * nb * 4);
     s.list_count = c.take<uint32_t>((nb << BIN_SHIFT) * 4);

@@ -121,7 +121,7 @@ __global__ __launch_bounds__(64) void project_kernel(gsplat_gaussians g, const f
         build_camera(m, cam);
         if (blockIdx.x == 0 && lane == 0) *cam_out = cam;
     }
-    for (int b = blockIdx.x * 64 + lane; b < 3 * nb; b += gridDim.x * 64) bin_total[b] = 0u;     // (+ the large Gaussians' totals and cursor)
+    for (int b = blockIdx.x * 64 + lane; b < BIN_TOTAL_ROWS * nb; b += gridDim.x * 64) bin_total[b] = 0u;     // (every shard + the large Gaussians' totals and cursor)
     if (!DIRECT) __syncthreads();
     Proj o;
     o.vis = VIS_CULLED;

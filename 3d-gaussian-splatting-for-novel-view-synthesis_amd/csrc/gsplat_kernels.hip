@@ -434,7 +434,7 @@ int gsplat_project(const gsplat_gaussians* g, const float* c2w, const gsplat_vie
         if (counts_host && !mapped && !late) HIP_TRY(hipMemcpyAsync(counts_host, ps.counts, sizeof(gsplat_counts), hipMemcpyDeviceToHost, st));
     } else {                        // no kernel runs: the counters are zero by definition
         HIP_TRY(hipMemsetAsync(ps.counts, 0, sizeof(DevCounts), st));
-        HIP_TRY(hipMemsetAsync(ps.bin_total, 0, 3 * nb * sizeof(uint32_t), st));
+        HIP_TRY(hipMemsetAsync(ps.bin_total, 0, BIN_TOTAL_ROWS * nb * sizeof(uint32_t), st));
         if (counts_host) HIP_TRY(hipMemsetAsync(counts_host, 0, sizeof(gsplat_counts), st));
     }
     if (counts_event && !late) HIP_TRY(hipEventRecord((hipEvent_t)counts_event, st));
