@@ -103,7 +103,7 @@ GS_HD void quat_to_rot(const float q[4], float R[9]) {
 }
 
 GS_HD void cov_from_params(const float scale_raw[3], const float q_raw[4], float S[6], CovMid& m) {
-    for (int k = 0; k < 3; ++k) { m.r[k] = scale_raw[k]; m.e[k] = expf(scale_raw[k]); m.s[k] = fmaxf(m.e[k], 1e-6f); }
+    for (int k = 0; k < 3; ++k) { m.r[k] = scale_raw[k]; m.e[k] = expf(scale_raw[k]); m.s[k] = m.e[k] < 1e-6f ? 1e-6f : m.e[k]; }   // (not fmaxf: a NaN scale stays a NaN, as under the reference's clamp_min, and is culled with its covariance)
     m.qn = sqrtf(q_raw[0] * q_raw[0] + q_raw[1] * q_raw[1] + q_raw[2] * q_raw[2] + q_raw[3] * q_raw[3]);
     const float inv = 1.0f / (m.qn + 1e-9f);
     for (int k = 0; k < 4; ++k) m.q[k] = q_raw[k] * inv;
@@ -491,6 +491,10 @@ GS_HD void project_gaussian(const float p[3], const float S[6], float o_raw, con
     m.a = r0x * m.j00 + r0z * m.j02;
     m.b = r0y * m.j11 + r0z * m.j12;
     m.d = r1y * m.j11 + r1z * m.j12;
+    // The reference drops a Gaussian whose recomposed 2-D covariance is not finite (render.py:187-201): eigh hands a NaN or Inf entry
+    // on to every entry.  Here it must be caught BEFORE the clamp: fminf / fmaxf return their other argument for a NaN, so NaN
+    // eigenvalues would come out of clampf_ as 1e-6 and the Gaussian as a finite 1e-6 px^2 dot, counted and binned.
+    if (!(isfinite(m.a) && isfinite(m.b) && isfinite(m.d))) return;
     // F8 eigenvalues of the symmetric 2x2, clamp to [1e-6, 1e4], recomposition
     [[maybe_unused]] const float ls = FILTER ? vk.lowpass : 0.f;             // (read by the FILTER branches only)
     float mid = 0.5f * (m.a + m.d);

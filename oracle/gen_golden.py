@@ -187,6 +187,35 @@ def gen_unfused():
     save(name, **arrs)
 
 
+def gen_nonfinite():
+    """G13 (non-finite): NaN / Inf in single parameters of ten Gaussians.  Forward only: inputs, the float64 and float32 image, the
+    survivors and their tile rectangles.  The reference drops such a Gaussian (render.py:187-201, or earlier): the image is that of
+    the scene without those rows, which is checked here (to one rounding: the batched operations of another batch size add in another
+    order; one row at a time it is bit for bit)."""
+    name = "g13_nonfinite"
+    print(name)
+    s = scenes.case_g13_nonfinite()
+    rows = 10 + np.arange(len(scenes.NONFINITE))
+    img64, _, _, _, snap = run_fused(s, torch.float64, capture=True)
+    img32, _, _, _, _ = run_fused(s, torch.float32)
+    im = intermediates(snap)
+    kept = np.isin(rows, im["im_ids"])
+    print("  poisoned rows kept by the reference:", [scenes.NONFINITE[k] for k in np.nonzero(kept)[0]])
+    drop = np.ones(len(s["pos"]), bool)
+    drop[rows[~kept]] = False
+    for dtype, img in ((torch.float64, img64), (torch.float32, img32)):
+        clean = dict(s, **{k: s[k][drop] for k in PARAMS})
+        diff = np.abs(run_fused(clean, dtype)[0] - img).max()
+        print(f"  {dtype}: against the scene without the dropped Gaussians: max |difference| {diff:.3g}")
+        assert diff <= (1e-13 if dtype == torch.float64 else 1e-6), "the image is not the image without the dropped Gaussians"
+    assert np.isfinite(img64).all() and np.isfinite(img32).all()
+    arrs = scene_arrays(s)
+    arrs.update(image=img64, image_f32=img32.astype(np.float32), im_ids=im["im_ids"], im_tile_rect=im["im_tile_rect"],
+                im_pair_gauss=im["im_pair_gauss"], poisoned=rows.astype(np.int32), kept=kept)
+    print(f"  image mean {img64.mean():.4f}  V={len(im['im_ids'])} P={len(im['im_pair_gauss'])}")
+    save(name, **arrs)
+
+
 def gen_pieces():
     """Stand-alone goldens for the small exported functions (forward + backward), float64."""
     print("pieces")
@@ -530,6 +559,8 @@ if __name__ == "__main__":
             gen_case(n)
     if not want or "g11_unfused" in want:
         gen_unfused()
+    if not want or "g13_nonfinite" in want:
+        gen_nonfinite()
     if not want or "pieces" in want:
         gen_pieces()
     if not want or "g13_config1_full" in want:

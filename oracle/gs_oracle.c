@@ -143,6 +143,10 @@ int ora_render(int64_t n, const double* pos, const double* f_dc, const double* f
             for (int a = 0; a < 2; ++a) for (int b = 0; b < 2; ++b) { double acc = 0; for (int k = 0; k < 3; ++k) acc += JC[a][k] * J[b][k]; S2[a][b] = acc; }
             r.a = S2[0][0]; r.d = S2[1][1]; r.b = 0.5 * (S2[0][1] + S2[1][0]);
         }
+        /* a non-finite entry reaches every entry of the reference's recomposition (eigh) and is dropped at render.py:187-201.  Said
+           here outright (tests/golden/g13_nonfinite.npz): the check behind the clamp holds only because clampd is written with
+           comparisons, which pass a NaN on -- with fmin / fmax NaN eigenvalues would come out as 1e-6 */
+        if (!(isfinite(r.a) && isfinite(r.b) && isfinite(r.d))) continue;
         /* eigen decomposition of the symmetric 2x2 (explicit angle), clamp, recomposition (render.py:177-179) */
         {
             const double th = 0.5 * atan2(2 * r.b, r.a - r.d);

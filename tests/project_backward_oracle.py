@@ -54,12 +54,15 @@ def _subpixel(z, f, jitter):
     return np.log(0.023 * z / f) + 0.5 * np.asarray(jitter)
 
 
-def synthetic(n):
+def synthetic(n, more_culls=False):
     """n Gaussians on a view of 32 x 48 pixels, with the edge rows of tests/test_gpu_pieces.py _sigma_inputs mixed in (every 3rd row
     below 64 rows, every 5th above): clamped scales, |q_raw| around 1e-6, 1e-4 and 1e-2, q_raw = 0, near-isotropic, sub-pixel (and
     every 11th ordinary row as well: _subpixel), huge (an eigenvalue beyond 1e4), saturated opacity -- and culled Gaussians (behind the camera, opacity below the cut, off screen):
     every 7th row of an ordinary block; n = 129: block 1 is invisible as a whole; n = 200: block 0 has lane 0 alone visible and
-    block 1 lane 63 alone.  The last block of every size but 64 is partial."""
+    block 1 lane 63 alone.  The last block of every size but 64 is partial.
+    more_culls (the forward tests): the culled rows take ten reasons in turn instead of three -- also inside the near plane, beyond the
+    far plane, beyond each of the four guard-band sides, and (s["offscreen"]) a SURVIVOR: inside the guard band with its AABB outside
+    the image, counted in n_survivors and not in n_visible.  The rows that are culled and every other row stay what they are."""
     H, W, f = 32, 48, 40.0
     rng = np.random.default_rng(100 + n)
     z = rng.uniform(3, 6, n)
@@ -116,18 +119,36 @@ def synthetic(n):
         sr[0], sr[127], qr[0], qr[127], op[0], op[127] = [-2.0, -2.3, -1.8], [-2.2, -1.9, -2.4], unit[0], unit[127], 0.5, -0.5
     x = (uv[:, 0] - W / 2) / f * z
     y = (uv[:, 1] - H / 2) / f * z
+    offscreen = np.zeros(n, bool)
     for k, i in enumerate(np.nonzero(culled)[0]):
-        if k % 3 == 0:
+        r = k % 10 if more_culls else k % 3
+        if r == 0:
             z[i] = -z[i]                                                       # behind the camera
-        elif k % 3 == 1:
+        elif r == 1:
             op[i] = -10.0                                                      # below the opacity cut
-        else:
+        elif r == 2:
             x[i] = (W + 200.0 - W / 2) / f * z[i]                              # beyond the guard band
+        elif r == 3:
+            x[i] = (W + 20.0 - W / 2) / f * z[i]                               # inside the guard band, its AABB (radius 1 px) off the image
+            sr[i] = np.log(0.2 * z[i] / f)
+            offscreen[i] = True
+        elif r in (4, 5):
+            z[i] = 0.005 if r == 4 else 150.0                                  # inside the near plane (0.01) / beyond the far plane (100)
+            x[i], y[i] = (uv[i, 0] - W / 2) / f * z[i], (uv[i, 1] - H / 2) / f * z[i]
+        elif r == 6:
+            x[i] = (-40.0 - W / 2) / f * z[i]                                  # beyond the guard band (32 px) on the left,
+        elif r == 7:
+            y[i] = (-40.0 - H / 2) / f * z[i]                                  # at the top,
+        elif r == 8:
+            y[i] = (H + 40.0 - H / 2) / f * z[i]                               # at the bottom,
+        else:
+            x[i] = (W + 40.0 - W / 2) / f * z[i]                               # and just beyond it on the right
     c2w = _c2w()
     pos = np.stack([x, y, z], 1) @ c2w[:3, :3].T + c2w[:3, 3]
     d = dict(pos=pos, scale_raw=sr, q_raw=qr, opacity_raw=op, f_dc=0.5 * rng.normal(0, 1, (n, 3)), f_rest=0.2 * rng.normal(0, 1, (n, 45)))
     s = list_scenes._pack(d, H, W, f, f * 1.1, W / 2.0 + 0.5, H / 2.0 - 0.25, c2w=c2w)
     s["culled"] = culled
+    s["offscreen"] = offscreen
     return s
 
 

@@ -30,6 +30,15 @@ def test_empty(name):
     assert st == 10 and np.abs(img).max() == 0 and all(np.abs(v).max() == 0 for v in g.values())
 
 
+def test_non_finite_parameters_are_dropped():
+    """g13_nonfinite (forward only): the Gaussians the reference drops for a NaN / Inf parameter are dropped here (its clamp is written with
+    comparisons, which pass a NaN on to the finite check; the non-finite covariance is also refused outright in front of it)."""
+    d = util.load("g13_nonfinite")
+    st, img, _, (V, P) = _run(d, grad=False)
+    assert st == 0 and V == len(d["im_ids"]) and P == len(d["im_pair_gauss"])
+    assert np.isfinite(img).all() and np.abs(img - d["image"]).max() < 1e-13
+
+
 def test_offscreen_status():
     d = util.load("g10_offscreen")
     assert _run(d, grad=False)[0] == 11
