@@ -29,6 +29,7 @@ GSPLAT_BACKWARD_PHASE_PROJECT = 4
 GSPLAT_BACKWARD_GRAD2D_DIRTY = 8
 GSPLAT_BACKWARD_ACCUMULATE = 16
 GSPLAT_BACKWARD_DEPTH = 64
+GSPLAT_BACKWARD_ABSGRAD = 128
 
 
 def sh_bands_dropped(degree):
@@ -157,12 +158,18 @@ SIGNATURES = {
     "gsplat_rasterize_backward_aux_scratch_bytes": (_I64, [_I64, _I64]),
     "gsplat_rasterize_backward_aux": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _VP, C.c_int32, _VP, _I64, _VP]),
     "gsplat_rasterize_backward": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP, _VP, C.c_int32, _VP, _I64, _VP]),
+    "gsplat_rasterize_backward_abs_scratch_bytes": (_I64, [_I64, _I64]),
+    "gsplat_rasterize_backward_aux_abs_scratch_bytes": (_I64, [_I64, _I64]),
+    "gsplat_rasterize_backward_aux_abs": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _VP, C.c_int32, _VP, _I64, _VP]),
+    "gsplat_rasterize_backward_abs": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP, _VP, C.c_int32, _VP, _I64, _VP]),
     "gsplat_project_backward": (_INT, [_PG, _VP, _PV, _VP, _VP, _PGG, C.c_int32, _VP]),
     "gsplat_pose_scratch_bytes": (_I64, [_I64]),
     "gsplat_project_backward_pose": (_INT, [_PG, _VP, _PV, _VP, _VP, _PGG, _VP, _VP, _I64, C.c_int32, _VP]),
     "gsplat_logit_grad": (_INT, [_I64, _PV, _VP, _VP, _VP, _VP]),
     "gsplat_densify_stats": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP]),
     "gsplat_frame_densify_stats": (_INT, [_I64, _I64, _PV, _VP, _I64, _VP, _VP]),
+    "gsplat_densify_stats_abs": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP]),
+    "gsplat_frame_densify_stats_abs": (_INT, [_I64, _I64, _PV, _VP, _I64, _VP, _VP]),
     "gsplat_densify_stats_merge": (_INT, [_I64, _VP, _VP, _VP]),
     "gsplat_contribution": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP]),
     "gsplat_frame_contribution": (_INT, [_I64, _I64, _PV, _VP, _I64, _VP, _VP]),

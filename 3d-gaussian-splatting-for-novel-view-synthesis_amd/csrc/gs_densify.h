@@ -21,6 +21,12 @@ namespace {
 // stream (or by events); two streams that add into one record at the same time lose updates.
 constexpr float DENSIFY_EXTENT_MAX = 250.f;      // 2.5 sqrt(1e4): the largest radius of the reference (eigenvalues clamped at 1e4)
 
+//
+// ABS (gsplat_densify_stats_abs): behind an absolute-gradient raster backward, columns 10-11 of grad2d hold
+// Sx = sum |a (A11 du + A12 dv)|, Sy = sum |a (A12 du + A22 dv)| over the Gaussian's pixels, and
+//     grad_sum  += sqrt((o Sx W/2)^2 + (o Sy H/2)^2)
+// -- the per-pixel gradients of the centre added by magnitude, nothing left to cancel.  Everything else is the same.
+template <bool ABS = false>
 __global__ __launch_bounds__(256) void densify_stats_kernel(int64_t n, const DevCounts* __restrict__ counts, long long capacity,
                                                             const uint32_t* __restrict__ tiles, const Rec64* __restrict__ rec,
                                                             const float* __restrict__ grad2d, float half_w, float half_h,
@@ -29,9 +35,15 @@ __global__ __launch_bounds__(256) void densify_stats_kernel(int64_t n, const Dev
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || tiles[i] == 0u) return;
     const f4 r0 = rec[i].r0, r1 = rec[i].r1;          // (u, v, A11, A12), (A22, opacity, ex, ey)
-    const float mx = grad2d[i * 16], my = grad2d[i * 16 + 1];
-    const float gu = r1.y * (r0.z * mx + r0.w * my) * half_w;
-    const float gv = r1.y * (r0.w * mx + r1.x * my) * half_h;
+    float gu, gv;
+    if constexpr (ABS) {
+        gu = r1.y * grad2d[i * 16 + 10] * half_w;
+        gv = r1.y * grad2d[i * 16 + 11] * half_h;
+    } else {
+        const float mx = grad2d[i * 16], my = grad2d[i * 16 + 1];
+        gu = r1.y * (r0.z * mx + r0.w * my) * half_w;
+        gv = r1.y * (r0.w * mx + r1.x * my) * half_h;
+    }
     f4 s = stats[i];
     s.x += sqrtf(gu * gu + gv * gv);
     s.y += 1.f;

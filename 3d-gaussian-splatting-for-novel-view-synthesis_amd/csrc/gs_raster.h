@@ -451,9 +451,15 @@ struct RasterLdsBwd {
 // tools/raster_stats.py: 2816 waves), at 12 608 B twelve (231 -> 221 us), at 11 456 B and 128 VGPRs fourteen (214 us); sixteen
 // (queue cap 18: 10 KB) lose more to chunks cut short than they gain (228 us).
 static_assert(sizeof(RasterLdsBwd<false>) <= 11520, "the backward kernel's LDS per wave decides its occupancy");
-static_assert(sizeof(f4) * 3 * (CHUNK + 1) >= sizeof(float) * CHUNK * 10, "acc must fit into the record arrays");
+static_assert(sizeof(f4) * 3 * (CHUNK + 1) >= sizeof(float) * CHUNK * 12, "acc must fit into the record arrays");
 // The depth / opacity variant (NS = 10) keeps the queue cap and runs at 3 waves per SIMD = 12 per CU, which 12 800 B each allow
 static_assert(sizeof(RasterLdsBwd<true, 10>) <= 12800, "the depth / opacity backward kernel's LDS per wave: 12 waves per CU");
+// The absolute-gradient variants (ABS: NS = 11, 12 with the depth / opacity channels) keep the queue cap, too.  Slots of 11 no longer fit
+// the 14 waves of the plain kernel but do fit 12 800 B: 3 waves per SIMD = 12 per CU, like the depth / opacity variant.  Slots of 12 need
+// 13 360 B = 11 of the 1280-byte pieces: 11 waves per CU by the granularity measured above (not measured on this variant).  A cap of 22 would buy the twelfth wave back; it is not taken: the frames
+// that are both aux and absolute are rare, and one cap keeps the chunk cuts of all eight variants the same.
+static_assert(sizeof(RasterLdsBwd<true, 11>) <= 12800, "the absolute-gradient backward kernel's LDS per wave: 12 waves per CU");
+static_assert(sizeof(RasterLdsBwd<true, 12>) > 12800 && sizeof(RasterLdsBwd<true, 12>) <= 14080, "absolute-gradient + depth / opacity: 11 pieces of 1280 B, 11 waves per CU");
 
 // K7: same traversal as K6 (identical T_i and alive decisions).  For pixel p and Gaussian i:
 //   d alpha_i = alive_i T_i (c_i . Gc) - (sum_{k>i} w_k (c_k . Gc)) / (1 - alpha_i),
@@ -484,17 +490,35 @@ struct AuxBwd {
     float bg[3]; int has_bg;
 };
 
+//
+// ABS (gsplat_rasterize_backward[_aux]_abs): the absolute-gradient densification statistic (AbsGS).  Two sums more
+// per pair, over its pixels: Sx = sum |a (A11 du + A12 dv)|, Sy = sum |a (A12 du + A22 dv)| -- what |dL/du|, |dL/dv| of the projected
+// centre are per pixel, up to the opacity, a factor the statistics kernel multiplies in once per Gaussian.  They land in columns 10
+// and 11 of grad2d with and without AUX (column 9 stays S_z's).  The linear terms come from the staged conic, which is pre-scaled by k:
+// |k x| = |k| |x|, so the pre-scaling is undone once per (list, Gaussian) row, where the chunk's slots are combined.
+constexpr float INV_ABS_QK = 1.38629436111989061883f;      // 1 / |QK| = 2 ln 2
+// the column of grad2d that sum v of a row of NS goes to: sums 9, 10 of a row without S_z skip column 9
+template <bool AUX>
+__device__ __forceinline__ constexpr int grad2d_column(int v) { return (!AUX && v >= 9) ? v + 1 : v; }
+// |x.x| + |x.y| as ONE v_add_f32 (source modifiers; see hadd)
+__device__ __forceinline__ float hadd_abs(v2f a) {
+    float r;
+    asm("v_add_f32 %0, |%1|, |%2|" : "=v"(r) : "v"(a.x), "v"(a.y));
+    return r;
+}
+
 // (4 waves per SIMD: the kernel needs 131 VGPRs left alone, 128 -- no spill -- when asked; with 11.4 KB of LDS 14 waves fit a CU.
-//  AUX: 3 waves per SIMD -- up to 168 VGPRs, and the 12 waves of a CU may have 12.8 KB each: the slots of 10 with the same queue cap)
-template <bool DET, bool AUX = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AUX ? 3 : 4, AUX ? 3 : 4))) void raster_backward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ ids,
+//  AUX: 3 waves per SIMD -- up to 168 VGPRs, and the 12 waves of a CU may have 12.8 KB each: the slots of 10 with the same queue cap.
+//  ABS: 3 waves per SIMD as well, see the static_asserts at RasterLdsBwd)
+template <bool DET, bool AUX = false, bool ABS = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((AUX || ABS) ? 3 : 4, (AUX || ABS) ? 3 : 4))) void raster_backward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ ids,
                                                              const Rec64* __restrict__ rec, const uint32_t* __restrict__ order,
                                                              int lists_x, int H, int W, float chi, float alpha_max,
                                                              float alpha_cutoff, const float* __restrict__ accum,
                                                              const float* __restrict__ gimg, float* __restrict__ grad2d,
                                                              WaveStats* __restrict__ stats, uint32_t id_max, DetArgs det,
                                                              const uint8_t* __restrict__ pair_mask, AuxBwd aux = AuxBwd{}) {
-    constexpr int NS = AUX ? 10 : 9;               // sums per (list, Gaussian) pair
+    constexpr int NS = (AUX ? 10 : 9) + (ABS ? 2 : 0);      // sums per (list, Gaussian) pair
     constexpr int RPI = 64 / NS;                   // rows per flush instruction
     __shared__ RasterLdsBwd<DET, NS> sb;
     RasterLdsB& s = sb.f;
@@ -638,6 +662,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AUX ? 3 : 4,
                 const float tot_z = all_reduce8(hadd(w * Gd));             // S_z = dL/dz
                 if (j == 1) myslot[k * NS + 8] = tot_z;                    // (lane 1 of the group: slot index 9)
             }
+            if constexpr (ABS) {
+                // k (A11 du + A12 dv) = (k A11 du) + (k A12) dv and k (A12 du + A22 dv) = (k A12) du + (k A22) dv from the staged conic
+                const float h = 0.5f * a.w;                                // k A12 (exact)
+                const v2f lu = a.z * du + h * dv, lv = h * du + b.x * dv;
+                const float tot_x = all_reduce8(hadd_abs(ao * lu));        // |k| Sx
+                const float tot_y = all_reduce8(hadd_abs(ao * lv));        // |k| Sy
+                if (j == NS - 10) myslot[k * NS + 8] = tot_x;              // (slot indices NS - 2, NS - 1)
+                if (j == NS - 9) myslot[k * NS + 8] = tot_y;
+            }
             T = T - al * T;
         };
         // Software pipeline over the queue (LDS latency is not covered by occupancy here: 3 waves per SIMD), two entries per step
@@ -678,6 +711,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AUX ? 3 : 4,
                     for (int v = 0; v < NS; ++v) tot[v] += p[v];
                 }
             }
+            if constexpr (ABS) { tot[NS - 2] *= INV_ABS_QK; tot[NS - 1] *= INV_ABS_QK; }      // the conic's pre-scaling, undone once per row
 #pragma unroll
             for (int v = 0; v < NS; ++v) acc[lane * NS + v] = tot[v];
         }
@@ -715,7 +749,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AUX ? 3 : 4,
                     const uint32_t slot = sb.eslot[c];
                     if (slot < det.capacity) det.part[(int64_t)slot * NS + my_k] = val;
                 } else if (val != 0.0f) {
-                    atomicAdd(&grad2d[(int64_t)sb.eid[c] * 16 + my_k], val);
+                    atomicAdd(&grad2d[(int64_t)sb.eid[c] * 16 + (ABS ? grad2d_column<AUX>(my_k) : my_k)], val);
                 }
             }
         }
@@ -772,8 +806,9 @@ __global__ __launch_bounds__(256) void pair_base_kernel(int64_t n, const uint32_
 
 // grad2d[i][0..NS-1] = sum of Gaussian i's rows, in the order of its lists (row-major in its rectangle): the same order every run;
 // columns NS .. 15 = 0.
-// NS = floats per row: 9, or 10 behind the depth / opacity backward.
-template <int NS = 9>
+// NS = floats per row: 9, or 10 behind the depth / opacity backward; 11 and 12 behind the absolute-gradient variants, whose rows of 11
+// (GAP) have no S_z: their sums 9, 10 go to columns 10, 11 (grad2d_column), column 9 = 0.
+template <int NS = 9, bool GAP = false>
 __global__ __launch_bounds__(256) void pair_reduce_kernel(int64_t n, const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ pair_base,
                                                           const float* __restrict__ part, uint32_t capacity, float* __restrict__ grad2d) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -788,6 +823,16 @@ __global__ __launch_bounds__(256) void pair_reduce_kernel(int64_t n, const uint3
         for (int v = 0; v < NS; ++v) t[v] += row[v];
     }
     float* o = grad2d + i * 16;
+    if constexpr (GAP) {
+        float full[16];
+#pragma unroll
+        for (int v = 0; v < 16; ++v) full[v] = 0.f;
+#pragma unroll
+        for (int v = 0; v < NS; ++v) full[grad2d_column<false>(v)] = t[v];
+#pragma unroll
+        for (int v = 0; v < 16; ++v) o[v] = full[v];
+        return;
+    }
 #pragma unroll
     for (int v = 0; v < NS; ++v) o[v] = t[v];
 #pragma unroll

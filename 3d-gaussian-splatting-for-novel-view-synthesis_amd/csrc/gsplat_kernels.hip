@@ -13,6 +13,7 @@
 //       (+ tile_block_sum / pair_base / pair_reduce_kernel: deterministic mode)
 //   K8  project_backward_kernel chain rule to the reference's input tensors                     [B2, B3]
 //   K9  densify_stats_kernel / densify_stats_merge_kernel   screen-space densification statistics behind K7 (not in the reference)
+//       (K7, K9 <ABS>: the absolute-gradient statistic -- two sums more per pair, columns 10-11 of grad2d)
 //   K10 raster_contrib_kernel  K6's traversal without colours: per-Gaussian blending-weight statistics (not in the reference)
 //
 // Everything is hand-written HIP for gfx950; no library kernels.  No MFMA: there is no dense contraction on this path.
@@ -152,7 +153,7 @@ int check_sh_degree(const char* entry, int degree, bool fused) {
 // (GSPLAT_BACKWARD_DEPTH: the two projection entries only -- the composite entries have no depth / opacity frame)
 constexpr int32_t PROJECT_BACKWARD_FLAGS = GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_ACCUMULATE | GSPLAT_BACKWARD_DEPTH;
 constexpr int32_t BACKWARD_FLAGS = GSPLAT_BACKWARD_SH_JACOBIAN | GSPLAT_BACKWARD_ACCUMULATE | GSPLAT_BACKWARD_PHASE_RASTER |
-                                   GSPLAT_BACKWARD_PHASE_PROJECT | GSPLAT_BACKWARD_GRAD2D_DIRTY;
+                                   GSPLAT_BACKWARD_PHASE_PROJECT | GSPLAT_BACKWARD_GRAD2D_DIRTY | GSPLAT_BACKWARD_ABSGRAD;
 
 // K8 for gsplat_project_backward, the composite entries (ar: the in-place f_rest step) and gsplat_project_backward_pose (pose: where
 // the camera-pose gradient goes; `out` may then be NULL = pose only).
@@ -251,13 +252,14 @@ void set_background(Aux& a, const float* background) {
 }
 
 // K7 and (deterministic mode) the kernels around it, for gsplat_rasterize_backward and gsplat_rasterize_backward_aux (aux: the
-// depth / opacity variant, rows of 10).
+// depth / opacity variant, rows of 10) and their _abs twins (abs: the absolute-gradient sums in columns 10-11, rows of 11 and 12).
+constexpr int raster_row(bool aux, bool abs) { return (aux ? 10 : 9) + (abs ? 2 : 0); }
 int raster_backward_impl(int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, const void* bin_state,
                          const float* accum, const float* grad_image, float* grad2d, int32_t grad2d_zeroed, void* det_scratch,
-                         int64_t det_scratch_bytes, void* stream_, const AuxBwd* aux) {
+                         int64_t det_scratch_bytes, void* stream_, const AuxBwd* aux, bool abs = false) {
     const auto [st, vk, nl, nb, ps] = open_ctx(n, v, project_state, stream_);
     const bool det = det_scratch != nullptr;
-    const int row = aux ? 10 : 9;
+    const int row = raster_row(aux != nullptr, abs);
     if (!grad2d_zeroed && !det) HIP_TRY(hipMemsetAsync(grad2d, 0, (size_t)(n > 0 ? n : 0) * 16 * sizeof(float), st));
     if (n == 0) return GSPLAT_OK;
     if (n_binned == 0) {
@@ -274,6 +276,18 @@ int raster_backward_impl(int64_t n, int64_t n_binned, const gsplat_view* v, cons
         LAUNCH("pair_base_kernel", pair_base_kernel, dim3(pb_blocks), dim3(256), 0, st, n, ps.tiles, ds.block_sum, ds.pair_base);
     }
     const DetArgs da = det ? DetArgs{ps.rect, ps.mask, ps.tiles, ds.pair_base, ds.part, (uint32_t)n_binned} : DetArgs{};
+    if (abs) {
+        const auto kernel = aux ? (det ? raster_backward_kernel<true, true, true> : raster_backward_kernel<false, true, true>)
+                                : (det ? raster_backward_kernel<true, false, true> : raster_backward_kernel<false, false, true>);
+        LAUNCH(aux ? "raster_backward_kernel<aux, abs>" : "raster_backward_kernel<abs>", kernel, dim3((unsigned)nl), dim3(64), 0, st, ps.ranges,
+               (const uint32_t*)bin_state, ps.rec, ps.order, vk.lists_x, vk.H, vk.W, vk.chi_clip, vk.alpha_max, vk.alpha_cutoff,
+               accum, grad_image, grad2d, STATS_BWD, (uint32_t)(n - 1), da, pair_mask_of(bin_state, n_binned), aux ? *aux : AuxBwd{});
+        if (det) {
+            LAUNCH("pair_reduce_kernel<abs>", (aux ? pair_reduce_kernel<12> : pair_reduce_kernel<11, true>), dim3(blocks256(n)), dim3(256), 0, st, n, ps.tiles, ds.pair_base, ds.part,
+                   (uint32_t)n_binned, grad2d);
+        }
+        return GSPLAT_OK;
+    }
     if (aux) {
         LAUNCH(det ? "raster_backward_kernel<deterministic, aux>" : "raster_backward_kernel<aux>", (det ? raster_backward_kernel<true, true> : raster_backward_kernel<false, true>),
                dim3((unsigned)nl), dim3(64), 0, st, ps.ranges, (const uint32_t*)bin_state, ps.rec, ps.order, vk.lists_x, vk.H, vk.W, vk.chi_clip,
@@ -291,7 +305,7 @@ int raster_backward_impl(int64_t n, int64_t n_binned, const gsplat_view* v, cons
 
 // gsplat_densify_stats / gsplat_frame_densify_stats behind their argument checks (every message names the entry)
 int densify_stats_impl(const char* name, int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, const float* grad2d,
-                       float* stats, void* stream_) {
+                       float* stats, void* stream_, bool abs = false) {
     if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
     if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
     if (n < 0 || n > (int64_t)ID_MASK + 1 || pair_capacity < 0) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
@@ -299,7 +313,7 @@ int densify_stats_impl(const char* name, int64_t n, int64_t pair_capacity, const
     if (!aligned16(stats) || !aligned16(grad2d)) return fail(GSPLAT_ERR_BAD_ARG, "%s: stats / grad2d must be 16-byte aligned", name);
     if (n == 0) return GSPLAT_OK;
     const Ctx c = open_ctx(n, v, project_state, stream_);
-    LAUNCH("densify_stats_kernel", densify_stats_kernel, dim3(blocks256(n)), dim3(256), 0, c.st, n, c.ps.counts, (long long)pair_capacity, c.ps.tiles,
+    LAUNCH("densify_stats_kernel", abs ? densify_stats_kernel<true> : densify_stats_kernel<false>, dim3(blocks256(n)), dim3(256), 0, c.st, n, c.ps.counts, (long long)pair_capacity, c.ps.tiles,
            c.ps.rec, grad2d, 0.5f * (float)v->W, 0.5f * (float)v->H, reinterpret_cast<f4*>(stats));
     return GSPLAT_OK;
 }
@@ -365,6 +379,10 @@ int64_t gsplat_bin_scratch_bytes(int64_t pair_capacity, const gsplat_view* v) {
 int64_t gsplat_rasterize_backward_scratch_bytes(int64_t n, int64_t pair_capacity) { return carve_det(nullptr, n, pair_capacity).bytes; }
 
 int64_t gsplat_rasterize_backward_aux_scratch_bytes(int64_t n, int64_t pair_capacity) { return carve_det(nullptr, n, pair_capacity, 10).bytes; }
+
+int64_t gsplat_rasterize_backward_abs_scratch_bytes(int64_t n, int64_t pair_capacity) { return carve_det(nullptr, n, pair_capacity, raster_row(false, true)).bytes; }
+
+int64_t gsplat_rasterize_backward_aux_abs_scratch_bytes(int64_t n, int64_t pair_capacity) { return carve_det(nullptr, n, pair_capacity, raster_row(true, true)).bytes; }
 
 int64_t gsplat_pose_scratch_bytes(int64_t n) { return n < 0 ? -1 : carve_pose(nullptr, n).bytes; }
 
@@ -559,6 +577,38 @@ int gsplat_rasterize_backward_aux(int64_t n, int64_t n_binned, const gsplat_view
                                 stream_, &aux);
 }
 
+// the _abs twins: the same arguments, the absolute-gradient sums beside the gradients; every refusal names the entry
+static int check_raster_abs(const char* name, int64_t n, int64_t n_binned, const gsplat_view* v) {
+    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
+    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
+    if (n < 0 || n > (int64_t)ID_MASK + 1 || n_binned < 0 || n_binned > 0xFFFFFFFFLL) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
+    return GSPLAT_OK;
+}
+
+int gsplat_rasterize_backward_abs(int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, const void* bin_state,
+                                  const float* accum, const float* grad_image, float* grad2d, int32_t grad2d_zeroed,
+                                  void* det_scratch, int64_t det_scratch_bytes, void* stream_) {
+    const char* name = "gsplat_rasterize_backward_abs";
+    if (int rc = check_raster_abs(name, n, n_binned, v)) return rc;
+    if (!project_state || !bin_state || !accum || !grad_image || !grad2d) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
+    return raster_backward_impl(n, n_binned, v, project_state, bin_state, accum, grad_image, grad2d, grad2d_zeroed, det_scratch, det_scratch_bytes,
+                                stream_, nullptr, true);
+}
+
+int gsplat_rasterize_backward_aux_abs(int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, const void* bin_state,
+                                      const float* accum, const float* accum_aux, const float* grad_image, const float* grad_depth,
+                                      const float* grad_alpha, const float* background, float* grad2d, int32_t grad2d_zeroed,
+                                      void* det_scratch, int64_t det_scratch_bytes, void* stream_) {
+    const char* name = "gsplat_rasterize_backward_aux_abs";
+    if (int rc = check_raster_abs(name, n, n_binned, v)) return rc;
+    if (!grad_image && !grad_depth && !grad_alpha) return fail(GSPLAT_ERR_BAD_ARG, "%s: grad_image, grad_depth and grad_alpha are all NULL", name);
+    if (!project_state || !bin_state || !accum || !accum_aux || !grad2d) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
+    AuxBwd aux = {accum_aux, grad_depth, grad_alpha, {0.f, 0.f, 0.f}, 0};
+    set_background(aux, background);
+    return raster_backward_impl(n, n_binned, v, project_state, bin_state, accum, grad_image, grad2d, grad2d_zeroed, det_scratch, det_scratch_bytes,
+                                stream_, &aux, true);
+}
+
 int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state,
                             const float* grad2d, const gsplat_gaussian_grads* out, int32_t flags, void* stream_) {
     if (flags & ~(PROJECT_BACKWARD_FLAGS | BACKWARD_SH_BITS | FILTER_BITS)) return fail(GSPLAT_ERR_BAD_ARG, "unknown flag bits");
@@ -619,8 +669,9 @@ static int backward_impl(const char* entry, const gsplat_gaussians* g, const flo
     if (both || (flags & GSPLAT_BACKWARD_PHASE_RASTER)) {
         if (!grad_image) return fail(GSPLAT_ERR_BAD_ARG, "grad_image is NULL");
         const int32_t zeroed = forward_clears_grad2d(g->n, v) && !(flags & GSPLAT_BACKWARD_GRAD2D_DIRTY);
-        if ((rc = gsplat_rasterize_backward(g->n, pair_capacity, v, base + f.project_state, base + f.bin_state, (const float*)(base + f.accum),
-                                            grad_image, grad2d, zeroed, det_scratch, det_scratch_bytes, stream_))) return rc;
+        const auto raster = (flags & GSPLAT_BACKWARD_ABSGRAD) ? gsplat_rasterize_backward_abs : gsplat_rasterize_backward;
+        if ((rc = raster(g->n, pair_capacity, v, base + f.project_state, base + f.bin_state, (const float*)(base + f.accum),
+                         grad_image, grad2d, zeroed, det_scratch, det_scratch_bytes, stream_))) return rc;
         if (grad_logit && (rc = gsplat_logit_grad(g->n, v, base + f.project_state, grad2d, grad_logit, stream_))) return rc;
     }
     if (both || (flags & GSPLAT_BACKWARD_PHASE_PROJECT)) {
@@ -735,9 +786,13 @@ int gsplat_densify_stats(int64_t n, int64_t pair_capacity, const gsplat_view* v,
     return densify_stats_impl("gsplat_densify_stats", n, pair_capacity, v, project_state, grad2d, stats, stream_);
 }
 
-int gsplat_frame_densify_stats(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame, int64_t frame_bytes,
-                               float* stats, void* stream_) {
-    const char* name = "gsplat_frame_densify_stats";
+int gsplat_densify_stats_abs(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, const float* grad2d,
+                             float* stats, void* stream_) {
+    return densify_stats_impl("gsplat_densify_stats_abs", n, pair_capacity, v, project_state, grad2d, stats, stream_, true);
+}
+
+static int frame_densify_stats_impl(const char* name, int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame, int64_t frame_bytes,
+                                    float* stats, void* stream_, bool abs) {
     if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
     if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
     if (n < 0 || pair_capacity < 0) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
@@ -746,7 +801,17 @@ int gsplat_frame_densify_stats(int64_t n, int64_t pair_capacity, const gsplat_vi
     const FrameParts f = frame_parts(n, pair_capacity, v, GSPLAT_FRAME_BACKWARD);
     if (f.total > frame_bytes) return fail(GSPLAT_ERR_BAD_ARG, "%s: frame arena too small: was it made with GSPLAT_FRAME_BACKWARD?", name);
     const char* base = (const char*)frame;
-    return densify_stats_impl(name, n, pair_capacity, v, base + f.project_state, (const float*)(base + f.grad2d), stats, stream_);
+    return densify_stats_impl(name, n, pair_capacity, v, base + f.project_state, (const float*)(base + f.grad2d), stats, stream_, abs);
+}
+
+int gsplat_frame_densify_stats(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame, int64_t frame_bytes,
+                               float* stats, void* stream_) {
+    return frame_densify_stats_impl("gsplat_frame_densify_stats", n, pair_capacity, v, frame, frame_bytes, stats, stream_, false);
+}
+
+int gsplat_frame_densify_stats_abs(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame, int64_t frame_bytes,
+                                   float* stats, void* stream_) {
+    return frame_densify_stats_impl("gsplat_frame_densify_stats_abs", n, pair_capacity, v, frame, frame_bytes, stats, stream_, true);
 }
 
 int gsplat_densify_stats_merge(int64_t n, float* pass, float* total, void* stream_) {

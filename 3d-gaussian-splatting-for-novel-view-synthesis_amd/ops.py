@@ -409,11 +409,11 @@ def _frame_spec(fused, H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis,
 class _Frame:
     """Everything the backward pass needs from one forward call: the call's FrameSpec (`spec`: camera and mode), the converted inputs
     by name, and the facts of this autograd call -- `need_grad`, `pose` (the backward also forms dL/dc2w), `stats` (the
-    densify_stats() record, if any) and the gradient route (`route`, `route_kind`: _route_of).  A frame queued by
+    densify_stats() record, if any; `absgrad`: its mode) and the gradient route (`route`, `route_kind`: _route_of).  A frame queued by
     gsplat_forward_deferred keeps ONE arena (project_state | bin_state | accum | grad2d, carved by the library); one that went
     through the separate calls keeps them as separate buffers."""
     __slots__ = ("spec", "n", "n_pairs", "proj_state", "bin_state", "accum", "inputs", "c2w", "empty", "grad2d", "sh_jacobian", "arena",
-                 "gaussians", "dirty", "src_ptrs", "route", "route_kind", "pose", "need_grad", "accum_aux", "stats")
+                 "gaussians", "dirty", "src_ptrs", "route", "route_kind", "pose", "need_grad", "accum_aux", "stats", "absgrad")
 
 
 def _forward_begin(spec, c2w, tensors, pose=False, need_grad=False):
@@ -440,6 +440,7 @@ def _forward_begin(spec, c2w, tensors, pose=False, need_grad=False):
     dev = pos.device
     fr = _Frame()
     fr.spec, fr.pose, fr.need_grad, fr.stats = spec, pose, need_grad, stats if need_grad else None
+    fr.absgrad = fr.stats is not None and _stats_absgrad.get()       # (read once, beside the record)
     fr.route, fr.route_kind = None, PLAIN       # (until _route_of finds a consumer for this frame)
     n, view, opa = pos.shape[0], spec.view, tensors["opacity_raw"]
     fr.n, fr.inputs = n, dict(pos=_f32(pos, (n, 3), "pos"), opacity_raw=_f32(opa if opa.dim() == 1 else opa.reshape(-1), (n,), "opacity_raw"))
@@ -741,7 +742,10 @@ def _backward_impl(fr, grad_image, need_params=True, grad_depth=None, grad_alpha
         torch.cuda.set_device(dev)
     stream = bp.stream = torch.cuda.current_stream(dev)
     bp.st = C.c_void_p(stream.cuda_stream)
-    det_bytes = lib.gsplat_rasterize_backward_aux_scratch_bytes if spec.is_aux else lib.gsplat_rasterize_backward_scratch_bytes
+    if fr.absgrad:             # the absolute-gradient raster backward: rows of 11 / 12
+        det_bytes = lib.gsplat_rasterize_backward_aux_abs_scratch_bytes if spec.is_aux else lib.gsplat_rasterize_backward_abs_scratch_bytes
+    else:
+        det_bytes = lib.gsplat_rasterize_backward_aux_scratch_bytes if spec.is_aux else lib.gsplat_rasterize_backward_scratch_bytes
     bp.det = _ws.get_scratch(dev, det_bytes(fr.n, fr.n_pairs), (dev.type, dev.index, stream.cuda_stream)) if _deterministic else None
     staged = bp.staged = _timer is not None and _timer.wants(_BACKWARD_STAGES)
     # only known now, each sending the frame down the ordinary backward: a timed pass (phase by phase), a second pass through the
@@ -790,18 +794,22 @@ def _backward_separate(fr, bp, grad_depth, grad_alpha, need_params):
     with _stage("raster_backward"):
         if spec.is_aux:
             # (z, 1) as two more colour channels; column 9 of grad2d = dL/dz, which the projection backward picks up (DEPTH)
-            _abi.check(lib.gsplat_rasterize_backward_aux(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state),
-                                                         _p(fr.accum), _p(fr.accum_aux), _p(bp.gi), _p(gd), _p(ga),
-                                                         _background_arg(spec.background), _p(grad2d), int(zeroed), _p(det),
-                                                         det.numel() if det is not None else 0, st), "gsplat_rasterize_backward_aux")
+            name = "gsplat_rasterize_backward_aux_abs" if fr.absgrad else "gsplat_rasterize_backward_aux"
+            _abi.check(getattr(lib, name)(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state),
+                                          _p(fr.accum), _p(fr.accum_aux), _p(bp.gi), _p(gd), _p(ga),
+                                          _background_arg(spec.background), _p(grad2d), int(zeroed), _p(det),
+                                          det.numel() if det is not None else 0, st), name)
             jac |= _abi.GSPLAT_BACKWARD_DEPTH
         else:
-            _abi.check(lib.gsplat_rasterize_backward(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state),
-                                                     _p(fr.accum), _p(bp.gi), _p(grad2d), int(zeroed), _p(det),
-                                                     det.numel() if det is not None else 0, st), "gsplat_rasterize_backward")
+            name = "gsplat_rasterize_backward_abs" if fr.absgrad else "gsplat_rasterize_backward"
+            _abi.check(getattr(lib, name)(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state),
+                                          _p(fr.accum), _p(bp.gi), _p(grad2d), int(zeroed), _p(det),
+                                          det.numel() if det is not None else 0, st), name)
     if fr.stats is not None:
-        _abi.check(lib.gsplat_densify_stats(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(grad2d), _p(fr.stats), st),
-                   "gsplat_densify_stats")
+        name = "gsplat_densify_stats_abs" if fr.absgrad else "gsplat_densify_stats"
+        _abi.check(getattr(lib, name)(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(grad2d), _p(fr.stats), st), name)
+        if fr.absgrad:
+            absgrad_calls["separate"] += 1
     if bp.kind == FACTORED:
         # logit gradients first: the exchange may start on them while the projection backward runs
         glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=dev)
@@ -840,7 +848,7 @@ def _backward_arena(fr, bp):
     """The frame was queued by gsplat_forward_deferred: one call for the whole backward pass (two, phase by phase, for a factored
     exchange or a timed pass)."""
     kind, route, jac, det = bp.kind, fr.route, bp.jac, bp.det
-    flags = jac | (_abi.GSPLAT_BACKWARD_GRAD2D_DIRTY if fr.dirty else 0)
+    flags = jac | (_abi.GSPLAT_BACKWARD_GRAD2D_DIRTY if fr.dirty else 0) | (_abi.GSPLAT_BACKWARD_ABSGRAD if fr.absgrad else 0)
     fr.dirty = True                            # a second backward through the same graph must not reuse a dirty buffer
     if kind == FACTORED or bp.staged:
         glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=fr.arena.device) if kind == FACTORED else None
@@ -870,8 +878,10 @@ def _backward_arena(fr, bp):
 def _frame_stats(fr, st):
     """The densification statistics of a frame on an arena, once its raster phase is queued (fr.stats: ops.densify_stats)."""
     if fr.stats is not None:
-        _abi.check(_abi.lib().gsplat_frame_densify_stats(fr.n, fr.n_pairs, C.byref(fr.spec.view), _p(fr.arena), fr.arena.numel(), _p(fr.stats), st),
-                   "gsplat_frame_densify_stats")
+        name = "gsplat_frame_densify_stats_abs" if fr.absgrad else "gsplat_frame_densify_stats"
+        _abi.check(getattr(_abi.lib(), name)(fr.n, fr.n_pairs, C.byref(fr.spec.view), _p(fr.arena), fr.arena.numel(), _p(fr.stats), st), name)
+        if fr.absgrad:
+            absgrad_calls["arena"] += 1
 
 
 class DensifyStats:
@@ -931,21 +941,34 @@ class DensifyStats:
 # The record the frames rendered inside a densify_stats() block add to.  A slot of its own (not a gradient route: it combines with
 # any route), read once, in the caller's thread, when a frame is rendered (fr.stats), like fr.route.
 _stats = contextvars.ContextVar("gsplat_densify_stats", default=None)
+_stats_absgrad = contextvars.ContextVar("gsplat_densify_stats_absgrad", default=False)
+absgrad_calls = {"separate": 0, "arena": 0}      # statistics calls queued in absolute-gradient mode, by the kind of frame
 
 
-@contextlib.contextmanager
-def densify_stats(rec):
+def densify_stats(rec, absgrad=False):
     """Every backward pass of a frame rendered inside the block adds that frame's statistics to `rec` (a DensifyStats, or its
     float32 [N, 4] tensor), once, on the backward's stream, behind its raster phase -- whatever route the gradients take.  Empty and
     all-culled frames, frames rendered under torch.no_grad() and frames that overflowed their pair capacity add nothing.  A record
-    that does not fit the frame (float32 [n, 4], contiguous, on the frame's device) raises ValueError when the frame is rendered."""
+    that does not fit the frame (float32 [n, 4], contiguous, on the frame's device) raises ValueError when the frame is rendered.
+
+    absgrad=True (a bool, else TypeError): grad_sum gets the ABSOLUTE-gradient statistic (AbsGS) -- per pixel, the
+    magnitudes of dL/du and dL/dv of the projected centre, added without their signs; the frame's raster backward is then the
+    variant that forms them, and its gradients are unchanged.  count and extent_max are the same in both modes."""
+    if type(absgrad) is not bool:
+        raise TypeError(f"densify_stats(): absgrad must be a bool, not {absgrad!r}")
     data = rec.data if isinstance(rec, DensifyStats) else rec
     if not isinstance(data, torch.Tensor):
         raise TypeError("densify_stats() takes a DensifyStats or its [N, 4] tensor")
-    token = _stats.set(data)
+    return _densify_stats_block(rec, data, absgrad)       # (the arguments are checked by the call, not by the `with`)
+
+
+@contextlib.contextmanager
+def _densify_stats_block(rec, data, absgrad):
+    token, token_abs = _stats.set(data), _stats_absgrad.set(absgrad)
     try:
         yield rec
     finally:
+        _stats_absgrad.reset(token_abs)
         _stats.reset(token)
 
 

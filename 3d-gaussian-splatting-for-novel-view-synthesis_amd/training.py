@@ -74,6 +74,11 @@ class TrainConfig:
     # pruned once iteration > opacity_reset_interval.
     densify_rule: str = "reference"
     densify_grad_threshold: float = 0.0002
+    # densify_rule = "screen" only (ValueError under the other rules): the windows hold the ABSOLUTE-gradient statistic (AbsGS;
+    # ops.densify_stats(absgrad=True)) -- per pixel, |dL/du| and |dL/dv| of the projected centre are added without their
+    # signs, so a large blurry Gaussian whose pixels pull its centre in opposite directions is still seen.  The statistic is larger than
+    # the signed one: densify_grad_threshold keeps its default but wants raising (the papers: 0.0004 - 0.0008).
+    densify_absgrad: bool = False
     max_screen_size: float = 20.0
     # the paper's SH schedule (not in the reference, which always evaluates degree 3).  0: degree 3 always.  k > 0: iteration i renders
     # every view at SH degree min(3, i // k) (the paper: k = 1000) -- until a band is switched on its coefficients colour nothing and
@@ -113,6 +118,16 @@ class TrainConfig:
     mcmc_growth: float = 1.05
     mcmc_seed: int = 0
 
+    def __post_init__(self):
+        _check_absgrad(self)
+
+
+def _check_absgrad(cfg):
+    if type(cfg.densify_absgrad) is not bool:
+        raise ValueError(f"densify_absgrad must be a bool, not {cfg.densify_absgrad!r}")
+    if cfg.densify_absgrad and cfg.densify_rule != "screen":
+        raise ValueError(f"densify_absgrad=True needs densify_rule='screen' (the other rules read no screen-space statistic), not {cfg.densify_rule!r}")
+
 
 _side_streams = {}           # per device: the two streams the views of an iteration alternate between (TrainConfig.view_streams)
 
@@ -128,6 +143,7 @@ class Trainer:
         if self.cfg.densify_rule not in ("reference", "screen", "mcmc"):
             raise ValueError(f"densify_rule must be 'reference', 'screen' or 'mcmc', not {self.cfg.densify_rule!r}")
         _check_mcmc(self.cfg)
+        _check_absgrad(self.cfg)                # (again: the fields of a config can be set after it is made)
         if type(self.cfg.sh_degree_interval) is not int or self.cfg.sh_degree_interval < 0:
             raise ValueError(f"sh_degree_interval must be an integer >= 0, not {self.cfg.sh_degree_interval!r}")
         self._filter_kw = _abi.filter_kwargs(self.cfg.lowpass, self.cfg.antialias)      # (ValueError for a mode the kernels cannot do)
@@ -309,6 +325,7 @@ class Trainer:
         self.optimizer.param_groups[0]['lr'] = pos_lr
         screen = c.densify_rule == "screen" and iteration < c.densify_until_iter
         pass_stats = self._prepare_stats(dev, len(views)) if screen else None
+        absgrad_kw = {'absgrad': True} if c.densify_absgrad else {}         # (the default call is the signed rule's)
         for attempt in range(4):
             self.optimizer.zero_grad()
             acc = torch.zeros(3, dtype=torch.float32, device=dev)
@@ -345,7 +362,7 @@ class Trainer:
                                 if image_gt.shape[-1] == 4:            # rgb + alpha: over black
                                     image_gt = losses.composite_over(image_gt[..., :3], image_gt[..., 3], (0.0, 0.0, 0.0))
                             c2w = torch.as_tensor(v['c2w'], dtype=torch.float32).to(dev)
-                            with (ops.densify_stats(pass_stats[k]) if screen else contextlib.nullcontext()):
+                            with (ops.densify_stats(pass_stats[k], **absgrad_kw) if screen else contextlib.nullcontext()):
                                 rendered = ops.render_gaussians(m.pos, m.f_dc, m.f_rest, m.opacity_raw, m.scale_raw, m.q_raw, c2w,
                                                                 int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']),
                                                                 **degree_kw, **self._filter_kw, **aux_kw)

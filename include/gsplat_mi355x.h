@@ -258,6 +258,26 @@ int gsplat_rasterize_backward_aux(int64_t n, int64_t pair_capacity, const gsplat
                                   const float* grad_depth, const float* grad_alpha, const float* background, float* grad2d,
                                   int32_t grad2d_zeroed, void* det_scratch, int64_t det_scratch_bytes, void* stream);
 
+/* The absolute-gradient twins (AbsGS, gsplat's absgrad): the arguments, the gradients and the deterministic mode of
+ * gsplat_rasterize_backward / gsplat_rasterize_backward_aux -- columns 0-8 (0-9) of grad2d are theirs, bit for bit in deterministic
+ * mode -- and, per Gaussian, two sums more over all pixels p of all its lists.  With a_p = dL/dalpha exp(-q/2) (zero unless the pixel
+ * is alive, alpha passed its tests and o g <= alpha_max: the quantity whose moments columns 0-5 hold), du = px - u, dv = py - v:
+ *     column 10 = Sx = sum_p |a_p (A11 du + A12 dv)|        column 11 = Sy = sum_p |a_p (A12 du + A22 dv)|
+ * in BOTH variants: o Sx, o Sy are the per-pixel |dL/du|, |dL/dv| of the projected centre added without their signs, where columns
+ * 0-1 let them cancel.  Column 9 stays dL/dz behind the aux entry and is otherwise left as gsplat_rasterize_backward leaves it.
+ * gsplat_densify_stats_abs reads the two columns.  The scratch of the deterministic mode has rows of 11 and 12 floats: its own size
+ * queries.  GSPLAT_ERR_BAD_ARG (the text names the entry): a NULL view or required pointer, a bad view, n or pair_capacity out of
+ * range.  n == 0: GSPLAT_OK, no kernel is launched.                                                                             */
+int64_t gsplat_rasterize_backward_abs_scratch_bytes(int64_t n, int64_t pair_capacity);
+int64_t gsplat_rasterize_backward_aux_abs_scratch_bytes(int64_t n, int64_t pair_capacity);
+int gsplat_rasterize_backward_abs(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state,
+                                  const void* bin_state, const float* accum, const float* grad_image, float* grad2d,
+                                  int32_t grad2d_zeroed, void* det_scratch, int64_t det_scratch_bytes, void* stream);
+int gsplat_rasterize_backward_aux_abs(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state,
+                                      const void* bin_state, const float* accum, const float* accum_aux, const float* grad_image,
+                                      const float* grad_depth, const float* grad_alpha, const float* background, float* grad2d,
+                                      int32_t grad2d_zeroed, void* det_scratch, int64_t det_scratch_bytes, void* stream);
+
 /* B2 (+B3 when fused): chain the 2D gradients back to the inputs of gsplat_project.
  * Factored form (fused inputs; out->f_dc and out->f_rest NULL): instead of the 48 SH-coefficient
  * gradients per Gaussian, out->color[n,3] (if given) receives the gradient w.r.t. the colour LOGIT (the sigmoid's argument,
@@ -325,6 +345,10 @@ int gsplat_project_backward_pose(const gsplat_gaussians* g, const float* c2w, co
 /* the gradients are ADDED to what `out` holds (the views of one iteration summed by the projection backward itself; the caller
  * clears or writes the arrays with the first view).  Fused inputs with GSPLAT_BACKWARD_SH_JACOBIAN, all six gradients given.  */
 #define GSPLAT_BACKWARD_ACCUMULATE 16
+/* gsplat_backward / gsplat_backward_adam_rest: the raster phase is gsplat_rasterize_backward_abs (its deterministic scratch then
+ * has gsplat_rasterize_backward_abs_scratch_bytes), so that gsplat_frame_densify_stats_abs may follow.  Accepted and ignored where
+ * only GSPLAT_BACKWARD_PHASE_PROJECT runs; an unknown bit to gsplat_project_backward[_pose].                                   */
+#define GSPLAT_BACKWARD_ABSGRAD 128
 int64_t gsplat_frame_bytes(int64_t n, int64_t pair_capacity, const gsplat_view* v, int32_t flags);
 int gsplat_forward_deferred(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, void* frame,
                             int64_t frame_bytes, int64_t pair_capacity, void* counters, int64_t counters_bytes,
@@ -376,6 +400,15 @@ int gsplat_densify_stats(int64_t n, int64_t pair_capacity, const gsplat_view* v,
 int gsplat_frame_densify_stats(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame,
                                int64_t frame_bytes, float* stats, void* stream);
 int gsplat_densify_stats_merge(int64_t n, float* pass, float* total, void* stream);
+/* The absolute-gradient statistic: the same record, rules, guards and errors, but
+ *     grad_sum += sqrt((o Sx W/2)^2 + (o Sy H/2)^2)        (Sx, Sy) = columns 10-11 of grad2d
+ * so grad2d / the frame must come from gsplat_rasterize_backward[_aux]_abs, or from gsplat_backward / gsplat_backward_adam_rest
+ * with GSPLAT_BACKWARD_ABSGRAD (behind the plain entries the two columns hold zeros or stale values).  count and extent_max are
+ * what the plain entries add; records of the two kinds merge with gsplat_densify_stats_merge alike.                               */
+int gsplat_densify_stats_abs(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state,
+                             const float* grad2d, float* stats, void* stream);
+int gsplat_frame_densify_stats_abs(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame,
+                                   int64_t frame_bytes, float* stats, void* stream);
 
 /* ---- per-Gaussian contribution statistics (not in the reference) ------------------------------------------------------------
  * How much does each Gaussian take part in the composite?  With the blending weight w_i(p) = alpha_i T_i [T_i > 5e-5] of Gaussian i

@@ -1,0 +1,134 @@
+"""The additive C ABI of the absolute-gradient statistic and its Python surface, without a GPU: the six new symbols
+exist and refuse bad arguments on the host under their own names, bit 7 (GSPLAT_BACKWARD_ABSGRAD) is known to the two composite
+backward entries and unknown to the two projection-backward entries, ops.densify_stats and TrainConfig refuse what they cannot do."""
+import ctypes as C
+import importlib
+
+import pytest
+import torch
+
+PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
+abi = importlib.import_module(PKG + "._abi")
+NEW = ("gsplat_rasterize_backward_abs", "gsplat_rasterize_backward_aux_abs", "gsplat_rasterize_backward_abs_scratch_bytes",
+       "gsplat_rasterize_backward_aux_abs_scratch_bytes", "gsplat_densify_stats_abs", "gsplat_frame_densify_stats_abs")
+
+
+def _refused(lib, status, name):
+    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, status)
+    assert name.encode() in lib.gsplat_last_error(), (name, lib.gsplat_last_error())
+
+
+def test_the_new_symbols_exist_and_the_version_stays():
+    lib = abi.lib()
+    for name in NEW:
+        assert name in abi.SIGNATURES and hasattr(lib, name)
+    assert lib.gsplat_abi_version() == 12 == abi.ABI_VERSION
+    assert abi.GSPLAT_BACKWARD_ABSGRAD == 128
+
+
+def test_scratch_sizes_have_rows_of_11_and_12():
+    lib = abi.lib()
+    n, p = 1000, 102_400                   # (p * 4 * row is a multiple of the carver's 256 bytes)
+    base = [lib.gsplat_rasterize_backward_scratch_bytes(n, q) for q in (p, 2 * p)]
+    for fn, row in ((lib.gsplat_rasterize_backward_abs_scratch_bytes, 11), (lib.gsplat_rasterize_backward_aux_abs_scratch_bytes, 12)):
+        a, b = fn(n, p), fn(n, 2 * p)
+        assert b - a == p * 4 * row and (base[1] - base[0]) == p * 4 * 9
+        assert a - p * 4 * row == base[0] - p * 4 * 9           # the rest of the scratch is the plain entry's
+
+
+def test_null_arguments_are_refused_under_the_entrys_own_name():
+    lib = abi.lib()
+    v = abi.make_view(64, 64, 50.0, 50.0, 32.0, 32.0)
+    bad = abi.make_view(0, 64, 50.0, 50.0, 32.0, 32.0)
+    buf = (C.c_float * 64)()
+    p = C.cast(buf, C.c_void_p)
+    odd = C.c_void_p(p.value + 4)
+
+    def rb(n=4, cap=8, view=C.byref(v), state=p, bins=p, accum=p, gi=p, g2d=p):
+        return lib.gsplat_rasterize_backward_abs(n, cap, view, state, bins, accum, gi, g2d, 0, None, 0, None)
+
+    def rba(n=4, cap=8, view=C.byref(v), state=p, bins=p, accum=p, aa=p, gi=p, g2d=p):
+        return lib.gsplat_rasterize_backward_aux_abs(n, cap, view, state, bins, accum, aa, gi, None, None, None, g2d, 0, None, 0, None)
+
+    for fn, name, ptrs in ((rb, "gsplat_rasterize_backward_abs", ("state", "bins", "accum", "gi", "g2d")),
+                           (rba, "gsplat_rasterize_backward_aux_abs", ("state", "bins", "accum", "aa", "g2d"))):
+        for k in ptrs:
+            _refused(lib, fn(**{k: None}), name)
+        _refused(lib, fn(view=None), name)
+        _refused(lib, fn(view=C.byref(bad)), name)
+        _refused(lib, fn(n=-1), name)
+        _refused(lib, fn(cap=-1), name)
+    _refused(lib, rba(gi=None), "gsplat_rasterize_backward_aux_abs")          # none of the three upstream gradients
+
+    def ds(n=4, cap=8, view=C.byref(v), state=p, g2d=p, stats=p):
+        return lib.gsplat_densify_stats_abs(n, cap, view, state, g2d, stats, None)
+
+    name = "gsplat_densify_stats_abs"
+    for kw in (dict(state=None), dict(g2d=None), dict(stats=None), dict(view=None), dict(view=C.byref(bad)), dict(n=-1), dict(cap=-1), dict(stats=odd)):
+        _refused(lib, ds(**kw), name)
+    assert ds(n=0) == abi.GSPLAT_OK
+
+    def fds(n=4, cap=8, view=C.byref(v), frame=None, nbytes=1 << 30, stats=p):
+        return lib.gsplat_frame_densify_stats_abs(n, cap, view, frame, nbytes, stats, None)
+
+    name = "gsplat_frame_densify_stats_abs"
+    aligned = C.c_void_p((p.value + 255) & ~255)
+    for kw in (dict(frame=None), dict(frame=aligned, stats=None), dict(frame=aligned, view=None), dict(frame=C.c_void_p(aligned.value + 16)),
+               dict(frame=aligned, nbytes=16), dict(frame=aligned, n=-1)):
+        _refused(lib, fds(**kw), name)
+    del buf
+
+
+def test_bit_7_is_known_to_the_composite_entries_only():
+    lib = abi.lib()
+    v = abi.make_view(64, 64, 50.0, 50.0, 32.0, 32.0)
+    bit = abi.GSPLAT_BACKWARD_ABSGRAD
+    assert lib.gsplat_backward(None, None, C.byref(v), None, 0, 0, None, None, None, None, 0, bit, None) == abi.GSPLAT_ERR_BAD_ARG
+    assert b"unknown flag" not in lib.gsplat_last_error()
+    group = abi.AdamGroup()
+    assert lib.gsplat_backward_adam_rest(None, None, C.byref(v), None, 0, 0, None, None, None, 0, bit, C.byref(group), 0.9, 0.999, 1e-15,
+                                         None) == abi.GSPLAT_ERR_BAD_ARG
+    assert b"unknown flag" not in lib.gsplat_last_error()
+    # with the projection phase alone the bit is accepted (and ignored): the call gets as far as its argument checks
+    assert lib.gsplat_backward(None, None, C.byref(v), None, 0, 0, None, None, None, None, 0, bit | abi.GSPLAT_BACKWARD_PHASE_PROJECT,
+                               None) == abi.GSPLAT_ERR_BAD_ARG
+    assert b"unknown flag" not in lib.gsplat_last_error()
+    assert lib.gsplat_project_backward(None, None, C.byref(v), None, None, None, bit, None) == abi.GSPLAT_ERR_BAD_ARG
+    assert b"unknown flag" in lib.gsplat_last_error()
+    assert lib.gsplat_project_backward_pose(None, None, C.byref(v), None, None, None, None, None, 0, bit, None) == abi.GSPLAT_ERR_BAD_ARG
+    assert b"unknown flag" in lib.gsplat_last_error()
+    for other in (1 << 5, 1 << 10, 1 << 25):             # still unknown everywhere
+        assert lib.gsplat_backward(None, None, C.byref(v), None, 0, 0, None, None, None, None, 0, other | bit, None) == abi.GSPLAT_ERR_BAD_ARG
+        assert b"unknown flag" in lib.gsplat_last_error()
+
+
+def test_densify_stats_refuses_an_absgrad_that_is_no_bool():
+    ops = importlib.import_module(PKG + ".ops")
+    rec = ops.DensifyStats(5, "cpu")
+    for bad in (1, 0, "yes", None, 1.0):
+        with pytest.raises(TypeError, match="absgrad"):
+            ops.densify_stats(rec, absgrad=bad)
+    assert ops._stats.get() is None and ops._stats_absgrad.get() is False
+    with ops.densify_stats(rec, absgrad=True):
+        assert ops._stats.get() is rec.data and ops._stats_absgrad.get() is True
+        with ops.densify_stats(rec):                      # a nested block has its own mode
+            assert ops._stats_absgrad.get() is False
+        assert ops._stats_absgrad.get() is True
+    assert ops._stats.get() is None and ops._stats_absgrad.get() is False
+    z = torch.zeros
+    with pytest.raises(RuntimeError, match="no CPU fallback"):            # the record fits: the render's own checks come next
+        with ops.densify_stats(rec, absgrad=True):
+            ops.render_gaussians(z(5, 3), z(5, 3), z(5, 45), z(5), z(5, 3), z(5, 4), torch.eye(4), 16, 16, 10., 10., 8., 8.)
+    assert ops._stats_absgrad.get() is False
+
+
+def test_train_config_wants_the_screen_rule():
+    training = importlib.import_module(PKG + ".training")
+    cfg = training.TrainConfig()
+    assert cfg.densify_absgrad is False and cfg.densify_grad_threshold == 0.0002
+    assert training.TrainConfig(densify_rule="screen", densify_absgrad=True).densify_grad_threshold == 0.0002
+    for rule in ("reference", "mcmc"):
+        with pytest.raises(ValueError, match="densify_absgrad"):
+            training.TrainConfig(densify_rule=rule, densify_absgrad=True)
+    with pytest.raises(ValueError, match="densify_absgrad"):
+        training.TrainConfig(densify_rule="screen", densify_absgrad=1)
