@@ -7,8 +7,9 @@
 using namespace gsm;
 namespace {
 
-// K10: the forward kernel's traversal (same lists, launch order, two pixels per lane, stage_chunk and the sub-tile queues, the same
-// alpha, the same T = T - alpha T, the same 16-entry alive poll) without colours and without an image.  What leaves the wave is,
+// K10: the forward kernel's traversal (same lists, launch order, two pixels per lane -- lane_pixels, fetch_candidate and stage_chunk
+// of gs_raster.h are K6's own -- the sub-tile queues, the same alpha, the same T = T - alpha T, the same 16-entry alive poll) without
+// colours and without an image.  What leaves the wave is,
 // per (list, Gaussian) pair, the blending weight w = alpha T [T > 5e-5] of the pair's <= 128 pixels as
 //     (sum of w, max of w, number of pixels with w > 0).
 // A record is one 16-byte row per Gaussian, four 32-bit words, every one an order-independent integer:
@@ -58,17 +59,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ra
     const uint2 rg = ranges[list];
     if (rg.x >= rg.y) return;
     raise_launch_priority(blockIdx.x, gridDim.x);
-    const int tx = list % lists_x, hy = list / lists_x;
-    const int grp = lane >> 3, j = lane & 7;
-    const int px = tx * LIST_W + (grp & 3) * 4 + (j & 3);
-    const int pya = hy * LIST_H + (grp >> 2) * 4 + (j >> 2), pyb = pya + 2;
-    const bool va = (px < W) && (pya < H), vb = (px < W) && (pyb < H);
-    const float fpx = (float)px;
-    const v2f fpy = {(float)pya, (float)pyb};
-    const float ox = (float)(tx * LIST_W), oy = (float)(hy * LIST_H);
-    v2f T = {va ? 1.0f : 0.0f, vb ? 1.0f : 0.0f};
+    const LanePixels lp = lane_pixels(list, lists_x, lane, H, W);
+    const int grp = lp.grp, j = lp.j;
+    const float fpx = lp.fpx;
+    const v2f fpy = lp.fpy;
+    v2f T = lp.T;
     const float chik = chi * QK;
-    bool alive_any = __any(va || vb);
+    bool alive_any = __any(lp.va || lp.vb);
     uint32_t base = rg.x;
     Candidate cand;
     if (alive_any) cand = fetch_candidate(lane, base, rg.y, ids, rec, id_max);
@@ -78,7 +75,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ra
     while (alive_any && base < rg.y) {
         uint32_t m8;
         uint64_t ranks;
-        const Staged sg = stage_chunk<MAXQ_CTB, 0, RasterLdsC, false>(s, cand, (int)min(rg.y - base, (uint32_t)CHUNK), lane, ox, oy, m8, ranks);
+        const Staged sg = stage_chunk<MAXQ_CTB, 0, RasterLdsC, false>(s, cand, (int)min(rg.y - base, (uint32_t)CHUNK), lane, lp.ox, lp.oy, m8, ranks);
         const int maxc = sg.maxc;
         const uint32_t my_id = cand.id;
         base += (uint32_t)sg.n;
@@ -94,7 +91,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ra
             g.x = __builtin_amdgcn_exp2f(q.x); g.y = __builtin_amdgcn_exp2f(q.y);
             v2f al = b.y * g;
             al.x = vmin(al.x, alpha_max); al.y = vmin(al.y, alpha_max);
-            al.x = (i0 && al.x >= alpha_cutoff && T.x > 5e-5f) ? al.x : 0.0f;               // the forward kernel's one select
+            al.x = (i0 && al.x >= alpha_cutoff && T.x > 5e-5f) ? al.x : 0.0f;               // the forward kernel's one select (copy: K6, K10 -- see there)
             al.y = (i1 && al.y >= alpha_cutoff && T.y > 5e-5f) ? al.y : 0.0f;
             const v2f w = al * T;
             T = T - al * T;
@@ -120,6 +117,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ra
         alive_any = __any(T.x > 5e-5f || T.y > 5e-5f);        // dead pixels stay dead
         __syncthreads();
         // entry `lane`: combine the slots of the sub-tiles it was queued in, in sub-tile order; one row per pair leaves the wave
+        // (copy: K7, K10 -- the loop over t, ranks and kdone)
         float tot = 0.0f, mx = 0.0f;
         uint32_t cnt = 0u;
 #pragma unroll

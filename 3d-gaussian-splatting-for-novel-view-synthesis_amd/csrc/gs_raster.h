@@ -222,6 +222,33 @@ __device__ __forceinline__ T lds_at(const T* base, uint32_t byte_off) {
     return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
 }
 
+// ---- the pieces K6, K7 and K10 (gs_contrib.h) share: ONE copy each, so that "the same traversal" is the same code ---------------
+// (with stage_chunk above.  Three pieces stay spelled out per kernel, because a shared copy changed the compiled kernels beyond
+//  register numbers and the order of a few prologue instructions: the two clock reads of the statistics, the
+//  alpha select of K6 / K10, and the slot combine of K7 / K10.  They are marked "(copy: ...)" where they stand.)
+
+// Which pixels does `lane` own in `list`?  Group grp = lane >> 3 owns sub-tile (grp & 3, grp >> 2), lane j of it the pixels (px, pya)
+// and (px, pyb = pya + 2); va / vb: inside the image; (ox, oy) = list origin; T = the initial transmittance (0 outside the image).
+struct LanePixels { int tx, hy, grp, j, px, pya, pyb; bool va, vb; float fpx; v2f fpy; float ox, oy; v2f T; };
+__device__ __forceinline__ LanePixels lane_pixels(uint32_t list, int lists_x, int lane, int H, int W) {
+    LanePixels p;
+    p.tx = list % lists_x; p.hy = list / lists_x;
+    p.grp = lane >> 3; p.j = lane & 7;
+    p.px = p.tx * LIST_W + (p.grp & 3) * 4 + (p.j & 3);
+    p.pya = p.hy * LIST_H + (p.grp >> 2) * 4 + (p.j >> 2); p.pyb = p.pya + 2;
+    p.va = (p.px < W) && (p.pya < H); p.vb = (p.px < W) && (p.pyb < H);
+    p.fpx = (float)p.px;
+    p.fpy = v2f{(float)p.pya, (float)p.pyb};
+    p.ox = (float)(p.tx * LIST_W); p.oy = (float)(p.hy * LIST_H);
+    p.T = v2f{p.va ? 1.0f : 0.0f, p.vb ? 1.0f : 0.0f};
+    return p;
+}
+
+// Per-wave statistics (K6, K7): the record lane 0 stores at the wave's end, from the two clocks the kernel read at its start.
+__device__ __forceinline__ WaveStats wave_stats_end(unsigned long long t_begin, unsigned long long t_real, uint2 rg, uint32_t chunks, uint32_t visited) {
+    return WaveStats{rg.y - rg.x, (chunks & 0xFFFu) | ((uint32_t)(__builtin_amdgcn_s_memrealtime() - t_real) << 12), visited, (uint32_t)(__builtin_amdgcn_s_memtime() - t_begin), (uint32_t)t_real, blockIdx.x | (xcc_id() << 24)};
+}
+
 // min as ONE v_min_f32 (fminf() first canonicalises a scalar operand with a v_max_f32 every time it is used; no NaNs here)
 // b is wave-uniform (a kernel argument): taken from its SGPR as src0, not copied to a VGPR first
 __device__ __forceinline__ float vmin(float a, float b) {
@@ -281,32 +308,28 @@ __global__ __launch_bounds__(64) void raster_forward_kernel(const uint2* __restr
         }
     }
     const uint32_t list = order[blockIdx.x];
-    const int tx = list % lists_x, hy = list / lists_x;
+    const LanePixels lp = lane_pixels(list, lists_x, lane, H, W);
     raise_launch_priority(blockIdx.x, gridDim.x);
-    const unsigned long long t_begin = stats ? __builtin_amdgcn_s_memtime() : 0ull;
+    const unsigned long long t_begin = stats ? __builtin_amdgcn_s_memtime() : 0ull;              // (copy: K6, K7)
     const unsigned long long t_real = stats ? __builtin_amdgcn_s_memrealtime() : 0ull;      // 100 MHz, one clock for the whole chip
     uint32_t st_chunks = 0, st_visited = 0;
-    const int grp = lane >> 3, j = lane & 7;
-    const int px = tx * LIST_W + (grp & 3) * 4 + (j & 3);
-    const int pya = hy * LIST_H + (grp >> 2) * 4 + (j >> 2), pyb = pya + 2;
-    const bool va = (px < W) && (pya < H), vb = (px < W) && (pyb < H);
-    const float fpx = (float)px;
-    const v2f fpy = {(float)pya, (float)pyb};
-    const float ox = (float)(tx * LIST_W), oy = (float)(hy * LIST_H);
-    v2f T = {va ? 1.0f : 0.0f, vb ? 1.0f : 0.0f};
+    const int px = lp.px;
+    const float fpx = lp.fpx;
+    const v2f fpy = lp.fpy;
+    v2f T = lp.T;
     v2f Cr = {0.f, 0.f}, Cg = {0.f, 0.f}, Cb = {0.f, 0.f};
     v2f Dz = {0.f, 0.f}, Aw = {0.f, 0.f};                    // (AUX) sum w z, sum w
     const uint2 rg = ranges[list];
     const float chik = chi * QK;
-    bool alive_any = __any(va || vb);
+    bool alive_any = __any(lp.va || lp.vb);
     uint32_t base = rg.x;
     Candidate cand;
     if (alive_any && base < rg.y) cand = fetch_candidate(lane, base, rg.y, ids, rec, id_max);
-    const uint16_t* myq = &s.q[grp][0];
+    const uint16_t* myq = &s.q[lp.grp][0];
     while (alive_any && base < rg.y) {
         uint32_t m8;
         uint64_t ranks;
-        const int maxc = stage_chunk<CHUNK, SAVE ? 1 : 0, RasterLds, AUX>(s, cand, (int)min(rg.y - base, (uint32_t)CHUNK), lane, ox, oy, m8, ranks, chi * 1.001f + 1e-4f).maxc;
+        const int maxc = stage_chunk<CHUNK, SAVE ? 1 : 0, RasterLds, AUX>(s, cand, (int)min(rg.y - base, (uint32_t)CHUNK), lane, lp.ox, lp.oy, m8, ranks, chi * 1.001f + 1e-4f).maxc;
         if (SAVE && base + (uint32_t)lane < rg.y) pair_mask[base + lane] = (uint8_t)m8;     // 64 contiguous bytes per chunk
         base += CHUNK;
         if (base < rg.y) cand = fetch_candidate(lane, base, rg.y, ids, rec, id_max);   // in flight during the loop below
@@ -334,6 +357,7 @@ __global__ __launch_bounds__(64) void raster_forward_kernel(const uint2* __restr
             al1.x = vmin(al1.x, alpha_max); al1.y = vmin(al1.y, alpha_max);
             // alpha = 0 outside the chi-square clip, below the cutoff, and on a dead pixel (T <= 5e-5: the term is masked, and a dead
             // pixel stays dead whether or not its T keeps shrinking) -- ONE select for the three, and w = alpha T needs none
+            // (copy: K6, K10 -- from a shared helper the compiler swaps the operands of the loop's s_and_b64 in both kernels)
             al0.x = (i00 && al0.x >= alpha_cutoff && T.x > 5e-5f) ? al0.x : 0.0f;
             al0.y = (i01 && al0.y >= alpha_cutoff && T.y > 5e-5f) ? al0.y : 0.0f;
             const v2f w0 = al0 * T;
@@ -354,30 +378,23 @@ __global__ __launch_bounds__(64) void raster_forward_kernel(const uint2* __restr
         }
         alive_any = __any(T.x > 5e-5f || T.y > 5e-5f);        // dead pixels stay dead
     }
-    if (stats && lane == 0)
-        stats[list] = WaveStats{rg.y - rg.x, (st_chunks & 0xFFFu) | ((uint32_t)(__builtin_amdgcn_s_memrealtime() - t_real) << 12), st_visited, (uint32_t)(__builtin_amdgcn_s_memtime() - t_begin), (uint32_t)t_real, blockIdx.x | (xcc_id() << 24)};
-    // one pixel: the clamped colour, and (a backward pass will follow) the colour before the clamp
-    const auto put = [&](int py, float r, float g, float b) {
-        const int64_t o = ((int64_t)py * W + px) * 3;
-        image[o + 0] = fminf(fmaxf(r, 0.0f), 1.0f); image[o + 1] = fminf(fmaxf(g, 0.0f), 1.0f); image[o + 2] = fminf(fmaxf(b, 0.0f), 1.0f);
-        if (accum) { accum[o + 0] = r; accum[o + 1] = g; accum[o + 2] = b; }
-    };
-    if (!AUX) {
-        if (va) put(pya, Cr.x, Cg.x, Cb.x);
-        if (vb) put(pyb, Cr.y, Cg.y, Cb.y);
-        return;
-    }
-    // (AUX) one pixel: the colour over the background, clamped; depth and opacity as they are; for a backward pass C, D, A unclamped
-    const auto put_aux = [&](int py, float r, float g, float b, float d, float a) {
+    if (stats && lane == 0) stats[list] = wave_stats_end(t_begin, t_real, rg, st_chunks, st_visited);
+    // One pixel: the clamped colour, and (a backward pass will follow) the colour before the clamp.  AUX: the colour lies over the
+    // background before the clamp; depth and opacity as they are; for a backward pass C, D, A unclamped.
+    const auto put = [&](int py, float r, float g, float b, float d, float a) {
         const int64_t p = (int64_t)py * W + px, o = p * 3;
-        if (accum) { accum[o + 0] = r; accum[o + 1] = g; accum[o + 2] = b; aux.accum_aux[p * 2] = d; aux.accum_aux[p * 2 + 1] = a; }
-        if (aux.has_bg) { r = over_background(r, a, aux.bg[0]); g = over_background(g, a, aux.bg[1]); b = over_background(b, a, aux.bg[2]); }
+        if constexpr (AUX) {
+            if (accum) { accum[o + 0] = r; accum[o + 1] = g; accum[o + 2] = b; aux.accum_aux[p * 2] = d; aux.accum_aux[p * 2 + 1] = a; }
+            if (aux.has_bg) { r = over_background(r, a, aux.bg[0]); g = over_background(g, a, aux.bg[1]); b = over_background(b, a, aux.bg[2]); }
+        }
         image[o + 0] = fminf(fmaxf(r, 0.0f), 1.0f); image[o + 1] = fminf(fmaxf(g, 0.0f), 1.0f); image[o + 2] = fminf(fmaxf(b, 0.0f), 1.0f);
-        if (aux.depth) aux.depth[p] = d;
-        if (aux.alpha) aux.alpha[p] = a;
+        if constexpr (AUX) {
+            if (aux.depth) aux.depth[p] = d;
+            if (aux.alpha) aux.alpha[p] = a;
+        } else if (accum) { accum[o + 0] = r; accum[o + 1] = g; accum[o + 2] = b; }     // (plain: accum AFTER image on purpose -- the parent's instruction order)
     };
-    if (va) put_aux(pya, Cr.x, Cg.x, Cb.x, Dz.x, Aw.x);
-    if (vb) put_aux(pyb, Cr.y, Cg.y, Cb.y, Dz.y, Aw.y);
+    if (lp.va) put(lp.pya, Cr.x, Cg.x, Cb.x, Dz.x, Aw.x);
+    if (lp.vb) put(lp.pyb, Cr.y, Cg.y, Cb.y, Dz.y, Aw.y);
 }
 
 // x + y of a two-pixel value as ONE v_add_f32 the SLP vectoriser cannot see: left to itself it pairs these horizontal adds
@@ -461,7 +478,8 @@ static_assert(sizeof(RasterLdsBwd<true, 10>) <= 12800, "the depth / opacity back
 static_assert(sizeof(RasterLdsBwd<true, 11>) <= 12800, "the absolute-gradient backward kernel's LDS per wave: 12 waves per CU");
 static_assert(sizeof(RasterLdsBwd<true, 12>) > 12800 && sizeof(RasterLdsBwd<true, 12>) <= 14080, "absolute-gradient + depth / opacity: 11 pieces of 1280 B, 11 waves per CU");
 
-// K7: same traversal as K6 (identical T_i and alive decisions).  For pixel p and Gaussian i:
+// K7: same traversal as K6 (identical T_i and alive decisions: lane_pixels, fetch_candidate and stage_chunk are K6's).  For pixel p
+// and Gaussian i:
 //   d alpha_i = alive_i T_i (c_i . Gc) - (sum_{k>i} w_k (c_k . Gc)) / (1 - alpha_i),
 // the suffix sum being (total - running prefix), total = Gc . C_unclamped, Gc = dL/dO masked by the output clamp.
 // Every group reduces its Gaussian's nine sums over its 8 lanes (reduce-scatter: 8 Gaussians at once in the same
@@ -473,7 +491,7 @@ static_assert(sizeof(RasterLdsBwd<true, 12>) > 12800 && sizeof(RasterLdsBwd<true
 // in the Gaussian's own rectangle), and pair_reduce_kernel adds each Gaussian's rows in that fixed order: bitwise
 // reproducible (the sums inside a wave are already in a fixed order).
 struct DetArgs {
-    const u2* rect; const uint32_t* mask; const uint32_t* tiles; const uint32_t* pair_base;
+    const u2* rect; const uint32_t* mask; const uint32_t* tiles; const uint32_t* pair_base;      // (tiles: read by nothing in K7; kept, so the arguments behind it stay where they are -- to go with a change that re-runs the ISA comparison anyway)
     float* part;             // [pair capacity][9] ([10] for the depth / opacity variant)
     uint32_t capacity;
 };
@@ -527,69 +545,48 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((AUX || ABS)
     const uint2 rg = ranges[list];
     if (rg.x >= rg.y) return;
     raise_launch_priority(blockIdx.x, gridDim.x);
-    const unsigned long long t_begin = stats ? __builtin_amdgcn_s_memtime() : 0ull;
+    const unsigned long long t_begin = stats ? __builtin_amdgcn_s_memtime() : 0ull;              // (copy: K6, K7)
     const unsigned long long t_real = stats ? __builtin_amdgcn_s_memrealtime() : 0ull;      // 100 MHz, one clock for the whole chip
     uint32_t st_chunks = 0, st_visited = 0;
-    const int tx = list % lists_x, hy = list / lists_x;
-    const int grp = lane >> 3, j = lane & 7;
-    const int px = tx * LIST_W + (grp & 3) * 4 + (j & 3);
-    const int pya = hy * LIST_H + (grp >> 2) * 4 + (j >> 2), pyb = pya + 2;
-    const bool va = (px < W) && (pya < H), vb = (px < W) && (pyb < H);
-    const float fpx = (float)px;
-    const v2f fpy = {(float)pya, (float)pyb};
-    const float ox = (float)(tx * LIST_W), oy = (float)(hy * LIST_H);
-    v2f T = {va ? 1.0f : 0.0f, vb ? 1.0f : 0.0f};
-    v2f Gr = {0.f, 0.f}, Gg = {0.f, 0.f}, Gb = {0.f, 0.f}, suffix = {0.f, 0.f};
-    v2f Gd = {0.f, 0.f}, Ga = {0.f, 0.f};          // (AUX) dL/dD, dL/dA - sum_c G_c bg_c
-    if (AUX) {
-        float g[2][5] = {{0.f, 0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f, 0.f}}, sfx[2] = {0.f, 0.f};
-        const bool vv[2] = {va, vb};
-        const int py[2] = {pya, pyb};
+    const LanePixels lp = lane_pixels(list, lists_x, lane, H, W);
+    const int tx = lp.tx, hy = lp.hy, grp = lp.grp, j = lp.j;
+    const float fpx = lp.fpx;
+    const v2f fpy = lp.fpy;
+    v2f T = lp.T;
+    // Upstream gradients of the lane's two pixels: g = (Gr, Gg, Gb, G_D, G_A - sum_c G_c bg_c), the last two AUX only, and the suffix
+    // sum's start sfx = G+ . (C, D, A).  clamp(x, 0, 1) passes the gradient where 0 <= x <= 1 (render.py:410): x = C, or (AUX) what the
+    // forward clamped, C over the background; gimg may be NULL in AUX only.
+    float g[2][5] = {}, sfx[2] = {0.f, 0.f};
+    const bool vv[2] = {lp.va, lp.vb};
+    const int py[2] = {lp.pya, lp.pyb};
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            if (vv[k]) {
-                const int64_t p = (int64_t)py[k] * W + px, o = p * 3;
-                const float D = aux.accum_aux[p * 2], A = aux.accum_aux[p * 2 + 1];
+    for (int k = 0; k < 2; ++k) {
+        if (vv[k]) {
+            const int64_t p = (int64_t)py[k] * W + lp.px, o = p * 3;
+            float D = 0.f, A = 0.f;                               // (AUX) the pixel's depth and opacity sums from the forward pass
+            if constexpr (AUX) {
+                D = aux.accum_aux[p * 2]; A = aux.accum_aux[p * 2 + 1];
                 g[k][3] = aux.gdepth ? aux.gdepth[p] : 0.0f;
                 g[k][4] = aux.galpha ? aux.galpha[p] : 0.0f;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float cu = accum[o + c];
-                    const float shown = aux.has_bg ? over_background(cu, A, aux.bg[c]) : cu;       // what the forward clamped
-                    const float gv = (gimg && shown >= 0.0f && shown <= 1.0f) ? gimg[o + c] : 0.0f;
-                    g[k][c] = gv;
-                    sfx[k] += gv * cu;
-                    if (aux.has_bg) g[k][4] -= gv * aux.bg[c];
-                }
-                sfx[k] += g[k][3] * D + g[k][4] * A;
             }
-        }
-        Gr = v2f{g[0][0], g[1][0]}; Gg = v2f{g[0][1], g[1][1]}; Gb = v2f{g[0][2], g[1][2]};
-        Gd = v2f{g[0][3], g[1][3]}; Ga = v2f{g[0][4], g[1][4]};
-        suffix = v2f{sfx[0], sfx[1]};
-    } else {
-        float g[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}}, sfx[2] = {0.f, 0.f};
-        const bool vv[2] = {va, vb};
-        const int py[2] = {pya, pyb};
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            if (vv[k]) {
-                const int64_t o = ((int64_t)py[k] * W + px) * 3;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float cu = accum[o + c];
-                    // clamp(C, 0, 1) passes the gradient where 0 <= C <= 1 (render.py:410)
-                    const float gv = (cu >= 0.0f && cu <= 1.0f) ? gimg[o + c] : 0.0f;
-                    g[k][c] = gv;
-                    sfx[k] += gv * cu;
-                }
+            for (int c = 0; c < 3; ++c) {
+                const float cu = accum[o + c];
+                float shown = cu;                                 // what the forward clamped
+                if constexpr (AUX) { if (aux.has_bg) shown = over_background(cu, A, aux.bg[c]); }
+                const float gv = ((!AUX || gimg) && shown >= 0.0f && shown <= 1.0f) ? gimg[o + c] : 0.0f;
+                g[k][c] = gv;
+                sfx[k] += gv * cu;
+                if constexpr (AUX) { if (aux.has_bg) g[k][4] -= gv * aux.bg[c]; }
             }
+            if constexpr (AUX) sfx[k] += g[k][3] * D + g[k][4] * A;
         }
-        Gr = v2f{g[0][0], g[1][0]}; Gg = v2f{g[0][1], g[1][1]}; Gb = v2f{g[0][2], g[1][2]};
-        suffix = v2f{sfx[0], sfx[1]};
     }
+    const v2f Gr = {g[0][0], g[1][0]}, Gg = {g[0][1], g[1][1]}, Gb = {g[0][2], g[1][2]};
+    const v2f Gd = {g[0][3], g[1][3]}, Ga = {g[0][4], g[1][4]};          // (AUX; else 0) dL/dD, dL/dA - sum_c G_c bg_c
+    v2f suffix = {sfx[0], sfx[1]};
     const float chik = chi * QK, amax = alpha_max;
-    bool alive_any = __any(va || vb);
+    bool alive_any = __any(lp.va || lp.vb);
     uint32_t base = rg.x;
     Candidate cand;
     if (alive_any) cand = fetch_candidate(lane, base, rg.y, ids, rec, id_max, pair_mask);
@@ -600,7 +597,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((AUX || ABS)
     while (alive_any && base < rg.y) {
         uint32_t m8;
         uint64_t ranks;
-        const Staged sg = stage_chunk<MAXQ_BWD, 2, RasterLdsB, AUX>(s, cand, (int)min(rg.y - base, (uint32_t)CHUNK), lane, ox, oy, m8, ranks);
+        const Staged sg = stage_chunk<MAXQ_BWD, 2, RasterLdsB, AUX>(s, cand, (int)min(rg.y - base, (uint32_t)CHUNK), lane, lp.ox, lp.oy, m8, ranks);
         const int n = sg.n, maxc = sg.maxc;
         sb.eid[lane] = cand.id;
         base += (uint32_t)n;
@@ -698,7 +695,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((AUX || ABS)
         }
         alive_any = __any(T.x > 5e-5f || T.y > 5e-5f);        // dead pixels stay dead
         __syncthreads();
-        {   // entry `lane`: add up the slots of the sub-tiles it was queued in
+        {   // entry `lane`: add up the slots of the sub-tiles it was queued in  (copy: K7, K10 -- the loop over t, ranks and kdone)
             float tot[NS];
 #pragma unroll
             for (int v = 0; v < NS; ++v) tot[v] = 0.f;
@@ -718,7 +715,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((AUX || ABS)
         if (DET && lane < n) {       // entry `lane`: its row's slot = first slot of its Gaussian + ordinal of this list in its rectangle
             const uint32_t id = sb.eid[lane];
             const u2 rc = det.rect[id];
-            const uint32_t mk = det.mask[id], nt = det.tiles[id];
+            const uint32_t mk = det.mask[id];
             const int x0 = (int)(rc.x & 0xFFFFu), y0 = (int)(rc.x >> 16), x1 = (int)(rc.y & 0xFFFFu);
             const uint32_t bit = (uint32_t)((hy - y0) * (x1 - x0 + 1) + (tx - x0));          // row-major, like for_each_list
             uint32_t ord;
@@ -736,7 +733,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((AUX || ABS)
             } else {
                 ord = (uint32_t)__popc(mk & ((1u << (bit & 31u)) - 1u));
             }
-            (void)nt;
             sb.eslot[lane] = det.pair_base[id] + ord;
         }
         __syncthreads();
@@ -754,8 +750,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((AUX || ABS)
             }
         }
     }
-    if (stats && lane == 0)
-        stats[list] = WaveStats{rg.y - rg.x, (st_chunks & 0xFFFu) | ((uint32_t)(__builtin_amdgcn_s_memrealtime() - t_real) << 12), st_visited, (uint32_t)(__builtin_amdgcn_s_memtime() - t_begin), (uint32_t)t_real, blockIdx.x | (xcc_id() << 24)};
+    if (stats && lane == 0) stats[list] = wave_stats_end(t_begin, t_real, rg, st_chunks, st_visited);
 }
 
 // ---- deterministic mode: slots of the (list, Gaussian) rows and their fixed-order sum ------------------------------------

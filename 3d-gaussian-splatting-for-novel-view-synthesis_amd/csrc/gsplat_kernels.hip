@@ -254,6 +254,17 @@ void set_background(Aux& a, const float* background) {
 // K7 and (deterministic mode) the kernels around it, for gsplat_rasterize_backward and gsplat_rasterize_backward_aux (aux: the
 // depth / opacity variant, rows of 10) and their _abs twins (abs: the absolute-gradient sums in columns 10-11, rows of 11 and 12).
 constexpr int raster_row(bool aux, bool abs) { return (aux ? 10 : 9) + (abs ? 2 : 0); }
+auto raster_backward_kernel_for(bool det, bool aux, bool abs) {
+    return abs ? (aux ? (det ? raster_backward_kernel<true, true, true> : raster_backward_kernel<false, true, true>)
+                      : (det ? raster_backward_kernel<true, false, true> : raster_backward_kernel<false, false, true>))
+               : (aux ? (det ? raster_backward_kernel<true, true> : raster_backward_kernel<false, true>)
+                      : (det ? raster_backward_kernel<true> : raster_backward_kernel<false>));
+}
+const char* raster_backward_name(bool det, bool aux, bool abs) {       // (the _abs launches never named their deterministic twin)
+    return abs ? (aux ? "raster_backward_kernel<aux, abs>" : "raster_backward_kernel<abs>")
+               : (aux ? (det ? "raster_backward_kernel<deterministic, aux>" : "raster_backward_kernel<aux>")
+                      : (det ? "raster_backward_kernel<deterministic>" : "raster_backward_kernel"));
+}
 int raster_backward_impl(int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, const void* bin_state,
                          const float* accum, const float* grad_image, float* grad2d, int32_t grad2d_zeroed, void* det_scratch,
                          int64_t det_scratch_bytes, void* stream_, const AuxBwd* aux, bool abs = false) {
@@ -276,30 +287,73 @@ int raster_backward_impl(int64_t n, int64_t n_binned, const gsplat_view* v, cons
         LAUNCH("pair_base_kernel", pair_base_kernel, dim3(pb_blocks), dim3(256), 0, st, n, ps.tiles, ds.block_sum, ds.pair_base);
     }
     const DetArgs da = det ? DetArgs{ps.rect, ps.mask, ps.tiles, ds.pair_base, ds.part, (uint32_t)n_binned} : DetArgs{};
-    if (abs) {
-        const auto kernel = aux ? (det ? raster_backward_kernel<true, true, true> : raster_backward_kernel<false, true, true>)
-                                : (det ? raster_backward_kernel<true, false, true> : raster_backward_kernel<false, false, true>);
-        LAUNCH(aux ? "raster_backward_kernel<aux, abs>" : "raster_backward_kernel<abs>", kernel, dim3((unsigned)nl), dim3(64), 0, st, ps.ranges,
-               (const uint32_t*)bin_state, ps.rec, ps.order, vk.lists_x, vk.H, vk.W, vk.chi_clip, vk.alpha_max, vk.alpha_cutoff,
-               accum, grad_image, grad2d, STATS_BWD, (uint32_t)(n - 1), da, pair_mask_of(bin_state, n_binned), aux ? *aux : AuxBwd{});
-        if (det) {
-            LAUNCH("pair_reduce_kernel<abs>", (aux ? pair_reduce_kernel<12> : pair_reduce_kernel<11, true>), dim3(blocks256(n)), dim3(256), 0, st, n, ps.tiles, ds.pair_base, ds.part,
-                   (uint32_t)n_binned, grad2d);
-        }
-        return GSPLAT_OK;
-    }
-    if (aux) {
-        LAUNCH(det ? "raster_backward_kernel<deterministic, aux>" : "raster_backward_kernel<aux>", (det ? raster_backward_kernel<true, true> : raster_backward_kernel<false, true>),
-               dim3((unsigned)nl), dim3(64), 0, st, ps.ranges, (const uint32_t*)bin_state, ps.rec, ps.order, vk.lists_x, vk.H, vk.W, vk.chi_clip,
-               vk.alpha_max, vk.alpha_cutoff, accum, grad_image, grad2d, STATS_BWD, (uint32_t)(n - 1), da, pair_mask_of(bin_state, n_binned), *aux);
-    } else {
-        LAUNCH(det ? "raster_backward_kernel<deterministic>" : "raster_backward_kernel", det ? raster_backward_kernel<true> : raster_backward_kernel<false>, dim3((unsigned)nl), dim3(64), 0, st, ps.ranges,
-               (const uint32_t*)bin_state, ps.rec, ps.order, vk.lists_x, vk.H, vk.W, vk.chi_clip, vk.alpha_max, vk.alpha_cutoff,
-               accum, grad_image, grad2d, STATS_BWD, (uint32_t)(n - 1), da, pair_mask_of(bin_state, n_binned), AuxBwd{});
-    }
+    const bool a = aux != nullptr;
+    LAUNCH(raster_backward_name(det, a, abs), raster_backward_kernel_for(det, a, abs), dim3((unsigned)nl), dim3(64), 0, st, ps.ranges,
+           (const uint32_t*)bin_state, ps.rec, ps.order, vk.lists_x, vk.H, vk.W, vk.chi_clip, vk.alpha_max, vk.alpha_cutoff,
+           accum, grad_image, grad2d, STATS_BWD, (uint32_t)(n - 1), da, pair_mask_of(bin_state, n_binned), a ? *aux : AuxBwd{});
     if (det) {
-        LAUNCH("pair_reduce_kernel", aux ? pair_reduce_kernel<10> : pair_reduce_kernel<9>, dim3(blocks256(n)), dim3(256), 0, st, n, ps.tiles, ds.pair_base, ds.part, (uint32_t)n_binned, grad2d);
+        const auto reduce = abs ? (a ? pair_reduce_kernel<12> : pair_reduce_kernel<11, true>) : (a ? pair_reduce_kernel<10> : pair_reduce_kernel<9>);
+        LAUNCH(abs ? "pair_reduce_kernel<abs>" : "pair_reduce_kernel", reduce, dim3(blocks256(n)), dim3(256), 0, st, n, ps.tiles, ds.pair_base, ds.part,
+               (uint32_t)n_binned, grad2d);
     }
+    return GSPLAT_OK;
+}
+
+// a refusal of an entry whose messages name it (name given), or of one of the older entries, whose messages do not (name == NULL)
+int refuse(const char* name, const char* msg) { return name ? fail(GSPLAT_ERR_BAD_ARG, "%s: %s", name, msg) : fail(GSPLAT_ERR_BAD_ARG, "%s", msg); }
+
+// The four gsplat_rasterize_backward* entries behind their checks.  name: the entries whose refusals name them (they check n / n_binned,
+// too); aux: the two depth / opacity entries, which read accum_aux ... background and may leave grad_image out; abs: the ABS kernels.
+int raster_backward_entry(const char* name, bool aux, bool abs, int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, const void* bin_state,
+                          const float* accum, const float* accum_aux, const float* grad_image, const float* grad_depth, const float* grad_alpha,
+                          const float* background, float* grad2d, int32_t grad2d_zeroed, void* det_scratch, int64_t det_scratch_bytes, void* stream_) {
+    if (name) {
+        if (!v) return refuse(name, "view is NULL");
+        if (check_view(v)) return refuse(name, "bad view (image size, tile size)");
+        if (n < 0 || n > (int64_t)ID_MASK + 1 || n_binned < 0 || n_binned > 0xFFFFFFFFLL) return refuse(name, "n / pair_capacity out of range");
+    } else if (int rc = check_view(v)) {
+        return rc;
+    }
+    if (aux && !grad_image && !grad_depth && !grad_alpha) return refuse(name, "grad_image, grad_depth and grad_alpha are all NULL");
+    if (!project_state || !bin_state || !accum || (aux ? !accum_aux : !grad_image) || !grad2d) return refuse(name, "NULL argument");
+    AuxBwd ab = {accum_aux, grad_depth, grad_alpha, {0.f, 0.f, 0.f}, 0};
+    if (aux) set_background(ab, background);
+    return raster_backward_impl(n, n_binned, v, project_state, bin_state, accum, grad_image, grad2d, grad2d_zeroed, det_scratch, det_scratch_bytes,
+                                stream_, aux ? &ab : nullptr, abs);
+}
+
+// K6 for gsplat_rasterize_forward and gsplat_rasterize_forward_aux (aux: depth, alpha and accum_aux are read, and the background)
+int raster_forward_impl(bool aux, int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, void* bin_state, float* image, float* depth,
+                        float* alpha, float* accum, float* accum_aux, float* grad2d, const float* background, void* stream_) {
+    int rc = check_view(v);
+    if (rc) return rc;
+    if (!project_state || !bin_state || !image) return fail(GSPLAT_ERR_BAD_ARG, "state / image is NULL");
+    if (aux && !accum != !accum_aux) return fail(GSPLAT_ERR_BAD_ARG, "accum and accum_aux go together");
+    const Ctx c = open_ctx(n, v, project_state, stream_);
+    AuxFwd af = {depth, alpha, accum_aux, {0.f, 0.f, 0.f}, 0};
+    if (aux) set_background(af, background);
+    // accum given = a backward pass will follow: exact sub-tile masks, saved per pair
+    const auto kernel = aux ? (accum ? raster_forward_kernel<true, true> : raster_forward_kernel<false, true>)
+                            : (accum ? raster_forward_kernel<true> : raster_forward_kernel<false>);
+    LAUNCH(aux ? "raster_forward_kernel<aux>" : "raster_forward_kernel", kernel, dim3((unsigned)c.nl), dim3(64), 0, c.st, c.ps.ranges,
+           (const uint32_t*)bin_state, c.ps.rec, c.ps.order, c.vk.lists_x, c.vk.H, c.vk.W, c.vk.chi_clip, c.vk.alpha_max, c.vk.alpha_cutoff,
+           image, accum, STATS_FWD, (uint32_t)(n > 0 ? n - 1 : 0), grad2d, grad2d ? n : 0,
+           accum ? pair_mask_of(bin_state, n_binned) : nullptr, af);
+    return GSPLAT_OK;
+}
+
+// The preamble of an entry that reads a finished frame arena (every message names the entry): the view, n / pair_capacity, the
+// arguments, the arena's alignment, and its size by frame_parts(flags) -- hint: how "frame arena too small" ends.
+// (gsplat_forward_deferred and the backward entries check other things in another order, with messages of their own: not through here.)
+int open_frame(const char* name, int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame, int64_t frame_bytes, const void* out,
+               int32_t flags, const char* hint, FrameParts* f) {
+    if (!v) return refuse(name, "view is NULL");
+    if (check_view(v)) return refuse(name, "bad view (image size, tile size)");
+    if (n < 0 || pair_capacity < 0) return refuse(name, "n / pair_capacity out of range");
+    if (!frame || !out) return refuse(name, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(frame) & 255u) return refuse(name, "frame must be 256-byte aligned");
+    *f = frame_parts(n, pair_capacity, v, flags);
+    if (f->total > frame_bytes) return fail(GSPLAT_ERR_BAD_ARG, "%s: frame arena too small%s", name, hint);
     return GSPLAT_OK;
 }
 
@@ -524,89 +578,44 @@ int gsplat_bin(int64_t n, int64_t pair_capacity, const gsplat_view* v, const voi
 
 int gsplat_rasterize_forward(int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, void* bin_state,
                              float* image, float* accum, float* grad2d, void* stream_) {
-    int rc = check_view(v);
-    if (rc) return rc;
-    if (!project_state || !bin_state || !image) return fail(GSPLAT_ERR_BAD_ARG, "state / image is NULL");
-    const Ctx c = open_ctx(n, v, project_state, stream_);
-    // accum given = a backward pass will follow: exact sub-tile masks, saved per pair
-    LAUNCH("raster_forward_kernel", accum ? raster_forward_kernel<true> : raster_forward_kernel<false>, dim3((unsigned)c.nl), dim3(64), 0, c.st, c.ps.ranges,
-           (const uint32_t*)bin_state, c.ps.rec, c.ps.order, c.vk.lists_x, c.vk.H, c.vk.W, c.vk.chi_clip, c.vk.alpha_max, c.vk.alpha_cutoff,
-           image, accum, STATS_FWD, (uint32_t)(n > 0 ? n - 1 : 0), grad2d, grad2d ? n : 0,
-           accum ? pair_mask_of(bin_state, n_binned) : nullptr, AuxFwd{});
-    return GSPLAT_OK;
+    return raster_forward_impl(false, n, n_binned, v, project_state, bin_state, image, nullptr, nullptr, accum, nullptr, grad2d, nullptr, stream_);
 }
 
 int gsplat_rasterize_forward_aux(int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, void* bin_state,
                                  float* image, float* depth, float* alpha, float* accum, float* accum_aux, float* grad2d,
                                  const float* background, void* stream_) {
-    int rc = check_view(v);
-    if (rc) return rc;
-    if (!project_state || !bin_state || !image) return fail(GSPLAT_ERR_BAD_ARG, "state / image is NULL");
-    if (!accum != !accum_aux) return fail(GSPLAT_ERR_BAD_ARG, "accum and accum_aux go together");
-    const Ctx c = open_ctx(n, v, project_state, stream_);
-    AuxFwd aux = {depth, alpha, accum_aux, {0.f, 0.f, 0.f}, 0};
-    set_background(aux, background);
-    LAUNCH("raster_forward_kernel<aux>", (accum ? raster_forward_kernel<true, true> : raster_forward_kernel<false, true>), dim3((unsigned)c.nl), dim3(64), 0, c.st,
-           c.ps.ranges, (const uint32_t*)bin_state, c.ps.rec, c.ps.order, c.vk.lists_x, c.vk.H, c.vk.W, c.vk.chi_clip, c.vk.alpha_max,
-           c.vk.alpha_cutoff, image, accum, STATS_FWD, (uint32_t)(n > 0 ? n - 1 : 0), grad2d, grad2d ? n : 0,
-           accum ? pair_mask_of(bin_state, n_binned) : nullptr, aux);
-    return GSPLAT_OK;
+    return raster_forward_impl(true, n, n_binned, v, project_state, bin_state, image, depth, alpha, accum, accum_aux, grad2d, background, stream_);
 }
 
 int gsplat_rasterize_backward(int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, const void* bin_state,
                               const float* accum, const float* grad_image, float* grad2d, int32_t grad2d_zeroed,
                               void* det_scratch, int64_t det_scratch_bytes, void* stream_) {
-    int rc = check_view(v);
-    if (rc) return rc;
-    if (!project_state || !bin_state || !accum || !grad_image || !grad2d) return fail(GSPLAT_ERR_BAD_ARG, "NULL argument");
-    return raster_backward_impl(n, n_binned, v, project_state, bin_state, accum, grad_image, grad2d, grad2d_zeroed, det_scratch, det_scratch_bytes,
-                                stream_, nullptr);
+    return raster_backward_entry(nullptr, false, false, n, n_binned, v, project_state, bin_state, accum, nullptr, grad_image, nullptr, nullptr, nullptr, grad2d,
+                                 grad2d_zeroed, det_scratch, det_scratch_bytes, stream_);
 }
 
 int gsplat_rasterize_backward_aux(int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, const void* bin_state,
                                   const float* accum, const float* accum_aux, const float* grad_image, const float* grad_depth,
                                   const float* grad_alpha, const float* background, float* grad2d, int32_t grad2d_zeroed,
                                   void* det_scratch, int64_t det_scratch_bytes, void* stream_) {
-    int rc = check_view(v);
-    if (rc) return rc;
-    if (!grad_image && !grad_depth && !grad_alpha) return fail(GSPLAT_ERR_BAD_ARG, "grad_image, grad_depth and grad_alpha are all NULL");
-    if (!project_state || !bin_state || !accum || !accum_aux || !grad2d) return fail(GSPLAT_ERR_BAD_ARG, "NULL argument");
-    AuxBwd aux = {accum_aux, grad_depth, grad_alpha, {0.f, 0.f, 0.f}, 0};
-    set_background(aux, background);
-    return raster_backward_impl(n, n_binned, v, project_state, bin_state, accum, grad_image, grad2d, grad2d_zeroed, det_scratch, det_scratch_bytes,
-                                stream_, &aux);
+    return raster_backward_entry(nullptr, true, false, n, n_binned, v, project_state, bin_state, accum, accum_aux, grad_image, grad_depth, grad_alpha, background,
+                                 grad2d, grad2d_zeroed, det_scratch, det_scratch_bytes, stream_);
 }
 
 // the _abs twins: the same arguments, the absolute-gradient sums beside the gradients; every refusal names the entry
-static int check_raster_abs(const char* name, int64_t n, int64_t n_binned, const gsplat_view* v) {
-    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
-    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
-    if (n < 0 || n > (int64_t)ID_MASK + 1 || n_binned < 0 || n_binned > 0xFFFFFFFFLL) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
-    return GSPLAT_OK;
-}
-
 int gsplat_rasterize_backward_abs(int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, const void* bin_state,
                                   const float* accum, const float* grad_image, float* grad2d, int32_t grad2d_zeroed,
                                   void* det_scratch, int64_t det_scratch_bytes, void* stream_) {
-    const char* name = "gsplat_rasterize_backward_abs";
-    if (int rc = check_raster_abs(name, n, n_binned, v)) return rc;
-    if (!project_state || !bin_state || !accum || !grad_image || !grad2d) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
-    return raster_backward_impl(n, n_binned, v, project_state, bin_state, accum, grad_image, grad2d, grad2d_zeroed, det_scratch, det_scratch_bytes,
-                                stream_, nullptr, true);
+    return raster_backward_entry("gsplat_rasterize_backward_abs", false, true, n, n_binned, v, project_state, bin_state, accum, nullptr, grad_image, nullptr, nullptr,
+                                 nullptr, grad2d, grad2d_zeroed, det_scratch, det_scratch_bytes, stream_);
 }
 
 int gsplat_rasterize_backward_aux_abs(int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, const void* bin_state,
                                       const float* accum, const float* accum_aux, const float* grad_image, const float* grad_depth,
                                       const float* grad_alpha, const float* background, float* grad2d, int32_t grad2d_zeroed,
                                       void* det_scratch, int64_t det_scratch_bytes, void* stream_) {
-    const char* name = "gsplat_rasterize_backward_aux_abs";
-    if (int rc = check_raster_abs(name, n, n_binned, v)) return rc;
-    if (!grad_image && !grad_depth && !grad_alpha) return fail(GSPLAT_ERR_BAD_ARG, "%s: grad_image, grad_depth and grad_alpha are all NULL", name);
-    if (!project_state || !bin_state || !accum || !accum_aux || !grad2d) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
-    AuxBwd aux = {accum_aux, grad_depth, grad_alpha, {0.f, 0.f, 0.f}, 0};
-    set_background(aux, background);
-    return raster_backward_impl(n, n_binned, v, project_state, bin_state, accum, grad_image, grad2d, grad2d_zeroed, det_scratch, det_scratch_bytes,
-                                stream_, &aux, true);
+    return raster_backward_entry("gsplat_rasterize_backward_aux_abs", true, true, n, n_binned, v, project_state, bin_state, accum, accum_aux, grad_image, grad_depth,
+                                 grad_alpha, background, grad2d, grad2d_zeroed, det_scratch, det_scratch_bytes, stream_);
 }
 
 int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const gsplat_view* v, const void* project_state,
@@ -793,13 +802,8 @@ int gsplat_densify_stats_abs(int64_t n, int64_t pair_capacity, const gsplat_view
 
 static int frame_densify_stats_impl(const char* name, int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame, int64_t frame_bytes,
                                     float* stats, void* stream_, bool abs) {
-    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
-    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
-    if (n < 0 || pair_capacity < 0) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
-    if (!frame || !stats) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
-    if (reinterpret_cast<uintptr_t>(frame) & 255u) return fail(GSPLAT_ERR_BAD_ARG, "%s: frame must be 256-byte aligned", name);
-    const FrameParts f = frame_parts(n, pair_capacity, v, GSPLAT_FRAME_BACKWARD);
-    if (f.total > frame_bytes) return fail(GSPLAT_ERR_BAD_ARG, "%s: frame arena too small: was it made with GSPLAT_FRAME_BACKWARD?", name);
+    FrameParts f;
+    if (int rc = open_frame(name, n, pair_capacity, v, frame, frame_bytes, stats, GSPLAT_FRAME_BACKWARD, ": was it made with GSPLAT_FRAME_BACKWARD?", &f)) return rc;
     const char* base = (const char*)frame;
     return densify_stats_impl(name, n, pair_capacity, v, base + f.project_state, (const float*)(base + f.grad2d), stats, stream_, abs);
 }
@@ -835,13 +839,8 @@ int gsplat_contribution(int64_t n, int64_t pair_capacity, const gsplat_view* v, 
 int gsplat_frame_contribution(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame, int64_t frame_bytes,
                               uint32_t* record, void* stream_) {
     const char* name = "gsplat_frame_contribution";
-    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
-    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
-    if (n < 0 || pair_capacity < 0) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
-    if (!frame || !record) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
-    if (reinterpret_cast<uintptr_t>(frame) & 255u) return fail(GSPLAT_ERR_BAD_ARG, "%s: frame must be 256-byte aligned", name);
-    const FrameParts f = frame_parts(n, pair_capacity, v, 0);         // (project_state | bin_state lie at the same offsets with and without GSPLAT_FRAME_BACKWARD)
-    if (f.total > frame_bytes) return fail(GSPLAT_ERR_BAD_ARG, "%s: frame arena too small (gsplat_frame_bytes)", name);
+    FrameParts f;         // (flags 0: project_state | bin_state lie at the same offsets with and without GSPLAT_FRAME_BACKWARD)
+    if (int rc = open_frame(name, n, pair_capacity, v, frame, frame_bytes, record, 0, " (gsplat_frame_bytes)", &f)) return rc;
     const char* base = (const char*)frame;
     return contribution_impl(name, n, pair_capacity, v, base + f.project_state, base + f.bin_state, record, stream_);
 }
