@@ -13,7 +13,7 @@ plus the fused entry `render_gaussians` and the data-parallel helpers in `.dp`.
 from .ops import (HARMONICS, build_sigma_from_params, evaluate_sh, inv2x2, project_points, quat_to_rotmat, render,
                   render_frames, render_gaussians, render_stats, scale_intrinsics, deferred_checks, run_deferred, set_deterministic,
                   PairCapacityExceeded, binned_pairs, reset_pair_capacity, DensifyStats, densify_stats,
-                  ContributionStats, contribution)
+                  ContributionStats, contribution, VisibleSet, visible_set)
 from . import ops  # noqa: E402,F401
 
 from . import losses  # noqa: E402,F401  (L1 + SSIM loss)
@@ -30,4 +30,5 @@ __all__ = [
     'build_sigma_from_params', 'quat_to_rotmat', 'evaluate_sh', 'HARMONICS', 'render', 'project_points', 'inv2x2',
     'scale_intrinsics', 'render_gaussians', 'render_stats', 'render_frames', 'deferred_checks', 'run_deferred', 'set_deterministic',
     'PairCapacityExceeded', 'binned_pairs', 'reset_pair_capacity', 'DensifyStats', 'densify_stats', 'ContributionStats', 'contribution',
+    'VisibleSet', 'visible_set',
 ]

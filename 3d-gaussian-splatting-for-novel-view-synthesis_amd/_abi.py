@@ -171,6 +171,8 @@ SIGNATURES = {
     "gsplat_densify_stats_abs": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP]),
     "gsplat_frame_densify_stats_abs": (_INT, [_I64, _I64, _PV, _VP, _I64, _VP, _VP]),
     "gsplat_densify_stats_merge": (_INT, [_I64, _VP, _VP, _VP]),
+    "gsplat_visible_set": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP]),
+    "gsplat_frame_visible_set": (_INT, [_I64, _I64, _PV, _VP, _I64, _VP, _VP]),
     "gsplat_contribution": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP]),
     "gsplat_frame_contribution": (_INT, [_I64, _I64, _PV, _VP, _I64, _VP, _VP]),
     "gsplat_frame_bytes": (_I64, [_I64, _I64, _PV, C.c_int32]),
@@ -195,6 +197,7 @@ SIGNATURES = {
     "gsplat_clip_grad_norm": (_INT, [_I64, _VP, C.c_float, _VP, _VP, _VP]),
     "gsplat_adam_step": (_INT, [_I64, _VP, _VP, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, _VP, _VP]),
     "gsplat_adam_step_multi": (_INT, [C.c_int32, C.POINTER(AdamGroup), C.c_float, C.c_float, C.c_float, _VP]),
+    "gsplat_adam_step_rows": (_INT, [C.c_int32, C.POINTER(AdamGroup), C.POINTER(C.c_int32), _I64, _VP, C.c_float, C.c_float, C.c_float, _VP]),
     "gsplat_backward_adam_rest": (_INT, [_PG, _VP, _PV, _VP, _I64, _I64, _VP, _PGG, _VP, _I64, C.c_int32, C.POINTER(AdamGroup), C.c_float, C.c_float,
                                          C.c_float, _VP]),
     "gsplat_mcmc_scratch_bytes": (_I64, [_I64]),

@@ -14,6 +14,7 @@
 //   K8  project_backward_kernel chain rule to the reference's input tensors                     [B2, B3]
 //   K9  densify_stats_kernel / densify_stats_merge_kernel   screen-space densification statistics behind K7 (not in the reference)
 //       (K7, K9 <ABS>: the absolute-gradient statistic -- two sums more per pair, columns 10-11 of grad2d)
+//   K9b visible_set_kernel                                  the rows a frame binned, one byte each (gs_visible.h; not in the reference)
 //   K10 raster_contrib_kernel  K6's traversal without colours: per-Gaussian blending-weight statistics (not in the reference)
 //
 // Everything is hand-written HIP for gfx950; no library kernels.  No MFMA: there is no dense contraction on this path.
@@ -35,6 +36,7 @@
 #include "gs_raster.h"
 #include "gs_project_backward.h"
 #include "gs_densify.h"
+#include "gs_visible.h"
 #include "gs_contrib.h"
 #include "gs_ops.h"
 
@@ -369,6 +371,19 @@ int densify_stats_impl(const char* name, int64_t n, int64_t pair_capacity, const
     const Ctx c = open_ctx(n, v, project_state, stream_);
     LAUNCH("densify_stats_kernel", abs ? densify_stats_kernel<true> : densify_stats_kernel<false>, dim3(blocks256(n)), dim3(256), 0, c.st, n, c.ps.counts, (long long)pair_capacity, c.ps.tiles,
            c.ps.rec, grad2d, 0.5f * (float)v->W, 0.5f * (float)v->H, reinterpret_cast<f4*>(stats));
+    return GSPLAT_OK;
+}
+
+// gsplat_visible_set / gsplat_frame_visible_set behind their argument checks (every message names the entry)
+int visible_set_impl(const char* name, int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, uint8_t* visible,
+                     void* stream_) {
+    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
+    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
+    if (n < 0 || n > (int64_t)ID_MASK + 1 || pair_capacity < 0) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
+    if (!project_state || !visible) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
+    if (n == 0) return GSPLAT_OK;
+    const Ctx c = open_ctx(n, v, project_state, stream_);
+    LAUNCH("visible_set_kernel", visible_set_kernel, dim3(blocks256(n)), dim3(256), 0, c.st, n, c.ps.counts, (long long)pair_capacity, c.ps.tiles, visible);
     return GSPLAT_OK;
 }
 
@@ -828,6 +843,19 @@ int gsplat_densify_stats_merge(int64_t n, float* pass, float* total, void* strea
     LAUNCH("densify_stats_merge_kernel", densify_stats_merge_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream_, n, reinterpret_cast<f4*>(pass),
            reinterpret_cast<f4*>(total));
     return GSPLAT_OK;
+}
+
+// ---- the visible set of a frame (include/gsplat_mi355x.h; the kernel: gs_visible.h) -----------------------------------------------
+int gsplat_visible_set(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, uint8_t* visible, void* stream_) {
+    return visible_set_impl("gsplat_visible_set", n, pair_capacity, v, project_state, visible, stream_);
+}
+
+int gsplat_frame_visible_set(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame, int64_t frame_bytes,
+                             uint8_t* visible, void* stream_) {
+    const char* name = "gsplat_frame_visible_set";
+    FrameParts f;         // (flags 0: project_state lies at the same offset with and without GSPLAT_FRAME_BACKWARD)
+    if (int rc = open_frame(name, n, pair_capacity, v, frame, frame_bytes, visible, 0, " (gsplat_frame_bytes)", &f)) return rc;
+    return visible_set_impl(name, n, pair_capacity, v, (const char*)frame + f.project_state, visible, stream_);
 }
 
 // ---- per-Gaussian contribution statistics (include/gsplat_mi355x.h; the kernel: gs_contrib.h) ----------------------------------

@@ -409,11 +409,11 @@ def _frame_spec(fused, H, W, fx, fy, cx, cy, near, far, pix_guard, T, min_conis,
 class _Frame:
     """Everything the backward pass needs from one forward call: the call's FrameSpec (`spec`: camera and mode), the converted inputs
     by name, and the facts of this autograd call -- `need_grad`, `pose` (the backward also forms dL/dc2w), `stats` (the
-    densify_stats() record, if any; `absgrad`: its mode) and the gradient route (`route`, `route_kind`: _route_of).  A frame queued by
+    densify_stats() record, if any; `absgrad`: its mode; `visible`: the visible_set() record, if any) and the gradient route (`route`, `route_kind`: _route_of).  A frame queued by
     gsplat_forward_deferred keeps ONE arena (project_state | bin_state | accum | grad2d, carved by the library); one that went
     through the separate calls keeps them as separate buffers."""
     __slots__ = ("spec", "n", "n_pairs", "proj_state", "bin_state", "accum", "inputs", "c2w", "empty", "grad2d", "sh_jacobian", "arena",
-                 "gaussians", "dirty", "src_ptrs", "route", "route_kind", "pose", "need_grad", "accum_aux", "stats", "absgrad")
+                 "gaussians", "dirty", "src_ptrs", "route", "route_kind", "pose", "need_grad", "accum_aux", "stats", "absgrad", "visible")
 
 
 def _forward_begin(spec, c2w, tensors, pose=False, need_grad=False):
@@ -436,11 +436,13 @@ def _forward_begin(spec, c2w, tensors, pose=False, need_grad=False):
                            "block (factored exchange, folded f_rest step, accumulate_grads): render the frame outside it")
     pos = tensors["pos"]
     stats = _stats_record(pos)              # (checked before anything else: a wrong record is refused even where nothing is rendered)
+    visible = _visible_record(pos)
     lib = _abi.lib()
     dev = pos.device
     fr = _Frame()
     fr.spec, fr.pose, fr.need_grad, fr.stats = spec, pose, need_grad, stats if need_grad else None
     fr.absgrad = fr.stats is not None and _stats_absgrad.get()       # (read once, beside the record)
+    fr.visible = visible if need_grad else None
     fr.route, fr.route_kind = None, PLAIN       # (until _route_of finds a consumer for this frame)
     n, view, opa = pos.shape[0], spec.view, tensors["opacity_raw"]
     fr.n, fr.inputs = n, dict(pos=_f32(pos, (n, 3), "pos"), opacity_raw=_f32(opa if opa.dim() == 1 else opa.reshape(-1), (n,), "opacity_raw"))
@@ -810,6 +812,8 @@ def _backward_separate(fr, bp, grad_depth, grad_alpha, need_params):
         _abi.check(getattr(lib, name)(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(grad2d), _p(fr.stats), st), name)
         if fr.absgrad:
             absgrad_calls["separate"] += 1
+    if fr.visible is not None:
+        _abi.check(lib.gsplat_visible_set(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.visible), st), "gsplat_visible_set")
     if bp.kind == FACTORED:
         # logit gradients first: the exchange may start on them while the projection backward runs
         glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=dev)
@@ -876,12 +880,16 @@ def _backward_arena(fr, bp):
 
 
 def _frame_stats(fr, st):
-    """The densification statistics of a frame on an arena, once its raster phase is queued (fr.stats: ops.densify_stats)."""
+    """The densification statistics of a frame on an arena, once its raster phase is queued (fr.stats: ops.densify_stats), and its
+    visible set (fr.visible: ops.visible_set)."""
     if fr.stats is not None:
         name = "gsplat_frame_densify_stats_abs" if fr.absgrad else "gsplat_frame_densify_stats"
         _abi.check(getattr(_abi.lib(), name)(fr.n, fr.n_pairs, C.byref(fr.spec.view), _p(fr.arena), fr.arena.numel(), _p(fr.stats), st), name)
         if fr.absgrad:
             absgrad_calls["arena"] += 1
+    if fr.visible is not None:
+        _abi.check(_abi.lib().gsplat_frame_visible_set(fr.n, fr.n_pairs, C.byref(fr.spec.view), _p(fr.arena), fr.arena.numel(), _p(fr.visible), st),
+                   "gsplat_frame_visible_set")
 
 
 class DensifyStats:
@@ -980,6 +988,72 @@ def _stats_record(pos):
     if data.dtype != torch.float32 or tuple(data.shape) != (n, 4) or data.device != pos.device or not data.is_contiguous() or data.data_ptr() % 16:
         raise ValueError(f"densify_stats: the record is {data.dtype} {tuple(data.shape)} on {data.device}; this frame needs a contiguous "
                          f"float32 {(n, 4)} record on {pos.device}")
+    return data
+
+
+class VisibleSet:
+    """The Gaussians the frames of a pass binned: `.data` [N] uint8, non-zero = binned into at least one list of at
+    least one frame -- the only rows that can have a non-zero gradient, and the rows optim.GaussianAdam.step(visible=...) steps.
+
+        seen = ops.VisibleSet(n, device)
+        with ops.visible_set(seen):
+            loss(render_gaussians(...)).backward()          # every backward pass of a frame rendered here adds that frame's set
+        optimizer.step(visible=seen)
+
+    A frame only ever stores 1 and never reads the record, so frames on different streams add into one record with no ordering
+    between them; reset() zeroes it.  Works on 'cpu' too (reset, all_reduce over gloo): only adding frames needs the GPU."""
+
+    def __init__(self, n, device):
+        self.data = torch.zeros(int(n), dtype=torch.uint8, device=device)
+
+    def reset(self, n=None):
+        """Zero the record; with another n, a fresh record of n rows (after a densification)."""
+        if n is None or int(n) == self.data.shape[0]:
+            self.data.zero_()
+        else:
+            self.data = torch.zeros(int(n), dtype=torch.uint8, device=self.data.device)
+        return self
+
+    def all_reduce(self, group=None):
+        """The union over the ranks of `group`: an element-wise MAX (plain torch.distributed: CPU tensors over gloo work too).  Every
+        rank ends with the same bytes."""
+        import torch.distributed as dist
+        dist.all_reduce(self.data, op=dist.ReduceOp.MAX, group=group)
+        return self
+
+
+# The record the frames rendered inside a visible_set() block add to: a slot of its own, like _stats.
+_visible = contextvars.ContextVar("gsplat_visible_set", default=None)
+
+
+def visible_set(rec):
+    """Every backward pass of a frame rendered inside the block adds that frame's visible set to `rec` (a VisibleSet, or its uint8 [N]
+    tensor), once, on the backward's stream -- whatever route the gradients take, and beside densify_stats().  Empty and all-culled
+    frames, frames rendered under torch.no_grad() and frames that overflowed their pair capacity add nothing.  A record that does
+    not fit the frame (uint8 [n], contiguous, on the frame's device) raises ValueError when the frame is rendered."""
+    data = rec.data if isinstance(rec, VisibleSet) else rec
+    if not isinstance(data, torch.Tensor):
+        raise TypeError("visible_set() takes a VisibleSet or its uint8 [N] tensor")
+    return _visible_set_block(rec, data)       # (the argument is checked by the call, not by the `with`)
+
+
+@contextlib.contextmanager
+def _visible_set_block(rec, data):
+    token = _visible.set(data)
+    try:
+        yield rec
+    finally:
+        _visible.reset(token)
+
+
+def _visible_record(pos):
+    data = _visible.get()
+    if data is None:
+        return None
+    n = pos.shape[0]
+    if data.dtype != torch.uint8 or tuple(data.shape) != (n,) or data.device != pos.device or not data.is_contiguous():
+        raise ValueError(f"visible_set: the record is {data.dtype} {tuple(data.shape)} on {data.device}; this frame needs a contiguous "
+                         f"uint8 {(n,)} record on {pos.device}")
     return data
 
 

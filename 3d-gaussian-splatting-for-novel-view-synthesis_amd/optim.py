@@ -149,10 +149,18 @@ class GaussianAdam:
         return out
 
     @torch.no_grad()
-    def step(self):
-        """One launch per device for all parameter groups (gsplat_adam_step_multi, eight tensors per launch)."""
+    def step(self, visible=None):
+        """One launch per device for all parameter groups (gsplat_adam_step_multi, eight tensors per launch).
+
+        visible (an ops.VisibleSet or its uint8 [N] tensor): the sparse step -- every stepped tensor has N rows
+        (shape[0] == N, else ValueError) and only the rows whose byte is non-zero are stepped (gsplat_adam_step_rows): exactly as
+        above, with the tensor's own `step` in the bias corrections; every other row keeps its parameter, gradient and moments bit for
+        bit.  `step` counts once per call either way, and clip_grad_norm_ composes unchanged."""
         lib = _abi.lib()
         pending = getattr(self, "_pending_clip", None)
+        mask = None
+        if visible is not None:
+            mask = self._row_mask(visible)
         per_device = {}
         for g in self.param_groups:
             for p in g['params']:
@@ -172,6 +180,32 @@ class GaussianAdam:
                     for k in range(0, len(groups), 8):
                         chunk = groups[k:k + 8]
                         arr = (_abi.AdamGroup * len(chunk))(*chunk)
-                        _abi.check(lib.gsplat_adam_step_multi(len(chunk), arr, float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                                                              _stream_ptr(dev)), "gsplat_adam_step_multi")
+                        if mask is None:
+                            _abi.check(lib.gsplat_adam_step_multi(len(chunk), arr, float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                                                                  _stream_ptr(dev)), "gsplat_adam_step_multi")
+                            continue
+                        n = mask.shape[0]
+                        if n == 0:                # (no rows: nothing to step, and an empty tensor has no address to give)
+                            continue
+                        widths = (C.c_int32 * len(chunk))(*[q.n // n for q in chunk])
+                        _abi.check(lib.gsplat_adam_step_rows(len(chunk), arr, widths, n, _p(mask), float(self.betas[0]), float(self.betas[1]),
+                                                             float(self.eps), _stream_ptr(dev)), "gsplat_adam_step_rows")
         self._pending_clip = None
+
+    def _row_mask(self, visible):
+        """The uint8 [N] tensor of step(visible=...), checked against every tensor the step will touch before anything is counted."""
+        mask = visible.data if isinstance(visible, ops.VisibleSet) else visible
+        if not isinstance(mask, torch.Tensor):
+            raise TypeError("step(visible=...) takes an ops.VisibleSet or its uint8 [N] tensor")
+        if mask.dtype != torch.uint8 or mask.dim() != 1 or not mask.is_contiguous():
+            raise ValueError(f"step(visible=...): the mask is {mask.dtype} {tuple(mask.shape)}; it must be a contiguous uint8 [N] tensor")
+        n = mask.shape[0]
+        for g in self.param_groups:
+            for p in g['params']:
+                if p.grad is None:
+                    continue
+                if p.dim() < 1 or p.shape[0] != n:
+                    raise ValueError(f"step(visible=...): a parameter of shape {tuple(p.shape)} does not have the mask's {n} rows")
+                if p.device != mask.device:
+                    raise ValueError(f"step(visible=...): the mask is on {mask.device}, a parameter on {p.device}")
+        return mask

@@ -117,9 +117,19 @@ class TrainConfig:
     mcmc_scale_reg: float = 0.01
     mcmc_growth: float = 1.05
     mcmc_seed: int = 0
+    # the sparse optimiser step (not in the reference, which steps every row with dense Adam; the INRIA trainer's sparse_adam, gsplat's
+    # visible_adam / SelectiveAdam): only the Gaussians that at least one view of the iteration -- on any rank -- binned
+    # are stepped; every other row keeps its parameter and both moments bit for bit instead of drifting on momentum left by other views.
+    # A bool, else ValueError; not with densify_rule = "mcmc" (its regularisers give every row a gradient and its noise step assumes a
+    # dense optimiser).  While it is on the folded f_rest step is not used (fold_rest_step is ignored): that kernel steps every row, and a
+    # sparse variant of it is a follow-up.  Several views on one process take the data-parallel route of the SH gradients
+    # (dp.FactoredExchange without a collective) instead of sum_views_in_kernel, so that ranks with one view each end with the bits of one
+    # process given all of them.  Off by default: where nearly every Gaussian is in view it only costs the fold.
+    sparse_adam: bool = False
 
     def __post_init__(self):
         _check_absgrad(self)
+        _check_sparse_adam(self)
 
 
 def _check_absgrad(cfg):
@@ -127,6 +137,14 @@ def _check_absgrad(cfg):
         raise ValueError(f"densify_absgrad must be a bool, not {cfg.densify_absgrad!r}")
     if cfg.densify_absgrad and cfg.densify_rule != "screen":
         raise ValueError(f"densify_absgrad=True needs densify_rule='screen' (the other rules read no screen-space statistic), not {cfg.densify_rule!r}")
+
+
+def _check_sparse_adam(cfg):
+    if type(cfg.sparse_adam) is not bool:
+        raise ValueError(f"sparse_adam must be a bool, not {cfg.sparse_adam!r}")
+    if cfg.sparse_adam and cfg.densify_rule == "mcmc":
+        raise ValueError("sparse_adam=True is not available with densify_rule='mcmc' (its regularisers give every row a gradient and its "
+                         "noise step assumes a dense optimiser)")
 
 
 _side_streams = {}           # per device: the two streams the views of an iteration alternate between (TrainConfig.view_streams)
@@ -144,6 +162,7 @@ class Trainer:
             raise ValueError(f"densify_rule must be 'reference', 'screen' or 'mcmc', not {self.cfg.densify_rule!r}")
         _check_mcmc(self.cfg)
         _check_absgrad(self.cfg)                # (again: the fields of a config can be set after it is made)
+        _check_sparse_adam(self.cfg)
         if type(self.cfg.sh_degree_interval) is not int or self.cfg.sh_degree_interval < 0:
             raise ValueError(f"sh_degree_interval must be an integer >= 0, not {self.cfg.sh_degree_interval!r}")
         self._filter_kw = _abi.filter_kwargs(self.cfg.lowpass, self.cfg.antialias)      # (ValueError for a mode the kernels cannot do)
@@ -161,6 +180,8 @@ class Trainer:
         self.densify_stats = None
         self._pass_stats = []
         self._pass_dirty = False
+        # sparse_adam: the Gaussians this iteration's views binned, one record per model size
+        self.visible = None
 
     def _new_optimizer(self, pos_lr):
         c = self.cfg
@@ -326,16 +347,21 @@ class Trainer:
         screen = c.densify_rule == "screen" and iteration < c.densify_until_iter
         pass_stats = self._prepare_stats(dev, len(views)) if screen else None
         absgrad_kw = {'absgrad': True} if c.densify_absgrad else {}         # (the default call is the signed rule's)
+        sparse = c.sparse_adam
+        if sparse and (self.visible is None or self.visible.data.shape[0] != m.get_num_gaussians() or self.visible.data.device != dev):
+            self.visible = ops.VisibleSet(m.get_num_gaussians(), dev)
         for attempt in range(4):
             self.optimizer.zero_grad()
             acc = torch.zeros(3, dtype=torch.float32, device=dev)
             acc_aux = torch.zeros(3, dtype=torch.float32, device=dev) if aux_pass else None
             # the route of the gradients (ops.gradient_route): data parallel, SH gradients in factored form (dp.FactoredExchange, 2.6x
             # fewer bytes over xGMI at 8 views); one view, the Adam step of f_rest inside its backward; several, their sum in the backward
+            # sparse_adam with several views on one process takes the exchange's route too (no collective there): the SH gradients are
+            # then rounded as a group of ranks rounds them, and a group steps the bits of one process given all its views
             exchange = (dp.FactoredExchange(m.get_params(), world_views=1, group=self.group, equal_views=even, sh_degree=sh_degree)
-                        if world > 1 else None)
+                        if world > 1 or (sparse and len(views) > 1) else None)
             # (an aux pass: no route on one process -- its frames take the separate library calls)
-            fold = exchange is None and len(views) == 1 and c.fold_rest_step and not aux_pass
+            fold = exchange is None and len(views) == 1 and c.fold_rest_step and not aux_pass and not sparse
             sum_in_kernel = exchange is None and len(views) > 1 and c.sum_views_in_kernel and not aux_pass
             route = (exchange if exchange is not None else self.optimizer.fused_rest_update(m.f_rest) if fold
                      else ops.accumulate_grads(m.get_params()) if sum_in_kernel else None)
@@ -349,6 +375,10 @@ class Trainer:
                     side = self._view_streams(dev) if (c.view_streams > 1 and len(views) > 1 and world == 1) else ()     # (one process: the
                     # exchange's collectives of a data-parallel pass stay on the caller's stream)
                     main = torch.cuda.current_stream(dev) if side else None
+                    if sparse:
+                        # zeroed in every attempt, on the caller's stream, before the side streams wait on it: a repeated pass
+                        # counts nothing from the failed one (whose streams the caller's stream has waited for)
+                        self.visible.reset()
                     for st in side:
                         st.wait_stream(main)                                           # parameters, zeroed gradients
                     per_view, per_view_aux = [], []
@@ -362,7 +392,8 @@ class Trainer:
                                 if image_gt.shape[-1] == 4:            # rgb + alpha: over black
                                     image_gt = losses.composite_over(image_gt[..., :3], image_gt[..., 3], (0.0, 0.0, 0.0))
                             c2w = torch.as_tensor(v['c2w'], dtype=torch.float32).to(dev)
-                            with (ops.densify_stats(pass_stats[k], **absgrad_kw) if screen else contextlib.nullcontext()):
+                            with (ops.densify_stats(pass_stats[k], **absgrad_kw) if screen else contextlib.nullcontext()), \
+                                    (ops.visible_set(self.visible) if sparse else contextlib.nullcontext()):
                                 rendered = ops.render_gaussians(m.pos, m.f_dc, m.f_rest, m.opacity_raw, m.scale_raw, m.q_raw, c2w,
                                                                 int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']),
                                                                 **degree_kw, **self._filter_kw, **aux_kw)
@@ -379,6 +410,9 @@ class Trainer:
                             per_view.append(vals)
                     for st in side:
                         main.wait_stream(st)
+                    if side and exchange is not None:
+                        for t in exchange.logits + exchange.eyes:                      # (allocated on a view's stream, read by finish() on the caller's)
+                            t.record_stream(main)
                     if sum_in_kernel:
                         consumer.assign()
                     for vals in per_view:                                              # (on the caller's stream, in view order)
@@ -451,7 +485,14 @@ class Trainer:
             # the gradients are complete (every view, every rank): the regularisers join them, and the loss, in ONE launch
             reg = mcmc.regularise(m, c.mcmc_opacity_reg, c.mcmc_scale_reg, base=acc[2] + acc_aux[2] if aux_pass else acc[2])
         self.optimizer.clip_grad_norm_(m.pos, max_norm=1.0)
-        self.optimizer.step()
+        if sparse:
+            # (the ranks agreed STATUS_OK above, so every rank is here: none can be left in the collective.)  The union over the ranks:
+            # every rank steps the same rows and the replicas stay bit-identical -- one collective of N bytes per iteration
+            if world > 1:
+                self.visible.all_reduce(self.group)
+            self.optimizer.step(visible=self.visible)
+        else:
+            self.optimizer.step()
         densified = False
         if use_mcmc:
             mcmc.add_noise(m, pos_lr * c.mcmc_noise_lr, c.mcmc_seed, int(iteration))

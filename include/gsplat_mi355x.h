@@ -410,6 +410,21 @@ int gsplat_densify_stats_abs(int64_t n, int64_t pair_capacity, const gsplat_view
 int gsplat_frame_densify_stats_abs(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame,
                                    int64_t frame_bytes, float* stats, void* stream);
 
+/* ---- the visible set of a frame (not in the reference) -----------------------------------------------------
+ * One byte per Gaussian: behind ONE frame, visible[i] = 1 for every Gaussian binned into at least one list of that frame -- the
+ * rows gsplat_densify_stats counts, and the only rows of the frame that can have a non-zero gradient.  The record is never read
+ * and 0 is never stored, so frames on different streams may add into one record with NO ordering between them (every store
+ * writes the same value); the caller zeroes it.  A frame with nothing on screen, or one whose pairs outgrew pair_capacity, adds
+ * nothing -- decided on the device, as in gsplat_densify_stats.
+ *   gsplat_visible_set        on the project_state of gsplat_project + gsplat_bin.
+ *   gsplat_frame_visible_set  the same on the arena of gsplat_forward_deferred (with or without GSPLAT_FRAME_BACKWARD).
+ * GSPLAT_ERR_BAD_ARG (the text names the entry): a NULL pointer, n < 0, pair_capacity < 0, frame_bytes below
+ * gsplat_frame_bytes(n, pair_capacity, v, 0).  n == 0: GSPLAT_OK, nothing is launched.                                            */
+int gsplat_visible_set(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, uint8_t* visible,
+                       void* stream);
+int gsplat_frame_visible_set(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame, int64_t frame_bytes,
+                             uint8_t* visible, void* stream);
+
 /* ---- per-Gaussian contribution statistics (not in the reference) ------------------------------------------------------------
  * How much does each Gaussian take part in the composite?  With the blending weight w_i(p) = alpha_i T_i [T_i > 5e-5] of Gaussian i
  * at pixel p, exactly as the forward rasteriser forms it, one frame adds to row i of `record`, over all pixels of all lists the
@@ -510,6 +525,14 @@ typedef struct gsplat_adam_group {
     const float* grad_scale;      /* nullable device scalar */
 } gsplat_adam_group;
 int gsplat_adam_step_multi(int32_t n_groups, const gsplat_adam_group* groups, float beta1, float beta2, float eps, void* stream);
+/* The sparse step: group k is n_rows rows of row_width[k] >= 1 values (groups[k].n == n_rows * row_width[k]),
+ * and only the rows whose byte of `visible` (device, n_rows bytes) is non-zero are stepped -- exactly as gsplat_adam_step_multi
+ * steps them, with the tensor's own `step` in the bias corrections and the clip coefficient where the group has one.  A row whose
+ * byte is zero keeps param, grad, exp_avg and exp_avg_sq bit for bit, whatever they hold (NaN included).  With every byte non-zero
+ * the result is bit-identical to gsplat_adam_step_multi.  Up to 8 groups in one launch.  GSPLAT_ERR_BAD_ARG, before any launch:
+ * more than 8 groups, a NULL `visible` or `row_width`, a width < 1, n != n_rows * width, and what gsplat_adam_step_multi refuses.  */
+int gsplat_adam_step_rows(int32_t n_groups, const gsplat_adam_group* groups, const int32_t* row_width, int64_t n_rows,
+                          const uint8_t* visible, float beta1, float beta2, float eps, void* stream);
 
 /* gsplat_backward with the Adam step of f_rest folded into the projection backward: the 45 SH gradients of a Gaussian (192 of the 236
  * gradient bytes) are applied to f_rest as they are formed -- they are neither written nor read again by the optimiser.  For an
