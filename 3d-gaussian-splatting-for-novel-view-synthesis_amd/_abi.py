@@ -30,6 +30,8 @@ GSPLAT_BACKWARD_GRAD2D_DIRTY = 8
 GSPLAT_BACKWARD_ACCUMULATE = 16
 GSPLAT_BACKWARD_DEPTH = 64
 GSPLAT_BACKWARD_ABSGRAD = 128
+GSPLAT_FILTER3D_CAMERA_FLOATS = 24
+GSPLAT_FILTER3D_CAMERA_CHUNK = 64
 
 
 def sh_bands_dropped(degree):
@@ -205,6 +207,10 @@ SIGNATURES = {
     "gsplat_mcmc_noise": (_INT, [_I64, _VP, _VP, _VP, _VP, C.c_float, C.c_uint64, C.c_uint32, _VP]),
     "gsplat_mcmc_regularise": (_INT, [_I64, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP, _VP, _VP, _VP]),
     "gsplat_mcmc_refine": (_INT, [_VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(McmcMoments), _I64, C.c_float, C.c_uint64, C.c_uint32, _VP, _VP]),
+    "gsplat_filter3d_scratch_bytes": (_I64, [_I64]),
+    "gsplat_filter3d_compute": (_INT, [_I64, _VP, C.c_int32, _VP, C.c_float, C.c_float, C.c_float, _VP, _VP, _VP]),
+    "gsplat_filter3d_apply": (_INT, [_I64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "gsplat_filter3d_apply_backward": (_INT, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int32, _VP]),
 }
 
 _lib = None

@@ -19,6 +19,9 @@ Follows scripts/train.py:446-569 statement by statement, on the fused pieces of 
                                                the complete gradients (mcmc.regularise), the position noise follows the step
                                                (mcmc.add_noise), and GaussianModel.refine_mcmc takes densification's place --
                                                rows are rewritten in place and the optimiser is KEPT; no opacity reset
+    [filter3d > 0, not in the reference; DESIGN.md §23]       the 3D smoothing filter of Mip-Splatting: every view renders
+                                               filter3d.apply(scale_raw, opacity_raw, filt) -- two leaves formed once per pass -- and ONE
+                                               backward launch turns the leaves' complete gradients into scale_raw.grad / opacity_raw.grad
 
 With data parallelism every rank holds the full model, renders its share of the batch's views and divides by the GLOBAL
 number of views; the split noise of densification comes from a generator seeded identically on all ranks, so the
@@ -30,7 +33,7 @@ from dataclasses import dataclass
 import torch
 import torch.distributed as dist
 
-from . import _abi, dp, losses, mcmc, ops, optim
+from . import _abi, dp, filter3d, losses, mcmc, ops, optim
 
 
 @dataclass
@@ -126,10 +129,22 @@ class TrainConfig:
     # (dp.FactoredExchange without a collective) instead of sum_views_in_kernel, so that ranks with one view each end with the bits of one
     # process given all of them.  Off by default: where nearly every Gaussian is in view it only costs the fold.
     sparse_adam: bool = False
+    # the 3D smoothing filter of Mip-Splatting (not in the reference; filter3d.py), the companion of lowpass / antialias.
+    # filter3d = s > 0 (the paper: 0.2; 0: off): Gaussian k is rendered convolved with an isotropic Gaussian of standard deviation
+    # sqrt(s) t_k, t_k the smallest z / focal over the training cameras that see it -- the cameras of the WHOLE training set, given to
+    # Trainer(cameras=...).  The limit is recomputed every filter3d_interval iterations and whenever the number of Gaussians changed; a
+    # camera sees a Gaussian beyond filter3d_near whose projection lies inside the image widened by filter3d_margin of its size.
+    # Densification, pruning, the opacity reset and the sparse optimiser keep acting on the RAW parameters and the raw gradients, as
+    # Mip-Splatting's do.  Not with densify_rule = "mcmc" (its relocation and regularisers are written for unfiltered opacity and scale).
+    filter3d: float = 0.0
+    filter3d_interval: int = 100
+    filter3d_near: float = 0.2
+    filter3d_margin: float = 0.15
 
     def __post_init__(self):
         _check_absgrad(self)
         _check_sparse_adam(self)
+        _check_filter3d(self)
 
 
 def _check_absgrad(cfg):
@@ -147,14 +162,35 @@ def _check_sparse_adam(cfg):
                          "noise step assumes a dense optimiser)")
 
 
+def _check_filter3d(cfg, cameras=False):
+    """The filter3d fields of a TrainConfig (ValueError); `cameras`: the trainer's (None: it was given none), False: not known yet."""
+    for name in ("filter3d", "filter3d_near", "filter3d_margin"):
+        x = getattr(cfg, name)
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not 0.0 <= x < float("inf"):
+            raise ValueError(f"{name} must be a finite number >= 0, not {x!r}")
+    if type(cfg.filter3d_interval) is not int or cfg.filter3d_interval < 1:
+        raise ValueError(f"filter3d_interval must be an integer >= 1, not {cfg.filter3d_interval!r}")
+    if cfg.filter3d > 0 and cfg.densify_rule == "mcmc":
+        raise ValueError("filter3d > 0 is not available with densify_rule='mcmc' (its relocation and its regularisers are written for "
+                         "unfiltered opacity and scale)")
+    if cfg.filter3d > 0 and cameras is None:
+        raise ValueError("filter3d > 0 needs the cameras of the whole training set: Trainer(model, config, group, cameras=views)")
+
+
 _side_streams = {}           # per device: the two streams the views of an iteration alternate between (TrainConfig.view_streams)
 
 
 class Trainer:
     """Owns the optimiser of a GaussianModel and runs iterations.  `group`: torch.distributed group for data parallelism
-    by camera view (None = default group if initialised, else single process)."""
+    by camera view (None = default group if initialised, else single process).  `cameras` (TrainConfig.filter3d > 0 only): the view
+    dicts of the WHOLE training set -- only c2w, H, W, fx, fy, cx, cy are read; under data parallelism every rank passes the same
+    list, so the filter is the same bits on every rank without a message.
 
-    def __init__(self, model, config=None, group=None):
+    With filter3d > 0 the views are rendered from the filtered scale and opacity (filter3d.apply) and `self.filter3d` holds the
+    per-Gaussian filter; densify_and_prune*, reset_opacity, prune_by_contribution's removal and the sparse optimiser keep acting on the
+    RAW parameters and the raw gradients (the chain rule through the filter is applied before them), as Mip-Splatting's do."""
+
+    def __init__(self, model, config=None, group=None, cameras=None):
         self.model = model
         self.cfg = config or TrainConfig()
         self.group = group
@@ -163,6 +199,11 @@ class Trainer:
         _check_mcmc(self.cfg)
         _check_absgrad(self.cfg)                # (again: the fields of a config can be set after it is made)
         _check_sparse_adam(self.cfg)
+        _check_filter3d(self.cfg, cameras)
+        # filter3d: the camera records (host copy; on the model's device from the first step on) and the per-Gaussian filter
+        self._cameras = filter3d.pack_cameras(cameras, "cpu") if cameras is not None and self.cfg.filter3d > 0 else None
+        self._cameras_dev = None
+        self.filter3d = None
         if type(self.cfg.sh_degree_interval) is not int or self.cfg.sh_degree_interval < 0:
             raise ValueError(f"sh_degree_interval must be an integer >= 0, not {self.cfg.sh_degree_interval!r}")
         self._filter_kw = _abi.filter_kwargs(self.cfg.lowpass, self.cfg.antialias)      # (ValueError for a mode the kernels cannot do)
@@ -188,6 +229,17 @@ class Trainer:
         groups = optim.reference_param_groups(self.model, position_lr_init=pos_lr, feature_lr=c.feature_lr,
                                               opacity_lr=c.opacity_lr, scaling_lr=c.scaling_lr, rotation_lr=c.rotation_lr)
         return optim.GaussianAdam(groups, lr=c.lr, eps=1e-15)
+
+    def _update_filter3d(self, iteration, dev):
+        """self.filter3d for this iteration: recomputed (one library call, nothing read back) when it is missing or has another length
+        than the model -- after a densification, a prune or a model swap -- and at every filter3d_interval-th iteration."""
+        c, m = self.cfg, self.model
+        if self._cameras_dev is None or self._cameras_dev.device != dev:
+            self._cameras_dev = self._cameras.to(dev)
+        f = self.filter3d
+        if f is None or f.shape[0] != m.get_num_gaussians() or f.device != dev or iteration % c.filter3d_interval == 0:
+            self.filter3d = filter3d.compute(m.pos, self._cameras_dev, s=c.filter3d, near=c.filter3d_near, margin=c.filter3d_margin)
+        return self.filter3d
 
     def _view_streams(self, dev):
         key = (dev.type, dev.index)
@@ -284,6 +336,10 @@ class Trainer:
         c, m = self.cfg, self.model
         dev = m.pos.device
         stats = ops.ContributionStats(m.get_num_gaussians(), dev)
+        scale_in, opacity_in = m.scale_raw, m.opacity_raw
+        if c.filter3d > 0:                                     # what the views of step() are rendered from
+            baked = filter3d.bake(m, self._update_filter3d(iteration, dev))
+            scale_in, opacity_in = baked["scale_raw"], baked["opacity_raw"]
         groups = {}
         for v in views:                                        # poses that share a camera go through one call
             cam = (int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']))
@@ -291,7 +347,7 @@ class Trainer:
         world, err = self._world(), None
         try:
             for cam, poses in groups.items():
-                ops.contribution(m.pos, m.f_dc, m.f_rest, m.opacity_raw, m.scale_raw, m.q_raw, poses, *cam, sh_degree=self.sh_degree(iteration),
+                ops.contribution(m.pos, m.f_dc, m.f_rest, opacity_in, scale_in, m.q_raw, poses, *cam, sh_degree=self.sh_degree(iteration),
                                  stats=stats, **self._filter_kw)
         except Exception as e:                # single process: the exception leaves as it is
             if world == 1:
@@ -350,21 +406,34 @@ class Trainer:
         sparse = c.sparse_adam
         if sparse and (self.visible is None or self.visible.data.shape[0] != m.get_num_gaussians() or self.visible.data.device != dev):
             self.visible = ops.VisibleSet(m.get_num_gaussians(), dev)
+        f3 = c.filter3d > 0
+        if f3:
+            self._update_filter3d(iteration, dev)
+        params, scale_in, opacity_in = m.get_params(), m.scale_raw, m.opacity_raw
         for attempt in range(4):
             self.optimizer.zero_grad()
+            if f3:
+                # the effective scale and opacity of this pass: ONE launch, on the caller's stream before the views' streams wait on it, and
+                # two fresh leaves -- their gradients start empty in every attempt, so a repeated pass counts nothing twice.  The routes get
+                # the parameter dict with the two leaves in place: their addresses are the same for every view of the pass
+                with torch.no_grad():
+                    scale_in, opacity_in = filter3d.apply(m.scale_raw.detach(), m.opacity_raw.detach(), self.filter3d)
+                scale_in.requires_grad_(True)
+                opacity_in.requires_grad_(True)
+                params = {**m.get_params(), 'scale_raw': scale_in, 'opacity_raw': opacity_in}
             acc = torch.zeros(3, dtype=torch.float32, device=dev)
             acc_aux = torch.zeros(3, dtype=torch.float32, device=dev) if aux_pass else None
             # the route of the gradients (ops.gradient_route): data parallel, SH gradients in factored form (dp.FactoredExchange, 2.6x
             # fewer bytes over xGMI at 8 views); one view, the Adam step of f_rest inside its backward; several, their sum in the backward
             # sparse_adam with several views on one process takes the exchange's route too (no collective there): the SH gradients are
             # then rounded as a group of ranks rounds them, and a group steps the bits of one process given all its views
-            exchange = (dp.FactoredExchange(m.get_params(), world_views=1, group=self.group, equal_views=even, sh_degree=sh_degree)
+            exchange = (dp.FactoredExchange(params, world_views=1, group=self.group, equal_views=even, sh_degree=sh_degree)
                         if world > 1 or (sparse and len(views) > 1) else None)
             # (an aux pass: no route on one process -- its frames take the separate library calls)
             fold = exchange is None and len(views) == 1 and c.fold_rest_step and not aux_pass and not sparse
             sum_in_kernel = exchange is None and len(views) > 1 and c.sum_views_in_kernel and not aux_pass
             route = (exchange if exchange is not None else self.optimizer.fused_rest_update(m.f_rest) if fold
-                     else ops.accumulate_grads(m.get_params()) if sum_in_kernel else None)
+                     else ops.accumulate_grads(params) if sum_in_kernel else None)
             pass_error = checks = consumer = None
             try:
                 # no host synchronisation per view: the renders size their buffers from earlier frames, the per-frame checks
@@ -394,7 +463,7 @@ class Trainer:
                             c2w = torch.as_tensor(v['c2w'], dtype=torch.float32).to(dev)
                             with (ops.densify_stats(pass_stats[k], **absgrad_kw) if screen else contextlib.nullcontext()), \
                                     (ops.visible_set(self.visible) if sparse else contextlib.nullcontext()):
-                                rendered = ops.render_gaussians(m.pos, m.f_dc, m.f_rest, m.opacity_raw, m.scale_raw, m.q_raw, c2w,
+                                rendered = ops.render_gaussians(m.pos, m.f_dc, m.f_rest, opacity_in, scale_in, m.q_raw, c2w,
                                                                 int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']),
                                                                 **degree_kw, **self._filter_kw, **aux_kw)
                             if aux_maps:
@@ -474,6 +543,15 @@ class Trainer:
                 break
         else:
             raise RuntimeError("the pair buffers overflowed four times in a row")
+        if f3 and (scale_in.grad is not None or opacity_in.grad is not None):
+            # the gradients of the two leaves are complete (every view; every rank: after the exchange's all-reduce): ONE launch takes them
+            # through the filter to the raw parameters -- linear in the gradient and row-local, so exact after the sum and the same on
+            # every rank.  Before the zero-fill, the clip and the optimiser step, which see the raw gradients only
+            m.scale_raw.grad, m.opacity_raw.grad = torch.empty_like(m.scale_raw), torch.empty_like(m.opacity_raw)
+            filter3d.backward_into(m.scale_raw.detach(), m.opacity_raw.detach(), self.filter3d,
+                                   scale_in.grad if scale_in.grad is not None else torch.zeros_like(scale_in),
+                                   opacity_in.grad if opacity_in.grad is not None else torch.zeros_like(opacity_in),
+                                   m.scale_raw.grad, m.opacity_raw.grad)
         names = dp.PARAM_NAMES
         folded = fold and consumer.applied      # f_rest was stepped inside the backward pass: no gradient, no second step
         for k in names:

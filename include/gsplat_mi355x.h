@@ -590,6 +590,38 @@ int gsplat_mcmc_refine(float* pos, float* f_dc, float* f_rest, float* opacity_ra
                        const gsplat_mcmc_moments* moments, int64_t n, float min_opacity, uint64_t seed, uint32_t iteration, void* scratch,
                        void* stream);
 
+/* ---- the Mip-Splatting 3D smoothing filter (not in the reference) -------------------------------------------------
+ * Every entry runs on the caller's stream, reads nothing back and allocates nothing.  n < 2^31.
+ *
+ * Compute: filt[k] = sqrt(s) t_k, the standard deviation in world units of the low-pass that Gaussian k is convolved with.
+ *   t_k = min over the cameras that SEE k of z / max(fx, fy), with (x, y, z) = R^T (p_k - t) of the camera's c2w = [R | t]; a camera
+ *   sees k iff z > near, -margin W <= fx x / z + cx <= (1 + margin) W and -margin H <= fy y / z + cy <= (1 + margin) H.  A NaN or
+ *   infinite position is seen by nobody.  A Gaussian nobody sees gets the largest t of the seen ones; with n_cams == 0 (filt is
+ *   zeroed; pos, cams and scratch may be NULL) or nobody seen at all, every filt[k] = 0.  Minimum and maximum are taken on the
+ *   integer bits of the floats: the same bits every call, on any stream.
+ *   cams: n_cams records of GSPLAT_FILTER3D_CAMERA_FLOATS floats on the device:
+ *     [0..11] c2w[:3, :4] row-major   [12] fx  [13] fy  [14] cx  [15] cy  [16] W  [17] H  [18..23] padding, not read
+ *   (they are staged through LDS GSPLAT_FILTER3D_CAMERA_CHUNK at a time).  A camera whose fx or fy is not a positive finite number
+ *   sees nothing.  scratch: gsplat_filter3d_scratch_bytes(n) device bytes, 256-byte aligned, any contents; one call at a time per
+ *   scratch buffer.  Two launches behind a 4-byte memset node.
+ * Apply, in raw-parameter space, with s_j = max(exp(scale_raw_j), 1e-6) (the render's activation), sigma = sigmoid(opacity_raw), f = filt[k]:
+ *     scale_out_j = log sqrt(s_j^2 + f^2),   c = sqrt(prod s_j^2 / prod (s_j^2 + f^2)),   opacity_out = logit(c sigma)
+ *   -- rendering (scale_out, opacity_out) renders the Gaussian convolved with an isotropic Gaussian of variance f^2, its peak rescaled
+ *   so that its integral is kept.  (The render's own clamp of the opacity at 0.999 then acts on c sigma.)  A row with f == 0 is
+ *   copied bit for bit.  scale arrays are [n, 3], the others [n]; no output may alias an input.
+ * Apply backward: g_scale_raw, g_opacity_raw = the vector-Jacobian product of (g_scale_out, g_opacity_out), c and sigma recomputed
+ *   from the inputs; zero through an active 1e-6 clamp; filt gets no gradient.  accumulate != 0: ADDED to the destinations.
+ * Arrays 4-byte aligned.  One launch each.                                                                                       */
+#define GSPLAT_FILTER3D_CAMERA_FLOATS 24
+#define GSPLAT_FILTER3D_CAMERA_CHUNK 64
+int64_t gsplat_filter3d_scratch_bytes(int64_t n);
+int gsplat_filter3d_compute(int64_t n, const float* pos, int32_t n_cams, const float* cams, float near, float margin, float s, float* filt,
+                            void* scratch, void* stream);
+int gsplat_filter3d_apply(int64_t n, const float* scale_raw, const float* opacity_raw, const float* filt, float* scale_out, float* opacity_out,
+                          void* stream);
+int gsplat_filter3d_apply_backward(int64_t n, const float* scale_raw, const float* opacity_raw, const float* filt, const float* g_scale_out,
+                                   const float* g_opacity_out, float* g_scale_raw, float* g_opacity_raw, int32_t accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

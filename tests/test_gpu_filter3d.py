@@ -1,0 +1,427 @@
+"""The 3D smoothing filter on the device against the float64 oracle (tests/filter3d_oracle.py): the sampling interval,
+the filter and its vector-Jacobian product, the filter through the render against oracle/torch_port.py, and the trainer's wiring."""
+import ctypes as C
+import functools
+import importlib
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import scenes
+from oracle import torch_port as tp
+from tests import filter3d_oracle as fo
+from tests import util
+
+PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+NAMES = ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")
+abi = importlib.import_module(PKG + "._abi")
+CHUNK = abi.GSPLAT_FILTER3D_CAMERA_CHUNK
+SEED, S, NEAR, MARGIN = 11, 0.2, 0.2, 0.15
+U = 2.0 ** -24                                                   # unit roundoff of float32
+
+
+def _bits(t):
+    return t.detach().contiguous().view(torch.int32)
+
+
+# ---- 1. the sampling interval ---------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def _interval_case(n, n_cams):
+    pos, views = fo.scene(SEED, n, n_cams)
+    return pos, views, fo.compute(pos, views, NEAR, MARGIN)
+
+
+def _eps(pos, views, seen):
+    """The relative error float32 may make in sqrt(s) z / max(fx, fy) -- 13 roundings: the three differences p - t, the three products
+    and two sums of the dot product (together at most 4 u |p - t| in z, i.e. 4 u |p - t| / z relative, z > near), the reciprocal of the
+    focal length, its product with z, s to float32, its square root, the last product (5 u); 1 % on top for the second-order terms."""
+    if not seen.any():
+        return 0.0
+    p = pos[seen].astype(np.float64)
+    D = max(np.linalg.norm(p - np.asarray(v["c2w"], np.float64)[:3, 3], axis=1).max() for v in views)
+    return 1.01 * U * (4.0 * D / (NEAR * (1.0 - fo.REL)) + 5.0)
+
+
+@pytest.mark.parametrize("n_cams", [0, 1, 2, CHUNK + 1])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 257, 5000])
+def test_interval_lies_in_the_oracle_band_and_is_the_same_bits_every_call(gs, n, n_cams):
+    pos, views, ref = _interval_case(n, n_cams)
+    seen = ref["seen_sure"]
+    # the scene itself, on the oracle alone: no Gaussian's visibility hangs on a float32 decision, and at most 1 % of the minima do
+    assert np.array_equal(ref["seen_sure"], ref["seen_possible"])
+    assert n == 0 or (ref["t_sure"] == ref["t_possible"]).mean() >= 0.99
+    if n >= 63 and n_cams:
+        k = n // 8
+        assert not seen[:2 * k].any() and not seen[n - 1] and seen[2 * k:n - 1].mean() > 0.7      # outside, behind, the NaN; the cloud
+    cams = gs.filter3d.pack_cameras(views, DEV)
+    assert tuple(cams.shape) == (n_cams, gs.filter3d.CAMERA_FLOATS)
+    p = torch.tensor(pos, device=DEV)
+    filt = gs.filter3d.compute(p, cams, s=S, near=NEAR, margin=MARGIN)
+    again = gs.filter3d.compute(p, cams, s=S, near=NEAR, margin=MARGIN)
+    side = torch.cuda.Stream(DEV)
+    side.wait_stream(torch.cuda.current_stream(DEV))
+    with torch.cuda.stream(side):
+        third = gs.filter3d.compute(p, cams, s=S, near=NEAR, margin=MARGIN, out=torch.full((n,), -1.0, device=DEV))
+    torch.cuda.synchronize()
+    assert filt.shape == (n,) and filt.dtype == torch.float32
+    assert torch.equal(_bits(filt), _bits(again)) and torch.equal(_bits(filt), _bits(third))
+    got = filt.cpu().numpy()
+    if n == 0:
+        return
+    if n_cams == 0 or not seen.any():
+        assert not got.any()                                     # no camera, or nobody seen: every interval is 0
+        return
+    eps, root = _eps(pos, views, seen), np.sqrt(S)
+    lo, hi = ref["t_possible"][seen] * root * (1 - eps), ref["t_sure"][seen] * root * (1 + eps)
+    print(f"n {n} cameras {n_cams}: eps {eps:.2e}, worst relative distance to t_sure {np.abs(got[seen] / (ref['t_sure'][seen] * root) - 1).max():.2e}")
+    assert np.all(got[seen] >= lo) and np.all(got[seen] <= hi)
+    top = got[seen].max()
+    assert np.all(got[~seen].view(np.uint32) == top.view(np.uint32))            # unseen rows: the device's own maximum, bit for bit
+
+
+def test_interval_with_mixed_focal_lengths_uses_each_cameras_own(gs):
+    """Two cameras at the same place, one with a lens four times as long: the long one decides wherever it sees the point."""
+    pos, views = fo.scene(SEED, 1000, 1)
+    tele = dict(views[0], fx=views[0]["fx"] * 4, fy=views[0]["fy"] * 4)
+    p = torch.tensor(pos, device=DEV)
+    wide_only = gs.filter3d.compute(p, gs.filter3d.pack_cameras(views, DEV), s=1.0).cpu().numpy()
+    both = gs.filter3d.compute(p, gs.filter3d.pack_cameras(views + [tele], DEV), s=1.0).cpu().numpy()
+    ref = fo.compute(pos, [tele])
+    inside = ref["seen_sure"]
+    assert inside.sum() > 20 and (fo.compute(pos, views)["seen_sure"] & ~ref["seen_possible"]).sum() > 20
+    np.testing.assert_allclose(both[inside], wide_only[inside] / 4, rtol=3 * U)
+    outside = fo.compute(pos, views)["seen_sure"] & ~ref["seen_possible"]
+    assert np.array_equal(both[outside], wide_only[outside])
+
+
+def test_compute_refuses_what_it_cannot_do(gs):
+    pos = torch.zeros(4, 3, device=DEV)
+    cams = gs.filter3d.pack_cameras(fo.scene(SEED, 4, 2)[1], DEV)
+    with pytest.raises(ValueError):
+        gs.filter3d.compute(pos, cams[:, :20].contiguous())
+    with pytest.raises(ValueError):
+        gs.filter3d.compute(pos, cams, out=torch.zeros(5, device=DEV))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        gs.filter3d.compute(pos, cams.cpu())
+
+
+# ---- 2. applying it -------------------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def _rows():
+    """The rows of the CPU test (tests/test_filter3d_cpu.py) and, measured ONCE on all 4000 of them, the float32 error of the plain
+    closed forms: the device may be 4 x that far from float64 (every N below takes a prefix of these rows)."""
+    a = fo.inputs(4000, 7)
+    return a, fo.errors(*a, *fo.plain_float32(*a))
+
+
+def _raw_call(n, arrays_in, widths_out, guard, entry, *tail):
+    """Call a library entry on interior views of buffers with `guard` rows of 12345 on either side: returns the outputs and checks
+    that no row outside [0, n) was written.  guard = 4 keeps every pointer 16-byte aligned, guard = 1 only 4-byte: both must work."""
+    lib = abi.lib()
+    ins = []
+    for a in arrays_in:
+        w = a.shape[1] if a.ndim == 2 else 1
+        buf = torch.full(((n + 2 * guard) * w,), 777.0, device=DEV)
+        buf[guard * w:(guard + n) * w] = torch.as_tensor(a, device=DEV).reshape(-1)
+        ins.append((buf, guard * w * 4))
+    outs = []
+    for w, init in widths_out:
+        buf = torch.full(((n + 2 * guard) * w,), 12345.0, device=DEV)
+        if init is not None:
+            buf[guard * w:(guard + n) * w] = torch.as_tensor(init, device=DEV).reshape(-1)
+        outs.append((buf, guard * w * 4, w))
+    ptr = lambda b, off: C.c_void_p(b.data_ptr() + off)
+    abi.check(getattr(lib, entry)(n, *[ptr(b, o) for b, o in ins], *[ptr(b, o) for b, o, _ in outs], *tail,
+                                 C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)), entry)
+    torch.cuda.synchronize()
+    res = []
+    for buf, off, w in outs:
+        assert bool((buf[:guard * w] == 12345.0).all()) and bool((buf[(guard + n) * w:] == 12345.0).all()), "a row outside [0, n) was written"
+        inner = buf[guard * w:(guard + n) * w].cpu().numpy()
+        res.append(inner if w == 1 else inner.reshape(n, w))
+    return res
+
+
+@pytest.mark.parametrize("guard", [4, 1])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1000])
+def test_apply_and_its_backward_against_the_oracle(gs, n, guard):
+    (scale_raw, opacity_raw, filt, gs_out, go_out), e_plain = _rows()
+    scale_raw, opacity_raw, filt, gs_out, go_out = (np.ascontiguousarray(a[:n]).copy() for a in (scale_raw, opacity_raw, filt, gs_out, go_out))
+    zero = np.arange(n) % 5 == 2
+    filt[zero] = 0.0
+    so, oo = _raw_call(n, (scale_raw, opacity_raw, filt), ((3, None), (1, None)), guard, "gsplat_filter3d_apply")
+    g_s, g_o = _raw_call(n, (scale_raw, opacity_raw, filt, gs_out, go_out), ((3, None), (1, None)), guard, "gsplat_filter3d_apply_backward", 0)
+    rng = np.random.default_rng(n)
+    pre_s, pre_o = rng.normal(size=(n, 3)).astype(np.float32), rng.normal(size=n).astype(np.float32)
+    a_s, a_o = _raw_call(n, (scale_raw, opacity_raw, filt, gs_out, go_out), ((3, pre_s), (1, pre_o)), guard, "gsplat_filter3d_apply_backward", 1)
+    if n == 0:
+        return
+    so, g_s, a_s = (x.reshape(n, 3) for x in (so, g_s, a_s))
+    oo, g_o, a_o = (x.reshape(n) for x in (oo, g_o, a_o))
+    # f == 0: the four inputs and the upstream gradients, bit for bit
+    for got, want in ((so, scale_raw), (oo, opacity_raw), (g_s, gs_out), (g_o, go_out)):
+        assert np.array_equal(got[zero].view(np.uint32), want[zero].view(np.uint32))
+    # accumulate adds (one float32 addition per entry)
+    assert np.array_equal(a_s, pre_s + g_s) and np.array_equal(a_o, pre_o + g_o)
+    e_dev = fo.errors(scale_raw, opacity_raw, filt, gs_out, go_out, so, oo, g_s, g_o)
+    for name, p_, d_ in zip(("exp(scale_raw')", "sigmoid(opacity_raw')", "g_scale_raw", "g_opacity_raw"), e_plain, e_dev):
+        print(f"n {n} guard {guard} {name}: device {d_:.3e}, float32 plain forms (4000 rows) {p_:.3e}")
+        assert np.isfinite(d_) and d_ <= 4.0 * p_, (name, d_, p_)
+
+
+def test_extreme_inputs_stay_finite_on_the_device(gs):
+    scales = np.array([-20.0, -14.0, -12.0, 0.0, 3.0, 20.0, 80.0], np.float32)
+    opac = np.array([-100.0, -12.0, 0.0, 12.0, 30.0, 100.0], np.float32)
+    filts = np.array([1e-38, 1e-6, 1e-3, 1.0, 10.0, 3e38], np.float32)
+    Sg, Og, Fg = np.meshgrid(scales, opac, filts, indexing="ij")
+    scale_raw = torch.tensor(np.stack([Sg.ravel(), Sg.ravel()[::-1], np.roll(Sg.ravel(), 5)], 1).copy(), device=DEV, requires_grad=True)
+    opacity_raw = torch.tensor(Og.ravel()[:, None].copy(), device=DEV, requires_grad=True)
+    so, oo = gs.filter3d.apply(scale_raw, opacity_raw, torch.tensor(Fg.ravel().copy(), device=DEV))
+    assert oo.shape == opacity_raw.shape                          # [N, 1] stays [N, 1]
+    (so.sum() - 2.0 * oo.sum()).backward()
+    for t in (so, oo, scale_raw.grad, opacity_raw.grad):
+        assert bool(torch.isfinite(t).all())
+
+
+def test_apply_function_is_the_two_entries(gs):
+    (scale_raw, opacity_raw, filt, gs_out, go_out), _ = _rows()
+    n = 333
+    s = torch.tensor(scale_raw[:n], device=DEV, requires_grad=True)
+    o = torch.tensor(opacity_raw[:n], device=DEV, requires_grad=True)
+    f = torch.tensor(filt[:n], device=DEV, requires_grad=True)
+    so, oo = gs.filter3d.apply(s, o, f)
+    ((so * torch.tensor(gs_out[:n], device=DEV)).sum() + (oo * torch.tensor(go_out[:n], device=DEV)).sum()).backward()
+    want_so, want_oo = _raw_call(n, (scale_raw[:n], opacity_raw[:n], filt[:n]), ((3, None), (1, None)), 4, "gsplat_filter3d_apply")
+    want_gs, want_go = _raw_call(n, (scale_raw[:n], opacity_raw[:n], filt[:n], gs_out[:n], go_out[:n]), ((3, None), (1, None)), 4,
+                                 "gsplat_filter3d_apply_backward", 0)
+    assert np.array_equal(so.detach().cpu().numpy(), want_so) and np.array_equal(oo.detach().cpu().numpy(), want_oo)
+    assert np.array_equal(s.grad.cpu().numpy(), want_gs) and np.array_equal(o.grad.cpu().numpy(), want_go)
+    assert f.grad is None                                         # filt gets no gradient
+
+
+# ---- 3. through the render ------------------------------------------------------------------------------------------------------
+
+def test_filtered_render_and_all_six_gradients_against_the_oracle(gs):
+    """g1_generic with a filter of up to 0.05 world units (a fifth of the rows 0): the image and the six gradients of
+    render_gaussians(..., *apply(...)) against oracle/torch_port.py given the oracle-filtered raw tensors, its gradients chained with
+    the oracle's vector-Jacobian product -- within the bounds tests/test_gpu_parity.py uses (tests/util.py; calibrated by the same
+    oracle run in float32).  bake() + render_frames() gives that image bit for bit."""
+    d = util.load("g1_generic")
+    n = len(d["pos"])
+    rng = np.random.default_rng(23)
+    filt = rng.uniform(0.0, 0.05, n).astype(np.float32)
+    filt[::5] = 0.0
+    cam = util.cam_args(d)
+    w = d["wrand"]
+    so, oo = fo.apply(d["scale_raw"], d["opacity_raw"], filt)
+
+    def oracle(dtype):
+        P = {k: torch.tensor(d[k], dtype=dtype) for k in NAMES}
+        P["scale_raw"], P["opacity_raw"] = torch.tensor(so, dtype=dtype), torch.tensor(oo, dtype=dtype)
+        for v in P.values():
+            v.requires_grad_(True)
+        img = tp.render_fused(*[P[k] for k in NAMES], torch.tensor(d["c2w"], dtype=dtype), *cam, **d["kwargs"])
+        (img * torch.tensor(w, dtype=dtype)).sum().backward()
+        g = {k: P[k].grad.double().numpy() for k in NAMES}
+        g["scale_raw"], g["opacity_raw"] = fo.apply_vjp(d["scale_raw"], d["opacity_raw"], filt, g["scale_raw"], g["opacity_raw"])
+        return img.detach().double().numpy(), g
+
+    ref_img, ref_g = oracle(torch.float64)
+    cal_img, cal_g = oracle(torch.float32)
+    p = {k: torch.tensor(d[k], device=DEV, requires_grad=True) for k in NAMES}
+    f = torch.tensor(filt, device=DEV)
+    s_eff, o_eff = gs.filter3d.apply(p["scale_raw"], p["opacity_raw"], f)
+    assert o_eff.shape == p["opacity_raw"].shape
+    c2w = torch.tensor(d["c2w"], device=DEV)
+    img = gs.render_gaussians(p["pos"], p["f_dc"], p["f_rest"], o_eff, s_eff, p["q_raw"], c2w, *cam, **d["kwargs"])
+    (img * torch.tensor(w, device=DEV)).sum().backward()
+    util.check_image(img.detach().cpu().numpy(), ref_img, cal=cal_img)
+    for k in NAMES:
+        util.check_grad(p[k].grad.cpu().numpy(), ref_g[k], k, cal=cal_g[k])
+    baked = gs.filter3d.bake(p, f)
+    assert set(baked) == set(NAMES) and not any(t.requires_grad for t in baked.values())
+    frames = gs.render_frames(*[baked[k] for k in NAMES], [c2w], *cam, **d["kwargs"])
+    assert torch.equal(frames[0], img.detach())
+    model_mod = importlib.import_module(PKG + ".model")
+    m = model_mod.GaussianModel({k: torch.tensor(d[k]) for k in NAMES}, device=DEV)
+    from_model = gs.filter3d.bake(m, f)
+    assert all(torch.equal(from_model[k], baked[k]) for k in NAMES)
+
+
+# ---- 4. the trainer -------------------------------------------------------------------------------------------------------------
+
+def _yaw(c2w, angle):
+    out = np.array(c2w, np.float64).copy()
+    out[:3, :3] = out[:3, :3] @ scenes._rot(0.0, angle, 0.0)
+    return out.astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def _train_scene():
+    s = scenes.case_g1()
+    rng = np.random.default_rng(31)
+    cams = [np.asarray(s["c2w"], np.float32), _yaw(s["c2w"], 0.2), _yaw(s["c2w"], -0.15)]
+    views = [dict(image=rng.uniform(0, 1, (s["H"], s["W"], 3)).astype(np.float32), c2w=c, H=s["H"], W=s["W"], fx=s["fx"], fy=s["fy"],
+                  cx=s["cx"], cy=s["cy"]) for c in cams]
+    return s, views
+
+
+def _trainer(s, cameras=None, **cfg):
+    model_mod = importlib.import_module(PKG + ".model")
+    training = importlib.import_module(PKG + ".training")
+    model = model_mod.GaussianModel({k: torch.tensor(s[k]) for k in NAMES}, device=DEV)
+    cfg = dict(dict(densify_until_iter=0, opacity_reset_interval=10 ** 9), **cfg)
+    return training.Trainer(model, training.TrainConfig(**cfg), cameras=cameras)
+
+
+def _warm(gs, s, views):
+    p = {k: torch.tensor(s[k], device=DEV) for k in NAMES}
+    with torch.no_grad():
+        for v in views:
+            gs.render_gaussians(*[p[k] for k in NAMES], torch.tensor(v["c2w"], device=DEV), v["H"], v["W"], v["fx"], v["fy"], v["cx"], v["cy"])
+
+
+def _view_loss(gs, p, scale_in, opacity_in, v, n_views):
+    img = gs.render_gaussians(p["pos"], p["f_dc"], p["f_rest"], opacity_in, scale_in, p["q_raw"], torch.tensor(v["c2w"], device=DEV),
+                              v["H"], v["W"], v["fx"], v["fy"], v["cx"], v["cy"])
+    return gs.losses.compute_loss_device(img, torch.tensor(v["image"], device=DEV), 0.8, 0.2, scale=1.0 / n_views)[0]
+
+
+def _autograd_grads(gs, s, views, filt):
+    """The iteration's gradients the plain way: per view, apply() as a Function inside the graph, a plain backward, no route."""
+    p = {k: torch.tensor(s[k], device=DEV, requires_grad=True) for k in NAMES}
+    for v in views:
+        s_eff, o_eff = gs.filter3d.apply(p["scale_raw"], p["opacity_raw"], filt)
+        _view_loss(gs, p, s_eff, o_eff, v, len(views)).backward()
+    return {k: p[k].grad for k in NAMES}
+
+
+def _ordered_grads(gs, s, views, filt):
+    """The same sums in the trainer's order: the two effective tensors as leaves, the views' gradients added to them in view order,
+    then the filter's backward once."""
+    p = {k: torch.tensor(s[k], device=DEV, requires_grad=True) for k in NAMES}
+    with torch.no_grad():
+        s_eff, o_eff = gs.filter3d.apply(p["scale_raw"], p["opacity_raw"], filt)
+    s_eff.requires_grad_(True)
+    o_eff.requires_grad_(True)
+    for v in views:
+        _view_loss(gs, p, s_eff, o_eff, v, len(views)).backward()
+    g_s, g_o = torch.empty_like(s_eff), torch.empty_like(o_eff)
+    gs.filter3d.backward_into(p["scale_raw"].detach(), p["opacity_raw"].detach(), filt, s_eff.grad, o_eff.grad, g_s, g_o)
+    return dict(scale_raw=g_s, opacity_raw=g_o, q_raw=p["q_raw"].grad)
+
+
+ROUTES = {"fold": (1, {}), "plain": (1, dict(fold_rest_step=False)), "summed": (3, {}), "exchange": (3, dict(sparse_adam=True))}
+
+
+@pytest.mark.parametrize("deterministic", [False, True])
+@pytest.mark.parametrize("route", list(ROUTES))
+def test_a_steps_raw_gradients_are_the_autograd_formulations(gs, route, deterministic):
+    """Trainer.step with filter3d = 0.2 leaves in scale_raw.grad / opacity_raw.grad what autograd gives with apply() inside the graph of
+    every view -- up to the order of the float atomics (rel-L2 1e-5, as __graft_entry__.smoke allows the composite entries) and, for
+    three views, of J^T (g1 + g2 + g3) against J^T g1 + J^T g2 + J^T g3.  Under set_deterministic(True): bit for bit against the per-view
+    autograd formulation for one view, and for three views against the same sums made in the trainer's order (_ordered_grads).
+    "exchange": three views through dp.FactoredExchange without a collective, the route a data-parallel rank takes."""
+    n_views, cfg = ROUTES[route]
+    s, views = _train_scene()
+    views = list(views[:n_views])
+    old = gs.set_deterministic(deterministic)
+    try:
+        _warm(gs, s, views)
+        tr = _trainer(s, cameras=_train_scene()[1], filter3d=S, **cfg)
+        out = tr.step(1, views)
+        torch.cuda.synchronize()
+        assert set(out) == {"loss", "l1", "ssim", "gaussians", "lr_pos", "densified", "sh_degree"}
+        filt = gs.filter3d.compute(torch.tensor(s["pos"], device=DEV), gs.filter3d.pack_cameras(_train_scene()[1], DEV), s=S)
+        assert torch.equal(_bits(tr.filter3d), _bits(filt)) and float(filt.min()) > 0
+        ref = _autograd_grads(gs, s, views, filt)
+        for k in ("scale_raw", "opacity_raw", "q_raw"):
+            got = getattr(tr.model, k).grad
+            rel = float((got - ref[k]).norm() / ref[k].norm())
+            print(f"{route} deterministic={deterministic} {k}: rel-L2 to the autograd formulation {rel:.2e}")
+            assert rel <= 1e-5, (k, rel)
+        if deterministic:
+            exact = ref if n_views == 1 else _ordered_grads(gs, s, views, filt)
+            for k in ("scale_raw", "opacity_raw"):
+                assert torch.equal(_bits(getattr(tr.model, k).grad), _bits(exact[k])), k
+        # the filter does something here: the raw gradients are not the gradients of the unfiltered render
+        plain = _trainer(s, **cfg)
+        plain.step(1, views)
+        assert not torch.equal(plain.model.scale_raw.grad, tr.model.scale_raw.grad)
+    finally:
+        gs.set_deterministic(old)
+
+
+def test_a_repeated_pass_counts_nothing_twice(gs):
+    ops = gs.ops
+    s, views = _train_scene()
+    old = gs.set_deterministic(True)
+    try:
+        _warm(gs, s, views)
+        key = ops.capacity_key(torch.device(DEV), types.SimpleNamespace(H=s["H"], W=s["W"]), len(s["pos"]))
+        keep = ops._ws.capacity[key]
+        try:
+            ref, tr = _trainer(s, cameras=views, filter3d=S), _trainer(s, cameras=views, filter3d=S)
+            ref.step(1, views)
+            ops._ws.capacity[key] = 100
+            before = dict(ops.forward_modes)
+            tr.step(1, views)
+            torch.cuda.synchronize()
+            assert ops.forward_modes["deferred"] == before["deferred"] + 2 * len(views), "the pass was not repeated"
+        finally:
+            ops._ws.capacity[key] = max(keep, ops._ws.capacity.get(key, 0))
+        for k in NAMES:
+            assert torch.equal(_bits(getattr(tr.model, k).grad), _bits(getattr(ref.model, k).grad)), k
+            assert torch.equal(_bits(getattr(tr.model, k)), _bits(getattr(ref.model, k))), k
+    finally:
+        gs.set_deterministic(old)
+
+
+def test_the_filter_follows_the_model_and_the_interval(gs):
+    s, views = _train_scene()
+    tr = _trainer(s, cameras=views, filter3d=S, filter3d_interval=5, densification_interval=3, densify_until_iter=4, max_grad=1e-4)
+    n0 = len(s["pos"])
+    seen = {}
+    for it in range(1, 8):
+        out = tr.step(it, views[:2])
+        seen[it] = tr.filter3d
+        assert tr.filter3d.shape[0] == (n0 if it <= 3 else out["gaussians"])
+        if it == 3:
+            assert out["densified"] and out["gaussians"] != n0, "the scene: the densification must change N"
+    assert seen[2] is seen[1] and seen[3] is seen[1]              # nothing changed, no interval: kept
+    assert seen[4] is not seen[3] and seen[4].shape[0] == tr.model.get_num_gaussians()      # N changed: recomputed
+    assert seen[5] is not seen[4]                                 # iteration % 5 == 0: recomputed
+    assert seen[6] is seen[5] and seen[7] is seen[5]
+    want = gs.filter3d.compute(tr.model.pos, gs.filter3d.pack_cameras(views, DEV), s=S)
+    assert seen[7].shape == want.shape and bool(torch.isfinite(seen[7]).all())
+    removed = tr.prune_by_contribution(8, views[:2], keep_fraction=0.5)["removed"]
+    assert removed > 0
+    tr.step(9, views[:2])
+    assert tr.filter3d.shape[0] == tr.model.get_num_gaussians() and tr.filter3d is not seen[7]
+
+
+def test_with_the_filter_off_the_trainer_is_the_one_it_was(gs):
+    s, views = _train_scene()
+    old = gs.set_deterministic(True)
+    try:
+        _warm(gs, s, views)
+        a, b = _trainer(s), _trainer(s, cameras=views, filter3d=0.0)
+        real, calls = gs.filter3d.compute, []
+        gs.filter3d.compute = lambda *x, **kw: calls.append(1) or real(*x, **kw)
+        try:
+            out_a, out_b = a.step(1, views), b.step(1, views)
+        finally:
+            gs.filter3d.compute = real
+        torch.cuda.synchronize()
+        assert not calls and a.filter3d is None and b.filter3d is None
+        assert list(out_a) == list(out_b) == ["loss", "l1", "ssim", "gaussians", "lr_pos", "densified", "sh_degree"]
+        for k in NAMES:
+            assert torch.equal(_bits(getattr(a.model, k)), _bits(getattr(b.model, k))), k
+    finally:
+        gs.set_deterministic(old)
