@@ -32,6 +32,7 @@ GSPLAT_BACKWARD_DEPTH = 64
 GSPLAT_BACKWARD_ABSGRAD = 128
 GSPLAT_FILTER3D_CAMERA_FLOATS = 24
 GSPLAT_FILTER3D_CAMERA_CHUNK = 64
+GSPLAT_EXPOSURE_ACCUMULATE = 1
 
 
 def sh_bands_dropped(degree):
@@ -211,6 +212,9 @@ SIGNATURES = {
     "gsplat_filter3d_compute": (_INT, [_I64, _VP, C.c_int32, _VP, C.c_float, C.c_float, C.c_float, _VP, _VP, _VP]),
     "gsplat_filter3d_apply": (_INT, [_I64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "gsplat_filter3d_apply_backward": (_INT, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int32, _VP]),
+    "gsplat_exposure_scratch_bytes": (_I64, [_I64, C.c_int32, C.c_int32]),
+    "gsplat_exposure_forward": (_INT, [_VP, _VP, _I64, C.c_int32, C.c_int32, _VP, _VP]),
+    "gsplat_exposure_backward": (_INT, [_VP, _VP, _VP, _I64, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
 }
 
 _lib = None

@@ -132,6 +132,23 @@ def allreduce_gradients(grads, world_views, group=None):
     return grads
 
 
+def allreduce_exposure_grad(grad, group=None):
+    """Sum the gradient of the exposure table ([V, 3, 4], exposure.ExposureTable.grad) over the ranks, in place: ONE all-reduce (SUM) of
+    48 V bytes per iteration.  A row only one rank's views used arrives as that rank's bits (x + 0 is exact), and the sum of two ranks is
+    the same bits in either order, so two ranks with one view each end with the bits of one process given both views.  A collective:
+    every rank calls it once per iteration, AFTER the ranks agreed STATUS_OK (agree_status) -- never on a path where a peer may have
+    raised.  A single process: nothing happens."""
+    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return grad
+    if dist.get_backend(group) == "gloo" and grad.is_cuda:           # (rehearsals: staged through the host)
+        host = grad.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        grad.copy_(host)
+        return grad
+    dist.all_reduce(grad, op=dist.ReduceOp.SUM, group=group)
+    return grad
+
+
 def data_parallel_step(render_fn, params, views, targets_grad_fn, world_views, group=None):
     """One DP step on this rank: render this rank's views, back-propagate, all-reduce the parameter gradients.
 

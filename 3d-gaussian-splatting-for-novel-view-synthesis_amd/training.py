@@ -22,6 +22,9 @@ Follows scripts/train.py:446-569 statement by statement, on the fused pieces of 
     [filter3d > 0, not in the reference; DESIGN.md §23]       the 3D smoothing filter of Mip-Splatting: every view renders
                                                filter3d.apply(scale_raw, opacity_raw, filt) -- two leaves formed once per pass -- and ONE
                                                backward launch turns the leaves' complete gradients into scale_raw.grad / opacity_raw.grad
+    [exposure, not in the reference; DESIGN.md §24]          per-view exposure compensation: each view's rendered colour goes through the
+                                               affine transform of ITS training image (exposure.ExposureTable.apply_view) before the loss;
+                                               the table has a gradient buffer, an Adam state and a learning-rate schedule of its own
 
 With data parallelism every rank holds the full model, renders its share of the batch's views and divides by the GLOBAL
 number of views; the split noise of densification comes from a generator seeded identically on all ranks, so the
@@ -33,7 +36,7 @@ from dataclasses import dataclass
 import torch
 import torch.distributed as dist
 
-from . import _abi, dp, filter3d, losses, mcmc, ops, optim
+from . import _abi, dp, exposure, filter3d, losses, mcmc, ops, optim
 
 
 @dataclass
@@ -140,11 +143,27 @@ class TrainConfig:
     filter3d_interval: int = 100
     filter3d_near: float = 0.2
     filter3d_margin: float = 0.15
+    # per-view exposure compensation (not in the reference; the INRIA trainer's exposure optimisation, gsplat's appearance transform;
+    # exposure.py).  exposure = True (a bool, else ValueError): every training image has an affine colour transform
+    # [M | t], the identity at the start, that its view's rendered colour -- after the background composite; the depth and opacity maps
+    # are untouched -- goes through before the loss.  The table of transforms (Trainer.exposure) is trained beside the model by an Adam
+    # of its own (eps 1e-8, dense) at the learning rate optim.position_lr gives for the four numbers below -- the INRIA trainer's
+    # defaults, taken from there and not measured here.  A view names its image by its integer 'idx' (data.GaussianDataset supplies it);
+    # the table has Trainer(exposure_views=V) rows, len(cameras) by default.  The op sits outside the render: every route of the
+    # gradients, every densify rule, sparse_adam, filter3d and the aux passes work unchanged, and a fresh optimiser after a
+    # densification touches neither the table nor its moments.  Novel views are rendered without it.  Off by default, and an iteration
+    # is then exactly the one above.
+    exposure: bool = False
+    exposure_lr_init: float = 0.01
+    exposure_lr_final: float = 0.001
+    exposure_lr_delay_mult: float = 0.0
+    exposure_lr_max_steps: int = 30000
 
     def __post_init__(self):
         _check_absgrad(self)
         _check_sparse_adam(self)
         _check_filter3d(self)
+        _check_exposure(self)
 
 
 def _check_absgrad(cfg):
@@ -177,6 +196,11 @@ def _check_filter3d(cfg, cameras=False):
         raise ValueError("filter3d > 0 needs the cameras of the whole training set: Trainer(model, config, group, cameras=views)")
 
 
+def _check_exposure(cfg):
+    if type(cfg.exposure) is not bool:
+        raise ValueError(f"exposure must be a bool, not {cfg.exposure!r}")
+
+
 _side_streams = {}           # per device: the two streams the views of an iteration alternate between (TrainConfig.view_streams)
 
 
@@ -188,9 +212,13 @@ class Trainer:
 
     With filter3d > 0 the views are rendered from the filtered scale and opacity (filter3d.apply) and `self.filter3d` holds the
     per-Gaussian filter; densify_and_prune*, reset_opacity, prune_by_contribution's removal and the sparse optimiser keep acting on the
-    RAW parameters and the raw gradients (the chain rule through the filter is applied before them), as Mip-Splatting's do."""
+    RAW parameters and the raw gradients (the chain rule through the filter is applied before them), as Mip-Splatting's do.
 
-    def __init__(self, model, config=None, group=None, cameras=None):
+    With exposure = True `self.exposure` is the exposure.ExposureTable of `exposure_views` rows (default: len(cameras)), one per training
+    image, else None; under data parallelism every rank holds the whole table and the replicas stay bit-identical.  It is not part of
+    harness.save_checkpoint's file set: it travels through its own state_dict() / load_state_dict()."""
+
+    def __init__(self, model, config=None, group=None, cameras=None, exposure_views=None):
         self.model = model
         self.cfg = config or TrainConfig()
         self.group = group
@@ -200,6 +228,14 @@ class Trainer:
         _check_absgrad(self.cfg)                # (again: the fields of a config can be set after it is made)
         _check_sparse_adam(self.cfg)
         _check_filter3d(self.cfg, cameras)
+        _check_exposure(self.cfg)
+        self.exposure = None
+        if self.cfg.exposure:
+            n_images = exposure_views if exposure_views is not None else len(cameras) if cameras is not None else None
+            if n_images is None:
+                raise ValueError("exposure=True needs the number of training images: Trainer(model, config, group, cameras=views) or "
+                                 "Trainer(..., exposure_views=V)")
+            self.exposure = exposure.ExposureTable(n_images, model.pos.device)       # (ValueError unless an integer >= 1)
         # filter3d: the camera records (host copy; on the model's device from the first step on) and the per-Gaussian filter
         self._cameras = filter3d.pack_cameras(cameras, "cpu") if cameras is not None and self.cfg.filter3d > 0 else None
         self._cameras_dev = None
@@ -384,8 +420,12 @@ class Trainer:
         An aux pass (TrainConfig.background / lambda_alpha / lambda_depth): a view may also carry 'alpha' [H, W] in [0, 1] (an
         'image' of [H, W, 4] is shorthand for rgb + alpha) and 'depth' [H, W] (camera-space z; <= 0 or non-finite: no data); the
         dict also has 'l_alpha' and 'l_depth' (device scalars like 'l1', 0 for a term that is off) and 'loss' is the whole total.
-        Otherwise those keys of a view are ignored, except that a 4-channel image is composited over black."""
+        Otherwise those keys of a view are ignored, except that a 4-channel image is composited over black.
+        exposure = True: every view carries 'idx', the integer in [0, V) of its training image (else ValueError, before anything is
+        queued); the dict also has 'lr_exposure', the learning rate the table was stepped at."""
         c, m = self.cfg, self.model
+        expo = self.exposure
+        view_rows = [expo.check_index(v.get('idx')) for v in views] if expo is not None else None
         aux_maps = c.lambda_alpha > 0 or c.lambda_depth > 0
         aux_pass = aux_maps or self._background is not None
         bg = self.background(iteration)
@@ -412,6 +452,9 @@ class Trainer:
         params, scale_in, opacity_in = m.get_params(), m.scale_raw, m.opacity_raw
         for attempt in range(4):
             self.optimizer.zero_grad()
+            if expo is not None:
+                # on the caller's stream, before the views' streams wait on it: a repeated pass counts nothing twice
+                expo.zero_grad()
             if f3:
                 # the effective scale and opacity of this pass: ONE launch, on the caller's stream before the views' streams wait on it, and
                 # two fresh leaves -- their gradients start empty in every attempt, so a repeated pass counts nothing twice.  The routes get
@@ -452,7 +495,15 @@ class Trainer:
                         st.wait_stream(main)                                           # parameters, zeroed gradients
                     per_view, per_view_aux = [], []
                     self._pass_dirty = screen
+                    row_stream = {}
                     for k, v in enumerate(views):
+                        if expo is not None and side:
+                            # two views of one training image add into ONE row of the table's gradient: the later one's stream waits
+                            # for the earlier one's, so that the row is their sum in view order whichever streams they ran on
+                            last = row_stream.get(view_rows[k])
+                            if last is not None and last != k % len(side):
+                                side[k % len(side)].wait_stream(side[last])
+                            row_stream[view_rows[k]] = k % len(side)
                         with (torch.cuda.stream(side[k % len(side)]) if side else contextlib.nullcontext()):
                             if aux_pass:
                                 image_gt, alpha_gt, depth_gt = self._view_targets(v, dev, bg)
@@ -468,6 +519,8 @@ class Trainer:
                                                                 **degree_kw, **self._filter_kw, **aux_kw)
                             if aux_maps:
                                 rendered, depth, alpha = rendered
+                            if expo is not None:
+                                rendered = expo.apply_view(rendered, view_rows[k])
                             loss, vals = losses.compute_loss_device(rendered, image_gt, c.lambda_l1, c.lambda_ssim, scale=1.0 / n_global)
                             if aux_maps:
                                 aux_total, aux_vals = losses.aux_loss(depth, alpha, depth_gt, alpha_gt, c.lambda_depth, c.lambda_alpha,
@@ -543,6 +596,16 @@ class Trainer:
                 break
         else:
             raise RuntimeError("the pair buffers overflowed four times in a row")
+        lr_expo = {}
+        if expo is not None:
+            # (the ranks agreed STATUS_OK above, so every rank is here: none can be left in the collective.)  The table's gradient is
+            # complete on this rank -- the caller's stream has waited for the views' streams; summed over the ranks, every replica
+            # steps the same bits.  The table's own Adam, at this iteration's exposure learning rate
+            if world > 1:
+                dp.allreduce_exposure_grad(expo.grad, self.group)
+            lr_expo = {'lr_exposure': optim.position_lr(iteration, c.exposure_lr_init, c.exposure_lr_final, c.exposure_lr_delay_mult,
+                                                        c.exposure_lr_max_steps)}
+            expo.step(lr_expo['lr_exposure'])
         if f3 and (scale_in.grad is not None or opacity_in.grad is not None):
             # the gradients of the two leaves are complete (every view; every rank: after the exchange's all-reduce): ONE launch takes them
             # through the filter to the raw parameters -- linear in the gradient and row-local, so exact after the sum and the same on
@@ -581,7 +644,7 @@ class Trainer:
                 densified = True
             return {'loss': reg[2], 'l1': acc[0], 'ssim': acc[1], 'reg_opacity': reg[0], 'reg_scale': reg[1],
                     'gaussians': m.get_num_gaussians(), 'lr_pos': pos_lr, 'densified': densified, 'sh_degree': sh_degree,
-                    **(dict(l_alpha=acc_aux[0], l_depth=acc_aux[1]) if aux_pass else {})}
+                    **(dict(l_alpha=acc_aux[0], l_depth=acc_aux[1]) if aux_pass else {}), **lr_expo}
         if iteration < c.densify_until_iter and iteration % c.densification_interval == 0:
             if screen:
                 if world > 1:                     # every rank decides from the statistics of all views: the replicas stay bit-identical
@@ -603,6 +666,7 @@ class Trainer:
                'densified': densified, 'sh_degree': sh_degree}
         if aux_pass:
             out.update(loss=acc[2] + acc_aux[2], l_alpha=acc_aux[0], l_depth=acc_aux[1])
+        out.update(lr_expo)
         return out
 
 

@@ -622,6 +622,29 @@ int gsplat_filter3d_apply(int64_t n, const float* scale_raw, const float* opacit
 int gsplat_filter3d_apply_backward(int64_t n, const float* scale_raw, const float* opacity_raw, const float* filt, const float* g_scale_out,
                                    const float* g_opacity_out, float* g_scale_raw, float* g_opacity_raw, int32_t accumulate, void* stream);
 
+/* ---- per-view exposure compensation (not in the reference) ---------------------------------------------------------
+ * An affine colour transform per image, E = [M | t], twelve floats row-major 3 x 4, applied to a frame before the loss:
+ *     o_r = fma(M_r0, c_0, fma(M_r1, c_1, fma(M_r2, c_2, t_r)))      (no clamp; the identity returns every finite c bit for bit)
+ * image, out, grad_out, grad_image: [batch, H, W, 3] floats; params: [batch, 12].  Every entry runs on the caller's stream, reads
+ * nothing back and allocates nothing.  H, W, batch > 0 and batch <= 65535, else GSPLAT_ERR_BAD_ARG (gsplat_exposure_scratch_bytes: -1),
+ * as for a NULL required pointer -- before anything is launched.  Arrays 4-byte aligned; 16-byte aligned ones are read 16 bytes at a
+ * time, with the same bits.  No output may alias an input.
+ * Forward: one launch.
+ * Backward: grad_image[k] = sum_r M_rk grad_out[r] per pixel (grad_image == NULL: not computed), and
+ *     grad_params[r, k] = sum over the pixels of grad_out[r] c_k (k < 3),  grad_params[r, 3] = sum over the pixels of grad_out[r]
+ *   (grad_params == NULL: not computed; scratch may then be NULL).  The sums are formed in a fixed order without float atomics -- per
+ *   thread, per wave, per workgroup in fp32, over the workgroups in double -- so they are the same bits on every call, stream and launch.
+ *   The twelve floats of image b go to row b of grad_params, or to row row_index[b] when row_index (batch int32 on the device; a
+ *   negative entry drops the row) is given; the rows named must be distinct.  flags: GSPLAT_EXPOSURE_ACCUMULATE adds to the
+ *   destination rows instead of overwriting them; any other bit is refused first ("unknown flag").
+ *   scratch: gsplat_exposure_scratch_bytes(batch, H, W) device bytes, any contents; one call at a time per scratch buffer.
+ *   One launch, two with grad_params.                                                                                             */
+#define GSPLAT_EXPOSURE_ACCUMULATE 1
+int64_t gsplat_exposure_scratch_bytes(int64_t batch, int32_t H, int32_t W);
+int gsplat_exposure_forward(const float* image, const float* params, int64_t batch, int32_t H, int32_t W, float* out, void* stream);
+int gsplat_exposure_backward(const float* image, const float* params, const float* grad_out, int64_t batch, int32_t H, int32_t W,
+                             float* grad_image, float* grad_params, const int32_t* row_index, int32_t flags, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
