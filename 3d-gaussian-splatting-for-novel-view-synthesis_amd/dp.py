@@ -68,6 +68,29 @@ def agree_status(code, group=None, device=None):
     return int(t.item())
 
 
+def status_of(err):
+    """The status code of what a rank's own work ended with: None -> STATUS_OK, the reference's off-screen Exception (render.py:235-236)
+    -> STATUS_OFFSCREEN, any other exception -> STATUS_ERROR.  (STATUS_REDO is the caller's: only a training pass can be repeated.)"""
+    from . import ops
+    if err is None:
+        return STATUS_OK
+    return STATUS_OFFSCREEN if str(err) == ops.OFFSCREEN_MSG else STATUS_ERROR
+
+
+def raise_agreed(status, err, what):
+    """After agree_status(): every rank raises, or none does.  A status below STATUS_OFFSCREEN returns; otherwise the rank that failed
+    raises its own exception `err`, and a rank that did not (err None) raises what its peer's status stands for -- the off-screen
+    Exception, or a RuntimeError naming `what` was running."""
+    from . import ops
+    if status < STATUS_OFFSCREEN:
+        return
+    if err is not None:
+        raise err
+    if status == STATUS_OFFSCREEN:
+        raise Exception(ops.OFFSCREEN_MSG + " (on another rank of the data-parallel group)")
+    raise RuntimeError(f"another rank of the data-parallel group failed in {what}")
+
+
 def _big_and_small(grads):
     """Split a list of gradient tensors into the largest (sent in place) and the rest (flattened together)."""
     order = sorted(range(len(grads)), key=lambda i: grads[i].numel(), reverse=True)

@@ -31,6 +31,7 @@ number of views; the split noise of densification comes from a generator seeded 
 replicas stay bit-identical without a broadcast.
 """
 import contextlib
+import types
 from dataclasses import dataclass
 
 import torch
@@ -160,33 +161,50 @@ class TrainConfig:
     exposure_lr_max_steps: int = 30000
 
     def __post_init__(self):
-        _check_absgrad(self)
-        _check_sparse_adam(self)
-        _check_filter3d(self)
-        _check_exposure(self)
+        _validate(self)
 
 
-def _check_absgrad(cfg):
+def _need_finite(cfg, *names, at_least=0):
+    """The numeric predicate of the checks below, for each of the fields `names`: an int or a float -- not a bool --, not NaN, finite
+    and >= at_least."""
+    for name in names:
+        x = getattr(cfg, name)
+        if not (isinstance(x, (int, float)) and not isinstance(x, bool) and at_least <= x < float("inf")):
+            raise ValueError(f"{name} must be a finite number >= {at_least}, not {x!r}")
+
+
+def _validate(cfg, cameras=False, exposure_views=None):
+    """Every check of a TrainConfig, in ONE order: ValueError for the first field that fails.  TrainConfig(...) itself -- the call
+    without `cameras` -- refuses only the absgrad, sparse_adam, filter3d and exposure groups.  A Trainer checks every field (the four
+    groups again: the fields of a config can be set after it is made) together with what its constructor was given -- `cameras` (None:
+    it was given none) and `exposure_views` --, and gets back what it keeps of the checks: the filter keyword arguments of its renders
+    and the background in the form background() returns."""
+    trainer = cameras is not False
+    if trainer:
+        if cfg.densify_rule not in ("reference", "screen", "mcmc"):
+            raise ValueError(f"densify_rule must be 'reference', 'screen' or 'mcmc', not {cfg.densify_rule!r}")
+        # the MCMC fields: a value the rule cannot run with is refused whatever the rule is
+        if type(cfg.cap_max) is not int or not 1 <= cfg.cap_max < 2 ** 31:
+            raise ValueError(f"cap_max must be an integer in [1, 2^31), not {cfg.cap_max!r}")
+        if type(cfg.mcmc_start_iter) is not int or cfg.mcmc_start_iter < 0:
+            raise ValueError(f"mcmc_start_iter must be an integer >= 0, not {cfg.mcmc_start_iter!r}")
+        if not (isinstance(cfg.mcmc_min_opacity, float) and 0.0 < cfg.mcmc_min_opacity < 1.0):
+            raise ValueError(f"mcmc_min_opacity must be a float in (0, 1), not {cfg.mcmc_min_opacity!r}")
+        _need_finite(cfg, "mcmc_noise_lr", "mcmc_opacity_reg", "mcmc_scale_reg")
+        _need_finite(cfg, "mcmc_growth", at_least=1)
+        if type(cfg.mcmc_seed) is not int or not 0 <= cfg.mcmc_seed < 2 ** 64:
+            raise ValueError(f"mcmc_seed must be an integer in [0, 2^64), not {cfg.mcmc_seed!r}")
+    # ---- the four groups TrainConfig(...) refuses too
     if type(cfg.densify_absgrad) is not bool:
         raise ValueError(f"densify_absgrad must be a bool, not {cfg.densify_absgrad!r}")
     if cfg.densify_absgrad and cfg.densify_rule != "screen":
         raise ValueError(f"densify_absgrad=True needs densify_rule='screen' (the other rules read no screen-space statistic), not {cfg.densify_rule!r}")
-
-
-def _check_sparse_adam(cfg):
     if type(cfg.sparse_adam) is not bool:
         raise ValueError(f"sparse_adam must be a bool, not {cfg.sparse_adam!r}")
     if cfg.sparse_adam and cfg.densify_rule == "mcmc":
         raise ValueError("sparse_adam=True is not available with densify_rule='mcmc' (its regularisers give every row a gradient and its "
                          "noise step assumes a dense optimiser)")
-
-
-def _check_filter3d(cfg, cameras=False):
-    """The filter3d fields of a TrainConfig (ValueError); `cameras`: the trainer's (None: it was given none), False: not known yet."""
-    for name in ("filter3d", "filter3d_near", "filter3d_margin"):
-        x = getattr(cfg, name)
-        if isinstance(x, bool) or not isinstance(x, (int, float)) or not 0.0 <= x < float("inf"):
-            raise ValueError(f"{name} must be a finite number >= 0, not {x!r}")
+    _need_finite(cfg, "filter3d", "filter3d_near", "filter3d_margin")
     if type(cfg.filter3d_interval) is not int or cfg.filter3d_interval < 1:
         raise ValueError(f"filter3d_interval must be an integer >= 1, not {cfg.filter3d_interval!r}")
     if cfg.filter3d > 0 and cfg.densify_rule == "mcmc":
@@ -194,14 +212,61 @@ def _check_filter3d(cfg, cameras=False):
                          "unfiltered opacity and scale)")
     if cfg.filter3d > 0 and cameras is None:
         raise ValueError("filter3d > 0 needs the cameras of the whole training set: Trainer(model, config, group, cameras=views)")
-
-
-def _check_exposure(cfg):
     if type(cfg.exposure) is not bool:
         raise ValueError(f"exposure must be a bool, not {cfg.exposure!r}")
+    if not trainer:
+        return None
+    # ---- the rest is the Trainer's alone
+    if cfg.exposure and exposure_views is None and cameras is None:
+        raise ValueError("exposure=True needs the number of training images: Trainer(model, config, group, cameras=views) or "
+                         "Trainer(..., exposure_views=V)")
+    if type(cfg.sh_degree_interval) is not int or cfg.sh_degree_interval < 0:
+        raise ValueError(f"sh_degree_interval must be an integer >= 0, not {cfg.sh_degree_interval!r}")
+    filter_kw = _abi.filter_kwargs(cfg.lowpass, cfg.antialias)      # (ValueError for a mode the kernels cannot do)
+    background = _check_background(cfg.background)
+    if type(cfg.background_seed) is not int:
+        raise ValueError(f"background_seed must be an integer, not {cfg.background_seed!r}")
+    _need_finite(cfg, "lambda_alpha", "lambda_depth")
+    return filter_kw, background
+
+
+def _check_background(background):
+    """TrainConfig.background as the trainer keeps it: None, "random" or a tuple of three floats in [0, 1] (ValueError otherwise)."""
+    if background is None or (isinstance(background, str) and background == "random"):
+        return background
+    try:
+        vals = tuple(float(x) for x in background) if not isinstance(background, str) else None
+    except (TypeError, ValueError):
+        vals = None
+    if vals is None or len(vals) != 3 or not all(0.0 <= x <= 1.0 for x in vals):
+        raise ValueError(f"background must be None, 'random' or three numbers (r, g, b) in [0, 1], not {background!r}")
+    return vals
+
+
+def _keyed_generator(seed, iteration):
+    """A CPU generator keyed by (seed, iteration): the same stream of numbers on every rank and in a repeated pass, with no message."""
+    g = torch.Generator()
+    g.manual_seed(seed * 1000003 + int(iteration))
+    return g
+
+
+def _add_in_view_order(acc, per_view, main):
+    """acc += the views' loss vectors, on the caller's stream `main` (None: the views ran on it), in view order."""
+    for vals in per_view:
+        if main is not None:
+            vals.record_stream(main)              # (allocated on the view's stream)
+        acc += vals
+
+
+def _total(acc, acc_aux):
+    """The loss of a pass from its two sum vectors (acc_aux None: no aux pass)."""
+    return acc[2] if acc_aux is None else acc[2] + acc_aux[2]
 
 
 _side_streams = {}           # per device: the two streams the views of an iteration alternate between (TrainConfig.view_streams)
+_NO_CONTEXT = contextlib.nullcontext()      # (reusable: what a view enters where it has no stream or no statistics record of its own)
+# the route of a pass that has none: autograd gets every gradient, and its consumer only says so
+_NO_ROUTE = contextlib.nullcontext(types.SimpleNamespace(route_kind=ops.PLAIN))
 
 
 class Trainer:
@@ -222,36 +287,16 @@ class Trainer:
         self.model = model
         self.cfg = config or TrainConfig()
         self.group = group
-        if self.cfg.densify_rule not in ("reference", "screen", "mcmc"):
-            raise ValueError(f"densify_rule must be 'reference', 'screen' or 'mcmc', not {self.cfg.densify_rule!r}")
-        _check_mcmc(self.cfg)
-        _check_absgrad(self.cfg)                # (again: the fields of a config can be set after it is made)
-        _check_sparse_adam(self.cfg)
-        _check_filter3d(self.cfg, cameras)
-        _check_exposure(self.cfg)
+        self._filter_kw, self._background = _validate(self.cfg, cameras, exposure_views)
         self.exposure = None
         if self.cfg.exposure:
-            n_images = exposure_views if exposure_views is not None else len(cameras) if cameras is not None else None
-            if n_images is None:
-                raise ValueError("exposure=True needs the number of training images: Trainer(model, config, group, cameras=views) or "
-                                 "Trainer(..., exposure_views=V)")
+            n_images = exposure_views if exposure_views is not None else len(cameras)
             self.exposure = exposure.ExposureTable(n_images, model.pos.device)       # (ValueError unless an integer >= 1)
         # filter3d: the camera records (host copy; on the model's device from the first step on) and the per-Gaussian filter
         self._cameras = filter3d.pack_cameras(cameras, "cpu") if cameras is not None and self.cfg.filter3d > 0 else None
         self._cameras_dev = None
         self.filter3d = None
-        if type(self.cfg.sh_degree_interval) is not int or self.cfg.sh_degree_interval < 0:
-            raise ValueError(f"sh_degree_interval must be an integer >= 0, not {self.cfg.sh_degree_interval!r}")
-        self._filter_kw = _abi.filter_kwargs(self.cfg.lowpass, self.cfg.antialias)      # (ValueError for a mode the kernels cannot do)
-        self._background = _check_background(self.cfg.background)
-        if type(self.cfg.background_seed) is not int:
-            raise ValueError(f"background_seed must be an integer, not {self.cfg.background_seed!r}")
-        for name in ("lambda_alpha", "lambda_depth"):
-            x = getattr(self.cfg, name)
-            if isinstance(x, bool) or not isinstance(x, (int, float)) or not 0.0 <= x < float("inf"):
-                raise ValueError(f"{name} must be a finite number >= 0, not {x!r}")
         self.optimizer = self._new_optimizer(self.cfg.position_lr_init)
-        self._gen = None
         # densify_rule = "screen": the statistics since the last densification (None until the first such step; not stored in
         # checkpoints: a resumed run starts its window at zero), and one pass record per view of an iteration
         self.densify_stats = None
@@ -265,6 +310,10 @@ class Trainer:
         groups = optim.reference_param_groups(self.model, position_lr_init=pos_lr, feature_lr=c.feature_lr,
                                               opacity_lr=c.opacity_lr, scaling_lr=c.scaling_lr, rotation_lr=c.rotation_lr)
         return optim.GaussianAdam(groups, lr=c.lr, eps=1e-15)
+
+    def _position_lr(self, iteration):
+        c = self.cfg
+        return optim.position_lr(iteration, c.position_lr_init, c.position_lr_final, c.position_lr_delay_mult, c.position_lr_max_steps)
 
     def _update_filter3d(self, iteration, dev):
         """self.filter3d for this iteration: recomputed (one library call, nothing read back) when it is missing or has another length
@@ -318,10 +367,7 @@ class Trainer:
         return 1
 
     def _densify_generator(self, iteration):
-        # same stream of split noise on every rank: CPU generator keyed by (seed, iteration)
-        g = torch.Generator()
-        g.manual_seed(self.cfg.densify_seed * 1000003 + iteration)
-        return g
+        return _keyed_generator(self.cfg.densify_seed, iteration)      # the same stream of split noise on every rank
 
     def background(self, iteration):
         """The background colour of iteration `iteration` (TrainConfig.background): None, the configured colour, or -- "random" --
@@ -329,17 +375,16 @@ class Trainer:
         pass, with no message."""
         if self._background != "random":
             return self._background
-        g = torch.Generator()
-        g.manual_seed(self.cfg.background_seed * 1000003 + int(iteration))
-        return tuple(torch.rand(3, generator=g).tolist())
+        return tuple(torch.rand(3, generator=_keyed_generator(self.cfg.background_seed, iteration)).tolist())
 
-    def _view_targets(self, v, dev, bg):
-        """(image, alpha, depth) targets of one view of an aux pass, on the device: the image over the background where the view
-        has an alpha (over black without a background), alpha / depth None unless their weight is > 0 -- and then a view
-        without one is an error of that view (ValueError)."""
+    def _view_targets(self, v, dev, bg, aux_pass):
+        """(image, alpha, depth) targets of one view, on the device.  An aux pass: the image over the background where the view has an
+        alpha ('alpha', or a 4-channel 'image'; over black without a background), alpha / depth None unless their weight is > 0 --
+        and then a view without one is an error of that view (ValueError).  Any other pass reads neither 'alpha' nor 'depth' (both
+        weights are 0 there): a 4-channel image goes over black by its own alpha, and that is all."""
         c = self.cfg
         image = torch.as_tensor(v['image']).to(dev)
-        alpha = v.get('alpha')
+        alpha = v.get('alpha') if aux_pass else None
         if alpha is not None:
             alpha = torch.as_tensor(alpha).to(dev)
         if image.shape[-1] == 4:
@@ -392,18 +437,10 @@ class Trainer:
         if world > 1:
             # as in step(): what happened on this rank as ONE code and ONE agreement, so that a rank whose pose is off screen does not
             # leave its peers waiting in the all-reduce -- every rank raises, or none does, and nothing is pruned anywhere
-            status = dp.STATUS_OK if err is None else (dp.STATUS_OFFSCREEN if str(err) == ops.OFFSCREEN_MSG else dp.STATUS_ERROR)
-            status = dp.agree_status(status, self.group, device=dev)
-            if status != dp.STATUS_OK:
-                if err is not None:
-                    raise err
-                if status == dp.STATUS_OFFSCREEN:
-                    raise Exception(ops.OFFSCREEN_MSG + " (on another rank of the data-parallel group)")
-                raise RuntimeError("another rank of the data-parallel group failed in prune_by_contribution")
+            dp.raise_agreed(dp.agree_status(dp.status_of(err), self.group, device=dev), err, "prune_by_contribution")
             stats.all_reduce(self.group)
         removed = m.prune_by_contribution(stats, min_weight_max=min_weight_max, keep_fraction=keep_fraction)
-        pos_lr = optim.position_lr(iteration, c.position_lr_init, c.position_lr_final, c.position_lr_delay_mult, c.position_lr_max_steps)
-        self.optimizer = self._new_optimizer(pos_lr)
+        self.optimizer = self._new_optimizer(self._position_lr(iteration))
         if self.densify_stats is not None:
             self.densify_stats.reset(m.get_num_gaussians())
         self._pass_stats, self._pass_dirty = [], False
@@ -424,189 +461,222 @@ class Trainer:
         exposure = True: every view carries 'idx', the integer in [0, V) of its training image (else ValueError, before anything is
         queued); the dict also has 'lr_exposure', the learning rate the table was stepped at."""
         c, m = self.cfg, self.model
-        expo = self.exposure
-        view_rows = [expo.check_index(v.get('idx')) for v in views] if expo is not None else None
+        # ---- the facts of this step
+        rows = [self.exposure.check_index(v.get('idx')) for v in views] if self.exposure is not None else None
         aux_maps = c.lambda_alpha > 0 or c.lambda_depth > 0
-        aux_pass = aux_maps or self._background is not None
+        aux = aux_maps if aux_maps or self._background is not None else None     # None: no aux pass; else: does it render the maps?
         bg = self.background(iteration)
-        aux_kw = dict(aux=aux_maps, background=bg) if aux_pass else {}
         sh_degree = self.sh_degree(iteration)
-        degree_kw = {} if sh_degree == 3 else {'sh_degree': sh_degree}      # (without a schedule the render call is the reference's)
-        world = self._world()
-        dev = m.pos.device
+        render_kw = dict(self._filter_kw)          # (without a schedule, a filter or an aux pass the render call is the reference's)
+        if sh_degree != 3:
+            render_kw['sh_degree'] = sh_degree
+        if aux is not None:
+            render_kw.update(aux=aux, background=bg)
+        world, dev = self._world(), m.pos.device
         even, n_global = dp.agree_on_views(len(views), self.group, views_per_rank, device=dev)
         if global_views is not None and int(global_views) != n_global:
             raise ValueError(f"global_views={global_views}, but the ranks hold {n_global} views in all")
-        pos_lr = optim.position_lr(iteration, c.position_lr_init, c.position_lr_final, c.position_lr_delay_mult,
-                                   c.position_lr_max_steps)
+        pos_lr = self._position_lr(iteration)
         self.optimizer.param_groups[0]['lr'] = pos_lr
         screen = c.densify_rule == "screen" and iteration < c.densify_until_iter
         pass_stats = self._prepare_stats(dev, len(views)) if screen else None
-        absgrad_kw = {'absgrad': True} if c.densify_absgrad else {}         # (the default call is the signed rule's)
-        sparse = c.sparse_adam
-        if sparse and (self.visible is None or self.visible.data.shape[0] != m.get_num_gaussians() or self.visible.data.device != dev):
+        if c.sparse_adam and (self.visible is None or self.visible.data.shape[0] != m.get_num_gaussians() or self.visible.data.device != dev):
             self.visible = ops.VisibleSet(m.get_num_gaussians(), dev)
-        f3 = c.filter3d > 0
-        if f3:
+        if c.filter3d > 0:
             self._update_filter3d(iteration, dev)
-        params, scale_in, opacity_in = m.get_params(), m.scale_raw, m.opacity_raw
+        # ---- the pass: repeated, on every rank or on none, while a view outgrows the pair buffers
         for attempt in range(4):
-            self.optimizer.zero_grad()
-            if expo is not None:
-                # on the caller's stream, before the views' streams wait on it: a repeated pass counts nothing twice
-                expo.zero_grad()
-            if f3:
-                # the effective scale and opacity of this pass: ONE launch, on the caller's stream before the views' streams wait on it, and
-                # two fresh leaves -- their gradients start empty in every attempt, so a repeated pass counts nothing twice.  The routes get
-                # the parameter dict with the two leaves in place: their addresses are the same for every view of the pass
-                with torch.no_grad():
-                    scale_in, opacity_in = filter3d.apply(m.scale_raw.detach(), m.opacity_raw.detach(), self.filter3d)
-                scale_in.requires_grad_(True)
-                opacity_in.requires_grad_(True)
-                params = {**m.get_params(), 'scale_raw': scale_in, 'opacity_raw': opacity_in}
-            acc = torch.zeros(3, dtype=torch.float32, device=dev)
-            acc_aux = torch.zeros(3, dtype=torch.float32, device=dev) if aux_pass else None
-            # the route of the gradients (ops.gradient_route): data parallel, SH gradients in factored form (dp.FactoredExchange, 2.6x
-            # fewer bytes over xGMI at 8 views); one view, the Adam step of f_rest inside its backward; several, their sum in the backward
-            # sparse_adam with several views on one process takes the exchange's route too (no collective there): the SH gradients are
-            # then rounded as a group of ranks rounds them, and a group steps the bits of one process given all its views
-            exchange = (dp.FactoredExchange(params, world_views=1, group=self.group, equal_views=even, sh_degree=sh_degree)
-                        if world > 1 or (sparse and len(views) > 1) else None)
-            # (an aux pass: no route on one process -- its frames take the separate library calls)
-            fold = exchange is None and len(views) == 1 and c.fold_rest_step and not aux_pass and not sparse
-            sum_in_kernel = exchange is None and len(views) > 1 and c.sum_views_in_kernel and not aux_pass
-            route = (exchange if exchange is not None else self.optimizer.fused_rest_update(m.f_rest) if fold
-                     else ops.accumulate_grads(params) if sum_in_kernel else None)
-            pass_error = checks = consumer = None
-            try:
-                # no host synchronisation per view: the renders size their buffers from earlier frames, the per-frame checks
-                # (off-screen exception, buffer capacity) are made ONCE, after the last backward is queued
-                with contextlib.ExitStack() as stack:
-                    checks = stack.enter_context(ops.deferred_checks())
-                    consumer = stack.enter_context(route) if route is not None else None
-                    side = self._view_streams(dev) if (c.view_streams > 1 and len(views) > 1 and world == 1) else ()     # (one process: the
-                    # exchange's collectives of a data-parallel pass stay on the caller's stream)
-                    main = torch.cuda.current_stream(dev) if side else None
-                    if sparse:
-                        # zeroed in every attempt, on the caller's stream, before the side streams wait on it: a repeated pass
-                        # counts nothing from the failed one (whose streams the caller's stream has waited for)
-                        self.visible.reset()
-                    for st in side:
-                        st.wait_stream(main)                                           # parameters, zeroed gradients
-                    per_view, per_view_aux = [], []
-                    self._pass_dirty = screen
-                    row_stream = {}
-                    for k, v in enumerate(views):
-                        if expo is not None and side:
-                            # two views of one training image add into ONE row of the table's gradient: the later one's stream waits
-                            # for the earlier one's, so that the row is their sum in view order whichever streams they ran on
-                            last = row_stream.get(view_rows[k])
-                            if last is not None and last != k % len(side):
-                                side[k % len(side)].wait_stream(side[last])
-                            row_stream[view_rows[k]] = k % len(side)
-                        with (torch.cuda.stream(side[k % len(side)]) if side else contextlib.nullcontext()):
-                            if aux_pass:
-                                image_gt, alpha_gt, depth_gt = self._view_targets(v, dev, bg)
-                            else:
-                                image_gt = torch.as_tensor(v['image']).to(dev)
-                                if image_gt.shape[-1] == 4:            # rgb + alpha: over black
-                                    image_gt = losses.composite_over(image_gt[..., :3], image_gt[..., 3], (0.0, 0.0, 0.0))
-                            c2w = torch.as_tensor(v['c2w'], dtype=torch.float32).to(dev)
-                            with (ops.densify_stats(pass_stats[k], **absgrad_kw) if screen else contextlib.nullcontext()), \
-                                    (ops.visible_set(self.visible) if sparse else contextlib.nullcontext()):
-                                rendered = ops.render_gaussians(m.pos, m.f_dc, m.f_rest, opacity_in, scale_in, m.q_raw, c2w,
-                                                                int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']),
-                                                                **degree_kw, **self._filter_kw, **aux_kw)
-                            if aux_maps:
-                                rendered, depth, alpha = rendered
-                            if expo is not None:
-                                rendered = expo.apply_view(rendered, view_rows[k])
-                            loss, vals = losses.compute_loss_device(rendered, image_gt, c.lambda_l1, c.lambda_ssim, scale=1.0 / n_global)
-                            if aux_maps:
-                                aux_total, aux_vals = losses.aux_loss(depth, alpha, depth_gt, alpha_gt, c.lambda_depth, c.lambda_alpha,
-                                                                      scale=1.0 / n_global)
-                                torch.autograd.backward((loss, aux_total))      # loss + aux_total, one pass through the render's backward
-                                per_view_aux.append(aux_vals)
-                            else:
-                                loss.backward()                        # (loss / batch size: the division is inside the loss kernels)
-                            per_view.append(vals)
-                    for st in side:
-                        main.wait_stream(st)
-                    if side and exchange is not None:
-                        for t in exchange.logits + exchange.eyes:                      # (allocated on a view's stream, read by finish() on the caller's)
-                            t.record_stream(main)
-                    if sum_in_kernel:
-                        consumer.assign()
-                    for vals in per_view:                                              # (on the caller's stream, in view order)
-                        if side:
-                            vals.record_stream(main)
-                        acc += vals
-                    for vals in per_view_aux:
-                        if side:
-                            vals.record_stream(main)
-                        acc_aux += vals
-            except Exception as e:                # single process: nothing to agree on, the exception leaves as it is
-                if world == 1:
-                    raise
-                pass_error = e
-            # ---- what happened on this rank, as ONE code; then ONE agreement over the ranks.  Nothing may leave this function
-            # between the first collective of the pass and the agreement: a rank that raised here while its peers sat in the
-            # exchange would leave them waiting for ever.
-            status, err = dp.STATUS_OK, None
-            try:
-                if checks is not None:
-                    checks.verify()
-                if exchange is not None and exchange.n_added != len(views):
-                    raise RuntimeError(f"{exchange.n_added} of this rank's {len(views)} views went through the factored exchange: a render "
-                                       "of this model took the ordinary backward (are f_dc / f_rest the model's own tensors?)")
-            except ops.PairCapacityExceeded:
-                status = dp.STATUS_REDO           # a view outgrew the buffers: this pass's gradients are invalid (capacity now raised)
-            except Exception as e:                # the reference's off-screen Exception (render.py:235-236), or anything else
-                status, err = (dp.STATUS_OFFSCREEN if str(e) == ops.OFFSCREEN_MSG else dp.STATUS_ERROR), e
-            if status != dp.STATUS_OK and fold:
-                consumer.rollback()               # (the kernel stepped nothing for a frame that overflowed or is off screen: nothing counts)
-            if pass_error is not None:            # an exception inside the render loop itself (a frame that waited for its counters, a device error)
-                err = pass_error
-                status = dp.STATUS_OFFSCREEN if str(err) == ops.OFFSCREEN_MSG else dp.STATUS_ERROR
-            if world > 1:                         # every rank repeats the pass, or none does; every rank raises, or none does
-                if exchange is not None:
-                    exchange.pad_views(len(views))          # (a pass that stopped early: keep the sequence of collectives aligned)
-                status = dp.agree_status(status, self.group, device=dev)
-            if screen:
-                # the caller's stream has waited for the views' streams: the pass records join the window in view order (and are zero
-                # again); a pass that is repeated or fails counts nothing -- its valid views would otherwise count twice
-                if status == dp.STATUS_OK:
-                    for rec in pass_stats:
-                        self.densify_stats.merge_(rec)
-                    self._pass_dirty = False
-                else:
-                    self._clear_pass_stats(dev)
-            if exchange is not None:
-                if status != dp.STATUS_OK:
-                    exchange.abandon()
-                else:
-                    exchange.finish()             # the loss was already divided by the global batch: world_views = 1
-            if status >= dp.STATUS_OFFSCREEN:
-                if err is not None:
-                    raise err
-                if status == dp.STATUS_OFFSCREEN:
-                    raise Exception(ops.OFFSCREEN_MSG + " (on another rank of the data-parallel group)")
-                raise RuntimeError("another rank of the data-parallel group failed in this training step")
-            if status == dp.STATUS_OK:
+            consumer, checks, error, leaves, acc, acc_aux = self._run_pass(views, rows, n_global, render_kw, aux, bg, pass_stats,
+                                                                           world, even, sh_degree)
+            if self._settle_pass(len(views), consumer, checks, error, pass_stats, world) == dp.STATUS_OK:
                 break
         else:
             raise RuntimeError("the pair buffers overflowed four times in a row")
-        lr_expo = {}
+        # ---- the update, the refinement, the result
+        lr_expo, reg = self._update(iteration, consumer, leaves, acc, acc_aux, world)
+        densified = self._refine(iteration, pos_lr, screen, world)
+        out = {'loss': reg[2] if reg is not None else _total(acc, acc_aux), 'l1': acc[0], 'ssim': acc[1],
+               'gaussians': m.get_num_gaussians(), 'lr_pos': pos_lr, 'densified': densified, 'sh_degree': sh_degree}
+        if reg is not None:
+            out.update(reg_opacity=reg[0], reg_scale=reg[1])
+        if aux is not None:
+            out.update(l_alpha=acc_aux[0], l_depth=acc_aux[1])
+        if lr_expo is not None:
+            out['lr_exposure'] = lr_expo
+        return out
+
+    def _choose_route(self, world, n_views, aux_pass, params, even, sh_degree):
+        """The route of a pass's gradients (ops.gradient_route), chosen ONCE per attempt: a context that yields the consumer.  Whatever
+        depends on the choice afterwards reads the consumer's route_kind ("none" below: _NO_ROUTE, kind PLAIN).  First match:
+
+            several ranks                                            FACTORED  the SH gradients in factored form (dp.FactoredExchange,
+                                                                               2.6x fewer bytes over xGMI at 8 views)
+            sparse_adam, several views                               FACTORED  the same exchange WITHOUT a collective: the SH gradients are
+                                                                               rounded as a group of ranks rounds them, so a group steps the
+                                                                               bits of one process given all its views
+            an aux pass                                              none      its frames take the separate library calls (the routes below
+                                                                               live on the composite entries, which have no aux variant)
+            one view, fold_rest_step, not sparse_adam                FOLDED    the Adam step of f_rest inside the backward (that kernel steps
+                                                                               every row: fold_rest_step is ignored under sparse_adam)
+            several views, sum_views_in_kernel                       SUMMED    the views' sum formed by the backward (ops.accumulate_grads)
+            anything else                                            none"""
+        c = self.cfg
+        if world > 1 or (c.sparse_adam and n_views > 1):
+            return dp.FactoredExchange(params, world_views=1, group=self.group, equal_views=even, sh_degree=sh_degree)
+        if aux_pass:
+            return _NO_ROUTE
+        if n_views == 1 and c.fold_rest_step and not c.sparse_adam:
+            return self.optimizer.fused_rest_update(self.model.f_rest)
+        if n_views > 1 and c.sum_views_in_kernel:
+            return ops.accumulate_grads(params)
+        return _NO_ROUTE
+
+    def _run_pass(self, views, rows, n_global, render_kw, aux, bg, pass_stats, world, even, sh_degree):
+        """One attempt at the pass: every view rendered and back-propagated, the losses summed.  Returns (the consumer of the gradient
+        route, the deferred checks, the exception that stopped the pass on a rank of several or None, the (scale, opacity) the views
+        were rendered from, the loss sums [l1, ssim, total], the aux sums [l_alpha, l_depth, total] or None).
+        Everything a pass adds into is zeroed HERE, in every attempt, on the caller's stream and before the side streams wait on it: a
+        repeated pass counts nothing from the failed one (whose streams the caller's stream has waited for)."""
+        c, m, expo = self.cfg, self.model, self.exposure
+        dev = m.pos.device
+        self.optimizer.zero_grad()
         if expo is not None:
-            # (the ranks agreed STATUS_OK above, so every rank is here: none can be left in the collective.)  The table's gradient is
-            # complete on this rank -- the caller's stream has waited for the views' streams; summed over the ranks, every replica
-            # steps the same bits.  The table's own Adam, at this iteration's exposure learning rate
+            expo.zero_grad()
+        params, scale_in, opacity_in = m.get_params(), m.scale_raw, m.opacity_raw
+        if c.filter3d > 0:
+            # the effective scale and opacity of this pass: ONE launch and two fresh leaves -- their gradients start empty in every
+            # attempt.  The routes get the parameter dict with the two leaves in place: their addresses are the same for every view
+            with torch.no_grad():
+                scale_in, opacity_in = filter3d.apply(m.scale_raw.detach(), m.opacity_raw.detach(), self.filter3d)
+            scale_in.requires_grad_(True)
+            opacity_in.requires_grad_(True)
+            params = {**params, 'scale_raw': scale_in, 'opacity_raw': opacity_in}
+        acc = torch.zeros(3, dtype=torch.float32, device=dev)
+        acc_aux = torch.zeros(3, dtype=torch.float32, device=dev) if aux is not None else None
+        route = self._choose_route(world, len(views), aux is not None, params, even, sh_degree)
+        consumer = route if world > 1 else None   # (the exchange is its own consumer: the settlement has it even if the pass stops before the `with`)
+        checks = error = None
+        try:
+            # no host synchronisation per view: the renders size their buffers from earlier frames, the per-frame checks
+            # (off-screen exception, buffer capacity) are made ONCE, after the last backward is queued
+            with ops.deferred_checks() as checks, route as consumer, (ops.visible_set(self.visible) if c.sparse_adam else _NO_CONTEXT):
+                if c.sparse_adam:
+                    self.visible.reset()
+                side = self._view_streams(dev) if (c.view_streams > 1 and len(views) > 1 and world == 1) else ()     # (one process: the
+                # exchange's collectives of a data-parallel pass stay on the caller's stream)
+                main = torch.cuda.current_stream(dev) if side else None
+                for st in side:
+                    st.wait_stream(main)                                           # parameters, zeroed gradients
+                self._pass_dirty = pass_stats is not None
+                per_view, per_view_aux, row_stream = [], [], {}
+                for k, v in enumerate(views):
+                    if rows is not None and side:
+                        # two views of one training image add into ONE row of the table's gradient: the later one's stream waits
+                        # for the earlier one's, so that the row is their sum in view order whichever streams they ran on
+                        last = row_stream.get(rows[k])
+                        if last is not None and last != k % len(side):
+                            side[k % len(side)].wait_stream(side[last])
+                        row_stream[rows[k]] = k % len(side)
+                    with (torch.cuda.stream(side[k % len(side)]) if side else _NO_CONTEXT):
+                        vals, aux_vals = self._view(v, rows[k] if rows is not None else None, scale_in, opacity_in, n_global, render_kw,
+                                                    aux, bg, pass_stats[k] if pass_stats is not None else None)
+                    per_view.append(vals)
+                    if aux_vals is not None:
+                        per_view_aux.append(aux_vals)
+                for st in side:
+                    main.wait_stream(st)
+                if side and consumer.route_kind == ops.FACTORED:
+                    for t in consumer.logits + consumer.eyes:                      # (allocated on a view's stream, read by finish() on the caller's)
+                        t.record_stream(main)
+                if consumer.route_kind == ops.SUMMED:
+                    consumer.assign()
+                _add_in_view_order(acc, per_view, main)
+                _add_in_view_order(acc_aux, per_view_aux, main)
+        except Exception as e:                # single process: nothing to agree on, the exception leaves as it is
+            if world == 1:
+                raise
+            error = e
+        return consumer, checks, error, (scale_in, opacity_in), acc, acc_aux
+
+    def _view(self, v, row, scale_in, opacity_in, n_global, render_kw, aux, bg, stats):
+        """One view of a pass, on the current stream: targets, render -- inside the view's statistics record `stats`, if any --, the
+        exposure of training image `row`, loss, backward.  Returns its loss vector and its aux-loss vector (None: no maps)."""
+        c, m = self.cfg, self.model
+        dev = m.pos.device
+        image_gt, alpha_gt, depth_gt = self._view_targets(v, dev, bg, aux is not None)
+        c2w = torch.as_tensor(v['c2w'], dtype=torch.float32).to(dev)
+        with (ops.densify_stats(stats, absgrad=c.densify_absgrad) if stats is not None else _NO_CONTEXT):
+            rendered = ops.render_gaussians(m.pos, m.f_dc, m.f_rest, opacity_in, scale_in, m.q_raw, c2w,
+                                            int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']), **render_kw)
+        if aux:
+            rendered, depth, alpha = rendered
+        if row is not None:
+            rendered = self.exposure.apply_view(rendered, row)
+        loss, vals = losses.compute_loss_device(rendered, image_gt, c.lambda_l1, c.lambda_ssim, scale=1.0 / n_global)
+        if not aux:
+            loss.backward()                        # (loss / batch size: the division is inside the loss kernels)
+            return vals, None
+        aux_total, aux_vals = losses.aux_loss(depth, alpha, depth_gt, alpha_gt, c.lambda_depth, c.lambda_alpha, scale=1.0 / n_global)
+        torch.autograd.backward((loss, aux_total))      # loss + aux_total, one pass through the render's backward
+        return vals, aux_vals
+
+    def _settle_pass(self, n_views, consumer, checks, error, pass_stats, world):
+        """What happened on this rank, as ONE code; then ONE agreement over the ranks: every rank repeats the pass, or none does; every
+        rank raises, or none does.  Returns dp.STATUS_OK or dp.STATUS_REDO.  NOTHING may leave this function between the first
+        collective of the pass and the agreement: a rank that raised here while its peers sat in the exchange would leave them waiting
+        for ever."""
+        dev = self.model.pos.device
+        kind = consumer.route_kind
+        status, err = dp.STATUS_OK, None
+        try:
+            if checks is not None:
+                checks.verify()
+            if kind == ops.FACTORED and consumer.n_added != n_views:
+                raise RuntimeError(f"{consumer.n_added} of this rank's {n_views} views went through the factored exchange: a render "
+                                   "of this model took the ordinary backward (are f_dc / f_rest the model's own tensors?)")
+        except ops.PairCapacityExceeded:
+            status = dp.STATUS_REDO           # a view outgrew the buffers: this pass's gradients are invalid (capacity now raised)
+        except Exception as e:                # the reference's off-screen Exception (render.py:235-236), or anything else
+            status, err = dp.status_of(e), e
+        if status != dp.STATUS_OK and kind == ops.FOLDED:
+            consumer.rollback()               # (the kernel stepped nothing for a frame that overflowed or is off screen: nothing counts)
+        if error is not None:                 # an exception inside the render loop itself (a frame that waited for its counters, a device error)
+            status, err = dp.status_of(error), error
+        if world > 1:
+            if kind == ops.FACTORED:
+                consumer.pad_views(n_views)   # (a pass that stopped early: keep the sequence of collectives aligned)
+            status = dp.agree_status(status, self.group, device=dev)
+        if pass_stats is not None:
+            # the caller's stream has waited for the views' streams: the pass records join the window in view order (and are zero
+            # again); a pass that is repeated or fails counts nothing -- its valid views would otherwise count twice
+            if status == dp.STATUS_OK:
+                for rec in pass_stats:
+                    self.densify_stats.merge_(rec)
+                self._pass_dirty = False
+            else:
+                self._clear_pass_stats(dev)
+        if kind == ops.FACTORED:
+            if status != dp.STATUS_OK:
+                consumer.abandon()
+            else:
+                consumer.finish()             # the loss was already divided by the global batch: world_views = 1
+        dp.raise_agreed(status, err, "this training step")
+        return status
+
+    def _update(self, iteration, consumer, leaves, acc, acc_aux, world):
+        """The optimiser steps of an iteration whose pass every rank agreed good -- so every rank is here, and none can be left in one
+        of the collectives below.  Returns (the exposure learning rate or None, mcmc.regularise's [reg_opacity, reg_scale, loss] or None)."""
+        c, m, expo = self.cfg, self.model, self.exposure
+        lr_expo = reg = None
+        if expo is not None:
+            # the table's gradient is complete on this rank -- the caller's stream has waited for the views' streams; summed over the
+            # ranks, every replica steps the same bits.  The table's own Adam, at this iteration's exposure learning rate
             if world > 1:
                 dp.allreduce_exposure_grad(expo.grad, self.group)
-            lr_expo = {'lr_exposure': optim.position_lr(iteration, c.exposure_lr_init, c.exposure_lr_final, c.exposure_lr_delay_mult,
-                                                        c.exposure_lr_max_steps)}
-            expo.step(lr_expo['lr_exposure'])
-        if f3 and (scale_in.grad is not None or opacity_in.grad is not None):
+            lr_expo = optim.position_lr(iteration, c.exposure_lr_init, c.exposure_lr_final, c.exposure_lr_delay_mult, c.exposure_lr_max_steps)
+            expo.step(lr_expo)
+        scale_in, opacity_in = leaves
+        if c.filter3d > 0 and (scale_in.grad is not None or opacity_in.grad is not None):
             # the gradients of the two leaves are complete (every view; every rank: after the exchange's all-reduce): ONE launch takes them
             # through the filter to the raw parameters -- linear in the gradient and row-local, so exact after the sum and the same on
             # every rank.  Before the zero-fill, the clip and the optimiser step, which see the raw gradients only
@@ -615,37 +685,41 @@ class Trainer:
                                    scale_in.grad if scale_in.grad is not None else torch.zeros_like(scale_in),
                                    opacity_in.grad if opacity_in.grad is not None else torch.zeros_like(opacity_in),
                                    m.scale_raw.grad, m.opacity_raw.grad)
-        names = dp.PARAM_NAMES
-        folded = fold and consumer.applied      # f_rest was stepped inside the backward pass: no gradient, no second step
-        for k in names:
+        # f_rest was stepped inside the backward pass: no gradient, no second step
+        folded = consumer.route_kind == ops.FOLDED and consumer.applied
+        for k in dp.PARAM_NAMES:
             p = getattr(m, k)
             if p.grad is None and not (folded and p is m.f_rest):
                 p.grad = torch.zeros_like(p)
-        use_mcmc = c.densify_rule == "mcmc"
-        if use_mcmc:
+        if c.densify_rule == "mcmc":
             # the gradients are complete (every view, every rank): the regularisers join them, and the loss, in ONE launch
-            reg = mcmc.regularise(m, c.mcmc_opacity_reg, c.mcmc_scale_reg, base=acc[2] + acc_aux[2] if aux_pass else acc[2])
+            reg = mcmc.regularise(m, c.mcmc_opacity_reg, c.mcmc_scale_reg, base=_total(acc, acc_aux))
         self.optimizer.clip_grad_norm_(m.pos, max_norm=1.0)
-        if sparse:
-            # (the ranks agreed STATUS_OK above, so every rank is here: none can be left in the collective.)  The union over the ranks:
-            # every rank steps the same rows and the replicas stay bit-identical -- one collective of N bytes per iteration
+        if c.sparse_adam:
+            # the union over the ranks: every rank steps the same rows and the replicas stay bit-identical -- one collective of N bytes
+            # per iteration
             if world > 1:
                 self.visible.all_reduce(self.group)
             self.optimizer.step(visible=self.visible)
         else:
             self.optimizer.step()
-        densified = False
-        if use_mcmc:
+        return lr_expo, reg
+
+    def _refine(self, iteration, pos_lr, screen, world):
+        """What follows the optimiser step: under MCMC the position noise and, at its interval, the relocation -- no densification, no
+        opacity reset --; else densification at its interval (a fresh optimiser at the current position learning rate) and the opacity
+        reset at its own.  Returns whether the set of Gaussians was refined."""
+        c, m = self.cfg, self.model
+        refine = bool(iteration < c.densify_until_iter and iteration % c.densification_interval == 0)
+        if c.densify_rule == "mcmc":
             mcmc.add_noise(m, pos_lr * c.mcmc_noise_lr, c.mcmc_seed, int(iteration))
-            if c.mcmc_start_iter <= iteration < c.densify_until_iter and iteration % c.densification_interval == 0:
+            refine = refine and bool(c.mcmc_start_iter <= iteration)
+            if refine:
                 # in place: the optimiser object and the moments of every row that did not change stay; nothing is read back
                 m.refine_mcmc(self.optimizer, cap_max=c.cap_max, min_opacity=c.mcmc_min_opacity, growth=c.mcmc_growth,
                               seed=c.mcmc_seed, iteration=int(iteration))
-                densified = True
-            return {'loss': reg[2], 'l1': acc[0], 'ssim': acc[1], 'reg_opacity': reg[0], 'reg_scale': reg[1],
-                    'gaussians': m.get_num_gaussians(), 'lr_pos': pos_lr, 'densified': densified, 'sh_degree': sh_degree,
-                    **(dict(l_alpha=acc_aux[0], l_depth=acc_aux[1]) if aux_pass else {}), **lr_expo}
-        if iteration < c.densify_until_iter and iteration % c.densification_interval == 0:
+            return refine
+        if refine:
             if screen:
                 if world > 1:                     # every rank decides from the statistics of all views: the replicas stay bit-identical
                     self.densify_stats.all_reduce(self.group)
@@ -659,45 +733,6 @@ class Trainer:
                 m.densify_and_prune(grads, opacity_threshold=c.prune_opacity_threshold, max_grad=c.max_grad,
                                     scale_threshold=c.scale_threshold, generator=self._densify_generator(iteration))
             self.optimizer = self._new_optimizer(pos_lr)
-            densified = True
         if iteration % c.opacity_reset_interval == 0:
             m.reset_opacity()
-        out = {'loss': acc[2], 'l1': acc[0], 'ssim': acc[1], 'gaussians': m.get_num_gaussians(), 'lr_pos': pos_lr,
-               'densified': densified, 'sh_degree': sh_degree}
-        if aux_pass:
-            out.update(loss=acc[2] + acc_aux[2], l_alpha=acc_aux[0], l_depth=acc_aux[1])
-        out.update(lr_expo)
-        return out
-
-
-def _check_mcmc(c):
-    """The MCMC fields of a TrainConfig (ValueError for a value the rule cannot run with), whatever the rule is."""
-    def real(x):
-        return isinstance(x, (int, float)) and not isinstance(x, bool) and x == x and abs(x) != float("inf")
-    if type(c.cap_max) is not int or not 1 <= c.cap_max < 2 ** 31:
-        raise ValueError(f"cap_max must be an integer in [1, 2^31), not {c.cap_max!r}")
-    if type(c.mcmc_start_iter) is not int or c.mcmc_start_iter < 0:
-        raise ValueError(f"mcmc_start_iter must be an integer >= 0, not {c.mcmc_start_iter!r}")
-    if not (isinstance(c.mcmc_min_opacity, float) and 0.0 < c.mcmc_min_opacity < 1.0):
-        raise ValueError(f"mcmc_min_opacity must be a float in (0, 1), not {c.mcmc_min_opacity!r}")
-    for name in ("mcmc_noise_lr", "mcmc_opacity_reg", "mcmc_scale_reg"):
-        x = getattr(c, name)
-        if not (real(x) and x >= 0):
-            raise ValueError(f"{name} must be a finite number >= 0, not {x!r}")
-    if not (real(c.mcmc_growth) and c.mcmc_growth >= 1.0):
-        raise ValueError(f"mcmc_growth must be a finite number >= 1, not {c.mcmc_growth!r}")
-    if type(c.mcmc_seed) is not int or not 0 <= c.mcmc_seed < 2 ** 64:
-        raise ValueError(f"mcmc_seed must be an integer in [0, 2^64), not {c.mcmc_seed!r}")
-
-
-def _check_background(background):
-    """TrainConfig.background as the trainer keeps it: None, "random" or a tuple of three floats in [0, 1] (ValueError otherwise)."""
-    if background is None or (isinstance(background, str) and background == "random"):
-        return background
-    try:
-        vals = tuple(float(x) for x in background) if not isinstance(background, str) else None
-    except (TypeError, ValueError):
-        vals = None
-    if vals is None or len(vals) != 3 or not all(0.0 <= x <= 1.0 for x in vals):
-        raise ValueError(f"background must be None, 'random' or three numbers (r, g, b) in [0, 1], not {background!r}")
-    return vals
+        return refine

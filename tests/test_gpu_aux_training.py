@@ -291,6 +291,68 @@ def test_a_view_without_its_target_raises_and_the_next_step_works():
     assert abs(float(a["loss"]) - float(b["loss"])) <= 1e-6 * float(b["loss"])
 
 
+# ---- every feature at once -------------------------------------------------------------------------------------------------------
+ALL_ON = dict(densify_rule="screen", densify_absgrad=True, sparse_adam=True, filter3d=0.2, exposure=True, lowpass=0.3, antialias=True,
+              sh_degree_interval=2, background="random", lambda_alpha=0.1, lambda_depth=0.1, densification_interval=2)
+
+
+def _bits_equal(a, b):
+    if not isinstance(a, torch.Tensor):
+        return a == b
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.reshape(-1).view(torch.uint8), b.reshape(-1).view(torch.uint8))
+
+
+def _all_on_run(s, views, streams):
+    """Four iterations with ALL_ON; after each one, everything the iteration leaves behind."""
+    model = _mod("model").GaussianModel({k: torch.tensor(s[k]) for k in NAMES}, device=DEV)
+    tr = _mod("training").Trainer(model, _mod("training").TrainConfig(view_streams=streams, **ALL_ON), cameras=views, exposure_views=3)
+    snaps = []
+    for it in (1, 2, 3, 4):
+        out = tr.step(it, views)
+        torch.cuda.synchronize()
+        snap = {("out", k): (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
+        for k in NAMES:
+            p = getattr(model, k)
+            st = tr.optimizer._state(p)
+            snap.update({("param", k): p.detach().clone(), ("exp_avg", k): st["exp_avg"].clone(), ("exp_avg_sq", k): st["exp_avg_sq"].clone(),
+                         ("adam_step", k): st["step"]})
+        st = tr.exposure.optimizer._state(tr.exposure.params)
+        snap.update(table=tr.exposure.params.clone(), table_grad=tr.exposure.grad.clone(), table_exp_avg=st["exp_avg"].clone(),
+                    table_exp_avg_sq=st["exp_avg_sq"].clone(), window=tr.densify_stats.data.clone(), visible=tr.visible.data.clone(),
+                    filter3d=tr.filter3d.clone())
+        snaps.append(snap)
+    return snaps
+
+
+def test_every_feature_at_once_gives_the_same_bits_on_one_stream_and_on_two(gs):
+    """Each feature is tested against the plain trainer; here they are all on together -- the screen rule with the absolute gradient,
+    the sparse optimiser (two views: the factored exchange without a collective), the 3D filter, the exposure table, low-pass with
+    antialiasing, the SH schedule, a random background and both aux weights.  Two views of ONE training image (one row of the table fed
+    from two streams), four iterations with a densification at the second and the fourth: under set_deterministic(True) the parameters,
+    the Adam moments, the exposure table, the densification window and every returned value are bit for bit the same with
+    view_streams = 2 and view_streams = 1, after every iteration.  (A first run leaves the pair capacities of every model size the run
+    goes through, so that the two compared runs queue the same frames in the same way.)"""
+    s, views = _scene()
+    views = [dict(v, idx=1) for v in views]
+    old = gs.set_deterministic(True)
+    try:
+        _all_on_run(s, views, 2)
+        two, one = _all_on_run(s, views, 2), _all_on_run(s, views, 1)
+    finally:
+        gs.set_deterministic(old)
+    assert [sn["out", "densified"] for sn in two] == [False, True, False, True]
+    assert [sn["out", "sh_degree"] for sn in two] == [0, 1, 1, 2]
+    eye = torch.eye(3, 4, device=DEV)
+    last = two[-1]
+    assert not torch.equal(last["table"][1], eye) and torch.equal(last["table"][0], eye) and torch.equal(last["table"][2], eye)
+    assert two[2]["window"][:, 1].any() and two[2]["visible"].any() and (last["filter3d"] > 0).any()
+    assert all(np.isfinite(float(sn["out", k])) for sn in two for k in ("loss", "l1", "ssim", "l_alpha", "l_depth"))
+    for it, (a, b) in enumerate(zip(two, one), 1):
+        assert set(a) == set(b)
+        for k in a:
+            assert _bits_equal(a[k], b[k]), (it, k)
+
+
 # ---- two ranks -------------------------------------------------------------------------------------------------------------------
 
 DP_CFG = dict(densification_interval=2, densify_until_iter=3, max_grad=1e-4, **AUX)

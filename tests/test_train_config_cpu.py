@@ -1,0 +1,57 @@
+"""The order of TrainConfig's checks, without a GPU: a config with TWO bad fields is refused for the same one every time -- by
+TrainConfig(...) itself, which refuses only the absgrad, sparse_adam, filter3d and exposure groups, and by Trainer(model, cfg), which
+checks every field (its constructor launches nothing).  Each field alone is covered by the tests of its feature; what is pinned here
+is which error comes FIRST, so that the checks can be reorganised without a caller seeing another message."""
+import importlib
+
+import pytest
+import torch
+
+PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
+training = importlib.import_module(PKG + ".training")
+
+# (the two bad fields, the start of TrainConfig(...)'s message or None where it constructs, the start of Trainer(model, cfg)'s message)
+CASES = [
+    (dict(densify_absgrad=1, filter3d_interval=0), "densify_absgrad must", "densify_absgrad must"),
+    (dict(densify_rule="paper", cap_max=0), None, "densify_rule must"),
+    (dict(sparse_adam="yes", background="blue"), "sparse_adam must", "sparse_adam must"),
+    (dict(sh_degree_interval=-1, lambda_depth=-1.0), None, "sh_degree_interval must"),
+    (dict(cap_max=0, densify_absgrad=1), "densify_absgrad must", "cap_max must"),
+    (dict(filter3d=-1.0, exposure="on"), "filter3d must", "filter3d must"),
+    (dict(filter3d_interval=0, filter3d_margin=float("nan")), "filter3d_margin must", "filter3d_margin must"),
+    (dict(exposure=1, sh_degree_interval=1.5), "exposure must", "exposure must"),
+    (dict(densify_rule="mcmc", sparse_adam=True, mcmc_growth=0.5), "sparse_adam=True is not available", "mcmc_growth must"),
+    (dict(densify_rule="mcmc", filter3d=0.2, sparse_adam=True), "sparse_adam=True is not available", "sparse_adam=True is not available"),
+    (dict(mcmc_seed=-1, mcmc_noise_lr=float("inf")), None, "mcmc_noise_lr must"),
+    (dict(filter3d=0.2, sh_degree_interval=-1), None, "filter3d > 0 needs the cameras"),           # (a Trainer without cameras)
+    (dict(exposure=True, lambda_alpha=-1.0), None, "exposure=True needs the number"),
+    (dict(lowpass=0.005, background="blue"), None, "lowpass must"),
+    (dict(antialias=True, lambda_depth=float("inf")), None, "antialias=True needs lowpass"),
+    (dict(background=(2.0, 0.0, 0.0), background_seed=1.5), None, "background must"),
+    (dict(background_seed=1.5, lambda_alpha=-1.0), None, "background_seed must"),
+    (dict(lambda_alpha=True, lambda_depth=float("inf")), None, "lambda_alpha must"),
+]
+
+
+def _model():
+    model_mod = importlib.import_module(PKG + ".model")
+    z = torch.zeros
+    return model_mod.GaussianModel(dict(pos=z(4, 3), f_dc=z(4, 3), f_rest=z(4, 45), opacity_raw=z(4), scale_raw=z(4, 3), q_raw=z(4, 4)), device="cpu")
+
+
+def _starts(message):
+    return "^" + message.replace("(", r"\(").replace(")", r"\)")
+
+
+@pytest.mark.parametrize("fields,from_config,from_trainer", CASES, ids=["+".join(c[0]) for c in CASES])
+def test_two_bad_fields_are_refused_for_the_same_one_as_ever(fields, from_config, from_trainer):
+    if from_config is None:
+        training.TrainConfig(**fields)                       # none of the four groups: the config constructs
+    else:
+        with pytest.raises(ValueError, match=_starts(from_config)):
+            training.TrainConfig(**fields)
+    cfg = training.TrainConfig()
+    for name, value in fields.items():                       # (set after it is made: only the Trainer sees them)
+        setattr(cfg, name, value)
+    with pytest.raises(ValueError, match=_starts(from_trainer)):
+        training.Trainer(_model(), cfg)
