@@ -33,6 +33,7 @@ GSPLAT_BACKWARD_ABSGRAD = 128
 GSPLAT_FILTER3D_CAMERA_FLOATS = 24
 GSPLAT_FILTER3D_CAMERA_CHUNK = 64
 GSPLAT_EXPOSURE_ACCUMULATE = 1
+GSPLAT_BILAGRID_ACCUMULATE = 1
 
 
 def sh_bands_dropped(degree):
@@ -215,6 +216,10 @@ SIGNATURES = {
     "gsplat_exposure_scratch_bytes": (_I64, [_I64, C.c_int32, C.c_int32]),
     "gsplat_exposure_forward": (_INT, [_VP, _VP, _I64, C.c_int32, C.c_int32, _VP, _VP]),
     "gsplat_exposure_backward": (_INT, [_VP, _VP, _VP, _I64, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
+    "gsplat_bilagrid_forward": (_INT, [_VP, _VP, _I64] + [C.c_int32] * 5 + [_VP, _VP]),
+    "gsplat_bilagrid_backward": (_INT, [_VP, _VP, _VP, _I64] + [C.c_int32] * 5 + [_VP, _VP, _VP, C.c_int32, _VP]),
+    "gsplat_bilagrid_tv_scratch_bytes": (_I64, [_I64, C.c_int32, C.c_int32, C.c_int32]),
+    "gsplat_bilagrid_tv": (_INT, [_VP, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_float, _VP, _VP, C.c_int32, _VP, _VP]),
 }
 
 _lib = None

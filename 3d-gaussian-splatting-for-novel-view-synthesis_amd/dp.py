@@ -155,9 +155,10 @@ def allreduce_gradients(grads, world_views, group=None):
     return grads
 
 
-def allreduce_exposure_grad(grad, group=None):
-    """Sum the gradient of the exposure table ([V, 3, 4], exposure.ExposureTable.grad) over the ranks, in place: ONE all-reduce (SUM) of
-    48 V bytes per iteration.  A row only one rank's views used arrives as that rank's bits (x + 0 is exact), and the sum of two ranks is
+def allreduce_table_grad(grad, group=None):
+    """Sum the gradient of a per-image table over the ranks, in place: ONE dense all-reduce (SUM) per iteration -- [V, 3, 4] of
+    exposure.ExposureTable.grad (48 V bytes) or [V, 12, L, Y, X] of bilagrid.BilateralGridTable.grad (48 L Y X bytes per image: 96 KiB
+    at the default shape).  A row only one rank's views used arrives as that rank's bits (x + 0 is exact), and the sum of two ranks is
     the same bits in either order, so two ranks with one view each end with the bits of one process given both views.  A collective:
     every rank calls it once per iteration, AFTER the ranks agreed STATUS_OK (agree_status) -- never on a path where a peer may have
     raised.  A single process: nothing happens."""
@@ -170,6 +171,9 @@ def allreduce_exposure_grad(grad, group=None):
         return grad
     dist.all_reduce(grad, op=dist.ReduceOp.SUM, group=group)
     return grad
+
+
+allreduce_exposure_grad = allreduce_table_grad           # (the name the exposure table's callers know)
 
 
 def data_parallel_step(render_fn, params, views, targets_grad_fn, world_views, group=None):

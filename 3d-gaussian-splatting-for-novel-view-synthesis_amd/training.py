@@ -25,6 +25,9 @@ Follows scripts/train.py:446-569 statement by statement, on the fused pieces of 
     [exposure, not in the reference; DESIGN.md §24]          per-view exposure compensation: each view's rendered colour goes through the
                                                affine transform of ITS training image (exposure.ExposureTable.apply_view) before the loss;
                                                the table has a gradient buffer, an Adam state and a learning-rate schedule of its own
+    [bilagrid, not in the reference; DESIGN.md §25]          per-view bilateral grids: instead of one affine transform per image, a grid of
+                                               them sliced at (x, y, luminance) (bilagrid.BilateralGridTable.apply_view), in the same
+                                               place and with the same ordering; a total-variation term joins the table's gradient once
 
 With data parallelism every rank holds the full model, renders its share of the batch's views and divides by the GLOBAL
 number of views; the split noise of densification comes from a generator seeded identically on all ranks, so the
@@ -37,7 +40,7 @@ from dataclasses import dataclass
 import torch
 import torch.distributed as dist
 
-from . import _abi, dp, exposure, filter3d, losses, mcmc, ops, optim
+from . import _abi, bilagrid, dp, exposure, filter3d, losses, mcmc, ops, optim
 
 
 @dataclass
@@ -159,6 +162,22 @@ class TrainConfig:
     exposure_lr_final: float = 0.001
     exposure_lr_delay_mult: float = 0.0
     exposure_lr_max_steps: int = 30000
+    # per-view bilateral grids (not in the reference; gsplat's use_bilateral_grid; bilagrid.py).  bilagrid = True (a bool,
+    # else ValueError): every training image has a grid of bilagrid_shape = (X, Y, L) affine colour transforms, the identity at the start,
+    # sliced at (pixel x, pixel y, pixel luminance) -- what an in-camera ISP does locally (tone mapping, vignetting) -- in the place of
+    # the exposure transform, which it contains: both at once is a ValueError (two tables on one colour are ill-conditioned).  The table
+    # (Trainer.bilagrid; Trainer(bilagrid_views=V) rows, len(cameras) by default) is trained by an Adam of its own (eps 1e-15, dense) at
+    # the learning rate optim.position_lr gives for the four numbers below, and bilagrid_tv times its total variation joins its gradient
+    # once per iteration.  The defaults follow gsplat's trainer -- taken from there and not measured here.  Everything said of exposure
+    # above about 'idx', the routes, the densify rules and novel views holds.  Off by default, and an iteration is then exactly the one
+    # above.
+    bilagrid: bool = False
+    bilagrid_shape: tuple = (16, 16, 8)
+    bilagrid_tv: float = 10.0
+    bilagrid_lr_init: float = 0.002
+    bilagrid_lr_final: float = 0.00002
+    bilagrid_lr_delay_mult: float = 0.0
+    bilagrid_lr_max_steps: int = 30000
 
     def __post_init__(self):
         _validate(self)
@@ -173,11 +192,11 @@ def _need_finite(cfg, *names, at_least=0):
             raise ValueError(f"{name} must be a finite number >= {at_least}, not {x!r}")
 
 
-def _validate(cfg, cameras=False, exposure_views=None):
+def _validate(cfg, cameras=False, exposure_views=None, bilagrid_views=None):
     """Every check of a TrainConfig, in ONE order: ValueError for the first field that fails.  TrainConfig(...) itself -- the call
-    without `cameras` -- refuses only the absgrad, sparse_adam, filter3d and exposure groups.  A Trainer checks every field (the four
+    without `cameras` -- refuses only the absgrad, sparse_adam, filter3d, exposure and bilagrid groups.  A Trainer checks every field (the five
     groups again: the fields of a config can be set after it is made) together with what its constructor was given -- `cameras` (None:
-    it was given none) and `exposure_views` --, and gets back what it keeps of the checks: the filter keyword arguments of its renders
+    it was given none), `exposure_views` and `bilagrid_views` --, and gets back what it keeps of the checks: the filter keyword arguments of its renders
     and the background in the form background() returns."""
     trainer = cameras is not False
     if trainer:
@@ -194,7 +213,7 @@ def _validate(cfg, cameras=False, exposure_views=None):
         _need_finite(cfg, "mcmc_growth", at_least=1)
         if type(cfg.mcmc_seed) is not int or not 0 <= cfg.mcmc_seed < 2 ** 64:
             raise ValueError(f"mcmc_seed must be an integer in [0, 2^64), not {cfg.mcmc_seed!r}")
-    # ---- the four groups TrainConfig(...) refuses too
+    # ---- the five groups TrainConfig(...) refuses too
     if type(cfg.densify_absgrad) is not bool:
         raise ValueError(f"densify_absgrad must be a bool, not {cfg.densify_absgrad!r}")
     if cfg.densify_absgrad and cfg.densify_rule != "screen":
@@ -214,12 +233,24 @@ def _validate(cfg, cameras=False, exposure_views=None):
         raise ValueError("filter3d > 0 needs the cameras of the whole training set: Trainer(model, config, group, cameras=views)")
     if type(cfg.exposure) is not bool:
         raise ValueError(f"exposure must be a bool, not {cfg.exposure!r}")
+    if type(cfg.bilagrid) is not bool:
+        raise ValueError(f"bilagrid must be a bool, not {cfg.bilagrid!r}")
+    bilagrid.check_shape(cfg.bilagrid_shape)
+    if cfg.bilagrid and cfg.exposure:
+        raise ValueError("bilagrid=True is not available with exposure=True (the grid at the identity contains the global affine, and "
+                         "two tables on one colour are ill-conditioned)")
     if not trainer:
         return None
     # ---- the rest is the Trainer's alone
     if cfg.exposure and exposure_views is None and cameras is None:
         raise ValueError("exposure=True needs the number of training images: Trainer(model, config, group, cameras=views) or "
                          "Trainer(..., exposure_views=V)")
+    if cfg.bilagrid and bilagrid_views is None and cameras is None:
+        raise ValueError("bilagrid=True needs the number of training images: Trainer(model, config, group, cameras=views) or "
+                         "Trainer(..., bilagrid_views=V)")
+    _need_finite(cfg, "bilagrid_tv", "bilagrid_lr_init", "bilagrid_lr_final", "bilagrid_lr_delay_mult")
+    if type(cfg.bilagrid_lr_max_steps) is not int or cfg.bilagrid_lr_max_steps < 1:
+        raise ValueError(f"bilagrid_lr_max_steps must be an integer >= 1, not {cfg.bilagrid_lr_max_steps!r}")
     if type(cfg.sh_degree_interval) is not int or cfg.sh_degree_interval < 0:
         raise ValueError(f"sh_degree_interval must be an integer >= 0, not {cfg.sh_degree_interval!r}")
     filter_kw = _abi.filter_kwargs(cfg.lowpass, cfg.antialias)      # (ValueError for a mode the kernels cannot do)
@@ -281,17 +312,26 @@ class Trainer:
 
     With exposure = True `self.exposure` is the exposure.ExposureTable of `exposure_views` rows (default: len(cameras)), one per training
     image, else None; under data parallelism every rank holds the whole table and the replicas stay bit-identical.  It is not part of
-    harness.save_checkpoint's file set: it travels through its own state_dict() / load_state_dict()."""
+    harness.save_checkpoint's file set: it travels through its own state_dict() / load_state_dict().
 
-    def __init__(self, model, config=None, group=None, cameras=None, exposure_views=None):
+    With bilagrid = True `self.bilagrid` is the bilagrid.BilateralGridTable of `bilagrid_views` rows (default: len(cameras)), else None;
+    everything said of the exposure table holds for it."""
+
+    def __init__(self, model, config=None, group=None, cameras=None, exposure_views=None, bilagrid_views=None):
         self.model = model
         self.cfg = config or TrainConfig()
         self.group = group
-        self._filter_kw, self._background = _validate(self.cfg, cameras, exposure_views)
+        self._filter_kw, self._background = _validate(self.cfg, cameras, exposure_views, bilagrid_views)
         self.exposure = None
         if self.cfg.exposure:
             n_images = exposure_views if exposure_views is not None else len(cameras)
             self.exposure = exposure.ExposureTable(n_images, model.pos.device)       # (ValueError unless an integer >= 1)
+        self.bilagrid = None
+        if self.cfg.bilagrid:
+            n_images = bilagrid_views if bilagrid_views is not None else len(cameras)
+            self.bilagrid = bilagrid.BilateralGridTable(n_images, model.pos.device, shape=self.cfg.bilagrid_shape)
+        # the per-image table a view's rendered colour goes through before the loss (the config check allows one at the most)
+        self._table = self.exposure if self.exposure is not None else self.bilagrid
         # filter3d: the camera records (host copy; on the model's device from the first step on) and the per-Gaussian filter
         self._cameras = filter3d.pack_cameras(cameras, "cpu") if cameras is not None and self.cfg.filter3d > 0 else None
         self._cameras_dev = None
@@ -459,10 +499,12 @@ class Trainer:
         dict also has 'l_alpha' and 'l_depth' (device scalars like 'l1', 0 for a term that is off) and 'loss' is the whole total.
         Otherwise those keys of a view are ignored, except that a 4-channel image is composited over black.
         exposure = True: every view carries 'idx', the integer in [0, V) of its training image (else ValueError, before anything is
-        queued); the dict also has 'lr_exposure', the learning rate the table was stepped at."""
+        queued); the dict also has 'lr_exposure', the learning rate the table was stepped at.
+        bilagrid = True: 'idx' likewise; the dict also has 'lr_bilagrid' and 'tv', the weighted total-variation term bilagrid_tv tv as a
+        device scalar -- it joined the table's gradient and is NOT part of 'loss', whose meaning stays."""
         c, m = self.cfg, self.model
         # ---- the facts of this step
-        rows = [self.exposure.check_index(v.get('idx')) for v in views] if self.exposure is not None else None
+        rows = [self._table.check_index(v.get('idx')) for v in views] if self._table is not None else None
         aux_maps = c.lambda_alpha > 0 or c.lambda_depth > 0
         aux = aux_maps if aux_maps or self._background is not None else None     # None: no aux pass; else: does it render the maps?
         bg = self.background(iteration)
@@ -493,7 +535,7 @@ class Trainer:
         else:
             raise RuntimeError("the pair buffers overflowed four times in a row")
         # ---- the update, the refinement, the result
-        lr_expo, reg = self._update(iteration, consumer, leaves, acc, acc_aux, world)
+        table_out, reg = self._update(iteration, consumer, leaves, acc, acc_aux, world)
         densified = self._refine(iteration, pos_lr, screen, world)
         out = {'loss': reg[2] if reg is not None else _total(acc, acc_aux), 'l1': acc[0], 'ssim': acc[1],
                'gaussians': m.get_num_gaussians(), 'lr_pos': pos_lr, 'densified': densified, 'sh_degree': sh_degree}
@@ -501,8 +543,7 @@ class Trainer:
             out.update(reg_opacity=reg[0], reg_scale=reg[1])
         if aux is not None:
             out.update(l_alpha=acc_aux[0], l_depth=acc_aux[1])
-        if lr_expo is not None:
-            out['lr_exposure'] = lr_expo
+        out.update(table_out)
         return out
 
     def _choose_route(self, world, n_views, aux_pass, params, even, sh_degree):
@@ -537,11 +578,11 @@ class Trainer:
         were rendered from, the loss sums [l1, ssim, total], the aux sums [l_alpha, l_depth, total] or None).
         Everything a pass adds into is zeroed HERE, in every attempt, on the caller's stream and before the side streams wait on it: a
         repeated pass counts nothing from the failed one (whose streams the caller's stream has waited for)."""
-        c, m, expo = self.cfg, self.model, self.exposure
+        c, m = self.cfg, self.model
         dev = m.pos.device
         self.optimizer.zero_grad()
-        if expo is not None:
-            expo.zero_grad()
+        if self._table is not None:
+            self._table.zero_grad()
         params, scale_in, opacity_in = m.get_params(), m.scale_raw, m.opacity_raw
         if c.filter3d > 0:
             # the effective scale and opacity of this pass: ONE launch and two fresh leaves -- their gradients start empty in every
@@ -600,7 +641,7 @@ class Trainer:
 
     def _view(self, v, row, scale_in, opacity_in, n_global, render_kw, aux, bg, stats):
         """One view of a pass, on the current stream: targets, render -- inside the view's statistics record `stats`, if any --, the
-        exposure of training image `row`, loss, backward.  Returns its loss vector and its aux-loss vector (None: no maps)."""
+        transform (exposure or bilateral grid) of training image `row`, loss, backward.  Returns its loss vector and its aux-loss vector (None: no maps)."""
         c, m = self.cfg, self.model
         dev = m.pos.device
         image_gt, alpha_gt, depth_gt = self._view_targets(v, dev, bg, aux is not None)
@@ -611,7 +652,7 @@ class Trainer:
         if aux:
             rendered, depth, alpha = rendered
         if row is not None:
-            rendered = self.exposure.apply_view(rendered, row)
+            rendered = self._table.apply_view(rendered, row)
         loss, vals = losses.compute_loss_device(rendered, image_gt, c.lambda_l1, c.lambda_ssim, scale=1.0 / n_global)
         if not aux:
             loss.backward()                        # (loss / batch size: the division is inside the loss kernels)
@@ -665,16 +706,26 @@ class Trainer:
 
     def _update(self, iteration, consumer, leaves, acc, acc_aux, world):
         """The optimiser steps of an iteration whose pass every rank agreed good -- so every rank is here, and none can be left in one
-        of the collectives below.  Returns (the exposure learning rate or None, mcmc.regularise's [reg_opacity, reg_scale, loss] or None)."""
-        c, m, expo = self.cfg, self.model, self.exposure
-        lr_expo = reg = None
+        of the collectives below.  Returns (what the per-image table adds to step()'s dict: 'lr_exposure', or 'lr_bilagrid' and 'tv';
+        mcmc.regularise's [reg_opacity, reg_scale, loss] or None)."""
+        c, m, expo, grid = self.cfg, self.model, self.exposure, self.bilagrid
+        table_out, reg = {}, None
+        if grid is not None:
+            # as for the exposure table below; the TV term joins AFTER the all-reduce: every rank computes the same one, and it counts once
+            if world > 1:
+                dp.allreduce_table_grad(grid.grad, self.group)
+            table_out['tv'] = grid.add_tv_grad(c.bilagrid_tv)
+            table_out['lr_bilagrid'] = optim.position_lr(iteration, c.bilagrid_lr_init, c.bilagrid_lr_final, c.bilagrid_lr_delay_mult,
+                                                         c.bilagrid_lr_max_steps)
+            grid.step(table_out['lr_bilagrid'])
         if expo is not None:
             # the table's gradient is complete on this rank -- the caller's stream has waited for the views' streams; summed over the
             # ranks, every replica steps the same bits.  The table's own Adam, at this iteration's exposure learning rate
             if world > 1:
                 dp.allreduce_exposure_grad(expo.grad, self.group)
-            lr_expo = optim.position_lr(iteration, c.exposure_lr_init, c.exposure_lr_final, c.exposure_lr_delay_mult, c.exposure_lr_max_steps)
-            expo.step(lr_expo)
+            table_out['lr_exposure'] = optim.position_lr(iteration, c.exposure_lr_init, c.exposure_lr_final, c.exposure_lr_delay_mult,
+                                                         c.exposure_lr_max_steps)
+            expo.step(table_out['lr_exposure'])
         scale_in, opacity_in = leaves
         if c.filter3d > 0 and (scale_in.grad is not None or opacity_in.grad is not None):
             # the gradients of the two leaves are complete (every view; every rank: after the exchange's all-reduce): ONE launch takes them
@@ -703,7 +754,7 @@ class Trainer:
             self.optimizer.step(visible=self.visible)
         else:
             self.optimizer.step()
-        return lr_expo, reg
+        return table_out, reg
 
     def _refine(self, iteration, pos_lr, screen, world):
         """What follows the optimiser step: under MCMC the position noise and, at its interval, the relocation -- no densification, no

@@ -9,9 +9,9 @@ all:
 # Sanitizers run on the CPU builds only (GPU AddressSanitizer is not available on the pool): the host build of the projection
 # math (the same gs_math.h / gs_body.h the HIP kernels inline) and the plain-C oracle, each under AddressSanitizer + UBSan,
 # driven by their own test files.  Python is not instrumented, so the runtime is preloaded and leak checking is off.
-# The MCMC arithmetic (gs_mcmc.h), the 3D filter (gs_filter3d.h) and the exposure transform (gs_exposure.h) go through stand-alone instrumented programs of their own, which
+# The MCMC arithmetic (gs_mcmc.h), the 3D filter (gs_filter3d.h), the exposure transform (gs_exposure.h) and the bilateral grid (gs_bilagrid.h) go through stand-alone instrumented programs of their own, which
 # need no preloaded runtime.
-check-asan: check-asan-mcmc check-asan-filter3d check-asan-exposure
+check-asan: check-asan-mcmc check-asan-filter3d check-asan-exposure check-asan-bilagrid
 	mkdir -p $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -std=c++17 -shared -fPIC -o $(ASAN_DIR)/libgsmath_host_asan.so $(PKG)/csrc/host_math_check.cpp
 	gcc $(ASAN_FLAGS) -std=c99 -fopenmp -shared -fPIC -o $(ASAN_DIR)/libgs_oracle_asan.so oracle/gs_oracle.c -lm
@@ -35,4 +35,9 @@ check-asan-exposure:
 	g++ $(ASAN_FLAGS) -std=c++17 -o $(ASAN_DIR)/host_exposure_selftest $(PKG)/csrc/host_exposure_selftest.cpp
 	ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/host_exposure_selftest
 
-.PHONY: all check-asan check-asan-mcmc check-asan-filter3d check-asan-exposure
+check-asan-bilagrid:
+	mkdir -p $(ASAN_DIR)
+	g++ $(ASAN_FLAGS) -std=c++17 -o $(ASAN_DIR)/host_bilagrid_selftest $(PKG)/csrc/host_bilagrid_selftest.cpp
+	ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/host_bilagrid_selftest
+
+.PHONY: all check-asan check-asan-mcmc check-asan-filter3d check-asan-exposure check-asan-bilagrid

@@ -645,6 +645,35 @@ int gsplat_exposure_forward(const float* image, const float* params, int64_t bat
 int gsplat_exposure_backward(const float* image, const float* params, const float* grad_out, int64_t batch, int32_t H, int32_t W,
                              float* grad_image, float* grad_params, const int32_t* row_index, int32_t flags, void* scratch, void* stream);
 
+/* ---- per-view bilateral grids (not in the reference) ----------------------------------------------------------------
+ * A grid of affine colour transforms per image, G[12, L, Y, X] floats (channel 4 r + k = entry (r, k) of [M | t]), sliced at
+ * (pixel x, pixel y, pixel luminance) with trilinear weights and applied to a frame before the loss (csrc/gs_bilagrid.h has the
+ * formulas; the identity grid returns every finite colour bit for bit).  image, out, grad_out, grad_image: [batch, H, W, 3] floats;
+ * grids: [batch, 12, L, Y, X].  2 <= X, Y <= 64 and 2 <= L <= 16; 0 < H, W <= 2^20, H W < 2^31, 0 < batch <= 65535; else GSPLAT_ERR_BAD_ARG (the
+ * scratch size: -1), as for a NULL required pointer -- before anything is launched.  Every entry runs on the caller's stream, reads
+ * nothing back and allocates nothing.  Arrays 4-byte aligned.  No output may alias an input.  No float atomics: every result is the
+ * same bits on every call, stream and launch.
+ * Forward: one launch.
+ * Backward: grad_image (NULL: not computed) is one launch over the pixels; grad_grids (NULL: not computed) is one launch of one
+ *   workgroup per spatial vertex and image, which gathers the pixels of the vertex's support and owns its 12 L outputs -- no scratch.
+ *   The grid of image b goes to row b of grad_grids ([V, 12, L, Y, X]), or to row row_index[b] when row_index (batch int32 on the
+ *   device; a negative entry drops the image) is given; the rows named must be distinct.  flags: GSPLAT_BILAGRID_ACCUMULATE adds to
+ *   the destination rows instead of overwriting them; any other bit is refused first ("unknown flag").
+ * Total variation of a table grids[V, 12, L, Y, X]:  tv = (1 / V) sum_v sum_axis mean((G shifted by one along the axis - G)^2), the
+ *   axes L, Y, X, the mean over the 12 channels and all pairs along the axis.  loss_out (one float, NULL: not computed) = scale tv;
+ *   grad (NULL: not computed) = scale dtv/dG, or += with GSPLAT_BILAGRID_ACCUMULATE: every element gathers from its at most six
+ *   neighbours.  scratch: gsplat_bilagrid_tv_scratch_bytes(V, X, Y, L) device bytes, 8-byte aligned, any contents, needed for loss_out
+ *   only (one double per workgroup -- V 12 planes of ceil(L Y X / 256) -- added in a fixed order by a second launch); one call at a time per
+ *   scratch buffer.                                                                                                              */
+#define GSPLAT_BILAGRID_ACCUMULATE 1
+int gsplat_bilagrid_forward(const float* image, const float* grids, int64_t batch, int32_t H, int32_t W, int32_t X, int32_t Y, int32_t L,
+                            float* out, void* stream);
+int gsplat_bilagrid_backward(const float* image, const float* grids, const float* grad_out, int64_t batch, int32_t H, int32_t W, int32_t X,
+                             int32_t Y, int32_t L, float* grad_image, float* grad_grids, const int32_t* row_index, int32_t flags, void* stream);
+int64_t gsplat_bilagrid_tv_scratch_bytes(int64_t V, int32_t X, int32_t Y, int32_t L);
+int gsplat_bilagrid_tv(const float* grids, int64_t V, int32_t X, int32_t Y, int32_t L, float scale, float* loss_out, float* grad, int32_t flags,
+                       void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
