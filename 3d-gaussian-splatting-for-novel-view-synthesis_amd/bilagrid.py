@@ -18,11 +18,10 @@ ctypes calls into csrc/gsplat_bilagrid.hip on the current stream, in the style o
 gradient of a grid is gathered per vertex in a fixed order without float atomics: the same bits on every call, every stream and every
 launch, with or without gs.set_deterministic(True).  There is no CPU fallback.
 """
-import numbers
-
 import torch
 
-from . import _abi, optim
+from . import _abi
+from ._viewtable import ViewFn, ViewOp, ViewTable
 from .ops import _f32, _p, _stream_ptr
 
 DEFAULT_SHAPE = (16, 16, 8)      # (X, Y, L)
@@ -51,58 +50,20 @@ def _shapes(image, grids):
         raise ValueError(f"image has an empty dimension: {shape}")
     L, Y, X = gshape[-3:]
     check_shape((X, Y, L))
-    return shape, b, shape[-3], shape[-2], (X, Y, L)
+    return shape, (b, shape[-3], shape[-2], X, Y, L)
 
 
-class _SliceFn(torch.autograd.Function):
-    """out = A [c, 1] over gsplat_bilagrid_forward / gsplat_bilagrid_backward.  `dest` and `anchor` as in exposure._ApplyFn: dest is
-    None (the gradient of grids is returned to autograd) or (grad buffer [V, 12, L, Y, X], row [1] int32 on the device): the backward
-    then ADDS the view's grid gradient into that row of the buffer itself and returns none."""
+def _forward(x, g, dims, out, stream):
+    _abi.check(_abi.lib().gsplat_bilagrid_forward(_p(x), _p(g), *dims, _p(out), stream), "gsplat_bilagrid_forward")
 
-    @staticmethod
-    def forward(ctx, image, grids, dest, anchor):
-        if not isinstance(image, torch.Tensor) or not isinstance(grids, torch.Tensor):
-            raise TypeError("image and grids must be torch.Tensors")
-        shape, b, h, w, xyl = _shapes(image, grids)
-        x, g = _f32(image, shape, "image"), _f32(grids, tuple(grids.shape), "grids")
-        if g.device != x.device:
-            raise ValueError(f"image is on {x.device}, grids on {g.device}")
-        dev = x.device
-        with torch.cuda.device(dev):
-            out = torch.empty(shape, dtype=torch.float32, device=dev)
-            _abi.check(_abi.lib().gsplat_bilagrid_forward(_p(x), _p(g), b, h, w, *xyl, _p(out), _stream_ptr(dev)), "gsplat_bilagrid_forward")
-        need_image = ctx.needs_input_grad[0]
-        need_grids = ctx.needs_input_grad[1] if dest is None else True
-        ctx.saved = (x, g, b, h, w, xyl, dest) if need_image or need_grids else None
-        ctx.need = (need_image, need_grids)
-        ctx.dtypes = (image.dtype, grids.dtype)
-        return out if image.dtype == torch.float32 else out.to(image.dtype)
 
-    @staticmethod
-    def backward(ctx, g_out):
-        need_image, need_grids = ctx.need
-        if ctx.saved is None:
-            return None, None, None, None
-        x, g, b, h, w, xyl, dest = ctx.saved
-        dev = x.device
-        go = _f32(g_out, tuple(x.shape), "grad_out")
-        with torch.cuda.device(dev):
-            g_image = torch.empty_like(x) if need_image else None
-            g_grids = target = rows = None
-            flags = 0
-            if need_grids:
-                if dest is None:
-                    g_grids = target = torch.empty_like(g)
-                else:
-                    target, rows = dest
-                    flags = _abi.GSPLAT_BILAGRID_ACCUMULATE
-            _abi.check(_abi.lib().gsplat_bilagrid_backward(_p(x), _p(g), _p(go), b, h, w, *xyl, _p(g_image), _p(target), _p(rows), flags,
-                                                           _stream_ptr(dev)), "gsplat_bilagrid_backward")
-        if g_image is not None and ctx.dtypes[0] != torch.float32:
-            g_image = g_image.to(ctx.dtypes[0])
-        if g_grids is not None and ctx.dtypes[1] != torch.float32:
-            g_grids = g_grids.to(ctx.dtypes[1])
-        return g_image, g_grids, None, None
+def _backward(x, g, go, dims, g_image, target, rows, flags, stream):
+    _abi.check(_abi.lib().gsplat_bilagrid_backward(_p(x), _p(g), _p(go), *dims, _p(g_image), _p(target), _p(rows), flags, stream),
+               "gsplat_bilagrid_backward")
+
+
+# out = A [c, 1] over gsplat_bilagrid_forward / gsplat_bilagrid_backward, in the skeleton of _viewtable.ViewFn
+_OP = ViewOp("grids", _shapes, _forward, _backward, _abi.GSPLAT_BILAGRID_ACCUMULATE)
 
 
 def slice(image, grids):
@@ -110,7 +71,7 @@ def slice(image, grids):
     [B, H, W, 3] with [B, 12, L, Y, X] (one grid per image).  Nothing is clamped; the identity grid returns the image bit for bit.
     Differentiable with respect to both; the half that is not needed is not computed.  fp32 is computed directly, other dtypes are
     converted.  One launch forward, one per gradient backward."""
-    return _SliceFn.apply(image, grids, None, None)
+    return ViewFn.apply(_OP, image, grids, None, None)
 
 
 def _tv(grids, scale, want_loss, grad, accumulate):
@@ -161,7 +122,7 @@ def tv_loss(grids):
     return _TvFn.apply(grids)
 
 
-class BilateralGridTable:
+class BilateralGridTable(ViewTable):
     """One grid per training image: `params` [V, 12, L, Y, X] at the identity, `grad` a buffer of the same shape, and an Adam state of
     its own -- a second optim.GaussianAdam over the one tensor (eps = 1e-15 and a dense step, as gsplat's trainer), apart from the
     model's optimiser: restarts of that one after a densification touch neither the table nor its moments.
@@ -172,62 +133,21 @@ class BilateralGridTable:
         table.step(lr)
     """
 
+    name, op = 'bilagrid', _OP
+
     def __init__(self, n_views, device, shape=DEFAULT_SHAPE, lr=0.002, betas=(0.9, 0.999), eps=1e-15):
-        if type(n_views) is not int or n_views < 1:
-            raise ValueError(f"n_views must be an integer >= 1, not {n_views!r}")
-        X, Y, L = self.shape = check_shape(shape)
-        device = torch.device(device)
-        self.n_views = n_views
-        eye = torch.eye(3, 4, dtype=torch.float32, device=device).reshape(1, 12, 1, 1, 1)
-        self.params = eye.expand(n_views, 12, L, Y, X).contiguous()
-        self.grad = torch.zeros_like(self.params)
-        self.optimizer = optim.GaussianAdam([{'params': [self.params], 'lr': float(lr), 'name': 'bilagrid'}], betas=betas, eps=eps)
-        # row k of the table names itself: the address of element k is the one-entry row_index of view k (nothing is copied per view)
-        self._rows = torch.arange(n_views, dtype=torch.int32, device=device)
-        self._anchor = torch.zeros((), dtype=torch.float32, device=device, requires_grad=True)
+        self.shape = shape                          # (checked in _identity: n_views is refused first)
+        super().__init__(n_views, device, lr, betas, eps)
 
-    def check_index(self, idx):
-        """idx as an int in [0, V) (bool, float and anything out of range: ValueError)."""
-        if isinstance(idx, bool) or not isinstance(idx, numbers.Integral) or not 0 <= idx < self.n_views:
-            raise ValueError(f"a view's 'idx' must be an integer in [0, {self.n_views}), not {idx!r}")
-        return int(idx)
-
-    def zero_grad(self):
-        self.grad.zero_()
-
-    def apply_view(self, image, idx):
-        """The grid of view `idx` sliced over image [H, W, 3].  Differentiable with respect to the image; the backward ADDS the view's
-        grid gradient into grad[idx] (gsplat_bilagrid_backward with a row_index and GSPLAT_BILAGRID_ACCUMULATE): no dense table-sized
-        tensor is produced or added per view.  Two views with the same idx must run their backward passes in one stream order
-        (Trainer.step sees to it)."""
-        idx = self.check_index(idx)
-        return _SliceFn.apply(image, self.params[idx], (self.grad, self._rows[idx:idx + 1]), self._anchor)
+    def _identity(self, device):
+        X, Y, L = self.shape = check_shape(self.shape)
+        return torch.eye(3, 4, dtype=torch.float32, device=device).reshape(12, 1, 1, 1).expand(12, L, Y, X)
 
     @torch.no_grad()
     def add_tv_grad(self, weight):
         """grad += weight dtv/dG over the whole table (one library call; nothing read back).  Returns the device scalar weight tv."""
         return _tv(self.params, weight, True, self.grad, True)
 
-    @torch.no_grad()
-    def step(self, lr=None):
-        """One dense Adam step of the whole table on `grad` (one launch; nothing read back)."""
-        if lr is not None:
-            self.optimizer.param_groups[0]['lr'] = float(lr)
-        self.params.grad = self.grad
-        self.optimizer.step()
-
-    def state_dict(self):
-        st = self.optimizer._state(self.params)
-        return {'params': self.params.detach().clone(), 'exp_avg': st['exp_avg'].clone(), 'exp_avg_sq': st['exp_avg_sq'].clone(),
-                'step': int(st['step'])}
-
-    @torch.no_grad()
-    def load_state_dict(self, state):
-        p = torch.as_tensor(state['params'])
-        if tuple(p.shape) != tuple(self.params.shape):
-            raise ValueError(f"the state holds a table of {tuple(p.shape)}, this one is {tuple(self.params.shape)}")
-        st = self.optimizer._state(self.params)
-        self.params.copy_(p)
-        st['exp_avg'].copy_(torch.as_tensor(state['exp_avg']))
-        st['exp_avg_sq'].copy_(torch.as_tensor(state['exp_avg_sq']))
-        st['step'] = int(state['step'])
+    def regularise(self, cfg):
+        """grad += cfg.bilagrid_tv dtv/dG; {'tv': the weighted term}."""
+        return {'tv': self.add_tv_grad(cfg.bilagrid_tv)}

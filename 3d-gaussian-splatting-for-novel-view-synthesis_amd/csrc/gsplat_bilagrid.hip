@@ -12,9 +12,8 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/gsplat_mi355x.h"
+#include "gs_entry.h"
 #include "gs_bilagrid.h"
-
-extern thread_local char gsplat_err_buf[512];
 
 namespace {
 
@@ -23,18 +22,6 @@ using namespace gsbila;
 constexpr int64_t MAX_BATCH = 65535;                       // the grid's y and z extents
 constexpr int64_t MAX_BLOCKS = 0x3FFFFFFF;                 // workgroups along x
 constexpr int32_t MAX_SIDE = 1 << 20;                      // H, W: pixel centres and cell boundaries stay apart in fp32 (gs_bilagrid.h, support())
-
-int bad_arg(const char* entry, const char* what) {
-    snprintf(gsplat_err_buf, sizeof(gsplat_err_buf), "%s: %s", entry, what);
-    return GSPLAT_ERR_BAD_ARG;
-}
-
-int launch_err(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GSPLAT_OK;
-    snprintf(gsplat_err_buf, sizeof(gsplat_err_buf), "%s launch: %s", what, hipGetErrorString(e));
-    return GSPLAT_ERR_HIP;
-}
 
 const char* grid_error(int32_t X, int32_t Y, int32_t L) {
     if (X < BILAGRID_MIN || X > BILAGRID_MAX_XY) return "X must be in [2, 64]";
@@ -66,8 +53,6 @@ const char* tv_shape_error(int64_t V, int32_t X, int32_t Y, int32_t L) {
     return nullptr;
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -83,7 +68,7 @@ int gsplat_bilagrid_forward(const float* image, const float* grids, int64_t batc
         if (!aligned(p, 4)) return bad_arg(E, "every array must be 4-byte aligned");
     hipLaunchKernelGGL((bilagrid_pixel_kernel<false>), dim3((unsigned)image_blocks(H, W), (unsigned)batch), dim3(BILAGRID_THREADS), 0,
                        (hipStream_t)stream, image, grids, (const float*)nullptr, H, W, X, Y, L, out);
-    return launch_err(E);
+    return launch_err("gsplat_bilagrid_forward launch");
 }
 
 int gsplat_bilagrid_backward(const float* image, const float* grids, const float* grad_out, int64_t batch, int32_t H, int32_t W, int32_t X,
@@ -105,7 +90,7 @@ int gsplat_bilagrid_backward(const float* image, const float* grids, const float
     if (grad_grids)
         hipLaunchKernelGGL(bilagrid_gather_kernel, dim3((unsigned)X, (unsigned)Y, (unsigned)batch), dim3(BILAGRID_GATHER_THREADS), 0, st, image, grad_out,
                            H, W, X, Y, L, row_index, (int)(flags & GSPLAT_BILAGRID_ACCUMULATE), grad_grids);
-    return launch_err(E);
+    return launch_err("gsplat_bilagrid_backward launch");
 }
 
 // scratch = one double per workgroup (V 12 planes, ceil(L Y X / 256) chunks each), rounded up to 256 bytes
@@ -136,7 +121,7 @@ int gsplat_bilagrid_tv(const float* grids, int64_t V, int32_t X, int32_t Y, int3
                        partial);
     if (loss_out)
         hipLaunchKernelGGL(bilagrid_tv_finish_kernel, dim3(1), dim3(BILAGRID_THREADS), 0, st, (const double*)partial, blocks, (double)scale, loss_out);
-    return launch_err(E);
+    return launch_err("gsplat_bilagrid_tv launch");
 }
 
 }  // extern "C"

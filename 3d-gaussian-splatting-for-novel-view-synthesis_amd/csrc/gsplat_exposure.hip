@@ -11,9 +11,8 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/gsplat_mi355x.h"
+#include "gs_entry.h"
 #include "gs_exposure.h"
-
-extern thread_local char gsplat_err_buf[512];
 
 namespace {
 
@@ -24,18 +23,6 @@ constexpr int64_t MAX_BLOCKS = 0x3FFFFFFF;                 // workgroups per ima
 
 int64_t image_blocks(int32_t H, int32_t W) { return ((int64_t)H * W + EXPOSURE_BLOCK_PIX - 1) / EXPOSURE_BLOCK_PIX; }
 
-int bad_arg(const char* entry, const char* what) {
-    snprintf(gsplat_err_buf, sizeof(gsplat_err_buf), "%s: %s", entry, what);
-    return GSPLAT_ERR_BAD_ARG;
-}
-
-int launch_err(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GSPLAT_OK;
-    snprintf(gsplat_err_buf, sizeof(gsplat_err_buf), "%s launch: %s", what, hipGetErrorString(e));
-    return GSPLAT_ERR_HIP;
-}
-
 // the shape checks every entry shares; NULL when the shape is good
 const char* shape_error(int64_t batch, int32_t H, int32_t W) {
     if (H <= 0) return "H must be > 0";
@@ -45,8 +32,6 @@ const char* shape_error(int64_t batch, int32_t H, int32_t W) {
     if (image_blocks(H, W) > MAX_BLOCKS) return "the image is too large";
     return nullptr;
 }
-
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // 16-byte accesses: every array on a 16-byte boundary, and every image of a batch too (an image is 12 H W bytes)
 int can_vectorise(std::initializer_list<const void*> ptrs, int64_t batch, int64_t pixels) {
@@ -76,7 +61,7 @@ int gsplat_exposure_forward(const float* image, const float* params, int64_t bat
     const int64_t n = (int64_t)H * W;
     hipLaunchKernelGGL(exposure_forward_kernel, dim3((unsigned)image_blocks(H, W), (unsigned)batch), dim3(EXPOSURE_THREADS), 0, (hipStream_t)stream,
                        image, params, n, can_vectorise({image, out}, batch, n), out);
-    return launch_err(E);
+    return launch_err("gsplat_exposure_forward launch");
 }
 
 int gsplat_exposure_backward(const float* image, const float* params, const float* grad_out, int64_t batch, int32_t H, int32_t W,
@@ -106,7 +91,7 @@ int gsplat_exposure_backward(const float* image, const float* params, const floa
     if (grad_params)
         hipLaunchKernelGGL(exposure_finish_kernel, dim3((unsigned)batch), block, 0, st, (const float*)partial, (int)blocks, row_index,
                            (int)(flags & GSPLAT_EXPOSURE_ACCUMULATE), grad_params);
-    return launch_err(E);
+    return launch_err("gsplat_exposure_backward launch");
 }
 
 }  // extern "C"

@@ -11,9 +11,8 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/gsplat_mi355x.h"
+#include "gs_entry.h"
 #include "gs_filter3d.h"
-
-extern thread_local char gsplat_err_buf[512];
 
 namespace {
 
@@ -128,19 +127,6 @@ __global__ __launch_bounds__(THREADS) void apply_backward_kernel(int64_t n, cons
     }
 }
 
-int launch_err(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GSPLAT_OK;
-    snprintf(gsplat_err_buf, sizeof(gsplat_err_buf), "%s: %s", what, hipGetErrorString(e));
-    return GSPLAT_ERR_HIP;
-}
-
-int bad_arg(const char* entry, const char* what) {
-    snprintf(gsplat_err_buf, sizeof(gsplat_err_buf), "%s: %s", entry, what);
-    return GSPLAT_ERR_BAD_ARG;
-}
-
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 inline bool real_nonneg(float x) { return std::isfinite(x) && x >= 0.f; }
 
 unsigned stream_blocks(int64_t items) {

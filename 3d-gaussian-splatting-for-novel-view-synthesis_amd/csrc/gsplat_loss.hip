@@ -40,6 +40,7 @@
 
 #include "../../include/gsplat_mi355x.h"
 #include "gs_aux_loss.h"
+#include "gs_entry.h"
 
 namespace {
 
@@ -359,9 +360,6 @@ __global__ __launch_bounds__(THREADS) void loss_finish_kernel(const float* __res
 
 }  // namespace
 
-extern thread_local char gsplat_err_buf[512];
-#define g_loss_err gsplat_err_buf
-
 extern "C" {
 
 // scratch = [per block of loss_stats_kernel: 2 partial sums | the three partial-derivative maps of every channel: batch x 3 x 3 x H x W floats]
@@ -374,10 +372,8 @@ int64_t gsplat_loss_scratch_bytes(int64_t batch, int32_t H, int32_t W, int32_t w
 
 int gsplat_loss(const float* pred, const float* target, int64_t batch, int32_t H, int32_t W, float lambda_l1, float lambda_ssim,
                 float* values, float* grad_pred, void* scratch, void* stream_) {
-    if (!pred || !target || !values || !scratch || batch <= 0 || H <= 0 || W <= 0 || batch > 65535 || loss_blocks(batch, H, W) > 0x3FFFFFFF) {
-        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_loss: bad argument");
-        return GSPLAT_ERR_BAD_ARG;
-    }
+    if (!pred || !target || !values || !scratch || batch <= 0 || H <= 0 || W <= 0 || batch > 65535 || loss_blocks(batch, H, W) > 0x3FFFFFFF)
+        return bad_arg("gsplat_loss", "bad argument");
     hipStream_t st = (hipStream_t)stream_;
     float* partial = (float*)scratch;
     const double n = (double)batch * H * W * 3;
@@ -390,12 +386,7 @@ int gsplat_loss(const float* pred, const float* target, int64_t batch, int32_t H
     else
         hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(THREADS), 0, st, (const float*)partial, (int)loss_blocks(batch, H, W), 1.0 / n,
                            lambda_l1, lambda_ssim, values, 1.0, (float*)nullptr);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_loss launch: %s", hipGetErrorString(e));
-        return GSPLAT_ERR_HIP;
-    }
-    return GSPLAT_OK;
+    return launch_err("gsplat_loss launch");
 }
 
 /* The same loss in two calls, for a caller whose graph supplies d L / d total only later (an autograd node): the forward leaves the
@@ -403,10 +394,8 @@ int gsplat_loss(const float* pred, const float* target, int64_t batch, int32_t H
  * over the gradient afterwards, no gradient computed for a value nobody differentiates.                                          */
 int gsplat_loss_forward(const float* pred, const float* target, int64_t batch, int32_t H, int32_t W, float lambda_l1, float lambda_ssim,
                         float scale, float* values, float* total, void* scratch, int32_t keep_maps, void* stream_) {
-    if (!pred || !target || !values || !scratch || batch <= 0 || H <= 0 || W <= 0 || batch > 65535 || loss_blocks(batch, H, W) > 0x3FFFFFFF) {
-        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_loss_forward: bad argument");
-        return GSPLAT_ERR_BAD_ARG;
-    }
+    if (!pred || !target || !values || !scratch || batch <= 0 || H <= 0 || W <= 0 || batch > 65535 || loss_blocks(batch, H, W) > 0x3FFFFFFF)
+        return bad_arg("gsplat_loss_forward", "bad argument");
     hipStream_t st = (hipStream_t)stream_;
     float* partial = (float*)scratch;
     const double n = (double)batch * H * W * 3;
@@ -415,31 +404,19 @@ int gsplat_loss_forward(const float* pred, const float* target, int64_t batch, i
     hipLaunchKernelGGL(loss_stats_kernel, grid, dim3(THREADS), 0, st, pred, target, (int)H, (int)W, partial, maps);
     hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(THREADS), 0, st, (const float*)partial, (int)loss_blocks(batch, H, W), 1.0 / n,
                        lambda_l1, lambda_ssim, values, (double)scale, total);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_loss_forward launch: %s", hipGetErrorString(e));
-        return GSPLAT_ERR_HIP;
-    }
-    return GSPLAT_OK;
+    return launch_err("gsplat_loss_forward launch");
 }
 
 int gsplat_loss_backward(const float* pred, const float* target, int64_t batch, int32_t H, int32_t W, float lambda_l1, float lambda_ssim,
                          float scale, const float* upstream, float* grad_pred, void* scratch, void* stream_) {
-    if (!pred || !target || !grad_pred || !scratch || batch <= 0 || H <= 0 || W <= 0 || batch > 65535 || loss_blocks(batch, H, W) > 0x3FFFFFFF) {
-        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_loss_backward: bad argument");
-        return GSPLAT_ERR_BAD_ARG;
-    }
+    if (!pred || !target || !grad_pred || !scratch || batch <= 0 || H <= 0 || W <= 0 || batch > 65535 || loss_blocks(batch, H, W) > 0x3FFFFFFF)
+        return bad_arg("gsplat_loss_backward", "bad argument");
     const double n = (double)batch * H * W * 3;
     const dim3 grid((W + TW - 1) / TW, (H + TH - 1) / TH, (unsigned)batch);
     const float* maps = (const float*)((char*)scratch + loss_sums_bytes(batch, H, W));
     hipLaunchKernelGGL(loss_grad_kernel, grid, dim3(THREADS), 0, (hipStream_t)stream_, pred, target, (int)H, (int)W, lambda_l1, lambda_ssim,
                        (float)((double)scale / n), 1.0 / n, maps, (const float*)scratch, (float*)nullptr, grad_pred, upstream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_loss_backward launch: %s", hipGetErrorString(e));
-        return GSPLAT_ERR_HIP;
-    }
-    return GSPLAT_OK;
+    return launch_err("gsplat_loss_backward launch");
 }
 
 /* ---- the auxiliary loss on the depth / opacity maps, and a target over a background (gs_aux_loss.h) ---- */
@@ -462,10 +439,8 @@ int64_t gsplat_aux_loss_scratch_bytes(int64_t batch, int32_t H, int32_t W) {
 int gsplat_aux_loss_forward(const float* depth, const float* alpha, const float* target_depth, const float* target_alpha, int64_t batch,
                             int32_t H, int32_t W, float lambda_depth, float lambda_alpha, float scale, float* values, float* total,
                             void* scratch, void* stream_) {
-    if (!alpha || !values || !scratch || (target_depth && !depth) || !aux_shape_ok(batch, H, W)) {
-        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_aux_loss_forward: bad argument");
-        return GSPLAT_ERR_BAD_ARG;
-    }
+    if (!alpha || !values || !scratch || (target_depth && !depth) || !aux_shape_ok(batch, H, W))
+        return bad_arg("gsplat_aux_loss_forward", "bad argument");
     hipStream_t st = (hipStream_t)stream_;
     const int64_t n = batch * (int64_t)H * W, blocks = aux_blocks(batch, H, W);
     float* partial = (float*)((char*)scratch + AUX_HEADER_BYTES);
@@ -474,50 +449,31 @@ int gsplat_aux_loss_forward(const float* depth, const float* alpha, const float*
                        partial);
     hipLaunchKernelGGL(aux_loss_finish_kernel, dim3(1), dim3(AUX_THREADS), 0, st, (const float*)partial, (int)blocks, 1.0 / (double)n,
                        lambda_depth, lambda_alpha, (double)scale, values, total, (double*)scratch);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_aux_loss_forward launch: %s", hipGetErrorString(e));
-        return GSPLAT_ERR_HIP;
-    }
-    return GSPLAT_OK;
+    return launch_err("gsplat_aux_loss_forward launch");
 }
 
 int gsplat_aux_loss_backward(const float* depth, const float* alpha, const float* target_depth, const float* target_alpha, int64_t batch,
                              int32_t H, int32_t W, float lambda_depth, float lambda_alpha, float scale, const float* upstream,
                              float* grad_depth, float* grad_alpha, void* scratch, void* stream_) {
-    if (!alpha || !grad_alpha || !scratch || (target_depth && (!depth || !grad_depth)) || !aux_shape_ok(batch, H, W)) {
-        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_aux_loss_backward: bad argument");
-        return GSPLAT_ERR_BAD_ARG;
-    }
+    if (!alpha || !grad_alpha || !scratch || (target_depth && (!depth || !grad_depth)) || !aux_shape_ok(batch, H, W))
+        return bad_arg("gsplat_aux_loss_backward", "bad argument");
     const int64_t n = batch * (int64_t)H * W, blocks = aux_blocks(batch, H, W);
     const int vec = aux_aligned({depth, alpha, target_depth, target_alpha, grad_depth, grad_alpha});
     hipLaunchKernelGGL(aux_loss_grad_kernel, dim3((unsigned)blocks), dim3(AUX_THREADS), 0, (hipStream_t)stream_, depth, alpha, target_depth,
                        target_alpha, n, vec, (double)scale * (double)lambda_alpha / (double)n, (double)scale * (double)lambda_depth,
                        (const double*)scratch, upstream, grad_depth, grad_alpha);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_aux_loss_backward launch: %s", hipGetErrorString(e));
-        return GSPLAT_ERR_HIP;
-    }
-    return GSPLAT_OK;
+    return launch_err("gsplat_aux_loss_backward launch");
 }
 
 int gsplat_composite_target(const float* rgb, const float* alpha, const float* background, int64_t batch, int32_t H, int32_t W, float* out,
                             void* stream_) {
-    if (!rgb || !alpha || !background || !out || !aux_shape_ok(batch, H, W)) {
-        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_composite_target: bad argument");
-        return GSPLAT_ERR_BAD_ARG;
-    }
+    if (!rgb || !alpha || !background || !out || !aux_shape_ok(batch, H, W))
+        return bad_arg("gsplat_composite_target", "bad argument");
     const int64_t n = batch * (int64_t)H * W;
     const AuxBackground bg{{background[0], background[1], background[2]}};
     hipLaunchKernelGGL(composite_target_kernel, dim3((unsigned)aux_blocks(batch, H, W)), dim3(AUX_THREADS), 0, (hipStream_t)stream_, rgb, alpha, bg,
                        n, aux_aligned({rgb, alpha, out}), out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(g_loss_err, sizeof(g_loss_err), "gsplat_composite_target launch: %s", hipGetErrorString(e));
-        return GSPLAT_ERR_HIP;
-    }
-    return GSPLAT_OK;
+    return launch_err("gsplat_composite_target launch");
 }
 
 }  // extern "C"

@@ -12,9 +12,8 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/gsplat_mi355x.h"
+#include "gs_entry.h"
 #include "gs_mcmc.h"
-
-extern thread_local char gsplat_err_buf[512];
 
 namespace {
 
@@ -234,21 +233,7 @@ __global__ __launch_bounds__(THREADS) void relocate_sources_kernel(int64_t n, Pa
     zero_moments(mo, i);
 }
 
-int launch_err(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GSPLAT_OK;
-    snprintf(gsplat_err_buf, sizeof(gsplat_err_buf), "%s: %s", what, hipGetErrorString(e));
-    return GSPLAT_ERR_HIP;
-}
-
-int bad_arg(const char* entry, const char* what) {
-    snprintf(gsplat_err_buf, sizeof(gsplat_err_buf), "%s: %s", entry, what);
-    return GSPLAT_ERR_BAD_ARG;
-}
-
 constexpr int64_t MAX_ROWS = 0x7fffffff;      // src is int32
-
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace
 

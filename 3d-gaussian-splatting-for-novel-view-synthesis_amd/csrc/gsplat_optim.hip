@@ -17,8 +17,7 @@
 
 #include "../../include/gsplat_mi355x.h"
 #include "gs_adam.h"
-
-extern thread_local char gsplat_err_buf[512];
+#include "gs_entry.h"
 
 namespace {
 
@@ -218,13 +217,6 @@ inline unsigned grid_for(int64_t n) {
     return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
-int launch_err(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GSPLAT_OK;
-    snprintf(gsplat_err_buf, sizeof(gsplat_err_buf), "%s: %s", what, hipGetErrorString(e));
-    return GSPLAT_ERR_HIP;
-}
-
 }  // namespace
 
 extern "C" {
@@ -232,10 +224,7 @@ extern "C" {
 int64_t gsplat_clip_scratch_bytes(void) { return NPART * sizeof(float); }
 
 int gsplat_clip_grad_norm(int64_t n, const float* grad, float max_norm, float* coef_and_norm, void* scratch, void* stream_) {
-    if (n < 0 || (n > 0 && !grad) || !coef_and_norm || !scratch) {
-        snprintf(gsplat_err_buf, sizeof(gsplat_err_buf), "gsplat_clip_grad_norm: bad argument");
-        return GSPLAT_ERR_BAD_ARG;
-    }
+    if (n < 0 || (n > 0 && !grad) || !coef_and_norm || !scratch) return bad_arg("gsplat_clip_grad_norm", "bad argument");
     hipStream_t st = (hipStream_t)stream_;
     float* part = (float*)scratch;
     const int n_part = n > 0 ? (int)(grid_for(n) > (unsigned)NPART ? (unsigned)NPART : grid_for(n)) : 0;
@@ -285,10 +274,7 @@ int gsplat_adam_step_rows(int32_t n_groups, const gsplat_adam_group* groups, con
         snprintf(gsplat_err_buf, sizeof(gsplat_err_buf), "%s: 0..%d groups, each with its row width", name, MAX_GROUPS);
         return GSPLAT_ERR_BAD_ARG;
     }
-    if (n_rows < 0 || !visible) {
-        snprintf(gsplat_err_buf, sizeof(gsplat_err_buf), "%s: %s", name, n_rows < 0 ? "n_rows < 0" : "visible is NULL");
-        return GSPLAT_ERR_BAD_ARG;
-    }
+    if (n_rows < 0 || !visible) return bad_arg(name, n_rows < 0 ? "n_rows < 0" : "visible is NULL");
     RowGroups a;
     a.count = 0; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.visible = visible; a.n_rows = n_rows;
     uint32_t blocks = 0;
@@ -326,10 +312,7 @@ int gsplat_adam_step_rows(int32_t n_groups, const gsplat_adam_group* groups, con
 
 int gsplat_adam_step(int64_t n, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
                      float eps, int32_t step, const float* grad_scale, void* stream_) {
-    if (n < 0 || step < 1 || (n > 0 && (!param || !grad || !exp_avg || !exp_avg_sq))) {
-        snprintf(gsplat_err_buf, sizeof(gsplat_err_buf), "gsplat_adam_step: bad argument");
-        return GSPLAT_ERR_BAD_ARG;
-    }
+    if (n < 0 || step < 1 || (n > 0 && (!param || !grad || !exp_avg || !exp_avg_sq))) return bad_arg("gsplat_adam_step", "bad argument");
     const gsplat_adam_group one = {n, param, grad, exp_avg, exp_avg_sq, lr, step, grad_scale};
     return gsplat_adam_step_multi(1, &one, beta1, beta2, eps, stream_);
 }

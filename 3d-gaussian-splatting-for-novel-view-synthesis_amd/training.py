@@ -242,12 +242,10 @@ def _validate(cfg, cameras=False, exposure_views=None, bilagrid_views=None):
     if not trainer:
         return None
     # ---- the rest is the Trainer's alone
-    if cfg.exposure and exposure_views is None and cameras is None:
-        raise ValueError("exposure=True needs the number of training images: Trainer(model, config, group, cameras=views) or "
-                         "Trainer(..., exposure_views=V)")
-    if cfg.bilagrid and bilagrid_views is None and cameras is None:
-        raise ValueError("bilagrid=True needs the number of training images: Trainer(model, config, group, cameras=views) or "
-                         "Trainer(..., bilagrid_views=V)")
+    for name, n_views in (("exposure", exposure_views), ("bilagrid", bilagrid_views)):
+        if getattr(cfg, name) and n_views is None and cameras is None:
+            raise ValueError(f"{name}=True needs the number of training images: Trainer(model, config, group, cameras=views) or "
+                             f"Trainer(..., {name}_views=V)")
     _need_finite(cfg, "bilagrid_tv", "bilagrid_lr_init", "bilagrid_lr_final", "bilagrid_lr_delay_mult")
     if type(cfg.bilagrid_lr_max_steps) is not int or cfg.bilagrid_lr_max_steps < 1:
         raise ValueError(f"bilagrid_lr_max_steps must be an integer >= 1, not {cfg.bilagrid_lr_max_steps!r}")
@@ -322,16 +320,16 @@ class Trainer:
         self.cfg = config or TrainConfig()
         self.group = group
         self._filter_kw, self._background = _validate(self.cfg, cameras, exposure_views, bilagrid_views)
-        self.exposure = None
-        if self.cfg.exposure:
-            n_images = exposure_views if exposure_views is not None else len(cameras)
-            self.exposure = exposure.ExposureTable(n_images, model.pos.device)       # (ValueError unless an integer >= 1)
-        self.bilagrid = None
-        if self.cfg.bilagrid:
-            n_images = bilagrid_views if bilagrid_views is not None else len(cameras)
-            self.bilagrid = bilagrid.BilateralGridTable(n_images, model.pos.device, shape=self.cfg.bilagrid_shape)
         # the per-image table a view's rendered colour goes through before the loss (the config check allows one at the most)
-        self._table = self.exposure if self.exposure is not None else self.bilagrid
+        self.exposure = self.bilagrid = self._table = None
+        if self.cfg.exposure or self.cfg.bilagrid:
+            n_views = exposure_views if self.cfg.exposure else bilagrid_views
+            if n_views is None:
+                n_views = len(cameras)
+            if self.cfg.exposure:                                                    # (either: ValueError unless n_views is an integer >= 1)
+                self._table = self.exposure = exposure.ExposureTable(n_views, model.pos.device)
+            else:
+                self._table = self.bilagrid = bilagrid.BilateralGridTable(n_views, model.pos.device, shape=self.cfg.bilagrid_shape)
         # filter3d: the camera records (host copy; on the model's device from the first step on) and the per-Gaussian filter
         self._cameras = filter3d.pack_cameras(cameras, "cpu") if cameras is not None and self.cfg.filter3d > 0 else None
         self._cameras_dev = None
@@ -708,24 +706,18 @@ class Trainer:
         """The optimiser steps of an iteration whose pass every rank agreed good -- so every rank is here, and none can be left in one
         of the collectives below.  Returns (what the per-image table adds to step()'s dict: 'lr_exposure', or 'lr_bilagrid' and 'tv';
         mcmc.regularise's [reg_opacity, reg_scale, loss] or None)."""
-        c, m, expo, grid = self.cfg, self.model, self.exposure, self.bilagrid
+        c, m, table = self.cfg, self.model, self._table
         table_out, reg = {}, None
-        if grid is not None:
-            # as for the exposure table below; the TV term joins AFTER the all-reduce: every rank computes the same one, and it counts once
-            if world > 1:
-                dp.allreduce_table_grad(grid.grad, self.group)
-            table_out['tv'] = grid.add_tv_grad(c.bilagrid_tv)
-            table_out['lr_bilagrid'] = optim.position_lr(iteration, c.bilagrid_lr_init, c.bilagrid_lr_final, c.bilagrid_lr_delay_mult,
-                                                         c.bilagrid_lr_max_steps)
-            grid.step(table_out['lr_bilagrid'])
-        if expo is not None:
+        if table is not None:
             # the table's gradient is complete on this rank -- the caller's stream has waited for the views' streams; summed over the
-            # ranks, every replica steps the same bits.  The table's own Adam, at this iteration's exposure learning rate
+            # ranks, every replica steps the same bits.  The table's once-per-iteration term (the grid's TV) joins AFTER the all-reduce:
+            # every rank computes the same one, and it counts once.  The table's own Adam, at this iteration's learning rate of its own
             if world > 1:
-                dp.allreduce_exposure_grad(expo.grad, self.group)
-            table_out['lr_exposure'] = optim.position_lr(iteration, c.exposure_lr_init, c.exposure_lr_final, c.exposure_lr_delay_mult,
-                                                         c.exposure_lr_max_steps)
-            expo.step(table_out['lr_exposure'])
+                dp.allreduce_table_grad(table.grad, self.group)
+            table_out.update(table.regularise(c))
+            lr = optim.position_lr(iteration, *(getattr(c, f"{table.name}_lr_{k}") for k in ("init", "final", "delay_mult", "max_steps")))
+            table_out['lr_' + table.name] = lr
+            table.step(lr)
         scale_in, opacity_in = leaves
         if c.filter3d > 0 and (scale_in.grad is not None or opacity_in.grad is not None):
             # the gradients of the two leaves are complete (every view; every rank: after the exchange's all-reduce): ONE launch takes them

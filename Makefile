@@ -20,24 +20,10 @@ check-asan: check-asan-mcmc check-asan-filter3d check-asan-exposure check-asan-b
 	  GSPLAT_HOSTMATH_LIB=$(CURDIR)/$(ASAN_DIR)/libgsmath_host_asan.so GS_ORACLE_LIB=$(CURDIR)/$(ASAN_DIR)/libgs_oracle_asan.so \
 	  python -m pytest tests/test_product_math_cpu.py tests/test_pose_grad_cpu.py tests/test_c_oracle_golden.py -x -q -p no:cacheprovider
 
-check-asan-mcmc:
+check-asan-%: $(PKG)/csrc/host_%_selftest.cpp
 	mkdir -p $(ASAN_DIR)
-	g++ $(ASAN_FLAGS) -std=c++17 -o $(ASAN_DIR)/host_mcmc_selftest $(PKG)/csrc/host_mcmc_selftest.cpp
-	ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/host_mcmc_selftest
+	g++ $(ASAN_FLAGS) -std=c++17 -o $(ASAN_DIR)/host_$*_selftest $<
+	ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/host_$*_selftest
 
-check-asan-filter3d:
-	mkdir -p $(ASAN_DIR)
-	g++ $(ASAN_FLAGS) -std=c++17 -o $(ASAN_DIR)/host_filter3d_selftest $(PKG)/csrc/host_filter3d_selftest.cpp
-	ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/host_filter3d_selftest
-
-check-asan-exposure:
-	mkdir -p $(ASAN_DIR)
-	g++ $(ASAN_FLAGS) -std=c++17 -o $(ASAN_DIR)/host_exposure_selftest $(PKG)/csrc/host_exposure_selftest.cpp
-	ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/host_exposure_selftest
-
-check-asan-bilagrid:
-	mkdir -p $(ASAN_DIR)
-	g++ $(ASAN_FLAGS) -std=c++17 -o $(ASAN_DIR)/host_bilagrid_selftest $(PKG)/csrc/host_bilagrid_selftest.cpp
-	ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/host_bilagrid_selftest
-
-.PHONY: all check-asan check-asan-mcmc check-asan-filter3d check-asan-exposure check-asan-bilagrid
+# (the check-asan-% targets are not listed: make skips the pattern-rule search for a phony target; they name no file, so they always run)
+.PHONY: all check-asan
