@@ -150,6 +150,13 @@ __device__ __forceinline__ uint32_t subtile_mask_exact(const Candidate& c, float
     return (A > 0.f && C > 0.f && A * C - B * B > 0.f) ? m : 0xFFu;
 }
 
+// max of two wave-uniform counts as ONE s_max_i32
+__device__ __forceinline__ int smax(int a, int b) {
+    int r;
+    asm("s_max_i32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc");
+    return r;
+}
+
 // MASK: 0 = box test, 1 = box and exact test, 2 = the mask the forward pass saved for this pair (c.saved_mask)
 // Z: the record's camera depth is staged too (r2.z: the depth / opacity variants composite it as a fourth channel)
 template <int MAXQ, int MASK = 0, class Lds = RasterLds, bool Z = false>
@@ -188,26 +195,28 @@ __device__ __forceinline__ Staged stage_chunk(Lds& s, const Candidate& c, int n,
         __syncthreads();
         return Staged{n, maxc};
     }
+    // (the bit tests are made ONCE: a queue is written under its ballot, cut to the entries taken -- scalar work where a second test of
+    //  the bit cost two vector instructions per sub-tile; the longest queue is a scalar maximum, smax: left to itself the compiler moves
+    //  the counts to VGPRs for a v_max3_u32)
     unsigned long long bal[N_SUB];
     int maxc = 0;
 #pragma unroll
     for (int t = 0; t < N_SUB; ++t) {
         bal[t] = __ballot((m8 >> t) & 1u);
-        maxc = max(maxc, (int)__popcll(bal[t]));
+        maxc = smax(maxc, (int)__popcll(bal[t]));
     }
-    {
-        while (maxc > MAXQ) {                 // rare (dense lists of large Gaussians): scalar work only
-            n = max(n - 4, MAXQ);             // n = MAXQ always fits
-            const unsigned long long keep = (1ull << n) - 1ull;
-            maxc = 0;
+    while (maxc > MAXQ) {                 // rare (dense lists of large Gaussians): scalar work only
+        n = max(n - 4, MAXQ);             // n = MAXQ always fits
+        const unsigned long long keep = (1ull << n) - 1ull;
+        maxc = 0;
 #pragma unroll
-            for (int t = 0; t < N_SUB; ++t) maxc = max(maxc, (int)__popcll(bal[t] & keep));
-        }
-        if (lane >= n) m8 = 0u;
+        for (int t = 0; t < N_SUB; ++t) maxc = smax(maxc, (int)__popcll(bal[t] & keep));
     }
+    const unsigned long long taken = n >= 64 ? ~0ull : (1ull << n) - 1ull;      // lanes [0, n)
+    if (lane >= n) m8 = 0u;
 #pragma unroll
     for (int t = 0; t < N_SUB; ++t) {
-        if ((m8 >> t) & 1u) {
+        if (__builtin_amdgcn_inverse_ballot_w64(bal[t] & taken)) {
             const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[t] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[t], 0u));
             s.q[t][r] = (uint16_t)(lane * 16);
             ranks |= (uint64_t)r << (8 * t);
@@ -459,9 +468,10 @@ constexpr int QSLOTS_BWD = (MAXQ_BWD + 4 + 7) / 8 * 8;   // the loop reads entri
 using RasterLdsB = RasterLdsT<QSLOTS_BWD>;
 template <bool DET, int NS = 9>              // NS = sums per (sub-tile, Gaussian): 9, or 10 with the depth / opacity channels (S_z)
 struct RasterLdsBwd {
+    float slots[N_SUB * MAXQ_BWD * NS];  // [sub-tile][queue position][NS sums]  (first: at LDS address 0 a slot's byte offset IS its address, and
+                                         //  the ds_read2 of the gather, whose two offsets reach 255 words, need no base added per pair of sums)
     RasterLdsB f;
-    float slots[N_SUB * MAXQ_BWD * NS];  // [sub-tile][queue position][NS sums]
-    uint32_t eid[CHUNK];                 // Gaussian id of every entry of the chunk
+    uint32_t eoff[CHUNK];                // every entry's row of grad2d as an element offset: 16 x its Gaussian id (< 2^26, gs_layout.h)
     uint32_t eslot[DET ? CHUNK : 1];     // (deterministic mode) the row's slot
 };
 // LDS is handed out in coarse pieces (1280 B by the look of it): at 12 848 B per wave 11 waves were resident per CU (measured with
@@ -525,7 +535,7 @@ __device__ __forceinline__ float hadd_abs(v2f a) {
     return r;
 }
 
-// (4 waves per SIMD: the kernel needs 131 VGPRs left alone, 128 -- no spill -- when asked; with 11.4 KB of LDS 14 waves fit a CU.
+// (4 waves per SIMD: 93 VGPRs -- 128 while the gather kept a base address per pair of sums and sub-tile; with 10.8 KB of LDS 14 waves fit a CU.
 //  AUX: 3 waves per SIMD -- up to 168 VGPRs, and the 12 waves of a CU may have 12.8 KB each: the slots of 10 with the same queue cap.
 //  ABS: 3 waves per SIMD as well, see the static_asserts at RasterLdsBwd)
 template <bool DET, bool AUX = false, bool ABS = false>
@@ -556,13 +566,32 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((AUX || ABS)
     // Upstream gradients of the lane's two pixels: g = (Gr, Gg, Gb, G_D, G_A - sum_c G_c bg_c), the last two AUX only, and the suffix
     // sum's start sfx = G+ . (C, D, A).  clamp(x, 0, 1) passes the gradient where 0 <= x <= 1 (render.py:410): x = C, or (AUX) what the
     // forward clamped, C over the background; gimg may be NULL in AUX only.
+    // Every load a wave starts with is issued before the first is waited for: the first chunk's ids (fetch_candidate, the oldest, so that
+    // its records can follow while the pixels' values arrive) and, per pixel, accum and gimg TOGETHER.  (gimg read only where the clamp
+    // passes put each of the six gimg loads behind its accum value: eight dependent round trips in front of every wave's first chunk.)
+    const bool alive_start = __any(lp.va || lp.vb);
+    Candidate cand;
+    if (alive_start) cand = fetch_candidate(lane, rg.x, rg.y, ids, rec, id_max, pair_mask);
     float g[2][5] = {}, sfx[2] = {0.f, 0.f};
     const bool vv[2] = {lp.va, lp.vb};
     const int py[2] = {lp.pya, lp.pyb};
+    float cu[2][3] = {}, gi[2][3] = {};
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         if (vv[k]) {
-            const int64_t p = (int64_t)py[k] * W + lp.px, o = p * 3;
+            const int64_t o = ((int64_t)py[k] * W + lp.px) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) cu[k][c] = accum[o + c];
+            if (!AUX || gimg) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) gi[k][c] = gimg[o + c];
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (vv[k]) {
+            const int64_t p = (int64_t)py[k] * W + lp.px;
             float D = 0.f, A = 0.f;                               // (AUX) the pixel's depth and opacity sums from the forward pass
             if constexpr (AUX) {
                 D = aux.accum_aux[p * 2]; A = aux.accum_aux[p * 2 + 1];
@@ -571,12 +600,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((AUX || ABS)
             }
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float cu = accum[o + c];
-                float shown = cu;                                 // what the forward clamped
-                if constexpr (AUX) { if (aux.has_bg) shown = over_background(cu, A, aux.bg[c]); }
-                const float gv = ((!AUX || gimg) && shown >= 0.0f && shown <= 1.0f) ? gimg[o + c] : 0.0f;
+                float shown = cu[k][c];                           // what the forward clamped
+                if constexpr (AUX) { if (aux.has_bg) shown = over_background(cu[k][c], A, aux.bg[c]); }
+                const float gv = (shown >= 0.0f && shown <= 1.0f) ? gi[k][c] : 0.0f;
                 g[k][c] = gv;
-                sfx[k] += gv * cu;
+                sfx[k] = __builtin_fmaf(gv, cu[k][c], sfx[k]);          // (spelled out: the three products of a pixel as ONE chain of fmas, whatever the vectoriser would pair)
                 if constexpr (AUX) { if (aux.has_bg) g[k][4] -= gv * aux.bg[c]; }
             }
             if constexpr (AUX) sfx[k] += g[k][3] * D + g[k][4] * A;
@@ -586,20 +614,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((AUX || ABS)
     const v2f Gd = {g[0][3], g[1][3]}, Ga = {g[0][4], g[1][4]};          // (AUX; else 0) dL/dD, dL/dA - sum_c G_c bg_c
     v2f suffix = {sfx[0], sfx[1]};
     const float chik = chi * QK, amax = alpha_max;
-    bool alive_any = __any(lp.va || lp.vb);
+    bool alive_any = alive_start;
     uint32_t base = rg.x;
-    Candidate cand;
-    if (alive_any) cand = fetch_candidate(lane, base, rg.y, ids, rec, id_max, pair_mask);
     const int my_g = lane / NS, my_k = lane - NS * my_g;           // flush: lane i carries sum my_k of the round's row my_g
     const uint16_t* myq = &s.q[grp][0];
     float* const myslot = &sb.slots[grp * MAXQ_BWD * NS + j];      // + NS k: where lane j of the group puts sum j of iteration k
     float* const acc = reinterpret_cast<float*>(&sb.f);            // [entry][NS]: over the record arrays, between a chunk's loop and the next stage
+    using Lds = RasterLdsBwd<DET, NS>;
+    static_assert(offsetof(Lds, f) == sizeof(sb.slots), "acc = the record arrays begin where the slots end");
+    float* const gcol = grad2d + (ABS ? grad2d_column<AUX>(my_k) : my_k);       // flush: the lane's column of row 0 of grad2d
+    uint32_t arow_off = (uint32_t)(sizeof(sb.slots) + lane * NS * 4);       // entry `lane`'s row of acc (acc lies behind the slots), its
+    asm("" : "+v"(arow_off));                                               // address kept whole like a slot's (see the gather)
+    float* const arow = reinterpret_cast<float*>(reinterpret_cast<char*>(&sb) + arow_off);
     while (alive_any && base < rg.y) {
         uint32_t m8;
         uint64_t ranks;
         const Staged sg = stage_chunk<MAXQ_BWD, 2, RasterLdsB, AUX>(s, cand, (int)min(rg.y - base, (uint32_t)CHUNK), lane, lp.ox, lp.oy, m8, ranks);
         const int n = sg.n, maxc = sg.maxc;
-        sb.eid[lane] = cand.id;
+        sb.eoff[lane] = cand.id * 16u;       // staged once per chunk: a flush round reads this one word per row and adds its column
         base += (uint32_t)n;
         if (base < rg.y) cand = fetch_candidate(lane, base, rg.y, ids, rec, id_max, pair_mask);   // in flight during the loop below
         ++st_chunks;
@@ -703,17 +735,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((AUX || ABS)
             for (int t = 0; t < N_SUB; ++t) {
                 const int r = (int)((ranks >> (8 * t)) & 0xFFu);
                 if (((m8 >> t) & 1u) && r < kdone) {
-                    const float* p = &sb.slots[(t * MAXQ_BWD + r) * NS];
+                    // The slot's byte offset as ONE v_mad_u32_u24, kept whole (the empty asm): the two offsets of a ds_read2 reach 255
+                    // words, so the compiler, left to fold the constant part, forms a base per pair of sums -- 5 instructions per round.
+                    // (The slots lie at LDS address 0 for the same reason: the offset is the address.)
+                    uint32_t off = __umul24((uint32_t)r, NS * 4) + (uint32_t)(t * MAXQ_BWD * NS * 4);
+                    asm("" : "+v"(off));
+                    const float* p = reinterpret_cast<const float*>(reinterpret_cast<const char*>(sb.slots) + off);
 #pragma unroll
                     for (int v = 0; v < NS; ++v) tot[v] += p[v];
                 }
             }
             if constexpr (ABS) { tot[NS - 2] *= INV_ABS_QK; tot[NS - 1] *= INV_ABS_QK; }      // the conic's pre-scaling, undone once per row
 #pragma unroll
-            for (int v = 0; v < NS; ++v) acc[lane * NS + v] = tot[v];
+            for (int v = 0; v < NS; ++v) arow[v] = tot[v];
         }
         if (DET && lane < n) {       // entry `lane`: its row's slot = first slot of its Gaussian + ordinal of this list in its rectangle
-            const uint32_t id = sb.eid[lane];
+            const uint32_t id = sb.eoff[lane] >> 4;
             const u2 rc = det.rect[id];
             const uint32_t mk = det.mask[id];
             const int x0 = (int)(rc.x & 0xFFFFu), y0 = (int)(rc.x >> 16), x1 = (int)(rc.y & 0xFFFFu);
@@ -745,7 +782,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((AUX || ABS)
                     const uint32_t slot = sb.eslot[c];
                     if (slot < det.capacity) det.part[(int64_t)slot * NS + my_k] = val;
                 } else if (val != 0.0f) {
-                    atomicAdd(&grad2d[(int64_t)sb.eid[c] * 16 + (ABS ? grad2d_column<AUX>(my_k) : my_k)], val);
+                    atomicAdd(gcol + sb.eoff[c], val);
                 }
             }
         }
