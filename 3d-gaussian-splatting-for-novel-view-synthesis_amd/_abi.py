@@ -34,6 +34,7 @@ GSPLAT_FILTER3D_CAMERA_FLOATS = 24
 GSPLAT_FILTER3D_CAMERA_CHUNK = 64
 GSPLAT_EXPOSURE_ACCUMULATE = 1
 GSPLAT_BILAGRID_ACCUMULATE = 1
+GSPLAT_METRICS_COLOUR_CORRECT = 1
 
 
 def sh_bands_dropped(degree):
@@ -220,6 +221,9 @@ SIGNATURES = {
     "gsplat_bilagrid_backward": (_INT, [_VP, _VP, _VP, _I64] + [C.c_int32] * 5 + [_VP, _VP, _VP, C.c_int32, _VP]),
     "gsplat_bilagrid_tv_scratch_bytes": (_I64, [_I64, C.c_int32, C.c_int32, C.c_int32]),
     "gsplat_bilagrid_tv": (_INT, [_VP, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_float, _VP, _VP, C.c_int32, _VP, _VP]),
+    "gsplat_metrics_scratch_bytes": (_I64, [C.c_int32] * 4),
+    "gsplat_metrics_fit_affine": (_INT, [_VP, _VP, _VP] + [C.c_int32] * 3 + [_VP, _VP, _VP]),
+    "gsplat_metrics_forward": (_INT, [_VP, _VP, _VP] + [C.c_int32] * 4 + [_VP, _VP, _VP, _VP]),
 }
 
 _lib = None

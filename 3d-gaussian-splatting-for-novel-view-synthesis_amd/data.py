@@ -175,6 +175,16 @@ class GaussianDataset:
                 'cy': cp['cy'] * s if has_c else H / 2.0, 'H': H, 'W': W, 'idx': idx, **extra}
 
 
+def split_views(n, hold=8):
+    """(train_indices, test_indices) of a dataset of n images (not in the reference, which trains on all of them): every hold-th image
+    -- i % hold == 0 -- is a held-out test view, the Mip-NeRF 360 / INRIA `--eval` convention (hold = 8).  hold < 1: ValueError."""
+    if type(n) is not int or n < 0:
+        raise ValueError(f"n must be an integer >= 0, not {n!r}")
+    if type(hold) is not int or hold < 1:
+        raise ValueError(f"hold must be an integer >= 1, not {hold!r}")
+    return [i for i in range(n) if i % hold], [i for i in range(n) if i % hold == 0]
+
+
 def initialize_gaussians_from_pointcloud(points, num_sh_bands=3):
     """One Gaussian per point: log-scale -2 +- 0.1, identity quaternion (0,0,0,1), opacity_raw 0.1, colours from columns
     3-5 (divided by 255 if > 1) or uniform random, zero higher-order SH (data_loader.py:287-367).  Only num_sh_bands >= 3

@@ -40,7 +40,7 @@ from dataclasses import dataclass
 import torch
 import torch.distributed as dist
 
-from . import _abi, bilagrid, dp, exposure, filter3d, losses, mcmc, ops, optim
+from . import _abi, bilagrid, dp, exposure, filter3d, losses, mcmc, metrics, ops, optim
 
 
 @dataclass
@@ -483,6 +483,31 @@ class Trainer:
             self.densify_stats.reset(m.get_num_gaussians())
         self._pass_stats, self._pass_dirty = [], False
         return {'removed': removed, 'gaussians': m.get_num_gaussians(), 'frames': stats.frames}
+
+    @torch.no_grad()
+    def evaluate(self, views, iteration=None, colour_correct=None):
+        """Per-image PSNR, SSIM and L1 of held-out `views` (the dicts step() takes, with their photographs):
+        metrics.evaluate of the model as step() renders it -- the trainer's lowpass / antialias, the SH degree of `iteration` (None:
+        degree 3), the filtered scale and opacity when filter3d > 0 (filter3d.apply, without gradient) -- over the trainer's group.
+        The views are rendered over the trainer's background colour; background = "random" evaluates over BLACK (a report must not
+        depend on a draw).  The exposure / bilateral-grid tables are NOT applied -- a held-out view has no row in them -- so with
+        either on the model is only known up to a colour transform per image: colour_correct (None: cfg.exposure or cfg.bilagrid) fits
+        that transform per view before measuring.  Returns metrics.evaluate's report.  Not part of step(); parameters, gradients, the
+        optimiser, the statistics windows, the visible set and both tables are left bit for bit as they were.  Data parallel:
+        collective -- every rank calls it with the same list."""
+        c, m = self.cfg, self.model
+        dev = m.pos.device
+        params = m
+        if c.filter3d > 0:
+            filt = self.filter3d                   # (a local one where step() has not made it yet: nothing of the trainer changes here)
+            if filt is None or filt.shape[0] != m.get_num_gaussians() or filt.device != dev:
+                filt = filter3d.compute(m.pos, self._cameras.to(dev), s=c.filter3d, near=c.filter3d_near, margin=c.filter3d_margin)
+            params = filter3d.bake(m, filt)
+        if colour_correct is None:
+            colour_correct = bool(c.exposure or c.bilagrid)
+        return metrics.evaluate(params, views, sh_degree=3 if iteration is None else self.sh_degree(iteration),
+                                background=None if self._background == "random" else self._background, colour_correct=colour_correct,
+                                group=self.group, **self._filter_kw)
 
     def step(self, iteration, views, global_views=None, views_per_rank=None):
         """One iteration on this rank's `views` (list of dicts with image [H,W,3], c2w [4,4], H, W, fx, fy, cx, cy — the

@@ -674,6 +674,29 @@ int64_t gsplat_bilagrid_tv_scratch_bytes(int64_t V, int32_t X, int32_t Y, int32_
 int gsplat_bilagrid_tv(const float* grids, int64_t V, int32_t X, int32_t Y, int32_t L, float scale, float* loss_out, float* grad, int32_t flags,
                        void* scratch, void* stream);
 
+/* ---- image quality metrics of held-out views (not in the reference) -------------------------------------------------
+ * Per image b of pred, target [B, H, W, 3] floats over the valid pixels of mask [B, H, W] bytes (nonzero = valid; NULL: every pixel):
+ *     l1 = sum |x - y| / (3 n),  mse = sum (x - y)^2 / (3 n),  psnr = -10 log10(mse) (+inf for mse == 0),
+ *     ssim = the SSIM map of gsplat_loss (computed from the whole images: the mask does not alter the window statistics) averaged over
+ *     the valid pixels and the three channels;  n == 0: NaN in all four (and in the affine), no other image is affected.
+ * out: [B, 4] = psnr, ssim, l1, mse.  GSPLAT_METRICS_COLOUR_CORRECT: first the affine [M | t] (twelve floats row-major 3 x 4, the layout of
+ * gsplat_exposure_forward's params) minimising sum_valid |M x + t - y|^2 with a ridge of 1e-8 n toward the identity is fitted per image
+ * and written to affine [B, 12]; the metrics are then those of clamp(M x + t, 0, 1) against y (the SSIM window's zero padding is of
+ * the corrected image).  Without the flag nothing is clamped and affine may be NULL.  gsplat_metrics_fit_affine runs the fit alone.
+ * B, H, W >= 1, B <= 65535, H <= 16 x 65535, H W < 2^38, else GSPLAT_ERR_BAD_ARG (the scratch size: -1), as for a NULL required pointer, an unknown flag
+ * bit or the flag with a NULL affine -- before anything is launched.  Every entry runs on the caller's stream, reads nothing back and
+ * allocates nothing.  No float atomics: every sum is formed in a fixed order (per thread, wave, workgroup and over the workgroups of
+ * an image, in double from the first term on -- the SSIM values themselves are fp32 --; pixel counts in integers), so the values are the same
+ * bits on every call, stream and launch, and an image gets in a batch the bits it gets alone.
+ * scratch: gsplat_metrics_scratch_bytes(B, H, W, flags) device bytes, 8-byte aligned, any contents (the fit alone: the size with the
+ * flag); one call at a time per scratch buffer.  Two launches, four with the flag (the fit alone: two).                             */
+#define GSPLAT_METRICS_COLOUR_CORRECT 1
+int64_t gsplat_metrics_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t flags);
+int gsplat_metrics_fit_affine(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t H, int32_t W, float* affine,
+                              void* scratch, void* stream);
+int gsplat_metrics_forward(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t H, int32_t W, int32_t flags,
+                           float* affine, float* out, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
