@@ -20,6 +20,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "gs_blocksum.h"
+
 namespace {
 
 constexpr int AUX_THREADS = 256;
@@ -59,7 +61,7 @@ __device__ __forceinline__ float aux_residual(float d, float a, float z) { retur
 __global__ __launch_bounds__(AUX_THREADS) void aux_loss_sums_kernel(const float* __restrict__ depth, const float* __restrict__ alpha,
                                                                     const float* __restrict__ tdepth, const float* __restrict__ talpha,
                                                                     int64_t n, int vec, float* __restrict__ partial) {
-    __shared__ float red[3][AUX_THREADS / 64];
+    __shared__ float red[AUX_THREADS / 64][3];
     const int tid = threadIdx.x;
     const int64_t i = ((int64_t)blockIdx.x * AUX_THREADS + tid) * AUX_PIX;
     float sa = 0.f, sd = 0.f, sv = 0.f;
@@ -85,14 +87,13 @@ __global__ __launch_bounds__(AUX_THREADS) void aux_loss_sums_kernel(const float*
         }
     }
     // the workgroup's three sums, in a fixed order (the count is exact: at most 1024)
-    for (int sft = 32; sft > 0; sft >>= 1) { sa += __shfl_xor(sa, sft); sd += __shfl_xor(sd, sft); sv += __shfl_xor(sv, sft); }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = sa; red[1][tid >> 6] = sd; red[2][tid >> 6] = sv; }
-    __syncthreads();
+    // (two sums of absolute values and a count: none can be -0.0)
+    const float sums[3] = {sa, sd, sv};
+    gsblk::sum(sums, red);
     if (tid == 0) {
-        float x = 0.f, y = 0.f, c = 0.f;
-        for (int k = 0; k < AUX_THREADS / 64; ++k) { x += red[0][k]; y += red[1][k]; c += red[2][k]; }
         float* out = partial + (int64_t)blockIdx.x * 3;
-        out[0] = x; out[1] = y; out[2] = c;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[k] = gsblk::column<AUX_THREADS / 64>(red, k);
     }
 }
 
@@ -100,18 +101,16 @@ __global__ __launch_bounds__(AUX_THREADS) void aux_loss_finish_kernel(const floa
                                                                       float lambda_depth, float lambda_alpha, double scale,
                                                                       float* __restrict__ values, float* __restrict__ total,
                                                                       double* __restrict__ n_valid) {
-    __shared__ double red[3][AUX_THREADS / 64];
+    __shared__ double red[AUX_THREADS / 64][3];
     const int tid = threadIdx.x;
     double x = 0.0, y = 0.0, c = 0.0;
     for (int k = tid; k < n_blocks; k += AUX_THREADS) {
         x += (double)partial[3 * (int64_t)k]; y += (double)partial[3 * (int64_t)k + 1]; c += (double)partial[3 * (int64_t)k + 2];
     }
-    for (int sft = 32; sft > 0; sft >>= 1) { x += __shfl_xor(x, sft); y += __shfl_xor(y, sft); c += __shfl_xor(c, sft); }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = x; red[1][tid >> 6] = y; red[2][tid >> 6] = c; }
-    __syncthreads();
+    const double sums[3] = {x, y, c};                                       // (of partials that are not negative: none can be -0.0)
+    gsblk::sum(sums, red);
     if (tid == 0) {
-        x = 0.0; y = 0.0; c = 0.0;
-        for (int k = 0; k < AUX_THREADS / 64; ++k) { x += red[0][k]; y += red[1][k]; c += red[2][k]; }
+        x = gsblk::column<AUX_THREADS / 64>(red, 0); y = gsblk::column<AUX_THREADS / 64>(red, 1); c = gsblk::column<AUX_THREADS / 64>(red, 2);
         const double nv = c > 1.0 ? c : 1.0;
         const double la = x * inv_n, ld = y / nv;
         values[0] = (float)(scale * la); values[1] = (float)(scale * ld);

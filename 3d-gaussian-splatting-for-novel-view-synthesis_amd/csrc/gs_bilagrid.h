@@ -46,6 +46,9 @@
 // wave order (7 additions): BILAGRID_SUM_DEPTH_FIXED = 13 additions above the thread's own.
 #pragma once
 #include "gs_math.h"
+#if defined(__HIPCC__)
+#include "gs_blocksum.h"
+#endif
 
 namespace gsbila {
 
@@ -314,18 +317,13 @@ __global__ __launch_bounds__(BILAGRID_GATHER_THREADS) void bilagrid_gather_kerne
         }
         // the workgroup's sums, in a fixed order
 #pragma unroll
-        for (int k = 0; k < NS; ++k)
-            for (int sft = 32; sft > 0; sft >>= 1) s[k] += __shfl_xor(s[k], sft);
+        for (int k = 0; k < NS; ++k) s[k] = gsblk::ladder(s[k]);
         __syncthreads();                                                        // (the last group's readers are done with red)
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < NS; ++k) red[wave][k] = s[k];
-        }
+        gsblk::stage(s, red);
         __syncthreads();
         const int lg = tid / BILAGRID_CHANNELS, ch = tid % BILAGRID_CHANNELS;
         if (tid < NS && l0 + lg < L) {
-            float x = red[0][tid];
-            for (int w = 1; w < WAVES; ++w) x += red[w][tid];
+            const float x = gsblk::column<WAVES>(red, tid);
             float* d = dest + ((row * BILAGRID_CHANNELS + ch) * L + (l0 + lg)) * Y * X + (int64_t)gy * X + gx;
             *d = add ? *d + x : x;
         }
@@ -349,14 +347,8 @@ __global__ __launch_bounds__(BILAGRID_THREADS) void bilagrid_tv_kernel(const flo
         if (grad) grad[e] = add ? grad[e] + g : g;
     }
     if (!partial) return;
-    for (int sft = 32; sft > 0; sft >>= 1) loss += __shfl_xor(loss, sft);
-    if ((tid & 63) == 0) red[tid >> 6] = loss;
-    __syncthreads();
-    if (tid == 0) {
-        double x = red[0];
-        for (int w = 1; w < BILAGRID_THREADS / 64; ++w) x += red[w];
-        partial[(int64_t)blockIdx.x * gridDim.y + blockIdx.y] = x;
-    }
+    gsblk::sum(loss, red);
+    if (tid == 0) partial[(int64_t)blockIdx.x * gridDim.y + blockIdx.y] = gsblk::column<BILAGRID_THREADS / 64>(red);
 }
 
 // ONE workgroup adds the partial sums in a fixed order, in double; loss_out = (float)(scale * the sum)
@@ -366,14 +358,8 @@ __global__ __launch_bounds__(BILAGRID_THREADS) void bilagrid_tv_finish_kernel(co
     const int tid = threadIdx.x;
     double s = 0.0;
     for (int64_t b = tid; b < n_blocks; b += BILAGRID_THREADS) s += partial[b];
-    for (int sft = 32; sft > 0; sft >>= 1) s += __shfl_xor(s, sft);
-    if ((tid & 63) == 0) red[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) {
-        double x = red[0];
-        for (int w = 1; w < BILAGRID_THREADS / 64; ++w) x += red[w];
-        *loss_out = (float)(scale * x);
-    }
+    gsblk::sum(s, red);
+    if (tid == 0) *loss_out = (float)(scale * gsblk::column<BILAGRID_THREADS / 64>(red));
 }
 
 #endif  // __HIPCC__

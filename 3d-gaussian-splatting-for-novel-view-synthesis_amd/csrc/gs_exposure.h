@@ -29,6 +29,9 @@
 // the stream or on the launch: the gradient is the same bits every time.
 #pragma once
 #include "gs_math.h"
+#if defined(__HIPCC__)
+#include "gs_blocksum.h"
+#endif
 
 namespace gsexp {
 
@@ -134,19 +137,9 @@ __global__ __launch_bounds__(EXPOSURE_THREADS) void exposure_backward_kernel(con
     }
     if (!PAR) return;
     // the workgroup's twelve sums, in a fixed order
-#pragma unroll
-    for (int k = 0; k < EXPOSURE_PARAMS; ++k)
-        for (int sft = 32; sft > 0; sft >>= 1) s[k] += __shfl_xor(s[k], sft);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < EXPOSURE_PARAMS; ++k) red[tid >> 6][k] = s[k];
-    }
-    __syncthreads();
-    if (tid < EXPOSURE_PARAMS) {
-        float x = red[0][tid];
-        for (int w = 1; w < EXPOSURE_THREADS / 64; ++w) x += red[w][tid];
-        partial[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * EXPOSURE_PARAMS + tid] = x;
-    }
+    gsblk::sum(s, red);
+    if (tid < EXPOSURE_PARAMS)
+        partial[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * EXPOSURE_PARAMS + tid] = gsblk::column<EXPOSURE_THREADS / 64>(red, tid);
 }
 
 // One workgroup per image.  row_index (device, int32, may be NULL): image b goes to row row_index[b] of dest, else to row b; a negative
@@ -163,6 +156,8 @@ __global__ __launch_bounds__(EXPOSURE_THREADS) void exposure_finish_kernel(const
 #pragma unroll
         for (int k = 0; k < EXPOSURE_PARAMS; ++k) s[k] += (double)rows[(int64_t)b * EXPOSURE_PARAMS + k];
     }
+    // (copy: gsblk::sum and gsblk::column of gs_blocksum.h, spelled out -- through the helpers this kernel, alone among their users,
+    //  comes out one VGPR and three s_waitcnt larger; the order of the additions is the same)
 #pragma unroll
     for (int k = 0; k < EXPOSURE_PARAMS; ++k)
         for (int sft = 32; sft > 0; sft >>= 1) s[k] += __shfl_xor(s[k], sft);

@@ -40,69 +40,22 @@
 
 #include "../../include/gsplat_mi355x.h"
 #include "gs_aux_loss.h"
+#include "gs_blocksum.h"
 #include "gs_entry.h"
+#include "gs_ssim_tile.h"
 
 namespace {
 
-constexpr int TW = 32, TH = 16, R = 5, TAPS = 11;
-constexpr int W1 = TW + 2 * R, H1 = TH + 2 * R;      // region with one halo   42 x 26
-constexpr int THREADS = 256;
-constexpr int G = 4;                                 // outputs per thread along a row in the horizontal passes
-constexpr int GV = 2;                                // rows per thread in the vertical passes
-static_assert(TW % G == 0 && TH % GV == 0 && (TH / GV) * TW == THREADS, "tile shape vs register blocking");
-
-// LDS access patterns.  Horizontal passes: lanes run over ROWS (row index fastest), every lane reads G + 10 = 14 consecutive words of
-// its own row as 3 x 16 + 8 bytes and writes G = 4 words as 16 bytes; the row pitches are multiples of 4 words (alignment) chosen so
-// that the 8 lanes a 16-byte access serves per cycle fall on 8 disjoint groups of 4 banks (44 r mod 32 = 0, 12, 24, 4, 16, 28, 8, 20;
-// 36 r mod 32 = 0, 4, ... 28).  (Odd pitches with 4-byte accesses, the first version: 14 + 14 instead of 4 + 4 LDS instructions per
-// thread and pass, 30-37 % of the LDS cycles bank conflicts.)  Vertical passes: lanes run over the 32 columns of a row group, two
-// row groups per wave: consecutive words.
-constexpr int XP = 44;           // pitch of the input planes / the map planes (W1 = 42 columns)
-constexpr int HP = 36;           // pitch of the horizontally filtered planes (TW = 32 columns)
-static_assert(XP >= W1 && XP % 4 == 0 && HP >= TW && HP % 4 == 0, "row pitches: 16-byte rows");
-
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-// 14 consecutive floats of an LDS row from a 16-byte aligned position
-__device__ __forceinline__ void load14(const float* p, float (&a)[G + 10]) {
-    const f4v v0 = *reinterpret_cast<const f4v*>(p), v1 = *reinterpret_cast<const f4v*>(p + 4), v2 = *reinterpret_cast<const f4v*>(p + 8);
-    const f2v v3 = *reinterpret_cast<const f2v*>(p + 12);
-    a[0] = v0.x; a[1] = v0.y; a[2] = v0.z; a[3] = v0.w; a[4] = v1.x; a[5] = v1.y; a[6] = v1.z; a[7] = v1.w;
-    a[8] = v2.x; a[9] = v2.y; a[10] = v2.z; a[11] = v2.w; a[12] = v3.x; a[13] = v3.y;
-}
-static_assert(G == 4, "load14 / the 16-byte stores assume four outputs per thread");
-
-__device__ __forceinline__ void gauss_taps(float g[TAPS]) {
-    // losses.py:131-155: exp(-(i - 5)^2 / (2 * 1.5^2)), normalised
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < TAPS; ++i) { const float d = (float)(i - R); g[i] = expf(-(d * d) / 4.5f); s += g[i]; }
-    const float inv = 1.0f / s;
-    // (the same eleven values in every lane: kept in SGPRs, they cost no vector register)
-#pragma unroll
-    for (int i = 0; i < TAPS; ++i) g[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g[i] * inv)));
-}
-
-// region element i (row-major over H1 x W1) of channel ch of a [H][W][3] image, zero outside the image
-struct alignas(16) StatsLds {
-    float x[3][H1][XP], y[3][H1][XP];     // the three channels of the region, de-interleaved
-    float h[5][H1][HP];                   // horizontally filtered x, y, xx, yy, (x - y)^2 of the channel being processed
-};
-static_assert(sizeof(StatsLds) <= 52 * 1024, "three workgroups per CU");
-
 // Sum of the blocks' partial sums in a fixed order (double), by one workgroup: -> values[3] = (l1, 1 - ssim, total)
 __device__ __forceinline__ void finish_sums(const float* __restrict__ partial, int n_blocks, double inv_n, float l1w, float sw,
-                                            float* __restrict__ values, double (*red)[THREADS / 64], double scale = 1.0,
+                                            float* __restrict__ values, double (*red)[2], double scale = 1.0,
                                             float* __restrict__ total_out = nullptr) {
     const int tid = threadIdx.x;
-    double a = 0.0, b = 0.0;
-    for (int k = tid; k < n_blocks; k += THREADS) { a += (double)partial[2 * k]; b += (double)partial[2 * k + 1]; }
-    for (int sft = 32; sft > 0; sft >>= 1) { a += __shfl_xor(a, sft); b += __shfl_xor(b, sft); }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = a; red[1][tid >> 6] = b; }
-    __syncthreads();
+    double ab[2] = {0.0, 0.0};                                             // (additions from +0.0 on: neither sum can be -0.0)
+    for (int k = tid; k < n_blocks; k += THREADS) { ab[0] += (double)partial[2 * k]; ab[1] += (double)partial[2 * k + 1]; }
+    gsblk::sum(ab, red);
     if (tid == 0) {
-        a = 0.0; b = 0.0;
-        for (int k = 0; k < THREADS / 64; ++k) { a += red[0][k]; b += red[1][k]; }
+        const double a = gsblk::column<THREADS / 64>(red, 0), b = gsblk::column<THREADS / 64>(red, 1);
         const double l1 = a * inv_n, sl = 1.0 - b * inv_n;
         values[0] = (float)(scale * l1); values[1] = (float)(scale * sl); values[2] = (float)(scale * (l1w * l1 + sw * sl));
         if (total_out) *total_out = values[2];
@@ -114,7 +67,7 @@ __device__ __forceinline__ void finish_sums(const float* __restrict__ partial, i
 __global__ __launch_bounds__(THREADS) void loss_stats_kernel(const float* __restrict__ pred, const float* __restrict__ target, int H, int W,
                                                              float* __restrict__ partial, float* __restrict__ maps) {
     __shared__ StatsLds s;
-    __shared__ float red[2][THREADS / 64];
+    __shared__ float red[THREADS / 64][2];
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
     const int64_t img = (int64_t)blockIdx.z * H * W * 3;
@@ -122,86 +75,53 @@ __global__ __launch_bounds__(THREADS) void loss_stats_kernel(const float* __rest
     float g[TAPS];
     gauss_taps(g);
     const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-    float l1_acc = 0.f, ssim_acc = 0.f;
-    {   // the region of all three channels at once: rows of 3 * 42 consecutive floats of the interleaved image, every load of the
-        // workgroup in flight together (one exposed round trip per workgroup; fetched channel by channel, with the next channel's
-        // prefetch in registers, a workgroup waited for memory three times: 87 -> 63 us was the LDS side, this is the other half)
-        // (pixel e = tid + 256 k of the region as (row, column): stepped, not divided -- 256 = 6 * 42 + 4; the three channels of a
-        //  pixel are 12 consecutive bytes of the interleaved image: one address per pixel and image)
-        constexpr int N = H1 * W1, SLOTS = (N + THREADS - 1) / THREADS;
-        static_assert(THREADS == 6 * W1 + 4, "the stepping below");
-        float ra[SLOTS][3], rb[SLOTS][3];
-        const int r_first = tid / W1, c_first = tid - r_first * W1;
-        {
-            int r = r_first, c = c_first;
+    float acc[2] = {0.f, 0.f};                                             // the sums of |x - y| and of S
+    {   // the region of all three channels at once: rows of 3 * 42 consecutive floats of the interleaved image (the three channels of
+        // a pixel are 12 consecutive bytes: one address per pixel and image), loaded in one walk and stored in a second (RegionWalk)
+        float ra[REGION_SLOTS][3], rb[REGION_SLOTS][3];
+        RegionWalk p(tid);
 #pragma unroll
-            for (int k = 0; k < SLOTS; ++k) {
-                const int gy = y0 - R + r, gx = x0 - R + c;
-                const bool in = r < H1 && gy >= 0 && gy < H && gx >= 0 && gx < W;      // zero outside the image = the reference's zero padding
-                const int64_t o = img + ((int64_t)gy * W + gx) * 3;
+        for (int k = 0; k < REGION_SLOTS; ++k, p.next()) {
+            const int gy = y0 - R + p.r, gx = x0 - R + p.c;
+            const bool in = p.r < H1 && gy >= 0 && gy < H && gx >= 0 && gx < W;    // zero outside the image = the reference's zero padding
+            const int64_t o = img + ((int64_t)gy * W + gx) * 3;
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) { ra[k][ch] = in ? pred[o + ch] : 0.f; rb[k][ch] = in ? target[o + ch] : 0.f; }
-                r += 6; c += 4;
-                if (c >= W1) { c -= W1; ++r; }
-            }
+            for (int ch = 0; ch < 3; ++ch) { ra[k][ch] = in ? pred[o + ch] : 0.f; rb[k][ch] = in ? target[o + ch] : 0.f; }
         }
-        {
-            int r = r_first, c = c_first;
+        RegionWalk q(tid);
 #pragma unroll
-            for (int k = 0; k < SLOTS; ++k) {
-                if (r < H1) {
+        for (int k = 0; k < REGION_SLOTS; ++k, q.next()) {
+            if (q.r < H1) {
 #pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) { s.x[ch][r][c] = ra[k][ch]; s.y[ch][r][c] = rb[k][ch]; }
-                }
-                r += 6; c += 4;
-                if (c >= W1) { c -= W1; ++r; }
+                for (int ch = 0; ch < 3; ++ch) { s.x[ch][q.r][q.c] = ra[k][ch]; s.y[ch][q.r][q.c] = rb[k][ch]; }
             }
         }
     }
+#pragma unroll                                                             // (three copies, as the compiler made of it unasked)
     for (int ch = 0; ch < 3; ++ch) {
         __syncthreads();                                                   // the region is staged / the previous channel's h is read
-        // horizontal pass of the five products: G outputs per thread from G + 10 inputs (the products formed once per input)
+        // horizontal pass of the five products: G outputs per thread from G + 10 inputs
         for (int i = tid; i < H1 * (TW / G); i += THREADS) {
-            const int r = i % H1, c = (i / H1) * G;                        // rows fastest across lanes
-            float a[G + 10], b[G + 10], aa[G + 10], bb[G + 10], dd[G + 10];
-            load14(&s.x[ch][r][c], a);
-            load14(&s.y[ch][r][c], b);
-#pragma unroll
-            for (int t = 0; t < G + 10; ++t) { const float d = a[t] - b[t]; aa[t] = a[t] * a[t]; bb[t] = b[t] * b[t]; dd[t] = d * d; }
-            f4v o0, o1, o2, o3, o4;
-#pragma unroll
-            for (int o = 0; o < G; ++o) {
-                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
-#pragma unroll
-                for (int t = 0; t < TAPS; ++t) {
-                    const float w = g[t];
-                    a0 += w * a[o + t]; a1 += w * b[o + t]; a2 += w * aa[o + t]; a3 += w * bb[o + t]; a4 += w * dd[o + t];
-                }
-                o0[o] = a0; o1[o] = a1; o2[o] = a2; o3[o] = a3; o4[o] = a4;
-            }
-            *reinterpret_cast<f4v*>(&s.h[0][r][c]) = o0; *reinterpret_cast<f4v*>(&s.h[1][r][c]) = o1; *reinterpret_cast<f4v*>(&s.h[2][r][c]) = o2;
-            *reinterpret_cast<f4v*>(&s.h[3][r][c]) = o3; *reinterpret_cast<f4v*>(&s.h[4][r][c]) = o4;
+            const int r = i % H1, c = (i / H1) * G;
+            float v[5][G + 10];
+            load14(&s.x[ch][r][c], v[0]);
+            load14(&s.y[ch][r][c], v[1]);
+            stats_planes(v);
+            filter_row<5>(g, v, s.h, r, c);
         }
         __syncthreads();
         // vertical pass -> SSIM value and its partial derivatives on the tile: GV rows per thread; the L1 term rides along
         {
             const int rg = tid / TW, c = tid - rg * TW, r0 = rg * GV;
             float v[5][GV + 10];
-#pragma unroll
-            for (int k = 0; k < 5; ++k)
-#pragma unroll
-                for (int t = 0; t < GV + 10; ++t) v[k][t] = s.h[k][r0 + t][c];
+            gather_column(&s.h[0][r0][c], v);
 #pragma unroll
             for (int o = 0; o < GV; ++o) {
                 const int gy = y0 + r0 + o, gx = x0 + c;
                 if (gy < H && gx < W) {
-                    float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, edd = 0.f;
-#pragma unroll
-                    for (int t = 0; t < TAPS; ++t) {
-                        const float w = g[t];
-                        mu1 += w * v[0][o + t]; mu2 += w * v[1][o + t]; e11 += w * v[2][o + t]; e22 += w * v[3][o + t];
-                        edd += w * v[4][o + t];
-                    }
+                    float f[5];
+                    filter_column(g, v, o, f);
+                    const float mu1 = f[0], mu2 = f[1], e11 = f[2], e22 = f[3], edd = f[4];
                     const float dm = mu1 - mu2, sd = edd - dm * dm;          // variance of x - y = s11 + s22 - 2 s12: 0 for x == y
                     const float A1 = 2.f * mu1 * mu2 + C1, B1 = mu1 * mu1 + mu2 * mu2 + C1;
                     const float B2 = (e11 - mu1 * mu1) + (e22 - mu2 * mu2) + C2, A2 = B2 - sd;
@@ -209,8 +129,8 @@ __global__ __launch_bounds__(THREADS) void loss_stats_kernel(const float* __rest
                     const float rb1 = __builtin_amdgcn_rcpf(B1), rb2 = __builtin_amdgcn_rcpf(B2);
                     const float ib = rb1 * rb2;
                     const float S = A1 * A2 * ib;
-                    ssim_acc += S;
-                    l1_acc += fabsf(s.x[ch][r0 + o + R][c + R] - s.y[ch][r0 + o + R][c + R]);
+                    acc[1] += S;
+                    acc[0] += fabsf(s.x[ch][r0 + o + R][c + R] - s.y[ch][r0 + o + R][c + R]);
                     if (maps) {
                         float* m = maps + ((int64_t)blockIdx.z * 3 + ch) * 3 * plane + (int64_t)gy * W + gx;
                         const float t1 = A2 * rb1 * (mu2 * dm * dm - dm * A1), t2 = A1 * rb2 * (mu2 * sd - dm * A2);
@@ -223,15 +143,13 @@ __global__ __launch_bounds__(THREADS) void loss_stats_kernel(const float* __rest
         }
     }
     // the block's two sums (fixed order inside the block)
-    for (int sft = 32; sft > 0; sft >>= 1) { l1_acc += __shfl_xor(l1_acc, sft); ssim_acc += __shfl_xor(ssim_acc, sft); }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = l1_acc; red[1][tid >> 6] = ssim_acc; }
-    __syncthreads();
+    gsblk::sum(acc, red);
     if (tid == 0) {
-        float a = 0.f, b = 0.f;
-        for (int k = 0; k < THREADS / 64; ++k) { a += red[0][k]; b += red[1][k]; }
         const int64_t blk = blockIdx.x + (int64_t)gridDim.x * (blockIdx.y + (int64_t)gridDim.y * blockIdx.z);
-        partial[2 * blk] = a;
-        partial[2 * blk + 1] = b;
+        partial[2 * blk] = gsblk::column<THREADS / 64>(red, 0);                     // (a sum of |d|: never -0.0)
+        // (S may ride an fma into its sum, and a product that underflows from below leaves -0.0 there: "0 +" keeps a tile of
+        //  nothing but such values at the +0.0 it has always been, and changes no other sum)
+        partial[2 * blk + 1] = 0.f + gsblk::column<THREADS / 64>(red, 1);
     }
 }
 
@@ -250,7 +168,7 @@ __global__ __launch_bounds__(THREADS) void loss_grad_kernel(const float* __restr
     // upstream (nullable device scalar): d L / d total of the caller's graph -- multiplied in here, not by a pass over the gradient
     const float inv_n = upstream ? inv_n_ * *upstream : inv_n_;
     __shared__ GradLds s;
-    __shared__ double red[2][THREADS / 64];
+    __shared__ double red[THREADS / 64][2];
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
     const int64_t img = (int64_t)blockIdx.z * H * W * 3;
@@ -260,26 +178,18 @@ __global__ __launch_bounds__(THREADS) void loss_grad_kernel(const float* __restr
     // this thread's GV pixels (rows r0, r0 + 1 of column c): x, y of the three channels, and the gradient as it comes
     const int rg = tid / TW, c = tid - rg * TW, r0 = rg * GV;
     float px[GV][3], py[GV][3], out[GV][3];
-    {   // the nine map planes of the region at once (see loss_stats_kernel), then this thread's pixels
-        // (pixel e = tid + 256 k of the region as (row, column): stepped, not divided -- 256 = 6 * 42 + 4; one address per pixel, the
-        //  nine planes at constant distances)
-        constexpr int N = H1 * W1, SLOTS = (N + THREADS - 1) / THREADS;
-        static_assert(THREADS == 6 * W1 + 4, "the stepping below");
+    {   // the nine map planes of the region at once (one address per pixel, the nine planes at constant distances), then this
+        // thread's pixels, then the stores (RegionWalk, as in loss_stats_kernel)
         const float* m = maps + (int64_t)blockIdx.z * 9 * plane;
-        float rp[SLOTS][9];
-        const int r_first = tid / W1, c_first = tid - r_first * W1;
-        {
-            int r = r_first, cc = c_first;
+        float rp[REGION_SLOTS][9];
+        RegionWalk p(tid);
 #pragma unroll
-            for (int k = 0; k < SLOTS; ++k) {
-                const int gy = y0 - R + r, gx = x0 - R + cc;
-                const bool in = r < H1 && gy >= 0 && gy < H && gx >= 0 && gx < W;
-                const float* mp = m + (int64_t)gy * W + gx;
+        for (int k = 0; k < REGION_SLOTS; ++k, p.next()) {
+            const int gy = y0 - R + p.r, gx = x0 - R + p.c;
+            const bool in = p.r < H1 && gy >= 0 && gy < H && gx >= 0 && gx < W;
+            const float* mp = m + (int64_t)gy * W + gx;
 #pragma unroll
-                for (int pl = 0; pl < 9; ++pl) rp[k][pl] = in ? mp[pl * plane] : 0.f;
-                r += 6; cc += 4;
-                if (cc >= W1) { cc -= W1; ++r; }
-            }
+            for (int pl = 0; pl < 9; ++pl) rp[k][pl] = in ? mp[pl * plane] : 0.f;
         }
 #pragma unroll
         for (int o = 0; o < GV; ++o) {
@@ -289,16 +199,12 @@ __global__ __launch_bounds__(THREADS) void loss_grad_kernel(const float* __restr
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) { px[o][ch] = in ? pred[a + ch] : 0.f; py[o][ch] = in ? target[a + ch] : 0.f; out[o][ch] = 0.f; }
         }
-        {
-            int r = r_first, cc = c_first;
+        RegionWalk q(tid);
 #pragma unroll
-            for (int k = 0; k < SLOTS; ++k) {
-                if (r < H1) {
+        for (int k = 0; k < REGION_SLOTS; ++k, q.next()) {
+            if (q.r < H1) {
 #pragma unroll
-                    for (int pl = 0; pl < 9; ++pl) s.p[pl / 3][pl % 3][r][cc] = rp[k][pl];
-                }
-                r += 6; cc += 4;
-                if (cc >= W1) { cc -= W1; ++r; }
+                for (int pl = 0; pl < 9; ++pl) s.p[pl / 3][pl % 3][q.r][q.c] = rp[k][pl];
             }
         }
     }
@@ -312,28 +218,17 @@ __global__ __launch_bounds__(THREADS) void loss_grad_kernel(const float* __restr
             float v[3][G + 10];
 #pragma unroll
             for (int k = 0; k < 3; ++k) load14(&s.p[ch][k][r][cc], v[k]);
-            f4v o0, o1, o2;
-#pragma unroll
-            for (int o = 0; o < G; ++o) {
-                float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-#pragma unroll
-                for (int t = 0; t < TAPS; ++t) { const float w = g[t]; a0 += w * v[0][o + t]; a1 += w * v[1][o + t]; a2 += w * v[2][o + t]; }
-                o0[o] = a0; o1[o] = a1; o2[o] = a2;
-            }
-            *reinterpret_cast<f4v*>(&s.q[0][r][cc]) = o0; *reinterpret_cast<f4v*>(&s.q[1][r][cc]) = o1; *reinterpret_cast<f4v*>(&s.q[2][r][cc]) = o2;
+            filter_row<3>(g, v, s.q, r, cc);
         }
         __syncthreads();
         {
             float v[3][GV + 10];
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-                for (int t = 0; t < GV + 10; ++t) v[k][t] = s.q[k][r0 + t][c];
+            gather_column(&s.q[0][r0][c], v);
 #pragma unroll
             for (int o = 0; o < GV; ++o) {
-                float cm = 0.f, cu = 0.f, c12 = 0.f;
-#pragma unroll
-                for (int t = 0; t < TAPS; ++t) { const float w = g[t]; cm += w * v[0][o + t]; cu += w * v[1][o + t]; c12 += w * v[2][o + t]; }
+                float f[3];
+                filter_column(g, v, o, f);
+                const float cm = f[0], cu = f[1], c12 = f[2];
                 const float a = px[o][ch], b = py[o][ch];
                 const float d = a - b;
                 const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
@@ -354,7 +249,7 @@ __global__ __launch_bounds__(THREADS) void loss_grad_kernel(const float* __restr
 // value only (no gradient asked for): the sums by a kernel of their own
 __global__ __launch_bounds__(THREADS) void loss_finish_kernel(const float* __restrict__ partial, int n_blocks, double inv_n, float l1w, float sw,
                                                               float* __restrict__ values, double scale, float* __restrict__ total_out) {
-    __shared__ double red[2][THREADS / 64];
+    __shared__ double red[THREADS / 64][2];
     finish_sums(partial, n_blocks, inv_n, l1w, sw, values, red, scale, total_out);
 }
 

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/gsplat_mi355x.h"
+#include "gs_blocksum.h"
 #include "gs_entry.h"
 #include "gs_mcmc.h"
 
@@ -60,11 +61,9 @@ __global__ __launch_bounds__(THREADS) void noise_kernel(int64_t n, float* __rest
 }
 
 __device__ __forceinline__ double block_sum(double v, double* red) {
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double t = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
+    gsblk::sum(v, red);
+    const double t = gsblk::column<THREADS / 64>(red);                     // (every thread: the caller's branches are uniform)
+    __syncthreads();                                                       // (red is free for the next sum)
     return t;
 }
 

@@ -22,51 +22,14 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/gsplat_mi355x.h"
+#include "gs_blocksum.h"
 #include "gs_entry.h"
 #include "gs_metrics.h"
+#include "gs_ssim_tile.h"
 
 namespace {
 
 using namespace gsmet;
-
-// ---- the tile geometry, the taps and the LDS pitches of gsplat_loss.hip (its own copy: see there for the bank arithmetic)
-constexpr int TW = 32, TH = 16, R = 5, TAPS = 11;
-constexpr int W1 = TW + 2 * R, H1 = TH + 2 * R;      // region with one halo   42 x 26
-constexpr int THREADS = 256;
-constexpr int G = 4;                                 // outputs per thread along a row in the horizontal pass
-constexpr int GV = 2;                                // rows per thread in the vertical pass
-static_assert(TW % G == 0 && TH % GV == 0 && (TH / GV) * TW == THREADS, "tile shape vs register blocking");
-constexpr int XP = 44;           // pitch of the input planes (W1 = 42 columns)
-constexpr int HP = 36;           // pitch of the horizontally filtered planes (TW = 32 columns)
-static_assert(XP >= W1 && XP % 4 == 0 && HP >= TW && HP % 4 == 0, "row pitches: 16-byte rows");
-
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-// 14 consecutive floats of an LDS row from a 16-byte aligned position
-__device__ __forceinline__ void load14(const float* p, float (&a)[G + 10]) {
-    const f4v v0 = *reinterpret_cast<const f4v*>(p), v1 = *reinterpret_cast<const f4v*>(p + 4), v2 = *reinterpret_cast<const f4v*>(p + 8);
-    const f2v v3 = *reinterpret_cast<const f2v*>(p + 12);
-    a[0] = v0.x; a[1] = v0.y; a[2] = v0.z; a[3] = v0.w; a[4] = v1.x; a[5] = v1.y; a[6] = v1.z; a[7] = v1.w;
-    a[8] = v2.x; a[9] = v2.y; a[10] = v2.z; a[11] = v2.w; a[12] = v3.x; a[13] = v3.y;
-}
-static_assert(G == 4, "load14 / the 16-byte stores assume four outputs per thread");
-
-__device__ __forceinline__ void gauss_taps(float g[TAPS]) {
-    // exp(-(i - 5)^2 / (2 * 1.5^2)), normalised
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < TAPS; ++i) { const float d = (float)(i - R); g[i] = expf(-(d * d) / 4.5f); s += g[i]; }
-    const float inv = 1.0f / s;
-    // (the same eleven values in every lane: kept in SGPRs, they cost no vector register)
-#pragma unroll
-    for (int i = 0; i < TAPS; ++i) g[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g[i] * inv)));
-}
-
-struct alignas(16) StatsLds {
-    float x[3][H1][XP], y[3][H1][XP];     // the three channels of the region, de-interleaved
-    float h[5][H1][HP];                   // horizontally filtered x, y, xx, yy, (x - y)^2 of the channel being processed
-};
-static_assert(sizeof(StatsLds) <= 52 * 1024, "three workgroups per CU");
 
 // ---- the fit
 constexpr int MOM_PIX = 4;                                   // pixels per thread
@@ -95,24 +58,17 @@ __global__ __launch_bounds__(THREADS) void metrics_moments_kernel(const float* _
         }
     }
 #pragma unroll
-    for (int k = 0; k < METRICS_MOMENTS; ++k)
-        for (int sft = 32; sft > 0; sft >>= 1) s[k] += __shfl_xor(s[k], sft);
-    for (int sft = 32; sft > 0; sft >>= 1) cnt += __shfl_xor(cnt, sft);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < METRICS_MOMENTS; ++k) red[tid >> 6][k] = s[k];
-        redn[tid >> 6] = cnt;
-    }
+    for (int k = 0; k < METRICS_MOMENTS; ++k) s[k] = gsblk::ladder(s[k]);
+    cnt = gsblk::ladder(cnt);
+    gsblk::stage(s, red);
+    gsblk::stage(cnt, redn);
     __syncthreads();
     double* row = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * METRICS_ROW;
     if (tid < METRICS_MOMENTS) {
-        double v = red[0][tid];
-        for (int w = 1; w < THREADS / 64; ++w) v += red[w][tid];
-        row[tid] = v;
+        row[tid] = gsblk::column<THREADS / 64>(red, tid);
     } else if (tid == METRICS_MOMENTS) {
-        long long v = redn[0];
-        for (int w = 1; w < THREADS / 64; ++w) v += redn[w];
-        row[METRICS_MOMENTS] = __longlong_as_double(v);                     // (the count travels as the 64 bits it is)
+        const long long n = gsblk::column<THREADS / 64>(redn);             // (four waves' counts added in 32 bits: at most 1024)
+        row[METRICS_MOMENTS] = __longlong_as_double(n);                     // (the count travels as the 64 bits it is)
     }
 }
 
@@ -133,24 +89,15 @@ __global__ __launch_bounds__(THREADS) void metrics_solve_kernel(const double* __
         cnt += __double_as_longlong(row[METRICS_MOMENTS]);
     }
 #pragma unroll
-    for (int k = 0; k < METRICS_MOMENTS; ++k)
-        for (int sft = 32; sft > 0; sft >>= 1) s[k] += __shfl_xor(s[k], sft);
-    for (int sft = 32; sft > 0; sft >>= 1) cnt += __shfl_xor(cnt, sft);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < METRICS_MOMENTS; ++k) red[tid >> 6][k] = s[k];
-        redn[tid >> 6] = cnt;
-    }
+    for (int k = 0; k < METRICS_MOMENTS; ++k) s[k] = gsblk::ladder(s[k]);
+    cnt = gsblk::ladder(cnt);
+    gsblk::stage(s, red);
+    gsblk::stage(cnt, redn);
     __syncthreads();
     if (tid == 0) {
 #pragma unroll
-        for (int k = 0; k < METRICS_MOMENTS; ++k) {
-            s[k] = red[0][k];
-#pragma unroll
-            for (int w = 1; w < THREADS / 64; ++w) s[k] += red[w][k];
-        }
-        cnt = redn[0];
-        for (int w = 1; w < THREADS / 64; ++w) cnt += redn[w];
+        for (int k = 0; k < METRICS_MOMENTS; ++k) s[k] = gsblk::column<THREADS / 64>(red, k);
+        cnt = gsblk::column<THREADS / 64>(redn);
         float E[12];
         solve_affine(s, (int64_t)cnt, E);
 #pragma unroll
@@ -167,7 +114,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(3, 3)))
                                                                 const uint8_t* __restrict__ mask, const float* __restrict__ affine, int H, int W,
                                                                 double* __restrict__ partial) {
     __shared__ StatsLds s;
-    __shared__ double red[3][THREADS / 64];
+    __shared__ double red[THREADS / 64][3];
     __shared__ int redn[THREADS / 64];
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
@@ -180,39 +127,27 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(3, 3)))
 #pragma unroll
         for (int k = 0; k < 12; ++k) E[k] = affine[(int64_t)blockIdx.z * 12 + k];          // (wave-uniform: scalar loads)
     }
-    {   // the region of all three channels at once, every load of the workgroup in flight together (see loss_stats_kernel); pixel
-        // e = tid + 256 k of the region as (row, column): stepped, not divided -- 256 = 6 * 42 + 4
-        constexpr int N = H1 * W1, SLOTS = (N + THREADS - 1) / THREADS;
-        static_assert(THREADS == 6 * W1 + 4, "the stepping below");
-        float ra[SLOTS][3], rb[SLOTS][3];
-        bool inside[SLOTS];
-        const int r_first = tid / W1, c_first = tid - r_first * W1;
-        {
-            int r = r_first, c = c_first;
+    {   // the region of all three channels at once, loaded in one walk and stored in a second (RegionWalk, as loss_stats_kernel)
+        float ra[REGION_SLOTS][3], rb[REGION_SLOTS][3];
+        bool inside[REGION_SLOTS];
+        RegionWalk p(tid);
 #pragma unroll
-            for (int k = 0; k < SLOTS; ++k) {
-                const int gy = y0 - R + r, gx = x0 - R + c;
-                const bool in = r < H1 && gy >= 0 && gy < H && gx >= 0 && gx < W;      // zero outside the image = the zero padding
-                const int64_t o = img + ((int64_t)gy * W + gx) * 3;
-                inside[k] = in;
+        for (int k = 0; k < REGION_SLOTS; ++k, p.next()) {
+            const int gy = y0 - R + p.r, gx = x0 - R + p.c;
+            const bool in = p.r < H1 && gy >= 0 && gy < H && gx >= 0 && gx < W;    // zero outside the image = the zero padding
+            const int64_t o = img + ((int64_t)gy * W + gx) * 3;
+            inside[k] = in;
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) { ra[k][ch] = in ? pred[o + ch] : 0.f; rb[k][ch] = in ? target[o + ch] : 0.f; }
-                r += 6; c += 4;
-                if (c >= W1) { c -= W1; ++r; }
-            }
+            for (int ch = 0; ch < 3; ++ch) { ra[k][ch] = in ? pred[o + ch] : 0.f; rb[k][ch] = in ? target[o + ch] : 0.f; }
         }
-        {
-            int r = r_first, c = c_first;
+        RegionWalk q(tid);
 #pragma unroll
-            for (int k = 0; k < SLOTS; ++k) {
-                if (r < H1) {
-                    float v[3] = {ra[k][0], ra[k][1], ra[k][2]};
-                    if (CC && inside[k]) correct_pixel(E, ra[k], v);                   // (outside the image x stays 0: the padding is of the corrected image)
+        for (int k = 0; k < REGION_SLOTS; ++k, q.next()) {
+            if (q.r < H1) {
+                float v[3] = {ra[k][0], ra[k][1], ra[k][2]};
+                if (CC && inside[k]) correct_pixel(E, ra[k], v);                       // (outside the image x stays 0: the padding is of the corrected image)
 #pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) { s.x[ch][r][c] = v[ch]; s.y[ch][r][c] = rb[k][ch]; }
-                }
-                r += 6; c += 4;
-                if (c >= W1) { c -= W1; ++r; }
+                for (int ch = 0; ch < 3; ++ch) { s.x[ch][q.r][q.c] = v[ch]; s.y[ch][q.r][q.c] = rb[k][ch]; }
             }
         }
     }
@@ -230,49 +165,29 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(3, 3)))
     // (the three sums in double from the first term on: x - y and its square are then exact, and a metric of two fp32 images carries
     //  no more error than its own rounding to fp32 -- 18 double additions per thread beside 2 x 230 FMAs per value)
     double l1_acc = 0.0, sq_acc = 0.0, ssim_acc = 0.0;
+#pragma unroll 1                                                           // (one copy: three do not fit in 168 VGPRs without scratch)
     for (int ch = 0; ch < 3; ++ch) {
         __syncthreads();                                                   // the region is staged / the previous channel's h is read
-        // horizontal pass of the five products: G outputs per thread from G + 10 inputs (the products formed once per input)
+        // horizontal pass of the five products: G outputs per thread from G + 10 inputs
         for (int i = tid; i < H1 * (TW / G); i += THREADS) {
-            const int r = i % H1, cc = (i / H1) * G;                       // rows fastest across lanes
-            float a[G + 10], b[G + 10], aa[G + 10], bb[G + 10], dd[G + 10];
-            load14(&s.x[ch][r][cc], a);
-            load14(&s.y[ch][r][cc], b);
-#pragma unroll
-            for (int t = 0; t < G + 10; ++t) { const float d = a[t] - b[t]; aa[t] = a[t] * a[t]; bb[t] = b[t] * b[t]; dd[t] = d * d; }
-            f4v o0, o1, o2, o3, o4;
-#pragma unroll
-            for (int o = 0; o < G; ++o) {
-                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
-#pragma unroll
-                for (int t = 0; t < TAPS; ++t) {
-                    const float w = g[t];
-                    a0 += w * a[o + t]; a1 += w * b[o + t]; a2 += w * aa[o + t]; a3 += w * bb[o + t]; a4 += w * dd[o + t];
-                }
-                o0[o] = a0; o1[o] = a1; o2[o] = a2; o3[o] = a3; o4[o] = a4;
-            }
-            *reinterpret_cast<f4v*>(&s.h[0][r][cc]) = o0; *reinterpret_cast<f4v*>(&s.h[1][r][cc]) = o1; *reinterpret_cast<f4v*>(&s.h[2][r][cc]) = o2;
-            *reinterpret_cast<f4v*>(&s.h[3][r][cc]) = o3; *reinterpret_cast<f4v*>(&s.h[4][r][cc]) = o4;
+            const int r = i % H1, cc = (i / H1) * G;
+            float v[5][G + 10];
+            load14(&s.x[ch][r][cc], v[0]);
+            load14(&s.y[ch][r][cc], v[1]);
+            stats_planes(v);
+            filter_row<5>(g, v, s.h, r, cc);
         }
         __syncthreads();
         // vertical pass -> the SSIM value on the tile: GV rows per thread; the L1 and squared-error terms ride along
         {
             float v[5][GV + 10];
-#pragma unroll
-            for (int k = 0; k < 5; ++k)
-#pragma unroll
-                for (int t = 0; t < GV + 10; ++t) v[k][t] = s.h[k][r0 + t][c];
+            gather_column(&s.h[0][r0][c], v);
 #pragma unroll
             for (int o = 0; o < GV; ++o) {
                 if (valid[o]) {
-                    float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, edd = 0.f;
-#pragma unroll
-                    for (int t = 0; t < TAPS; ++t) {
-                        const float w = g[t];
-                        mu1 += w * v[0][o + t]; mu2 += w * v[1][o + t]; e11 += w * v[2][o + t]; e22 += w * v[3][o + t];
-                        edd += w * v[4][o + t];
-                    }
-                    ssim_acc += (double)ssim_value(mu1, mu2, e11, e22, edd);
+                    float f[5];                                            // mu1, mu2, e11, e22, edd
+                    filter_column(g, v, o, f);
+                    ssim_acc += (double)ssim_value(f[0], f[1], f[2], f[3], f[4]);
                     const double d = (double)s.x[ch][r0 + o + R][c + R] - (double)s.y[ch][r0 + o + R][c + R];
                     l1_acc += fabs(d);
                     sq_acc += d * d;
@@ -281,25 +196,25 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(3, 3)))
         }
     }
     // the tile's four sums (fixed order inside the workgroup)
-    for (int sft = 32; sft > 0; sft >>= 1) {
-        l1_acc += __shfl_xor(l1_acc, sft); sq_acc += __shfl_xor(sq_acc, sft); ssim_acc += __shfl_xor(ssim_acc, sft);
-        cnt += __shfl_xor(cnt, sft);
-    }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = l1_acc; red[1][tid >> 6] = sq_acc; red[2][tid >> 6] = ssim_acc; redn[tid >> 6] = cnt; }
+    // (none of the three can be -0.0: |d| and d d are not negative, and S joins its sum by a plain addition that started at +0.0)
+    const double acc[3] = {gsblk::ladder(l1_acc), gsblk::ladder(sq_acc), gsblk::ladder(ssim_acc)};
+    cnt = gsblk::ladder(cnt);
+    gsblk::stage(acc, red);
+    gsblk::stage(cnt, redn);
     __syncthreads();
     if (tid == 0) {
-        double a = 0.0, b = 0.0, e = 0.0;
-        long long n = 0;
-        for (int k = 0; k < THREADS / 64; ++k) { a += red[0][k]; b += red[1][k]; e += red[2][k]; n += redn[k]; }
         const int64_t blk = blockIdx.x + (int64_t)gridDim.x * (blockIdx.y + (int64_t)gridDim.y * blockIdx.z);
         double* row = partial + blk * METRICS_STATS_ROW;
-        row[0] = a; row[1] = b; row[2] = e; row[3] = __longlong_as_double(n);                 // (the count travels as the 64 bits it is)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) row[k] = gsblk::column<THREADS / 64>(red, k);
+        const long long n = gsblk::column<THREADS / 64>(redn);             // (four waves' counts added in 32 bits: at most 512)
+        row[3] = __longlong_as_double(n);                                   // (the count travels as the 64 bits it is)
     }
 }
 
 // One workgroup per image: its n_tiles rows in a fixed order, in double -> out[image][4] = psnr, ssim, l1, mse
 __global__ __launch_bounds__(THREADS) void metrics_finish_kernel(const double* __restrict__ partial, int n_tiles, float* __restrict__ out) {
-    __shared__ double red[3][THREADS / 64];
+    __shared__ double red[THREADS / 64][3];
     __shared__ long long redn[THREADS / 64];
     const int tid = threadIdx.x;
     const double* rows = partial + (int64_t)blockIdx.x * n_tiles * METRICS_STATS_ROW;
@@ -310,14 +225,15 @@ __global__ __launch_bounds__(THREADS) void metrics_finish_kernel(const double* _
         a += row[0]; b += row[1]; e += row[2];
         cnt += __double_as_longlong(row[3]);
     }
-    for (int sft = 32; sft > 0; sft >>= 1) {
-        a += __shfl_xor(a, sft); b += __shfl_xor(b, sft); e += __shfl_xor(e, sft); cnt += __shfl_xor(cnt, sft);
-    }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = a; red[1][tid >> 6] = b; red[2][tid >> 6] = e; redn[tid >> 6] = cnt; }
+    // (plain additions from +0.0 on: none of the three can be -0.0)
+    const double abe[3] = {gsblk::ladder(a), gsblk::ladder(b), gsblk::ladder(e)};
+    cnt = gsblk::ladder(cnt);
+    gsblk::stage(abe, red);
+    gsblk::stage(cnt, redn);
     __syncthreads();
     if (tid == 0) {
-        a = 0.0; b = 0.0; e = 0.0; cnt = 0;
-        for (int k = 0; k < THREADS / 64; ++k) { a += red[0][k]; b += red[1][k]; e += red[2][k]; cnt += redn[k]; }
+        a = gsblk::column<THREADS / 64>(red, 0); b = gsblk::column<THREADS / 64>(red, 1); e = gsblk::column<THREADS / 64>(red, 2);
+        cnt = gsblk::column<THREADS / 64>(redn);
         float v[4];
         finish_values(a, b, e, (int64_t)cnt, v);
 #pragma unroll

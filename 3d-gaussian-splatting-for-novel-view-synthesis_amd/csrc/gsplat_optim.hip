@@ -17,6 +17,7 @@
 
 #include "../../include/gsplat_mi355x.h"
 #include "gs_adam.h"
+#include "gs_blocksum.h"
 #include "gs_entry.h"
 
 namespace {
@@ -27,17 +28,15 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(int64_t n, const float* __r
     __shared__ float red[4];
     float acc = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) { const float v = g[i]; acc += v * v; }
-    for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    gsblk::sum(acc, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = gsblk::column<4>(red);
 }
 
 // one wave: sum of the partial sums in a fixed order (double) -> (coef, norm)
 __global__ __launch_bounds__(64) void clip_coef_kernel(const float* __restrict__ part, int n_part, float max_norm, float* __restrict__ out /* coef, norm */) {
     double s = 0.0;
     for (int k = threadIdx.x; k < n_part; k += 64) s += (double)part[k];
-    for (int sft = 32; sft > 0; sft >>= 1) s += __shfl_xor(s, sft);
+    s = gsblk::ladder(s);                                                  // (one wave: the ladder is the whole sum)
     if (threadIdx.x == 0) {
         const float norm = (float)sqrt(s);
         const float coef = max_norm / (norm + 1e-6f);
