@@ -35,6 +35,7 @@ GSPLAT_FILTER3D_CAMERA_CHUNK = 64
 GSPLAT_EXPOSURE_ACCUMULATE = 1
 GSPLAT_BILAGRID_ACCUMULATE = 1
 GSPLAT_METRICS_COLOUR_CORRECT = 1
+GSPLAT_KNN_BOX = 256
 
 
 def sh_bands_dropped(degree):
@@ -224,6 +225,8 @@ SIGNATURES = {
     "gsplat_metrics_scratch_bytes": (_I64, [C.c_int32] * 4),
     "gsplat_metrics_fit_affine": (_INT, [_VP, _VP, _VP] + [C.c_int32] * 3 + [_VP, _VP, _VP]),
     "gsplat_metrics_forward": (_INT, [_VP, _VP, _VP] + [C.c_int32] * 4 + [_VP, _VP, _VP, _VP]),
+    "gsplat_knn_scratch_bytes": (_I64, [_I64]),
+    "gsplat_knn_mean_dist2": (_INT, [_I64, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None

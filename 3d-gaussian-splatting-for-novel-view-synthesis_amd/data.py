@@ -2,7 +2,7 @@
 
 Layout (gaussian_splatting/data_loader.py:153-284; written by datasets/prepare_mipnerf360.py:410-431):
     <data_dir>/images/*.{jpg,png,JPG,PNG}   cam_meta.npy (a pickled dict: fx, fy[, cx, cy][, c2w])   poses.npy [K,4,4]
-    pointcloud.ply (ASCII, x y z first)
+    pointcloud.ply (ASCII, x y z first; a binary little-endian file, with its colours, is read as well)
 Functions mirror the reference's names and return values: load_image (:15), load_camera_parameters (:27),
 load_point_cloud (:50), GaussianDataset (:153), initialize_gaussians_from_pointcloud (:287).  `write_dataset` produces
 the same layout (so a scene can be prepared without the reference's download / COLMAP tooling).  Host-side I/O only.
@@ -65,46 +65,111 @@ def load_camera_parameters(cam_meta_path):
     return obj.item() if isinstance(obj, np.ndarray) and obj.shape == () else obj
 
 
-def _filter_points(pts):
+def _filter_points(pts, extra=None):
     """The sanitising of data_loader.py:106-148: drop NaN/Inf, keep |coord| < 1000 if any such point exists, otherwise
-    fall back to the 99th-percentile / 100 x median distance filters; an empty result raises ValueError."""
-    pts = pts[torch.isfinite(pts).all(dim=1)]
+    fall back to the 99th-percentile / 100 x median distance filters; an empty result raises ValueError.  `extra` (not in the
+    reference): further columns of the same rows (colours), which play no part in the tests; the kept rows come back as [K, 3 + E]."""
+    rows = torch.arange(len(pts))
+
+    def keep(mask):
+        return pts[mask], rows[mask]
+
+    pts, rows = keep(torch.isfinite(pts).all(dim=1))
     if len(pts) > 0:
         near = (pts.abs() < 1000).all(dim=1)
         if near.sum() > 0:
-            pts = pts[near]
+            pts, rows = keep(near)
         else:
             dist = (pts - pts.mean(dim=0)).norm(dim=1)
             if len(dist) > 100:
-                keep = dist < torch.quantile(dist, 0.99)
-                if keep.sum() > 0:
-                    pts = pts[keep]
+                ok = dist < torch.quantile(dist, 0.99)
+                if ok.sum() > 0:
+                    pts, rows = keep(ok)
                 else:
                     med = dist.median()
                     if torch.isfinite(med) and med > 0 and (dist < med * 100).sum() > 0:
-                        pts = pts[dist < med * 100]
+                        pts, rows = keep(dist < med * 100)
     if len(pts) == 0:
         raise ValueError("Point cloud is empty after filtering invalid values!")
-    return pts
+    return pts if extra is None else torch.cat([pts, extra[rows]], dim=1)
+
+
+# PLY scalar types -> little-endian numpy types
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': '<i2', 'int16': '<i2', 'ushort': '<u2', 'uint16': '<u2',
+              'int': '<i4', 'int32': '<i4', 'uint': '<u4', 'uint32': '<u4', 'float': '<f4', 'float32': '<f4', 'double': '<f8',
+              'float64': '<f8'}
+
+
+def _ply_header(f, ply_path):
+    """(format, vertex count, [(name, numpy type)] of `element vertex`) of the PLY open (binary) at its start; the file is left at
+    the first byte after end_header.  ValueError for anything _load_ply cannot read."""
+    fmt, n, props, element, ended = 'ascii', 0, [], None, False
+    for k, raw in enumerate(iter(f.readline, b'')):
+        line = raw.decode('ascii', errors='replace')
+        tok = line.split()
+        if k == 0 and tok[:1] != ['ply']:
+            raise ValueError(f"{ply_path}: not a PLY file")
+        if line.startswith('end_header'):
+            ended = True
+            break
+        if not tok:
+            continue
+        if tok[0] == 'format':
+            fmt = tok[1] if len(tok) > 1 else ''
+            if fmt not in ('ascii', 'binary_little_endian') or (fmt != 'ascii' and tok[2:3] != ['1.0']):
+                raise ValueError(f"{ply_path}: format {' '.join(tok[1:])!r} is not supported (ascii or binary_little_endian 1.0)")
+        elif tok[0] == 'element':
+            element = tok[1] if len(tok) > 1 else None
+            if line.startswith('element vertex'):
+                n = int(tok[-1])
+        elif tok[0] == 'property' and element == 'vertex':
+            if len(tok) > 1 and tok[1] == 'list':
+                raise ValueError(f"{ply_path}: a list property on the vertex element is not supported")
+            if len(tok) != 3 or tok[1] not in _PLY_TYPES:
+                raise ValueError(f"{ply_path}: vertex property {' '.join(tok[1:])!r} has an unsupported type")
+            props.append((tok[2], _PLY_TYPES[tok[1]]))
+    if not ended:
+        raise ValueError(f"{ply_path}: no end_header")
+    return fmt, n, props
 
 
 def _load_ply(ply_path):
-    """ASCII PLY, first three numbers of each vertex line (data_loader.py:78-104)."""
-    pts, n, header = [], 0, True
-    with open(ply_path, 'r') as f:
-        for line in f:
-            if header:
-                if line.startswith('element vertex'):
-                    n = int(line.split()[-1])
-                elif line.startswith('end_header'):
-                    header = False
-            elif len(pts) < n:
+    """A PLY's vertices, sanitised by _filter_points on x y z (data_loader.py:78-104 for ASCII; the header is read properly: `format
+    ascii` or `binary_little_endian 1.0`, the property list of `element vertex` with the scalar types float / double / uchar and the
+    int types; anything else, binary_big_endian or a list property on the vertex element: ValueError; other elements after the
+    vertices are ignored).
+      * ASCII: [N, 3], the first three numbers of each vertex line, exactly as the reference reads it -- the colour columns of an
+        ASCII file are dropped, as they always were.
+      * binary_little_endian (what COLMAP and the INRIA tools write): x y z by name, and when red, green and blue exist the result is
+        [N, 6] with the colours in the file's own range (initialize_gaussians_from_pointcloud divides by 255 when the maximum
+        exceeds 1), filtered with their rows."""
+    with open(ply_path, 'rb') as f:
+        fmt, n, props = _ply_header(f, ply_path)
+        body = f.read()
+    if fmt == 'ascii':
+        pts = []
+        lines = body.decode('utf-8', errors='replace').replace('\r\n', '\n').replace('\r', '\n').split('\n')
+        for line in lines[:-1] if lines[-1] == '' else lines:       # (the lines a text-mode file object yields)
+            if len(pts) < n:
                 pts.append([float(v) for v in line.split()[:3]])
-    return _filter_points(torch.tensor(pts, dtype=torch.float32).reshape(-1, 3))
+        return _filter_points(torch.tensor(pts, dtype=torch.float32).reshape(-1, 3))
+    names = [name for name, _ in props]
+    if len(set(names)) != len(names) or not all(k in names for k in 'xyz'):
+        raise ValueError(f"{ply_path}: the vertex element needs one x, y and z property each (it has {names})")
+    dtype = np.dtype(props)
+    if len(body) < n * dtype.itemsize:
+        raise ValueError(f"{ply_path}: {n} vertices of {dtype.itemsize} bytes announced, {len(body)} bytes present")
+    v = np.frombuffer(body, dtype=dtype, count=n)
+
+    def cols(keys):
+        return torch.from_numpy(np.stack([v[k].astype(np.float32) for k in keys], axis=1)).reshape(-1, len(keys))
+
+    has_rgb = all(k in names for k in ('red', 'green', 'blue'))
+    return _filter_points(cols('xyz'), cols(('red', 'green', 'blue')) if has_rgb else None)
 
 
 def load_point_cloud(pcd_path):
-    """.ply (ASCII) / .npy / .pt -> [N, 3+] float tensor (data_loader.py:50-76)."""
+    """.ply (ASCII or binary little-endian: _load_ply) / .npy / .pt -> [N, 3+] float tensor (data_loader.py:50-76)."""
     ext = Path(pcd_path).suffix.lower()
     if ext == '.pt':
         return torch.load(pcd_path, weights_only=True)
@@ -185,15 +250,32 @@ def split_views(n, hold=8):
     return [i for i in range(n) if i % hold], [i for i in range(n) if i % hold == 0]
 
 
-def initialize_gaussians_from_pointcloud(points, num_sh_bands=3):
+def initialize_gaussians_from_pointcloud(points, num_sh_bands=3, *, scale_init="reference", init_scale=1.0, device=None):
     """One Gaussian per point: log-scale -2 +- 0.1, identity quaternion (0,0,0,1), opacity_raw 0.1, colours from columns
     3-5 (divided by 255 if > 1) or uniform random, zero higher-order SH (data_loader.py:287-367).  Only num_sh_bands >= 3
-    gives the [N, 45] f_rest that evaluate_sh / the HIP path accept (as in the reference)."""
+    gives the [N, 45] f_rest that evaluate_sh / the HIP path accept (as in the reference).
+
+    Not in the reference (keyword-only; the default is the reference's rule, draw for draw): scale_init="knn" starts every Gaussian
+    as the isotropic blob of the paper, scale_raw = log(init_scale sqrt(max(d2, 1e-7))) in all three columns with d2 the mean squared
+    distance to the three nearest neighbours (knn.init_scale_raw; a HIP search, so the points must be on a GPU); every other field is
+    as with "reference" under the same seed.  device: where the points are moved first and everything is returned (None: the points'
+    own device; "knn" with CPU points and no device= is a RuntimeError)."""
+    if scale_init not in ("reference", "knn"):
+        raise ValueError(f"scale_init must be 'reference' or 'knn', not {scale_init!r}")
+    if isinstance(init_scale, bool) or not isinstance(init_scale, (int, float)) or not 0.0 < init_scale < float("inf"):
+        raise ValueError(f"init_scale must be a finite number > 0, not {init_scale!r}")
     if not isinstance(points, torch.Tensor):
         points = torch.from_numpy(np.asarray(points)).float()
+    if device is not None:
+        points = points.to(device)
+    if scale_init == "knn" and not points.is_cuda:
+        raise RuntimeError("scale_init='knn' runs on the GPU and there is no CPU fallback: pass device= (the points are on the CPU)")
     n, dev = points.shape[0], points.device
     pos = points[:, :3]
     scale_raw = torch.randn(n, 3, device=dev) * 0.1 - 2.0
+    if scale_init == "knn":                                  # (after the draw: the colours below come out as with "reference")
+        from . import knn
+        scale_raw = knn.init_scale_raw(pos.to(torch.float32).contiguous(), float(init_scale))
     q_raw = torch.zeros(n, 4, device=dev)
     q_raw[:, 3] = 1.0
     opacity_raw = torch.ones(n, device=dev) * 0.1

@@ -697,6 +697,24 @@ int gsplat_metrics_fit_affine(const float* pred, const float* target, const uint
 int gsplat_metrics_forward(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t H, int32_t W, int32_t flags,
                            float* affine, float* out, void* scratch, void* stream);
 
+/* ---- scale initialisation: exact 3-nearest-neighbour mean squared distance (not in the reference) --------------------
+ * dist2[i] = the mean of the m = min(3, F - 1) smallest d2(i, j) over the FINITE rows j != i of points [n, 3] (F = their number):
+ * what the paper, simple_knn's distCUDA2 and gsplat's knn(points, 4) start the scales from.
+ *   d2 = fmaf(dz, dz, fmaf(dy, dy, dx dx)) of the three fp32 differences (csrc/gs_knn.h: one function for the device and the host
+ *   test build); the m values are summed in ascending order and scaled by a float constant (1, 1/2, 1/3): no division.
+ *   j != i is by index: a duplicate of a point is its neighbour at distance 0.  A row with a NaN or an infinity is nobody's
+ *   neighbour and gets 0; F <= 1 gives 0 everywhere.
+ * The search is exact: the result depends on the multiset of the other points only -- the same bits every call, on any stream, and
+ * under any permutation of the rows.  Points are sorted by a 63-bit Morton key (a stable radix sort written here), cut into boxes of
+ * GSPLAT_KNN_BOX sorted points with the AABB of their actual points, and a wave skips a box only when the box is strictly farther than
+ * the third-best of every one of its lanes.  O(n * n / GSPLAT_KNN_BOX) box tests.
+ * scratch: gsplat_knn_scratch_bytes(n) device bytes (about 40 n; -1 for n outside [0, 2^31)), 256-byte aligned, any contents; one
+ * call at a time per scratch buffer.  points and dist2 4-byte aligned.  n == 0 launches nothing.  No float atomic; nothing is read
+ * back to the host.                                                                                                               */
+#define GSPLAT_KNN_BOX 256
+int64_t gsplat_knn_scratch_bytes(int64_t n);
+int gsplat_knn_mean_dist2(int64_t n, const float* points, float* dist2, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
