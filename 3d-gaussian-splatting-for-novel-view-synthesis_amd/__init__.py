@@ -26,6 +26,7 @@ from . import mcmc  # noqa: E402,F401  (density control at a fixed budget: MCMC 
 from . import filter3d  # noqa: E402,F401  (the 3D smoothing filter of Mip-Splatting: per-Gaussian sampling limit from the cameras)
 from . import exposure  # noqa: E402,F401  (per-view exposure compensation: an affine colour transform per training image)
 from . import bilagrid  # noqa: E402,F401  (per-view bilateral grids: a sliced grid of affine colour transforms per training image)
+from . import poses  # noqa: E402,F401  (per-view camera-pose corrections: a learned rigid correction per training camera)
 from . import metrics  # noqa: E402,F401  (held-out views: per-image PSNR / SSIM / L1, colour-corrected on request)
 from . import knn  # noqa: E402,F401  (scale initialisation from the 3 nearest neighbours: exact k-NN over a Morton sort)
 from . import model  # noqa: E402,F401  (GaussianModel: densify / prune / opacity reset)

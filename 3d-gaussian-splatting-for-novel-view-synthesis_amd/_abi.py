@@ -36,6 +36,7 @@ GSPLAT_EXPOSURE_ACCUMULATE = 1
 GSPLAT_BILAGRID_ACCUMULATE = 1
 GSPLAT_METRICS_COLOUR_CORRECT = 1
 GSPLAT_KNN_BOX = 256
+GSPLAT_POSE_DELTA_ACCUMULATE = 1
 
 
 def sh_bands_dropped(degree):
@@ -227,6 +228,9 @@ SIGNATURES = {
     "gsplat_metrics_forward": (_INT, [_VP, _VP, _VP] + [C.c_int32] * 4 + [_VP, _VP, _VP, _VP]),
     "gsplat_knn_scratch_bytes": (_I64, [_I64]),
     "gsplat_knn_mean_dist2": (_INT, [_I64, _VP, _VP, _VP, _VP]),
+    "gsplat_pose_delta_forward": (_INT, [_VP, _VP, _I64, _VP, _VP]),
+    "gsplat_pose_delta_backward": (_INT, [_VP, _VP, _VP, _I64, _VP, _VP, _VP, C.c_int32, _VP]),
+    "gsplat_pose_delta_decay": (_INT, [_VP, _I64, C.c_float, _VP, _VP]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
-"""What the per-view colour tables share (exposure.ExposureTable, bilagrid.BilateralGridTable): one autograd
-skeleton for an op `out = f(image, table row)` over a pair of library entries, and one table of such rows with its gradient buffer and
-its own Adam.  An op plugs its three parts into the skeleton as a ViewOp; a table names its op, its identity and its Adam defaults.
+"""What the per-view tables share (exposure.ExposureTable, bilagrid.BilateralGridTable, poses.PoseTable): one
+autograd skeleton for an op `out = f(image, table row)` over a pair of library entries (for the pose table the "image" is the camera
+pose), and one table of such rows with its gradient buffer and its own Adam.  An op plugs its three parts into the skeleton as a
+ViewOp; a table names its op, its identity and its Adam defaults.
 Nothing here reads the device, and there is no CPU fallback."""
 import collections
 import numbers
@@ -13,8 +14,9 @@ from .ops import _f32, _stream_ptr
 # The parts of an op.  `arg`: what its second argument is called in messages.  shapes(image, table) -> (the image's shape, the integers
 # both entries take after the arrays); ValueError for a pair that does not fit.  forward(x, t, dims, out, stream) and
 # backward(x, t, g, dims, g_image, target, rows, flags, stream) make the library calls (target None: the table's gradient is not wanted;
-# whatever scratch the call needs is allocated there).  `accumulate`: the entry's flag for "ADD into the rows `rows` names".
-ViewOp = collections.namedtuple("ViewOp", "arg shapes forward backward accumulate")
+# whatever scratch the call needs is allocated there).  `accumulate`: the entry's flag for "ADD into the rows `rows` names".  `first`:
+# what the first argument is called in messages.
+ViewOp = collections.namedtuple("ViewOp", "arg shapes forward backward accumulate first", defaults=("image",))
 
 
 class ViewFn(torch.autograd.Function):
@@ -26,11 +28,11 @@ class ViewFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, op, image, table, dest, anchor):
         if not isinstance(image, torch.Tensor) or not isinstance(table, torch.Tensor):
-            raise TypeError(f"image and {op.arg} must be torch.Tensors")
+            raise TypeError(f"{op.first} and {op.arg} must be torch.Tensors")
         shape, dims = op.shapes(image, table)
-        x, t = _f32(image, shape, "image"), _f32(table, tuple(table.shape), op.arg)
+        x, t = _f32(image, shape, op.first), _f32(table, tuple(table.shape), op.arg)
         if t.device != x.device:
-            raise ValueError(f"image is on {x.device}, {op.arg} on {t.device}")
+            raise ValueError(f"{op.first} is on {x.device}, {op.arg} on {t.device}")
         dev = x.device
         with torch.cuda.device(dev):
             out = torch.empty(shape, dtype=torch.float32, device=dev)
@@ -73,7 +75,7 @@ class ViewTable:
     of its own -- a second optim.GaussianAdam over the one tensor (a dense step), apart from the model's optimiser: restarts of that one
     after a densification touch neither the table nor its moments.
 
-    A subclass has `name` ('exposure', 'bilagrid': its optimiser group, and the prefix of its TrainConfig fields), `op` (the ViewOp
+    A subclass has `name` ('exposure', 'bilagrid', 'pose': its optimiser group, and the prefix of its TrainConfig fields), `op` (the ViewOp
     apply_view calls) and _identity(device) (one row at the identity); it may override regularise()."""
 
     def __init__(self, n_views, device, lr, betas, eps):

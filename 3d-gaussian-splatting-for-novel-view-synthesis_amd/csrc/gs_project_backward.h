@@ -19,7 +19,7 @@ namespace {
 // place (adam_rows) -- the 192 of the 236 gradient bytes per Gaussian neither leave this kernel nor come back into the optimiser's.
 // ACC (fused inputs, saved Jacobian, not factored): every gradient is ADDED to what `out` holds -- the gradients of the views of one
 // iteration summed by the kernel that forms them, instead of a pass of the host's autograd per view (read two, write one).
-// POSE (not factored): also the camera-pose gradient.  Every lane forms its Gaussian's 12 terms -- dL/dW (gs_math.h pose_grad_w)
+// POSE (plain or factored): also the camera-pose gradient.  Every lane forms its Gaussian's 12 terms -- dL/dW (gs_math.h pose_grad_w)
 // and dL/dp -- the wave adds them up in a fixed order (wave_sum_f) and stores ONE 64-byte row per block into pose_rows[blockIdx.x]
 // (every block writes its row: nothing to clear); pose_reduce_kernel adds the rows.  out.pos == NULL: no gradient row is stored
 // (pose only).

@@ -203,8 +203,9 @@ int project_backward_impl(const char* entry, const gsplat_gaussians* g, const fl
     } else if (g->n == 0) {
         return GSPLAT_OK;
     }
-    // fused inputs, f_dc and f_rest NULL, color given: hand out the colour-logit gradients instead of the SH gradients
-    const bool factored = !pose && fused && !out->f_dc && !out->f_rest;
+    // fused inputs, f_dc and f_rest NULL, color given: hand out the colour-logit gradients instead of the SH gradients (a pose call
+    // too: the kernel's `factored` branches do not depend on POSE; a pose call without `out` writes no gradient rows at all)
+    const bool factored = out && fused && !out->f_dc && !out->f_rest;
     const bool jac = fused && (flags & GSPLAT_BACKWARD_SH_JACOBIAN) != 0;
     const bool acc = (flags & GSPLAT_BACKWARD_ACCUMULATE) != 0;
     const bool depth = (flags & GSPLAT_BACKWARD_DEPTH) != 0;

@@ -422,10 +422,12 @@ def _forward_begin(spec, c2w, tensors, pose=False, need_grad=False):
     inside a deferred_checks() block once a pair capacity is known for this image size -- the whole forward pass was queued by ONE
     library call (gsplat_forward_deferred) and the result is there.  The result is always (image, depth, alpha), the maps None where
     the frame has none (_deliver turns it into what the caller gets).  pose (from _RenderFn): the backward pass will also form
-    dL/dc2w -- a pose frame: always the separate library calls, never a gradient route.  spec.is_aux: an aux frame -- depth and
+    dL/dc2w -- a pose frame: always the separate library calls, and no gradient route but the factored exchange.  spec.is_aux: an aux frame -- depth and
     opacity maps, or an image over a background -- which takes the separate library calls like a pose frame."""
     route = _route.get()
-    if pose and route is not None:
+    # (the factored exchange takes a pose frame as it takes an aux frame, below: the separate calls, gsplat_logit_grad -> route.add,
+    #  then gsplat_project_backward_pose with the SH-less destination -- the kernel's factored branches do not depend on the pose)
+    if pose and route is not None and route.route_kind != FACTORED:
         raise RuntimeError("a camera-pose gradient (c2w.requires_grad) is not available inside a gradient_route() block "
                            "(factored exchange, folded f_rest step, accumulate_grads): render the pose frame outside it")
     auxf = spec.is_aux
@@ -1243,7 +1245,7 @@ def render(pos, color, opacity_raw, sigma, c2w, H, W, fx, fy, cx, cy, near=0.01,
 
     Returns the image [H, W, 3] in [0, 1], same dtype/device as `pos`, differentiable w.r.t. pos, color, opacity_raw,
     sigma and the camera pose c2w (c2w.requires_grad: dL/dc2w [4, 4] in c2w's dtype, last row 0; such a frame always takes
-    the separate library calls and may not be rendered inside a gradient_route() block).  No opacity / frustum / finite
+    the separate library calls and may not be rendered inside a gradient_route() block other than a factored exchange).  No opacity / frustum / finite
     survivor -> zero image with zero gradients; survivors but none on screen -> Exception("All projected points are
     off-screen"), as in the reference.
 

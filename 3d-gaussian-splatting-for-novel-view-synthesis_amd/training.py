@@ -40,7 +40,7 @@ from dataclasses import dataclass
 import torch
 import torch.distributed as dist
 
-from . import _abi, bilagrid, dp, exposure, filter3d, losses, mcmc, metrics, ops, optim
+from . import _abi, bilagrid, dp, exposure, filter3d, losses, mcmc, metrics, ops, optim, poses
 
 
 @dataclass
@@ -178,6 +178,22 @@ class TrainConfig:
     bilagrid_lr_final: float = 0.00002
     bilagrid_lr_delay_mult: float = 0.0
     bilagrid_lr_max_steps: int = 30000
+    # per-view camera-pose corrections (not in the reference; gsplat's pose_opt, nerfstudio's camera optimiser; poses.py).
+    # pose_opt = True (a bool, else ValueError): every training camera has a rigid correction of nine numbers, zero at the start, that
+    # its given c2w is composed with before the render (poses.PoseTable.apply_view); the render's pose gradient trains
+    # it.  The table (Trainer.poses; Trainer(pose_views=V) rows, len(cameras) by default) is trained by an Adam of its own (eps 1e-8,
+    # dense) at the learning rate optim.position_lr gives for the four numbers below, and pose_reg times the table joins its gradient
+    # once per iteration.  The defaults are gsplat's (pose_opt_lr, pose_opt_reg, a decay to 1 %) -- taken from there, not measured here
+    # and NOT scaled by a scene extent.  A view names its camera by its integer 'idx'.  Allowed together with exposure or bilagrid.  A
+    # view of such a pass is a pose frame: it takes the separate library calls, under the factored exchange where the pass has one
+    # and under no route otherwise (fold_rest_step and sum_views_in_kernel do not apply).  filter3d's camera limits and
+    # prune_by_contribution keep using the GIVEN poses.  Off by default, and an iteration is then exactly the one above.
+    pose_opt: bool = False
+    pose_lr_init: float = 1e-5
+    pose_lr_final: float = 1e-7
+    pose_lr_delay_mult: float = 0.0
+    pose_lr_max_steps: int = 30000
+    pose_reg: float = 1e-6
 
     def __post_init__(self):
         _validate(self)
@@ -192,12 +208,12 @@ def _need_finite(cfg, *names, at_least=0):
             raise ValueError(f"{name} must be a finite number >= {at_least}, not {x!r}")
 
 
-def _validate(cfg, cameras=False, exposure_views=None, bilagrid_views=None):
+def _validate(cfg, cameras=False, exposure_views=None, bilagrid_views=None, pose_views=None):
     """Every check of a TrainConfig, in ONE order: ValueError for the first field that fails.  TrainConfig(...) itself -- the call
-    without `cameras` -- refuses only the absgrad, sparse_adam, filter3d, exposure and bilagrid groups.  A Trainer checks every field (the five
-    groups again: the fields of a config can be set after it is made) together with what its constructor was given -- `cameras` (None:
-    it was given none), `exposure_views` and `bilagrid_views` --, and gets back what it keeps of the checks: the filter keyword arguments of its renders
-    and the background in the form background() returns."""
+    without `cameras` -- refuses only the absgrad, sparse_adam, filter3d, exposure, bilagrid and pose_opt groups.  A Trainer checks
+    every field (the six groups again: the fields of a config can be set after it is made) together with what its constructor was
+    given -- `cameras` (None: it was given none), `exposure_views`, `bilagrid_views` and `pose_views` --, and gets back what it keeps
+    of the checks: the filter keyword arguments of its renders and the background in the form background() returns."""
     trainer = cameras is not False
     if trainer:
         if cfg.densify_rule not in ("reference", "screen", "mcmc"):
@@ -213,7 +229,7 @@ def _validate(cfg, cameras=False, exposure_views=None, bilagrid_views=None):
         _need_finite(cfg, "mcmc_growth", at_least=1)
         if type(cfg.mcmc_seed) is not int or not 0 <= cfg.mcmc_seed < 2 ** 64:
             raise ValueError(f"mcmc_seed must be an integer in [0, 2^64), not {cfg.mcmc_seed!r}")
-    # ---- the five groups TrainConfig(...) refuses too
+    # ---- the six groups TrainConfig(...) refuses too
     if type(cfg.densify_absgrad) is not bool:
         raise ValueError(f"densify_absgrad must be a bool, not {cfg.densify_absgrad!r}")
     if cfg.densify_absgrad and cfg.densify_rule != "screen":
@@ -239,16 +255,22 @@ def _validate(cfg, cameras=False, exposure_views=None, bilagrid_views=None):
     if cfg.bilagrid and cfg.exposure:
         raise ValueError("bilagrid=True is not available with exposure=True (the grid at the identity contains the global affine, and "
                          "two tables on one colour are ill-conditioned)")
+    if type(cfg.pose_opt) is not bool:
+        raise ValueError(f"pose_opt must be a bool, not {cfg.pose_opt!r}")
     if not trainer:
         return None
     # ---- the rest is the Trainer's alone
-    for name, n_views in (("exposure", exposure_views), ("bilagrid", bilagrid_views)):
+    for name, n_views, views_kw in (("exposure", exposure_views, "exposure_views"), ("bilagrid", bilagrid_views, "bilagrid_views"),
+                                    ("pose_opt", pose_views, "pose_views")):
         if getattr(cfg, name) and n_views is None and cameras is None:
             raise ValueError(f"{name}=True needs the number of training images: Trainer(model, config, group, cameras=views) or "
-                             f"Trainer(..., {name}_views=V)")
+                             f"Trainer(..., {views_kw}=V)")
     _need_finite(cfg, "bilagrid_tv", "bilagrid_lr_init", "bilagrid_lr_final", "bilagrid_lr_delay_mult")
     if type(cfg.bilagrid_lr_max_steps) is not int or cfg.bilagrid_lr_max_steps < 1:
         raise ValueError(f"bilagrid_lr_max_steps must be an integer >= 1, not {cfg.bilagrid_lr_max_steps!r}")
+    _need_finite(cfg, "pose_reg", "pose_lr_init", "pose_lr_final", "pose_lr_delay_mult")
+    if type(cfg.pose_lr_max_steps) is not int or cfg.pose_lr_max_steps < 1:
+        raise ValueError(f"pose_lr_max_steps must be an integer >= 1, not {cfg.pose_lr_max_steps!r}")
     if type(cfg.sh_degree_interval) is not int or cfg.sh_degree_interval < 0:
         raise ValueError(f"sh_degree_interval must be an integer >= 0, not {cfg.sh_degree_interval!r}")
     filter_kw = _abi.filter_kwargs(cfg.lowpass, cfg.antialias)      # (ValueError for a mode the kernels cannot do)
@@ -313,13 +335,16 @@ class Trainer:
     harness.save_checkpoint's file set: it travels through its own state_dict() / load_state_dict().
 
     With bilagrid = True `self.bilagrid` is the bilagrid.BilateralGridTable of `bilagrid_views` rows (default: len(cameras)), else None;
-    everything said of the exposure table holds for it."""
+    everything said of the exposure table holds for it.
 
-    def __init__(self, model, config=None, group=None, cameras=None, exposure_views=None, bilagrid_views=None):
+    With pose_opt = True `self.poses` is the poses.PoseTable of `pose_views` rows (default: len(cameras)), one per training camera, else
+    None; everything said of the exposure table holds for it, and it may stand beside either colour table."""
+
+    def __init__(self, model, config=None, group=None, cameras=None, exposure_views=None, bilagrid_views=None, pose_views=None):
         self.model = model
         self.cfg = config or TrainConfig()
         self.group = group
-        self._filter_kw, self._background = _validate(self.cfg, cameras, exposure_views, bilagrid_views)
+        self._filter_kw, self._background = _validate(self.cfg, cameras, exposure_views, bilagrid_views, pose_views)
         # the per-image table a view's rendered colour goes through before the loss (the config check allows one at the most)
         self.exposure = self.bilagrid = self._table = None
         if self.cfg.exposure or self.cfg.bilagrid:
@@ -330,6 +355,12 @@ class Trainer:
                 self._table = self.exposure = exposure.ExposureTable(n_views, model.pos.device)
             else:
                 self._table = self.bilagrid = bilagrid.BilateralGridTable(n_views, model.pos.device, shape=self.cfg.bilagrid_shape)
+        # the table of pose corrections a view's c2w is composed with before the render; the tables of a pass, in ONE fixed order --
+        # the colour table, then the poses: the order of their all-reduces on every rank
+        self.poses = None
+        if self.cfg.pose_opt:
+            self.poses = poses.PoseTable(len(cameras) if pose_views is None else pose_views, model.pos.device)
+        self._tables = [t for t in (self._table, self.poses) if t is not None]
         # filter3d: the camera records (host copy; on the model's device from the first step on) and the per-Gaussian filter
         self._cameras = filter3d.pack_cameras(cameras, "cpu") if cameras is not None and self.cfg.filter3d > 0 else None
         self._cameras_dev = None
@@ -485,14 +516,16 @@ class Trainer:
         return {'removed': removed, 'gaussians': m.get_num_gaussians(), 'frames': stats.frames}
 
     @torch.no_grad()
-    def evaluate(self, views, iteration=None, colour_correct=None):
+    def evaluate(self, views, iteration=None, colour_correct=None, refined_poses=False):
         """Per-image PSNR, SSIM and L1 of held-out `views` (the dicts step() takes, with their photographs):
         metrics.evaluate of the model as step() renders it -- the trainer's lowpass / antialias, the SH degree of `iteration` (None:
         degree 3), the filtered scale and opacity when filter3d > 0 (filter3d.apply, without gradient) -- over the trainer's group.
         The views are rendered over the trainer's background colour; background = "random" evaluates over BLACK (a report must not
         depend on a draw).  The exposure / bilateral-grid tables are NOT applied -- a held-out view has no row in them -- so with
         either on the model is only known up to a colour transform per image: colour_correct (None: cfg.exposure or cfg.bilagrid) fits
-        that transform per view before measuring.  Returns metrics.evaluate's report.  Not part of step(); parameters, gradients, the
+        that transform per view before measuring.  refined_poses = True (pose_opt only, else ValueError): a view that carries 'idx' --
+        a TRAINING view -- is rendered at its corrected pose (poses.PoseTable.c2w); held-out views, which carry none, are always
+        rendered at their given poses (there is no test-time pose alignment).  Returns metrics.evaluate's report.  Not part of step(); parameters, gradients, the
         optimiser, the statistics windows, the visible set and both tables are left bit for bit as they were.  Data parallel:
         collective -- every rank calls it with the same list."""
         c, m = self.cfg, self.model
@@ -505,6 +538,18 @@ class Trainer:
             params = filter3d.bake(m, filt)
         if colour_correct is None:
             colour_correct = bool(c.exposure or c.bilagrid)
+        if type(refined_poses) is not bool:
+            raise ValueError(f"refined_poses must be a bool, not {refined_poses!r}")
+        if refined_poses:
+            if self.poses is None:
+                raise ValueError("refined_poses=True needs a trainer with pose_opt=True")
+            named = [k for k, v in enumerate(views) if v.get('idx') is not None]
+            if named:                              # ONE launch for all of them; the callers' dicts are left as they are
+                c2ws = torch.stack([torch.as_tensor(views[k]['c2w'], dtype=torch.float32) for k in named]).to(dev)
+                refined = self.poses.c2w(c2ws, [views[k]['idx'] for k in named])
+                views = list(views)
+                for j, k in enumerate(named):
+                    views[k] = {**views[k], 'c2w': refined[j]}
         return metrics.evaluate(params, views, sh_degree=3 if iteration is None else self.sh_degree(iteration),
                                 background=None if self._background == "random" else self._background, colour_correct=colour_correct,
                                 group=self.group, **self._filter_kw)
@@ -524,10 +569,13 @@ class Trainer:
         exposure = True: every view carries 'idx', the integer in [0, V) of its training image (else ValueError, before anything is
         queued); the dict also has 'lr_exposure', the learning rate the table was stepped at.
         bilagrid = True: 'idx' likewise; the dict also has 'lr_bilagrid' and 'tv', the weighted total-variation term bilagrid_tv tv as a
-        device scalar -- it joined the table's gradient and is NOT part of 'loss', whose meaning stays."""
+        device scalar -- it joined the table's gradient and is NOT part of 'loss', whose meaning stays.
+        pose_opt = True: 'idx' likewise (valid for every table of the trainer); the dict also has 'lr_pose'."""
         c, m = self.cfg, self.model
         # ---- the facts of this step
-        rows = [self._table.check_index(v.get('idx')) for v in views] if self._table is not None else None
+        rows = None
+        for table in self._tables:                 # (one 'idx' per view names its row in every table: valid for each)
+            rows = [table.check_index(v.get('idx')) for v in views]
         aux_maps = c.lambda_alpha > 0 or c.lambda_depth > 0
         aux = aux_maps if aux_maps or self._background is not None else None     # None: no aux pass; else: does it render the maps?
         bg = self.background(iteration)
@@ -578,8 +626,9 @@ class Trainer:
             sparse_adam, several views                               FACTORED  the same exchange WITHOUT a collective: the SH gradients are
                                                                                rounded as a group of ranks rounds them, so a group steps the
                                                                                bits of one process given all its views
-            an aux pass                                              none      its frames take the separate library calls (the routes below
-                                                                               live on the composite entries, which have no aux variant)
+            an aux pass, a pose_opt pass                             none      its frames take the separate library calls (the routes below
+                                                                               live on the composite entries, which have no aux and no
+                                                                               pose variant)
             one view, fold_rest_step, not sparse_adam                FOLDED    the Adam step of f_rest inside the backward (that kernel steps
                                                                                every row: fold_rest_step is ignored under sparse_adam)
             several views, sum_views_in_kernel                       SUMMED    the views' sum formed by the backward (ops.accumulate_grads)
@@ -587,7 +636,7 @@ class Trainer:
         c = self.cfg
         if world > 1 or (c.sparse_adam and n_views > 1):
             return dp.FactoredExchange(params, world_views=1, group=self.group, equal_views=even, sh_degree=sh_degree)
-        if aux_pass:
+        if aux_pass or self.poses is not None:
             return _NO_ROUTE
         if n_views == 1 and c.fold_rest_step and not c.sparse_adam:
             return self.optimizer.fused_rest_update(self.model.f_rest)
@@ -604,8 +653,8 @@ class Trainer:
         c, m = self.cfg, self.model
         dev = m.pos.device
         self.optimizer.zero_grad()
-        if self._table is not None:
-            self._table.zero_grad()
+        for table in self._tables:
+            table.zero_grad()
         params, scale_in, opacity_in = m.get_params(), m.scale_raw, m.opacity_raw
         if c.filter3d > 0:
             # the effective scale and opacity of this pass: ONE launch and two fresh leaves -- their gradients start empty in every
@@ -635,7 +684,7 @@ class Trainer:
                 per_view, per_view_aux, row_stream = [], [], {}
                 for k, v in enumerate(views):
                     if rows is not None and side:
-                        # two views of one training image add into ONE row of the table's gradient: the later one's stream waits
+                        # two views of one training image add into ONE row of every table's gradient: the later one's stream waits
                         # for the earlier one's, so that the row is their sum in view order whichever streams they ran on
                         last = row_stream.get(rows[k])
                         if last is not None and last != k % len(side):
@@ -664,17 +713,20 @@ class Trainer:
 
     def _view(self, v, row, scale_in, opacity_in, n_global, render_kw, aux, bg, stats):
         """One view of a pass, on the current stream: targets, render -- inside the view's statistics record `stats`, if any --, the
-        transform (exposure or bilateral grid) of training image `row`, loss, backward.  Returns its loss vector and its aux-loss vector (None: no maps)."""
+        transform (exposure or bilateral grid) of training image `row`, loss, backward; with pose_opt the render is at the corrected pose of
+        camera `row`.  Returns its loss vector and its aux-loss vector (None: no maps)."""
         c, m = self.cfg, self.model
         dev = m.pos.device
         image_gt, alpha_gt, depth_gt = self._view_targets(v, dev, bg, aux is not None)
         c2w = torch.as_tensor(v['c2w'], dtype=torch.float32).to(dev)
+        if self.poses is not None:
+            c2w = self.poses.apply_view(c2w, row)      # (requires a gradient: the render below is a pose frame)
         with (ops.densify_stats(stats, absgrad=c.densify_absgrad) if stats is not None else _NO_CONTEXT):
             rendered = ops.render_gaussians(m.pos, m.f_dc, m.f_rest, opacity_in, scale_in, m.q_raw, c2w,
                                             int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']), **render_kw)
         if aux:
             rendered, depth, alpha = rendered
-        if row is not None:
+        if self._table is not None:
             rendered = self._table.apply_view(rendered, row)
         loss, vals = losses.compute_loss_device(rendered, image_gt, c.lambda_l1, c.lambda_ssim, scale=1.0 / n_global)
         if not aux:
@@ -729,18 +781,19 @@ class Trainer:
 
     def _update(self, iteration, consumer, leaves, acc, acc_aux, world):
         """The optimiser steps of an iteration whose pass every rank agreed good -- so every rank is here, and none can be left in one
-        of the collectives below.  Returns (what the per-image table adds to step()'s dict: 'lr_exposure', or 'lr_bilagrid' and 'tv';
+        of the collectives below.  Returns (what the per-image tables add to step()'s dict: 'lr_exposure', or 'lr_bilagrid' and 'tv'; 'lr_pose';
         mcmc.regularise's [reg_opacity, reg_scale, loss] or None)."""
-        c, m, table = self.cfg, self.model, self._table
+        c, m = self.cfg, self.model
         table_out, reg = {}, None
-        if table is not None:
+        for table in self._tables:                 # (the fixed order of the constructor: one all-reduce per table, the same on every rank)
             # the table's gradient is complete on this rank -- the caller's stream has waited for the views' streams; summed over the
             # ranks, every replica steps the same bits.  The table's once-per-iteration term (the grid's TV) joins AFTER the all-reduce:
             # every rank computes the same one, and it counts once.  The table's own Adam, at this iteration's learning rate of its own
             if world > 1:
                 dp.allreduce_table_grad(table.grad, self.group)
             table_out.update(table.regularise(c))
-            lr = optim.position_lr(iteration, *(getattr(c, f"{table.name}_lr_{k}") for k in ("init", "final", "delay_mult", "max_steps")))
+            sched = [getattr(c, f"{table.name}_lr_{k}") for k in ("init", "final", "delay_mult", "max_steps")]
+            lr = optim.position_lr(iteration, *sched) if sched[0] > 0 else 0.0        # (a table frozen by a zero rate: no 0 / 0)
             table_out['lr_' + table.name] = lr
             table.step(lr)
         scale_in, opacity_in = leaves

@@ -9,9 +9,9 @@ all:
 # Sanitizers run on the CPU builds only (GPU AddressSanitizer is not available on the pool): the host build of the projection
 # math (the same gs_math.h / gs_body.h the HIP kernels inline) and the plain-C oracle, each under AddressSanitizer + UBSan,
 # driven by their own test files.  Python is not instrumented, so the runtime is preloaded and leak checking is off.
-# The MCMC arithmetic (gs_mcmc.h), the 3D filter (gs_filter3d.h), the exposure transform (gs_exposure.h), the bilateral grid (gs_bilagrid.h), the image metrics (gs_metrics.h) and the nearest-neighbour search (gs_knn.h) go through stand-alone instrumented programs of their own, which
+# The MCMC arithmetic (gs_mcmc.h), the 3D filter (gs_filter3d.h), the exposure transform (gs_exposure.h), the bilateral grid (gs_bilagrid.h), the image metrics (gs_metrics.h), the nearest-neighbour search (gs_knn.h) and the pose corrections (gs_pose_delta.h) go through stand-alone instrumented programs of their own, which
 # need no preloaded runtime.
-check-asan: check-asan-mcmc check-asan-filter3d check-asan-exposure check-asan-bilagrid check-asan-metrics check-asan-knn
+check-asan: check-asan-mcmc check-asan-filter3d check-asan-exposure check-asan-bilagrid check-asan-metrics check-asan-knn check-asan-pose_delta
 	mkdir -p $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -std=c++17 -shared -fPIC -o $(ASAN_DIR)/libgsmath_host_asan.so $(PKG)/csrc/host_math_check.cpp
 	gcc $(ASAN_FLAGS) -std=c99 -fopenmp -shared -fPIC -o $(ASAN_DIR)/libgs_oracle_asan.so oracle/gs_oracle.c -lm

@@ -303,7 +303,9 @@ int gsplat_project_backward(const gsplat_gaussians* g, const float* c2w, const g
 
 /* gsplat_project_backward plus the gradient w.r.t. the camera pose: grad_c2w[16] (device, row-major 4 x 4) receives dL/dc2w of
  * the same grad2d (render.py:122,156-159 and spherical_harmonics.py:132 differentiated w.r.t. c2w; its last row is 0).
- *   out            as for gsplat_project_backward (all gradients of the inputs, not factored), or NULL: the pose gradient only.
+ *   out            as for gsplat_project_backward: all gradients of the inputs, or -- fused inputs, f_dc and f_rest NULL -- the
+ *                  factored form (the colour-logit gradients into out->color if given, no SH gradients: a pose frame inside a
+ *                  factored exchange); or NULL: the pose gradient only.
  *   pose_scratch   gsplat_pose_scratch_bytes(n) bytes, 64-byte aligned, caller-owned; nothing needs clearing.
  *   flags          GSPLAT_BACKWARD_SH_JACOBIAN and GSPLAT_BACKWARD_DEPTH; any other bit is refused with GSPLAT_ERR_BAD_ARG.
  * The per-Gaussian terms are added in a fixed order, without atomics: the same inputs give the same bits.  NULL grad_c2w is
@@ -714,6 +716,30 @@ int gsplat_metrics_forward(const float* pred, const float* target, const uint8_t
 #define GSPLAT_KNN_BOX 256
 int64_t gsplat_knn_scratch_bytes(int64_t n);
 int gsplat_knn_mean_dist2(int64_t n, const float* points, float* dist2, void* scratch, void* stream);
+
+/* ---- per-view camera-pose corrections (not in the reference) --------------------------------------------------------
+ * A rigid correction per training camera, delta = (d[3], p[3], s[3]), nine floats with zero as the identity -- a translation and the
+ * 6-D rotation of Zhou et al., gsplat's pose_opt parametrisation --, composed with the given pose before the render.  With
+ * c2w = [[R, e], [r3]] (row-major 4 x 4):
+ *     a1 = p + (1,0,0)   a2 = s + (0,1,0)   b1 = a1 / max(|a1|, 1e-12)   u2 = a2 - (b1.a2) b1   b2 = u2 / max(|u2|, 1e-12)   b3 = b1 x b2
+ *     out[:3,:3] = R D, D the 3 x 3 with ROWS b1, b2, b3;      out[:3,3] = R d + e;      out[3,:] = c2w[3,:]
+ * (csrc/gs_pose_delta.h has the fma chains: delta = 0 returns every finite c2w as the same numbers -- a -0 may come back as +0.)  An
+ * active clamp treats its denominator as a constant in the backward.  c2w, out, grad_out, grad_c2w: [batch, 16] floats; delta:
+ * [batch, 9].  These are NOT the render's own pose gradient (gsplat_pose_scratch_bytes / gsplat_project_backward_pose, dL/dc2w of a
+ * frame): they take that gradient as grad_out.  Every entry is one launch of one lane per view on the caller's stream, reads
+ * nothing back, allocates nothing and needs no scratch.  batch (n_views) > 0 and <= 2^30, else GSPLAT_ERR_BAD_ARG, as for a NULL
+ * required pointer -- before anything is launched.  Arrays 4-byte aligned.  No output may alias an input.
+ * Backward: grad_c2w (NULL: not computed) = dL/dc2w, and the nine floats dL/ddelta of view b (grad_delta == NULL: not computed) go to
+ *   row b of grad_delta, or to row row_index[b] when row_index (batch int32 on the device; a negative entry drops the view) is given;
+ *   the rows named must be distinct; a row no view names keeps its bits.  flags: GSPLAT_POSE_DELTA_ACCUMULATE adds to the
+ *   destination rows instead of overwriting them; any other bit is refused first ("unknown flag").  Either half alone has the bits
+ *   it has in a call for both.  No atomics: the same bits on every call, stream and launch.
+ * Decay: grad[v, k] = fma(reg, delta[v, k], grad[v, k]) over a table of n_views rows -- the gradient of (reg / 2) |delta|^2.      */
+#define GSPLAT_POSE_DELTA_ACCUMULATE 1
+int gsplat_pose_delta_forward(const float* c2w, const float* delta, int64_t batch, float* out, void* stream);
+int gsplat_pose_delta_backward(const float* c2w, const float* delta, const float* grad_out, int64_t batch, float* grad_c2w, float* grad_delta,
+                               const int32_t* row_index, int32_t flags, void* stream);
+int gsplat_pose_delta_decay(const float* delta, int64_t n_views, float reg, float* grad, void* stream);
 
 #ifdef __cplusplus
 }
