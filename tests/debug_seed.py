@@ -1,60 +1,58 @@
 #!/usr/bin/env python3
-"""For one seed of tests/test_gpu_parity.py::test_random_scenes_vs_oracle: gradient errors of the HIP path AND of the oracle
-run in float32 (= the reference's own fp32 arithmetic), both against the float64 oracle (diagnostic; needs a GPU)."""
+"""For one seed of tests/test_gpu_parity.py::test_random_scenes_vs_oracle, or -- with a row of tests/mode_scenes.MODES -- one case of
+tests/test_gpu_mode_scenes.py: the errors of the HIP path AND of the oracle run in float32 (= the reference's own fp32 arithmetic),
+both against the float64 oracle, for the image, the maps and every gradient (diagnostic; needs a GPU).
+    python tests/debug_seed.py <seed> [row] [det]"""
 import importlib
 import sys
 
 import numpy as np
-import torch
 
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
-from oracle import scenes
-from oracle import torch_port as tp
+from tests import mode_scenes as ms
 from tests import util
 
-seed = int(sys.argv[1])
+args = [a for a in sys.argv[1:] if a != "det"]
+seed = int(args[0])
 gs = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd")
-if len(sys.argv) > 2 and sys.argv[2] == "det":          # fixed-order sums instead of float atomics (is an error an accumulation error?)
-    gs.set_deterministic(True)
-rng = np.random.default_rng(1000 + seed)
-H, W = int(rng.integers(9, 150)), int(rng.integers(9, 200))
-n = int(rng.integers(1, 1800))
-f = float(rng.uniform(40, 160))
-cam = (H, W, f, f * float(rng.uniform(0.9, 1.1)), W / 2 + float(rng.uniform(-5, 5)), H / 2 + float(rng.uniform(-5, 5)))
-c2w = torch.tensor(scenes._camera(rng, tilt=0.3))
-s = scenes._base(rng, n, H, W, cam[2], cam[3], cam[4], cam[5], mu_s=float(rng.uniform(-3.2, -1.2)), sd_s=float(rng.uniform(0.2, 1.0)),
-                 op_mu=float(rng.uniform(-2, 3)), op_sd=1.5, spread=1.3, c2w=c2w.numpy())
-t = {k: torch.tensor(s[k]) for k in util.PARAMS}
-zc = tp.to_camera(t["pos"].double(), c2w.double())[2]
-zs, order = torch.sort(zc)
-keep = torch.ones(n, dtype=torch.bool)
-keep[order[1:][(zs[1:] - zs[:-1]) < 2e-5]] = False
-t = {k: v[keep].contiguous() for k, v in t.items()}
-w = torch.tensor(rng.uniform(0, 1, (H, W, 3)).astype(np.float32))
-print("H W n", H, W, len(t["pos"]))
-names = ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")
-res = {}
-for tag, dt in (("f64", torch.float64), ("f32", torch.float32)):
-    p = {k: v.to(dt).detach().clone().requires_grad_(True) for k, v in t.items()}
-    img = tp.render_fused(*[p[k] for k in names], c2w.to(dt), *cam)
-    (img * w.to(dt)).sum().backward()
-    res[tag] = (img.detach().double().numpy(), {k: p[k].grad.double().numpy() for k in names})
-p = {k: v.to("cuda:0").detach().requires_grad_(True) for k, v in t.items()}
-img = gs.render_gaussians(*[p[k] for k in names], c2w.to("cuda:0"), *cam)
-(img * w.to("cuda:0")).sum().backward()
-res["hip"] = (img.detach().cpu().double().numpy(), {k: p[k].grad.cpu().double().numpy() for k in names})
+if len(args) > 1:
+    row = int(args[1])
+    d, m = ms.mode_scene(seed), ms.MODES[row]
+    print("row", row, m)
+else:
+    d, m = ms.parity_scene(seed), ms.MODES[0]
+if "det" in sys.argv[1:]:                                # fixed-order sums instead of float atomics (is an error an accumulation error?)
+    m = m._replace(route=ms.DETERMINISTIC)
+print("H W n", d["H"], d["W"], len(d["pos"]))
+res = {"f64": ms.oracle(d, m, ms.F64), "f32": ms.oracle(d, m, ms.F32), "hip": ms.render_hip(gs, d, m)}
 ref = res["f64"]
+names = ms.grad_names(m)
 for tag in ("f32", "hip"):
-    im, g = res[tag]
-    d = np.abs(im - ref[0])
-    print(tag, "image: mean %.2e max %.2e frac>1e-5 %.2e" % (d.mean(), d.max(), (d > 1e-5).mean()))
+    for what, im, r in zip(("image", "depth / max", "alpha"), res[tag][:3], ref[:3]):
+        if im is not None:
+            scale = max(np.abs(r).max(), 1e-30) if what.startswith("depth") else 1.0
+            dd = np.abs(im - r) / scale
+            y, x = np.unravel_index(int(dd.reshape(dd.shape[0], dd.shape[1], -1).max(-1).argmax()), dd.shape[:2])
+            print(tag, "%-11s mean %.2e max %.2e at pixel (%d, %d) frac>1e-5 %.2e  >5e-3: %d" %
+                  (what + ":", dd.mean(), dd.max(), y, x, (dd > util.IMG_TOL_BULK).mean(), int((dd > util.IMG_TOL_REST).sum())))
     for k in names:
-        e = g[k] - ref[1][k]
-        print("   %-12s rel-L2 %.3e  max/max %.3e" % (k, np.linalg.norm(e) / (np.linalg.norm(ref[1][k]) + 1e-300), np.abs(e).max() / (np.abs(ref[1][k]).max() + 1e-300)))
+        e = util.grad_errors(res[tag][3][k], ref[3][k])
+        print("   %-12s rel-L2 %.3e  max/max %.3e" % (k, e["l2"], e["mx"]))
 # where the largest error of every gradient sits, and what the float32 oracle does at the same Gaussian
 for k in names:
-    e = np.abs(res["hip"][1][k] - ref[1][k]).reshape(len(ref[1][k]), -1).max(1)
+    if k == "c2w":
+        continue
+    n = len(ref[3][k])
+    e = np.abs(res["hip"][3][k] - ref[3][k]).reshape(n, -1).max(1)
     i = int(e.argmax())
-    e32 = np.abs(res["f32"][1][k] - ref[1][k]).reshape(len(ref[1][k]), -1).max(1)
+    e32 = np.abs(res["f32"][3][k] - ref[3][k]).reshape(n, -1).max(1)
     print("   worst %-12s Gaussian %5d: |err| hip %.3e, f32 oracle %.3e there (its own worst %.3e at %d); |ref| there %.3e, max |ref| %.3e"
-          % (k, i, e[i], e32[i], e32.max(), int(e32.argmax()), np.abs(ref[1][k]).reshape(len(e), -1).max(1)[i], np.abs(ref[1][k]).max()))
+          % (k, i, e[i], e32[i], e32.max(), int(e32.argmax()), np.abs(ref[3][k]).reshape(n, -1).max(1)[i], np.abs(ref[3][k]).max()))
+# what moving the chi-square clip and alpha_cutoff by -+ 1e-4 (relative) does to the gradients in float64, beside the HIP error
+for thr in ("chi_square_clip", "alpha_cutoff"):
+    band = ms.threshold_band(d, m, 1e-4, (thr,))
+    for k in names:
+        e = np.abs(res["hip"][3][k] - ref[3][k])
+        out = np.maximum(e - util.K_CAL * band[k], 0.0)
+        print("   %s -+1e-4 %-12s band max %.3e; |hip err| max %.3e, outside K_CAL x band %.3e (max |ref| %.3e)"
+              % (thr, k, band[k].max(), e.max(), out.max(), np.abs(ref[3][k]).max()))

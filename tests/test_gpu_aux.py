@@ -13,6 +13,7 @@ import torch
 
 from oracle import torch_port as tp
 from tests import device_frame, list_scenes, util
+from tests.mode_scenes import check_grads as _check_grads, check_maps as _check_maps, loss as _loss
 
 pytestmark = pytest.mark.gpu
 abi = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd._abi")
@@ -43,13 +44,6 @@ def _scene(name):
     d["w_depth"] = rng.uniform(0, 1, (d["H"], d["W"])) / 8
     d["w_alpha"] = rng.uniform(-1, 1, (d["H"], d["W"]))
     return d
-
-
-def _loss(out, d, dtype, device, which):
-    """L = sum image * w_img + sum depth * w_depth + sum alpha * w_alpha, or one of the three terms."""
-    terms = dict(image=(out[0], "w_img"), depth=(out[1], "w_depth"), alpha=(out[2], "w_alpha"))
-    use = terms if which == "all" else {which: terms[which]}
-    return sum((t * torch.as_tensor(np.asarray(d[w]), dtype=dtype, device=device)).sum() for t, w in use.values())
 
 
 @functools.lru_cache(maxsize=None)
@@ -85,21 +79,6 @@ def _render(gs, name, which="all", aux=True, background=None, c2w_grad=True, fn=
     return out, grads
 
 
-def _check_maps(out, ref, cal, what):
-    img, depth, alpha = (t.detach().double().cpu().numpy() for t in out)
-    assert out[0].dtype == out[1].dtype == out[2].dtype == F32
-    assert depth.shape == alpha.shape == img.shape[:2]
-    util.check_image(img, ref[0], cal=cal[0], what=f"{what} image")
-    util.check_image(alpha, ref[2], cal=cal[2], what=f"{what} alpha")
-    scale = max(float(np.abs(ref[1]).max()), 1e-30)
-    util.check_image(depth / scale, ref[1] / scale, cal=cal[1] / scale, what=f"{what} depth / max")
-
-
-def _check_grads(grads, ref, cal, what, names=NAMES + ("c2w",)):
-    for k in names:
-        util.check_grad(grads[k].double().cpu().numpy(), ref[3][k], f"{what} {k}", cal=cal[3][k])
-
-
 # ---- 1, 2: maps and gradients against float64 ------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("name", util.RENDER_CASES + [STACKED])
@@ -107,7 +86,7 @@ def test_maps_and_gradients_of_render_gaussians_vs_oracle(gs, name):
     ref, cal = _reference(name, F64), _reference(name, F32)
     out, grads = _render(gs, name)
     _check_maps(out, ref, cal, name)
-    _check_grads(grads, ref, cal, name)
+    _check_grads(grads, ref[3], cal[3], name)
 
 
 def test_stacked_scene_runs_the_capped_multi_chunk_path(gs):
@@ -149,7 +128,7 @@ def test_maps_and_gradients_of_unfused_render_vs_oracle(gs, name):
     grads = {k: v.grad for k, v in p.items()}
     grads["c2w"] = c.grad
     _check_maps(out, ref, cal, f"render {name}")
-    _check_grads(grads, ref, cal, f"render {name}", names=UNFUSED + ("c2w",))
+    _check_grads(grads, ref[3], cal[3], f"render {name}", names=UNFUSED + ("c2w",))
 
 
 # ---- 3: the aux image is the plain image -----------------------------------------------------------------------------------------
@@ -177,7 +156,7 @@ def test_depth_only_loss(gs):
     ref, cal = _reference(name, F64, which="depth"), _reference(name, F32, which="depth")
     out, grads = _render(gs, name, which="depth")
     assert float(grads["f_dc"].abs().max()) == 0.0 and float(grads["f_rest"].abs().max()) == 0.0
-    _check_grads(grads, ref, cal, "depth only", names=("pos", "c2w"))
+    _check_grads(grads, ref[3], cal[3], "depth only", names=("pos", "c2w"))
     g, s = grads["c2w"].double().cpu(), -grads["pos"].double().sum(0).cpu()          # the translation identity
     assert float((g[:3, 3] - s).abs().max()) <= 1e-5 * float(grads["pos"].double().abs().sum()), (g[:3, 3], s)
     assert bool((grads["c2w"][3] == 0).all())
@@ -188,13 +167,13 @@ def test_alpha_only_and_image_only_losses(gs):
     ref, cal = _reference(name, F64, which="alpha"), _reference(name, F32, which="alpha")
     _, grads = _render(gs, name, which="alpha")
     assert float(grads["f_dc"].abs().max()) == 0.0 and float(grads["f_rest"].abs().max()) == 0.0
-    _check_grads(grads, ref, cal, "alpha only", names=("pos", "opacity_raw", "scale_raw", "q_raw", "c2w"))
+    _check_grads(grads, ref[3], cal[3], "alpha only", names=("pos", "opacity_raw", "scale_raw", "q_raw", "c2w"))
     # image only: the aux call and the plain call against the same float64 reference
     ref, cal = _reference(name, F64, which="image"), _reference(name, F32, which="image")
     _, g_aux = _render(gs, name, which="image")
     _, g_plain = _render(gs, name, aux=False)
-    _check_grads(g_aux, ref, cal, "image only (aux)")
-    _check_grads(g_plain, ref, cal, "image only (plain)")
+    _check_grads(g_aux, ref[3], cal[3], "image only (aux)")
+    _check_grads(g_plain, ref[3], cal[3], "image only (plain)")
 
 
 # ---- 6: background -------------------------------------------------------------------------------------------------------------
@@ -204,13 +183,13 @@ def test_background(gs, name):
     ref, cal = _reference(name, F64, background=BG), _reference(name, F32, background=BG)
     out, grads = _render(gs, name, background=BG)
     _check_maps(out, ref, cal, f"{name} over a background")
-    _check_grads(grads, ref, cal, f"{name} over a background")
+    _check_grads(grads, ref[3], cal[3], f"{name} over a background")
     # without aux: ONE tensor, the aux call's image; its gradients are those of the image term
     one, g_one = _render(gs, name, aux=False, background=torch.tensor(BG))
     assert isinstance(one, torch.Tensor) and one.shape == out[0].shape
     assert torch.equal(one.detach(), out[0].detach())
     ref_i, cal_i = _reference(name, F64, background=BG, which="image"), _reference(name, F32, background=BG, which="image")
-    _check_grads(g_one, ref_i, cal_i, f"{name} background only")
+    _check_grads(g_one, ref_i[3], cal_i[3], f"{name} background only")
 
 
 # ---- 7: deterministic mode ---------------------------------------------------------------------------------------------------------
@@ -226,7 +205,7 @@ def test_deterministic_mode(gs, name):
         gs.set_deterministic(old)
     for k in g1:
         assert torch.equal(g1[k], g2[k]), k
-    _check_grads(g1, ref, cal, f"{name} deterministic")
+    _check_grads(g1, ref[3], cal[3], f"{name} deterministic")
 
 
 # ---- 8: deferred checks, no_grad ---------------------------------------------------------------------------------------------------
@@ -244,8 +223,8 @@ def test_deferred_frame_gives_the_waited_frame(gs):
     _check_maps(out_d, ref, cal, "deferred")
     _check_maps(out_w, ref, cal, "waited")
     print("max |deferred - waited|:", [float((a.detach() - b.detach()).abs().max()) for a, b in zip(out_d, out_w)])
-    _check_grads(g_d, ref, cal, "deferred")
-    _check_grads(g_w, ref, cal, "waited")
+    _check_grads(g_d, ref[3], cal[3], "deferred")
+    _check_grads(g_w, ref[3], cal[3], "waited")
 
 
 def test_no_grad_saves_nothing(gs):

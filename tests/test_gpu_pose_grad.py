@@ -8,6 +8,7 @@ import torch
 from oracle import scenes
 from oracle import torch_port as tp
 from tests import util
+from tests.mode_scenes import check_pose as _check_pose
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -31,11 +32,6 @@ def _render_fused(gs, s, c2w, cam, w, kw=None, c2w_grad=True, param_grad=True, c
     (img * torch.as_tensor(np.asarray(w), dtype=F32, device=DEV)).sum().backward()
     torch.cuda.synchronize()
     return img, c, p
-
-
-def _check_pose(g, ref, what, cal=None):
-    util.check_grad(g[:3, :3], ref[:3, :3], f"{what} c2w[:3,:3]", cal=None if cal is None else cal[:3, :3])
-    util.check_grad(g, ref, f"{what} c2w", cal=cal)
 
 
 def _translation_identity(c, pos_grad):
