@@ -1,13 +1,12 @@
 """What the GPU tests of the pose table share (tests/test_gpu_pose_delta.py, tests/test_gpu_pose_training.py): direct calls into the
 three entries, the bits of a trainer's tables, and the two-rank run.  The plumbing is tests/view_table_harness.py's; its _table_bits
 and its workers know the two colour tables only, so the ones here are their pose-aware twins."""
-import datetime
 import importlib
-import os
 
 import numpy as np
 import torch
 
+from tests.ranks import run_ranks
 from tests.view_table_harness import DEV, NAMES, PKG, _dev, _model_bits, _p, _scene, _stream, _warm  # noqa: F401  (shared with the test files)
 
 N_CAMERAS = 5
@@ -65,10 +64,7 @@ def table_bits(tr):
 DP_CFG = dict(sparse_adam=True, pose_opt=True, pose_lr_init=1e-3, pose_lr_final=1e-4)       # (a rate at which two iterations move the rows)
 
 
-def _dp_worker(extra, iterations, rank, world, port, q):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _dp_worker(rank, world, extra, iterations):
     gs = importlib.import_module(PKG)
     gs.set_deterministic(True)
     s, views = dp_views()
@@ -77,9 +73,7 @@ def _dp_worker(extra, iterations, rank, world, port, q):
     for it in iterations:
         tr.step(it, [views[rank]], global_views=world)
     torch.cuda.synchronize()
-    q.put((rank, {k: v.cpu().numpy() for k, v in table_bits(tr).items()}, {k: v.cpu().numpy() for k, v in _model_bits(tr).items()}))
-    dist.barrier()
-    dist.destroy_process_group()
+    return {k: v.cpu().numpy() for k, v in table_bits(tr).items()}, {k: v.cpu().numpy() for k, v in _model_bits(tr).items()}
 
 
 def dp_views():
@@ -91,26 +85,7 @@ def dp_views():
 def two_ranks_against_one_process(gs, extra, iterations):
     """Two ranks (gloo, both on cuda:0) with one view each against one process given both views, DP_CFG plus `extra`: asserts that the
     tables and the model of either rank are those of the one process, bit for bit, and returns the one process's table bits."""
-    import socket
-    import torch.multiprocessing as mp
-    sock = socket.socket()
-    sock.bind(("127.0.0.1", 0))
-    port = sock.getsockname()[1]
-    sock.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_dp_worker, args=(extra, iterations, r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    try:
-        got = dict((r, (table, model)) for r, table, model in (q.get(timeout=150) for _ in range(2)))
-        for p in procs:
-            p.join(timeout=120)
-            assert p.exitcode == 0
-    finally:
-        for p in procs:
-            if p.is_alive():
-                p.kill()
+    got = run_ranks(_dp_worker, 2, extra, iterations)
     s, views = dp_views()
     _warm(gs, s, views)
     tr = trainer(s, **DP_CFG, **extra)

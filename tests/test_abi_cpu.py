@@ -3,23 +3,17 @@
 import ctypes as C
 import importlib
 import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_checks import exported_functions, header_defines, header_functions, refused
+
 abi = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd._abi")
 
 
-def _header_functions():
-    txt = open(os.path.join(ROOT, "include", "gsplat_mi355x.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(gsplat_[a-z0-9_]+)\s*\(", txt)))
-
-
 def test_header_and_python_mirror_agree():
-    names = _header_functions()
+    names = header_functions()
     assert len(names) >= 16
     assert sorted(abi.SIGNATURES) == names
 
@@ -27,8 +21,7 @@ def test_header_and_python_mirror_agree():
 def test_header_constants_and_python_mirror_agree():
     """Every integer #define of the header that the Python host mirrors (flags, status / scene codes, ABI version) has the
     header's value there; the flag bits of one call are distinct."""
-    txt = open(os.path.join(ROOT, "include", "gsplat_mi355x.h")).read()
-    defs = {k: int(v, 0) for k, v in re.findall(r"^#define\s+(GSPLAT_[A-Z0-9_]+)\s+(-?(?:0x[0-9a-fA-F]+|\d+))\s*$", txt, flags=re.M)}
+    defs = header_defines()
     assert defs["GSPLAT_ABI_VERSION"] == abi.ABI_VERSION
     mirrored = [k for k in defs if hasattr(abi, k)]
     assert {"GSPLAT_PROJECT_COLOUR_FUSED", "GSPLAT_PROJECT_COUNTS_MAPPED", "GSPLAT_PROJECT_SAVE_SH_JACOBIAN", "GSPLAT_PROJECT_COUNTS_LATE",
@@ -42,7 +35,7 @@ def test_header_constants_and_python_mirror_agree():
 def test_library_exports_every_declared_symbol():
     assert os.path.exists(abi.LIB_PATH), "build the library first: python __graft_entry__.py"
     lib = C.CDLL(abi.LIB_PATH)
-    for name in _header_functions():
+    for name in header_functions():
         assert hasattr(lib, name), f"{name} is declared in include/gsplat_mi355x.h but not exported"
     assert abi.lib().gsplat_abi_version() == abi.ABI_VERSION
 
@@ -50,10 +43,8 @@ def test_library_exports_every_declared_symbol():
 def test_library_exports_nothing_but_the_declared_entry_points():
     """Every defined dynamic FUNCTION symbol of the product library is an entry point of include/gsplat_mi355x.h (a helper with C
     linkage inside the extern "C" block would be exported silently: round 2's carve_det)."""
-    import subprocess
-    out = subprocess.run(["nm", "-D", "--defined-only", abi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    funcs = [ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TtWw"]
-    declared = set(_header_functions())
+    funcs = exported_functions()
+    declared = set(header_functions())
     stray = [f for f in funcs if f not in declared and not f.startswith(("_init", "_fini", "__hip", "_ZN", "_ZT", "_ZS"))]
     assert not stray, f"non-ABI symbols exported by the product library: {stray}"
     assert not [f for f in funcs if f.startswith("gsplat_") and f not in declared], "exported gsplat_* symbol missing from the header"
@@ -116,21 +107,16 @@ def test_bad_arguments_are_rejected_without_touching_the_gpu():
     bad = abi.make_view(0, 64, 50.0, 50.0, 32.0, 32.0)
     for status in (lib.gsplat_project_state_layout(4, None, C.byref(lay)), lib.gsplat_project_state_layout(4, C.byref(v), None),
                    lib.gsplat_project_state_layout(-1, C.byref(v), C.byref(lay)), lib.gsplat_project_state_layout(4, C.byref(bad), C.byref(lay))):
-        _refused(lib, status, "gsplat_project_state_layout")
+        refused(lib, status, "gsplat_project_state_layout")
     for status in (lib.gsplat_bin_state_layout(4, None, C.byref(bl)), lib.gsplat_bin_state_layout(4, C.byref(v), None),
                    lib.gsplat_bin_state_layout(-1, C.byref(v), C.byref(bl))):
-        _refused(lib, status, "gsplat_bin_state_layout")
+        refused(lib, status, "gsplat_bin_state_layout")
 
 
 def _host_words(n=16):
     """A non-NULL address for an argument check to look at; every call below is refused on the host before anything is launched."""
     buf = (C.c_float * n)()
     return buf, C.cast(buf, C.c_void_p)
-
-
-def _refused(lib, status, name):
-    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, status)
-    assert name.encode() in lib.gsplat_last_error(), (name, lib.gsplat_last_error())
 
 
 def test_loss_entries_reject_bad_arguments_on_the_host():
@@ -152,33 +138,33 @@ def test_loss_entries_reject_bad_arguments_on_the_host():
                                (fwd, "gsplat_loss_forward", ("pred", "target", "values", "scratch")),
                                (bwd, "gsplat_loss_backward", ("pred", "target", "grad", "scratch"))):
         for arg in required:
-            _refused(lib, fn(**{arg: None}), name)
+            refused(lib, fn(**{arg: None}), name)
         for bad in (dict(H=0), dict(H=-3), dict(W=0), dict(W=-1), dict(batch=0), dict(batch=-2), dict(batch=65536), dict(batch=1 << 40)):
-            _refused(lib, fn(**bad), name)
+            refused(lib, fn(**bad), name)
     del keep
 
 
 def test_optimiser_entries_reject_bad_arguments_on_the_host():
     lib = abi.lib()
     keep, p = _host_words()
-    _refused(lib, lib.gsplat_clip_grad_norm(-1, p, 1.0, p, p, None), "gsplat_clip_grad_norm")
-    _refused(lib, lib.gsplat_clip_grad_norm(4, None, 1.0, p, p, None), "gsplat_clip_grad_norm")
-    _refused(lib, lib.gsplat_clip_grad_norm(4, p, 1.0, None, p, None), "gsplat_clip_grad_norm")
+    refused(lib, lib.gsplat_clip_grad_norm(-1, p, 1.0, p, p, None), "gsplat_clip_grad_norm")
+    refused(lib, lib.gsplat_clip_grad_norm(4, None, 1.0, p, p, None), "gsplat_clip_grad_norm")
+    refused(lib, lib.gsplat_clip_grad_norm(4, p, 1.0, None, p, None), "gsplat_clip_grad_norm")
     nine = (abi.AdamGroup * 9)(*[abi.AdamGroup(0, None, None, None, None, 0.01, 1, None) for _ in range(9)])
-    _refused(lib, lib.gsplat_adam_step_multi(9, nine, 0.9, 0.999, 1e-15, None), "gsplat_adam_step_multi")
+    refused(lib, lib.gsplat_adam_step_multi(9, nine, 0.9, 0.999, 1e-15, None), "gsplat_adam_step_multi")
     assert lib.gsplat_adam_step_multi(8, nine, 0.9, 0.999, 1e-15, None) == abi.GSPLAT_OK       # eight empty groups: nothing to launch
-    _refused(lib, lib.gsplat_adam_step_multi(-1, nine, 0.9, 0.999, 1e-15, None), "gsplat_adam_step_multi")
-    _refused(lib, lib.gsplat_adam_step_multi(1, None, 0.9, 0.999, 1e-15, None), "gsplat_adam_step_multi")
+    refused(lib, lib.gsplat_adam_step_multi(-1, nine, 0.9, 0.999, 1e-15, None), "gsplat_adam_step_multi")
+    refused(lib, lib.gsplat_adam_step_multi(1, None, 0.9, 0.999, 1e-15, None), "gsplat_adam_step_multi")
     for bad in (abi.AdamGroup(0, None, None, None, None, 0.01, 0, None),             # step < 1 (the bias correction divides by 1 - b^step)
                 abi.AdamGroup(4, p, p, p, p, 0.01, -1, None),
                 abi.AdamGroup(-1, p, p, p, p, 0.01, 1, None),                        # n < 0
                 abi.AdamGroup(4, p, None, p, p, 0.01, 1, None)):                     # a NULL array of a non-empty group
         two = (abi.AdamGroup * 2)(abi.AdamGroup(0, None, None, None, None, 0.01, 1, None), bad)
-        _refused(lib, lib.gsplat_adam_step_multi(2, two, 0.9, 0.999, 1e-15, None), "gsplat_adam_step_multi")
+        refused(lib, lib.gsplat_adam_step_multi(2, two, 0.9, 0.999, 1e-15, None), "gsplat_adam_step_multi")
         assert b"group 1" in lib.gsplat_last_error()
-    _refused(lib, lib.gsplat_adam_step(-1, p, p, p, p, 0.01, 0.9, 0.999, 1e-15, 1, None, None), "gsplat_adam_step")
-    _refused(lib, lib.gsplat_adam_step(4, p, p, p, p, 0.01, 0.9, 0.999, 1e-15, 0, None, None), "gsplat_adam_step")
-    _refused(lib, lib.gsplat_adam_step(4, p, p, None, p, 0.01, 0.9, 0.999, 1e-15, 1, None, None), "gsplat_adam_step")
+    refused(lib, lib.gsplat_adam_step(-1, p, p, p, p, 0.01, 0.9, 0.999, 1e-15, 1, None, None), "gsplat_adam_step")
+    refused(lib, lib.gsplat_adam_step(4, p, p, p, p, 0.01, 0.9, 0.999, 1e-15, 0, None, None), "gsplat_adam_step")
+    refused(lib, lib.gsplat_adam_step(4, p, p, None, p, 0.01, 0.9, 0.999, 1e-15, 1, None, None), "gsplat_adam_step")
     del keep
 
 

@@ -7,15 +7,12 @@ import importlib
 import pytest
 import torch
 
+from tests.abi_checks import refused
+
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
 abi = importlib.import_module(PKG + "._abi")
 NEW = ("gsplat_rasterize_backward_abs", "gsplat_rasterize_backward_aux_abs", "gsplat_rasterize_backward_abs_scratch_bytes",
        "gsplat_rasterize_backward_aux_abs_scratch_bytes", "gsplat_densify_stats_abs", "gsplat_frame_densify_stats_abs")
-
-
-def _refused(lib, status, name):
-    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, status)
-    assert name.encode() in lib.gsplat_last_error(), (name, lib.gsplat_last_error())
 
 
 def test_the_new_symbols_exist_and_the_version_stays():
@@ -53,19 +50,19 @@ def test_null_arguments_are_refused_under_the_entrys_own_name():
     for fn, name, ptrs in ((rb, "gsplat_rasterize_backward_abs", ("state", "bins", "accum", "gi", "g2d")),
                            (rba, "gsplat_rasterize_backward_aux_abs", ("state", "bins", "accum", "aa", "g2d"))):
         for k in ptrs:
-            _refused(lib, fn(**{k: None}), name)
-        _refused(lib, fn(view=None), name)
-        _refused(lib, fn(view=C.byref(bad)), name)
-        _refused(lib, fn(n=-1), name)
-        _refused(lib, fn(cap=-1), name)
-    _refused(lib, rba(gi=None), "gsplat_rasterize_backward_aux_abs")          # none of the three upstream gradients
+            refused(lib, fn(**{k: None}), name)
+        refused(lib, fn(view=None), name)
+        refused(lib, fn(view=C.byref(bad)), name)
+        refused(lib, fn(n=-1), name)
+        refused(lib, fn(cap=-1), name)
+    refused(lib, rba(gi=None), "gsplat_rasterize_backward_aux_abs")          # none of the three upstream gradients
 
     def ds(n=4, cap=8, view=C.byref(v), state=p, g2d=p, stats=p):
         return lib.gsplat_densify_stats_abs(n, cap, view, state, g2d, stats, None)
 
     name = "gsplat_densify_stats_abs"
     for kw in (dict(state=None), dict(g2d=None), dict(stats=None), dict(view=None), dict(view=C.byref(bad)), dict(n=-1), dict(cap=-1), dict(stats=odd)):
-        _refused(lib, ds(**kw), name)
+        refused(lib, ds(**kw), name)
     assert ds(n=0) == abi.GSPLAT_OK
 
     def fds(n=4, cap=8, view=C.byref(v), frame=None, nbytes=1 << 30, stats=p):
@@ -75,7 +72,7 @@ def test_null_arguments_are_refused_under_the_entrys_own_name():
     aligned = C.c_void_p((p.value + 255) & ~255)
     for kw in (dict(frame=None), dict(frame=aligned, stats=None), dict(frame=aligned, view=None), dict(frame=C.c_void_p(aligned.value + 16)),
                dict(frame=aligned, nbytes=16), dict(frame=aligned, n=-1)):
-        _refused(lib, fds(**kw), name)
+        refused(lib, fds(**kw), name)
     del buf
 
 

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from tests import aux_loss_oracle as alo
+from tests.abi_checks import refused
 
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
 abi = importlib.import_module(PKG + "._abi")
@@ -154,11 +155,6 @@ def _host_words(n=16):
     return buf, C.cast(buf, C.c_void_p)
 
 
-def _refused(lib, status, name):
-    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, status)
-    assert name.encode() in lib.gsplat_last_error(), (name, lib.gsplat_last_error())
-
-
 def test_aux_entries_reject_bad_arguments_on_the_host():
     """A NULL required pointer, H, W or batch <= 0 and batch > 65535 come back as GSPLAT_ERR_BAD_ARG with a message naming the entry.
     Required: alpha, values / grad_alpha, scratch; depth (and grad_depth in the backward) once a target depth is given."""
@@ -179,9 +175,9 @@ def test_aux_entries_reject_bad_arguments_on_the_host():
                                (bwd, "gsplat_aux_loss_backward", ("alpha", "galpha", "scratch", "depth", "gdepth")),
                                (comp, "gsplat_composite_target", ("rgb", "alpha", "background", "out"))):
         for arg in required:
-            _refused(lib, fn(**{arg: None}), name)
+            refused(lib, fn(**{arg: None}), name)
         for bad in (dict(H=0), dict(H=-3), dict(W=0), dict(W=-1), dict(batch=0), dict(batch=-2), dict(batch=65536), dict(batch=1 << 40)):
-            _refused(lib, fn(**bad), name)
+            refused(lib, fn(**bad), name)
     del keep
 
 

@@ -3,18 +3,17 @@ is still 12; every bad argument comes back as GSPLAT_ERR_BAD_ARG naming the entr
 against the layout in the source; the host build of the per-pixel functions against the oracle within bounds counted from the header's
 chain, the identity bit for bit; what TrainConfig / Trainer refuse; the data-parallel helper over gloo; no CPU fallback."""
 import ctypes as C
-import datetime
 import importlib
 import os
-import re
-import socket
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import bilagrid_oracle as bo
+from tests.abi_checks import check_entries, header_defines, refused
+from tests.ranks import run_ranks
+from tests.util import zero_model
 
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,31 +34,8 @@ PIXEL_DEPTH, IMAGE_GRAD_DEPTH, TERM_DEPTH, COORD_DEPTH = 9, 14, 7, 4
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------------
 def test_header_mirror_and_library_agree_and_the_version_stays_12():
-    header = open(os.path.join(ROOT, "include", "gsplat_mi355x.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    for name, n_args in ENTRIES.items():
-        m = re.search(rf"\b(?:int|int64_t)\s+{name}\s*\(([^)]*)\)\s*;", txt)
-        assert m, f"{name} is not declared in include/gsplat_mi355x.h"
-        assert len(m.group(1).split(",")) == n_args, name
-        assert name in abi.SIGNATURES and len(abi.SIGNATURES[name][1]) == n_args, name
-    assert re.search(r"^#define\s+GSPLAT_ABI_VERSION\s+12\s*$", header, flags=re.M) and abi.ABI_VERSION == 12
-    flag = re.search(r"^#define\s+GSPLAT_BILAGRID_ACCUMULATE\s+(\d+)\s*$", header, flags=re.M)
-    assert int(flag.group(1)) == abi.GSPLAT_BILAGRID_ACCUMULATE == 1
-    lib = abi.lib()
-    assert lib.gsplat_abi_version() == 12
-    out = subprocess.run(["nm", "-D", "--defined-only", abi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TtWw"}
-    assert set(ENTRIES) <= exported
-    stray = [f for f in exported if "bilagrid" in f and f not in ENTRIES and not f.startswith(("_ZN", "__hip"))]
-    assert not stray, f"helpers of the bilateral-grid entries exported: {stray}"
-
-
-def _refused(lib, status, name, word=None):
-    msg = lib.gsplat_last_error()
-    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, word, status)
-    assert name.encode() + b":" in msg, (name, msg)
-    if word is not None:
-        assert word.encode() in msg, (name, word, msg)
+    check_entries(ENTRIES, family="bilagrid", stubs_in_namespace=True)
+    assert header_defines()["GSPLAT_BILAGRID_ACCUMULATE"] == abi.GSPLAT_BILAGRID_ACCUMULATE == 1
 
 
 def test_entries_refuse_bad_arguments_on_the_host():
@@ -81,30 +57,30 @@ def test_entries_refuse_bad_arguments_on_the_host():
     grid_shapes = (dict(X=1), dict(X=0), dict(X=-5), dict(X=65), dict(Y=1), dict(Y=65), dict(Y=-1), dict(L=1), dict(L=0), dict(L=17), dict(L=-2))
     shapes = (dict(H=0), dict(H=-3), dict(H=(1 << 20) + 1), dict(W=0), dict(W=-1), dict(W=1 << 21), dict(H=1 << 16, W=1 << 16), dict(batch=0), dict(batch=-2), dict(batch=65536), dict(batch=1 << 40)) + grid_shapes
     for arg in ("image", "grids", "out"):
-        _refused(lib, fwd(**{arg: None}), "gsplat_bilagrid_forward", arg + " is NULL")
+        refused(lib, fwd(**{arg: None}), "gsplat_bilagrid_forward", arg + " is NULL")
     for bad in shapes:
-        _refused(lib, fwd(**bad), "gsplat_bilagrid_forward", next(iter(bad)))
+        refused(lib, fwd(**bad), "gsplat_bilagrid_forward", next(iter(bad)))
     for arg in ("image", "grids", "grad_out"):
-        _refused(lib, bwd(**{arg: None}), "gsplat_bilagrid_backward", arg + " is NULL")
+        refused(lib, bwd(**{arg: None}), "gsplat_bilagrid_backward", arg + " is NULL")
     for bad in shapes:
-        _refused(lib, bwd(**bad), "gsplat_bilagrid_backward", next(iter(bad)))
-    _refused(lib, tv(grids=None), "gsplat_bilagrid_tv", "grids is NULL")
-    _refused(lib, tv(scratch=None), "gsplat_bilagrid_tv", "scratch is NULL")
+        refused(lib, bwd(**bad), "gsplat_bilagrid_backward", next(iter(bad)))
+    refused(lib, tv(grids=None), "gsplat_bilagrid_tv", "grids is NULL")
+    refused(lib, tv(scratch=None), "gsplat_bilagrid_tv", "scratch is NULL")
     for bad in (dict(V=0), dict(V=-1), dict(V=1 << 40)) + grid_shapes:
-        _refused(lib, tv(**bad), "gsplat_bilagrid_tv", next(iter(bad)))
+        refused(lib, tv(**bad), "gsplat_bilagrid_tv", next(iter(bad)))
     for flags in (2, 4, 1 << 5, 3, -2, 1 << 30):
-        _refused(lib, bwd(flags=flags), "gsplat_bilagrid_backward", "unknown flag")
-        _refused(lib, bwd(flags=flags, image=None, H=0), "gsplat_bilagrid_backward", "unknown flag")      # refused FIRST
-        _refused(lib, tv(flags=flags, grids=None), "gsplat_bilagrid_tv", "unknown flag")
+        refused(lib, bwd(flags=flags), "gsplat_bilagrid_backward", "unknown flag")
+        refused(lib, bwd(flags=flags, image=None, H=0), "gsplat_bilagrid_backward", "unknown flag")      # refused FIRST
+        refused(lib, tv(flags=flags, grids=None), "gsplat_bilagrid_tv", "unknown flag")
     # the defined bit with the same bad arguments gets as far as the argument checks
-    _refused(lib, bwd(flags=abi.GSPLAT_BILAGRID_ACCUMULATE, image=None), "gsplat_bilagrid_backward", "image is NULL")
+    refused(lib, bwd(flags=abi.GSPLAT_BILAGRID_ACCUMULATE, image=None), "gsplat_bilagrid_backward", "image is NULL")
     # nothing asked for: nothing to do, nothing launched (and no scratch needed without a loss)
     assert bwd(grad_image=None, grad_grids=None) == abi.GSPLAT_OK
     assert tv(loss_out=None, grad=None, scratch=None) == abi.GSPLAT_OK
     odd = C.c_void_p(p.value + 2)
-    _refused(lib, fwd(image=odd), "gsplat_bilagrid_forward", "aligned")
-    _refused(lib, bwd(grad_out=odd), "gsplat_bilagrid_backward", "aligned")
-    _refused(lib, tv(scratch=C.c_void_p(p.value + 4)), "gsplat_bilagrid_tv", "aligned")
+    refused(lib, fwd(image=odd), "gsplat_bilagrid_forward", "aligned")
+    refused(lib, bwd(grad_out=odd), "gsplat_bilagrid_backward", "aligned")
+    refused(lib, tv(scratch=C.c_void_p(p.value + 4)), "gsplat_bilagrid_tv", "aligned")
     del buf
 
 
@@ -215,12 +191,6 @@ def test_host_tv_matches_the_oracle(host):
 
 
 # ---- TrainConfig / Trainer ---------------------------------------------------------------------------------------------------------
-def _model():
-    model_mod = importlib.import_module(PKG + ".model")
-    z = torch.zeros
-    return model_mod.GaussianModel(dict(pos=z(4, 3), f_dc=z(4, 3), f_rest=z(4, 45), opacity_raw=z(4), scale_raw=z(4, 3), q_raw=z(4, 4)), device="cpu")
-
-
 VIEWS = [dict(c2w=torch.eye(4), H=8, W=8, fx=10.0, fy=10.0, cx=4.0, cy=4.0, image=torch.zeros(8, 8, 3), idx=k) for k in range(3)]
 
 
@@ -229,14 +199,14 @@ def test_the_mode_is_off_by_default_and_a_trainer_with_it_has_a_table(gs):
     c = training.TrainConfig()
     assert (c.bilagrid, tuple(c.bilagrid_shape), c.bilagrid_tv) == (False, (16, 16, 8), 10.0)
     assert (c.bilagrid_lr_init, c.bilagrid_lr_final, c.bilagrid_lr_delay_mult, c.bilagrid_lr_max_steps) == (0.002, 0.00002, 0.0, 30000)
-    assert training.Trainer(_model()).bilagrid is None
-    assert training.Trainer(_model(), training.TrainConfig(), None, cameras=VIEWS, bilagrid_views=7).bilagrid is None
-    tr = training.Trainer(_model(), training.TrainConfig(bilagrid=True), cameras=VIEWS)              # (the constructor launches nothing)
+    assert training.Trainer(zero_model()).bilagrid is None
+    assert training.Trainer(zero_model(), training.TrainConfig(), None, cameras=VIEWS, bilagrid_views=7).bilagrid is None
+    tr = training.Trainer(zero_model(), training.TrainConfig(bilagrid=True), cameras=VIEWS)              # (the constructor launches nothing)
     assert isinstance(tr.bilagrid, gs.bilagrid.BilateralGridTable) and tuple(tr.bilagrid.params.shape) == (3, 12, 8, 16, 16)
     assert tr.exposure is None
     assert torch.equal(tr.bilagrid.params, torch.tensor(bo.identity(3, (16, 16, 8)), dtype=torch.float32)) and not tr.bilagrid.grad.any()
     assert tr.bilagrid.optimizer.eps == 1e-15 and tr.bilagrid.optimizer is not tr.optimizer
-    tr = training.Trainer(_model(), training.TrainConfig(bilagrid=True, bilagrid_shape=(3, 5, 4)), cameras=VIEWS, bilagrid_views=5)
+    tr = training.Trainer(zero_model(), training.TrainConfig(bilagrid=True, bilagrid_shape=(3, 5, 4)), cameras=VIEWS, bilagrid_views=5)
     assert tuple(tr.bilagrid.params.shape) == (5, 12, 4, 5, 3) and tr.bilagrid.shape == (3, 5, 4)
     sd = tr.bilagrid.state_dict()
     assert set(sd) == {"params", "exp_avg", "exp_avg_sq", "step"} and sd["step"] == 0
@@ -256,7 +226,7 @@ def test_trainer_refuses_a_bilagrid_that_is_not_a_bool(value):
     cfg = training.TrainConfig()
     cfg.bilagrid = value                                                 # (the fields of a config can be set after it is made)
     with pytest.raises(ValueError, match="bilagrid must be a bool"):
-        training.Trainer(_model(), cfg, cameras=VIEWS)
+        training.Trainer(zero_model(), cfg, cameras=VIEWS)
 
 
 @pytest.mark.parametrize("shape", [(16, 16), (1, 16, 8), (16, 65, 8), (16, 16, 17), (16, 16, 1), (16.0, 16, 8), (True, 16, 8), "16x16x8", None, 8])
@@ -271,26 +241,26 @@ def test_a_bad_shape_is_refused(gs, shape):
 def test_trainer_refuses_the_mode_without_a_number_of_images_or_beside_exposure():
     training = importlib.import_module(PKG + ".training")
     with pytest.raises(ValueError, match="bilagrid_views"):
-        training.Trainer(_model(), training.TrainConfig(bilagrid=True))
+        training.Trainer(zero_model(), training.TrainConfig(bilagrid=True))
     for bad in (0, -1, 2.0, True):
         with pytest.raises(ValueError, match="n_views"):
-            training.Trainer(_model(), training.TrainConfig(bilagrid=True), bilagrid_views=bad)
+            training.Trainer(zero_model(), training.TrainConfig(bilagrid=True), bilagrid_views=bad)
     with pytest.raises(ValueError, match="not available with exposure=True"):
         training.TrainConfig(bilagrid=True, exposure=True)
     for name, bad in (("bilagrid_tv", -1.0), ("bilagrid_tv", float("nan")), ("bilagrid_lr_init", True), ("bilagrid_lr_max_steps", 0)):
         with pytest.raises(ValueError, match=name):
-            training.Trainer(_model(), training.TrainConfig(bilagrid=True, **{name: bad}), cameras=VIEWS)
+            training.Trainer(zero_model(), training.TrainConfig(bilagrid=True, **{name: bad}), cameras=VIEWS)
     # the checks keep their order: the exposure section's own messages still come first
     with pytest.raises(ValueError, match="exposure must be a bool"):
         training.TrainConfig(exposure=1, bilagrid=1)
     with pytest.raises(ValueError, match="exposure=True needs the number"):
-        training.Trainer(_model(), training.TrainConfig(exposure=True, bilagrid_tv=-1.0))
+        training.Trainer(zero_model(), training.TrainConfig(exposure=True, bilagrid_tv=-1.0))
 
 
 @pytest.mark.parametrize("idx", ["missing", None, -1, 3, 1.0, True, "0"])
 def test_step_refuses_a_view_without_a_valid_idx_before_anything_is_queued(idx):
     training = importlib.import_module(PKG + ".training")
-    tr = training.Trainer(_model(), training.TrainConfig(bilagrid=True), cameras=VIEWS)
+    tr = training.Trainer(zero_model(), training.TrainConfig(bilagrid=True), cameras=VIEWS)
     view = dict(VIEWS[0])
     if idx == "missing":
         del view["idx"]
@@ -321,12 +291,6 @@ def test_ops_have_no_cpu_fallback(gs):
 
 
 # ---- the data-parallel helper ----------------------------------------------------------------------------------------------------
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def _rank_rows(rank, n_views=5):
     """The gradient a rank's views leave: rank 0 used rows 0 and 3, rank 1 rows 1 and 3 (row 3 is shared), the rest are zero."""
     g = torch.Generator().manual_seed(80 + rank)
@@ -336,36 +300,21 @@ def _rank_rows(rank, n_views=5):
     return grad
 
 
-def _worker(rank, world, port, q):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _worker(rank, world):
     dp = importlib.import_module(PKG + ".dp")
     grad = _rank_rows(rank)
     assert dp.allreduce_table_grad(grad) is grad
-    q.put((rank, grad.numpy().copy()))
-    dist.barrier()
-    dist.destroy_process_group()
+    return grad.numpy().copy()
 
 
 def test_allreduce_table_grad_over_gloo_gives_the_bits_of_one_process():
-    import torch.multiprocessing as mp
     dp = importlib.import_module(PKG + ".dp")
     alone = _rank_rows(0)
     assert dp.allreduce_table_grad(alone) is alone and torch.equal(alone, _rank_rows(0))      # a single process: nothing happens
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=120) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    got = run_ranks(_worker, 2, answer_s=120, join_s=60)
     a, b = _rank_rows(0), _rank_rows(1)
     want = a.clone()                     # one process given both ranks' views: rank 0's rows, then rank 1's added in view order
     want += b
     assert torch.equal(want[0], a[0]) and torch.equal(want[1], b[1]) and not want[2].any() and not want[4].any()
-    for rank, grad in got:
+    for rank, grad in enumerate(got):
         assert np.array_equal(grad.view(np.uint32), want.numpy().view(np.uint32)), rank

@@ -3,41 +3,18 @@ them, the built library exports them and nothing stray, the ABI version is still
 GSPLAT_ERR_BAD_ARG with the entry's name in gsplat_last_error() before anything is launched."""
 import ctypes as C
 import importlib
-import os
-import re
-import subprocess
+
+from tests.abi_checks import check_entries, header_text, refused
 
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 abi = importlib.import_module(PKG + "._abi")
 ENTRIES = ("gsplat_contribution", "gsplat_frame_contribution")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "gsplat_mi355x.h")).read()
-
-
-def _refused(lib, status, name):
-    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, status)
-    assert name.encode() in lib.gsplat_last_error(), (name, lib.gsplat_last_error())
-
-
 def test_header_mirror_and_library_agree_and_the_version_stays_12():
-    txt = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    for name in ENTRIES:
-        m = re.search(rf"\bint\s+{name}\s*\(([^)]*)\)\s*;", txt)
-        assert m, f"{name} is not declared in include/gsplat_mi355x.h"
-        assert len(m.group(1).split(",")) == 7 and "uint32_t* record" in m.group(1)
-        assert name in abi.SIGNATURES and len(abi.SIGNATURES[name][1]) == 7
-    assert "gsplat_contribution_scratch_bytes" not in txt          # the flush needs no scratch
-    assert re.search(r"^#define\s+GSPLAT_ABI_VERSION\s+12\s*$", _header(), flags=re.M) and abi.ABI_VERSION == 12
-    lib = abi.lib()
-    assert lib.gsplat_abi_version() == 12
-    out = subprocess.run(["nm", "-D", "--defined-only", abi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TtWw"}
-    assert set(ENTRIES) <= exported
-    stray = [f for f in exported if "contrib" in f and f not in ENTRIES]
-    assert not stray, f"helpers of the contribution entries exported: {stray}"
+    params = check_entries(dict.fromkeys(ENTRIES, 7), family="contrib", returns=("int",))
+    assert all("uint32_t* record" in p for p in params.values())
+    assert "gsplat_contribution_scratch_bytes" not in header_text()          # the flush needs no scratch
 
 
 def test_entries_refuse_bad_arguments_on_the_host():
@@ -51,7 +28,7 @@ def test_entries_refuse_bad_arguments_on_the_host():
     for status in (f(4, 16, None, p, p, p, None), f(4, 16, C.byref(bad_view), p, p, p, None), f(-1, 16, C.byref(v), p, p, p, None),
                    f(4, -1, C.byref(v), p, p, p, None), f(4, 16, C.byref(v), None, p, p, None), f(4, 16, C.byref(v), p, None, p, None),
                    f(4, 16, C.byref(v), p, p, None, None), f(4, 16, C.byref(v), p, p, odd, None), f(1 << 40, 16, C.byref(v), p, p, p, None)):
-        _refused(lib, status, name)
+        refused(lib, status, name)
     assert f(0, 16, C.byref(v), p, p, p, None) == abi.GSPLAT_OK
     name, f = "gsplat_frame_contribution", lib.gsplat_frame_contribution
     need = lib.gsplat_frame_bytes(4, 16, C.byref(v), 0)
@@ -59,6 +36,6 @@ def test_entries_refuse_bad_arguments_on_the_host():
     for status in (f(4, 16, None, p, need, p, None), f(4, 16, C.byref(bad_view), p, need, p, None), f(-1, 16, C.byref(v), p, need, p, None),
                    f(4, -1, C.byref(v), p, need, p, None), f(4, 16, C.byref(v), None, need, p, None), f(4, 16, C.byref(v), p, need, None, None),
                    f(4, 16, C.byref(v), odd, need, p, None), f(4, 16, C.byref(v), p, need - 1, p, None), f(4, 16, C.byref(v), p, need, odd, None)):
-        _refused(lib, status, name)
+        refused(lib, status, name)
     assert f(0, 16, C.byref(v), p, lib.gsplat_frame_bytes(0, 16, C.byref(v), 0), p, None) == abi.GSPLAT_OK
     del buf

@@ -1,15 +1,12 @@
 """ops.ContributionStats and GaussianModel.prune_by_contribution on the CPU: the accessors on hand-written words, merge_,
 all_reduce over two gloo ranks (identical bits on both), and the two pruning rules on hand-made records."""
-import datetime
 import importlib
-import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from tests.ranks import run_ranks
 
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
 ops = importlib.import_module(PKG + ".ops")
@@ -63,14 +60,6 @@ def test_merge_adds_takes_the_maximum_and_adds():
             a.merge_(other)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _rank_record(rank, n=257):
     g = torch.Generator().manual_seed(60 + rank)
     st = ops.ContributionStats(n, "cpu")
@@ -82,27 +71,14 @@ def _rank_record(rank, n=257):
     return st
 
 
-def _worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _worker(rank, world):
     st = _rank_record(rank)
     st.all_reduce()
-    q.put((rank, st.data.numpy().copy(), st.frames))
-    dist.barrier()
-    dist.destroy_process_group()
+    return st.data.numpy().copy(), st.frames
 
 
 def test_all_reduce_over_gloo_world2():
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = {r: (d, f) for r, d, f in (q.get(timeout=120) for _ in range(world))}
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    got = run_ranks(_worker, 2, answer_s=120, join_s=60)
     want = _rank_record(0).merge_(_rank_record(1))
     assert np.array_equal(got[0][0], want.data.numpy()) and got[0][1] == want.frames == 7
     assert got[0][0].tobytes() == got[1][0].tobytes() and got[1][1] == 7
@@ -189,9 +165,7 @@ def test_contribution_refuses_a_record_that_does_not_fit_before_anything_is_queu
 
 # ---- Trainer.prune_by_contribution over two gloo ranks, the GPU call stubbed ------------------------------------------------------------
 
-def _trainer_worker(rank, world, port, q, fail):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _trainer_worker(rank, world, fail):
     m, _ = _model(8)
     tr = training.Trainer(m, training.TrainConfig())
 
@@ -207,25 +181,14 @@ def _trainer_worker(rank, world, port, q, fail):
     view = dict(c2w=torch.eye(4), H=16, W=16, fx=10.0, fy=10.0, cx=8.0, cy=8.0)
     try:
         out = tr.prune_by_contribution(1, [view] * (rank + 1), min_weight_max=0.2)
-        q.put((rank, "ok", out, m.pos.detach().numpy().copy()))
+        return "ok", out, m.pos.detach().numpy().copy()
     except Exception as e:
-        q.put((rank, "raised", str(e), m.get_num_gaussians()))
-    dist.barrier()
-    dist.destroy_process_group()
+        return "raised", str(e), m.get_num_gaussians()
 
 
 @pytest.mark.parametrize("fail", [False, True], ids=["all_ranks_good", "one_rank_off_screen"])
 def test_trainer_prune_is_collective_over_gloo(fail):
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_trainer_worker, args=(r, world, port, q, fail)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = {r: rest for r, *rest in (q.get(timeout=120) for _ in range(world))}
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    got = run_ranks(_trainer_worker, 2, fail, answer_s=120, join_s=60)
     if fail:           # every rank raises, the failing one its own exception, and nothing is pruned anywhere
         assert got[0][0] == got[1][0] == "raised" and got[0][2] == got[1][2] == 8
         assert got[1][1] == ops.OFFSCREEN_MSG and got[0][1].startswith(ops.OFFSCREEN_MSG) and "another rank" in got[0][1]

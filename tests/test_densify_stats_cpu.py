@@ -2,30 +2,23 @@
 arguments on the host, ops.densify_stats refuses a record that does not fit, GaussianModel.densify_and_prune_screen on hand-made
 tensors and against densify_and_prune, DensifyStats.all_reduce over gloo, and the oracle helper in float32 against float64."""
 import ctypes as C
-import datetime
 import importlib
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from tests import densify_stats_oracle as dso
 from tests import util
+from tests.abi_checks import refused
+from tests.ranks import run_ranks
 
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
 abi = importlib.import_module(PKG + "._abi")
 ops = importlib.import_module(PKG + ".ops")
 model_mod = importlib.import_module(PKG + ".model")
 KEYS = ("pos", "opacity_raw", "f_dc", "f_rest", "scale_raw", "q_raw")
-
-
-def _refused(lib, status, name):
-    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, status)
-    assert name.encode() in lib.gsplat_last_error(), (name, lib.gsplat_last_error())
 
 
 def test_entries_refuse_bad_arguments_on_the_host():
@@ -42,7 +35,7 @@ def test_entries_refuse_bad_arguments_on_the_host():
                    lib.gsplat_densify_stats(-1, 16, C.byref(v), p, p, p, None), lib.gsplat_densify_stats(4, -1, C.byref(v), p, p, p, None),
                    lib.gsplat_densify_stats(4, 16, C.byref(v), None, p, p, None), lib.gsplat_densify_stats(4, 16, C.byref(v), p, None, p, None),
                    lib.gsplat_densify_stats(4, 16, C.byref(v), p, p, None, None), lib.gsplat_densify_stats(4, 16, C.byref(v), p, p, odd, None)):
-        _refused(lib, status, name)
+        refused(lib, status, name)
     assert lib.gsplat_densify_stats(0, 16, C.byref(v), p, p, p, None) == abi.GSPLAT_OK
     name = "gsplat_frame_densify_stats"
     need = lib.gsplat_frame_bytes(4, 16, C.byref(v), abi.GSPLAT_FRAME_BACKWARD)
@@ -54,7 +47,7 @@ def test_entries_refuse_bad_arguments_on_the_host():
                    lib.gsplat_frame_densify_stats(4, 16, C.byref(v), p, need - 1, p, None),
                    lib.gsplat_frame_densify_stats(4, 16, C.byref(v), p, forward_only, p, None),          # a frame without the backward parts
                    lib.gsplat_frame_densify_stats(4, 16, C.byref(v), p, need, odd, None)):
-        _refused(lib, status, name)
+        refused(lib, status, name)
     assert lib.gsplat_frame_densify_stats(0, 16, C.byref(v), p, lib.gsplat_frame_bytes(0, 16, C.byref(v), abi.GSPLAT_FRAME_BACKWARD), p,
                                           None) == abi.GSPLAT_OK
     name = "gsplat_densify_stats_merge"
@@ -62,7 +55,7 @@ def test_entries_refuse_bad_arguments_on_the_host():
     for status in (lib.gsplat_densify_stats_merge(-1, p, q, None), lib.gsplat_densify_stats_merge(4, None, q, None),
                    lib.gsplat_densify_stats_merge(4, p, None, None), lib.gsplat_densify_stats_merge(4, p, p, None),
                    lib.gsplat_densify_stats_merge(4, odd, q, None)):
-        _refused(lib, status, name)
+        refused(lib, status, name)
     assert lib.gsplat_densify_stats_merge(0, p, q, None) == abi.GSPLAT_OK
     del buf
 
@@ -176,14 +169,6 @@ def test_screen_rule_with_the_reference_mask_is_bit_identical_to_densify_and_pru
         assert b.get_num_gaussians() == gold[f"{case}_pos"].shape[0]
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _rank_record(rank, n=257):
     g = torch.Generator().manual_seed(40 + rank)
     st = ops.DensifyStats(n, "cpu")
@@ -193,27 +178,14 @@ def _rank_record(rank, n=257):
     return st
 
 
-def _worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _worker(rank, world):
     st = _rank_record(rank)
     st.all_reduce()
-    q.put((rank, st.data.numpy().copy()))
-    dist.barrier()
-    dist.destroy_process_group()
+    return st.data.numpy().copy()
 
 
 def test_all_reduce_over_gloo_world2():
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=120) for _ in range(world))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    got = run_ranks(_worker, 2, answer_s=120, join_s=60)
     a, b = _rank_record(0).data, _rank_record(1).data
     want = torch.stack([a[:, 0] + b[:, 0], a[:, 1] + b[:, 1], torch.maximum(a[:, 2], b[:, 2]), torch.zeros(257)], 1).numpy()
     assert np.array_equal(got[0], want)

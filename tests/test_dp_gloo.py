@@ -1,24 +1,13 @@
 """Data-parallel-by-view helper on CPU: world_size 2 over gloo (the GPU path uses the same code over RCCL)."""
-import datetime
 import importlib
-import os
-import socket
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from tests.ranks import run_ranks
 
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
 SHAPES = {"pos": (257, 3), "opacity_raw": (257,), "f_dc": (257, 3), "f_rest": (257, 45), "scale_raw": (257, 3), "q_raw": (257, 4)}
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _grads(rank):
@@ -26,9 +15,7 @@ def _grads(rank):
     return [torch.randn(*shape, generator=g) for shape in SHAPES.values()]
 
 
-def _worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _worker(rank, world):
     dp = importlib.import_module(PKG + ".dp")
     grads = _grads(rank)
     dp.allreduce_gradients(grads, world_views=world)
@@ -49,25 +36,15 @@ def _worker(rank, world, port, q):
     def render(p, v):
         return sum((t * (v + 1)).sum() for t in p.values())
     dp.data_parallel_step(render, params, views, lambda img, v: img, world_views=4)
-    q.put((rank, [g.numpy().copy() for g in grads], {k: p.grad.numpy().copy() for k, p in params.items()}, views))
-    dist.barrier()
-    dist.destroy_process_group()
+    return [g.numpy().copy() for g in grads], {k: p.grad.numpy().copy() for k, p in params.items()}, views
 
 
 def test_allreduce_gradients_world2():
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=120) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    world = 2
+    got = run_ranks(_worker, world, answer_s=120, join_s=60)
     expect = [(a + b) / world for a, b in zip(_grads(0), _grads(1))]
     views_seen = []
-    for rank, grads, pg, views in got:
+    for grads, pg, views in got:
         for g, e in zip(grads, expect):
             assert torch.allclose(torch.from_numpy(g), e, atol=1e-6)
         # views 0..3 have weights 1..4; d/dp sum_v (v+1) * p / 4 views = 10 / 4
@@ -107,9 +84,7 @@ def _factored_inputs(rank, n=257, views=None):
     return logits, eyes, small
 
 
-def _factored_worker(rank, world, port, q, even=False):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _factored_worker(rank, world, even=False):
     dp = importlib.import_module(PKG + ".dp")
     pos = torch.randn(257, 3, generator=torch.Generator().manual_seed(7))          # replicated parameters
     params = {k: torch.zeros(*s, requires_grad=True) for k, s in SHAPES.items()}
@@ -122,25 +97,15 @@ def _factored_worker(rank, world, port, q, even=False):
     for gl, e in zip(logits, eyes):              # ... and what it hands to the sink, one entry per view
         ex.add(gl, e)
     ex.finish()
-    q.put((rank, {k: p.grad.numpy().copy() for k, p in params.items()}))
-    dist.barrier()
-    dist.destroy_process_group()
+    return {k: p.grad.numpy().copy() for k, p in params.items()}
 
 
 @pytest.mark.parametrize("even", [False, True])
 def test_factored_exchange_world2(even):
     """The factored exchange (all-reduce of 44 B + all-gather of the logit gradients + local rebuild) gives every rank the
     gradients the plain all-reduce of all six tensors would give."""
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_factored_worker, args=(r, world, port, q, even)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=120) for _ in range(world))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    world = 2
+    got = run_ranks(_factored_worker, world, even, answer_s=120, join_s=60)
     pos = torch.randn(257, 3, generator=torch.Generator().manual_seed(7))
     ins = [_factored_inputs(r, views=2 if even else None) for r in range(world)]
     nv = 4 if even else 5
@@ -157,9 +122,7 @@ def test_factored_exchange_world2(even):
     assert all((got[0][k] == got[1][k]).all() for k in SHAPES)          # replicas stay bit-identical
 
 
-def _uneven3_worker(rank, world, port, q, given):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _uneven3_worker(rank, world, given):
     dp = importlib.import_module(PKG + ".dp")
     counts = (2, 1, 3)
     # what Trainer.step does first: every rank must come out with the same (equal, n_global)
@@ -174,26 +137,16 @@ def _uneven3_worker(rank, world, port, q, given):
     for gl, e in zip(logits, eyes):
         ex.add(gl, e)
     ex.finish()
-    q.put((rank, even, n_global, {k: p.grad.numpy().copy() for k, p in params.items()}))
-    dist.barrier()
-    dist.destroy_process_group()
+    return even, n_global, {k: p.grad.numpy().copy() for k, p in params.items()}
 
 
 @pytest.mark.parametrize("given", [False, True])
 def test_three_ranks_with_2_1_3_views_agree_on_the_exchange(given):
     """Rank 0 alone would see 2 * 3 == 6 views and take the equal-views path while ranks 1 and 2 take the other one (the
     collectives then mismatch and the step hangs): the decision is made from ALL ranks' counts (exchanged, or given)."""
-    world, port = 3, _free_port()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_uneven3_worker, args=(r, world, port, q, given)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = {r: (e, n, g) for r, e, n, g in (q.get(timeout=120) for _ in range(world))}
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    assert all(e is False and n == 6 for e, n, _ in got.values())
+    world = 3
+    got = run_ranks(_uneven3_worker, world, given, answer_s=120, join_s=60)
+    assert all(e is False and n == 6 for e, n, _ in got)
     pos = torch.randn(257, 3, generator=torch.Generator().manual_seed(7))
     ins = [_factored_inputs(r, views=c) for r, c in enumerate((2, 1, 3))]
     all_logits = torch.stack([gl for logits, _, _ in ins for gl in logits])
@@ -228,9 +181,7 @@ def test_gradient_routes_do_not_nest():
 
 
 # ---- Trainer.step: one agreement per pass, whatever happens on a rank (host logic; the renderer is a toy: the HIP op needs a GPU) ----
-def _toy_trainer_worker(rank, world, port, q, mode):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _toy_trainer_worker(rank, world, mode):
     ops = importlib.import_module(PKG + ".ops")
     training = importlib.import_module(PKG + ".training")
     losses = importlib.import_module(PKG + ".losses")
@@ -308,11 +259,9 @@ def _toy_trainer_worker(rank, world, port, q, mode):
     views = [dict(image=torch.zeros(2, 2, 3), c2w=torch.eye(4), H=2, W=2, fx=1., fy=1., cx=1., cy=1.) for _ in range(2)]
     try:
         tr.step(1, views)
-        q.put((rank, "ok", "", calls["render"], {k: p.grad.numpy().copy() for k, p in model.get_params().items()}))
+        return "ok", "", calls["render"], {k: p.grad.numpy().copy() for k, p in model.get_params().items()}
     except Exception as e:
-        q.put((rank, type(e).__name__, str(e), calls["render"], None))
-    dist.barrier()
-    dist.destroy_process_group()
+        return type(e).__name__, str(e), calls["render"], None
 
 
 @pytest.mark.parametrize("mode", ["verify_offscreen", "render_raises", "other_error", "redo_once", "fine"])
@@ -320,19 +269,7 @@ def test_trainer_step_agrees_on_the_outcome_of_a_routed_pass(mode):
     """One rank's view has survivors but nothing on screen (found in verify(), or by a frame that waited for its counters after one
     of its views' collectives was already issued), or it fails otherwise: EVERY rank raises within the timeout -- nobody is left
     waiting in a collective.  One rank's pair buffers overflowed: both repeat the pass, and the gradients are those of a clean pass."""
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_toy_trainer_worker, args=(r, world, port, q, mode)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = {}
-    for _ in range(world):
-        r = q.get(timeout=120)
-        got[r[0]] = r[1:]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    got = run_ranks(_toy_trainer_worker, 2, mode, answer_s=120, join_s=60)
     ops = importlib.import_module(PKG + ".ops")
     if mode in ("verify_offscreen", "render_raises"):
         assert got[1][0] == "Exception" and got[1][1] == ops.OFFSCREEN_MSG                  # the reference's exception, where it happened

@@ -5,45 +5,25 @@ the filter cannot run with and leave it off by default."""
 import ctypes as C
 import dataclasses
 import importlib
-import os
 import re
-import subprocess
 
 import pytest
 import torch
 
+from tests.abi_checks import check_entries, header_defines, header_text, refused
+from tests.util import zero_model
+
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 abi = importlib.import_module(PKG + "._abi")
 ENTRIES = {"gsplat_filter3d_scratch_bytes": 1, "gsplat_filter3d_compute": 10, "gsplat_filter3d_apply": 7, "gsplat_filter3d_apply_backward": 10}
 
 
-def _refused(lib, status, name, arg):
-    msg = lib.gsplat_last_error()
-    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, arg, status)
-    assert name.encode() + b":" in msg and arg.encode() in msg, (name, arg, msg)
-
-
 def test_header_mirror_and_library_agree_and_the_version_stays_12():
-    header = open(os.path.join(ROOT, "include", "gsplat_mi355x.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    for name, n_args in ENTRIES.items():
-        m = re.search(rf"\b(?:int|int64_t)\s+{name}\s*\(([^)]*)\)\s*;", txt)
-        assert m, f"{name} is not declared in include/gsplat_mi355x.h"
-        assert len(m.group(1).split(",")) == n_args, name
-        assert name in abi.SIGNATURES and len(abi.SIGNATURES[name][1]) == n_args, name
-    assert re.search(r"^#define\s+GSPLAT_ABI_VERSION\s+12\s*$", header, flags=re.M) and abi.ABI_VERSION == 12
-    assert not re.search(r"^#define\s+GSPLAT_PROJECT_\w*FILTER3D", header, flags=re.M)
-    floats = re.search(r"^#define\s+GSPLAT_FILTER3D_CAMERA_FLOATS\s+(\d+)\s*$", header, flags=re.M)
-    chunk = re.search(r"^#define\s+GSPLAT_FILTER3D_CAMERA_CHUNK\s+(\d+)\s*$", header, flags=re.M)
-    assert int(floats.group(1)) == abi.GSPLAT_FILTER3D_CAMERA_FLOATS >= 18 and int(chunk.group(1)) == abi.GSPLAT_FILTER3D_CAMERA_CHUNK >= 1
-    lib = abi.lib()
-    assert lib.gsplat_abi_version() == 12
-    out = subprocess.run(["nm", "-D", "--defined-only", abi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TtWw"}
-    assert set(ENTRIES) <= exported
-    stray = [f for f in exported if "filter3d" in f and f not in ENTRIES]
-    assert not stray, f"helpers of the filter3d entries exported: {stray}"
+    check_entries(ENTRIES, family="filter3d")
+    defs = header_defines()
+    assert not re.search(r"^#define\s+GSPLAT_PROJECT_\w*FILTER3D", header_text(comments=True), flags=re.M)
+    assert defs["GSPLAT_FILTER3D_CAMERA_FLOATS"] == abi.GSPLAT_FILTER3D_CAMERA_FLOATS >= 18
+    assert defs["GSPLAT_FILTER3D_CAMERA_CHUNK"] == abi.GSPLAT_FILTER3D_CAMERA_CHUNK >= 1
 
 
 def test_scratch_size_is_a_pure_host_function():
@@ -70,10 +50,10 @@ def test_entries_refuse_bad_arguments_on_the_host():
     for arg, bad in ([(k, None) for k in ("pos", "cams", "filt", "scratch")] + [("n", -1), ("n", 2 ** 31), ("n_cams", -1)]
                      + [(k, v) for k in ("near", "margin", "s") for v in (nan, inf, -inf, -0.5)]
                      + [("pos", odd), ("cams", odd), ("filt", odd), ("scratch", C.c_void_p(p.value + 16))]):
-        _refused(lib, compute(**{arg: bad}), name, arg)
+        refused(lib, compute(**{arg: bad}), name, arg)
     assert compute(n=0, pos=None, cams=None, filt=None, scratch=None) == abi.GSPLAT_OK
     assert compute(n=0, n_cams=0, pos=None, cams=None, filt=None, scratch=None) == abi.GSPLAT_OK
-    _refused(lib, compute(n_cams=0, filt=None), name, "filt")                       # no camera still writes filt
+    refused(lib, compute(n_cams=0, filt=None), name, "filt")                       # no camera still writes filt
 
     name, f = "gsplat_filter3d_apply", lib.gsplat_filter3d_apply
     args = ("scale_raw", "opacity_raw", "filt", "scale_out", "opacity_out")
@@ -82,10 +62,10 @@ def test_entries_refuse_bad_arguments_on_the_host():
         return f(n, *[kw.get(k, p) for k in args], None)
 
     for k in args:
-        _refused(lib, apply(**{k: None}), name, k)
-        _refused(lib, apply(**{k: odd}), name, "aligned")
-    _refused(lib, apply(n=-1), name, "n ")
-    _refused(lib, apply(n=2 ** 31), name, "n ")
+        refused(lib, apply(**{k: None}), name, k)
+        refused(lib, apply(**{k: odd}), name, "aligned")
+    refused(lib, apply(n=-1), name, "n ")
+    refused(lib, apply(n=2 ** 31), name, "n ")
     assert f(0, None, None, None, None, None, None) == abi.GSPLAT_OK
 
     name, f = "gsplat_filter3d_apply_backward", lib.gsplat_filter3d_apply_backward
@@ -95,10 +75,10 @@ def test_entries_refuse_bad_arguments_on_the_host():
         return f(n, *[kw.get(k, p) for k in args], accumulate, None)
 
     for k in args:
-        _refused(lib, backward(**{k: None}), name, k)
-        _refused(lib, backward(**{k: odd}, accumulate=1), name, "aligned")
-    _refused(lib, backward(n=-1), name, "n ")
-    _refused(lib, backward(n=2 ** 31), name, "n ")
+        refused(lib, backward(**{k: None}), name, k)
+        refused(lib, backward(**{k: odd}, accumulate=1), name, "aligned")
+    refused(lib, backward(n=-1), name, "n ")
+    refused(lib, backward(n=2 ** 31), name, "n ")
     assert f(0, None, None, None, None, None, None, None, 1, None) == abi.GSPLAT_OK
     del buf
 
@@ -120,12 +100,6 @@ def test_python_side_fails_loudly_without_a_gpu(gs):
         gs.filter3d.pack_cameras([dict(views[0], c2w=torch.eye(3))], "cpu")
 
 
-def _model():
-    model_mod = importlib.import_module(PKG + ".model")
-    z = torch.zeros
-    return model_mod.GaussianModel(dict(pos=z(4, 3), f_dc=z(4, 3), f_rest=z(4, 45), opacity_raw=z(4), scale_raw=z(4, 3), q_raw=z(4, 4)), device="cpu")
-
-
 VIEWS = [dict(c2w=torch.eye(4), H=8, W=8, fx=10.0, fy=10.0, cx=4.0, cy=4.0, image=torch.zeros(8, 8, 3))]
 
 
@@ -133,11 +107,11 @@ def test_the_filter_is_off_by_default_and_a_trainer_with_it_constructs():
     training = importlib.import_module(PKG + ".training")
     c = training.TrainConfig()
     assert (c.filter3d, c.filter3d_interval, c.filter3d_near, c.filter3d_margin) == (0.0, 100, 0.2, 0.15)
-    tr = training.Trainer(_model())
+    tr = training.Trainer(zero_model())
     assert tr.filter3d is None and tr._cameras is None
-    tr = training.Trainer(_model(), training.TrainConfig(), None, cameras=VIEWS)           # cameras without the filter: ignored
+    tr = training.Trainer(zero_model(), training.TrainConfig(), None, cameras=VIEWS)           # cameras without the filter: ignored
     assert tr.filter3d is None and tr._cameras is None
-    tr = training.Trainer(_model(), training.TrainConfig(filter3d=0.2), cameras=VIEWS)     # (the constructor launches nothing)
+    tr = training.Trainer(zero_model(), training.TrainConfig(filter3d=0.2), cameras=VIEWS)     # (the constructor launches nothing)
     assert tr.filter3d is None and tuple(tr._cameras.shape) == (1, 24)
 
 
@@ -153,17 +127,17 @@ def test_trainer_refuses_bad_filter3d_fields(field, value):
     cfg = training.TrainConfig(filter3d=0.2)
     object.__setattr__(cfg, field, value)                                   # (the fields of a config can be set after it is made)
     with pytest.raises(ValueError, match=field):
-        training.Trainer(_model(), cfg, cameras=VIEWS)
+        training.Trainer(zero_model(), cfg, cameras=VIEWS)
 
 
 def test_trainer_refuses_the_filter_without_cameras_and_with_the_mcmc_rule():
     training = importlib.import_module(PKG + ".training")
     with pytest.raises(ValueError, match="cameras"):
-        training.Trainer(_model(), training.TrainConfig(filter3d=0.2))
+        training.Trainer(zero_model(), training.TrainConfig(filter3d=0.2))
     with pytest.raises(ValueError, match="mcmc"):
         training.TrainConfig(filter3d=0.2, densify_rule="mcmc")
     cfg = dataclasses.replace(training.TrainConfig(densify_rule="mcmc"))
     cfg.filter3d = 0.2
     with pytest.raises(ValueError, match="mcmc"):
-        training.Trainer(_model(), cfg, cameras=VIEWS)
-    training.Trainer(_model(), training.TrainConfig(densify_rule="mcmc"), cameras=VIEWS)   # the rule alone is fine
+        training.Trainer(zero_model(), cfg, cameras=VIEWS)
+    training.Trainer(zero_model(), training.TrainConfig(densify_rule="mcmc"), cameras=VIEWS)   # the rule alone is fine

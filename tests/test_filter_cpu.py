@@ -3,7 +3,6 @@ against its plain call, the host build of the FILTER variants of csrc/gs_math.h 
 bits of the C ABI, and the validation of the Python keywords.  Nothing here needs a GPU."""
 import ctypes as C
 import importlib
-import os
 import re
 
 import numpy as np
@@ -12,13 +11,13 @@ import torch
 
 from oracle import torch_port as tp
 from tests import listcheck, util
+from tests.abi_checks import header_defines, header_text
 from tests.cpu_frame import hm, oracle_stage_grads, project, ptr, row_spans  # noqa: F401  (hm is a fixture)
 
 abi = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd._abi")
 ops = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd.ops")
 harness = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd.harness")
 training = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd.training")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUSED = ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")
 MODES = ((0.3, False), (0.3, True))
 
@@ -222,11 +221,9 @@ def test_filtered_needles_have_no_determinant_cancellation(hm):
 # ---- 4. the flags --------------------------------------------------------------------------------------------------------
 
 def test_filter_macros_and_their_python_mirror_agree():
-    txt = open(os.path.join(ROOT, "include", "gsplat_mi355x.h")).read()
-    aa = re.search(r"^#define\s+GSPLAT_FILTER_ANTIALIAS\s+(\d+)\s*$", txt, flags=re.M)
-    lp = re.search(r"^#define\s+GSPLAT_FILTER_LOWPASS\(c\)\s+(\(\(c\) << \d+\))\s*$", txt, flags=re.M)
-    assert aa and lp
-    assert int(aa.group(1)) == abi.GSPLAT_FILTER_ANTIALIAS == 1 << 16
+    lp = re.search(r"^#define\s+GSPLAT_FILTER_LOWPASS\(c\)\s+(\(\(c\) << \d+\))\s*$", header_text(comments=True), flags=re.M)
+    assert lp
+    assert header_defines()["GSPLAT_FILTER_ANTIALIAS"] == abi.GSPLAT_FILTER_ANTIALIAS == 1 << 16
     for c in (0, 1, 30, 255):
         assert eval(lp.group(1).replace("(c)", f"({c})")) == abi.GSPLAT_FILTER_LOWPASS(c) == c << 17
     assert not [k for k in ("GSPLAT_FILTER_ANTIALIAS", "GSPLAT_FILTER_LOWPASS") if k.startswith("GSPLAT_PROJECT_")]

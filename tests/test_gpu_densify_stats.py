@@ -306,19 +306,15 @@ def _sentinel_stats(gs, n):
 
 def test_a_frame_that_overflows_its_pair_capacity_adds_nothing(gs):
     """The set-up of the overflow test of the folded Adam step: the capacity kept from earlier frames is far below the frame's pairs."""
-    ops = gs.ops
     optim = importlib.import_module(PKG + ".optim")
     s = list_scenes.golden("g1_generic")
     c2w, w = _views(s)[0]
     p = _params(s)
     with torch.no_grad():
         gs.render_gaussians(*[p[k] for k in NAMES], torch.tensor(c2w, device=DEV), *list_scenes.cam_args(s), **s["kwargs"])
-    key = ops.capacity_key(torch.device(DEV), types.SimpleNamespace(H=s["H"], W=s["W"]), len(s["pos"]))
-    keep = ops._ws.capacity[key]
     rec, before = _sentinel_stats(gs, len(s["pos"]))
-    try:
-        for folded in (False, True):
-            ops._ws.capacity[key] = 100                                  # far below the ~1600 pairs of the frame
+    for folded in (False, True):
+        with util.forced_pair_capacity(gs, s["H"], s["W"], len(s["pos"]), 100):          # far below the ~1600 pairs of the frame
             p = _params(s)
             opt = optim.GaussianAdam(optim.reference_param_groups(types.SimpleNamespace(**p)), lr=0.01, eps=1e-15)
             route = opt.fused_rest_update(p["f_rest"]) if folded else contextlib.nullcontext()
@@ -328,8 +324,6 @@ def test_a_frame_that_overflows_its_pair_capacity_adds_nothing(gs):
                 chk.verify()
             torch.cuda.synchronize()
             assert torch.equal(rec.data, before), "an overflowed frame touched the record"
-    finally:
-        ops._ws.capacity[key] = max(keep, ops._ws.capacity.get(key, 0))
 
 
 @pytest.mark.parametrize("name", util.EMPTY_CASES)
@@ -414,18 +408,13 @@ def test_trainer_accumulates_the_statistics_of_its_views(gs):
         assert torch.equal(got[2], got[1]), "view_streams = 2 differs from view_streams = 1"
         # a step whose first pass overflows: the third view's capacity is far too small, the other two views are valid -- and must
         # not count twice when the pass is repeated
-        key = ops.capacity_key(torch.device(DEV), types.SimpleNamespace(H=views[2]["H"], W=views[2]["W"]), len(s["pos"]))
-        keep = ops._ws.capacity[key]
-        try:
-            ops._ws.capacity[key] = 100
+        with util.forced_pair_capacity(gs, views[2]["H"], views[2]["W"], len(s["pos"]), 100):
             tr = _trainer(s)
             before = dict(ops.forward_modes)
             tr.step(1, views)
             torch.cuda.synchronize()
             assert ops.forward_modes["deferred"] == before["deferred"] + 6 and ops.forward_modes["waited"] == before["waited"]
             assert torch.equal(tr.densify_stats.data, ref), "a repeated pass changed the statistics"
-        finally:
-            ops._ws.capacity[key] = max(keep, ops._ws.capacity.get(key, 0))
     finally:
         gs.set_deterministic(old)
 

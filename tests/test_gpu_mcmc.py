@@ -2,7 +2,6 @@
 bit for bit, the relocation row by row, growth with a carried optimiser, the position noise, the regularisers, and the trainer's
 "mcmc" rule end to end.  Every buffer a kernel writes sits between guard margins that are read back."""
 import ctypes as C
-import datetime
 import importlib
 
 import numpy as np
@@ -11,6 +10,7 @@ import torch
 
 from oracle import scenes
 from tests import mcmc_oracle as mo
+from tests.ranks import run_ranks
 
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
 NAMES = ("pos", "opacity_raw", "f_dc", "f_rest", "scale_raw", "q_raw")
@@ -414,11 +414,7 @@ def test_mcmc_rule_runs_with_the_other_routes(mode):
         assert "l_alpha" in outs[-1]
 
 
-def _dp_worker(rank, world, port, q):
-    import os
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _dp_worker(rank, world):
     model_mod = importlib.import_module(PKG + ".model")
     training = importlib.import_module(PKG + ".training")
     init, views = _scene()
@@ -430,28 +426,12 @@ def _dp_worker(rank, world, port, q):
         out = tr.step(it, [views[rank]], global_views=world)
         refined += out["densified"]
     torch.cuda.synchronize()
-    q.put((rank, {k: getattr(model, k).detach().cpu().numpy() for k in NAMES},
-           {k: tr.optimizer.state[getattr(model, k)]['exp_avg'].cpu().numpy() for k in NAMES}, out["gaussians"], refined, tr.optimizer is opt))
-    dist.barrier()
-    dist.destroy_process_group()
+    return ({k: getattr(model, k).detach().cpu().numpy() for k in NAMES},
+            {k: tr.optimizer.state[getattr(model, k)]['exp_avg'].cpu().numpy() for k in NAMES}, out["gaussians"], refined, tr.optimizer is opt)
 
 
 def test_data_parallel_ranks_stay_bit_identical_through_two_refinements():
-    import socket
-    import torch.multiprocessing as mp
-    sock = socket.socket()
-    sock.bind(("127.0.0.1", 0))
-    port = sock.getsockname()[1]
-    sock.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = {r: rest for r, *rest in (q.get(timeout=150) for _ in range(2))}
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    got = run_ranks(_dp_worker, 2)
     n0 = scenes.case_g1()["pos"].shape[0]
     assert got[0][2] == got[1][2] == int(1.05 * int(1.05 * n0)) and got[0][3] == got[1][3] == 2 and got[0][4] and got[1][4]
     for k in NAMES:

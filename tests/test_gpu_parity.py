@@ -509,10 +509,7 @@ def test_deferred_checks_report_overflow_offscreen_and_empty_scenes(gs):
     ops = _ops()
     d = util.load("g1_generic")
     _fused(gs, d, grad=False)
-    key = _cap_key(ops, d)
-    real = ops._ws.capacity[key]
-    try:
-        ops._ws.capacity[key] = 64                              # far fewer pairs than the frame has (1616)
+    with util.forced_pair_capacity(gs, d["H"], d["W"], len(d["pos"]), 64) as key:          # far fewer pairs than the frame has (1616)
         with ops.deferred_checks() as chk:
             img, p = _fused(gs, d)                              # memory-safe garbage
         torch.cuda.synchronize()
@@ -525,8 +522,6 @@ def test_deferred_checks_report_overflow_offscreen_and_empty_scenes(gs):
         util.check_image(img.detach().cpu().numpy(), d["image"], cal=d["image_f32"])
         for k in util.PARAMS:
             util.check_grad(p[k].grad.cpu().numpy(), d["grad_" + k], k, cal=d["grad32_" + k])
-    finally:
-        ops._ws.capacity[key] = max(real, ops._ws.capacity[key])
     off = util.load("g10_offscreen")
     with ops.deferred_checks() as chk:
         _fused(gs, off, grad=False)                             # the reference raises here; deferred: in verify()
@@ -622,23 +617,20 @@ def test_deterministic_backward_with_too_small_buffers_is_memory_safe(gs):
     ops = _ops()
     d = util.load("g1_generic")
     _fused(gs, d, grad=False)
-    key = _cap_key(ops, d)
-    real = ops._ws.capacity[key]
     old = gs.set_deterministic(True)
     try:
-        ops._ws.capacity[key] = 200
-        with ops.deferred_checks() as chk:
-            _fused(gs, d)
-        torch.cuda.synchronize()
-        with pytest.raises(ops.PairCapacityExceeded):
-            chk.verify()
-        (_, p1), (_, p2) = gs.run_deferred(lambda: (_fused(gs, d), _fused(gs, d)))
-        for k in util.PARAMS:
-            assert torch.equal(p1[k].grad, p2[k].grad), k
-            util.check_grad(p1[k].grad.cpu().numpy(), d["grad_" + k], k, cal=d["grad32_" + k])
+        with util.forced_pair_capacity(gs, d["H"], d["W"], len(d["pos"]), 200):
+            with ops.deferred_checks() as chk:
+                _fused(gs, d)
+            torch.cuda.synchronize()
+            with pytest.raises(ops.PairCapacityExceeded):
+                chk.verify()
+            (_, p1), (_, p2) = gs.run_deferred(lambda: (_fused(gs, d), _fused(gs, d)))
+            for k in util.PARAMS:
+                assert torch.equal(p1[k].grad, p2[k].grad), k
+                util.check_grad(p1[k].grad.cpu().numpy(), d["grad_" + k], k, cal=d["grad32_" + k])
     finally:
         gs.set_deterministic(old)
-        ops._ws.capacity[key] = max(real, ops._ws.capacity[key])
 
 
 def test_the_ctypes_stub_of_integration_md_renders_the_golden(gs):

@@ -4,7 +4,6 @@
   * Trainer(sparse_adam=True) against the default trainer, on one process and on two data-parallel ranks."""
 import contextlib
 import ctypes as C
-import datetime
 import functools
 import importlib
 import types
@@ -17,6 +16,7 @@ from oracle import scenes
 from tests import densify_stats_oracle as dso
 from tests import device_frame as dfm
 from tests import list_scenes, util
+from tests.ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
@@ -26,13 +26,9 @@ NAMES = ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")
 TNAMES = ("pos", "opacity_raw", "f_dc", "f_rest", "scale_raw", "q_raw")
 
 
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
-
-
 def _same(a, b):
     """Equal bit for bit (NaNs included)."""
-    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
+    return a.shape == b.shape and torch.equal(util.bits(a), util.bits(b))
 
 
 # ---- 1. the kernel against the dense kernel -----------------------------------------------------------------------------------------
@@ -362,19 +358,15 @@ def test_an_empty_scene_adds_nothing(gs, name):
 
 def test_a_frame_that_overflows_its_pair_capacity_adds_nothing(gs):
     """The set-up of the overflow test of the densification statistics: the capacity kept from earlier frames is far below the frame's pairs."""
-    ops = gs.ops
     optim = importlib.import_module(PKG + ".optim")
     s = list_scenes.golden("g1_generic")
     c2w, w = _views(s)[0]
     p = _params(s)
     with torch.no_grad():
         gs.render_gaussians(*[p[k] for k in NAMES], torch.tensor(c2w, device=DEV), *list_scenes.cam_args(s), **s["kwargs"])
-    key = ops.capacity_key(torch.device(DEV), types.SimpleNamespace(H=s["H"], W=s["W"]), len(s["pos"]))
-    keep = ops._ws.capacity[key]
     rec, before = _prefilled(gs, len(s["pos"]))
-    try:
-        for folded in (False, True):
-            ops._ws.capacity[key] = 100                                  # far below the ~1600 pairs of the frame
+    for folded in (False, True):
+        with util.forced_pair_capacity(gs, s["H"], s["W"], len(s["pos"]), 100):          # far below the ~1600 pairs of the frame
             p = _params(s)
             opt = optim.GaussianAdam(optim.reference_param_groups(types.SimpleNamespace(**p)), lr=0.01, eps=1e-15)
             route = opt.fused_rest_update(p["f_rest"]) if folded else contextlib.nullcontext()
@@ -384,8 +376,6 @@ def test_a_frame_that_overflows_its_pair_capacity_adds_nothing(gs):
                 chk.verify()
             torch.cuda.synchronize()
             assert torch.equal(rec.data, before), "an overflowed frame touched the record"
-    finally:
-        ops._ws.capacity[key] = max(keep, ops._ws.capacity.get(key, 0))
 
 
 def test_a_record_that_does_not_fit_the_frame_is_refused(gs):
@@ -552,18 +542,13 @@ def test_a_repeated_pass_ends_like_one_that_was_not_repeated(gs):
     old = gs.set_deterministic(True)
     try:
         _warm(gs, s, views)
-        key = ops.capacity_key(torch.device(DEV), types.SimpleNamespace(H=s["H"], W=s["W"]), len(s["pos"]))
-        keep = ops._ws.capacity[key]
-        try:
-            ref, tr = _trainer(s, sparse_adam=True), _trainer(s, sparse_adam=True)
-            ref.step(1, views)
-            ops._ws.capacity[key] = 100
+        ref, tr = _trainer(s, sparse_adam=True), _trainer(s, sparse_adam=True)
+        ref.step(1, views)
+        with util.forced_pair_capacity(gs, s["H"], s["W"], len(s["pos"]), 100):
             before = dict(ops.forward_modes)
             tr.step(1, views)
             torch.cuda.synchronize()
             assert ops.forward_modes["deferred"] == before["deferred"] + 4, "the pass was not repeated"
-        finally:
-            ops._ws.capacity[key] = max(keep, ops._ws.capacity.get(key, 0))
         assert torch.equal(tr.visible.data, ref.visible.data) and tr.visible.data.any()
         a, b = _snapshot(ref), _snapshot(tr)
         for k in TNAMES:
@@ -574,11 +559,7 @@ def test_a_repeated_pass_ends_like_one_that_was_not_repeated(gs):
 
 # ---- 4. data parallel -------------------------------------------------------------------------------------------------------------
 
-def _dp_worker(rank, world, port, q, sparse=True):
-    import os
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _dp_worker(rank, world, sparse=True):
     gs = importlib.import_module(PKG)
     gs.set_deterministic(True)
     s, views, _, _ = _two_view_scene()
@@ -588,30 +569,7 @@ def _dp_worker(rank, world, port, q, sparse=True):
     for it in (1, 2):
         tr.step(it, [views[rank]], global_views=world)
         sets.append(tr.visible.data.cpu().numpy().copy() if sparse else None)
-    q.put((rank, {k: getattr(tr.model, k).detach().cpu().numpy() for k in TNAMES}, sets))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-def _two_ranks(sparse=True):
-    """rank -> (parameters, [record after iteration 1, after iteration 2]) of two ranks (gloo, both on cuda:0): view A on rank 0, view B
-    on rank 1, two iterations."""
-    import socket
-    import torch.multiprocessing as mp
-    sock = socket.socket()
-    sock.bind(("127.0.0.1", 0))
-    port = sock.getsockname()[1]
-    sock.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q, sparse)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = dict((r, (params, sets)) for r, params, sets in (q.get(timeout=150) for _ in range(2)))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    return got
+    return {k: getattr(tr.model, k).detach().cpu().numpy() for k in TNAMES}, sets
 
 
 def _one_process(gs, sparse=True):
@@ -633,8 +591,9 @@ def _one_process(gs, sparse=True):
 
 @functools.lru_cache(maxsize=None)
 def _dp_runs():
-    """The two ranks and the single process, run once for the tests below."""
-    return _two_ranks(), _one_process(importlib.import_module(PKG))
+    """The two ranks and the single process, run once for the tests below.  The ranks (gloo, both on cuda:0; view A on rank 0, view B
+    on rank 1, two iterations): per rank (parameters, [record after iteration 1, after iteration 2])."""
+    return run_ranks(_dp_worker, 2), _one_process(importlib.import_module(PKG))
 
 
 def _i32(a):

@@ -1,7 +1,7 @@
 """Next row 2 end to end: training.Trainer.step against the same iteration written with the oracle
 (oracle/torch_port.py render + loss, float64) and torch.optim.Adam / clip_grad_norm_ at the reference's settings
 (scripts/train.py:394-401, 446-569)."""
-import datetime
+import contextlib
 import importlib
 
 import numpy as np
@@ -10,6 +10,8 @@ import torch
 
 from oracle import scenes
 from oracle import torch_port as tp
+from tests import util
+from tests.ranks import run_ranks
 
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
 NAMES = ("pos", "opacity_raw", "f_dc", "f_rest", "scale_raw", "q_raw")
@@ -111,11 +113,7 @@ def test_loss_goes_down_and_densification_keeps_training():
     assert np.mean(losses[-5:]) < 0.8 * np.mean(losses[:5]), (losses[:5], losses[-5:])
 
 
-def _dp_worker(rank, world, port, q):
-    import os
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _dp_worker(rank, world):
     model_mod = importlib.import_module(PKG + ".model")
     training = importlib.import_module(PKG + ".training")
     s, views = _scene()
@@ -124,29 +122,13 @@ def _dp_worker(rank, world, port, q):
     out = None
     for it in (1, 2, 3):                     # iteration 2 densifies: the replicas must stay identical through it
         out = tr.step(it, [views[rank]], global_views=world)
-    q.put((rank, {k: getattr(model, k).detach().cpu().numpy() for k in NAMES}, out["gaussians"]))
-    dist.barrier()
-    dist.destroy_process_group()
+    return {k: getattr(model, k).detach().cpu().numpy() for k in NAMES}, out["gaussians"]
 
 
 def test_data_parallel_training_matches_single_process():
     """Two ranks (gloo, both on cuda:0), one view each, factored gradient exchange, against one process rendering both
     views: same parameters after three iterations including a densification, and bit-identical replicas."""
-    import socket
-    import torch.multiprocessing as mp
-    sock = socket.socket()
-    sock.bind(("127.0.0.1", 0))
-    port = sock.getsockname()[1]
-    sock.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = dict((r, (params, n)) for r, params, n in (q.get(timeout=150) for _ in range(2)))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    got = run_ranks(_dp_worker, 2)
     model_mod = importlib.import_module(PKG + ".model")
     training = importlib.import_module(PKG + ".training")
     s, views = _scene()
@@ -163,12 +145,7 @@ def test_data_parallel_training_matches_single_process():
         assert np.quantile(err, 0.99) <= 1e-4 * max(1.0, np.abs(ref).max()), (k, float(np.quantile(err, 0.99)))
 
 
-def _rccl_worker(port, q):
-    import os
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1")
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+def _rccl_worker(rank, world):
     gs = importlib.import_module(PKG)
     dp = importlib.import_module(PKG + ".dp")
     s, views = _scene()
@@ -188,27 +165,13 @@ def _rccl_worker(port, q):
         else:
             dp.allreduce_gradients([p[k].grad for k in NAMES], world_views=2)
         res[mode] = {k: p[k].grad.cpu().numpy() for k in NAMES}
-    q.put(res)
-    dist.barrier()
-    dist.destroy_process_group()
+    return res
 
 
 def test_exchange_collectives_run_over_rccl():
     """The collectives of the data-parallel exchange through the real RCCL backend (a one-rank group is what a one-GPU box
     allows): same gradients as the plain path."""
-    import socket
-    import torch.multiprocessing as mp
-    sock = socket.socket()
-    sock.bind(("127.0.0.1", 0))
-    port = sock.getsockname()[1]
-    sock.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    proc = ctx.Process(target=_rccl_worker, args=(port, q))
-    proc.start()
-    res = q.get(timeout=150)
-    proc.join(timeout=120)
-    assert proc.exitcode == 0
+    res, = run_ranks(_rccl_worker, 1, backend="nccl")
     for k in NAMES:
         scale = np.abs(res["plain"][k]).max()
         assert np.abs(res["factored"][k] - res["plain"][k]).max() <= 2e-5 * scale, k
@@ -264,6 +227,7 @@ def test_adam_step_of_f_rest_inside_the_backward_pass_is_the_optimisers_step():
     deterministic gradients every parameter -- and both moments of f_rest -- are bit-identical after three iterations.  A pass that
     outgrew its pair buffers steps nothing (the kernel reads the frame's counters itself) and is repeated; an off-screen view raises
     the reference's exception with every parameter untouched."""
+    gs = importlib.import_module(PKG)
     model_mod = importlib.import_module(PKG + ".model")
     training = importlib.import_module(PKG + ".training")
     ops = importlib.import_module(PKG + ".ops")
@@ -281,19 +245,14 @@ def test_adam_step_of_f_rest_inside_the_backward_pass_is_the_optimisers_step():
             assert ops.composite_calls["backward"] == calls + 3
             st = tr.optimizer.state[model.f_rest]
             assert st['step'] == 4 and (model.f_rest.grad is None) == fold
-            if fold:                                           # an iteration whose buffers are too small: one garbage pass, one good one
-                import types
-                key = ops.capacity_key(torch.device("cuda:0"), types.SimpleNamespace(H=one[0]["H"], W=one[0]["W"]), len(s["pos"]))
-                keep = ops._ws.capacity[key]
             torch.cuda.synchronize()
             res.append((losses, {k: getattr(model, k).detach().clone() for k in NAMES}, st['exp_avg'].clone(), st['exp_avg_sq'].clone()))
-            if fold:
-                ops._ws.capacity[key] = 100
-                before = dict(ops.forward_modes)
-                tr.step(5, one)
-                assert ops.forward_modes["deferred"] == before["deferred"] + 2 and tr.optimizer.state[model.f_rest]['step'] == 5
-                folded_after_redo = model.f_rest.detach().clone()
-                ops._ws.capacity[key] = keep
+            if fold:                                           # an iteration whose buffers are too small: one garbage pass, one good one
+                with util.forced_pair_capacity(gs, one[0]["H"], one[0]["W"], len(s["pos"]), 100):
+                    before = dict(ops.forward_modes)
+                    tr.step(5, one)
+                    assert ops.forward_modes["deferred"] == before["deferred"] + 2 and tr.optimizer.state[model.f_rest]['step'] == 5
+                    folded_after_redo = model.f_rest.detach().clone()
             else:
                 tr.step(5, one)
                 plain_after = model.f_rest.detach().clone()
@@ -370,6 +329,7 @@ def test_config4_training_iteration():
 def test_trainer_repeats_a_pass_that_outgrew_the_pair_buffers():
     """The pair capacity kept from earlier frames is too small for this iteration's views (as after a densification or a new
     camera): the pass is repeated with larger buffers and the iteration's result is the one of an undisturbed iteration."""
+    gs = importlib.import_module(PKG)
     model_mod = importlib.import_module(PKG + ".model")
     training = importlib.import_module(PKG + ".training")
     ops = importlib.import_module(PKG + ".ops")
@@ -379,16 +339,15 @@ def test_trainer_repeats_a_pass_that_outgrew_the_pair_buffers():
         model = model_mod.GaussianModel({k: torch.tensor(s[k]) for k in NAMES}, device="cuda:0")
         tr = training.Trainer(model, training.TrainConfig(densify_until_iter=0, opacity_reset_interval=10 ** 9))
         tr.step(1, views)
-        if shrink:
-            import types
-            key = ops.capacity_key(torch.device("cuda:0"), types.SimpleNamespace(H=views[0]["H"], W=views[0]["W"]), len(s["pos"]))
-            ops._ws.capacity[key] = 100                       # far below the ~1600 pairs of a view
-        before = dict(ops.forward_modes)
-        out = tr.step(2, views)
-        torch.cuda.synchronize()
-        if shrink:                                            # one garbage pass + one good pass, nothing waited for
-            assert ops.forward_modes["deferred"] == before["deferred"] + 4 and ops.forward_modes["waited"] == before["waited"]
-            assert ops._ws.capacity[key] > 1600
+        # (100: far below the ~1600 pairs of a view)
+        shrunk = util.forced_pair_capacity(gs, views[0]["H"], views[0]["W"], len(s["pos"]), 100) if shrink else contextlib.nullcontext()
+        with shrunk as key:
+            before = dict(ops.forward_modes)
+            out = tr.step(2, views)
+            torch.cuda.synchronize()
+            if shrink:                                        # one garbage pass + one good pass, nothing waited for
+                assert ops.forward_modes["deferred"] == before["deferred"] + 4 and ops.forward_modes["waited"] == before["waited"]
+                assert ops._ws.capacity[key] > 1600
         return float(out["loss"]), {k: getattr(model, k).detach().clone() for k in NAMES}
 
     loss_a, pa = run(False)
@@ -398,11 +357,7 @@ def test_trainer_repeats_a_pass_that_outgrew_the_pair_buffers():
         assert float((pa[k] - pb[k]).abs().max()) <= 1e-5 * max(1.0, float(pa[k].abs().max())), k
 
 
-def _dp_offscreen_worker(rank, world, port, q):
-    import os
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _dp_offscreen_worker(rank, world):
     model_mod = importlib.import_module(PKG + ".model")
     training = importlib.import_module(PKG + ".training")
     s = scenes.case_g10()                                        # 48 Gaussians whose centres project into the guard band LEFT of a 32 x 32 image
@@ -415,33 +370,17 @@ def _dp_offscreen_worker(rank, world, port, q):
     before = {k: getattr(model, k).detach().clone() for k in NAMES}
     try:
         tr.step(2, [bad], global_views=world)
-        q.put((rank, "ok", ""))
+        return "ok", ""
     except Exception as e:
         unchanged = all(torch.equal(before[k], getattr(model, k).detach()) for k in NAMES)
-        q.put((rank, type(e).__name__, str(e) + ("" if unchanged else " [parameters changed]")))
-    dist.barrier()
-    dist.destroy_process_group()
+        return type(e).__name__, str(e) + ("" if unchanged else " [parameters changed]")
 
 
 def test_an_offscreen_view_on_one_rank_raises_on_every_rank():
     """Data parallel, real renderer: rank 1's view has survivors but nothing on screen.  The reference raises
     Exception("All projected points are off-screen") for such a view; here EVERY rank raises it, in the same step, within the
     timeout (nobody waits in a collective), and no rank has stepped its optimiser."""
-    import socket
-    import torch.multiprocessing as mp
-    sock = socket.socket()
-    sock.bind(("127.0.0.1", 0))
-    port = sock.getsockname()[1]
-    sock.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_dp_offscreen_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = dict((r, (name, msg)) for r, name, msg in (q.get(timeout=150) for _ in range(2)))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    got = run_ranks(_dp_offscreen_worker, 2)
     ops = importlib.import_module(PKG + ".ops")
     assert got[1] == ("Exception", ops.OFFSCREEN_MSG), got
     assert got[0][0] == "Exception" and got[0][1].startswith(ops.OFFSCREEN_MSG) and "changed" not in got[0][1], got

@@ -1,6 +1,7 @@
 """The trainer modes of the two per-view colour tables on the MI355X, in deterministic mode (DESIGN.md §24 exposure, §25 bilateral
 grids): one set of tests over both modes; a MODES record carries what differs.  The kernels and the autograd ops have their own files
 (tests/test_gpu_exposure.py, tests/test_gpu_bilagrid.py), and each keeps the two-rank test of its mode."""
+import contextlib
 import importlib
 import io
 import types
@@ -10,6 +11,7 @@ import pytest
 import torch
 
 from tests import bilagrid_oracle as bo
+from tests.util import forced_pair_capacity
 from tests.view_table_harness import (DEV, N_IMAGES, NAMES, PKG, ROUTES, _assert_same_dict, _model_bits, _same, _scene, _table_bits, _trainer,
                                       _warm, deterministic)  # noqa: F401  (deterministic: a fixture)
 
@@ -100,23 +102,18 @@ def test_a_repeated_pass_counts_the_table_gradient_once(deterministic, mode):
     ops = importlib.import_module(PKG + ".ops")
     s, views = _scene()
     views = list(views[:2])
-    key = ops.capacity_key(torch.device(DEV), types.SimpleNamespace(H=views[0]["H"], W=views[0]["W"]), len(s["pos"]))
     res = []
     for shrink in (False, True):
         _warm(gs, s, views)
         tr = _trainer(s, **{mode: True})
         tr.step(1, views)
         torch.cuda.synchronize()
-        keep = ops._ws.capacity[key]
-        try:
-            if shrink:
-                ops._ws.capacity[key] = 100                   # far below the ~1600 pairs of a view
+        # (100: far below the ~1600 pairs of a view)
+        with forced_pair_capacity(gs, views[0]["H"], views[0]["W"], len(s["pos"]), 100) if shrink else contextlib.nullcontext():
             before = dict(ops.forward_modes)
             tr.step(2, views)
             torch.cuda.synchronize()
             assert ops.forward_modes["deferred"] == before["deferred"] + (4 if shrink else 2), "the pass was (not) repeated"
-        finally:
-            ops._ws.capacity[key] = max(keep, ops._ws.capacity.get(key, 0))
         res.append((_table_bits(tr), _model_bits(tr)))
     assert res[0][0]["grad"][0].any() and res[0][0]["grad"][2].any()
     _assert_same_dict(res[0][0], res[1][0], "table")

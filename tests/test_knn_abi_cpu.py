@@ -5,46 +5,23 @@ on CPU tensors, the default initialisation is the reference's draw for draw, and
 colours."""
 import ctypes as C
 import importlib
-import os
-import re
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from tests.abi_checks import check_entries, header_defines, refused
+
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 abi = importlib.import_module(PKG + "._abi")
 ENTRIES = {"gsplat_knn_scratch_bytes": 1, "gsplat_knn_mean_dist2": 5}
 NAMES = ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")
 
 
-def _refused(lib, status, name, arg):
-    msg = lib.gsplat_last_error()
-    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, arg, status)
-    assert name.encode() + b":" in msg and arg.encode() in msg, (name, arg, msg)
-
-
 def test_header_mirror_and_library_agree_and_the_version_stays_12():
-    header = open(os.path.join(ROOT, "include", "gsplat_mi355x.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    for name, n_args in ENTRIES.items():
-        m = re.search(rf"\b(?:int|int64_t)\s+{name}\s*\(([^)]*)\)\s*;", txt)
-        assert m, f"{name} is not declared in include/gsplat_mi355x.h"
-        assert len(m.group(1).split(",")) == n_args, name
-        assert name in abi.SIGNATURES and len(abi.SIGNATURES[name][1]) == n_args, name
-    assert re.search(r"^#define\s+GSPLAT_ABI_VERSION\s+12\s*$", header, flags=re.M) and abi.ABI_VERSION == 12
-    box = re.search(r"^#define\s+GSPLAT_KNN_BOX\s+(\d+)\s*$", header, flags=re.M)
-    assert int(box.group(1)) == abi.GSPLAT_KNN_BOX and abi.GSPLAT_KNN_BOX % 64 == 0 and abi.GSPLAT_KNN_BOX >= 64
-    lib = abi.lib()
-    assert lib.gsplat_abi_version() == 12
-    out = subprocess.run(["nm", "-D", "--defined-only", abi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TtWw"}
-    assert set(ENTRIES) <= exported
-    stray = [f for f in exported if "knn" in f.lower() and f not in ENTRIES]
-    assert not stray, f"helpers of the knn entries exported: {stray}"
+    check_entries(ENTRIES, family="knn")
+    assert header_defines()["GSPLAT_KNN_BOX"] == abi.GSPLAT_KNN_BOX and abi.GSPLAT_KNN_BOX % 64 == 0 and abi.GSPLAT_KNN_BOX >= 64
 
 
 def test_scratch_size_is_a_pure_host_function_monotone_in_n():
@@ -70,7 +47,7 @@ def test_entry_refuses_bad_arguments_on_the_host():
 
     for arg, bad in ([(k, None) for k in ("points", "dist2", "scratch")] + [("n", -1), ("n", 2 ** 31)]
                      + [("points", odd), ("dist2", odd), ("scratch", odd), ("scratch", C.c_void_p(p.value + 16)), ("scratch", C.c_void_p(p.value + 128))]):
-        _refused(lib, call(**{arg: bad}), name, arg)
+        refused(lib, call(**{arg: bad}), name, arg)
     assert call(n=0, points=None, dist2=None, scratch=None) == abi.GSPLAT_OK       # n == 0: nothing to do, nothing is looked at
     del buf
 

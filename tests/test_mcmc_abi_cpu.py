@@ -5,42 +5,24 @@ anything is launched -- and a Trainer of densify_rule="mcmc" constructs (its con
 import ctypes as C
 import dataclasses
 import importlib
-import os
 import re
-import subprocess
 
 import pytest
 import torch
 
+from tests.abi_checks import check_entries, header_text, refused
+from tests.util import zero_model
+
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 abi = importlib.import_module(PKG + "._abi")
 ENTRIES = {"gsplat_mcmc_scratch_bytes": 1, "gsplat_mcmc_scratch_layout": 2, "gsplat_mcmc_noise": 9, "gsplat_mcmc_regularise": 11,
            "gsplat_mcmc_refine": 13}
 
 
-def _refused(lib, status, name):
-    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, status)
-    assert name.encode() in lib.gsplat_last_error(), (name, lib.gsplat_last_error())
-
-
 def test_header_mirror_and_library_agree_and_the_version_stays_12():
-    header = open(os.path.join(ROOT, "include", "gsplat_mi355x.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    for name, n_args in ENTRIES.items():
-        m = re.search(rf"\b(?:int|int64_t)\s+{name}\s*\(([^)]*)\)\s*;", txt)
-        assert m, f"{name} is not declared in include/gsplat_mi355x.h"
-        assert len(m.group(1).split(",")) == n_args, name
-        assert name in abi.SIGNATURES and len(abi.SIGNATURES[name][1]) == n_args, name
+    check_entries(ENTRIES, family=("mcmc", "philox", "relocat"))
+    txt = header_text()
     assert "const gsplat_mcmc_moments* moments" in txt and "uint64_t seed, uint32_t iteration" in txt
-    assert re.search(r"^#define\s+GSPLAT_ABI_VERSION\s+12\s*$", header, flags=re.M) and abi.ABI_VERSION == 12
-    lib = abi.lib()
-    assert lib.gsplat_abi_version() == 12
-    out = subprocess.run(["nm", "-D", "--defined-only", abi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TtWw"}
-    assert set(ENTRIES) <= exported
-    stray = [f for f in exported if ("mcmc" in f or "philox" in f or "relocat" in f) and f not in ENTRIES]
-    assert not stray, f"helpers of the MCMC entries exported: {stray}"
     # the structs the entries take, field for field
     assert C.sizeof(abi.McmcMoments) == 12 * 8 and C.sizeof(abi.McmcLayout) == 8 * 8 + 2 * 4
     fields = re.search(r"typedef struct gsplat_mcmc_moments \{(.*?)\} gsplat_mcmc_moments;", txt, flags=re.S).group(1)
@@ -62,9 +44,9 @@ def test_layout_query_is_a_pure_host_function_consistent_with_the_size_query():
         assert lay.reg == 0                                  # the counter that must start at zero does not move with n
     assert lay.bytes < 2 ** 31 * 24
     assert lib.gsplat_mcmc_scratch_bytes(-1) == -1 and lib.gsplat_mcmc_scratch_bytes(2 ** 31) == -1
-    _refused(lib, lib.gsplat_mcmc_scratch_layout(-1, C.byref(lay)), "gsplat_mcmc_scratch_layout")
-    _refused(lib, lib.gsplat_mcmc_scratch_layout(2 ** 31, C.byref(lay)), "gsplat_mcmc_scratch_layout")
-    _refused(lib, lib.gsplat_mcmc_scratch_layout(4, None), "gsplat_mcmc_scratch_layout")
+    refused(lib, lib.gsplat_mcmc_scratch_layout(-1, C.byref(lay)), "gsplat_mcmc_scratch_layout")
+    refused(lib, lib.gsplat_mcmc_scratch_layout(2 ** 31, C.byref(lay)), "gsplat_mcmc_scratch_layout")
+    refused(lib, lib.gsplat_mcmc_scratch_layout(4, None), "gsplat_mcmc_scratch_layout")
 
 
 def test_entries_refuse_bad_arguments_on_the_host():
@@ -78,7 +60,7 @@ def test_entries_refuse_bad_arguments_on_the_host():
     for status in (f(-1, p, p, p, p, 1.0, 0, 0, None), f(2 ** 31, p, p, p, p, 1.0, 0, 0, None), f(4, None, p, p, p, 1.0, 0, 0, None),
                    f(4, p, None, p, p, 1.0, 0, 0, None), f(4, p, p, None, p, 1.0, 0, 0, None), f(4, p, p, p, None, 1.0, 0, 0, None),
                    f(4, p, p, p, odd, 1.0, 0, 0, None), f(4, p, p, p, p, nan, 0, 0, None), f(4, p, p, p, p, inf, 0, 0, None)):
-        _refused(lib, status, name)
+        refused(lib, status, name)
     assert f(0, None, None, None, None, 1.0, 0, 0, None) == abi.GSPLAT_OK
 
     name, f = "gsplat_mcmc_regularise", lib.gsplat_mcmc_regularise
@@ -87,7 +69,7 @@ def test_entries_refuse_bad_arguments_on_the_host():
                    f(4, p, p, p, p, 0.01, 0.01, None, None, p, None), f(4, p, p, p, p, 0.01, 0.01, None, p, None, None),
                    f(4, p, p, p, p, 0.01, 0.01, None, p, odd, None), f(4, p, p, p, p, -0.01, 0.01, None, p, p, None),
                    f(4, p, p, p, p, 0.01, nan, None, p, p, None), f(4, p, p, p, p, inf, 0.01, None, p, p, None)):
-        _refused(lib, status, name)
+        refused(lib, status, name)
     assert f(0, None, None, None, None, 0.01, 0.01, None, None, None, None) == abi.GSPLAT_OK
 
     name, f = "gsplat_mcmc_refine", lib.gsplat_mcmc_refine
@@ -103,7 +85,7 @@ def test_entries_refuse_bad_arguments_on_the_host():
     for bad in ([dict([(k, None)]) for k in ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw", "scratch")]
                 + [dict(n=-1), dict(n=2 ** 31), dict(min_opacity=-0.1), dict(min_opacity=1.0), dict(min_opacity=nan), dict(scratch=odd),
                    dict(moments=C.byref(half))]):
-        _refused(lib, call(**bad), name)
+        refused(lib, call(**bad), name)
     assert call(n=0, pos=None, scratch=None) == abi.GSPLAT_OK
     del buf
 
@@ -141,21 +123,15 @@ def test_grow_rows_moves_the_state_and_keeps_the_step():
         opt.grow_rows(a2, torch.nn.Parameter(torch.ones(4, 2)))     # rows cannot leave
 
 
-def _model():
-    model_mod = importlib.import_module(PKG + ".model")
-    z = torch.zeros
-    return model_mod.GaussianModel(dict(pos=z(4, 3), f_dc=z(4, 3), f_rest=z(4, 45), opacity_raw=z(4), scale_raw=z(4, 3), q_raw=z(4, 4)), device="cpu")
-
-
 def test_trainer_of_the_mcmc_rule_constructs_and_keeps_the_defaults():
     training = importlib.import_module(PKG + ".training")
     c = training.TrainConfig()
     assert (c.densify_rule, c.cap_max, c.mcmc_start_iter, c.mcmc_min_opacity, c.mcmc_noise_lr, c.mcmc_opacity_reg, c.mcmc_scale_reg,
             c.mcmc_growth, c.mcmc_seed) == ("reference", 1_000_000, 500, 0.005, 5e5, 0.01, 0.01, 1.05, 0)
-    tr = training.Trainer(_model(), training.TrainConfig(densify_rule="mcmc"))
+    tr = training.Trainer(zero_model(), training.TrainConfig(densify_rule="mcmc"))
     assert tr.cfg.densify_rule == "mcmc" and len(tr.optimizer.param_groups) == 6
     with pytest.raises(ValueError, match="densify_rule"):
-        training.Trainer(_model(), training.TrainConfig(densify_rule="paper"))
+        training.Trainer(zero_model(), training.TrainConfig(densify_rule="paper"))
 
 
 @pytest.mark.parametrize("field,value", [("cap_max", 0), ("cap_max", 1.5), ("cap_max", True), ("cap_max", 2 ** 31), ("mcmc_start_iter", -1),
@@ -168,4 +144,4 @@ def test_trainer_refuses_bad_mcmc_fields(field, value):
     training = importlib.import_module(PKG + ".training")
     cfg = dataclasses.replace(training.TrainConfig(densify_rule="mcmc"), **{field: value})
     with pytest.raises(ValueError, match=field):
-        training.Trainer(_model(), cfg)
+        training.Trainer(zero_model(), cfg)

@@ -2,17 +2,17 @@
 scratch layout, the host build of csrc/gs_metrics.h against the float64 oracle, data.split_views, the aggregation over gloo, and
 what evaluate() refuses before it touches a GPU."""
 import ctypes as C
-import datetime
 import importlib
 import os
-import re
-import socket
 
 import numpy as np
 import pytest
 import torch
 
 from tests import metrics_oracle as mo
+from tests.abi_checks import check_entries, header_defines, refused
+from tests.ranks import run_ranks
+from tests.util import zero_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
@@ -25,27 +25,13 @@ ENTRIES = {"gsplat_metrics_scratch_bytes": 4, "gsplat_metrics_fit_affine": 9, "g
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------------------
 
 def test_header_mirror_and_library_agree_on_the_three_entries():
-    txt = open(os.path.join(ROOT, "include", "gsplat_mi355x.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    lib = C.CDLL(abi.LIB_PATH)
-    for name, n_args in ENTRIES.items():
-        m = re.search(r"\b" + name + r"\s*\(([^)]*)\)\s*;", code)
-        assert m, f"{name} is not declared in the header"
-        assert len(m.group(1).split(",")) == n_args == len(abi.SIGNATURES[name][1]), name
-        assert hasattr(lib, name), f"{name} is not exported"
-    assert re.search(r"^#define\s+GSPLAT_METRICS_COLOUR_CORRECT\s+1\s*$", txt, flags=re.M) and abi.GSPLAT_METRICS_COLOUR_CORRECT == 1
-    assert re.search(r"^#define\s+GSPLAT_ABI_VERSION\s+12\s*$", txt, flags=re.M)
-    assert abi.ABI_VERSION == 12 and abi.lib().gsplat_abi_version() == 12
+    check_entries(ENTRIES)
+    assert header_defines()["GSPLAT_METRICS_COLOUR_CORRECT"] == abi.GSPLAT_METRICS_COLOUR_CORRECT == 1
 
 
 def _host_words(n=16):
     buf = (C.c_float * n)()
     return buf, C.cast(buf, C.c_void_p)
-
-
-def _refused(lib, status, name):
-    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, status)
-    assert name.encode() in lib.gsplat_last_error(), (name, lib.gsplat_last_error())
 
 
 def test_every_bad_argument_is_refused_on_the_host():
@@ -63,18 +49,18 @@ def test_every_bad_argument_is_refused_on_the_host():
 
     shapes = (dict(B=0), dict(B=-1), dict(H=0), dict(H=-3), dict(W=0), dict(W=-2), dict(B=65536))
     for arg in ("pred", "target", "affine", "scratch"):
-        _refused(lib, fit(**{arg: None}), "gsplat_metrics_fit_affine")
+        refused(lib, fit(**{arg: None}), "gsplat_metrics_fit_affine")
     for bad in shapes:
-        _refused(lib, fit(**bad), "gsplat_metrics_fit_affine")
+        refused(lib, fit(**bad), "gsplat_metrics_fit_affine")
     for arg in ("pred", "target", "out", "scratch"):
-        _refused(lib, fwd(**{arg: None}), "gsplat_metrics_forward")
-        _refused(lib, fwd(flags=CCF, affine=p, **{arg: None}), "gsplat_metrics_forward")
+        refused(lib, fwd(**{arg: None}), "gsplat_metrics_forward")
+        refused(lib, fwd(flags=CCF, affine=p, **{arg: None}), "gsplat_metrics_forward")
     for bad in shapes:
-        _refused(lib, fwd(**bad), "gsplat_metrics_forward")
+        refused(lib, fwd(**bad), "gsplat_metrics_forward")
     for flags in (2, 4, 1 << 5, CCF | 8, -1):
-        _refused(lib, fwd(flags=flags, affine=p), "gsplat_metrics_forward")
+        refused(lib, fwd(flags=flags, affine=p), "gsplat_metrics_forward")
         assert b"unknown flag" in lib.gsplat_last_error()
-    _refused(lib, fwd(flags=CCF, affine=None), "gsplat_metrics_forward")
+    refused(lib, fwd(flags=CCF, affine=None), "gsplat_metrics_forward")
     assert b"affine" in lib.gsplat_last_error()
     del keep
 
@@ -246,48 +232,21 @@ def test_aggregate_of_one_process_is_the_plain_means():
         metrics.aggregate(rows[:4], idx)
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _worker(rank, world, port, q):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+def _worker(rank, world):
     metrics = importlib.import_module(PKG + ".metrics")
     dp = importlib.import_module(PKG + ".dp")
     rows = _rows(3)
-    q.put((rank, metrics.aggregate(rows[dp.shard_views(3, rank, world)], [4, 9, 2])))
-    dist.barrier()
-    dist.destroy_process_group()
+    return metrics.aggregate(rows[dp.shard_views(3, rank, world)], [4, 9, 2])
 
 
 def test_aggregate_over_gloo_gives_both_ranks_the_bits_and_the_order_of_one_process():
     """World 2, three views: rank 0 holds views 0 and 2, rank 1 view 1 (uneven shards)."""
-    import torch.multiprocessing as mp
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=120) for _ in range(world))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    got = run_ranks(_worker, 2, answer_s=120, join_s=60)
     want = _plain(_rows(3), [4, 9, 2])
     assert got[0] == want and got[1] == want
 
 
 # ---- what evaluate() refuses without a GPU -------------------------------------------------------------------------------------------
-
-def _model():
-    model_mod = importlib.import_module(PKG + ".model")
-    z = torch.zeros
-    return model_mod.GaussianModel(dict(pos=z(4, 3), f_dc=z(4, 3), f_rest=z(4, 45), opacity_raw=z(4), scale_raw=z(4, 3), q_raw=z(4, 4)), device="cpu")
-
 
 def _view(**kw):
     v = dict(c2w=torch.eye(4), H=8, W=6, fx=10.0, fy=10.0, cx=3.0, cy=4.0, image=torch.zeros(8, 6, 3))
@@ -297,7 +256,7 @@ def _view(**kw):
 
 def test_evaluate_refuses_bad_views_before_anything_is_queued(gs):
     training = importlib.import_module(PKG + ".training")
-    tr = training.Trainer(_model())
+    tr = training.Trainer(zero_model())
     no_image = _view()
     del no_image['image']
     cases = [([_view(), no_image], "no 'image'"), ([_view(image=None)], "no 'image'"), ([_view(image=torch.zeros(8, 6, 2))], "'image' must be"),

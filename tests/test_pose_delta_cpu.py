@@ -5,14 +5,14 @@ as GSPLAT_ERR_BAD_ARG naming the entry before anything is launched; the host bui
 import ctypes as C
 import importlib
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import pose_delta_oracle as po
+from tests.abi_checks import check_entries, exported_functions, header_defines, refused
+from tests.util import zero_model
 
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -98,33 +98,10 @@ def test_oracle_clamp_matches_torch_float64_autograd():
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------------
 def test_header_mirror_and_library_agree_and_the_version_stays_12():
-    header = open(os.path.join(ROOT, "include", "gsplat_mi355x.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    for name, n_args in ENTRIES.items():
-        m = re.search(rf"\b(?:int|int64_t)\s+{name}\s*\(([^)]*)\)\s*;", txt)
-        assert m, f"{name} is not declared in include/gsplat_mi355x.h"
-        assert len(m.group(1).split(",")) == n_args, name
-        assert name in abi.SIGNATURES and len(abi.SIGNATURES[name][1]) == n_args, name
-    assert re.search(r"^#define\s+GSPLAT_ABI_VERSION\s+12\s*$", header, flags=re.M) and abi.ABI_VERSION == 12
-    flag = re.search(r"^#define\s+GSPLAT_POSE_DELTA_ACCUMULATE\s+(\d+)\s*$", header, flags=re.M)
-    assert int(flag.group(1)) == abi.GSPLAT_POSE_DELTA_ACCUMULATE == 1
-    lib = abi.lib()
-    assert lib.gsplat_abi_version() == 12
-    out = subprocess.run(["nm", "-D", "--defined-only", abi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TtWw"}
-    assert set(ENTRIES) <= exported
+    check_entries(ENTRIES, family="pose_delta", stubs_in_namespace=True)
+    assert header_defines()["GSPLAT_POSE_DELTA_ACCUMULATE"] == abi.GSPLAT_POSE_DELTA_ACCUMULATE == 1
     # the render's own pose gradient (ABI 10) keeps its two names, and nothing else of this unit is exported
-    assert {"gsplat_pose_scratch_bytes", "gsplat_project_backward_pose"} <= exported
-    stray = [f for f in exported if "pose_delta" in f and f not in ENTRIES and not f.startswith(("_ZN", "__hip"))]
-    assert not stray, f"helpers of the pose-delta entries exported: {stray}"
-
-
-def _refused(lib, status, name, word=None):
-    msg = lib.gsplat_last_error()
-    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, word, status)
-    assert name.encode() + b":" in msg, (name, msg)
-    if word is not None:
-        assert word.encode() in msg, (name, word, msg)
+    assert {"gsplat_pose_scratch_bytes", "gsplat_project_backward_pose"} <= exported_functions()
 
 
 def test_entries_refuse_bad_arguments_on_the_host():
@@ -145,27 +122,27 @@ def test_entries_refuse_bad_arguments_on_the_host():
 
     sizes = (0, -2, (1 << 30) + 1, 1 << 40)
     for arg in ("c2w", "delta", "out"):
-        _refused(lib, fwd(**{arg: None}), "gsplat_pose_delta_forward", arg + " is NULL")
+        refused(lib, fwd(**{arg: None}), "gsplat_pose_delta_forward", arg + " is NULL")
     for bad in sizes:
-        _refused(lib, fwd(batch=bad), "gsplat_pose_delta_forward", "batch")
+        refused(lib, fwd(batch=bad), "gsplat_pose_delta_forward", "batch")
     for arg in ("c2w", "delta", "grad_out"):
-        _refused(lib, bwd(**{arg: None}), "gsplat_pose_delta_backward", arg + " is NULL")
+        refused(lib, bwd(**{arg: None}), "gsplat_pose_delta_backward", arg + " is NULL")
     for bad in sizes:
-        _refused(lib, bwd(batch=bad), "gsplat_pose_delta_backward", "batch")
+        refused(lib, bwd(batch=bad), "gsplat_pose_delta_backward", "batch")
     for flags in (2, 4, 1 << 5, 3, -2, 1 << 30):
-        _refused(lib, bwd(flags=flags), "gsplat_pose_delta_backward", "unknown flag")
-        _refused(lib, bwd(flags=flags, c2w=None, batch=0), "gsplat_pose_delta_backward", "unknown flag")      # refused FIRST
-    _refused(lib, bwd(flags=abi.GSPLAT_POSE_DELTA_ACCUMULATE, c2w=None), "gsplat_pose_delta_backward", "c2w is NULL")
+        refused(lib, bwd(flags=flags), "gsplat_pose_delta_backward", "unknown flag")
+        refused(lib, bwd(flags=flags, c2w=None, batch=0), "gsplat_pose_delta_backward", "unknown flag")      # refused FIRST
+    refused(lib, bwd(flags=abi.GSPLAT_POSE_DELTA_ACCUMULATE, c2w=None), "gsplat_pose_delta_backward", "c2w is NULL")
     assert bwd(grad_c2w=None, grad_delta=None) == abi.GSPLAT_OK          # neither half asked for: nothing to do, nothing launched
     for arg in ("delta", "grad"):
-        _refused(lib, decay(**{arg: None}), "gsplat_pose_delta_decay", arg + " is NULL")
+        refused(lib, decay(**{arg: None}), "gsplat_pose_delta_decay", arg + " is NULL")
     for bad in sizes:
-        _refused(lib, decay(n_views=bad), "gsplat_pose_delta_decay", "n_views")
+        refused(lib, decay(n_views=bad), "gsplat_pose_delta_decay", "n_views")
     odd = C.c_void_p(p.value + 2)
-    _refused(lib, fwd(c2w=odd), "gsplat_pose_delta_forward", "aligned")
-    _refused(lib, bwd(grad_out=odd), "gsplat_pose_delta_backward", "aligned")
-    _refused(lib, bwd(row_index=odd), "gsplat_pose_delta_backward", "aligned")
-    _refused(lib, decay(grad=odd), "gsplat_pose_delta_decay", "aligned")
+    refused(lib, fwd(c2w=odd), "gsplat_pose_delta_forward", "aligned")
+    refused(lib, bwd(grad_out=odd), "gsplat_pose_delta_backward", "aligned")
+    refused(lib, bwd(row_index=odd), "gsplat_pose_delta_backward", "aligned")
+    refused(lib, decay(grad=odd), "gsplat_pose_delta_decay", "aligned")
     del buf
 
 
@@ -241,12 +218,6 @@ def test_host_active_clamp_is_finite_and_matches_the_oracle(host):
 
 
 # ---- TrainConfig / Trainer ---------------------------------------------------------------------------------------------------------
-def _model():
-    model_mod = importlib.import_module(PKG + ".model")
-    z = torch.zeros
-    return model_mod.GaussianModel(dict(pos=z(4, 3), f_dc=z(4, 3), f_rest=z(4, 45), opacity_raw=z(4), scale_raw=z(4, 3), q_raw=z(4, 4)), device="cpu")
-
-
 VIEWS = [dict(c2w=torch.eye(4), H=8, W=8, fx=10.0, fy=10.0, cx=4.0, cy=4.0, image=torch.zeros(8, 8, 3), idx=k) for k in range(3)]
 
 
@@ -254,13 +225,13 @@ def test_the_mode_is_off_by_default_and_a_trainer_with_it_has_a_table(gs):
     training = importlib.import_module(PKG + ".training")
     c = training.TrainConfig()
     assert (c.pose_opt, c.pose_lr_init, c.pose_lr_final, c.pose_lr_delay_mult, c.pose_lr_max_steps, c.pose_reg) == (False, 1e-5, 1e-7, 0.0, 30000, 1e-6)
-    assert training.Trainer(_model()).poses is None
-    assert training.Trainer(_model(), training.TrainConfig(), None, cameras=VIEWS, pose_views=7).poses is None
-    tr = training.Trainer(_model(), training.TrainConfig(pose_opt=True), cameras=VIEWS)              # (the constructor launches nothing)
+    assert training.Trainer(zero_model()).poses is None
+    assert training.Trainer(zero_model(), training.TrainConfig(), None, cameras=VIEWS, pose_views=7).poses is None
+    tr = training.Trainer(zero_model(), training.TrainConfig(pose_opt=True), cameras=VIEWS)              # (the constructor launches nothing)
     assert isinstance(tr.poses, gs.poses.PoseTable) and tuple(tr.poses.params.shape) == (3, 9) and tr.poses.name == "pose"
     assert not tr.poses.params.any() and not tr.poses.grad.any() and tr.exposure is None and tr.bilagrid is None
     assert tr.poses.optimizer.eps == 1e-8 and tr.poses.optimizer is not tr.optimizer
-    tr = training.Trainer(_model(), training.TrainConfig(pose_opt=True), cameras=VIEWS, pose_views=5)
+    tr = training.Trainer(zero_model(), training.TrainConfig(pose_opt=True), cameras=VIEWS, pose_views=5)
     assert tuple(tr.poses.params.shape) == (5, 9)
     sd = tr.poses.state_dict()
     assert set(sd) == {"params", "exp_avg", "exp_avg_sq", "step"} and sd["step"] == 0
@@ -273,7 +244,7 @@ def test_the_mode_is_off_by_default_and_a_trainer_with_it_has_a_table(gs):
 @pytest.mark.parametrize("other", ["exposure", "bilagrid"])
 def test_pose_opt_is_accepted_together_with_a_colour_table(gs, other):
     training = importlib.import_module(PKG + ".training")
-    tr = training.Trainer(_model(), training.TrainConfig(pose_opt=True, **{other: True}), cameras=VIEWS, pose_views=4)
+    tr = training.Trainer(zero_model(), training.TrainConfig(pose_opt=True, **{other: True}), cameras=VIEWS, pose_views=4)
     assert tuple(tr.poses.params.shape) == (4, 9) and getattr(tr, other) is not None and getattr(tr, other).n_views == 3
     assert tr._tables == [getattr(tr, other), tr.poses]                  # the fixed order of the all-reduces
     with pytest.raises(ValueError, match="idx"):                         # 'idx' must be valid for EVERY table: 3 is a row of the poses only
@@ -288,21 +259,21 @@ def test_trainer_refuses_a_pose_opt_that_is_not_a_bool(value):
     cfg = training.TrainConfig()
     cfg.pose_opt = value                                                 # (the fields of a config can be set after it is made)
     with pytest.raises(ValueError, match="pose_opt"):
-        training.Trainer(_model(), cfg, cameras=VIEWS)
+        training.Trainer(zero_model(), cfg, cameras=VIEWS)
 
 
 def test_trainer_refuses_the_mode_without_a_number_of_images_and_bad_numbers():
     training = importlib.import_module(PKG + ".training")
     with pytest.raises(ValueError, match="pose_views"):
-        training.Trainer(_model(), training.TrainConfig(pose_opt=True))
+        training.Trainer(zero_model(), training.TrainConfig(pose_opt=True))
     for bad in (0, -1, 2.0, True):
         with pytest.raises(ValueError, match="n_views"):
-            training.Trainer(_model(), training.TrainConfig(pose_opt=True), pose_views=bad)
+            training.Trainer(zero_model(), training.TrainConfig(pose_opt=True), pose_views=bad)
     for field, bad in (("pose_reg", -1.0), ("pose_lr_init", float("nan")), ("pose_lr_final", float("inf")), ("pose_lr_delay_mult", True),
                        ("pose_lr_max_steps", 0), ("pose_lr_max_steps", 2.5)):
         with pytest.raises(ValueError, match=field):
-            training.Trainer(_model(), training.TrainConfig(pose_opt=True, **{field: bad}), cameras=VIEWS)
-    tr = training.Trainer(_model(), training.TrainConfig(), cameras=VIEWS)
+            training.Trainer(zero_model(), training.TrainConfig(pose_opt=True, **{field: bad}), cameras=VIEWS)
+    tr = training.Trainer(zero_model(), training.TrainConfig(), cameras=VIEWS)
     with pytest.raises(ValueError, match="pose_opt"):
         tr.evaluate(VIEWS, refined_poses=True)
     with pytest.raises(ValueError, match="refined_poses"):
@@ -312,7 +283,7 @@ def test_trainer_refuses_the_mode_without_a_number_of_images_and_bad_numbers():
 @pytest.mark.parametrize("idx", ["missing", None, -1, 3, 1.0, True, "0"])
 def test_step_refuses_a_view_without_a_valid_idx_before_anything_is_queued(idx):
     training = importlib.import_module(PKG + ".training")
-    tr = training.Trainer(_model(), training.TrainConfig(pose_opt=True), cameras=VIEWS)
+    tr = training.Trainer(zero_model(), training.TrainConfig(pose_opt=True), cameras=VIEWS)
     view = dict(VIEWS[0])
     if idx == "missing":
         del view["idx"]

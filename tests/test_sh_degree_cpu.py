@@ -10,7 +10,6 @@ short rounds less often, not more.
 """
 import ctypes as C
 import importlib
-import os
 
 import numpy as np
 import pytest
@@ -18,6 +17,7 @@ import torch
 
 from oracle import torch_port as tp
 from tests import util
+from tests.abi_checks import header_text
 from tests.cpu_frame import hm, ptr  # noqa: F401  (hm is a fixture)
 
 abi = importlib.import_module("3d-gaussian-splatting-for-novel-view-synthesis_amd._abi")
@@ -133,8 +133,7 @@ def test_host_math_refuses_a_degree_outside_0_to_3(hm, scene):
 def _macros():
     """The three function-like degree macros of the header, evaluated by the C compiler for d = 0..3."""
     import re
-    txt = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "gsplat_mi355x.h")).read()
-    found = dict(re.findall(r"^#define\s+(GSPLAT_[A-Z]+_SH_DEGREE)\(d\)\s+(\(\(3 - \(d\)\) << \d+\))", txt, flags=re.M))
+    found = dict(re.findall(r"^#define\s+(GSPLAT_[A-Z]+_SH_DEGREE)\(d\)\s+(\(\(3 - \(d\)\) << \d+\))", header_text(comments=True), flags=re.M))
     return {name: [eval(body.replace("(d)", f"({d})")) for d in range(4)] for name, body in found.items()}
 
 

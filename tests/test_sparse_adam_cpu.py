@@ -2,45 +2,32 @@
 gsplat_adam_step_rows refuses on the host; the trainer switch; ops.VisibleSet on CPU tensors, its all_reduce over gloo; what
 GaussianAdam.step(visible=...) refuses."""
 import ctypes as C
-import datetime
+import functools
 import importlib
-import os
-import re
-import socket
 import types
 
 import pytest
 import torch
 
+from tests import abi_checks
+from tests.abi_checks import check_entries
+from tests.ranks import run_ranks
+
 PKG = "3d-gaussian-splatting-for-novel-view-synthesis_amd"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+refused = functools.partial(abi_checks.refused, detail=True)
 abi = importlib.import_module(PKG + "._abi")
 NEW = ("gsplat_visible_set", "gsplat_frame_visible_set", "gsplat_adam_step_rows")
 SHAPES = {"pos": (5, 3), "opacity_raw": (5,), "f_dc": (5, 3), "f_rest": (5, 45), "scale_raw": (5, 3), "q_raw": (5, 4)}
 
 
 def test_the_three_entries_are_declared_exported_and_mirrored_at_abi_12():
-    txt = open(os.path.join(ROOT, "include", "gsplat_mi355x.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    handle = C.CDLL(abi.LIB_PATH)
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, code), f"{name} is not declared in the header"
-        assert hasattr(handle, name), f"{name} is not exported"
-        assert name in abi.SIGNATURES
-    assert "#define GSPLAT_ABI_VERSION 12" in re.sub(r"[ \t]+", " ", txt)
-    assert abi.ABI_VERSION == 12 and abi.lib().gsplat_abi_version() == 12
+    check_entries(dict(zip(NEW, (6, 7, 9))), returns=("int",))
     # the argument lists, as the header gives them
     assert abi.SIGNATURES["gsplat_visible_set"][1] == [C.c_int64, C.c_int64, C.POINTER(abi.View), C.c_void_p, C.c_void_p, C.c_void_p]
     assert abi.SIGNATURES["gsplat_frame_visible_set"][1] == [C.c_int64, C.c_int64, C.POINTER(abi.View), C.c_void_p, C.c_int64, C.c_void_p,
                                                              C.c_void_p]
     assert abi.SIGNATURES["gsplat_adam_step_rows"][1] == [C.c_int32, C.POINTER(abi.AdamGroup), C.POINTER(C.c_int32), C.c_int64, C.c_void_p,
                                                           C.c_float, C.c_float, C.c_float, C.c_void_p]
-
-
-def _refused(lib, status, name):
-    assert status == abi.GSPLAT_ERR_BAD_ARG, (name, status)
-    msg = lib.gsplat_last_error()
-    assert name.encode() in msg and len(msg) > len(name) + 2, msg
 
 
 def test_adam_step_rows_refuses_bad_arguments_on_the_host():
@@ -55,28 +42,28 @@ def test_adam_step_rows_refuses_bad_arguments_on_the_host():
         w = widths if widths is not None else (C.c_int32 * 1)(width)
         return lib.gsplat_adam_step_rows(n_groups, arr, w, n_rows, mask, 0.9, 0.999, 1e-15, None)
 
-    _refused(lib, call(mask=None), name)                                     # a null mask
+    refused(lib, call(mask=None), name)                                     # a null mask
     assert b"visible" in lib.gsplat_last_error()
-    _refused(lib, call(width=0, n=0, n_rows=0), name)                        # a width 0
-    _refused(lib, call(width=0), name)
-    _refused(lib, call(width=-3, n=-12), name)
-    _refused(lib, call(n=13), name)                                          # n != n_rows * width
-    _refused(lib, call(n=12, width=4, n_rows=4), name)
-    _refused(lib, call(n=12, width=3, n_rows=5), name)
+    refused(lib, call(width=0, n=0, n_rows=0), name)                        # a width 0
+    refused(lib, call(width=0), name)
+    refused(lib, call(width=-3, n=-12), name)
+    refused(lib, call(n=13), name)                                          # n != n_rows * width
+    refused(lib, call(n=12, width=4, n_rows=4), name)
+    refused(lib, call(n=12, width=3, n_rows=5), name)
     assert b"group 0" in lib.gsplat_last_error()
     nine = (abi.AdamGroup * 9)(*[abi.AdamGroup(0, None, None, None, None, 0.01, 1, None) for _ in range(9)])
     w9 = (C.c_int32 * 9)(*[1] * 9)
-    _refused(lib, call(n_groups=9, groups=nine, widths=w9, n_rows=0), name)  # 9 groups
+    refused(lib, call(n_groups=9, groups=nine, widths=w9, n_rows=0), name)  # 9 groups
     assert call(n_groups=8, groups=nine, widths=w9, n_rows=0) == abi.GSPLAT_OK          # eight empty groups: nothing to launch
-    _refused(lib, call(n_groups=-1), name)
-    _refused(lib, lib.gsplat_adam_step_rows(1, None, (C.c_int32 * 1)(3), 4, p, 0.9, 0.999, 1e-15, None), name)
-    _refused(lib, lib.gsplat_adam_step_rows(1, (abi.AdamGroup * 1)(abi.AdamGroup(12, p, p, p, p, 0.01, 1, None)), None, 4, p, 0.9, 0.999, 1e-15,
+    refused(lib, call(n_groups=-1), name)
+    refused(lib, lib.gsplat_adam_step_rows(1, None, (C.c_int32 * 1)(3), 4, p, 0.9, 0.999, 1e-15, None), name)
+    refused(lib, lib.gsplat_adam_step_rows(1, (abi.AdamGroup * 1)(abi.AdamGroup(12, p, p, p, p, 0.01, 1, None)), None, 4, p, 0.9, 0.999, 1e-15,
                                             None), name)
-    _refused(lib, call(n_rows=-1, n=-3), name)
+    refused(lib, call(n_rows=-1, n=-3), name)
     # what gsplat_adam_step_multi refuses in a group: step < 1, a NULL array of a non-empty group -- the second of two groups
     for bad in (abi.AdamGroup(12, p, p, p, p, 0.01, 0, None), abi.AdamGroup(12, p, None, p, p, 0.01, 1, None)):
         two = (abi.AdamGroup * 2)(abi.AdamGroup(4, p, p, p, p, 0.01, 1, None), bad)
-        _refused(lib, call(n_groups=2, groups=two, widths=(C.c_int32 * 2)(1, 3)), name)
+        refused(lib, call(n_groups=2, groups=two, widths=(C.c_int32 * 2)(1, 3)), name)
         assert b"group 1" in lib.gsplat_last_error()
     del buf
 
@@ -89,7 +76,7 @@ def test_visible_set_entries_refuse_bad_arguments_on_the_host():
     for status in (lib.gsplat_visible_set(4, 8, None, p, p, None), lib.gsplat_visible_set(-1, 8, C.byref(v), p, p, None),
                    lib.gsplat_visible_set(4, -1, C.byref(v), p, p, None), lib.gsplat_visible_set(4, 8, C.byref(v), None, p, None),
                    lib.gsplat_visible_set(4, 8, C.byref(v), p, None, None)):
-        _refused(lib, status, "gsplat_visible_set")
+        refused(lib, status, "gsplat_visible_set")
     assert lib.gsplat_visible_set(0, 8, C.byref(v), p, p, None) == abi.GSPLAT_OK                     # n == 0: nothing is launched
     aligned = C.c_void_p((C.addressof(buf) + 255) & ~255)
     for status in (lib.gsplat_frame_visible_set(4, 8, None, aligned, 1 << 30, p, None),
@@ -97,7 +84,7 @@ def test_visible_set_entries_refuse_bad_arguments_on_the_host():
                    lib.gsplat_frame_visible_set(4, 8, C.byref(v), aligned, 1 << 30, None, None),
                    lib.gsplat_frame_visible_set(4, 8, C.byref(v), C.c_void_p(aligned.value + 16), 1 << 30, p, None),
                    lib.gsplat_frame_visible_set(4, 8, C.byref(v), aligned, 16, p, None)):            # an arena too small
-        _refused(lib, status, "gsplat_frame_visible_set")
+        refused(lib, status, "gsplat_frame_visible_set")
     del buf
 
 
@@ -159,14 +146,6 @@ def test_visible_set_record_on_cpu(gs):
             gs.render_gaussians(z(5, 3), z(5, 3), z(5, 45), z(5), z(5, 3), z(5, 4), torch.eye(4), 16, 16, 10., 10., 8., 8.)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _rank_bytes(rank, n=301):
     g = torch.Generator().manual_seed(40 + rank)
     data = (torch.rand(n, generator=g) < 0.3).to(torch.uint8)
@@ -174,10 +153,8 @@ def _rank_bytes(rank, n=301):
     return data
 
 
-def _worker(rank, world, port, q):
+def _worker(rank, world):
     import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
     gs = importlib.import_module(PKG)
     rec = gs.VisibleSet(301, "cpu")
     rec.data.copy_(_rank_bytes(rank))
@@ -185,27 +162,15 @@ def _worker(rank, world, port, q):
     sub = gs.VisibleSet(301, "cpu")
     sub.data.copy_(_rank_bytes(rank))
     sub.all_reduce(dist.new_group([0, 1]))
-    q.put((rank, rec.data.numpy().copy(), sub.data.numpy().copy()))
-    dist.barrier()
-    dist.destroy_process_group()
+    return rec.data.numpy().copy(), sub.data.numpy().copy()
 
 
 def test_visible_set_all_reduce_over_gloo_is_the_union():
-    import torch.multiprocessing as mp
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=120) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    got = run_ranks(_worker, 2, answer_s=120, join_s=60)
     a, b = _rank_bytes(0), _rank_bytes(1)
     union = ((a != 0) | (b != 0)).numpy()
     assert union.any() and not union.all() and ((a != 0) != (b != 0)).any()
-    for rank, data, sub in got:
+    for rank, (data, sub) in enumerate(got):
         assert ((data != 0) == union).all(), rank                  # the element-wise OR, on both ranks
         assert (data == torch.maximum(a, b).numpy()).all()         # (as a MAX of the bytes: the same bytes on every rank)
         assert (sub == data).all()

@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.util import bits
+
 V = 4
 GRID = (3, 5, 4)                     # (X, Y, L)
 
@@ -58,10 +60,6 @@ def test_params_start_at_the_identity_and_zero_grad_clears_grad(gs, kind):
     assert not t.grad.any()
 
 
-def _bits(x):
-    return x.detach().contiguous().view(torch.int32)
-
-
 @pytest.mark.parametrize("kind", KINDS)
 def test_state_dict_round_trips_bit_for_bit(gs, kind):
     a, b = _make(gs, kind), _make(gs, kind)
@@ -78,8 +76,8 @@ def test_state_dict_round_trips_bit_for_bit(gs, kind):
     b.load_state_dict(sd)
     back = b.state_dict()
     for k in ("params", "exp_avg", "exp_avg_sq"):
-        assert torch.equal(_bits(back[k]), _bits(sd[k])), k
-    assert back["step"] == 5 and torch.equal(_bits(b.params), _bits(a.params))
+        assert torch.equal(bits(back[k]), bits(sd[k])), k
+    assert back["step"] == 5 and torch.equal(bits(b.params), bits(a.params))
 
 
 @pytest.mark.parametrize("kind", KINDS)
