@@ -9,7 +9,7 @@ import numbers
 import torch
 
 from . import optim
-from .ops import _f32, _stream_ptr
+from ._dev import _f32, _stream_ptr
 
 # The parts of an op.  `arg`: what its second argument is called in messages.  shapes(image, table) -> (the image's shape, the integers
 # both entries take after the arrays); ValueError for a pair that does not fit.  forward(x, t, dims, out, stream) and

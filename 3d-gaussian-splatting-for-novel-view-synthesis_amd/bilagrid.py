@@ -22,7 +22,7 @@ import torch
 
 from . import _abi
 from ._viewtable import ViewFn, ViewOp, ViewTable
-from .ops import _f32, _p, _stream_ptr
+from ._dev import _f32, _p, _stream_ptr
 
 DEFAULT_SHAPE = (16, 16, 8)      # (X, Y, L)
 

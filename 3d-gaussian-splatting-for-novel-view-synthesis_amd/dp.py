@@ -13,7 +13,16 @@ waited together, so RCCL can pipeline them.
 import torch
 import torch.distributed as dist
 
+from ._workspace import OFFSCREEN_MSG
+
 PARAM_NAMES = ("pos", "opacity_raw", "f_dc", "f_rest", "scale_raw", "q_raw")
+
+
+def world_and_rank(group=None):
+    """(world size, this process's rank) of `group`; (1, 0) without torch.distributed."""
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_world_size(group), dist.get_rank(group)
+    return 1, 0
 
 
 def shard_views(n_views, rank, world_size):
@@ -71,23 +80,21 @@ def agree_status(code, group=None, device=None):
 def status_of(err):
     """The status code of what a rank's own work ended with: None -> STATUS_OK, the reference's off-screen Exception (render.py:235-236)
     -> STATUS_OFFSCREEN, any other exception -> STATUS_ERROR.  (STATUS_REDO is the caller's: only a training pass can be repeated.)"""
-    from . import ops
     if err is None:
         return STATUS_OK
-    return STATUS_OFFSCREEN if str(err) == ops.OFFSCREEN_MSG else STATUS_ERROR
+    return STATUS_OFFSCREEN if str(err) == OFFSCREEN_MSG else STATUS_ERROR
 
 
 def raise_agreed(status, err, what):
     """After agree_status(): every rank raises, or none does.  A status below STATUS_OFFSCREEN returns; otherwise the rank that failed
     raises its own exception `err`, and a rank that did not (err None) raises what its peer's status stands for -- the off-screen
     Exception, or a RuntimeError naming `what` was running."""
-    from . import ops
     if status < STATUS_OFFSCREEN:
         return
     if err is not None:
         raise err
     if status == STATUS_OFFSCREEN:
-        raise Exception(ops.OFFSCREEN_MSG + " (on another rank of the data-parallel group)")
+        raise Exception(OFFSCREEN_MSG + " (on another rank of the data-parallel group)")
     raise RuntimeError(f"another rank of the data-parallel group failed in {what}")
 
 

@@ -22,7 +22,7 @@ import torch
 
 from . import _abi
 from ._viewtable import ViewFn, ViewOp, ViewTable
-from .ops import _p
+from ._dev import _p
 
 
 def _shapes(image, params):

@@ -23,7 +23,7 @@ There is no CPU fallback.
 import torch
 
 from . import _abi
-from .ops import _p, _stream_ptr
+from ._dev import _gpu_f32, _launch, _p, _stream_ptr
 
 CAMERA_FLOATS = _abi.GSPLAT_FILTER3D_CAMERA_FLOATS
 PARAMS = ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")
@@ -33,14 +33,6 @@ def _real(x, name):
     if isinstance(x, bool) or not isinstance(x, (int, float)) or not 0.0 <= x < float("inf"):
         raise ValueError(f"{name} must be a finite number >= 0, not {x!r}")
     return float(x)
-
-
-def _gpu_f32(t, name):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise RuntimeError(f"filter3d needs contiguous fp32 GPU tensors ({name}; there is no CPU fallback)")
-    return t
 
 
 def pack_cameras(views, device):
@@ -62,8 +54,8 @@ def compute(pos, cameras, s=0.2, near=0.2, margin=0.15, out=None):
     the seen ones; no camera, or nobody seen: 0).  `cameras`: pack_cameras(...).  A camera sees k iff z > near and its projection lies
     inside the image widened by `margin` of its size on every side.  One library call (a 4-byte memset and two launches)."""
     s, near, margin = _real(s, "s"), _real(near, "near"), _real(margin, "margin")
-    pos = _gpu_f32(pos.detach() if isinstance(pos, torch.Tensor) else pos, "pos")
-    cameras = _gpu_f32(cameras, "cameras")
+    pos = _gpu_f32(pos.detach() if isinstance(pos, torch.Tensor) else pos, "pos", "filter3d")
+    cameras = _gpu_f32(cameras, "cameras", "filter3d")
     n = pos.shape[0]
     if pos.numel() != n * 3:
         raise ValueError(f"pos has shape {tuple(pos.shape)}, expected [N, 3]")
@@ -73,7 +65,7 @@ def compute(pos, cameras, s=0.2, near=0.2, margin=0.15, out=None):
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty(n, dtype=torch.float32, device=dev)
-        elif _gpu_f32(out, "out").shape != (n,) or out.device != dev:
+        elif _gpu_f32(out, "out", "filter3d").shape != (n,) or out.device != dev:
             raise ValueError(f"out has shape {tuple(out.shape)} on {out.device}, expected ({n},) on {dev}")
         lib = _abi.lib()
         # the maximum's word: a fresh block from the caching allocator per call, so that calls on different streams never share one
@@ -84,7 +76,7 @@ def compute(pos, cameras, s=0.2, near=0.2, margin=0.15, out=None):
 
 
 def _check_triple(scale_raw, opacity_raw, filt):
-    scale_raw, opacity_raw, filt = _gpu_f32(scale_raw, "scale_raw"), _gpu_f32(opacity_raw, "opacity_raw"), _gpu_f32(filt, "filt")
+    scale_raw, opacity_raw, filt = _gpu_f32(scale_raw, "scale_raw", "filter3d"), _gpu_f32(opacity_raw, "opacity_raw", "filter3d"), _gpu_f32(filt, "filt", "filter3d")
     n = scale_raw.shape[0]
     if scale_raw.numel() != n * 3 or opacity_raw.numel() != n or filt.numel() != n:
         raise ValueError(f"scale_raw {tuple(scale_raw.shape)}, opacity_raw {tuple(opacity_raw.shape)}, filt {tuple(filt.shape)}: expected "
@@ -136,13 +128,11 @@ def backward_into(scale_raw, opacity_raw, filt, g_scale_out, g_opacity_out, g_sc
     n = _check_triple(scale_raw, opacity_raw, filt)
     for name, t, ref in (("g_scale_out", g_scale_out, scale_raw), ("g_opacity_out", g_opacity_out, opacity_raw),
                          ("g_scale_raw", g_scale_raw, scale_raw), ("g_opacity_raw", g_opacity_raw, opacity_raw)):
-        if _gpu_f32(t, name).numel() != ref.numel() or t.device != ref.device:
+        if _gpu_f32(t, name, "filter3d").numel() != ref.numel() or t.device != ref.device:
             raise ValueError(f"{name} has shape {tuple(t.shape)} on {t.device}, expected {tuple(ref.shape)} on {ref.device}")
     dev = scale_raw.device
-    with torch.cuda.device(dev):
-        _abi.check(_abi.lib().gsplat_filter3d_apply_backward(n, _p(scale_raw), _p(opacity_raw), _p(filt), _p(g_scale_out), _p(g_opacity_out),
-                                                             _p(g_scale_raw), _p(g_opacity_raw), 1 if accumulate else 0, _stream_ptr(dev)),
-                   "gsplat_filter3d_apply_backward")
+    _launch("gsplat_filter3d_apply_backward", dev, n, _p(scale_raw), _p(opacity_raw), _p(filt), _p(g_scale_out), _p(g_opacity_out),
+            _p(g_scale_raw), _p(g_opacity_raw), 1 if accumulate else 0)
 
 
 @torch.no_grad()

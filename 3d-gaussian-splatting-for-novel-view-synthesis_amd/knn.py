@@ -25,23 +25,15 @@ import math
 import torch
 
 from . import _abi
-from .ops import _p, _stream_ptr
+from ._dev import _gpu_f32, _p, _stream_ptr
 
 BOX = _abi.GSPLAT_KNN_BOX
-
-
-def _gpu_f32(t, name):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise RuntimeError(f"knn needs contiguous fp32 GPU tensors ({name}; there is no CPU fallback)")
-    return t
 
 
 def mean_dist2(points, out=None):
     """dist2 [N] fp32 of points [N, 3] (the module docstring has the definition).  One library call on the current stream; the scratch
     (about 40 N bytes) is a fresh block from the caching allocator per call, so that calls on different streams never share one."""
-    points = _gpu_f32(points.detach() if isinstance(points, torch.Tensor) else points, "points")
+    points = _gpu_f32(points.detach() if isinstance(points, torch.Tensor) else points, "points", "knn")
     n = points.shape[0] if points.dim() > 0 else 0
     if points.dim() != 2 or points.shape[1] != 3:
         raise ValueError(f"points has shape {tuple(points.shape)}, expected [N, 3]")
@@ -49,7 +41,7 @@ def mean_dist2(points, out=None):
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty(n, dtype=torch.float32, device=dev)
-        elif _gpu_f32(out, "out").shape != (n,) or out.device != dev:
+        elif _gpu_f32(out, "out", "knn").shape != (n,) or out.device != dev:
             raise ValueError(f"out has shape {tuple(out.shape)} on {out.device}, expected ({n},) on {dev}")
         lib = _abi.lib()
         size = int(lib.gsplat_knn_scratch_bytes(n))

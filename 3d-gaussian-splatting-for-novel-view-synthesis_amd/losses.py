@@ -15,7 +15,8 @@ import ctypes as C
 import torch
 
 from . import _abi
-from .ops import _f32, _p, _stage, _stream_ptr
+from ._dev import _f32, _p, _stream_ptr
+from ._timing import _stage
 
 
 class _LossFn(torch.autograd.Function):

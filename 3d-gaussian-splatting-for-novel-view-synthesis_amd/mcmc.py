@@ -17,7 +17,7 @@ import ctypes as C
 import torch
 
 from . import _abi
-from .ops import _p, _stream_ptr
+from ._dev import _launch, _p, _stream_ptr
 
 PARAMS = ("pos", "f_dc", "f_rest", "opacity_raw", "scale_raw", "q_raw")
 _WIDTH = {"pos": 3, "f_dc": 3, "f_rest": 45, "opacity_raw": 1, "scale_raw": 3, "q_raw": 4}
@@ -70,9 +70,7 @@ def add_noise(model_or_tensors, scale, seed, iteration):
     _check_seed(seed, iteration)
     t, n = _tensors(model_or_tensors)
     dev = t["pos"].device
-    with torch.cuda.device(dev):
-        _abi.check(_abi.lib().gsplat_mcmc_noise(n, _p(t["pos"]), _p(t["opacity_raw"]), _p(t["scale_raw"]), _p(t["q_raw"]), float(scale),
-                                                seed, iteration, _stream_ptr(dev)), "gsplat_mcmc_noise")
+    _launch("gsplat_mcmc_noise", dev, n, _p(t["pos"]), _p(t["opacity_raw"]), _p(t["scale_raw"]), _p(t["q_raw"]), float(scale), seed, iteration)
 
 
 @torch.no_grad()

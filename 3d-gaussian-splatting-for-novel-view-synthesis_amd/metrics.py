@@ -24,10 +24,9 @@ gradient and no CPU fallback.
 import collections
 
 import torch
-import torch.distributed as dist
 
 from . import _abi, dp, harness, losses, ops
-from .ops import _f32, _p, _stream_ptr
+from ._dev import _f32, _p, _stream_ptr
 
 ImageMetrics = collections.namedtuple("ImageMetrics", ("psnr", "ssim", "l1", "mse", "affine"))
 MAX_BATCH = 65535          # images per call: the z extent of the kernels' grid (include/gsplat_mi355x.h)
@@ -159,12 +158,6 @@ def _check_views(views):
                 raise ValueError(f"view {k}: 'mask' must be bool or uint8 (nonzero = valid), not {mask.dtype}")
 
 
-def _world(group):
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_world_size(group), dist.get_rank(group)
-    return 1, 0
-
-
 def aggregate(rows, idx, group=None):
     """The report of evaluate() from per-view rows.  `rows`: [n_local, 4] fp32 = (psnr, ssim, l1, mse) of THIS rank's views -- under a
     process group the views dp.shard_views(len(idx), rank, world) of the list, in that order; `idx`: the label of every view of the
@@ -174,7 +167,7 @@ def aggregate(rows, idx, group=None):
     forms the same numbers from the same bits.  An image without a
     valid pixel (NaN) or equal to its target (psnr = +inf) enters the means as it is."""
     n = len(idx)
-    world, rank = _world(group)
+    world, rank = dp.world_and_rank(group)
     if world > 1:
         mine = dp.shard_views(n, rank, world)
         if rows.shape[0] != len(mine):
@@ -223,7 +216,7 @@ def evaluate(params, views, *, sh_degree=3, lowpass=0.0, antialias=False, backgr
         raise ValueError(f"colour_correct must be a bool, not {colour_correct!r}")
     p = harness._as_dict(params)
     dev = p['pos'].device
-    world, rank = _world(group)
+    world, rank = dp.world_and_rank(group)
     mine = dp.shard_views(len(views), rank, world)
     idx = [int(v['idx']) if v.get('idx') is not None else k for k, v in enumerate(views)]
     rows = torch.empty((len(mine), 4), dtype=torch.float32, device=dev)

@@ -19,338 +19,27 @@ There is no CPU path: CPU tensors, or a missing library, raise.
 
 The render entries turn their arguments into ONE immutable FrameSpec (_frame_spec: camera, mode, input names), which the forward
 pass keeps on the frame (_Frame.spec) for the backward pass; the facts of one autograd call (pose, need_grad, route) lie beside it.
+
+This file holds the frame (spec, forward halves, backward pass, gradient routes, public entries) and the switches that tests and tools
+assign (_composite, _sh_jacobian, _deterministic: read here only, at call time).  What outlives a frame lives in modules that never
+import this one -- _dev, _timing, _workspace, records -- and is re-exported here under the names it always had.
 """
-import collections
 import contextlib
 import contextvars
 import ctypes as C
 import dataclasses
-import weakref
 
 import torch
 
-from . import _abi
+from . import _abi, _timing
+from ._dev import _f32, _launch, _p, _stream_ptr  # noqa: F401
+from ._timing import StageTimer, _stage, set_stage_timer  # noqa: F401
+from ._workspace import (OFFSCREEN_MSG, PINNED_SLOTS, DeferredChecks, PairCapacityExceeded, _deferred_stack, _note_counts, _Unread,  # noqa: F401
+                         _Workspace, _ws, binned_pairs, capacity_key, deferred_checks, forward_modes, read_counts, render_stats, reset_pair_capacity, run_deferred)
+from .records import (ContributionStats, DensifyStats, VisibleSet, _stats, _stats_absgrad, _visible, absgrad_calls, add_frame_records,  # noqa: F401
+                      densify_stats, frame_records, visible_set)
 
-OFFSCREEN_MSG = "All projected points are off-screen"      # reference render.py:236
-
-
-def _stream_ptr(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _f32(t, shape, name):
-    """Detached, contiguous fp32 view/copy of a tensor argument (reference tensors are already fp32 contiguous)."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    # (the usual case first: an fp32, contiguous, aligned GPU tensor of the right shape is used as it stands -- only its
-    #  address travels to the library, autograd never sees it)
-    if t.dtype is torch.float32 and t.is_cuda and t.shape == shape and t.is_contiguous() and not t.data_ptr() % 16:
-        return t
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} is on {t.device}: the MI355X rasterizer needs GPU tensors (there is no CPU fallback)")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    t = t.contiguous()
-    if t.data_ptr() % 16:            # the kernels stage rows with 16-byte accesses (views into a larger storage may be offset)
-        t = t.clone()
-    return t
-
-
-class PairCapacityExceeded(RuntimeError):
-    """A frame rendered without waiting for its pair count (deferred_checks) had more (list, Gaussian) pairs than the buffers
-    kept from earlier frames: its image and gradients are invalid.  The capacity has been raised; render it again."""
-
-
-PINNED_SLOTS = 256      # counter blocks in flight per (device, stream) before one is reused
-
-
-def capacity_key(device, view, n):
-    """Pair capacities are kept per (device, image size, power-of-two bucket of the Gaussian count, filter mode): one large scene
-    does not make every later frame of a small one allocate, launch over and (deterministic mode) clear its buffers, and a
-    filtered frame -- the low-pass grows every footprint, and the pair count with it -- learns its own capacity."""
-    return (device.type, device.index, view.H, view.W, max(int(n), 1).bit_length(), getattr(view, "filter", 0))
-
-
-class _Workspace:
-    """Grow-only scratch buffers, the persistent counter block of gsplat_project, a ring of pinned counter blocks and one
-    event per (device, stream): calls on different streams never share them (scratch is dead after each call, in stream
-    order).  `capacity`: per capacity_key(), the largest pair count seen x 1.25 (sizes the buffers of frames that do not wait)."""
-
-    def __init__(self):
-        self.scratch = {}
-        self.pinned = {}
-        self.events = {}
-        self.counters = {}
-        self.capacity = {}
-        self.slot = {}
-        self.owners = {}            # per (device, stream): slot -> weak reference to the DeferredChecks that still has to read it
-        self.event_pool = {}        # per device: events of frames whose counters have been read, handed out again (get_event(fresh=True))
-        self.sizes = {}             # (n, capacity, H, W, flags) -> (frame bytes, bin scratch bytes): host arithmetic, cached
-
-    def get_counter_block(self, device, nbytes, key=None):
-        """Zeroed once; every gsplat_project call leaves it zeroed again (include/gsplat_mi355x.h).  (`key`: the caller's
-        _key(device), when it has it already -- looking up the current stream is the costliest thing these methods do.)"""
-        key = key or self._key(device)
-        buf = self.counters.get(key)
-        if buf is None or buf.numel() < nbytes:
-            buf = torch.zeros(int(nbytes), dtype=torch.uint8, device=device)
-            self.counters[key] = buf
-        return buf
-
-    def next_pinned(self, device, key=None, owner=None):
-        """A pinned, device-mapped counter block nobody else is using.  A slot whose last frame still waits to be looked at by
-        its DeferredChecks (a block left without verify(), or a very long one) is read by that owner first -- the frame
-        finished long ago -- so a ring that comes round never hands out a block somebody still has to read."""
-        key = key or self._key(device)
-        ring = self.pinned.get(key)
-        if ring is None:
-            ring = self.pinned[key] = torch.zeros((PINNED_SLOTS, C.sizeof(_abi.Counts)), dtype=torch.uint8).pin_memory()
-            self.owners[key] = {}
-        i = self.slot.get(key, 0)
-        self.slot[key] = (i + 1) % PINNED_SLOTS
-        owners = self.owners[key]
-        ref = owners.pop(i, None)
-        if ref is not None:
-            prev = ref()
-            if prev is not None:
-                prev._release_slot(key, i)
-        if owner is not None:
-            owners[i] = weakref.ref(owner)
-        return ring[i], i
-
-    def note_pairs(self, ckey, n_binned):
-        want = int(n_binned * 1.25) + 4096
-        if want > self.capacity.get(ckey, 0):
-            self.capacity[ckey] = want
-
-    def pair_capacity(self, ckey):
-        return self.capacity.get(ckey, 0)
-
-    def reset_pair_capacity(self):
-        self.capacity.clear()
-
-    @staticmethod
-    def _key(device):
-        return (device.type, device.index, torch.cuda.current_stream(device).cuda_stream)
-
-    def get_event(self, device, fresh=False, key=None):
-        """One reusable event per stream: gsplat_project records it right behind the counters (fresh: an event of its own,
-        for a frame whose counters are read later)."""
-        if fresh:
-            pool = self.event_pool.get((device.type, device.index))
-            if pool:
-                return pool.pop()             # (its handle exists, and the frame it belonged to is long done)
-        key = key or self._key(device)
-        ev = None if fresh else self.events.get(key)
-        if ev is None:
-            ev = torch.cuda.Event(enable_timing=False, blocking=False)
-            ev.record(torch.cuda.current_stream(device))          # events are created lazily: force the handle to exist
-            if not fresh:
-                self.events[key] = ev
-        return ev
-
-    def recycle_event(self, device, ev):
-        pool = self.event_pool.setdefault((device.type, device.index), [])
-        if len(pool) < 4 * PINNED_SLOTS:
-            pool.append(ev)
-
-    def get_scratch(self, device, nbytes, key=None):
-        key = key or self._key(device)
-        buf = self.scratch.get(key)
-        if buf is None or buf.numel() < nbytes:
-            buf = torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8, device=device)
-            self.scratch[key] = buf
-        return buf
-
-    def frame_sizes(self, lib, n, capacity, view, flags):
-        k = (n, capacity, view.H, view.W, flags)                  # (the filter bits change no size)
-        got = self.sizes.get(k)
-        if got is None:
-            if len(self.sizes) > 4096:
-                self.sizes.clear()
-            got = self.sizes[k] = (lib.gsplat_frame_bytes(n, capacity, C.byref(view), flags),
-                                   lib.gsplat_bin_scratch_bytes(capacity, C.byref(view)))
-        return got
-
-
-def reset_pair_capacity():
-    """Forget the pair capacities kept from earlier frames (a new scene, a new Trainer): the next frame of every (device, image
-    size, Gaussian-count bucket) waits for its own count again."""
-    _ws.reset_pair_capacity()
-
-
-_ws = _Workspace()
-
-
-class StageTimer:
-    """Optional per-stage timing with HIP events recorded on the stream the kernels are launched on (torch's current
-    stream).  bench.py installs one with `set_stage_timer`; when none is installed the hooks cost nothing."""
-
-    def __init__(self, only=None, every=1):
-        self.events = []          # (stage, start_event, end_event)
-        self.only = set(only) if only else None      # restrict to these stages (every event pair costs ~10 us of stream time)
-        self.every = max(1, int(every))              # ... and to every n-th pass (the passes in between run exactly as without a timer)
-        self.passes = 0
-
-    def wants(self, stages):
-        """Does this pass bracket any of `stages`?  (asked ONCE per pass and direction by the render op; counts the passes)"""
-        if self.only is not None and not (self.only & stages):
-            return False
-        self.passes += 1
-        return (self.passes - 1) % self.every == 0
-
-    def totals_ms(self):
-        """stage -> (launches, total milliseconds); call after a device synchronise."""
-        out = {}
-        for name, a, b in self.events:
-            n, t = out.get(name, (0, 0.0))
-            out[name] = (n + 1, t + a.elapsed_time(b))
-        return out
-
-    def reset(self):
-        self.events = []
-
-
-_timer = None
-
-
-def set_stage_timer(timer):
-    global _timer
-    _timer = timer
-
-
-class _stage:
-    __slots__ = ("name", "a")
-
-    def __init__(self, name):
-        self.name = name
-
-    def __enter__(self):
-        self.a = None
-        if _timer is not None and (_timer.only is None or self.name in _timer.only):
-            self.a = torch.cuda.Event(enable_timing=True)
-            self.a.record()
-
-    def __exit__(self, *exc):
-        if self.a is not None and _timer is not None:
-            b = torch.cuda.Event(enable_timing=True)
-            b.record()
-            _timer.events.append((self.name, self.a, b))
-        return False
-
-
-class DeferredChecks:
-    """Render without waiting for the per-frame counters (training loops, frame sequences):
-
-        with ops.deferred_checks() as chk:
-            for view in views: loss(render_gaussians(...)).backward()      # no host synchronisation per view
-        chk.verify()                                                        # ONE wait, then every frame's checks
-
-    Inside the block a render sizes its pair buffers from the capacity kept from earlier frames (x 1.25 of the largest
-    count seen for that image size and Gaussian-count bucket) instead of waiting for its own count, and the SH colour is
-    evaluated inside the projection kernel (one pass over the inputs).  What the reference decides from the counts is decided
-    in verify(): survivors but none on screen -> the same Exception("All projected points are off-screen"), now raised there; no
-    survivor -> the frame was a zero image with zero gradients anyway.  A frame with more pairs than the capacity raises
-    PairCapacityExceeded (capacity raised; render the block again: its results are invalid).  The first render of a size on a
-    device (no capacity known yet) waits like an ordinary one.
-
-    A block that is left by an exception has its frames' counters read then and there (nothing is raised on top of the exception
-    in flight); one that is simply never verified keeps its findings, and its pinned counter blocks are read before the ring
-    hands them to another frame (_Workspace.next_pinned): no block is ever reused unread."""
-
-    def __init__(self):
-        self.pending = []          # _Unread, one per frame whose counters have not been looked at, in frame order
-        self.counts = []
-        self._overflow = self._offscreen = False
-
-    def add(self, pinned, event, capacity, device, ckey, slot):
-        self.pending.append(_Unread(pinned, event, capacity, device, ckey, slot))
-        if len(self.pending) >= PINNED_SLOTS // 2:           # long sequences: look at the oldest frames before their pinned
-            self._drain(len(self.pending) // 2)              # counter blocks come round again (they finished long ago)
-
-    def _drain(self, count):
-        for entry in self.pending[:count]:
-            entry.event.synchronize()
-            counts = _abi.Counts.from_buffer_copy(entry.pinned.numpy().tobytes())
-            self.counts.append(counts)
-            _ws.note_pairs(entry.ckey, counts.n_binned)
-            self._overflow |= entry.capacity is not None and counts.n_binned > entry.capacity
-            self._offscreen |= _abi.lib().gsplat_classify_counts(C.byref(counts)) == _abi.GSPLAT_SCENE_ALL_OFFSCREEN
-            _note_counts(counts)
-            _ws.recycle_event(entry.device, entry.event)
-            ring_key, index = entry.slot
-            owners = _ws.owners.get(ring_key)
-            if owners is not None:
-                ref = owners.get(index)
-                if ref is not None and ref() is self:
-                    del owners[index]
-        del self.pending[:count]
-
-    def _release_slot(self, ring_key, index):
-        """The ring is about to hand slot `index` to another frame: read everything up to the frame that holds it."""
-        for k, entry in enumerate(self.pending):
-            if entry.slot == (ring_key, index):
-                self._drain(k + 1)
-                return
-
-    def __enter__(self):
-        _deferred_stack.append(self)
-        return self
-
-    def __exit__(self, exc_type, exc, tb):
-        _deferred_stack.remove(self)
-        if exc_type is not None and self.pending:           # nobody will call verify(): read the counters now, raise nothing
-            try:
-                self._drain(len(self.pending))
-            except Exception:                                # (a device error while draining must not mask the exception in flight)
-                self.pending = []
-        return False
-
-    def verify(self):
-        self._drain(len(self.pending))
-        overflow, offscreen = self._overflow, self._offscreen
-        self._overflow = self._offscreen = False
-        if offscreen:
-            raise Exception(OFFSCREEN_MSG)
-        if overflow:
-            raise PairCapacityExceeded("more (list, Gaussian) pairs than the buffers kept from earlier frames: render the block again")
-        return self.counts
-
-
-# a frame whose counters are still unread (between the halves of its forward pass, or in a DeferredChecks): its pinned counter block,
-# the event recorded behind the counters, the pair capacity its buffers were sized with (None: it waits for its own count), its device
-# and capacity_key(), and slot = (ring key, index) of the block in the ring, ring key = (device type, device index, stream)
-_Unread = collections.namedtuple("_Unread", "pinned event capacity device ckey slot")
-_deferred_stack = []
-forward_modes = {"waited": 0, "deferred": 0}     # forward passes that waited for their counters / that did not (diagnostics, tests)
 composite_calls = {"forward": 0, "backward": 0}  # passes queued through ONE library call (gsplat_forward_deferred / gsplat_backward)
-
-
-def deferred_checks():
-    return DeferredChecks()
-
-
-def run_deferred(fn, attempts=4):
-    """fn() queues renders (and their backward passes) -- it runs inside deferred_checks() and is REPEATED while one of its frames
-    outgrows the pair buffers kept from earlier frames (the capacity is raised each time; the first frame of a much larger scene
-    does that once).  Returns fn()'s result of the pass that passed its checks; the off-screen exception propagates."""
-    for _ in range(attempts):
-        with deferred_checks() as chk:
-            out = fn()
-        try:
-            chk.verify()
-            return out
-        except PairCapacityExceeded:
-            continue
-    raise RuntimeError(f"the pair buffers overflowed {attempts} times in a row")
-
 
 _sh_jacobian = True      # tests / ablations switch it off: the backward then reads the SH coefficients again (same gradients)
 _composite = True        # tests / ablations switch it off: a deferred frame then goes through the separate library calls
@@ -437,20 +126,14 @@ def _forward_begin(spec, c2w, tensors, pose=False, need_grad=False):
         raise RuntimeError("depth / opacity maps and a background (aux=True, background=...) are not available inside a gradient_route() "
                            "block (factored exchange, folded f_rest step, accumulate_grads): render the frame outside it")
     pos = tensors["pos"]
-    stats = _stats_record(pos)              # (checked before anything else: a wrong record is refused even where nothing is rendered)
-    visible = _visible_record(pos)
-    lib = _abi.lib()
-    dev = pos.device
+    dev, n, view = pos.device, pos.shape[0], spec.view
     fr = _Frame()
-    fr.spec, fr.pose, fr.need_grad, fr.stats = spec, pose, need_grad, stats if need_grad else None
-    fr.absgrad = fr.stats is not None and _stats_absgrad.get()       # (read once, beside the record)
-    fr.visible = visible if need_grad else None
+    # (the records are checked before anything else: a wrong one is refused even where nothing is rendered)
+    fr.stats, fr.absgrad, fr.visible = frame_records(pos, need_grad)
+    fr.spec, fr.pose, fr.need_grad, fr.n = spec, pose, need_grad, n
     fr.route, fr.route_kind = None, PLAIN       # (until _route_of finds a consumer for this frame)
-    n, view, opa = pos.shape[0], spec.view, tensors["opacity_raw"]
-    fr.n, fr.inputs = n, dict(pos=_f32(pos, (n, 3), "pos"), opacity_raw=_f32(opa if opa.dim() == 1 else opa.reshape(-1), (n,), "opacity_raw"))
+    fr.inputs, g = _convert_inputs(spec.names, tensors, n)
     c2w32 = fr.c2w = _f32(c2w, (4, 4), "c2w")
-    for name in spec.names[2:]:
-        fr.inputs[name] = _f32(tensors[name], (n,) + _ROW_SHAPE[name], name)
     fr.arena = fr.gaussians = fr.proj_state = fr.bin_state = fr.accum = fr.grad2d = fr.accum_aux = None
     fr.empty = fr.sh_jacobian = fr.dirty = False
     # the caller's own SH tensors (before any dtype / layout conversion): what dp.FactoredExchange.owns() compares
@@ -459,33 +142,25 @@ def _forward_begin(spec, c2w, tensors, pose=False, need_grad=False):
         fr.empty = True
         _route_of(fr, False)
         return None, (_empty_result(spec, dev), fr, _abi.Counts(0, 0, 0, 0, 0, 0))
-    g = fr.gaussians = _abi.Gaussians(n, *map(_p, map(fr.inputs.get, _INPUT_FIELDS)))      # (addresses of fr.inputs, which the frame keeps)
+    fr.gaussians = g                            # (addresses of fr.inputs, which the frame keeps)
     ckey = capacity_key(dev, spec, n)
     capacity = _ws.pair_capacity(ckey) if _deferred_stack else 0
     deferred = capacity > 0
-    if torch.cuda.current_device() != dev.index:
-        torch.cuda.set_device(dev)            # (a context manager per call costs more than the call: the one-process-per-GPU host never switches)
-    sp = torch.cuda.current_stream(dev).cuda_stream               # looked up ONCE per forward pass
-    key = (dev.type, dev.index, sp)
-    st = C.c_void_p(sp)
-    counters = _ws.get_counter_block(dev, _COUNTER_BYTES or _counter_bytes(lib), key)
+    _, key, st = _stream_key(dev)               # looked up ONCE per forward pass
     fr.sh_jacobian = bool(spec.fused and need_grad and _sh_jacobian)   # 48 bytes per Gaussian that spare the backward the 192 bytes of SH coefficients
     chk = _deferred_stack[-1] if deferred else None
-    pinned, slot = _ws.next_pinned(dev, key, chk)
-    ready = _ws.get_event(dev, fresh=deferred, key=key)
-    wants_stages = _timer is not None and _timer.wants(_FORWARD_STAGES)
-    composite = deferred and _composite and not wants_stages and not pose and not auxf
+    composite = deferred and _composite and not _timing.wants(_FORWARD_STAGES) and not pose and not auxf
     _route_of(fr, composite)
+    lib = _abi.lib()
     if composite:
         # ---- the whole forward pass in one call, on one arena
-        H, W = spec.H, spec.W
+        counters, pinned, slot, ready = _ws.counter_set(dev, key, chk, True)
         flags = (_abi.GSPLAT_FRAME_BACKWARD if need_grad else 0) | (0 if _sh_jacobian else _abi.GSPLAT_FRAME_NO_SH_JACOBIAN)
         frame_bytes, scratch_bytes = _ws.frame_sizes(lib, n, capacity, view, flags)
         flags |= _FRAME_DEGREE[spec.sh_degree] | spec.filter
-        fr.arena = torch.empty(frame_bytes, dtype=torch.uint8, device=dev)
-        image = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        fr.arena, fr.n_pairs = torch.empty(frame_bytes, dtype=torch.uint8, device=dev), capacity
+        image = torch.empty((spec.H, spec.W, 3), dtype=torch.float32, device=dev)
         scratch = _ws.get_scratch(dev, scratch_bytes, key)
-        fr.n_pairs = capacity
         _abi.check(lib.gsplat_forward_deferred(g, c2w32.data_ptr(), view, fr.arena.data_ptr(), frame_bytes, capacity, counters.data_ptr(),
                                                counters.numel(), scratch.data_ptr(), scratch.numel(), pinned.data_ptr(), ready.cuda_event,
                                                image.data_ptr(), flags, st), "gsplat_forward_deferred")
@@ -493,20 +168,57 @@ def _forward_begin(spec, c2w, tensors, pose=False, need_grad=False):
         composite_calls["forward"] += 1
         chk.add(pinned, ready, capacity, dev, ckey, (key, slot))
         return None, ((image, None, None), fr, None)
-    pend = fr, _Unread(pinned, ready, capacity if deferred else None, dev, ckey, (key, slot))
     fr.proj_state = torch.empty(lib.gsplat_project_state_bytes(n, C.byref(view)), dtype=torch.uint8, device=dev)
-    # the counters go straight into the pinned block (mapped into the device's address space: no copy operation);
-    # a frame that will not wait for them evaluates the SH colour inside the projection kernel and lets the first binning
+    # a frame that will not wait for its counters evaluates the SH colour inside the projection kernel and lets the first binning
     # kernel total the counters (the projection's waves then retire without waiting for their stores)
-    flags = _abi.GSPLAT_PROJECT_COUNTS_MAPPED | ((_abi.GSPLAT_PROJECT_COLOUR_FUSED | _abi.GSPLAT_PROJECT_COUNTS_LATE) if deferred else 0)
+    flags = (_abi.GSPLAT_PROJECT_COLOUR_FUSED | _abi.GSPLAT_PROJECT_COUNTS_LATE) if deferred else 0
     if fr.sh_jacobian:
         flags |= _abi.GSPLAT_PROJECT_SAVE_SH_JACOBIAN
     flags |= _PROJECT_DEGREE[spec.sh_degree] | spec.filter
+    pinned, slot, ready = _queue_project(g, c2w32, view, fr.proj_state, flags, dev, key, st, chk, deferred)
+    return (fr, _Unread(pinned, ready, capacity if deferred else None, dev, ckey, (key, slot))), None
+
+
+# ---- the front end of a frame, shared by the forward pass and contribution(): convert, project, (read_counts,) bin.  The pieces take
+# the ring key and the stream handle of _stream_key(), which their caller looks up once.
+
+def _convert_inputs(names, tensors, n):
+    """(inputs by name in fp32, the C struct of their addresses -- the caller keeps the former alive) of the entry's inputs `names`."""
+    opa = tensors["opacity_raw"]
+    ins = dict(pos=_f32(tensors["pos"], (n, 3), "pos"), opacity_raw=_f32(opa if opa.dim() == 1 else opa.reshape(-1), (n,), "opacity_raw"))
+    for name in names[2:]:
+        ins[name] = _f32(tensors[name], (n,) + _ROW_SHAPE[name], name)
+    return ins, _abi.Gaussians(n, *map(_p, map(ins.get, _INPUT_FIELDS)))
+
+
+def _stream_key(dev):
+    """(stream, key, st) of the current stream of `dev`, made the current device: the key of the workspace's per-stream buffers and the
+    handle the library takes.  Looking the stream up is the costliest thing a pass does on the host: once per pass and direction."""
+    if torch.cuda.current_device() != dev.index:
+        torch.cuda.set_device(dev)            # (a context manager per call costs more than the call: the one-process-per-GPU host never switches)
+    stream = torch.cuda.current_stream(dev)
+    return stream, (dev.type, dev.index, stream.cuda_stream), C.c_void_p(stream.cuda_stream)
+
+
+def _queue_project(g, c2w32, view, proj_state, flags, dev, key, st, owner=None, fresh_event=False):
+    """Queue gsplat_project; returns (pinned, slot, ready): the counters go straight into the pinned block (mapped into the device's
+    address space: no copy operation), and `ready` is recorded behind them."""
+    counters, pinned, slot, ready = _ws.counter_set(dev, key, owner, fresh_event)
     with _stage("project"):
-        _abi.check(lib.gsplat_project(C.byref(g), _p(c2w32), C.byref(view), _p(fr.proj_state), _p(counters),
-                                      counters.numel(), C.c_void_p(pinned.data_ptr()), C.c_void_p(ready.cuda_event),
-                                      flags, st), "gsplat_project")
-    return pend, None
+        _abi.check(_abi.lib().gsplat_project(C.byref(g), _p(c2w32), C.byref(view), _p(proj_state), _p(counters), counters.numel(),
+                                             C.c_void_p(pinned.data_ptr()), C.c_void_p(ready.cuda_event),
+                                             flags | _abi.GSPLAT_PROJECT_COUNTS_MAPPED, st), "gsplat_project")
+    return pinned, slot, ready
+
+
+def _queue_bin(n, pairs, view, proj_state, dev, key, st):
+    """Queue gsplat_bin of `pairs` pairs; returns the frame's bin_state (the scratch is the stream's own)."""
+    lib = _abi.lib()
+    bin_state = torch.empty(lib.gsplat_bin_state_bytes(pairs, C.byref(view)), dtype=torch.uint8, device=dev)
+    scratch = _ws.get_scratch(dev, lib.gsplat_bin_scratch_bytes(pairs, C.byref(view)), key)
+    with _stage("bin"):
+        _abi.check(lib.gsplat_bin(n, pairs, C.byref(view), _p(proj_state), _p(bin_state), _p(scratch), scratch.numel(), st), "gsplat_bin")
+    return bin_state
 
 
 def _empty_result(spec, dev):
@@ -534,19 +246,12 @@ def _background_arg(background):
     return (C.c_float * 3)(*background) if background is not None else None
 
 
-_COUNTER_BYTES = 0
 # the flag bits of an SH degree, per entry family (index = degree; 0 for degree 3)
 _PROJECT_DEGREE = tuple(_abi.GSPLAT_PROJECT_SH_DEGREE(d) for d in range(4))
 _FRAME_DEGREE = tuple(_abi.GSPLAT_FRAME_SH_DEGREE(d) for d in range(4))
 _BACKWARD_DEGREE = tuple(_abi.GSPLAT_BACKWARD_SH_DEGREE(d) for d in range(4))
 _FORWARD_STAGES = frozenset(("project", "bin", "raster_forward"))
 _BACKWARD_STAGES = frozenset(("raster_backward", "project_backward"))
-
-
-def _counter_bytes(lib):
-    global _COUNTER_BYTES
-    _COUNTER_BYTES = int(lib.gsplat_project_scratch_bytes(0))
-    return _COUNTER_BYTES
 
 
 def _forward_end(fr, unread):
@@ -570,13 +275,11 @@ def _forward_end(fr, unread):
     else:
         unread.event.synchronize()
         forward_modes["waited"] += 1
-        counts = _abi.Counts.from_buffer_copy(unread.pinned.numpy().tobytes())
-        _ws.note_pairs(unread.ckey, counts.n_binned)
+        counts, scene = read_counts(unread.pinned, unread.ckey)
         if _deferred_stack:                      # a frame that had to wait inside a deferred block (first of its size): verify() still
             chk = _deferred_stack[-1]            # returns one entry per frame, in frame order (the earlier frames are done by now)
             chk._drain(len(chk.pending))
             chk.counts.append(counts)
-        scene = lib.gsplat_classify_counts(C.byref(counts))
         if scene == _abi.GSPLAT_SCENE_ALL_OFFSCREEN:
             raise Exception(OFFSCREEN_MSG)
         if scene == _abi.GSPLAT_SCENE_ALL_CULLED:
@@ -585,30 +288,27 @@ def _forward_end(fr, unread):
             return _empty_result(spec, dev), fr, counts
         fr.n_pairs = int(counts.n_binned)        # pairs actually binned (16 x 8 lists); counts.n_pairs = the reference's P
     image = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-    fr.bin_state = torch.empty(lib.gsplat_bin_state_bytes(fr.n_pairs, C.byref(view)), dtype=torch.uint8, device=dev)
-    scratch = _ws.get_scratch(dev, lib.gsplat_bin_scratch_bytes(fr.n_pairs, C.byref(view)), key)
-    with _stage("bin"):
-        _abi.check(lib.gsplat_bin(n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state), _p(scratch),
-                                  scratch.numel(), st), "gsplat_bin")
+    fr.bin_state = _queue_bin(n, fr.n_pairs, view, fr.proj_state, dev, key, st)
     fr.accum = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if need_grad else None
     # the forward rasterizer clears the backward's accumulation buffer on the side (its waves are VALU-bound), unless
     # there are so few lists that a wave's share would be long
     lists = ((W + 15) // 16) * ((H + 7) // 8)
     fr.grad2d = torch.empty((n, 16), dtype=torch.float32, device=dev) if need_grad and n <= 256 * lists else None
+    depth = alpha = None
     if spec.is_aux:
         # depth and opacity beside the colour (and the colour over the background): the aux variant of the raster kernel
-        depth = torch.empty((H, W), dtype=torch.float32, device=dev) if spec.aux else None
-        alpha = torch.empty((H, W), dtype=torch.float32, device=dev) if spec.aux else None
+        if spec.aux:
+            depth, alpha = (torch.empty((H, W), dtype=torch.float32, device=dev) for _ in range(2))
         fr.accum_aux = torch.empty((H, W, 2), dtype=torch.float32, device=dev) if need_grad else None
         with _stage("raster_forward"):
             _abi.check(lib.gsplat_rasterize_forward_aux(n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state), _p(image),
                                                         _p(depth), _p(alpha), _p(fr.accum), _p(fr.accum_aux), _p(fr.grad2d),
                                                         _background_arg(spec.background), st), "gsplat_rasterize_forward_aux")
-        return (image, depth, alpha), fr, counts
-    with _stage("raster_forward"):
-        _abi.check(lib.gsplat_rasterize_forward(n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state),
-                                                _p(image), _p(fr.accum), _p(fr.grad2d), st), "gsplat_rasterize_forward")
-    return (image, None, None), fr, counts
+    else:
+        with _stage("raster_forward"):
+            _abi.check(lib.gsplat_rasterize_forward(n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state),
+                                                    _p(image), _p(fr.accum), _p(fr.grad2d), st), "gsplat_rasterize_forward")
+    return (image, depth, alpha), fr, counts
 
 
 def _forward_impl(spec, c2w, tensors, pose, need_grad):
@@ -724,6 +424,11 @@ def _route_of(fr, composite):
         fr.route, fr.route_kind = r, kind
 
 
+# the raster backward of a frame: (aux variant?, absolute-gradient statistics? -- rows of 11 / 12) -> (entry, its scratch-size entry)
+_RASTER_BACKWARD = {(aux, absgrad): (name, name + "_scratch_bytes") for aux in (False, True) for absgrad in (False, True)
+                    for name in ["gsplat_rasterize_backward" + "_aux" * aux + "_abs" * absgrad]}
+
+
 class _BackwardPass:
     """What _backward_impl prepares for either call sequence: the route kind of THIS pass, timed pass?, fp32 grad_image, the stream and
     its handle, deterministic scratch, destination buffers (dict and C struct), SUMMED: add to them?, flag bits of the projection backward."""
@@ -738,20 +443,15 @@ def _backward_impl(fr, grad_image, need_params=True, grad_depth=None, grad_alpha
     spec, ins = fr.spec, fr.inputs
     if fr.empty or fr.n == 0 or (spec.is_aux and grad_image is None and grad_depth is None and grad_alpha is None):
         return _backward_empty(fr)
-    lib = _abi.lib()
     dev = ins["pos"].device
     bp = _BackwardPass()
     bp.gi = _f32(grad_image, (spec.H, spec.W, 3), "grad_image") if grad_image is not None else None
-    if torch.cuda.current_device() != dev.index:
-        torch.cuda.set_device(dev)
-    stream = bp.stream = torch.cuda.current_stream(dev)
-    bp.st = C.c_void_p(stream.cuda_stream)
-    if fr.absgrad:             # the absolute-gradient raster backward: rows of 11 / 12
-        det_bytes = lib.gsplat_rasterize_backward_aux_abs_scratch_bytes if spec.is_aux else lib.gsplat_rasterize_backward_abs_scratch_bytes
-    else:
-        det_bytes = lib.gsplat_rasterize_backward_aux_scratch_bytes if spec.is_aux else lib.gsplat_rasterize_backward_scratch_bytes
-    bp.det = _ws.get_scratch(dev, det_bytes(fr.n, fr.n_pairs), (dev.type, dev.index, stream.cuda_stream)) if _deterministic else None
-    staged = bp.staged = _timer is not None and _timer.wants(_BACKWARD_STAGES)
+    stream, key, bp.st = _stream_key(dev)
+    bp.stream, bp.det = stream, None
+    if _deterministic:
+        det_bytes = getattr(_abi.lib(), _RASTER_BACKWARD[spec.is_aux, fr.absgrad][1])
+        bp.det = _ws.get_scratch(dev, det_bytes(fr.n, fr.n_pairs), key)
+    staged = bp.staged = _timing.wants(_BACKWARD_STAGES)
     # only known now, each sending the frame down the ordinary backward: a timed pass (phase by phase), a second pass through the
     # frame (views' sum), a step of f_rest already applied (folded step)
     kind = fr.route_kind
@@ -795,27 +495,17 @@ def _backward_separate(fr, bp, grad_depth, grad_alpha, need_params):
     fr.grad2d = None                       # a second backward through the same graph must not reuse a dirty buffer
     gd = _f32(grad_depth, (spec.H, spec.W), "grad_depth") if grad_depth is not None else None
     ga = _f32(grad_alpha, (spec.H, spec.W), "grad_alpha") if grad_alpha is not None else None
+    name = _RASTER_BACKWARD[spec.is_aux, fr.absgrad][0]
+    if spec.is_aux:
+        # (z, 1) as two more colour channels; column 9 of grad2d = dL/dz, which the projection backward picks up (DEPTH)
+        upstream = (_p(fr.accum_aux), _p(bp.gi), _p(gd), _p(ga), _background_arg(spec.background))
+        jac |= _abi.GSPLAT_BACKWARD_DEPTH
+    else:
+        upstream = (_p(bp.gi),)
     with _stage("raster_backward"):
-        if spec.is_aux:
-            # (z, 1) as two more colour channels; column 9 of grad2d = dL/dz, which the projection backward picks up (DEPTH)
-            name = "gsplat_rasterize_backward_aux_abs" if fr.absgrad else "gsplat_rasterize_backward_aux"
-            _abi.check(getattr(lib, name)(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state),
-                                          _p(fr.accum), _p(fr.accum_aux), _p(bp.gi), _p(gd), _p(ga),
-                                          _background_arg(spec.background), _p(grad2d), int(zeroed), _p(det),
-                                          det.numel() if det is not None else 0, st), name)
-            jac |= _abi.GSPLAT_BACKWARD_DEPTH
-        else:
-            name = "gsplat_rasterize_backward_abs" if fr.absgrad else "gsplat_rasterize_backward"
-            _abi.check(getattr(lib, name)(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state),
-                                          _p(fr.accum), _p(bp.gi), _p(grad2d), int(zeroed), _p(det),
-                                          det.numel() if det is not None else 0, st), name)
-    if fr.stats is not None:
-        name = "gsplat_densify_stats_abs" if fr.absgrad else "gsplat_densify_stats"
-        _abi.check(getattr(lib, name)(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(grad2d), _p(fr.stats), st), name)
-        if fr.absgrad:
-            absgrad_calls["separate"] += 1
-    if fr.visible is not None:
-        _abi.check(lib.gsplat_visible_set(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.visible), st), "gsplat_visible_set")
+        _abi.check(getattr(lib, name)(fr.n, fr.n_pairs, C.byref(view), _p(fr.proj_state), _p(fr.bin_state), _p(fr.accum), *upstream,
+                                      _p(grad2d), int(zeroed), _p(det), det.numel() if det is not None else 0, st), name)
+    add_frame_records(fr, st, grad2d)
     if bp.kind == FACTORED:
         # logit gradients first: the exchange may start on them while the projection backward runs
         glogit = torch.empty((fr.n, 3), dtype=torch.float32, device=dev)
@@ -862,7 +552,7 @@ def _backward_arena(fr, bp):
             _backward_call(fr, bp, flags | _abi.GSPLAT_BACKWARD_PHASE_RASTER, det, glogit)
         if kind == FACTORED:                   # logit gradients first: the exchange may start on them while the projection backward runs
             route.add(glogit, fr.c2w[:3, 3], fr.spec.sh_degree)
-        _frame_stats(fr, bp.st)
+        add_frame_records(fr, bp.st)
         with _stage("project_backward"):
             _backward_call(fr, bp, jac | _abi.GSPLAT_BACKWARD_PHASE_PROJECT)
     else:
@@ -876,247 +566,9 @@ def _backward_arena(fr, bp):
             route.commit()
         else:
             _backward_call(fr, bp, flags, det)
-        _frame_stats(fr, bp.st)                # (the projection phase only reads grad2d)
+        add_frame_records(fr, bp.st)           # (the projection phase only reads grad2d)
     composite_calls["backward"] += 1
     return {} if kind == SUMMED else bp.dst
-
-
-def _frame_stats(fr, st):
-    """The densification statistics of a frame on an arena, once its raster phase is queued (fr.stats: ops.densify_stats), and its
-    visible set (fr.visible: ops.visible_set)."""
-    if fr.stats is not None:
-        name = "gsplat_frame_densify_stats_abs" if fr.absgrad else "gsplat_frame_densify_stats"
-        _abi.check(getattr(_abi.lib(), name)(fr.n, fr.n_pairs, C.byref(fr.spec.view), _p(fr.arena), fr.arena.numel(), _p(fr.stats), st), name)
-        if fr.absgrad:
-            absgrad_calls["arena"] += 1
-    if fr.visible is not None:
-        _abi.check(_abi.lib().gsplat_frame_visible_set(fr.n, fr.n_pairs, C.byref(fr.spec.view), _p(fr.arena), fr.arena.numel(), _p(fr.visible), st),
-                   "gsplat_frame_visible_set")
-
-
-class DensifyStats:
-    """Screen-space densification statistics of N Gaussians: `.data` [N, 4] float32 = (grad_sum, count, extent_max, 0).
-
-        stats = ops.DensifyStats(n, device)
-        with ops.densify_stats(stats):
-            loss(render_gaussians(...)).backward()          # every backward pass of a frame rendered here adds that frame
-        hot = stats.mean_grad() >= 0.0002
-
-    Per frame, every Gaussian binned into at least one list adds the norm of the gradient of its projected centre (NDC units: the
-    paper's 0.0002 carries over) to grad_sum and 1 to count, and raises extent_max to its screen half-extent (pixels, at most 250).
-    The accumulation is a plain read-modify-write: backward passes that add into one record must be ordered on one stream."""
-
-    def __init__(self, n, device):
-        self.data = torch.zeros((int(n), 4), dtype=torch.float32, device=device)
-
-    grad_sum = property(lambda self: self.data[:, 0])
-    count = property(lambda self: self.data[:, 1])
-    extent_max = property(lambda self: self.data[:, 2])
-
-    def mean_grad(self):
-        return self.grad_sum / self.count.clamp(min=1)
-
-    def reset(self, n=None):
-        """Zero the record; with another n, a fresh record of n rows (after a densification)."""
-        if n is None or int(n) == self.data.shape[0]:
-            self.data.zero_()
-        else:
-            self.data = torch.zeros((int(n), 4), dtype=torch.float32, device=self.data.device)
-        return self
-
-    def merge_(self, other):
-        """self (+)= other -- (sum, sum, max) -- on the current stream; `other` is zero afterwards (the merge kernel clears the
-        rows it consumed)."""
-        a, b = self.data, other.data
-        if not a.is_cuda:
-            raise RuntimeError(f"the record is on {a.device}: the merge kernel needs GPU tensors (there is no CPU fallback)")
-        if b.shape != a.shape or b.device != a.device or b.dtype != torch.float32 or not b.is_contiguous() or other is self:
-            raise ValueError(f"merge_: the other record must be another float32 {tuple(a.shape)} record on {a.device}")
-        with torch.cuda.device(a.device):
-            _abi.check(_abi.lib().gsplat_densify_stats_merge(a.shape[0], _p(b), _p(a), _stream_ptr(a.device)), "gsplat_densify_stats_merge")
-        return self
-
-    def all_reduce(self, group=None):
-        """Sum grad_sum and count, take the maximum of extent_max over the ranks of `group` (plain torch.distributed on contiguous
-        copies: CPU tensors over gloo work too).  Every rank ends with the same bits."""
-        import torch.distributed as dist
-        sums, ext = self.data[:, :2].contiguous(), self.data[:, 2].contiguous()
-        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
-        dist.all_reduce(ext, op=dist.ReduceOp.MAX, group=group)
-        self.data[:, :2] = sums
-        self.data[:, 2] = ext
-        return self
-
-
-# The record the frames rendered inside a densify_stats() block add to.  A slot of its own (not a gradient route: it combines with
-# any route), read once, in the caller's thread, when a frame is rendered (fr.stats), like fr.route.
-_stats = contextvars.ContextVar("gsplat_densify_stats", default=None)
-_stats_absgrad = contextvars.ContextVar("gsplat_densify_stats_absgrad", default=False)
-absgrad_calls = {"separate": 0, "arena": 0}      # statistics calls queued in absolute-gradient mode, by the kind of frame
-
-
-def densify_stats(rec, absgrad=False):
-    """Every backward pass of a frame rendered inside the block adds that frame's statistics to `rec` (a DensifyStats, or its
-    float32 [N, 4] tensor), once, on the backward's stream, behind its raster phase -- whatever route the gradients take.  Empty and
-    all-culled frames, frames rendered under torch.no_grad() and frames that overflowed their pair capacity add nothing.  A record
-    that does not fit the frame (float32 [n, 4], contiguous, on the frame's device) raises ValueError when the frame is rendered.
-
-    absgrad=True (a bool, else TypeError): grad_sum gets the ABSOLUTE-gradient statistic (AbsGS) -- per pixel, the
-    magnitudes of dL/du and dL/dv of the projected centre, added without their signs; the frame's raster backward is then the
-    variant that forms them, and its gradients are unchanged.  count and extent_max are the same in both modes."""
-    if type(absgrad) is not bool:
-        raise TypeError(f"densify_stats(): absgrad must be a bool, not {absgrad!r}")
-    data = rec.data if isinstance(rec, DensifyStats) else rec
-    if not isinstance(data, torch.Tensor):
-        raise TypeError("densify_stats() takes a DensifyStats or its [N, 4] tensor")
-    return _densify_stats_block(rec, data, absgrad)       # (the arguments are checked by the call, not by the `with`)
-
-
-@contextlib.contextmanager
-def _densify_stats_block(rec, data, absgrad):
-    token, token_abs = _stats.set(data), _stats_absgrad.set(absgrad)
-    try:
-        yield rec
-    finally:
-        _stats_absgrad.reset(token_abs)
-        _stats.reset(token)
-
-
-def _stats_record(pos):
-    data = _stats.get()
-    if data is None:
-        return None
-    n = pos.shape[0]
-    if data.dtype != torch.float32 or tuple(data.shape) != (n, 4) or data.device != pos.device or not data.is_contiguous() or data.data_ptr() % 16:
-        raise ValueError(f"densify_stats: the record is {data.dtype} {tuple(data.shape)} on {data.device}; this frame needs a contiguous "
-                         f"float32 {(n, 4)} record on {pos.device}")
-    return data
-
-
-class VisibleSet:
-    """The Gaussians the frames of a pass binned: `.data` [N] uint8, non-zero = binned into at least one list of at
-    least one frame -- the only rows that can have a non-zero gradient, and the rows optim.GaussianAdam.step(visible=...) steps.
-
-        seen = ops.VisibleSet(n, device)
-        with ops.visible_set(seen):
-            loss(render_gaussians(...)).backward()          # every backward pass of a frame rendered here adds that frame's set
-        optimizer.step(visible=seen)
-
-    A frame only ever stores 1 and never reads the record, so frames on different streams add into one record with no ordering
-    between them; reset() zeroes it.  Works on 'cpu' too (reset, all_reduce over gloo): only adding frames needs the GPU."""
-
-    def __init__(self, n, device):
-        self.data = torch.zeros(int(n), dtype=torch.uint8, device=device)
-
-    def reset(self, n=None):
-        """Zero the record; with another n, a fresh record of n rows (after a densification)."""
-        if n is None or int(n) == self.data.shape[0]:
-            self.data.zero_()
-        else:
-            self.data = torch.zeros(int(n), dtype=torch.uint8, device=self.data.device)
-        return self
-
-    def all_reduce(self, group=None):
-        """The union over the ranks of `group`: an element-wise MAX (plain torch.distributed: CPU tensors over gloo work too).  Every
-        rank ends with the same bytes."""
-        import torch.distributed as dist
-        dist.all_reduce(self.data, op=dist.ReduceOp.MAX, group=group)
-        return self
-
-
-# The record the frames rendered inside a visible_set() block add to: a slot of its own, like _stats.
-_visible = contextvars.ContextVar("gsplat_visible_set", default=None)
-
-
-def visible_set(rec):
-    """Every backward pass of a frame rendered inside the block adds that frame's visible set to `rec` (a VisibleSet, or its uint8 [N]
-    tensor), once, on the backward's stream -- whatever route the gradients take, and beside densify_stats().  Empty and all-culled
-    frames, frames rendered under torch.no_grad() and frames that overflowed their pair capacity add nothing.  A record that does
-    not fit the frame (uint8 [n], contiguous, on the frame's device) raises ValueError when the frame is rendered."""
-    data = rec.data if isinstance(rec, VisibleSet) else rec
-    if not isinstance(data, torch.Tensor):
-        raise TypeError("visible_set() takes a VisibleSet or its uint8 [N] tensor")
-    return _visible_set_block(rec, data)       # (the argument is checked by the call, not by the `with`)
-
-
-@contextlib.contextmanager
-def _visible_set_block(rec, data):
-    token = _visible.set(data)
-    try:
-        yield rec
-    finally:
-        _visible.reset(token)
-
-
-def _visible_record(pos):
-    data = _visible.get()
-    if data is None:
-        return None
-    n = pos.shape[0]
-    if data.dtype != torch.uint8 or tuple(data.shape) != (n,) or data.device != pos.device or not data.is_contiguous():
-        raise ValueError(f"visible_set: the record is {data.dtype} {tuple(data.shape)} on {data.device}; this frame needs a contiguous "
-                         f"uint8 {(n,)} record on {pos.device}")
-    return data
-
-
-class ContributionStats:
-    """Per-Gaussian contribution statistics of N Gaussians: how much each Gaussian takes part in the composite of the
-    frames added so far.  `.data` [N, 4] int32 -- the 32-bit words of include/gsplat_mi355x.h, every one an order-independent integer:
-    words 0-1 the little-endian uint64 sum_q (units of 2^-32), word 2 the float32 bits of weight_max, word 3 the uint32 pixel count
-    (wraps after 2^32 pixel hits).
-
-        stats = ops.contribution(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2ws, H, W, fx, fy, cx, cy)
-        never_matters = stats.weight_max == 0
-
-    Adding is integer add / max, so the record holds the same bits whatever order frames, streams or ranks arrive in.  Works on
-    'cpu' too (accessors, merge_, all_reduce over gloo): only ops.contribution needs the GPU."""
-
-    def __init__(self, n, device):
-        self.data = torch.zeros((int(n), 4), dtype=torch.int32, device=device)
-        self.frames = 0                     # frames accumulated (a host count)
-
-    n = property(lambda self: self.data.shape[0])
-    sum_q = property(lambda self: self.data.view(torch.int64)[:, 0])                 # (read as unsigned: below 2^63 in practice)
-    weight_sum = property(lambda self: self.sum_q.to(torch.float64) * 2.0 ** -32)
-    weight_max = property(lambda self: self.data[:, 2].contiguous().view(torch.float32))
-    pixels = property(lambda self: self.data[:, 3].to(torch.int64) & 0xFFFFFFFF)
-
-    def reset(self, n=None):
-        """Zero the record; with another n, a fresh record of n rows (after a pruning)."""
-        if n is None or int(n) == self.data.shape[0]:
-            self.data.zero_()
-        else:
-            self.data = torch.zeros((int(n), 4), dtype=torch.int32, device=self.data.device)
-        self.frames = 0
-        return self
-
-    def merge_(self, other):
-        """self (+)= other -- (add, max, add) on the integer words, frames added; `other` is left as it is."""
-        a, b = self.data, other.data
-        if b.shape != a.shape or b.device != a.device or b.dtype != torch.int32 or not b.is_contiguous() or other is self:
-            raise ValueError(f"merge_: the other record must be another int32 {tuple(a.shape)} record on {a.device}")
-        a.view(torch.int64)[:, 0] += b.view(torch.int64)[:, 0]
-        a[:, 2] = torch.maximum(a[:, 2], b[:, 2])        # (non-negative floats order like their bits)
-        a[:, 3] += b[:, 3]                                # (int32 wraps like uint32)
-        self.frames += other.frames
-        return self
-
-    def all_reduce(self, group=None):
-        """SUM of sum_q and pixels, MAX of word 2 over the ranks of `group`, and the sum of .frames (plain torch.distributed on integer
-        copies: CPU tensors over gloo work too).  Every rank ends with the same bits."""
-        import torch.distributed as dist
-        sums = torch.stack([self.sum_q, self.pixels, torch.full_like(self.sum_q, int(self.frames))], 1).contiguous()      # int64 [N, 3]
-        if sums.shape[0] == 0:
-            sums = torch.tensor([[0, 0, int(self.frames)]], dtype=torch.int64, device=self.data.device)
-        mx = self.data[:, 2].contiguous()
-        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
-        dist.all_reduce(mx, op=dist.ReduceOp.MAX, group=group)
-        self.frames = int(sums[0, 2])
-        if self.data.shape[0]:
-            self.data.view(torch.int64)[:, 0] = sums[:, 0]
-            self.data[:, 2] = mx
-            self.data[:, 3] = sums[:, 1].contiguous().view(torch.int32).view(-1, 2)[:, 0]      # the low words: pixels mod 2^32
-        return self
 
 
 @torch.no_grad()
@@ -1136,14 +588,10 @@ def contribution(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2ws, H, W, f
     n, dev = pos.shape[0], pos.device
     if stats is not None:
         data = getattr(stats, "data", None)
-        if (not isinstance(stats, ContributionStats) or data.dtype != torch.int32 or tuple(data.shape) != (n, 4) or data.device != dev
-                or not data.is_contiguous() or data.data_ptr() % 16):
+        if not isinstance(stats, ContributionStats) or not stats.fits(data, n, dev):
             raise ValueError(f"contribution: stats must be a ContributionStats of {n} rows (contiguous int32 {(n, 4)}) on {dev}, not "
                              f"{type(stats).__name__}" + (f" {data.dtype} {tuple(data.shape)} on {data.device}" if isinstance(data, torch.Tensor) else ""))
-    opa = opacity_raw if opacity_raw.dim() == 1 else opacity_raw.reshape(-1)
-    ins = dict(pos=_f32(pos, (n, 3), "pos"), opacity_raw=_f32(opa, (n,), "opacity_raw"))
-    for name, t in (("scale_raw", scale_raw), ("q_raw", q_raw), ("f_dc", f_dc), ("f_rest", f_rest)):
-        ins[name] = _f32(t, (n,) + _ROW_SHAPE[name], name)
+    ins, g = _convert_inputs(spec.names, dict(pos=pos, opacity_raw=opacity_raw, scale_raw=scale_raw, q_raw=q_raw, f_dc=f_dc, f_rest=f_rest), n)
     cams = [_f32(torch.as_tensor(c, dtype=torch.float32, device=dev) if not isinstance(c, torch.Tensor) else c, (4, 4), "c2w") for c in c2ws]
     if stats is None:
         stats = ContributionStats(n, dev)
@@ -1151,33 +599,21 @@ def contribution(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2ws, H, W, f
         stats.frames += len(cams)
         return stats
     lib, view = _abi.lib(), spec.view
-    g = _abi.Gaussians(n, *map(_p, map(ins.get, _INPUT_FIELDS)))
-    if torch.cuda.current_device() != dev.index:
-        torch.cuda.set_device(dev)
-    sp = torch.cuda.current_stream(dev).cuda_stream
-    key, st = (dev.type, dev.index, sp), C.c_void_p(sp)
-    counters = _ws.get_counter_block(dev, _COUNTER_BYTES or _counter_bytes(lib), key)
+    _, key, st = _stream_key(dev)
     proj_state = torch.empty(lib.gsplat_project_state_bytes(n, C.byref(view)), dtype=torch.uint8, device=dev)
-    flags = _abi.GSPLAT_PROJECT_COUNTS_MAPPED | _PROJECT_DEGREE[spec.sh_degree] | spec.filter
+    flags = _PROJECT_DEGREE[spec.sh_degree] | spec.filter
     ckey = capacity_key(dev, spec, n)
     for c2w in cams:
-        pinned, _ = _ws.next_pinned(dev, key)
-        ready = _ws.get_event(dev, key=key)
-        _abi.check(lib.gsplat_project(C.byref(g), _p(c2w), C.byref(view), _p(proj_state), _p(counters), counters.numel(),
-                                      C.c_void_p(pinned.data_ptr()), C.c_void_p(ready.cuda_event), flags, st), "gsplat_project")
+        pinned, _, ready = _queue_project(g, c2w, view, proj_state, flags, dev, key, st)
         ready.synchronize()                      # the one host wait of a frame: the pair count sizes the binning buffers
-        counts = _abi.Counts.from_buffer_copy(pinned.numpy().tobytes())
-        _ws.note_pairs(ckey, counts.n_binned)
-        scene = lib.gsplat_classify_counts(C.byref(counts))
+        counts, scene = read_counts(pinned, ckey)
         if scene == _abi.GSPLAT_SCENE_ALL_OFFSCREEN:
             raise Exception(OFFSCREEN_MSG)
         stats.frames += 1
         if scene == _abi.GSPLAT_SCENE_ALL_CULLED:
             continue
         pairs = int(counts.n_binned)
-        bin_state = torch.empty(lib.gsplat_bin_state_bytes(pairs, C.byref(view)), dtype=torch.uint8, device=dev)
-        scratch = _ws.get_scratch(dev, lib.gsplat_bin_scratch_bytes(pairs, C.byref(view)), key)
-        _abi.check(lib.gsplat_bin(n, pairs, C.byref(view), _p(proj_state), _p(bin_state), _p(scratch), scratch.numel(), st), "gsplat_bin")
+        bin_state = _queue_bin(n, pairs, view, proj_state, dev, key, st)
         _abi.check(lib.gsplat_contribution(n, pairs, C.byref(view), _p(proj_state), _p(bin_state), _p(stats.data), st), "gsplat_contribution")
     return stats
 
@@ -1186,17 +622,12 @@ def sh_accumulate(pos, eyes, grad_logit, scale=1.0, sh_degree=3):
     """(grad_f_dc [N,3], grad_f_rest [N,45]) = scale * sum over views of grad_logit[v] (x) Y(direction from eyes[v] to pos).
     sh_degree: the degree the views were rendered at; the columns of the inactive bases are zeros."""
     _abi.sh_bands_dropped(sh_degree)
-    lib = _abi.lib()
-    n = pos.shape[0]
-    v = grad_logit.shape[0]
+    n, v = pos.shape[0], grad_logit.shape[0]
     pos32, eyes32, gl32 = _f32(pos, (n, 3), "pos"), _f32(eyes, (v, 3), "eyes"), _f32(grad_logit, (v, n, 3), "grad_logit")
-    dev = pos32.device
-    with torch.cuda.device(dev):
-        off = (n * 3 + 63) // 64 * 64                     # both views 256-byte aligned inside one buffer
-        flat = torch.empty(off + n * 45, dtype=torch.float32, device=dev)
-        g_dc, g_rest = flat[:n * 3].view(n, 3), flat[off:off + n * 45].view(n, 45)
-        _abi.check(lib.gsplat_sh_accumulate_degree(n, v, _p(pos32), _p(eyes32), _p(gl32), float(scale), _p(g_dc), _p(g_rest),
-                                                   sh_degree, _stream_ptr(dev)), "gsplat_sh_accumulate_degree")
+    off = (n * 3 + 63) // 64 * 64                     # both views 256-byte aligned inside one buffer
+    flat = torch.empty(off + n * 45, dtype=torch.float32, device=pos32.device)
+    g_dc, g_rest = flat[:n * 3].view(n, 3), flat[off:off + n * 45].view(n, 45)
+    _launch("gsplat_sh_accumulate_degree", pos32.device, n, v, _p(pos32), _p(eyes32), _p(gl32), float(scale), _p(g_dc), _p(g_rest), sh_degree)
     return g_dc, g_rest
 
 
@@ -1346,59 +777,30 @@ _pipe_streams = {}
 
 def _pipeline_streams(dev):
     key = (dev.type, dev.index)
-    got = _pipe_streams.get(key)
-    if got is None:
-        got = _pipe_streams[key] = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
-    return got
+    if key not in _pipe_streams:
+        _pipe_streams[key] = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
+    return _pipe_streams[key]
 
-
-_last_counts = None
-_last_binned = None
-
-
-def _note_counts(counts):
-    """Keep the counters of the most recent call for render_stats() / binned_pairs(); returns the render_stats() triple."""
-    global _last_counts, _last_binned
-    _last_counts = (counts.n_survivors, counts.n_visible, int(counts.n_pairs))
-    _last_binned = int(counts.n_binned)
-    return _last_counts
-
-
-def binned_pairs():
-    """(list, Gaussian) pairs the most recent call really binned (after the exact ellipse / list test): P_b of DESIGN.md."""
-    return _last_binned
-
-
-def render_stats(image=None):
-    """(n_survivors, n_visible V, n_pairs P) of the call that produced `image` (or of the most recent call)."""
-    fn = image.grad_fn if image is not None else None
-    got = getattr(fn, "counts", None) if fn is not None else None
-    return got if got is not None else _last_counts
 
 
 class _BuildSigmaFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scale_raw, q_raw):
-        lib = _abi.lib()
         n = scale_raw.shape[0]
         sr, qr = _f32(scale_raw, (n, 3), "scale_raw"), _f32(q_raw, (n, 4), "q_raw")
         out = torch.empty((n, 3, 3), dtype=torch.float32, device=sr.device)
-        with torch.cuda.device(sr.device):
-            _abi.check(lib.gsplat_build_sigma(n, _p(sr), _p(qr), _p(out), _stream_ptr(sr.device)), "gsplat_build_sigma")
+        _launch("gsplat_build_sigma", sr.device, n, _p(sr), _p(qr), _p(out))
         ctx.save_for_backward(sr, qr)
         ctx.dtypes = (scale_raw.dtype, q_raw.dtype)
         return out if scale_raw.dtype == torch.float32 else out.to(scale_raw.dtype)
 
     @staticmethod
     def backward(ctx, grad_sigma):
-        lib = _abi.lib()
         sr, qr = ctx.saved_tensors
         n = sr.shape[0]
         gs = _f32(grad_sigma, (n, 3, 3), "grad_sigma")
         gsr, gqr = torch.empty_like(sr), torch.empty_like(qr)
-        with torch.cuda.device(sr.device):
-            _abi.check(lib.gsplat_build_sigma_backward(n, _p(sr), _p(qr), _p(gs), _p(gsr), _p(gqr), _stream_ptr(sr.device)),
-                       "gsplat_build_sigma_backward")
+        _launch("gsplat_build_sigma_backward", sr.device, n, _p(sr), _p(qr), _p(gs), _p(gsr), _p(gqr))
         return gsr.to(ctx.dtypes[0]), gqr.to(ctx.dtypes[1])
 
 
@@ -1410,7 +812,6 @@ def build_sigma_from_params(scale_raw, q_raw):
 class _EvaluateShFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, f_dc, f_rest, points, c2w):
-        lib = _abi.lib()
         n = points.shape[0]
         if f_rest.shape[-1] != 45:
             # the reference raises RuntimeError for any other width
@@ -1418,23 +819,18 @@ class _EvaluateShFn(torch.autograd.Function):
         dc, rest = _f32(f_dc, (n, 3), "f_dc"), _f32(f_rest, (n, 45), "f_rest")
         pts, cam = _f32(points, (n, 3), "points"), _f32(c2w, (4, 4), "c2w")
         out = torch.empty((n, 3), dtype=torch.float32, device=pts.device)
-        with torch.cuda.device(pts.device):
-            _abi.check(lib.gsplat_evaluate_sh(n, _p(dc), _p(rest), _p(pts), _p(cam), _p(out), _stream_ptr(pts.device)),
-                       "gsplat_evaluate_sh")
+        _launch("gsplat_evaluate_sh", pts.device, n, _p(dc), _p(rest), _p(pts), _p(cam), _p(out))
         ctx.save_for_backward(dc, rest, pts, cam)
         ctx.dtypes = (f_dc.dtype, f_rest.dtype, points.dtype, c2w.dtype)
         return out if points.dtype == torch.float32 else out.to(points.dtype)
 
     @staticmethod
     def backward(ctx, grad_color):
-        lib = _abi.lib()
         dc, rest, pts, cam = ctx.saved_tensors
         n = pts.shape[0]
         gc = _f32(grad_color, (n, 3), "grad_color")
         gdc, grest, gpts = torch.empty_like(dc), torch.empty_like(rest), torch.empty_like(pts)
-        with torch.cuda.device(pts.device):
-            _abi.check(lib.gsplat_evaluate_sh_backward(n, _p(dc), _p(rest), _p(pts), _p(cam), _p(gc), _p(gdc), _p(grest),
-                                                       _p(gpts), _stream_ptr(pts.device)), "gsplat_evaluate_sh_backward")
+        _launch("gsplat_evaluate_sh_backward", pts.device, n, _p(dc), _p(rest), _p(pts), _p(cam), _p(gc), _p(gdc), _p(grest), _p(gpts))
         gc2w = None
         if ctx.needs_input_grad[3]:
             # the colour depends on c2w only through the direction p - c2w[:3,3]: dL/dc2w[:3,3] = -sum dL/dp, the rest is 0

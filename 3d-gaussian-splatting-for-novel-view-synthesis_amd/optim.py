@@ -10,7 +10,8 @@ import ctypes as C
 import torch
 
 from . import _abi, ops
-from .ops import _p, _stage, _stream_ptr
+from ._dev import _p, _stream_ptr
+from ._timing import _stage
 
 
 def position_lr(iteration, position_lr_init=0.00016, position_lr_final=0.0000016, position_lr_delay_mult=0.01,

@@ -22,7 +22,7 @@ import torch
 
 from . import _abi
 from ._viewtable import ViewFn, ViewOp, ViewTable
-from .ops import _p, _stream_ptr
+from ._dev import _launch, _p
 
 
 def _shapes(c2w, delta):
@@ -80,9 +80,7 @@ class PoseTable(ViewTable):
         """grad += cfg.pose_reg * params (the gradient of (pose_reg / 2) |params|^2; gsplat's pose_opt_reg, a weight decay inside its
         Adam): one launch over the whole table, after the all-reduce of `grad`.  Adds nothing to step()'s dict."""
         dev = self.params.device
-        with torch.cuda.device(dev):
-            _abi.check(_abi.lib().gsplat_pose_delta_decay(_p(self.params), self.n_views, float(cfg.pose_reg), _p(self.grad), _stream_ptr(dev)),
-                       "gsplat_pose_delta_decay")
+        _launch("gsplat_pose_delta_decay", dev, _p(self.params), self.n_views, float(cfg.pose_reg), _p(self.grad))
         return {}
 
     @torch.no_grad()

@@ -38,7 +38,6 @@ import types
 from dataclasses import dataclass
 
 import torch
-import torch.distributed as dist
 
 from . import _abi, bilagrid, dp, exposure, filter3d, losses, mcmc, metrics, ops, optim, poses
 
@@ -430,11 +429,6 @@ class Trainer:
             rec.data.zero_()
         self._pass_dirty = False
 
-    def _world(self):
-        if dist.is_available() and dist.is_initialized():
-            return dist.get_world_size(self.group)
-        return 1
-
     def _densify_generator(self, iteration):
         return _keyed_generator(self.cfg.densify_seed, iteration)      # the same stream of split noise on every rank
 
@@ -494,7 +488,7 @@ class Trainer:
         for v in views:                                        # poses that share a camera go through one call
             cam = (int(v['H']), int(v['W']), float(v['fx']), float(v['fy']), float(v['cx']), float(v['cy']))
             groups.setdefault(cam, []).append(torch.as_tensor(v['c2w'], dtype=torch.float32).to(dev))
-        world, err = self._world(), None
+        world, err = dp.world_and_rank(self.group)[0], None
         try:
             for cam, poses in groups.items():
                 ops.contribution(m.pos, m.f_dc, m.f_rest, opacity_in, scale_in, m.q_raw, poses, *cam, sh_degree=self.sh_degree(iteration),
@@ -585,7 +579,7 @@ class Trainer:
             render_kw['sh_degree'] = sh_degree
         if aux is not None:
             render_kw.update(aux=aux, background=bg)
-        world, dev = self._world(), m.pos.device
+        world, dev = dp.world_and_rank(self.group)[0], m.pos.device
         even, n_global = dp.agree_on_views(len(views), self.group, views_per_rank, device=dev)
         if global_views is not None and int(global_views) != n_global:
             raise ValueError(f"global_views={global_views}, but the ranks hold {n_global} views in all")

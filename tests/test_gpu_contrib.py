@@ -276,6 +276,42 @@ def test_a_pose_with_nothing_on_screen_raises_and_keeps_the_poses_before_it(gs):
     assert str(e.value) == gs.ops.OFFSCREEN_MSG and st.frames == 1 and torch.equal(st.data, first.data)
 
 
+def test_contribution_and_a_waited_render_share_one_front_end(gs):
+    """The front end that ops.contribution and the render's forward pass share, seen from outside, on the golden scene case_g1 at its
+    own image size: the same pose leaves the same pair capacity; contribution leaves render_stats() and binned_pairs() as the render
+    left them; a pose with every Gaussian behind the camera adds a frame and no statistics."""
+    ops, s = gs.ops, scenes.case_g1()
+    p = [torch.tensor(s[k], device=DEV) for k in NAMES]
+    cam = (s["H"], s["W"], s["fx"], s["fy"], s["cx"], s["cy"])
+    c2w = torch.tensor(s["c2w"], device=DEV)
+    behind = c2w.clone()
+    behind[:3, :3] = c2w[:3, :3] @ torch.diag(torch.tensor([-1.0, 1.0, -1.0], device=DEV))      # flipped: every z is below near
+    moved = torch.tensor(_poses(s)[1], device=DEV)
+    key = ops.capacity_key(p[0].device, ops._frame_spec(True, *cam, 0.01, 100.0, 32, 16, 1e-6, 6.25, 0.99, 1 / 128.), len(s["pos"]))
+    saved = dict(ops._ws.capacity)
+    try:
+        ops._ws.capacity.pop(key, None)
+        first = gs.contribution(*p, [c2w], *cam)
+        cap_contribution = ops._ws.pair_capacity(key)
+        ops._ws.capacity.pop(key)
+        waited = ops.forward_modes["waited"]
+        with torch.no_grad():
+            gs.render_gaussians(*p, c2w, *cam)
+        assert ops.forward_modes["waited"] == waited + 1
+        stats, binned = ops.render_stats(), ops.binned_pairs()
+        assert binned > 0 and stats[0] > 0 and cap_contribution == ops._ws.pair_capacity(key) == int(binned * 1.25) + 4096
+        both = gs.contribution(*p, [moved, behind, c2w], *cam)             # (poses of other counts than the render's, and the render's)
+        assert ops.render_stats() == stats and ops.binned_pairs() == binned
+        assert both.frames == 3 and first.frames == 1 and first.data.any()
+        second = gs.contribution(*p, [c2w, behind], *cam)
+        torch.cuda.synchronize()
+        assert second.frames == 2 and torch.equal(second.data, first.data)
+        assert not gs.contribution(*p, [behind], *cam).data.any()
+    finally:
+        ops._ws.capacity.clear()
+        ops._ws.capacity.update(saved)
+
+
 # ---- pruning ------------------------------------------------------------------------------------------------------------------
 
 def test_pruning_the_gaussians_of_zero_weight_changes_no_bit_of_the_render(gs):
