@@ -29,6 +29,7 @@ from . import bilagrid  # noqa: E402,F401  (per-view bilateral grids: a sliced g
 from . import poses  # noqa: E402,F401  (per-view camera-pose corrections: a learned rigid correction per training camera)
 from . import metrics  # noqa: E402,F401  (held-out views: per-image PSNR / SSIM / L1, colour-corrected on request)
 from . import knn  # noqa: E402,F401  (scale initialisation from the 3 nearest neighbours: exact k-NN over a Morton sort)
+from . import features  # noqa: E402,F401  (per-Gaussian feature vectors: N-channel maps and their adjoint, 2D maps lifted onto the Gaussians)
 from . import model  # noqa: E402,F401  (GaussianModel: densify / prune / opacity reset)
 from . import training  # noqa: E402,F401  (one training iteration of the reference's loop on the fused pieces)
 

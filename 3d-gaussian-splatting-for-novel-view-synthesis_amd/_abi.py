@@ -37,6 +37,7 @@ GSPLAT_BILAGRID_ACCUMULATE = 1
 GSPLAT_METRICS_COLOUR_CORRECT = 1
 GSPLAT_KNN_BOX = 256
 GSPLAT_POSE_DELTA_ACCUMULATE = 1
+GSPLAT_FEATURES_MAX_CHANNELS = 512
 
 
 def sh_bands_dropped(degree):
@@ -182,6 +183,8 @@ SIGNATURES = {
     "gsplat_frame_visible_set": (_INT, [_I64, _I64, _PV, _VP, _I64, _VP, _VP]),
     "gsplat_contribution": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _VP]),
     "gsplat_frame_contribution": (_INT, [_I64, _I64, _PV, _VP, _I64, _VP, _VP]),
+    "gsplat_features_forward": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _INT, _VP, _VP]),
+    "gsplat_features_adjoint": (_INT, [_I64, _I64, _PV, _VP, _VP, _VP, _INT, _VP, _VP]),
     "gsplat_frame_bytes": (_I64, [_I64, _I64, _PV, C.c_int32]),
     "gsplat_forward_deferred": (_INT, [_PG, _VP, _PV, _VP, _I64, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, C.c_int32, _VP]),
     "gsplat_backward": (_INT, [_PG, _VP, _PV, _VP, _I64, _I64, _VP, _PGG, _VP, _VP, _I64, C.c_int32, _VP]),

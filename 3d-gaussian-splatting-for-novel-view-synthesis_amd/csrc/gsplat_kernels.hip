@@ -16,6 +16,8 @@
 //       (K7, K9 <ABS>: the absolute-gradient statistic -- two sums more per pair, columns 10-11 of grad2d)
 //   K9b visible_set_kernel                                  the rows a frame binned, one byte each (gs_visible.h; not in the reference)
 //   K10 raster_contrib_kernel  K6's traversal without colours: per-Gaussian blending-weight statistics (not in the reference)
+//   K11 raster_features_kernel / K12 raster_features_adjoint_kernel   K6's traversal over an [n, C] feature table, 8 channels per wave,
+//                              and its adjoint (gs_features.h; not in the reference)
 //
 // Everything is hand-written HIP for gfx950; no library kernels.  No MFMA: there is no dense contraction on this path.
 // No CPU fallback: without a GPU every entry point returns GSPLAT_ERR_HIP.
@@ -38,6 +40,7 @@
 #include "gs_densify.h"
 #include "gs_visible.h"
 #include "gs_contrib.h"
+#include "gs_features.h"
 #include "gs_ops.h"
 
 thread_local char gsplat_err_buf[512] = "";      // shared with gsplat_loss.hip; read through gsplat_last_error()
@@ -401,6 +404,31 @@ int contribution_impl(const char* name, int64_t n, int64_t pair_capacity, const 
     LAUNCH("raster_contrib_kernel", raster_contrib_kernel, dim3((unsigned)c.nl), dim3(64), 0, c.st, c.ps.counts, (long long)pair_capacity, c.ps.ranges,
            (const uint32_t*)bin_state, c.ps.rec, c.ps.order, c.vk.lists_x, c.vk.H, c.vk.W, c.vk.chi_clip, c.vk.alpha_max, c.vk.alpha_cutoff,
            (uint32_t)(n - 1), record);
+    return GSPLAT_OK;
+}
+
+// gsplat_features_forward / gsplat_features_adjoint behind their argument checks (every message names the entry): `in` -> `out` is
+// features -> the map, or grad_out -> grad_features
+int features_impl(const char* name, bool adjoint, int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state,
+                  const void* bin_state, const float* in, int channels, float* out, void* stream_) {
+    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
+    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
+    if (n < 0 || n > (int64_t)ID_MASK + 1 || pair_capacity < 0 || pair_capacity > 0xFFFFFFFFLL) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
+    if (!project_state || !bin_state || !in || !out) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
+    if (channels < 1 || channels > GSPLAT_FEATURES_MAX_CHANNELS) return fail(GSPLAT_ERR_BAD_ARG, "%s: channels out of range (1 .. 512)", name);
+    if (n == 0) return GSPLAT_OK;
+    const Ctx c = open_ctx(n, v, project_state, stream_);
+    const dim3 grid((unsigned)c.nl, (unsigned)((channels + FGROUP - 1) / FGROUP));
+    // rows as two 16-byte accesses where every row of a full group is 16-byte aligned; the arrays the kernel moves float by float need no alignment
+    const int vec = channels % 4 == 0 && aligned16(in) && (adjoint || aligned16(out));
+    if (adjoint)
+        LAUNCH("raster_features_adjoint_kernel", raster_features_adjoint_kernel, grid, dim3(64), 0, c.st, c.ps.counts, (long long)pair_capacity,
+               c.ps.ranges, (const uint32_t*)bin_state, c.ps.rec, c.ps.order, c.vk.lists_x, c.vk.H, c.vk.W, c.vk.chi_clip, c.vk.alpha_max,
+               c.vk.alpha_cutoff, (uint32_t)(n - 1), in, channels, vec, out);
+    else
+        LAUNCH("raster_features_kernel", raster_features_kernel, grid, dim3(64), 0, c.st, c.ps.counts, (long long)pair_capacity, c.ps.ranges,
+               (const uint32_t*)bin_state, c.ps.rec, c.ps.order, c.vk.lists_x, c.vk.H, c.vk.W, c.vk.chi_clip, c.vk.alpha_max,
+               c.vk.alpha_cutoff, (uint32_t)(n - 1), in, channels, vec, out);
     return GSPLAT_OK;
 }
 
@@ -872,6 +900,17 @@ int gsplat_frame_contribution(int64_t n, int64_t pair_capacity, const gsplat_vie
     if (int rc = open_frame(name, n, pair_capacity, v, frame, frame_bytes, record, 0, " (gsplat_frame_bytes)", &f)) return rc;
     const char* base = (const char*)frame;
     return contribution_impl(name, n, pair_capacity, v, base + f.project_state, base + f.bin_state, record, stream_);
+}
+
+// ---- per-Gaussian feature vectors (include/gsplat_mi355x.h; the kernels: gs_features.h) -----------------------------------------
+int gsplat_features_forward(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, const void* bin_state,
+                            const float* features, int channels, float* out, void* stream_) {
+    return features_impl("gsplat_features_forward", false, n, pair_capacity, v, project_state, bin_state, features, channels, out, stream_);
+}
+
+int gsplat_features_adjoint(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, const void* bin_state,
+                            const float* grad_out, int channels, float* grad_features, void* stream_) {
+    return features_impl("gsplat_features_adjoint", true, n, pair_capacity, v, project_state, bin_state, grad_out, channels, grad_features, stream_);
 }
 
 }  // extern "C"

@@ -451,6 +451,30 @@ int gsplat_contribution(int64_t n, int64_t pair_capacity, const gsplat_view* v, 
 int gsplat_frame_contribution(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* frame,
                               int64_t frame_bytes, uint32_t* record, void* stream);
 
+/* ---- per-Gaussian feature vectors: N-channel maps and their adjoint (not in the reference) ----------------------------------
+ * With the blending weight w_i(p) = alpha_i T_i [T_i > 5e-5] of Gaussian i at pixel p, exactly as the forward rasteriser forms it,
+ * and a table features [n, channels] (float32, row i = Gaussian i, rows contiguous):
+ *   gsplat_features_forward   out[p, c] = sum_i w_i(p) features[i, c].  out is [H, W, channels] float32, channel last; every pixel
+ *                             and channel is written, zeros where nothing reaches the pixel: the caller clears nothing.  Neither
+ *                             clamped nor normalised; a channel of ones renders the opacity map.
+ *   gsplat_features_adjoint   grad_features[i, c] += sum_p w_i(p) grad_out[p, c]: the gradient with respect to the table, and the
+ *                             closed-form lift of a 2D map [H, W, channels] onto the Gaussians.  It ADDS, with float atomics (the sums
+ *                             differ in their last bits from run to run; there is no deterministic variant): the caller zeroes the
+ *                             table, or accumulates over views.  A zero is never added: the row of a Gaussian in no list, or whose
+ *                             weights are all zero (everything behind an opaque surface), is not touched.
+ * Both run after gsplat_bin on the same project_state / bin_state and pair_capacity; no raster call is needed.  The records' colours
+ * are not read.  A table of C channels costs ceil(C / 8) traversals of the lists.  A frame with nothing on screen, or one whose pairs
+ * outgrew pair_capacity (n_binned > pair_capacity in its device counters: its lists are garbage), writes and adds nothing -- decided
+ * on the device, as in gsplat_contribution.  No array needs more than float alignment; 16-byte aligned arrays of a channel count
+ * divisible by 4 move in 16-byte pieces.
+ * GSPLAT_ERR_BAD_ARG (the text begins with the entry's name and a colon): a NULL pointer, n < 0, pair_capacity < 0, channels outside
+ * 1 .. GSPLAT_FEATURES_MAX_CHANNELS, a bad view.  n == 0: GSPLAT_OK, nothing is launched.                                         */
+#define GSPLAT_FEATURES_MAX_CHANNELS 512
+int gsplat_features_forward(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state,
+                            const void* bin_state, const float* features, int channels, float* out, void* stream);
+int gsplat_features_adjoint(int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state,
+                            const void* bin_state, const float* grad_out, int channels, float* grad_features, void* stream);
+
 /* ---- the two small exported functions as stand-alone ops --------------------------------------- */
 int gsplat_build_sigma(int64_t n, const float* scale_raw, const float* q_raw, float* sigma, void* stream);
 int gsplat_build_sigma_backward(int64_t n, const float* scale_raw, const float* q_raw, const float* grad_sigma,
