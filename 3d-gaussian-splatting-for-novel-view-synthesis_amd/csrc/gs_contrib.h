@@ -8,7 +8,7 @@ using namespace gsm;
 namespace {
 
 // K10: the forward kernel's traversal (same lists, launch order, two pixels per lane -- lane_pixels, fetch_candidate and stage_chunk
-// of gs_raster.h are K6's own -- the sub-tile queues, the same alpha, the same T = T - alpha T, the same 16-entry alive poll) without
+// of gs_raster.h are K6's own -- the sub-tile queues, the same alpha and T = T - alpha T (GS_WALK_WEIGHT), the same 16-entry alive poll) without
 // colours and without an image.  What leaves the wave is,
 // per (list, Gaussian) pair, the blending weight w = alpha T [T > 5e-5] of the pair's <= 128 pixels as
 //     (sum of w, max of w, number of pixels with w > 0).
@@ -83,18 +83,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ra
         int kdone = 0;                       // iterations executed (uniform): slots [0, kdone) of every queue are valid
         // one queue entry: the group's 16 pixels against one Gaussian; (sum, max, count) go to slot k of the group's queue
         auto entry = [&](const f4& a, const f4& b, const int k) {
-            const float du = fpx - a.x;
-            const v2f dv = fpy - a.y;
-            const v2f q = (a.z * du * du) + dv * ((a.w * du) + b.x * dv);                  // k q  (k < 0)
-            const bool i0 = q.x >= chik, i1 = q.y >= chik;                                  // q <= chi
-            v2f g;
-            g.x = __builtin_amdgcn_exp2f(q.x); g.y = __builtin_amdgcn_exp2f(q.y);
-            v2f al = b.y * g;
-            al.x = vmin(al.x, alpha_max); al.y = vmin(al.y, alpha_max);
-            al.x = (i0 && al.x >= alpha_cutoff && T.x > 5e-5f) ? al.x : 0.0f;               // the forward kernel's one select (copy: K6, K10 -- see there)
-            al.y = (i1 && al.y >= alpha_cutoff && T.y > 5e-5f) ? al.y : 0.0f;
-            const v2f w = al * T;
-            T = T - al * T;
+            GS_WALK_WEIGHT(a, b);                                     // w of the two pixels; T advances (gs_raster.h: K11 and K12 use the same)
             const float sum = all_reduce8(hadd(w));
             const float mx = all_reduce8_max(__builtin_fmaxf(w.x, w.y));
             const unsigned long long bx = __ballot(w.x > 0.0f), by = __ballot(w.y > 0.0f);
@@ -117,7 +106,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ra
         alive_any = __any(T.x > 5e-5f || T.y > 5e-5f);        // dead pixels stay dead
         __syncthreads();
         // entry `lane`: combine the slots of the sub-tiles it was queued in, in sub-tile order; one row per pair leaves the wave
-        // (copy: K7, K10 -- the loop over t, ranks and kdone)
+        // (copy: K7, K10, K12 -- the loop over t, ranks and kdone)
         float tot = 0.0f, mx = 0.0f;
         uint32_t cnt = 0u;
 #pragma unroll

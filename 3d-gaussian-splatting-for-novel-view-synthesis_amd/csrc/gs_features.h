@@ -10,7 +10,8 @@ namespace {
 
 // With the blending weight w_i(p) = alpha_i T_i [T_i > 5e-5] of Gaussian i at pixel p, exactly as K6 forms it (same lists, launch
 // order, two pixels per lane -- lane_pixels, fetch_candidate and stage_chunk of gs_raster.h are K6's own -- the sub-tile queues, the
-// pre-scaled conic and exp2, the v_min against alpha_max, the one select, T = T - alpha T, the 16-entry alive poll):
+// pre-scaled conic and exp2, the v_min against alpha_max, the one select, T = T - alpha T -- GS_WALK_WEIGHT of gs_raster.h, which
+// K10 uses too -- and the 16-entry alive poll):
 //     K11   F[p, c] = sum_i w_i(p) f_i[c]          features [n, C] -> out [H, W, C]
 //     K12   g_i[c] += sum_p w_i(p) G[p, c]         grad_out [H, W, C] -> grad_features [n, C]   (adds)
 // The weights do not depend on the features, so K12 walks the lists front to back like K11; there is no suffix sum.
@@ -55,22 +56,6 @@ struct FeatLds {
 };
 // 6.2 KB per wave: even 24 waves per CU would fit the CU's 160 KB; the VGPRs decide (4 waves per SIMD, see the kernel)
 static_assert(sizeof(FeatLds) <= 6656, "the feature kernel's LDS per wave: no limit below 24 waves per CU");
-
-// one alpha for the lane's two pixels against one staged record (a = r0, b = r1 of the entry); T advances
-// (spelled as in K10's entry; the select is the third copy of K6's)
-#define GS_FEATURES_WEIGHT(a, b)                                                                                             \
-    const float du = fpx - (a).x;                                                                                            \
-    const v2f dv = fpy - (a).y;                                                                                              \
-    const v2f q = ((a).z * du * du) + dv * (((a).w * du) + (b).x * dv);                  /* k q  (k < 0) */                 \
-    const bool i0 = q.x >= chik, i1 = q.y >= chik;                                        /* q <= chi */                     \
-    v2f g;                                                                                                                   \
-    g.x = __builtin_amdgcn_exp2f(q.x); g.y = __builtin_amdgcn_exp2f(q.y);                                                    \
-    v2f al = (b).y * g;                                                                                                      \
-    al.x = vmin(al.x, alpha_max); al.y = vmin(al.y, alpha_max);                                                              \
-    al.x = (i0 && al.x >= alpha_cutoff && T.x > 5e-5f) ? al.x : 0.0f;      /* the forward kernel's one select (copy: K6, K10 -- see there) */ \
-    al.y = (i1 && al.y >= alpha_cutoff && T.y > 5e-5f) ? al.y : 0.0f;                                                        \
-    const v2f w = al * T;                                                                                                    \
-    T = T - al * T
 
 // (4 waves per SIMD as the compiler leaves it: 118 VGPRs, no spill -- K6's 76, the 16 accumulators, the 16 feature values of the two
 //  entries in flight and the 8 of the next chunk's row.  A fifth wave needs 102: not tried)
@@ -118,7 +103,7 @@ __global__ __launch_bounds__(64) void raster_features_kernel(
         }
         // one queue entry: the group's 16 pixels against one Gaussian; its 8 channels join the running sums
         auto entry = [&](const f4& a, const f4& b, const f4& f0, const f4& f1) {
-            GS_FEATURES_WEIGHT(a, b);
+            GS_WALK_WEIGHT(a, b);
             acc[0] += w * f0.x; acc[1] += w * f0.y; acc[2] += w * f0.z; acc[3] += w * f0.w;
             acc[4] += w * f1.x; acc[5] += w * f1.y; acc[6] += w * f1.z; acc[7] += w * f1.w;
         };
@@ -225,7 +210,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ra
         int kdone = 0;                       // iterations executed (uniform): slots [0, kdone) of every queue are valid
         // one queue entry: the group's 16 pixels against one Gaussian; the eight sums go to slot k of the group's queue
         auto entry = [&](const f4& a, const f4& b, const int k) {
-            GS_FEATURES_WEIGHT(a, b);
+            GS_WALK_WEIGHT(a, b);
             float r[FGROUP];
 #pragma unroll
             for (int c = 0; c < FGROUP; ++c) r[c] = hadd(w * G[c]);
@@ -245,7 +230,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ra
         }
         alive_any = __any(T.x > 5e-5f || T.y > 5e-5f);        // dead pixels stay dead
         __syncthreads();
-        {   // entry `lane`: add up the slots of the sub-tiles it was queued in  (copy: K7, K10 -- the loop over t, ranks and kdone)
+        {   // entry `lane`: add up the slots of the sub-tiles it was queued in  (copy: K7, K10, K12 -- the loop over t, ranks and kdone)
             f4 lo = f4{0.f, 0.f, 0.f, 0.f}, hi = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int t = 0; t < N_SUB; ++t) {
@@ -271,7 +256,5 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ra
         }
     }
 }
-
-#undef GS_FEATURES_WEIGHT
 
 }  // namespace

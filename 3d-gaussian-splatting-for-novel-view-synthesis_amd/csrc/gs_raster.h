@@ -232,9 +232,10 @@ __device__ __forceinline__ T lds_at(const T* base, uint32_t byte_off) {
 }
 
 // ---- the pieces K6, K7 and K10 (gs_contrib.h) share: ONE copy each, so that "the same traversal" is the same code ---------------
-// (with stage_chunk above.  Three pieces stay spelled out per kernel, because a shared copy changed the compiled kernels beyond
-//  register numbers and the order of a few prologue instructions: the two clock reads of the statistics, the
-//  alpha select of K6 / K10, and the slot combine of K7 / K10.  They are marked "(copy: ...)" where they stand.)
+// (with stage_chunk above.  Three pieces stay spelled out, because a shared copy changed the compiled kernels beyond register numbers
+//  and the order of a few prologue instructions (DESIGN.md sections 21, 31): the two clock reads of the statistics and the slot
+//  combine of K7 / K10 / K12, marked "(copy: ...)" where they stand, and the alpha of an entry, which has two spellings: K6's own,
+//  and GS_WALK_WEIGHT for K10, K11 and K12.)
 
 // Which pixels does `lane` own in `list`?  Group grp = lane >> 3 owns sub-tile (grp & 3, grp >> 2), lane j of it the pixels (px, pya)
 // and (px, pyb = pya + 2); va / vb: inside the image; (ox, oy) = list origin; T = the initial transmittance (0 outside the image).
@@ -265,6 +266,23 @@ __device__ __forceinline__ float vmin(float a, float b) {
     asm("v_min_f32 %0, %2, %1" : "=v"(r) : "v"(a), "s"(b));
     return r;
 }
+
+// One queue entry against the lane's two pixels, "the forward's way" (K10, K11, K12; a = r0, b = r1 of the staged record): the
+// weight w = alpha T, and T advances.  Reads fpx, fpy, chik, alpha_max, alpha_cutoff and T of the kernel around it.  K6 spells the
+// same arithmetic for two entries interleaved and keeps that one spelling of its own (DESIGN.md sections 21, 31); this is the other.
+#define GS_WALK_WEIGHT(a, b)                                                                                                 \
+    const float du = fpx - (a).x;                                                                                            \
+    const v2f dv = fpy - (a).y;                                                                                              \
+    const v2f q = ((a).z * du * du) + dv * (((a).w * du) + (b).x * dv);                  /* k q  (k < 0) */                 \
+    const bool i0 = q.x >= chik, i1 = q.y >= chik;                                        /* q <= chi */                     \
+    v2f g;                                                                                                                   \
+    g.x = __builtin_amdgcn_exp2f(q.x); g.y = __builtin_amdgcn_exp2f(q.y);                                                    \
+    v2f al = (b).y * g;                                                                                                      \
+    al.x = vmin(al.x, alpha_max); al.y = vmin(al.y, alpha_max);                                                              \
+    al.x = (i0 && al.x >= alpha_cutoff && T.x > 5e-5f) ? al.x : 0.0f;      /* K6's one select: see there */                  \
+    al.y = (i1 && al.y >= alpha_cutoff && T.y > 5e-5f) ? al.y : 0.0f;                                                        \
+    const v2f w = al * T;                                                                                                    \
+    T = T - al * T
 
 // the first blocks of a launch (the longest lists) raise their wave priority (s_setprio takes a constant)
 __device__ __forceinline__ void raise_launch_priority(uint32_t b, uint32_t grid) {
@@ -366,7 +384,8 @@ __global__ __launch_bounds__(64) void raster_forward_kernel(const uint2* __restr
             al1.x = vmin(al1.x, alpha_max); al1.y = vmin(al1.y, alpha_max);
             // alpha = 0 outside the chi-square clip, below the cutoff, and on a dead pixel (T <= 5e-5: the term is masked, and a dead
             // pixel stays dead whether or not its T keeps shrinking) -- ONE select for the three, and w = alpha T needs none
-            // (copy: K6, K10 -- from a shared helper the compiler swaps the operands of the loop's s_and_b64 in both kernels)
+            // (K6's own spelling, two entries interleaved; GS_WALK_WEIGHT above is the other, of K10 - K12 -- from a shared helper
+            //  the compiler swaps the operands of this loop's s_and_b64)
             al0.x = (i00 && al0.x >= alpha_cutoff && T.x > 5e-5f) ? al0.x : 0.0f;
             al0.y = (i01 && al0.y >= alpha_cutoff && T.y > 5e-5f) ? al0.y : 0.0f;
             const v2f w0 = al0 * T;
@@ -727,7 +746,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((AUX || ABS)
         }
         alive_any = __any(T.x > 5e-5f || T.y > 5e-5f);        // dead pixels stay dead
         __syncthreads();
-        {   // entry `lane`: add up the slots of the sub-tiles it was queued in  (copy: K7, K10 -- the loop over t, ranks and kdone)
+        {   // entry `lane`: add up the slots of the sub-tiles it was queued in  (copy: K7, K10, K12 -- the loop over t, ranks and kdone)
             float tot[NS];
 #pragma unroll
             for (int v = 0; v < NS; ++v) tot[v] = 0.f;

@@ -68,6 +68,11 @@ int fail(int code, const char* fmt, const char* a = "", const char* b = "") {
         if (e_ != hipSuccess) return fail(GSPLAT_ERR_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
     } while (0)
 
+// the 13 traversal arguments that K10, K11 and K12 begin with (counts ... id_max), from the entry's Ctx `c` and its own arguments
+#define WALK_ARGS(c, pair_capacity, bin_state, n)                                                                      \
+    (c).ps.counts, (long long)(pair_capacity), (c).ps.ranges, (const uint32_t*)(bin_state), (c).ps.rec, (c).ps.order, \
+    (c).vk.lists_x, (c).vk.H, (c).vk.W, (c).vk.chi_clip, (c).vk.alpha_max, (c).vk.alpha_cutoff, (uint32_t)((n) - 1)
+
 int check_view(const gsplat_view* v) {
     if (!v) return fail(GSPLAT_ERR_BAD_ARG, "view is NULL");
     if (v->H <= 0 || v->W <= 0) return fail(GSPLAT_ERR_BAD_ARG, "image size must be positive");
@@ -308,18 +313,21 @@ int raster_backward_impl(int64_t n, int64_t n_binned, const gsplat_view* v, cons
 // a refusal of an entry whose messages name it (name given), or of one of the older entries, whose messages do not (name == NULL)
 int refuse(const char* name, const char* msg) { return name ? fail(GSPLAT_ERR_BAD_ARG, "%s: %s", name, msg) : fail(GSPLAT_ERR_BAD_ARG, "%s", msg); }
 
+// The opening refusals of an entry that walks a projected frame and names itself in its messages: the view, n, pair_capacity
+// (pairs32: the entry's kernels index the pairs with 32 bits).
+int check_walk(const char* name, int64_t n, int64_t pair_capacity, const gsplat_view* v, bool pairs32) {
+    if (!v) return refuse(name, "view is NULL");
+    if (check_view(v)) return refuse(name, "bad view (image size, tile size)");
+    if (n < 0 || n > (int64_t)ID_MASK + 1 || pair_capacity < 0 || (pairs32 && pair_capacity > 0xFFFFFFFFLL)) return refuse(name, "n / pair_capacity out of range");
+    return GSPLAT_OK;
+}
+
 // The four gsplat_rasterize_backward* entries behind their checks.  name: the entries whose refusals name them (they check n / n_binned,
 // too); aux: the two depth / opacity entries, which read accum_aux ... background and may leave grad_image out; abs: the ABS kernels.
 int raster_backward_entry(const char* name, bool aux, bool abs, int64_t n, int64_t n_binned, const gsplat_view* v, const void* project_state, const void* bin_state,
                           const float* accum, const float* accum_aux, const float* grad_image, const float* grad_depth, const float* grad_alpha,
                           const float* background, float* grad2d, int32_t grad2d_zeroed, void* det_scratch, int64_t det_scratch_bytes, void* stream_) {
-    if (name) {
-        if (!v) return refuse(name, "view is NULL");
-        if (check_view(v)) return refuse(name, "bad view (image size, tile size)");
-        if (n < 0 || n > (int64_t)ID_MASK + 1 || n_binned < 0 || n_binned > 0xFFFFFFFFLL) return refuse(name, "n / pair_capacity out of range");
-    } else if (int rc = check_view(v)) {
-        return rc;
-    }
+    if (int rc = name ? check_walk(name, n, n_binned, v, true) : check_view(v)) return rc;
     if (aux && !grad_image && !grad_depth && !grad_alpha) return refuse(name, "grad_image, grad_depth and grad_alpha are all NULL");
     if (!project_state || !bin_state || !accum || (aux ? !accum_aux : !grad_image) || !grad2d) return refuse(name, "NULL argument");
     AuxBwd ab = {accum_aux, grad_depth, grad_alpha, {0.f, 0.f, 0.f}, 0};
@@ -366,9 +374,7 @@ int open_frame(const char* name, int64_t n, int64_t pair_capacity, const gsplat_
 // gsplat_densify_stats / gsplat_frame_densify_stats behind their argument checks (every message names the entry)
 int densify_stats_impl(const char* name, int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, const float* grad2d,
                        float* stats, void* stream_, bool abs = false) {
-    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
-    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
-    if (n < 0 || n > (int64_t)ID_MASK + 1 || pair_capacity < 0) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
+    if (int rc = check_walk(name, n, pair_capacity, v, false)) return rc;
     if (!project_state || !grad2d || !stats) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
     if (!aligned16(stats) || !aligned16(grad2d)) return fail(GSPLAT_ERR_BAD_ARG, "%s: stats / grad2d must be 16-byte aligned", name);
     if (n == 0) return GSPLAT_OK;
@@ -381,9 +387,7 @@ int densify_stats_impl(const char* name, int64_t n, int64_t pair_capacity, const
 // gsplat_visible_set / gsplat_frame_visible_set behind their argument checks (every message names the entry)
 int visible_set_impl(const char* name, int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, uint8_t* visible,
                      void* stream_) {
-    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
-    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
-    if (n < 0 || n > (int64_t)ID_MASK + 1 || pair_capacity < 0) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
+    if (int rc = check_walk(name, n, pair_capacity, v, false)) return rc;
     if (!project_state || !visible) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
     if (n == 0) return GSPLAT_OK;
     const Ctx c = open_ctx(n, v, project_state, stream_);
@@ -394,16 +398,12 @@ int visible_set_impl(const char* name, int64_t n, int64_t pair_capacity, const g
 // gsplat_contribution / gsplat_frame_contribution behind their argument checks (every message names the entry)
 int contribution_impl(const char* name, int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state, const void* bin_state,
                       uint32_t* record, void* stream_) {
-    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
-    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
-    if (n < 0 || n > (int64_t)ID_MASK + 1 || pair_capacity < 0 || pair_capacity > 0xFFFFFFFFLL) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
+    if (int rc = check_walk(name, n, pair_capacity, v, true)) return rc;
     if (!project_state || !bin_state || !record) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
     if (!aligned16(record)) return fail(GSPLAT_ERR_BAD_ARG, "%s: record must be 16-byte aligned", name);
     if (n == 0) return GSPLAT_OK;
     const Ctx c = open_ctx(n, v, project_state, stream_);
-    LAUNCH("raster_contrib_kernel", raster_contrib_kernel, dim3((unsigned)c.nl), dim3(64), 0, c.st, c.ps.counts, (long long)pair_capacity, c.ps.ranges,
-           (const uint32_t*)bin_state, c.ps.rec, c.ps.order, c.vk.lists_x, c.vk.H, c.vk.W, c.vk.chi_clip, c.vk.alpha_max, c.vk.alpha_cutoff,
-           (uint32_t)(n - 1), record);
+    LAUNCH("raster_contrib_kernel", raster_contrib_kernel, dim3((unsigned)c.nl), dim3(64), 0, c.st, WALK_ARGS(c, pair_capacity, bin_state, n), record);
     return GSPLAT_OK;
 }
 
@@ -411,9 +411,7 @@ int contribution_impl(const char* name, int64_t n, int64_t pair_capacity, const 
 // features -> the map, or grad_out -> grad_features
 int features_impl(const char* name, bool adjoint, int64_t n, int64_t pair_capacity, const gsplat_view* v, const void* project_state,
                   const void* bin_state, const float* in, int channels, float* out, void* stream_) {
-    if (!v) return fail(GSPLAT_ERR_BAD_ARG, "%s: view is NULL", name);
-    if (check_view(v)) return fail(GSPLAT_ERR_BAD_ARG, "%s: bad view (image size, tile size)", name);
-    if (n < 0 || n > (int64_t)ID_MASK + 1 || pair_capacity < 0 || pair_capacity > 0xFFFFFFFFLL) return fail(GSPLAT_ERR_BAD_ARG, "%s: n / pair_capacity out of range", name);
+    if (int rc = check_walk(name, n, pair_capacity, v, true)) return rc;
     if (!project_state || !bin_state || !in || !out) return fail(GSPLAT_ERR_BAD_ARG, "%s: NULL argument", name);
     if (channels < 1 || channels > GSPLAT_FEATURES_MAX_CHANNELS) return fail(GSPLAT_ERR_BAD_ARG, "%s: channels out of range (1 .. 512)", name);
     if (n == 0) return GSPLAT_OK;
@@ -421,14 +419,8 @@ int features_impl(const char* name, bool adjoint, int64_t n, int64_t pair_capaci
     const dim3 grid((unsigned)c.nl, (unsigned)((channels + FGROUP - 1) / FGROUP));
     // rows as two 16-byte accesses where every row of a full group is 16-byte aligned; the arrays the kernel moves float by float need no alignment
     const int vec = channels % 4 == 0 && aligned16(in) && (adjoint || aligned16(out));
-    if (adjoint)
-        LAUNCH("raster_features_adjoint_kernel", raster_features_adjoint_kernel, grid, dim3(64), 0, c.st, c.ps.counts, (long long)pair_capacity,
-               c.ps.ranges, (const uint32_t*)bin_state, c.ps.rec, c.ps.order, c.vk.lists_x, c.vk.H, c.vk.W, c.vk.chi_clip, c.vk.alpha_max,
-               c.vk.alpha_cutoff, (uint32_t)(n - 1), in, channels, vec, out);
-    else
-        LAUNCH("raster_features_kernel", raster_features_kernel, grid, dim3(64), 0, c.st, c.ps.counts, (long long)pair_capacity, c.ps.ranges,
-               (const uint32_t*)bin_state, c.ps.rec, c.ps.order, c.vk.lists_x, c.vk.H, c.vk.W, c.vk.chi_clip, c.vk.alpha_max,
-               c.vk.alpha_cutoff, (uint32_t)(n - 1), in, channels, vec, out);
+    LAUNCH(adjoint ? "raster_features_adjoint_kernel" : "raster_features_kernel", adjoint ? raster_features_adjoint_kernel : raster_features_kernel,
+           grid, dim3(64), 0, c.st, WALK_ARGS(c, pair_capacity, bin_state, n), in, channels, vec, out);
     return GSPLAT_OK;
 }
 

@@ -27,7 +27,6 @@ import torch
 
 from . import _abi, ops
 from ._dev import _f32, _p
-from ._workspace import OFFSCREEN_MSG, capacity_key, read_counts
 
 MAX_CHANNELS = _abi.GSPLAT_FEATURES_MAX_CHANNELS
 
@@ -69,75 +68,55 @@ def _need_gpu(who, name, t):
         raise RuntimeError(f"{who}: {name} is on {t.device}: the MI355X rasterizer needs GPU tensors (there is no CPU fallback)")
 
 
-class _Front:
-    """The front end of ops.contribution() for one model: the converted geometry, a zero f_dc of the op's own (SH degree 0 reads no
-    f_rest: its address is f_dc's), one project_state for all poses.  frame(c2w) queues project, waits for the pair count, bins with
-    exact buffers; returns (pairs, bin_state), or None for a pose without a survivor; a pose with survivors but none on screen raises
-    the reference's off-screen Exception."""
+def _front(spec, tensors, n, dev):
+    """(front, held): ops._WaitedFront over the converted geometry (None for n == 0) and the tensors behind its addresses, which the
+    caller keeps until its last frame is queued: the geometry in fp32, a zero f_dc of the op's own (degree 0 reads no f_rest: f_dc again)."""
+    opa = tensors["opacity_raw"]
+    ins = dict(pos=_f32(tensors["pos"], (n, 3), "pos"), opacity_raw=_f32(opa if opa.dim() == 1 else opa.reshape(-1), (n,), "opacity_raw"),
+               scale_raw=_f32(tensors["scale_raw"], (n, 3), "scale_raw"), q_raw=_f32(tensors["q_raw"], (n, 4), "q_raw"))
+    if n == 0:
+        return None, ins
+    f_dc = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+    g = _abi.Gaussians(n, _p(ins["pos"]), _p(ins["opacity_raw"]), None, None, _p(ins["scale_raw"]), _p(ins["q_raw"]), _p(f_dc), _p(f_dc))
+    return ops._WaitedFront(spec, g, n, dev, ops._PROJECT_DEGREE[0] | spec.filter), (ins, f_dc)
 
-    def __init__(self, spec, tensors, n, dev):
-        self.spec, self.n, self.dev = spec, n, dev
-        opa = tensors["opacity_raw"]
-        self.ins = dict(pos=_f32(tensors["pos"], (n, 3), "pos"), opacity_raw=_f32(opa if opa.dim() == 1 else opa.reshape(-1), (n,), "opacity_raw"),
-                        scale_raw=_f32(tensors["scale_raw"], (n, 3), "scale_raw"), q_raw=_f32(tensors["q_raw"], (n, 4), "q_raw"))
-        if n == 0:
-            return
-        self.f_dc = torch.zeros((n, 3), dtype=torch.float32, device=dev)
-        i = self.ins
-        self.g = _abi.Gaussians(n, _p(i["pos"]), _p(i["opacity_raw"]), None, None, _p(i["scale_raw"]), _p(i["q_raw"]), _p(self.f_dc), _p(self.f_dc))
-        self.lib, self.view = _abi.lib(), spec.view
-        _, self.key, self.st = ops._stream_key(dev)
-        self.proj_state = torch.empty(self.lib.gsplat_project_state_bytes(n, C.byref(self.view)), dtype=torch.uint8, device=dev)
-        self.flags = ops._PROJECT_DEGREE[0] | spec.filter
-        self.ckey = capacity_key(dev, spec, n)
 
-    def frame(self, c2w):
-        pinned, _, ready = ops._queue_project(self.g, c2w, self.view, self.proj_state, self.flags, self.dev, self.key, self.st)
-        ready.synchronize()                      # the one host wait of a frame: the pair count sizes the binning buffers
-        counts, scene = read_counts(pinned, self.ckey)
-        if scene == _abi.GSPLAT_SCENE_ALL_OFFSCREEN:
-            raise Exception(OFFSCREEN_MSG)
-        if scene == _abi.GSPLAT_SCENE_ALL_CULLED:
-            return None
-        pairs = int(counts.n_binned)
-        return pairs, ops._queue_bin(self.n, pairs, self.view, self.proj_state, self.dev, self.key, self.st)
-
-    def call(self, name, pairs, bin_state, src, channels, dst):
-        _abi.check(getattr(self.lib, name)(self.n, pairs, C.byref(self.view), _p(self.proj_state), _p(bin_state), _p(src), channels, _p(dst),
-                                           self.st), name)
+def _call(name, front, fr, src, channels, dst, st):
+    """The library's `name` (gsplat_features_forward / _adjoint) on the frame fr = (pairs, bin_state) of `front`, on the stream `st`."""
+    _abi.check(getattr(_abi.lib(), name)(front.n, fr[0], C.byref(front.view), _p(front.proj_state), _p(fr[1]), _p(src), channels, _p(dst), st), name)
 
 
 class _FeatureFn(torch.autograd.Function):
-    """apply(feats, front, c2w): the map [H, W, C].  The node keeps the frame's project_state and bin_state (the front end is not run
-    again) and its backward pass is gsplat_features_adjoint into a zeroed [N, C]."""
+    """apply(feats, spec, front, c2w): the map [H, W, C].  The node keeps the front end with its project_state and the frame's
+    bin_state (neither run again nor changed) and its backward pass is gsplat_features_adjoint into a zeroed
+    [N, C], on the backward pass's own current stream."""
 
     @staticmethod
-    def forward(ctx, feats, front, c2w):
-        spec, dev, ch = front.spec, front.dev, feats.shape[1]
+    def forward(ctx, feats, spec, front, c2w):
+        dev, ch = feats.device, feats.shape[1]
         ctx.frame = None
         ctx.shape = feats.shape
-        fr = front.frame(c2w) if front.n else None
+        fr = front.frame(c2w) if front is not None else None
         if fr is None:                           # no survivor: the zero map, and a zero gradient
             return torch.zeros((spec.H, spec.W, ch), dtype=torch.float32, device=dev)
         out = torch.empty((spec.H, spec.W, ch), dtype=torch.float32, device=dev)
-        front.call("gsplat_features_forward", fr[0], fr[1], feats, ch, out)
-        ctx.frame = (front, fr[0], fr[1], torch.cuda.current_stream(dev))
+        _call("gsplat_features_forward", front, fr, feats, ch, out, front.st)
+        ctx.frame = (front, fr, torch.cuda.current_stream(dev))
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         grad = torch.zeros(ctx.shape, dtype=torch.float32, device=grad_out.device)
         if ctx.frame is not None:
-            front, pairs, bin_state, stream = ctx.frame
+            front, fr, stream = ctx.frame
             g = grad_out.detach()
             if g.dtype != torch.float32 or not g.is_contiguous():
                 g = g.float().contiguous()
-            here = torch.cuda.current_stream(g.device)
-            _, front.key, front.st = ops._stream_key(g.device)       # (the backward pass's own current stream)
+            here, _, st = ops._stream_key(g.device)                  # (the backward pass's own current stream)
             if here != stream:
                 here.wait_stream(stream)
-            front.call("gsplat_features_adjoint", pairs, bin_state, g, ctx.shape[1], grad)
-        return grad, None, None
+            _call("gsplat_features_adjoint", front, fr, g, ctx.shape[1], grad, st)
+        return grad, None, None, None
 
 
 def render(pos, feats, opacity_raw, scale_raw, q_raw, c2w, H, W, fx, fy, cx, cy, near=0.01, far=100.0, pix_guard=32, T=16,
@@ -166,8 +145,8 @@ def render(pos, feats, opacity_raw, scale_raw, q_raw, c2w, H, W, fx, fy, cx, cy,
         raise ValueError(f"{who}: there is no deterministic adjoint (float atomics add in arrival order): not available under set_deterministic(True)")
     _check_table(who, "feats", feats, (n, None), dev, MAX_CHANNELS)
     _need_gpu(who, "feats", feats)
-    front = _Front(spec, geometry, n, dev)
-    return _FeatureFn.apply(feats, front, _f32(c2w, (4, 4), "c2w"))
+    front, held = _front(spec, geometry, n, dev)
+    return _FeatureFn.apply(feats, spec, front, _f32(c2w, (4, 4), "c2w"))
 
 
 @torch.no_grad()
@@ -209,15 +188,15 @@ def lift(pos, opacity_raw, scale_raw, q_raw, c2ws, maps, H, W, fx, fy, cx, cy, n
         _check_table(who, "out[0]", out[0], (n, ch), dev, MAX_CHANNELS - 1)
         _check_table(who, "out[1]", out[1].unsqueeze(-1) if isinstance(out[1], torch.Tensor) and out[1].dim() == 1 else out[1], (n, 1), dev, 1)
     _need_gpu(who, "maps" if isinstance(maps, torch.Tensor) else "maps[0]", maps if isinstance(maps, torch.Tensor) else maps[0])
-    cams = [_f32(torch.as_tensor(c, dtype=torch.float32, device=dev) if not isinstance(c, torch.Tensor) else c, (4, 4), "c2w") for c in c2ws]
-    front = _Front(spec, geometry, n, dev)
+    cams = ops._convert_cameras(c2ws, dev)
+    front, held = _front(spec, geometry, n, dev)
     table = torch.zeros((n, ch + 1), dtype=torch.float32, device=dev)          # (sums | weight): one table, one launch sequence per pose
     for c2w, m in zip(cams, maps):
         fr = front.frame(c2w) if n else None
         if fr is None:
             continue
         g = torch.cat([m, torch.ones((spec.H, spec.W, 1), dtype=torch.float32, device=dev)], dim=-1)
-        front.call("gsplat_features_adjoint", fr[0], fr[1], g, ch + 1, table)
+        _call("gsplat_features_adjoint", front, fr, g, ch + 1, table, front.st)
     if out is None:
         return table[:, :ch].contiguous(), table[:, ch].contiguous()
     out[0].add_(table[:, :ch])

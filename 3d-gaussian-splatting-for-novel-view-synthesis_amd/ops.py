@@ -221,6 +221,36 @@ def _queue_bin(n, pairs, view, proj_state, dev, key, st):
     return bin_state
 
 
+def _convert_cameras(c2ws, dev):
+    """The poses `c2ws` (tensors, or what torch.as_tensor takes) as fp32 [4, 4] on `dev`."""
+    return [_f32(c if isinstance(c, torch.Tensor) else torch.as_tensor(c, dtype=torch.float32, device=dev), (4, 4), "c2w") for c in c2ws]
+
+
+class _WaitedFront:
+    """The waited front end of contribution() and features.render / lift, for one model `g` (n > 0; the caller keeps its tensors): one
+    project_state for all poses, the current stream looked up once.  frame(c2w) queues project, waits for the pair count, bins with
+    exact buffers: (pairs, bin_state), None for a pose without a survivor, the reference's off-screen Exception for survivors none of
+    which is on screen.  `proj_state`, `view`, `st`: for the caller's own library call.  (Not _forward_end's waited branch, which
+    drains the deferred block between reading the counters and raising.)"""
+
+    def __init__(self, spec, g, n, dev, flags):
+        self.g, self.n, self.dev, self.flags, self.view = g, n, dev, flags, spec.view
+        _, self.key, self.st = _stream_key(dev)
+        self.proj_state = torch.empty(_abi.lib().gsplat_project_state_bytes(n, C.byref(self.view)), dtype=torch.uint8, device=dev)
+        self.ckey = capacity_key(dev, spec, n)
+
+    def frame(self, c2w):
+        pinned, _, ready = _queue_project(self.g, c2w, self.view, self.proj_state, self.flags, self.dev, self.key, self.st)
+        ready.synchronize()                      # the one host wait of a frame: the pair count sizes the binning buffers
+        counts, scene = read_counts(pinned, self.ckey)
+        if scene == _abi.GSPLAT_SCENE_ALL_OFFSCREEN:
+            raise Exception(OFFSCREEN_MSG)
+        if scene == _abi.GSPLAT_SCENE_ALL_CULLED:
+            return None
+        pairs = int(counts.n_binned)
+        return pairs, _queue_bin(self.n, pairs, self.view, self.proj_state, self.dev, self.key, self.st)
+
+
 def _empty_result(spec, dev):
     """(image, depth, alpha) of a frame without a survivor: the zero image -- the clamped background where one is given -- and zero
     maps (None without aux=True)."""
@@ -592,29 +622,19 @@ def contribution(pos, f_dc, f_rest, opacity_raw, scale_raw, q_raw, c2ws, H, W, f
             raise ValueError(f"contribution: stats must be a ContributionStats of {n} rows (contiguous int32 {(n, 4)}) on {dev}, not "
                              f"{type(stats).__name__}" + (f" {data.dtype} {tuple(data.shape)} on {data.device}" if isinstance(data, torch.Tensor) else ""))
     ins, g = _convert_inputs(spec.names, dict(pos=pos, opacity_raw=opacity_raw, scale_raw=scale_raw, q_raw=q_raw, f_dc=f_dc, f_rest=f_rest), n)
-    cams = [_f32(torch.as_tensor(c, dtype=torch.float32, device=dev) if not isinstance(c, torch.Tensor) else c, (4, 4), "c2w") for c in c2ws]
+    cams = _convert_cameras(c2ws, dev)
     if stats is None:
         stats = ContributionStats(n, dev)
     if n == 0:                                  # nothing survives by construction
         stats.frames += len(cams)
         return stats
-    lib, view = _abi.lib(), spec.view
-    _, key, st = _stream_key(dev)
-    proj_state = torch.empty(lib.gsplat_project_state_bytes(n, C.byref(view)), dtype=torch.uint8, device=dev)
-    flags = _PROJECT_DEGREE[spec.sh_degree] | spec.filter
-    ckey = capacity_key(dev, spec, n)
+    front = _WaitedFront(spec, g, n, dev, _PROJECT_DEGREE[spec.sh_degree] | spec.filter)
     for c2w in cams:
-        pinned, _, ready = _queue_project(g, c2w, view, proj_state, flags, dev, key, st)
-        ready.synchronize()                      # the one host wait of a frame: the pair count sizes the binning buffers
-        counts, scene = read_counts(pinned, ckey)
-        if scene == _abi.GSPLAT_SCENE_ALL_OFFSCREEN:
-            raise Exception(OFFSCREEN_MSG)
+        fr = front.frame(c2w)                    # (an off-screen pose raises: not counted)
         stats.frames += 1
-        if scene == _abi.GSPLAT_SCENE_ALL_CULLED:
-            continue
-        pairs = int(counts.n_binned)
-        bin_state = _queue_bin(n, pairs, view, proj_state, dev, key, st)
-        _abi.check(lib.gsplat_contribution(n, pairs, C.byref(view), _p(proj_state), _p(bin_state), _p(stats.data), st), "gsplat_contribution")
+        if fr is not None:
+            _abi.check(_abi.lib().gsplat_contribution(n, fr[0], C.byref(front.view), _p(front.proj_state), _p(fr[1]), _p(stats.data), front.st),
+                       "gsplat_contribution")
     return stats
 
 

@@ -420,3 +420,67 @@ def test_a_culled_pose_gives_zeros_and_an_offscreen_pose_raises(gs):
     with gs.deferred_checks() as chk:
         inside = op.render(gs, feats.detach())
     assert chk.verify() == [] and torch.equal(inside, op.render(gs, feats.detach()))
+
+
+def test_features_share_the_waited_front_end_and_keep_it_unchanged(gs):
+    """The front end features.render / lift share with ops.contribution, seen from outside, on the golden scene case_g1
+    at its own image size (tests/test_gpu_contrib.py has the sibling for contribution): the pair capacity a waited pose leaves under
+    the features' own key; render_stats() and binned_pairs() untouched; "project" and "bin" counted once per pose that bins; a
+    backward pass on another stream, which may not change the front end the node saved."""
+    op, ops = _op(), gs.ops
+    s, g1 = op.s, scenes.case_g1()
+    assert all(np.array_equal(g1[k], s[k]) for k in NAMES + ("c2w", "H", "W")) and not op.kw
+    c2w, moved = (torch.tensor(p, device=DEV) for p in op.poses)
+    behind = c2w.clone()
+    behind[:3, :3] = c2w[:3, :3] @ torch.diag(torch.tensor([-1.0, 1.0, -1.0], device=DEV))      # flipped: every z is below near
+    dev = op.t["pos"].device
+    key = ops.capacity_key(dev, ops._frame_spec(True, *op.cam, 0.01, 100.0, 32, 16, 1e-6, 6.25, 0.99, 1 / 128., sh_degree=0), op.n)
+    feats = torch.tensor(op.feats, device=DEV)
+    maps = [torch.tensor(np.ascontiguousarray(op.G[..., :op.ch]), device=DEV)] * 3
+    saved = dict(ops._ws.capacity)
+    try:
+        ops._ws.capacity.pop(key, None)                                   # (the key holds no SH degree: the render's entry too)
+        waited = ops.forward_modes["waited"]
+        with torch.no_grad():                                             # the waited render of the same pose: what the counters say
+            gs.render_gaussians(*[op.t[k] for k in NAMES], c2w, *op.cam)
+        assert ops.forward_modes["waited"] == waited + 1
+        stats = ops.render_stats()
+        ops._ws.capacity.pop(key)
+        first = op.render(gs, feats)
+        binned = ops.binned_pairs()
+        assert binned > 0 and stats[0] > 0 and ops._ws.pair_capacity(key) == int(binned * 1.25) + 4096
+        timer = ops.StageTimer()
+        ops.set_stage_timer(timer)
+        try:
+            sums, weight = gs.features.lift(*op.geo, [moved, behind, c2w], maps, *op.cam)
+            torch.cuda.synchronize()
+        finally:
+            ops.set_stage_timer(None)
+        assert {k: v[0] for k, v in timer.totals_ms().items()} == {"project": 3, "bin": 2}      # (the culled pose projects and bins nothing)
+        assert ops.render_stats() == stats and ops.binned_pairs() == binned and sums.any() and weight.any()
+    finally:
+        ops._ws.capacity.clear()
+        ops._ws.capacity.update(saved)
+    # one channel, upstream ones: the gradient is the weight column of the adjoint's reference (channel C of op.G is all ones)
+    adj, K = op.frames[0]["adj"], op.frames[0]["K_rows"]
+    ref = fo.Ref(adj.value[:, op.ch:], adj.scale[:, op.ch:], adj.allow[:, op.ch:], adj.in_list)
+    table = [torch.tensor(op.feats[:, :1].copy(), device=DEV, requires_grad=True) for _ in range(2)]
+    op.render(gs, table[0]).sum().backward()
+    side = torch.cuda.Stream(DEV)
+    side.wait_stream(torch.cuda.current_stream(DEV))
+    with torch.cuda.stream(side):
+        out = op.render(gs, table[1])
+        out.sum().backward(retain_graph=True)
+    torch.cuda.current_stream(DEV).wait_stream(side)
+    torch.cuda.synchronize()
+    r0 = fo.check(table[0].grad.cpu().numpy(), ref, K, "feats.grad, default stream")
+    r1 = fo.check(table[1].grad.cpu().numpy(), ref, K, "feats.grad, render and backward on a side stream")
+    bound = K * fo.EPS * ref.scale + ref.allow
+    assert (np.abs(table[1].grad.cpu().numpy().astype(np.float64) - table[0].grad.cpu().numpy()) <= 2.0 * bound).all()
+    print(f"backward on a side stream: device ratio {r1:.2f} (default stream {r0:.2f}), float32 mode {K / 3:.2f}")
+    # a second backward pass through the same node, now on the default stream: the saved front end serves it as it is
+    out.sum().backward()
+    torch.cuda.synchronize()
+    fo.check(table[1].grad.cpu().numpy(), ref, K, "feats.grad after a second backward pass on the default stream", calls=2)
+    again = op.render(gs, table[1].detach())
+    assert torch.equal(again, out.detach()) and torch.equal(op.render(gs, feats), first)

@@ -3,7 +3,9 @@
   * raster_features_kernel (gsplat_features_forward) and raster_features_adjoint_kernel (gsplat_features_adjoint, into a table zeroed
     outside the timed interval) at C = 3, 8, 32, 128, beside
   * raster_forward_kernel<false> (gsplat_rasterize_forward without accum) of the SAME frame -- one project_state / bin_state, through
-    ops internals -- in the same run, on the same box.
+    ops internals -- in the same run, on the same box;
+  * the whole features.render under torch.no_grad() and the whole features.lift per pose, at C = 8 (projection, the host's wait for
+    the pair count, binning, the kernel), as tools/contribution_time.py times ops.contribution.
 Prints one JSON line (microseconds, medians) and, with a third argument, writes it to that file.
     python tools/features_time.py [config] [iterations] [out.json]
 A kernel trace of the same run (no counters in it): rocprofv3 --kernel-trace --stats -- python tools/features_time.py"""
@@ -86,6 +88,16 @@ with torch.no_grad():
                          "forward_over_raster": round(statistics.median(ts_f) / raster, 2), "adjoint_over_raster": round(statistics.median(ts_a) / raster, 2),
                          "adjoint_rows_written": int((table != 0).any(1).sum())}
         del feats, G, out, table
+    # the whole call per pose (device events round the call; C = 8)
+    geometry = [pdev[k] for k in ("pos", "opacity_raw", "scale_raw", "q_raw")]
+    feats8 = torch.randn((n, 8), device=dev, generator=gen)
+    map8 = torch.randn((cam["H"], cam["W"], 8), device=dev, generator=gen)
+    render = lambda: gs.features.render(geometry[0], feats8, *geometry[1:], c2w, *camargs)
+    lift = lambda: gs.features.lift(*geometry, [c2w], [map8], *camargs)
+    render()
+    lift()
+    res["render_no_grad_per_pose_us"] = round(statistics.median(timed(render) for _ in range(iters)), 1)
+    res["lift_per_pose_us"] = round(statistics.median(timed(lift) for _ in range(iters)), 1)
 print(json.dumps(res))
 if len(sys.argv) > 3:
     os.makedirs(os.path.dirname(os.path.abspath(sys.argv[3])), exist_ok=True)
